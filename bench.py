@@ -3,6 +3,7 @@
 kernel and the CPU baseline measured in the same run.
 
     python bench.py --gpus 1 --steps 128 --warmup 8          (default: Llama-3-8B Q4_K_M, 128-token prompt)
+    python bench.py ... --dump-outputs DIR                    (also writes the timed decode's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N   (layer pipeline)
     python bench.py --gpus N                                  (the same: the GPU-free parent starts that launcher itself)
 
@@ -122,7 +123,28 @@ def parse_args():
     ap.add_argument("--stages", type=int, default=0, help="with --inlib: stage count when it differs from --gpus (several stages on one GPU)")
     ap.add_argument("--fake-stage", action="store_true",
                     help="CPU rehearsal of the N>1 launcher and hop protocol: gloo + pipeline.FakeStage, no GPU, no engine (not a measurement)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last repetition as DIR/<name>.npy "
+                         "(single GPU and --batch only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """`--dump-outputs`: token ids as float64 (exact), everything else as float32, so that two builds can be compared
+    output for output on identical inputs (the synthetic weights and the prompts are fixed by the arguments)."""
+    out = {name: np.asarray(a, dtype=np.float64 if np.asarray(a).dtype.kind in "iu" else np.float32) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES}); use fewer --steps")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def prompt_tokens(n: int, vocab: int):
@@ -222,8 +244,16 @@ def run_single(args, pkg):
     tok_s = K / elapsed
     mean_kv = (kv0 + 1 + kv1) / 2.0
     step_bytes = model.step_alg_bytes(int(round(mean_kv)))
-    # ---- PCIe-inclusive variant (GpuInference::forward returns all logits to the host)
     orc_argmax = lambda v: int(len(v) - 1 - np.argmax(v[::-1]))      # last maximal index (main.rs:1815-1821)
+    if args.dump_outputs:
+        # the timed path returns the K tokens; the logits of its last step are recomputed from the same cache state through
+        # lgh_forward, which runs the same kernels minus the on-device arg-max (the cache ends where it was)
+        eng.kv_truncate(kv1 - 1)
+        last_logits = eng.forward(int(toks[-2]) if K > 1 else tok)
+        if orc_argmax(last_logits) != int(toks[-1]):
+            raise SystemExit("bench.py: the recomputed last step does not give the token the timed path decoded")
+        dump_outputs(args.dump_outputs, {"tokens": toks, "last_logits": last_logits})
+    # ---- PCIe-inclusive variant (GpuInference::forward returns all logits to the host)
     n_pcie = min(K, 32)
     # ---- prompt processing (untimed for the metric): the batched f16-GEMM path against n exact prefill_tokens
     prefill = None
@@ -366,6 +396,8 @@ def run_batch(args, pkg):
         rep_s.append(time.perf_counter() - t0)
         toks = [int(t) for t in out[-1]]
     elapsed = sum(rep_s) / len(rep_s)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tokens": out})           # [K, B]: the last repetition's tokens per step and sequence
     kv1 = eng.batch_position(0)
     mean_kv = (kv0 + 1 + kv1) / 2.0
     one = model.step_alg_bytes(int(round(mean_kv)))        # a single sequence's step: weights + its KV rows + vectors
@@ -612,6 +644,9 @@ def self_launch(args) -> int:
 
 def main():
     args = parse_args()
+    pipeline = args.inlib or int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("LGH_BENCH_FORCE_PIPELINE")
+    if args.dump_outputs and (args.gpus > 1 or (pipeline and not args.batch)):
+        raise SystemExit("bench.py: --dump-outputs is implemented for the single-GPU decode and --batch only")
     if args.gpus > 1 and "RANK" not in os.environ and not os.environ.get("LGH_BENCH_FORCE_PIPELINE") and not args.inlib:
         sys.exit(self_launch(args))
     # ONE JSON line on stdout, nothing else: native libraries write banners to fd 1 (RCCL prints its version block there
