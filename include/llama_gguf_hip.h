@@ -287,6 +287,44 @@ int lgh_forward_multi(lgh_ctx* ctx, const uint32_t* slots, const uint32_t* token
  * synchronisation at the end (the bench's timed region for --batch). */
 int lgh_decode_greedy_multi(lgh_ctx* ctx, const uint32_t* slots, const uint32_t* first_tokens, uint32_t n_seq, size_t n_steps, uint32_t* tokens_out);
 
+/* ---- sampling on the device: Sampler::sample (src/sampling/mod.rs:188-304, the non-mirostat path) inside the per-token
+ * graph, so that the reference's default generation settings (EngineConfig::default, src/engine.rs:117-130) stay on the
+ * graph-replayed decode loop.  Steps as the reference does them, all in f32: repetition penalty once per occurrence in the
+ * window (x > 0: x /= p, else x *= p), frequency then presence penalty for every token this sampler emitted, x *= 1.0f / T,
+ * softmax, greedy (T == 0 or top_k == 1: the LAST index of the maximal probability; no draw, not counted), stable sort by
+ * probability, top-k, top-p (a cutoff at position 0 truncates nothing), renormalize, draw (first r < cumulative sum, else the
+ * last kept token), count.  The random draws are INPUTS: uniforms[i] is what the reference's `self.rng.gen::<f32>()` returns at
+ * step i, so a host that draws them from its own StdRng gets the reference's tokens.  Single-stage contexts
+ * only; bad configs (non-finite or negative temperature, top_p outside (0, 1], repeat_penalty <= 0, non-finite penalties)
+ * and sampling without a prior set_sampler answer LGH_INVALID_ARGUMENT. ---- */
+typedef struct lgh_sampler_config {   /* SamplerConfig (sampling/mod.rs:37-62) minus seed / min_p / typical_p / mirostat */
+  float temperature;
+  uint32_t top_k;                     /* 0: no top-k truncation */
+  float top_p;
+  float repeat_penalty;
+  uint32_t repeat_window;             /* 0: every token so far */
+  float frequency_penalty;
+  float presence_penalty;
+  int32_t eos_token;                  /* -1: none.  Within one call, steps after the step that sampled it do not update the counts
+                                         (the reference stops there; the host truncates the KV cache with lgh_kv_truncate) */
+} lgh_sampler_config;
+
+/* Sampler::new (mod.rs:150-165): the config and zeroed counts.  The counts persist across decode calls until the next call. */
+int lgh_set_sampler(lgh_ctx* ctx, const lgh_sampler_config* config);
+/* Engine::generate's loop (src/engine.rs:424-431) with the token fed back on the device: n_steps tokens, the first from the
+ * logits of first_token at the current position.  history: the tokens in the context before first_token (at least
+ * min(position, repeat_window) of them, all when the window is 0); the device appends first_token and every sampled token.
+ * uniforms[n_steps] (may be NULL under a greedy config).  One host synchronisation at the end. */
+int lgh_decode_sample(lgh_ctx* ctx, uint32_t first_token, const uint32_t* history, size_t n_history, size_t n_steps,
+                      const float* uniforms, uint32_t* tokens_out);
+/* BatchedEngine's per-sequence sampler (src/engine_batched.rs:358, 397): lgh_set_sampler for one slot */
+int lgh_batch_set_sampler(lgh_ctx* ctx, uint32_t slot, const lgh_sampler_config* config);
+/* lgh_decode_greedy_multi with each sequence sampled by its slot's sampler.  histories: the n_seq histories back to back,
+ * history_lens[n_seq] long; uniforms[n_steps][n_seq]; tokens_out[n_steps][n_seq]. */
+int lgh_decode_sample_multi(lgh_ctx* ctx, const uint32_t* slots, const uint32_t* first_tokens, uint32_t n_seq,
+                            const uint32_t* histories, const size_t* history_lens, size_t n_steps, const float* uniforms,
+                            uint32_t* tokens_out);
+
 const char* lgh_last_error(const lgh_ctx* ctx);
 int lgh_get_stats(lgh_ctx* ctx, lgh_stats* out);
 /* on: run eagerly with hipEvent pairs around every launch and accumulate lgh_stats.k_* */
@@ -390,6 +428,11 @@ int lgh_op_scale(int device, const float* a, float scalar, float* out, size_t n)
  * dequantizers (src/model/kv_quantized.rs:385-565) as the attention launch applies them.  kv_cache_type LGH_KV_INT8 /
  * LGH_KV_FP8_E4M3 / LGH_KV_FP8_E5M2; bytes_out[n]; *scale_out = the int8 row scale (1 for the FP8 formats; may be NULL). */
 int lgh_op_kv_roundtrip(int device, uint32_t kv_cache_type, const float* row, size_t n, uint8_t* bytes_out, float* scale_out, float* back_out);
+/* One Sampler::sample call (sampling/mod.rs:188-304) through the device kernels of lgh_decode_sample: logits[vocab]; recent =
+ * the recent_tokens argument (the window is taken from its end); counts[vocab] = the sampler's token_counts (NULL: zero);
+ * `uniform` = the draw (ignored under a greedy config). */
+int lgh_op_sample(int device, const float* logits, size_t vocab, const lgh_sampler_config* config, const uint32_t* recent,
+                  size_t n_recent, const uint32_t* counts, float uniform, uint32_t* token_out);
 int lgh_op_silu(int device, const float* x, float* out, size_t n);
 int lgh_op_gelu(int device, const float* x, float* out, size_t n);
 int lgh_op_softmax(int device, const float* x, float* out, size_t rows, size_t last_dim);

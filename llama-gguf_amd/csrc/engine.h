@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.h"
+#include "sample.h"
 
 namespace lgh {
 
@@ -25,7 +26,7 @@ struct LayerW {
   bool moe() const { return router != nullptr; }
 };
 
-enum TokenMode { MODE_PREFILL = 0, MODE_FORWARD = 1, MODE_GREEDY = 2, MODE_COUNT = 3 };
+enum TokenMode { MODE_PREFILL = 0, MODE_FORWARD = 1, MODE_GREEDY = 2, MODE_SAMPLE = 3, MODE_COUNT = 4 };   // SAMPLE: GREEDY with the sampler (sample.hip) for the arg-max
 
 // The XQ image (xq.h) of an f32 activation buffer, for int8-MFMA consumers.  `fresh` = the image matches the buffer's
 // current contents; `tag` = the RMSNorm weights it was multiplied with (nullptr: none).
@@ -74,7 +75,10 @@ struct BatchScratch {
   float *moe_act = nullptr, *moe_tmp = nullptr;
   int *moe_cnt = nullptr, *moe_idx = nullptr;
   std::vector<size_t> pos;                            // per slot: tokens in its cache
-  hipGraphExec_t graph[kMaxBatch + 1][2] = {};        // [n_seq][0 logits only, 1 + arg-max fed back]
+  hipGraphExec_t graph[kMaxBatch + 1][3] = {};        // [n_seq][0 logits only, 1 + arg-max fed back, 2 + sampled token fed back]
+  SampBufs samp;                                      // one sampler per slot (lgh_batch_set_sampler)
+  std::vector<lgh_sampler_config> samp_cfg;
+  std::vector<uint8_t> samp_set;
 };
 
 }  // namespace lgh
@@ -121,6 +125,9 @@ struct lgh_ctx {
   float* tq_qjl = nullptr;                     // TurboQuantProd: [owned layer][kv head][head_dim][head_dim] QJL projection matrices (device)
   std::vector<float> tq_qjl_host;
   float* kv_shift_tmp = nullptr;               // scratch of lgh_kv_shift_left (one cache tensor), allocated at first use
+  lgh::SampBufs samp;                          // single-stage contexts: the sampler of lgh_set_sampler / lgh_decode_sample
+  lgh_sampler_config samp_cfg{};
+  bool samp_set = false;
 };
 
 // ---- helpers shared by engine.hip and ops_api.hip ----
@@ -172,6 +179,16 @@ void xq_stale(lgh_ctx* c, const float* f32);
 int linear_any(lgh_ctx* c, int cls, const lgh::DevWeight& W, const float* x, float* out, const float* norm_w,
                const float* resid, const float* bias, int xq_next = 0, const float* xq_next_nw = nullptr);
 int drain_prof(lgh_ctx* c);
+// sampler plumbing (sample.hip)
+int samp_alloc(lgh_ctx* c, lgh::SampBufs& B, uint32_t n_slots, uint32_t n_rows);
+int samp_check(lgh_ctx* c, const lgh_sampler_config* cfg);
+int samp_reset(lgh_ctx* c, lgh::SampBufs& B, uint32_t slot);   // zero the slot's counts
+// before the first step of a decode call: the slot's config, window, leaving tokens and draws (synchronises)
+int samp_begin(lgh_ctx* c, lgh::SampBufs& B, uint32_t slot, const lgh_sampler_config& cfg, const uint32_t* hist, size_t n_hist,
+               uint32_t first, size_t n_steps, const float* uni, size_t uni_stride);
+int samp_warm(lgh_ctx* c, lgh::SampBufs& B, const float* logits, uint32_t n_seq);   // eager launch of the sampling kernels (before any capture)
+int samp_one(lgh_ctx* c, lgh::SampBufs& B, const lgh_sampler_config& cfg, const uint32_t* recent, size_t n_recent, const uint32_t* counts,
+             float uniform, const float* d_logits, uint32_t* token_out);   // lgh_op_sample
 
 // ------------------------------------------------------------------------------------------------
 // launch recording (profiling mode: hipEvent pair per launch, on the launch stream)

@@ -679,6 +679,11 @@ static int enqueue_token(lgh_ctx* c, int mode) {
              return argmax_launch(c->logits, d.vocab_size, c->amax_v, c->amax_i, c->state, c->tok_log, c->stream);
            })))
         return rc;
+    } else if (mode == MODE_SAMPLE) {   // Sampler::sample in place of the arg-max (sample.hip); the token lands where the arg-max's does
+      if ((rc = run_k(c, LGH_K_ARGMAX, LGH_SYM_OTHER, (uint64_t)d.vocab_size * 4, [&] {
+             return sample_launch(c->samp, c->logits, d.vocab_size, 1, nullptr, c->state, c->tok_log, nullptr, c->stream);
+           })))
+        return rc;
     }
   }
   // in-graph hops to a stage on the same device (lgh_stage_set_forward_targets)
@@ -711,6 +716,7 @@ static int warm_kernels(lgh_ctx* c) {
   c->attn_direct = keep_direct;
   for (auto& q : c->xqs) q.fresh = false;
   if (rc) return rc;
+  if (c->samp.ctl && (rc = samp_warm(c, c->samp, c->logits, 1))) return rc;   // the sampling kernels of MODE_SAMPLE
   HIP_TRY(c, LGH_OPERATION_FAILED, hipMemsetAsync(c->state, 0, ST_WORDS * 4, c->stream));
   HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
   return LGH_OK;
@@ -727,7 +733,7 @@ static int ensure_graph(lgh_ctx* c, int mode) {
   if (e != hipSuccess) return fail(c, LGH_OPERATION_FAILED, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
   size_t n_nodes = 0;
   (void)hipGraphGetNodes(g, nullptr, &n_nodes);
-  if (mode == MODE_GREEDY || c->graph_nodes == 0) c->graph_nodes = n_nodes;
+  if (mode == MODE_GREEDY || (c->graph_nodes == 0 && mode != MODE_SAMPLE)) c->graph_nodes = n_nodes;
   e = hipGraphInstantiate(&c->graph[mode][var], g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
   if (e != hipSuccess) return fail(c, LGH_OPERATION_FAILED, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
@@ -1299,6 +1305,7 @@ int lgh_finalize(lgh_ctx* c) {
       HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpy(c->tq_qjl, c->tq_qjl_host.data(), nm * 4, hipMemcpyHostToDevice));
     }
   }
+  if (c->first && c->last && (rc = samp_alloc(c, c->samp, 1, 1))) return rc;   // lgh_decode_sample's sampler
   // XQ images of the vectors that feed quantized mat-vecs (allocated here, never during a graph capture)
   if (!xq_get(c, c->hidden, d.hidden_size) || !xq_get(c, c->attn_out, d.num_heads * d.head_dim) || !xq_get(c, c->act, (uint32_t)ffn) ||
       !xq_get(c, c->act2, (uint32_t)ffn))
@@ -1537,6 +1544,40 @@ int lgh_decode_greedy(lgh_ctx* c, uint32_t first_token, size_t n_steps, uint32_t
   return LGH_OK;
 }
 
+int lgh_set_sampler(lgh_ctx* c, const lgh_sampler_config* cfg) {
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (!c->samp.ctl) return fail(c, LGH_INVALID_ARGUMENT, "sampling needs a single-stage context");
+  if ((rc = samp_check(c, cfg))) return rc;
+  if ((rc = samp_reset(c, c->samp, 0))) return rc;
+  c->samp_cfg = *cfg;
+  c->samp_set = true;
+  return LGH_OK;
+}
+
+int lgh_decode_sample(lgh_ctx* c, uint32_t first_token, const uint32_t* history, size_t n_history, size_t n_steps, const float* uniforms,
+                      uint32_t* tokens_out) {
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (!c->samp.ctl) return fail(c, LGH_INVALID_ARGUMENT, "sampling needs a single-stage context");
+  if (!c->samp_set) return fail(c, LGH_INVALID_ARGUMENT, "lgh_set_sampler has not been called");
+  if (n_steps && !tokens_out) return fail(c, LGH_INVALID_ARGUMENT, "tokens_out is NULL");
+  if (n_history && !history) return fail(c, LGH_INVALID_ARGUMENT, "history is NULL");
+  const bool greedy = c->samp_cfg.temperature == 0.0f || c->samp_cfg.top_k == 1;
+  if (n_steps && !uniforms && !greedy) return fail(c, LGH_INVALID_ARGUMENT, "uniforms is NULL");
+  if (c->pos + n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "decode would exceed max_seq_len");
+  if (n_steps == 0) return LGH_OK;
+  if ((rc = set_token(c, first_token))) return rc;
+  if ((rc = samp_begin(c, c->samp, 0, c->samp_cfg, history, n_history, first_token, n_steps, uniforms, 1))) return rc;
+  // samp_merge writes each token into state[TOKEN] (the feedback) and into tok_log[position], as argmax_stage2 does
+  const size_t pos0 = c->pos;
+  for (size_t i = 0; i < n_steps; i++)
+    if ((rc = step(c, MODE_SAMPLE))) return rc;
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(tokens_out, c->tok_log + pos0, n_steps * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  return LGH_OK;
+}
+
 const char* lgh_last_error(const lgh_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 int lgh_get_stats(lgh_ctx* c, lgh_stats* out) {
@@ -1665,7 +1706,7 @@ int lgh_stage_io_buffers(lgh_ctx* c, void** token_in, void** argmax_out) {
 int lgh_stage_step(lgh_ctx* c, int mode) {
   int rc = check_ready(c);
   if (rc) return rc;
-  if (mode < 0 || mode >= MODE_COUNT) return fail(c, LGH_INVALID_ARGUMENT, "mode must be 0 (layers only), 1 (logits) or 2 (arg-max)");
+  if (mode < 0 || mode > MODE_GREEDY) return fail(c, LGH_INVALID_ARGUMENT, "mode must be 0 (layers only), 1 (logits) or 2 (arg-max)");
   if (!c->last) mode = MODE_PREFILL;
   return step(c, mode);
 }

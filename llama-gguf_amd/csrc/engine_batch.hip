@@ -153,7 +153,7 @@ bool batch_weights_ok(const lgh_ctx* c, std::string& why) {
 
 // everything one step of n_seq sequences needs, in stream order (eager or under capture); tokens / positions / slots are read
 // from the device words
-int enqueue_multi(lgh_ctx* c, uint32_t n_seq, bool greedy) {
+int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits only, 1 + arg-max, 2 + sampled token
   BatchScratch& Bs = c->batch;
   const lgh_model_desc& d = c->d;
   const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim;
@@ -327,10 +327,16 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, bool greedy) {
     const uint32_t os[1] = {d.vocab_size}, rs[1] = {0}, xk[1] = {0};
     if ((rc = launch_mvb(c, LGH_K_OUTPUT, &sp, 1, c->output_norm, H, n_seq, os, rs, xk))) return rc;
   }
-  if (greedy) {
+  if (mode == 1) {
     // arg-max per sequence (last maximal index), fed back as the next step's token; the positions move on
     if ((rc = run_k(c, LGH_K_ARGMAX, LGH_SYM_ARGMAX, (uint64_t)n_seq * d.vocab_size * 4, [&] {
            return argmax_multi_launch(Bs.logits, d.vocab_size, n_seq, Bs.amax_v, Bs.amax_i, Bs.d_tokens, c->stream);
+         })))
+      return rc;
+  } else if (mode == 2) {
+    // each sequence sampled by its slot's sampler (sample.hip), fed back the same way
+    if ((rc = run_k(c, LGH_K_ARGMAX, LGH_SYM_OTHER, (uint64_t)n_seq * d.vocab_size * 4, [&] {
+           return sample_launch(Bs.samp, Bs.logits, d.vocab_size, n_seq, Bs.d_slot, nullptr, nullptr, Bs.d_tokens, c->stream);
          })))
       return rc;
   }
@@ -368,18 +374,18 @@ int stage_control(lgh_ctx* c, const uint32_t* slots, const uint32_t* tokens, uin
   return LGH_OK;
 }
 
-int run_multi(lgh_ctx* c, uint32_t n_seq, bool greedy) {
+int run_multi(lgh_ctx* c, uint32_t n_seq, int mode) {
   BatchScratch& Bs = c->batch;
   if (c->profiling || (c->d.flags & LGH_FLAG_NO_GRAPH)) {
-    int rc = enqueue_multi(c, n_seq, greedy);
+    int rc = enqueue_multi(c, n_seq, mode);
     if (rc) return rc;
     return c->profiling ? drain_prof(c) : LGH_OK;
   }
-  hipGraphExec_t& ge = Bs.graph[n_seq][greedy ? 1 : 0];
+  hipGraphExec_t& ge = Bs.graph[n_seq][mode];
   if (!ge) {
     hipGraph_t g = nullptr;
     HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_multi(c, n_seq, greedy);
+    int rc = enqueue_multi(c, n_seq, mode);
     hipError_t e = hipStreamEndCapture(c->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
     if (e != hipSuccess) return fail(c, LGH_OPERATION_FAILED, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -500,21 +506,28 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
   register_views(c, Bs.act, xq_f, ssq_f, ffn, max_batch);
   register_views(c, Bs.act2, xq_f2, ssq_f2, ffn, max_batch);
   Bs.pos.assign(max_batch, 0);
+  // the slots' samplers (allocated before the context counts as ready: the sampler entry points index these per slot)
+  if ((rc = samp_alloc(c, Bs.samp, max_batch, max_batch))) return rc;
+  Bs.samp_cfg.assign(max_batch, lgh_sampler_config{});
+  Bs.samp_set.assign(max_batch, 0);
   Bs.ready = true;
   // one step through every kernel of the path, eagerly, before any of them is first launched inside a capture (engine.hip:
   // warm_kernels explains the ROCm trap); it writes row 0 of slot 0's caches, which that slot's first real token overwrites
   {
     const uint32_t slot0 = 0, tok0 = 0;
     if ((rc = stage_control(c, &slot0, &tok0, 1))) return rc;
-    if ((rc = enqueue_multi(c, 1, true))) return rc;
+    if ((rc = enqueue_multi(c, 1, 1))) return rc;
     HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
     if (max_batch >= 2) {   // ... and the kernels only a step of several sequences launches (rows 0 of slots 0 and 1)
       const uint32_t slots2[2] = {0, 1}, toks2[2] = {0, 0};
       if ((rc = stage_control(c, slots2, toks2, 2))) return rc;
-      if ((rc = enqueue_multi(c, 2, true))) return rc;
+      if ((rc = enqueue_multi(c, 2, 1))) return rc;
       HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
     }
   }
+  // the sampling kernels launched eagerly for every n_seq a step can have
+  for (uint32_t n = 1; n <= max_batch; n++)
+    if ((rc = samp_warm(c, Bs.samp, Bs.logits, n))) return rc;
   return LGH_OK;
 }
 
@@ -536,7 +549,7 @@ int lgh_forward_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* tokens,
   if (rc) return rc;
   if (!slots || !tokens) return fail(c, LGH_INVALID_ARGUMENT, "slots / tokens is NULL");
   if ((rc = stage_control(c, slots, tokens, n_seq))) return rc;
-  if ((rc = run_multi(c, n_seq, next_tokens != nullptr))) return rc;
+  if ((rc = run_multi(c, n_seq, next_tokens != nullptr ? 1 : 0))) return rc;
   BatchScratch& Bs = c->batch;
   if (logits_out)
     HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(logits_out, Bs.logits, (size_t)n_seq * c->d.vocab_size * 4, hipMemcpyDeviceToHost, c->stream));
@@ -558,12 +571,70 @@ int lgh_decode_greedy_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* f
   if (n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "too many steps");
   if ((rc = stage_control(c, slots, first_tokens, n_seq))) return rc;
   for (size_t st = 0; st < n_steps; st++) {
-    if ((rc = run_multi(c, n_seq, true))) return rc;
+    if ((rc = run_multi(c, n_seq, 1))) return rc;
     if (tokens_out)
       HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_log + st * kMaxBatch, Bs.d_tokens, (size_t)n_seq * 4, hipMemcpyDeviceToDevice, c->stream));
   }
   HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
   if (tokens_out && n_steps) {
+    std::vector<int> log(n_steps * kMaxBatch);
+    HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpy(log.data(), Bs.d_log, log.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t st = 0; st < n_steps; st++)
+      for (uint32_t i = 0; i < n_seq; i++) tokens_out[st * n_seq + i] = (uint32_t)log[st * kMaxBatch + i];
+  }
+  for (uint32_t i = 0; i < n_seq; i++) Bs.pos[slots[i]] += n_steps;
+  c->stats.tokens_processed += n_steps * n_seq;
+  return LGH_OK;
+}
+
+int lgh_batch_set_sampler(lgh_ctx* c, uint32_t slot, const lgh_sampler_config* cfg) {
+  int rc = check_batch(c);
+  if (rc) return rc;
+  BatchScratch& Bs = c->batch;
+  if (!Bs.ready || slot >= Bs.max_batch || slot >= Bs.samp_set.size()) return fail(c, LGH_INVALID_ARGUMENT, "no such slot");
+  if ((rc = samp_check(c, cfg))) return rc;
+  if ((rc = samp_reset(c, Bs.samp, slot))) return rc;
+  Bs.samp_cfg[slot] = *cfg;
+  Bs.samp_set[slot] = 1;
+  return LGH_OK;
+}
+
+int lgh_decode_sample_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* first_tokens, uint32_t n_seq, const uint32_t* histories,
+                            const size_t* history_lens, size_t n_steps, const float* uniforms, uint32_t* tokens_out) {
+  int rc = check_batch(c);
+  if (rc) return rc;
+  if (!slots || !first_tokens) return fail(c, LGH_INVALID_ARGUMENT, "slots / first_tokens is NULL");
+  BatchScratch& Bs = c->batch;
+  if (!Bs.ready) return fail(c, LGH_INVALID_ARGUMENT, "lgh_batch_create has not been called");
+  if (n_seq == 0 || n_seq > Bs.max_batch) return fail(c, LGH_INVALID_ARGUMENT, "n_seq must be 1 .. max_batch");
+  if (n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "too many steps");
+  if (Bs.samp_set.size() != Bs.max_batch || Bs.samp_cfg.size() != Bs.max_batch) return fail(c, LGH_INVALID_ARGUMENT, "no samplers");
+  size_t hist_off[kMaxBatch];
+  size_t off = 0;
+  for (uint32_t i = 0; i < n_seq; i++) {
+    if (slots[i] >= Bs.max_batch) return fail(c, LGH_INVALID_ARGUMENT, "slot numbers must be distinct and below max_batch");
+    if (!Bs.samp_set[slots[i]]) return fail(c, LGH_INVALID_ARGUMENT, "slot " + std::to_string(slots[i]) + ": lgh_batch_set_sampler has not been called");
+    if (Bs.pos[slots[i]] + n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "the steps would run past max_seq_len");
+    const lgh_sampler_config& g = Bs.samp_cfg[slots[i]];
+    if (n_steps && !uniforms && !(g.temperature == 0.0f || g.top_k == 1)) return fail(c, LGH_INVALID_ARGUMENT, "uniforms is NULL");
+    const size_t n = history_lens ? history_lens[i] : 0;
+    if (n && !histories) return fail(c, LGH_INVALID_ARGUMENT, "histories is NULL");
+    hist_off[i] = off;
+    off += n;
+  }
+  if ((rc = stage_control(c, slots, first_tokens, n_seq))) return rc;   // (checks the slots and tokens)
+  if (n_steps == 0) return LGH_OK;
+  for (uint32_t i = 0; i < n_seq; i++)
+    if ((rc = samp_begin(c, Bs.samp, slots[i], Bs.samp_cfg[slots[i]], histories ? histories + hist_off[i] : nullptr,
+                         history_lens ? history_lens[i] : 0, first_tokens[i], n_steps, uniforms ? uniforms + i : nullptr, n_seq)))
+      return rc;
+  for (size_t st = 0; st < n_steps; st++) {
+    if ((rc = run_multi(c, n_seq, 2))) return rc;
+    if (tokens_out)
+      HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_log + st * kMaxBatch, Bs.d_tokens, (size_t)n_seq * 4, hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  if (tokens_out) {
     std::vector<int> log(n_steps * kMaxBatch);
     HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpy(log.data(), Bs.d_log, log.size() * 4, hipMemcpyDeviceToHost));
     for (size_t st = 0; st < n_steps; st++)

@@ -229,6 +229,23 @@ int lgh_op_silu_mul(int device, const float* gate, const float* up, float* out, 
   return t.down(out, dout, n);
 }
 
+// ---- Sampler::sample (sampling/mod.rs:188-304) through the kernels of lgh_decode_sample ----
+int lgh_op_sample(int device, const float* logits, size_t vocab, const lgh_sampler_config* config, const uint32_t* recent, size_t n_recent,
+                  const uint32_t* counts, float uniform, uint32_t* token_out) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!logits || !token_out || vocab == 0 || vocab > 0x7FFFFFFFu || (n_recent && !recent)) return LGH_INVALID_ARGUMENT;
+  int rc = samp_check(t.c, config);
+  if (rc) return rc;
+  t.c->d.vocab_size = (uint32_t)vocab;
+  t.c->d.max_seq_len = 1;
+  SampBufs B;
+  if ((rc = samp_alloc(t.c, B, 1, 1))) return rc;
+  const float* dl = t.up(logits, vocab);
+  if (!dl) return LGH_ALLOCATION_FAILED;
+  return samp_one(t.c, B, *config, recent, n_recent, counts, uniform, dl, token_out);
+}
+
 // ---- Backend::add / mul / scale / silu / gelu / softmax / matmul / matvec / matvec_q / attention (backend/mod.rs:29-265) ----
 static int ewise_impl(int device, int op, const float* a, const float* b, float s, float* out, size_t n) {
   Tmp t(device);

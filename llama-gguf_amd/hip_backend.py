@@ -37,6 +37,7 @@ ABI_SYMBOLS = (
     "lgh_pipeline_last_error",
     "lgh_set_kv_rotation_signs", "lgh_op_tq_compress", "lgh_set_kv_qjl_matrices", "lgh_op_tq_compress_qjl",
     "lgh_batch_create", "lgh_batch_reset", "lgh_batch_position", "lgh_batch_prefill", "lgh_forward_multi", "lgh_decode_greedy_multi",
+    "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -87,6 +88,29 @@ class GgufInfo(C.Structure):
 class GgufValue(C.Structure):
     _fields_ = [("type", C.c_uint32), ("reserved", C.c_uint32), ("u", C.c_uint64), ("f", C.c_double), ("arr_len", C.c_uint64),
                 ("s", C.c_char * 256)]
+
+
+class SamplerConfig(C.Structure):
+    """lgh_sampler_config: SamplerConfig (src/sampling/mod.rs:37-62) minus seed / min_p / typical_p / mirostat."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_uint32), ("top_p", C.c_float), ("repeat_penalty", C.c_float),
+                ("repeat_window", C.c_uint32), ("frequency_penalty", C.c_float), ("presence_penalty", C.c_float),
+                ("eos_token", C.c_int32)]
+
+
+# SamplerConfig presets of the reference (sampling/mod.rs:64-122) and EngineConfig::default's settings (src/engine.rs:117-130)
+SAMPLER_PRESETS = {
+    "engine_default": dict(temperature=0.7, top_k=40, top_p=0.95, repeat_penalty=1.1, repeat_window=64),
+    "sampler_default": dict(temperature=0.8, top_k=40, top_p=0.95, repeat_penalty=1.1, repeat_window=64),
+    "greedy": dict(temperature=0.0, top_k=1, top_p=1.0, repeat_penalty=1.0, repeat_window=0),
+    "creative": dict(temperature=1.0, top_k=0, top_p=0.9, repeat_penalty=1.2, repeat_window=64),
+}
+
+
+def sampler_config(temperature: float = 0.8, top_k: int = 40, top_p: float = 0.95, repeat_penalty: float = 1.1,
+                   repeat_window: int = 64, frequency_penalty: float = 0.0, presence_penalty: float = 0.0,
+                   eos_token: int = -1) -> SamplerConfig:
+    """An lgh_sampler_config; the defaults are SamplerConfig::default's (sampling/mod.rs:64-80)."""
+    return SamplerConfig(temperature, top_k, top_p, repeat_penalty, repeat_window, frequency_penalty, presence_penalty, eos_token)
 
 
 class Stats(C.Structure):
@@ -165,6 +189,11 @@ def load_library() -> C.CDLL:
         "lgh_batch_create": (C.c_int, [vp, u32]), "lgh_batch_reset": (C.c_int, [vp, u32]), "lgh_batch_position": (sz, [vp, u32]),
         "lgh_batch_prefill": (C.c_int, [vp, u32, vp, sz]), "lgh_forward_multi": (C.c_int, [vp, vp, vp, u32, vp, vp]),
         "lgh_decode_greedy_multi": (C.c_int, [vp, vp, vp, u32, sz, vp]),
+        "lgh_set_sampler": (C.c_int, [vp, C.POINTER(SamplerConfig)]),
+        "lgh_decode_sample": (C.c_int, [vp, u32, vp, sz, sz, vp, vp]),
+        "lgh_batch_set_sampler": (C.c_int, [vp, u32, C.POINTER(SamplerConfig)]),
+        "lgh_decode_sample_multi": (C.c_int, [vp, vp, vp, u32, vp, vp, sz, vp, vp]),
+        "lgh_op_sample": (C.c_int, [C.c_int, vp, sz, C.POINTER(SamplerConfig), vp, sz, vp, f32, C.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -335,6 +364,44 @@ class HipGpuInference:
         tk = np.ascontiguousarray(first_tokens, dtype=np.uint32)
         out = np.zeros((n_steps, sl.size), dtype=np.uint32)
         self._call(load_library().lgh_decode_greedy_multi(self._h, sl.ctypes.data, tk.ctypes.data, sl.size, n_steps, out.ctypes.data))
+        return out
+
+    # -- sampling on the device (Sampler::sample, src/sampling/mod.rs:188-304; include/llama_gguf_hip.h lgh_set_sampler)
+    def set_sampler(self, **cfg) -> None:
+        """Sampler::new: the config (keyword arguments of `sampler_config`) and zeroed counts."""
+        self._call(load_library().lgh_set_sampler(self._h, C.byref(sampler_config(**cfg))))
+
+    def decode_sample(self, first_token: int, history: Sequence[int], n_steps: int, uniforms=None) -> np.ndarray:
+        """n_steps sampled tokens fed back on the device; history = the context's tokens before first_token, uniforms[n_steps] =
+        the reference's rng.gen::<f32>() draws (None under a greedy config)."""
+        h = np.ascontiguousarray(history, dtype=np.uint32)
+        u = _f32(uniforms) if uniforms is not None else None
+        if u is not None:
+            assert u.size >= n_steps
+        out = np.zeros(n_steps, dtype=np.uint32)
+        self._call(load_library().lgh_decode_sample(self._h, first_token, h.ctypes.data if h.size else None, h.size, n_steps,
+                                                    u.ctypes.data if u is not None else None, out.ctypes.data))
+        return out
+
+    def batch_set_sampler(self, slot: int, **cfg) -> None:
+        self._call(load_library().lgh_batch_set_sampler(self._h, slot, C.byref(sampler_config(**cfg))))
+
+    def decode_sample_multi(self, slots: Sequence[int], first_tokens: Sequence[int], histories: Sequence[Sequence[int]], n_steps: int,
+                            uniforms=None) -> np.ndarray:
+        """decode_greedy_multi with each slot's sampler; uniforms [n_steps, n_seq]; returns [n_steps, n_seq]."""
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        tk = np.ascontiguousarray(first_tokens, dtype=np.uint32)
+        assert sl.size == tk.size == len(histories)
+        lens = np.array([len(h) for h in histories], dtype=np.uint64)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(h, dtype=np.uint32) for h in histories]) if lens.sum() else
+                                    np.zeros(0, dtype=np.uint32), dtype=np.uint32)
+        u = _f32(uniforms).reshape(-1) if uniforms is not None else None
+        if u is not None:
+            assert u.size >= n_steps * sl.size
+        out = np.zeros((n_steps, sl.size), dtype=np.uint32)
+        self._call(load_library().lgh_decode_sample_multi(self._h, sl.ctypes.data, tk.ctypes.data, sl.size,
+                                                          flat.ctypes.data if flat.size else None, lens.ctypes.data, n_steps,
+                                                          u.ctypes.data if u is not None else None, out.ctypes.data))
         return out
 
     # -- pipeline stage
@@ -624,6 +691,20 @@ def op_tq_compress_qjl(x, bits: int, signs, qjl_matrix, device: int = 0):
     _chk(load_library().lgh_op_tq_compress_qjl(device, bits, x.ctypes.data, x.size, sg.ctypes.data, S.ctypes.data, codes.ctypes.data,
                                                qb.ctypes.data, C.addressof(norm)), "tq_compress_qjl")
     return codes, qb, float(norm.value)
+
+
+def op_sample(logits, recent: Sequence[int] = (), counts=None, uniform: float = 0.0, device: int = 0, **cfg) -> int:
+    """One Sampler::sample call on the device (lgh_op_sample); cfg: keyword arguments of `sampler_config`."""
+    lg = _f32(logits)
+    rc = np.ascontiguousarray(recent, dtype=np.uint32)
+    cn = np.ascontiguousarray(counts, dtype=np.uint32) if counts is not None else None
+    if cn is not None:
+        assert cn.size == lg.size
+    tok = C.c_uint32()
+    _chk(load_library().lgh_op_sample(device, lg.ctypes.data, lg.size, C.byref(sampler_config(**cfg)),
+                                      rc.ctypes.data if rc.size else None, rc.size, cn.ctypes.data if cn is not None else None,
+                                      float(uniform), C.byref(tok)), "lgh_op_sample")
+    return tok.value
 
 
 def op_silu_mul(gate, up, device: int = 0) -> np.ndarray:
