@@ -441,6 +441,34 @@ int lgh_op_matvec(int device, const float* a, const float* x, float* out, size_t
 int lgh_op_matvec_q(int device, uint32_t ggml_type, const void* a, const float* x, float* out, size_t m, size_t k);
 int lgh_op_attention(int device, const float* q, const float* k, const float* v, float* out, size_t n_heads, size_t n_kv_heads,
                      size_t seq_len, size_t kv_len, size_t head_dim, float scale);
+/* The engine's attention launch sequences, one path at a time, for kernel-level tests.  Each takes the cache contents from the
+ * host and the position `pos` through the device word the engine's kernels read; the token at `pos` attends to rows 0..pos.
+ * A shape the chosen path has no kernel for answers LGH_UNSUPPORTED (never another kernel).  q / out [n_heads][head_dim].
+ *
+ * Backend::attention_cached (ops.rs:1479-1537) over the f32 cache [n_kv_heads][max_seq_len][head_dim], rows 0..pos already
+ * stored (as after the engine's kv_store).  path 0: split + merge (4 or 8 waves per workgroup, chosen from max_seq_len as in
+ * the engine; n_splits 1..32); path 1: the single-launch kernel of short contexts; path 2: the kernel of any head_dim / group
+ * size (max_seq_len <= 38400). */
+int lgh_op_attention_decode(int device, int path, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
+                            size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos, int n_splits);
+/* QuantizedKVCache (kv_quantized.rs:143-300, 385-565): kv_cache_type LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2.  k_bytes / v_bytes
+ * [n_kv_heads][max_seq_len][head_dim] and (int8 only; may be NULL otherwise) k_scale / v_scale [n_kv_heads][max_seq_len] are in / out:
+ * rows 0..pos-1 are read, row `pos` comes back as the launch quantized and stored k_new / v_new [n_kv_heads][head_dim]. */
+int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
+                         const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv_heads, size_t head_dim,
+                         size_t max_seq_len, float scale, size_t pos, int n_splits);
+/* TurboQuantKVCache::write_kv + attention_layer (kv_turboquant.rs:88-201): kv_cache_type LGH_KV_TQ2 / TQ3 / TQ2_QJL / TQ3_QJL.
+ * k_codes / v_codes [n_kv_heads][max_seq_len][row bytes] and, for the QJL types, k_qjl [n_kv_heads][max_seq_len][head_dim / 32 + 1]
+ * words (sign bits, then the residual norm's bits) are in / out: row `pos` comes back as the launch compressed k_new / v_new.
+ * signs [n_kv_heads][k, v][head_dim] (+1 / -1); qjl_matrices [n_kv_heads][head_dim][head_dim] (QJL types; NULL otherwise). */
+int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl,
+                        const float* k_new, const float* v_new, const float* signs, const float* qjl_matrices, float* out, size_t n_heads,
+                        size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos, int n_splits);
+/* Causal Backend::attention (ops.rs:1353-1472) of m_tokens prompt tokens at positions pos0.. as the batched prefill runs it:
+ * q [m_tokens][n_heads][head_dim]; the f32 caches hold rows 0..pos0 + m_tokens - 1; out [m_tokens][n_heads * head_dim] = the
+ * kernel's f16 results widened to f32.  m_tokens <= 128, n_heads * head_dim % 256 == 0, pos0 + m_tokens <= max_seq_len. */
+int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
+                             size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos0, size_t m_tokens);
 /* Device-resident weights by tensor name for the per-op surface: `CudaBackend::load_model_weights` and the `b.name()`
  * lookups in its vec_mat / vec_mat_q (src/backend/cuda/mod.rs:121-146, 436-470, 511-575).  A weight is uploaded once
  * (native GGUF bytes; the library re-lays it out as lgh_upload_tensor does) and later calls name it. */

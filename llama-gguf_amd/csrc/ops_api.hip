@@ -394,6 +394,177 @@ int lgh_op_attention(int device, const float* q, const float* k, const float* v,
   return t.down(out, dout, n_heads * seq_len * d);
 }
 
+// ---- the engine's attention launch sequences one path at a time (test surface: tests/test_gpu_attention.py holds each to a
+// float64 restatement).  The caches come from the host, the position through the device word the engine's kernels read
+// (state[ST_POS]); nothing falls back to another kernel: a shape the path has no kernel for answers LGH_UNSUPPORTED. ----
+}  // extern "C"
+
+namespace {
+
+void* up_bytes(Tmp& t, const void* host, size_t n) {   // device copy of n host bytes (nullptr on failure)
+  void* d = nullptr;
+  if (dev_alloc(t.c, &d, n ? n : 4)) return nullptr;
+  if (host && n && hipMemcpyAsync(d, host, n, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return nullptr;
+  return d;
+}
+
+int down_bytes(Tmp& t, void* host, const void* dev, size_t n) {
+  if (n && hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  return hipStreamSynchronize(t.c->stream) == hipSuccess ? LGH_OK : LGH_OPERATION_FAILED;
+}
+
+int set_pos(Tmp& t, size_t pos) {   // the engine's position word
+  const int p = (int)pos;
+  if (hipMemcpyAsync(t.c->state + ST_POS, &p, 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  return hipStreamSynchronize(t.c->stream) == hipSuccess ? LGH_OK : LGH_OPERATION_FAILED;
+}
+
+float half_to_float(uint16_t h) {
+  const uint32_t s = (uint32_t)(h >> 15) << 31, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
+  float v;
+  if (e == 0) v = (float)m * 0x1p-24f;
+  else if (e == 31) v = m ? NAN : INFINITY;
+  else v = std::ldexp((float)(m | 0x400u), (int)e - 25);
+  uint32_t b;
+  std::memcpy(&b, &v, 4);
+  b |= s;
+  std::memcpy(&v, &b, 4);
+  return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lgh_op_attention_decode(int device, int path, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
+                            size_t n_kv, size_t head_dim, size_t max_seq, float scale, size_t pos, int n_splits) {
+  // Backend::attention_cached (ops.rs:1479-1537) as the engine's decode step runs it over the f32 cache
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!q || !k_cache || !v_cache || !out || n_kv == 0 || n_heads % n_kv || head_dim == 0 || pos >= max_seq || max_seq > 0x7FFFFFFFu)
+    return LGH_INVALID_ARGUMENT;
+  if (path < 0 || path > 2) return LGH_INVALID_ARGUMENT;
+  const size_t g = n_heads / n_kv, cache = n_kv * max_seq * head_dim;
+  const bool fast = attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)g);
+  if (path != 2 && !fast) return LGH_UNSUPPORTED;
+  if (path == 0 && (n_splits < 1 || n_splits > 32)) return LGH_INVALID_ARGUMENT;
+  if (path == 2 && max_seq * 4 > 150 * 1024) return LGH_UNSUPPORTED;   // the scores of a head live in LDS
+  float *dq = t.up(q, n_heads * head_dim), *dk = t.up(k_cache, cache), *dv = t.up(v_cache, cache), *dout = t.up(nullptr, n_heads * head_dim);
+  if (!dq || !dk || !dv || !dout) return LGH_ALLOCATION_FAILED;
+  int rc = set_pos(t, pos);
+  if (rc) return rc;
+  hipStream_t st = t.c->stream;
+  const int* dpos = t.c->state + ST_POS;
+  const uint32_t H = (uint32_t)n_heads, KV = (uint32_t)n_kv, D = (uint32_t)head_dim, MS = (uint32_t)max_seq;
+  if (path == 0) {   // split + merge; attn_launch picks 4 or 8 waves from max_seq, as in the engine
+    float *pml = t.up(nullptr, n_kv * n_splits * g * 2), *pacc = t.up(nullptr, n_kv * n_splits * g * head_dim);
+    if (!pml || !pacc) return LGH_ALLOCATION_FAILED;
+    if (attn_launch(dq, dk, dv, H, KV, D, MS, scale, dpos, 0, (uint32_t)n_splits, pml, pacc, st) != hipSuccess) return LGH_OPERATION_FAILED;
+    if (attn_combine_launch(pml, pacc, H, KV, D, (uint32_t)n_splits, dout, nullptr, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  } else if (path == 1) {   // one launch (engine: pos + 1 <= direct_attn_max_kv)
+    if (attn_direct_launch(dq, dk, dv, H, KV, D, MS, scale, dpos, dout, nullptr, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  } else if (attn_decode_any_launch(dq, dk, dv, dout, H, KV, D, MS, scale, dpos, st) != hipSuccess) {   // any head_dim / group size
+    return LGH_OPERATION_FAILED;
+  }
+  return t.down(out, dout, n_heads * head_dim);
+}
+
+int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
+                         const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq,
+                         float scale, size_t pos, int n_splits) {
+  // QuantizedKVCache (kv_quantized.rs:143-300): the attention launch also quantizes the current rows and stores them at `pos`
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (kv_cache_type < LGH_KV_INT8 || kv_cache_type > LGH_KV_FP8_E5M2) return LGH_UNSUPPORTED;
+  const bool i8 = kv_cache_type == LGH_KV_INT8;
+  if (!q || !k_bytes || !v_bytes || !k_new || !v_new || !out || (i8 && (!k_scale || !v_scale))) return LGH_INVALID_ARGUMENT;
+  if (n_kv == 0 || n_heads % n_kv || pos >= max_seq || max_seq > 0x7FFFFFFFu || n_splits < 1 || n_splits > 32) return LGH_INVALID_ARGUMENT;
+  const size_t g = n_heads / n_kv, rows = n_kv * max_seq, cache = rows * head_dim;
+  if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)g)) return LGH_UNSUPPORTED;
+  float *dq = t.up(q, n_heads * head_dim), *dkn = t.up(k_new, n_kv * head_dim), *dvn = t.up(v_new, n_kv * head_dim);
+  int8_t *dk = (int8_t*)up_bytes(t, k_bytes, cache), *dv = (int8_t*)up_bytes(t, v_bytes, cache);
+  float *dks = i8 ? t.up(k_scale, rows) : nullptr, *dvs = i8 ? t.up(v_scale, rows) : nullptr;
+  float *dout = t.up(nullptr, n_heads * head_dim), *pml = t.up(nullptr, n_kv * n_splits * g * 2), *pacc = t.up(nullptr, n_kv * n_splits * g * head_dim);
+  if (!dq || !dkn || !dvn || !dk || !dv || (i8 && (!dks || !dvs)) || !dout || !pml || !pacc) return LGH_ALLOCATION_FAILED;
+  int rc = set_pos(t, pos);
+  if (rc) return rc;
+  hipStream_t st = t.c->stream;
+  if (attn_q8_launch((int)kv_cache_type, dq, dk, dv, dks, dvs, dkn, dvn, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, scale,
+                     t.c->state + ST_POS, (uint32_t)n_splits, pml, pacc, st) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  if (attn_combine_launch(pml, pacc, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)n_splits, dout, nullptr, st) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  if ((rc = down_bytes(t, k_bytes, dk, cache)) || (rc = down_bytes(t, v_bytes, dv, cache))) return rc;
+  if (i8 && ((rc = t.down(k_scale, dks, rows)) || (rc = t.down(v_scale, dvs, rows)))) return rc;
+  return t.down(out, dout, n_heads * head_dim);
+}
+
+int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl, const float* k_new,
+                        const float* v_new, const float* signs, const float* qjl_matrices, float* out, size_t n_heads, size_t n_kv, size_t head_dim,
+                        size_t max_seq, float scale, size_t pos, int n_splits) {
+  // TurboQuantKVCache::write_kv + attention_layer (kv_turboquant.rs:88-201): the split launch compresses and stores the current
+  // rows, the merge inverts the V rotation
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!kv_is_tq(kv_cache_type)) return LGH_UNSUPPORTED;
+  const bool qjl = kv_is_qjl(kv_cache_type);
+  const int bits = kv_tq_bits(kv_cache_type);
+  if (!q || !k_codes || !v_codes || !k_new || !v_new || !signs || !out || (qjl && (!k_qjl || !qjl_matrices))) return LGH_INVALID_ARGUMENT;
+  if (n_kv == 0 || n_heads % n_kv || pos >= max_seq || max_seq > 0x7FFFFFFFu || n_splits < 1 || n_splits > 32) return LGH_INVALID_ARGUMENT;
+  const size_t g = n_heads / n_kv, rows = n_kv * max_seq, d = head_dim;
+  if (!attn_shape_has_fast_kernel((uint32_t)d, (uint32_t)g)) return LGH_UNSUPPORTED;
+  for (size_t i = 0; i < n_kv * 2 * d; i++)
+    if (signs[i] != 1.0f && signs[i] != -1.0f) return LGH_INVALID_ARGUMENT;
+  const size_t cb = rows * tq_row_bytes_host(bits, (uint32_t)d), xw = rows * (d / 32 + 1);
+  float *dq = t.up(q, n_heads * d), *dkn = t.up(k_new, n_kv * d), *dvn = t.up(v_new, n_kv * d), *ds = t.up(signs, n_kv * 2 * d);
+  uint8_t *dk = (uint8_t*)up_bytes(t, k_codes, cb), *dv = (uint8_t*)up_bytes(t, v_codes, cb);
+  uint32_t* dx = qjl ? (uint32_t*)up_bytes(t, k_qjl, xw * 4) : nullptr;
+  float* dS = qjl ? t.up(qjl_matrices, n_kv * d * d) : nullptr;
+  float *dout = t.up(nullptr, n_heads * d), *pml = t.up(nullptr, n_kv * n_splits * g * 2), *pacc = t.up(nullptr, n_kv * n_splits * g * d);
+  if (!dq || !dkn || !dvn || !ds || !dk || !dv || (qjl && (!dx || !dS)) || !dout || !pml || !pacc) return LGH_ALLOCATION_FAILED;
+  int rc = set_pos(t, pos);
+  if (rc) return rc;
+  hipStream_t st = t.c->stream;
+  if (attn_tq_launch(bits, dq, dk, dv, dkn, dvn, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, scale, t.c->state + ST_POS,
+                     (uint32_t)n_splits, pml, pacc, st, dS, dx) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  if (attn_tq_combine_launch(bits, pml, pacc, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)n_splits, dout, nullptr, st, 0, 0) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  if ((rc = down_bytes(t, k_codes, dk, cb)) || (rc = down_bytes(t, v_codes, dv, cb))) return rc;
+  if (qjl && (rc = down_bytes(t, k_qjl, dx, xw * 4))) return rc;
+  return t.down(out, dout, n_heads * d);
+}
+
+int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads, size_t n_kv,
+                             size_t head_dim, size_t max_seq, float scale, size_t pos0, size_t m_tokens) {
+  // causal Backend::attention (ops.rs:1353-1472) of a block of prompt tokens as the batched prefill runs it: the f16 XH matrix that
+  // the wo GEMM reads, un-swizzled here and widened to f32
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!q || !k_cache || !v_cache || !out || n_kv == 0 || n_heads % n_kv || max_seq > 0x7FFFFFFFu) return LGH_INVALID_ARGUMENT;
+  const size_t qd = n_heads * head_dim, cache = n_kv * max_seq * head_dim;
+  if (m_tokens == 0 || m_tokens > (size_t)kPfTokens || qd % 256 || pos0 + m_tokens > max_seq) return LGH_INVALID_ARGUMENT;
+  float *dq = t.up(q, m_tokens * qd), *dk = t.up(k_cache, cache), *dv = t.up(v_cache, cache);
+  const size_t xb = xh_bytes((uint32_t)qd);
+  uint8_t* xh = (uint8_t*)up_bytes(t, nullptr, xb);
+  if (!dq || !dk || !dv || !xh) return LGH_ALLOCATION_FAILED;
+  hipStream_t st = t.c->stream;
+  if (hipMemsetAsync(xh, 0, xb, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  if (attn_prefill_launch(dq, dk, dv, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, scale, (uint32_t)pos0,
+                          (uint32_t)m_tokens, xh, st) != hipSuccess)
+    return LGH_UNSUPPORTED;
+  std::vector<uint8_t> host(xb);
+  int rc = down_bytes(t, host.data(), xh, xb);
+  if (rc) return rc;
+  for (size_t tk = 0; tk < m_tokens; tk++)
+    for (size_t k = 0; k < qd; k++) {
+      uint16_t h;
+      std::memcpy(&h, host.data() + xh_offset((uint32_t)tk, (uint32_t)k), 2);
+      out[tk * qd + k] = half_to_float(h);
+    }
+  return LGH_OK;
+}
+
 // ---- device-resident weights by tensor name: CudaBackend::load_model_weights + the `b.name()` lookups of its vec_mat /
 // vec_mat_q (src/backend/cuda/mod.rs:121-146, 436-470, 511-575; store: cuda/dequant_weights.rs) ----
 }  // extern "C"

@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     "lgh_set_kv_rotation_signs", "lgh_op_tq_compress", "lgh_set_kv_qjl_matrices", "lgh_op_tq_compress_qjl",
     "lgh_batch_create", "lgh_batch_reset", "lgh_batch_position", "lgh_batch_prefill", "lgh_forward_multi", "lgh_decode_greedy_multi",
     "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
+    "lgh_op_attention_decode", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -194,6 +195,10 @@ def load_library() -> C.CDLL:
         "lgh_batch_set_sampler": (C.c_int, [vp, u32, C.POINTER(SamplerConfig)]),
         "lgh_decode_sample_multi": (C.c_int, [vp, vp, vp, u32, vp, vp, sz, vp, vp]),
         "lgh_op_sample": (C.c_int, [C.c_int, vp, sz, C.POINTER(SamplerConfig), vp, sz, vp, f32, C.POINTER(u32)]),
+        "lgh_op_attention_decode": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
+        "lgh_op_attention_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
+        "lgh_op_attention_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
+        "lgh_op_attention_prefill": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -659,6 +664,66 @@ def op_attention_cached(q, k_cache, v_cache, scale: float, kv_len: int, n_splits
     _chk(load_library().lgh_op_attention_cached(device, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, out.ctypes.data,
                                                 q.shape[0], kc.shape[0], q.shape[1], kc.shape[1], scale, kv_len,
                                                 n_splits), "attention_cached")
+    return out
+
+
+ATTN_SPLIT, ATTN_DIRECT, ATTN_ANY = 0, 1, 2   # lgh_op_attention_decode paths
+
+
+def op_attention_decode(path: int, q, k_cache, v_cache, scale: float, pos: int, n_splits: int = 8, device: int = 0) -> np.ndarray:
+    """One decode step's attention over the f32 cache (rows 0..pos stored) on the engine path `path`: ATTN_SPLIT (split + merge),
+    ATTN_DIRECT (one launch) or ATTN_ANY (any head_dim / group size).  q [nh, d]; caches [nkv, max_seq, d]; pos via the device word."""
+    q, kc, vc = _f32(q), _f32(k_cache), _f32(v_cache)
+    out = np.empty_like(q)
+    _chk(load_library().lgh_op_attention_decode(device, path, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, out.ctypes.data, q.shape[0],
+                                                kc.shape[0], q.shape[1], kc.shape[1], scale, pos, n_splits), "attention_decode")
+    return out
+
+
+def op_attention_kv8(kv_cache_type: int, q, k_bytes, v_bytes, k_scale, v_scale, k_new, v_new, scale: float, pos: int, n_splits: int = 8,
+                     device: int = 0):
+    """One decode step's attention over an int8 / FP8 cache (KV_INT8 / KV_FP8_E4M3 / KV_FP8_E5M2): bytes [nkv, max_seq, d] (uint8 or
+    int8), scales [nkv, max_seq] (int8 only, else None); the launch stores k_new / v_new [nkv, d] at row `pos`.
+    -> (out [nh, d], k_bytes, v_bytes, k_scale, v_scale) after the call (copies; the inputs are untouched)."""
+    q, kn, vn = _f32(q), _f32(k_new), _f32(v_new)
+    kb, vb = np.array(k_bytes, dtype=np.uint8, copy=True), np.array(v_bytes, dtype=np.uint8, copy=True)
+    i8 = kv_cache_type == KV_INT8
+    ks = np.array(k_scale, dtype=np.float32, copy=True) if i8 else None
+    vs = np.array(v_scale, dtype=np.float32, copy=True) if i8 else None
+    out = np.empty_like(q)
+    _chk(load_library().lgh_op_attention_kv8(device, kv_cache_type, q.ctypes.data, kb.ctypes.data, vb.ctypes.data,
+                                             ks.ctypes.data if i8 else None, vs.ctypes.data if i8 else None, kn.ctypes.data, vn.ctypes.data,
+                                             out.ctypes.data, q.shape[0], kb.shape[0], q.shape[1], kb.shape[1], scale, pos, n_splits),
+         "attention_kv8")
+    return out, kb, vb, ks, vs
+
+
+def op_attention_tq(kv_cache_type: int, q, k_codes, v_codes, k_qjl, k_new, v_new, signs, qjl_matrices, scale: float, pos: int,
+                    n_splits: int = 8, device: int = 0):
+    """One decode step's attention over a TurboQuant cache (KV_TQ2 / TQ3 / TQ2_QJL / TQ3_QJL): codes [nkv, max_seq, row bytes];
+    k_qjl [nkv, max_seq, d / 32 + 1] uint32 words (QJL types, else None); signs [nkv, 2, d]; qjl_matrices [nkv, d, d] (QJL types).
+    The launch compresses k_new / v_new [nkv, d] into row `pos`.  -> (out [nh, d], k_codes, v_codes, k_qjl) after the call (copies)."""
+    q, kn, vn, sg = _f32(q), _f32(k_new), _f32(v_new), _f32(signs)
+    kc, vc = np.array(k_codes, dtype=np.uint8, copy=True), np.array(v_codes, dtype=np.uint8, copy=True)
+    qjl = kv_cache_type in (KV_TQ2_QJL, KV_TQ3_QJL)
+    kx = np.array(k_qjl, dtype=np.uint32, copy=True) if qjl else None
+    S = _f32(qjl_matrices) if qjl else None
+    out = np.empty_like(q)
+    _chk(load_library().lgh_op_attention_tq(device, kv_cache_type, q.ctypes.data, kc.ctypes.data, vc.ctypes.data,
+                                            kx.ctypes.data if qjl else None, kn.ctypes.data, vn.ctypes.data, sg.ctypes.data,
+                                            S.ctypes.data if qjl else None, out.ctypes.data, q.shape[0], kc.shape[0], q.shape[1],
+                                            kc.shape[1], scale, pos, n_splits), "attention_tq")
+    return out, kc, vc, kx
+
+
+def op_attention_prefill(q, k_cache, v_cache, scale: float, pos0: int, device: int = 0) -> np.ndarray:
+    """Causal attention of a block of prompt tokens on the batched-prefill kernel: q [m, nh, d] at positions pos0..pos0+m-1; the
+    caches [nkv, max_seq, d] hold rows 0..pos0+m-1.  -> [m, nh * d]: the kernel's f16 outputs widened to f32."""
+    q, kc, vc = _f32(q), _f32(k_cache), _f32(v_cache)
+    m, nh, d = q.shape
+    out = np.empty((m, nh * d), dtype=np.float32)
+    _chk(load_library().lgh_op_attention_prefill(device, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, out.ctypes.data, nh, kc.shape[0], d,
+                                                 kc.shape[1], scale, pos0, m), "attention_prefill")
     return out
 
 
