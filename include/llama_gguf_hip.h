@@ -469,6 +469,31 @@ int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint
  * kernel's f16 results widened to f32.  m_tokens <= 128, n_heads * head_dim % 256 == 0, pos0 + m_tokens <= max_seq_len. */
 int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
                              size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos0, size_t m_tokens);
+/* The engine's quantized mat-vec launches (launch_mv), one call site at a time, for kernel-level tests.  Test surface: these
+ * exist to hold the kernels to a reference and are not part of the inference API.  Weights are native GGUF bytes, row-major
+ * [out][in]; the library re-lays them out as lgh_upload_tensor does, so each weight runs on the kernel family the engine picks.
+ *
+ * layer_forward's fused QKV launch: types / w / bias hold Q, K, V (bias entries may be NULL); RMSNorm(x) * norm_w feeds all
+ * three; q_out [n_heads * head_dim] is rotated at `pos` (through the device position word), and row `pos` of every head of the
+ * caches [n_kv_heads][max_seq_len][head_dim] (in / out) receives the rotated K and the plain V.  Non-fused types: LGH_UNSUPPORTED. */
+int lgh_op_qkv_rope(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                    float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
+                    float rope_base, float rope_scale, float* q_out, float* k_cache, float* v_cache);
+/* Launch A then launch B on A's output.  A: out_a = W_a . (RMSNorm(x) * norm_w, or x when norm_w is NULL) + bias_a (+ resid), or
+ * with w_a_up the SwiGLU gate-up launch silu(W_a . x') * (W_a_up . x') (no bias / resid); A is asked to leave the XQ image of
+ * out_a for its consumer: xq_next 0 no, 1 plain, 2 multiplied by next_nw.  B: out_b = W_b . (RMSNorm(out_a) * next_nw when
+ * xq_next == 2, else out_a), [n_b][n_a], run as the engine runs it (from A's image when one was left: *image_used = 1); then
+ * again into out_b_requant after the image is marked stale, which converts out_a afresh. */
+int lgh_op_linear_chain(int device, uint32_t type_a, const void* w_a, const void* w_a_up, const float* bias_a, size_t k, size_t n_a,
+                        const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
+                        uint32_t type_b, const void* w_b, size_t n_b, float* out_a, float* out_b, float* out_b_requant, int* image_used);
+/* ffn_forward's MoE half: out = x + sum_p sel_w[p] * down_e(silu(gate_e . x') * (up_e . x')), e = sel[p], x' = RMSNorm(x) * norm_w.
+ * Expert stacks in GGUF order: w_gate / w_up [n_experts][ffn][hidden], w_down [n_experts][hidden][ffn].  With `router`
+ * ([n_experts][hidden] f32) the device router selects (sel / sel_w are ignored); otherwise sel / sel_w (top_k entries) drive the
+ * same expert launches.  sel_out / sel_w_out (may be NULL) receive the selection used.  top_k <= 8, n_experts <= 64. */
+int lgh_op_moe_experts(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down,
+                       size_t n_experts, size_t hidden, size_t ffn, size_t top_k, const float* router, const int* sel, const float* sel_w,
+                       const float* x, const float* norm_w, float eps, float* out, int* sel_out, float* sel_w_out);
 /* Device-resident weights by tensor name for the per-op surface: `CudaBackend::load_model_weights` and the `b.name()`
  * lookups in its vec_mat / vec_mat_q (src/backend/cuda/mod.rs:121-146, 436-470, 511-575).  A weight is uploaded once
  * (native GGUF bytes; the library re-lays it out as lgh_upload_tensor does) and later calls name it. */

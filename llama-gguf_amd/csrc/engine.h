@@ -166,6 +166,8 @@ int fail(lgh_ctx* c, int status, const std::string& msg);
 int build_mv_group(lgh_ctx* c, const SegSpec* specs, int nseg, const float* norm_w, uint32_t k, bool mfma, lgh::MvLaunch& L, uint32_t& wg,
                    uint32_t& threads, uint64_t& alg, uint32_t tile_cap);
 int ffn_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma);
+int moe_experts_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma);   // given v.moe_sel / v.moe_w
+void rope_table_host(const lgh_model_desc& d, std::vector<float>& cs);
 int engine_shape_check(const lgh_model_desc& d, std::string& why);   // LGH_OK, or the status lgh_create returns and why
 int dev_alloc(lgh_ctx* c, void** p, size_t bytes);
 LayoutInfo layout_for(int src_type);

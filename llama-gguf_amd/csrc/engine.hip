@@ -420,6 +420,21 @@ int launch_mv(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float* 
   return rc;
 }
 
+// RoPE table [max_seq][head_dim / 2][cos, sin] in the reference's own arithmetic (ops.rs:1303-1313): libm powf / cosf / sinf on the host
+void rope_table_host(const lgh_model_desc& d, std::vector<float>& cs) {
+  const uint32_t half = d.head_dim / 2;
+  cs.assign((size_t)d.max_seq_len * half * 2, 0.0f);
+  for (uint32_t p = 0; p < d.max_seq_len; p++) {
+    const float position = (float)p / d.rope_freq_scale;
+    for (uint32_t i = 0; i < half; i++) {
+      const float freq = 1.0f / std::pow(d.rope_freq_base, (float)(2 * i) / (float)d.head_dim);
+      const float theta = position * freq;
+      cs[((size_t)p * half + i) * 2] = std::cos(theta);
+      cs[((size_t)p * half + i) * 2 + 1] = std::sin(theta);
+    }
+  }
+}
+
 // one Linear with optional norm prologue / residual epilogue, any device type
 int linear_any(lgh_ctx* c, int cls, const DevWeight& W, const float* x, float* out, const float* norm_w,
                       const float* resid, const float* bias, int xq_next, const float* xq_next_nw) {
@@ -473,6 +488,15 @@ int ffn_forward(lgh_ctx* c, LayerW& Lw, const FfnView& v, const float* next_nw, 
          return moe_router_launch(v.hidden, Lw.ffn_norm, d.norm_eps, Lw.router, H, d.num_experts, topk, v.moe_sel, v.moe_w, c->stream);
        })))
     return rc;
+  return moe_experts_forward(c, Lw, v, next_nw, next_mfma);
+}
+
+// The expert half of MoeLayer::forward: the num_experts_per_token experts in v.moe_sel (device), weighted by v.moe_w, plus the residual.
+int moe_experts_forward(lgh_ctx* c, LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma) {
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size;
+  const uint32_t topk = d.num_experts_per_token;
+  int rc;
   if (!fused_type(Lw.gate_exps.type) || Lw.gate_exps.type != Lw.up_exps.type || !fused_type(Lw.down_exps.type) || topk > 8)
     return fail(c, LGH_UNSUPPORTED, "MoE needs fused-format experts and top-k <= 8");
   // The selected experts run two at a time (a launch carries up to four passes: gate and up of two experts).  Every group
@@ -1311,18 +1335,8 @@ int lgh_finalize(lgh_ctx* c) {
       !xq_get(c, c->act2, (uint32_t)ffn))
     return fail(c, LGH_ALLOCATION_FAILED, "XQ image allocation failed");
   {
-    // RoPE table in the reference's own arithmetic (ops.rs:1303-1313): libm powf / cosf / sinf on the host
-    const uint32_t half = d.head_dim / 2;
-    std::vector<float> cs((size_t)d.max_seq_len * half * 2);
-    for (uint32_t p = 0; p < d.max_seq_len; p++) {
-      const float position = (float)p / d.rope_freq_scale;
-      for (uint32_t i = 0; i < half; i++) {
-        const float freq = 1.0f / std::pow(d.rope_freq_base, (float)(2 * i) / (float)d.head_dim);
-        const float theta = position * freq;
-        cs[((size_t)p * half + i) * 2] = std::cos(theta);
-        cs[((size_t)p * half + i) * 2 + 1] = std::sin(theta);
-      }
-    }
+    std::vector<float> cs;
+    rope_table_host(d, cs);
     HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpy(c->rope_cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
   }
   HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));

@@ -801,4 +801,147 @@ int lgh_bench_hbm_read(int device, size_t bytes, int iters, double* gbps) {
   return LGH_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The engine's mat-vec launch assembly (launch_mv -> build_mv_group -> mvq_launch / mv_launch) one call site at a time, for
+// kernel-level tests (tests/test_gpu_matvec.py).  Test surface: not part of the inference API.
+// ------------------------------------------------------------------------------------------------
+static size_t weight_bytes(uint32_t type, size_t k, size_t n) {
+  const uint32_t be = blk_elems((int)type);
+  return be && k % be == 0 ? n * (k / be) * blk_bytes((int)type) : 0;
+}
+
+int lgh_op_qkv_rope(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                    float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
+                    float rope_base, float rope_scale, float* q_out, float* k_cache, float* v_cache) {
+  // layer_forward's fused QKV launch: RMSNorm prologue, Q with RoPE, K with RoPE into cache row `pos`, V into cache row `pos`
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!types || !w || !x || !norm_w || !q_out || !k_cache || !v_cache || hidden == 0 || head_dim == 0 || head_dim % 2 || n_kv_heads == 0 ||
+      n_heads % n_kv_heads || pos >= max_seq_len || max_seq_len > 0x7FFFFFFFu || rope_scale == 0.0f)
+    return LGH_INVALID_ARGUMENT;
+  lgh_model_desc& d = t.c->d;
+  d.norm_eps = eps;
+  d.hidden_size = (uint32_t)hidden;
+  d.head_dim = (uint32_t)head_dim;
+  d.num_heads = (uint32_t)n_heads;
+  d.num_kv_heads = (uint32_t)n_kv_heads;
+  d.max_seq_len = (uint32_t)max_seq_len;
+  d.rope_freq_base = rope_base;
+  d.rope_freq_scale = rope_scale;
+  const size_t rows[3] = {n_heads * head_dim, n_kv_heads * head_dim, n_kv_heads * head_dim};
+  DevWeight W[3];
+  int rc;
+  for (int s = 0; s < 3; s++) {
+    const size_t nb = weight_bytes(types[s], hidden, rows[s]);
+    if (!nb || !w[s]) return LGH_SHAPE_MISMATCH;
+    if ((rc = upload_matrix(t.c, W[s], (int)types[s], (uint32_t)hidden, (uint32_t)rows[s], 1, -1, w[s], nb))) return rc;
+    if (!fused_type(W[s].type)) return LGH_UNSUPPORTED;   // the engine runs such layers unfused
+  }
+  std::vector<float> cs;
+  rope_table_host(d, cs);
+  const size_t cache = n_kv_heads * max_seq_len * head_dim;
+  t.c->rope_cs = t.up(cs.data(), cs.size());
+  float *dx = t.up(x, hidden), *dnw = t.up(norm_w, hidden), *dq = t.up(nullptr, rows[0]), *dk = t.up(k_cache, cache), *dv = t.up(v_cache, cache);
+  float* db[3] = {nullptr, nullptr, nullptr};
+  for (int s = 0; s < 3; s++)
+    if (bias && bias[s] && !(db[s] = t.up(bias[s], rows[s]))) return LGH_ALLOCATION_FAILED;
+  if (!t.c->rope_cs || !dx || !dnw || !dq || !dk || !dv) return LGH_ALLOCATION_FAILED;
+  if ((rc = set_pos(t, pos))) return rc;
+  SegSpec sp[3];
+  sp[0].W[0] = &W[0]; sp[0].x[0] = dx; sp[0].epi = EPI_ROPE_Q; sp[0].out = dq; sp[0].bias = db[0];
+  sp[1].W[0] = &W[1]; sp[1].x[0] = dx; sp[1].epi = EPI_ROPE_K; sp[1].out = dk; sp[1].bias = db[1];
+  sp[2].W[0] = &W[2]; sp[2].x[0] = dx; sp[2].epi = EPI_V_CACHE; sp[2].out = dv; sp[2].bias = db[2];
+  if ((rc = launch_mv(t.c, LGH_K_QKV, sp, 3, dnw, (uint32_t)hidden))) return rc;
+  if ((rc = t.down(q_out, dq, rows[0])) || (rc = t.down(k_cache, dk, cache))) return rc;
+  return t.down(v_cache, dv, cache);
+}
+
+int lgh_op_linear_chain(int device, uint32_t type_a, const void* w_a, const void* w_a_up, const float* bias_a, size_t k, size_t n_a,
+                        const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
+                        uint32_t type_b, const void* w_b, size_t n_b, float* out_a, float* out_b, float* out_b_requant, int* image_used) {
+  // launch A (linear_any: STORE / RESID with bias; or the SWIGLU gate-up launch), asked to leave its output's XQ image; then launch B
+  // on A's output twice: first as the engine runs it (from A's image when A left one), then after marking the image stale
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w_a || !x || !w_b || !out_a || !out_b || !out_b_requant || xq_next < 0 || xq_next > 2 || (xq_next == 2 && !next_nw) ||
+      (w_a_up && (resid || bias_a)))
+    return LGH_INVALID_ARGUMENT;
+  t.c->d.norm_eps = eps;
+  const size_t nba = weight_bytes(type_a, k, n_a), nbb = weight_bytes(type_b, n_a, n_b);
+  if (!nba || !nbb) return LGH_SHAPE_MISMATCH;
+  DevWeight WA, WU, WB;
+  int rc;
+  if ((rc = upload_matrix(t.c, WA, (int)type_a, (uint32_t)k, (uint32_t)n_a, 1, -1, w_a, nba))) return rc;
+  if (w_a_up && (rc = upload_matrix(t.c, WU, (int)type_a, (uint32_t)k, (uint32_t)n_a, 1, -1, w_a_up, nba))) return rc;
+  if ((rc = upload_matrix(t.c, WB, (int)type_b, (uint32_t)n_a, (uint32_t)n_b, 1, -1, w_b, nbb))) return rc;
+  if (w_a_up && !fused_type(WA.type)) return LGH_UNSUPPORTED;
+  float *dx = t.up(x, k), *dnw = norm_w ? t.up(norm_w, k) : nullptr, *dres = resid ? t.up(resid, n_a) : nullptr;
+  float *dbias = bias_a ? t.up(bias_a, n_a) : nullptr, *dnext = next_nw ? t.up(next_nw, n_a) : nullptr;
+  float *da = t.up(nullptr, n_a), *db = t.up(nullptr, n_b), *db2 = t.up(nullptr, n_b);
+  if (!dx || (norm_w && !dnw) || (resid && !dres) || (bias_a && !dbias) || (next_nw && !dnext) || !da || !db || !db2) return LGH_ALLOCATION_FAILED;
+  XqBuf* qa = xq_get(t.c, da, (uint32_t)n_a);   // A's output has an image slot, as the engine's activation buffers do
+  if (!qa) return LGH_ALLOCATION_FAILED;
+  if (w_a_up) {
+    SegSpec sp;
+    sp.npass = 2;
+    sp.W[0] = &WA; sp.W[1] = &WU;
+    sp.x[0] = sp.x[1] = dx;
+    sp.epi = EPI_SWIGLU;
+    sp.out = da;
+    sp.xq_next = xq_next; sp.xq_next_nw = dnext;
+    if ((rc = launch_mv(t.c, LGH_K_GATEUP, &sp, 1, dnw, (uint32_t)k))) return rc;
+  } else if ((rc = linear_any(t.c, LGH_K_MISC, WA, dx, da, dnw, dres, dbias, xq_next, dnext))) {
+    return rc;
+  }
+  qa = xq_get(t.c, da, (uint32_t)n_a);   // (A's launch may have registered more images: look it up again)
+  if (image_used) *image_used = qa && qa->fresh ? 1 : 0;
+  const float* bnw = xq_next == 2 ? dnext : nullptr;
+  if ((rc = linear_any(t.c, LGH_K_MISC, WB, da, db, bnw, nullptr, nullptr))) return rc;
+  xq_stale(t.c, da);
+  if ((rc = linear_any(t.c, LGH_K_MISC, WB, da, db2, bnw, nullptr, nullptr))) return rc;
+  if ((rc = t.down(out_a, da, n_a)) || (rc = t.down(out_b, db, n_b))) return rc;
+  return t.down(out_b_requant, db2, n_b);
+}
+
+int lgh_op_moe_experts(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down,
+                       size_t n_experts, size_t hidden, size_t ffn, size_t top_k, const float* router, const int* sel, const float* sel_w,
+                       const float* x, const float* norm_w, float eps, float* out, int* sel_out, float* sel_w_out) {
+  // ffn_forward's MoE half on x (also the residual): with `router` the device router picks the experts, otherwise the given
+  // selection and weights drive the same expert launches
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w_gate || !w_up || !w_down || !x || !norm_w || !out || (!router && (!sel || !sel_w)) || top_k == 0 || top_k > 8 ||
+      top_k > n_experts || n_experts > 64)
+    return LGH_INVALID_ARGUMENT;
+  if (sel)
+    for (size_t i = 0; i < top_k; i++)
+      if (sel[i] < 0 || (size_t)sel[i] >= n_experts) return LGH_INVALID_ARGUMENT;
+  lgh_model_desc& d = t.c->d;
+  d.norm_eps = eps;
+  d.hidden_size = (uint32_t)hidden;
+  d.num_experts = (uint32_t)n_experts;
+  d.num_experts_per_token = (uint32_t)top_k;
+  const size_t ngu = weight_bytes(type_gate_up, hidden, ffn), nd = weight_bytes(type_down, ffn, hidden);
+  if (!ngu || !nd) return LGH_SHAPE_MISMATCH;
+  LayerW Lw;
+  const uint32_t E = (uint32_t)n_experts;
+  int rc;
+  if ((rc = upload_matrix(t.c, Lw.gate_exps, (int)type_gate_up, (uint32_t)hidden, (uint32_t)ffn, E, -1, w_gate, ngu * E)) ||
+      (rc = upload_matrix(t.c, Lw.up_exps, (int)type_gate_up, (uint32_t)hidden, (uint32_t)ffn, E, -1, w_up, ngu * E)) ||
+      (rc = upload_matrix(t.c, Lw.down_exps, (int)type_down, (uint32_t)ffn, (uint32_t)hidden, E, -1, w_down, nd * E)))
+    return rc;
+  Lw.ffn_norm = t.up(norm_w, hidden);
+  if (router) Lw.router = t.up(router, n_experts * hidden);
+  FfnView v{t.up(x, hidden), t.up(nullptr, ffn), t.up(nullptr, ffn), t.up(nullptr, hidden), nullptr, nullptr};
+  v.moe_sel = (int*)up_bytes(t, sel, top_k * 4);
+  v.moe_w = t.up(sel_w, top_k);
+  if (!Lw.ffn_norm || (router && !Lw.router) || !v.hidden || !v.act || !v.act2 || !v.xnorm || !v.moe_sel || !v.moe_w) return LGH_ALLOCATION_FAILED;
+  // the engine's activation buffers have XQ image slots (the residual stream, act, act2), the scratch running sum has none
+  if (!xq_get(t.c, v.hidden, (uint32_t)hidden) || !xq_get(t.c, v.act, (uint32_t)ffn) || !xq_get(t.c, v.act2, (uint32_t)ffn)) return LGH_ALLOCATION_FAILED;
+  if ((rc = router ? ffn_forward(t.c, Lw, v, nullptr, false) : moe_experts_forward(t.c, Lw, v, nullptr, false))) return rc;
+  if (sel_out && (rc = down_bytes(t, sel_out, v.moe_sel, top_k * 4))) return rc;
+  if (sel_w_out && (rc = t.down(sel_w_out, v.moe_w, top_k))) return rc;
+  return t.down(out, v.hidden, hidden);
+}
+
 }  // extern "C"

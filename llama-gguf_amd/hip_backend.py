@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "lgh_batch_create", "lgh_batch_reset", "lgh_batch_position", "lgh_batch_prefill", "lgh_forward_multi", "lgh_decode_greedy_multi",
     "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
     "lgh_op_attention_decode", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
+    "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -199,6 +200,10 @@ def load_library() -> C.CDLL:
         "lgh_op_attention_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_prefill": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
+        "lgh_op_qkv_rope": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, sz, sz, f32, f32, vp, vp, vp]),
+        "lgh_op_linear_chain": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, f32, vp, C.c_int, vp, u32, vp, sz, vp, vp, vp,
+                                          C.POINTER(C.c_int)]),
+        "lgh_op_moe_experts": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -678,6 +683,61 @@ def op_attention_decode(path: int, q, k_cache, v_cache, scale: float, pos: int, 
     _chk(load_library().lgh_op_attention_decode(device, path, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, out.ctypes.data, q.shape[0],
                                                 kc.shape[0], q.shape[1], kc.shape[1], scale, pos, n_splits), "attention_decode")
     return out
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def op_qkv_rope(types, ws, biases, x, norm_w, eps: float, head_dim: int, n_heads: int, n_kv: int, k_cache, v_cache, pos: int,
+                rope_base: float, rope_scale: float, device: int = 0):
+    """layer_forward's fused QKV launch (norm, Q / K / V with their own types, RoPE on Q and K, K and V into cache row `pos`).
+    ws: three native GGUF byte arrays; biases: three f32 vectors or None; caches [n_kv, max_seq, head_dim].
+    -> (q [n_heads * head_dim], k_cache, v_cache) after the call (copies; the inputs are untouched)."""
+    x, nw = _f32(x), _f32(norm_w)
+    kc, vc = np.array(k_cache, dtype=np.float32, copy=True), np.array(v_cache, dtype=np.float32, copy=True)
+    ws = [np.ascontiguousarray(w, dtype=np.uint8) for w in ws]
+    bs = [None if b is None else _f32(b) for b in biases]
+    tarr = np.array(types, dtype=np.uint32)
+    warr = (C.c_void_p * 3)(*[w.ctypes.data for w in ws])
+    barr = (C.c_void_p * 3)(*[_ptr(b) for b in bs])
+    q = np.empty(n_heads * head_dim, np.float32)
+    _chk(load_library().lgh_op_qkv_rope(device, tarr.ctypes.data, C.cast(warr, C.c_void_p), C.cast(barr, C.c_void_p), x.ctypes.data,
+                                        nw.ctypes.data, eps, x.size, head_dim, n_heads, n_kv, kc.shape[1], pos, rope_base, rope_scale,
+                                        q.ctypes.data, kc.ctypes.data, vc.ctypes.data), "qkv_rope")
+    return q, kc, vc
+
+
+def op_linear_chain(type_a: int, w_a, k: int, n_a: int, x, type_b: int, w_b, n_b: int, *, w_a_up=None, bias_a=None, norm_w=None,
+                    eps: float = 1e-5, resid=None, xq_next: int = 0, next_nw=None, device: int = 0):
+    """Launch A (STORE / RESID + bias, or SwiGLU with w_a_up) leaving its output's XQ image (xq_next 0 / 1 / 2), then launch B on
+    A's output from that image and again from a fresh conversion.  -> (out_a, out_b, out_b_requant, image_used)."""
+    x = _f32(x)
+    wa, wb = np.ascontiguousarray(w_a, dtype=np.uint8), np.ascontiguousarray(w_b, dtype=np.uint8)
+    wu = None if w_a_up is None else np.ascontiguousarray(w_a_up, dtype=np.uint8)
+    ba, nw, rs, nn = (None if v is None else _f32(v) for v in (bias_a, norm_w, resid, next_nw))
+    oa, ob, ob2 = np.empty(n_a, np.float32), np.empty(n_b, np.float32), np.empty(n_b, np.float32)
+    used = C.c_int(-1)
+    _chk(load_library().lgh_op_linear_chain(device, type_a, wa.ctypes.data, _ptr(wu), _ptr(ba), k, n_a, x.ctypes.data, _ptr(nw), eps,
+                                            _ptr(rs), xq_next, _ptr(nn), type_b, wb.ctypes.data, n_b, oa.ctypes.data, ob.ctypes.data,
+                                            ob2.ctypes.data, C.byref(used)), "linear_chain")
+    return oa, ob, ob2, bool(used.value)
+
+
+def op_moe_experts(type_gate_up: int, w_gate, w_up, type_down: int, w_down, n_experts: int, hidden: int, ffn: int, top_k: int, x,
+                   norm_w, eps: float, *, router=None, sel=None, sel_w=None, device: int = 0):
+    """ffn_forward's MoE half: x + sum_p w_p down_e(silu(gate_e x') up_e x'), with the device router (router [E, hidden] f32) or the
+    given selection (sel int32 / sel_w f32, top_k each).  -> (out [hidden], sel used, weights used)."""
+    x, nw = _f32(x), _f32(norm_w)
+    wg, wu, wd = (np.ascontiguousarray(w, dtype=np.uint8) for w in (w_gate, w_up, w_down))
+    r = None if router is None else _f32(router)
+    s = None if sel is None else np.ascontiguousarray(sel, dtype=np.int32)
+    sw = None if sel_w is None else _f32(sel_w)
+    out, so, swo = np.empty(hidden, np.float32), np.empty(top_k, np.int32), np.empty(top_k, np.float32)
+    _chk(load_library().lgh_op_moe_experts(device, type_gate_up, wg.ctypes.data, wu.ctypes.data, type_down, wd.ctypes.data, n_experts,
+                                           hidden, ffn, top_k, _ptr(r), _ptr(s), _ptr(sw), x.ctypes.data, nw.ctypes.data, eps,
+                                           out.ctypes.data, so.ctypes.data, swo.ctypes.data), "moe_experts")
+    return out, so, swo
 
 
 def op_attention_kv8(kv_cache_type: int, q, k_bytes, v_bytes, k_scale, v_scale, k_new, v_new, scale: float, pos: int, n_splits: int = 8,

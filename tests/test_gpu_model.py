@@ -479,6 +479,7 @@ def test_generic_attention_shapes_and_top_k_follow_the_oracle(pkg, orc):
     kernels.rs:1395-1458) run the one-workgroup-per-head kernel; MoE layers with more than two selected experts run them two
     at a time (moe.rs:321-413).  Qwen2-7B's 7 query heads per kv head, head_dim 96, top-3 and top-4 routing."""
     cases = [("test-dense", "Q8_0", dict(num_heads=14, num_kv_heads=2, head_dim=64, hidden_size=896)),           # G = 7, k % 256 != 0
+             ("test-dense", "Q4_0", dict(num_heads=14, num_kv_heads=2, head_dim=64, hidden_size=896)),           # Q4_0 on mv_kernel
              ("test-dense", "Q4_K_M", dict(num_heads=8, num_kv_heads=4, head_dim=96, hidden_size=768, intermediate_size=1536)),   # head_dim 96
              ("test-dense", "Q4_K_M", dict(num_heads=6, num_kv_heads=2, head_dim=128, hidden_size=768, intermediate_size=1536)),  # G = 3
              ("test-moe", "Q4_K_M", dict(num_experts=6, num_experts_per_token=3)),
