@@ -287,17 +287,17 @@ int lgh_forward_multi(lgh_ctx* ctx, const uint32_t* slots, const uint32_t* token
  * synchronisation at the end (the bench's timed region for --batch). */
 int lgh_decode_greedy_multi(lgh_ctx* ctx, const uint32_t* slots, const uint32_t* first_tokens, uint32_t n_seq, size_t n_steps, uint32_t* tokens_out);
 
-/* ---- sampling on the device: Sampler::sample (src/sampling/mod.rs:188-304, the non-mirostat path) inside the per-token
+/* ---- sampling on the device: Sampler::sample and sample_mirostat (src/sampling/mod.rs:188-387) inside the per-token
  * graph, so that the reference's default generation settings (EngineConfig::default, src/engine.rs:117-130) stay on the
  * graph-replayed decode loop.  Steps as the reference does them, all in f32: repetition penalty once per occurrence in the
  * window (x > 0: x /= p, else x *= p), frequency then presence penalty for every token this sampler emitted, x *= 1.0f / T,
  * softmax, greedy (T == 0 or top_k == 1: the LAST index of the maximal probability; no draw, not counted), stable sort by
  * probability, top-k, top-p (a cutoff at position 0 truncates nothing), renormalize, draw (first r < cumulative sum, else the
- * last kept token), count.  The random draws are INPUTS: uniforms[i] is what the reference's `self.rng.gen::<f32>()` returns at
+ * last kept token), count.  min-p and Mirostat come with lgh_sampler_config_ex below.  The random draws are INPUTS: uniforms[i] is what the reference's `self.rng.gen::<f32>()` returns at
  * step i, so a host that draws them from its own StdRng gets the reference's tokens.  Single-stage contexts
  * only; bad configs (non-finite or negative temperature, top_p outside (0, 1], repeat_penalty <= 0, non-finite penalties)
  * and sampling without a prior set_sampler answer LGH_INVALID_ARGUMENT. ---- */
-typedef struct lgh_sampler_config {   /* SamplerConfig (sampling/mod.rs:37-62) minus seed / min_p / typical_p / mirostat */
+typedef struct lgh_sampler_config {   /* SamplerConfig (sampling/mod.rs:37-62) minus seed / typical_p; min_p and mirostat: lgh_sampler_config_ex */
   float temperature;
   uint32_t top_k;                     /* 0: no top-k truncation */
   float top_p;
@@ -324,6 +324,36 @@ int lgh_batch_set_sampler(lgh_ctx* ctx, uint32_t slot, const lgh_sampler_config*
 int lgh_decode_sample_multi(lgh_ctx* ctx, const uint32_t* slots, const uint32_t* first_tokens, uint32_t n_seq,
                             const uint32_t* histories, const size_t* history_lens, size_t n_steps, const float* uniforms,
                             uint32_t* tokens_out);
+
+/* SamplerConfig's remaining fields that Sampler::sample reads (typical_p is stored but never read; the seed stays with the
+ * host's rng).  lgh_set_sampler(cfg) is lgh_set_sampler_ex with min_p 0 and mirostat 0.
+ *   min_p (mod.rs:248-258): after the stable sort and before top-k the order is cut at the first probability below
+ *     p[order[0]] * min_p (never to nothing); top-k then compares against the cut length, and top-p's cutoff-0 quirk keeps the
+ *     min-p set.  Ignored under a greedy config (the greedy return comes first).
+ *   mirostat (MirostatConfig, mod.rs:15-34; sample_mirostat 304-387; mod.rs:210-213): after the penalties, and INSTEAD of the
+ *     temperature, the greedy test, min-p, top-k and top-p: softmax, stable descending sort; v2 keeps the ranks before the
+ *     first whose -log2(p) exceeds mu (at least one), v1 keeps clamp((2^mu * vocab) as usize, 1, vocab) = all of them (mu >= 0,
+ *     see below); r = uniform * sum of the kept, unnormalized; the first token whose cumulative sum exceeds r, else the TOP
+ *     token; mu -= eta * (-log2(p_token) - tau), clamped to [0, 20]; the token is always counted.  Every step needs its
+ *     uniform, whatever temperature and top_k say.
+ * InvalidArgument: struct_size != sizeof, min_p outside [0, 1] or not finite, mirostat > 2, tau or eta not finite, tau < 0 (a
+ * narrowing of the reference, which takes any f32: with tau >= 0, mu starts at 2 * tau >= 0 and stays in [0, 20], which is
+ * what makes v1's candidate count the whole vocabulary). */
+typedef struct lgh_sampler_config_ex {
+  uint32_t struct_size;               /* sizeof(lgh_sampler_config_ex) */
+  lgh_sampler_config base;
+  float min_p;                        /* 0: off */
+  uint32_t mirostat;                  /* 0: off, 1, 2 (MirostatConfig::version) */
+  float mirostat_tau, mirostat_eta;   /* MirostatConfig::tau, eta (default 5.0, 0.1) */
+} lgh_sampler_config_ex;
+/* Sampler::new (mod.rs:150-169): the config, zeroed counts and mirostat_mu = 2 * tau.  Counts and mu persist across decode
+ * calls until the next set_sampler; within one call, steps after the step that sampled eos_token update neither. */
+int lgh_set_sampler_ex(lgh_ctx* ctx, const lgh_sampler_config_ex* config);
+/* lgh_set_sampler_ex for one slot (src/engine_batched.rs:358, 397); slots may mix Mirostat and ordinary samplers in one step */
+int lgh_batch_set_sampler_ex(lgh_ctx* ctx, uint32_t slot, const lgh_sampler_config_ex* config);
+/* Sampler::mirostat_mu (mod.rs:144-145) of the context's own sampler (slot -1) or of a batch slot, after the steps enqueued so
+ * far (synchronises).  10.0 when Mirostat is off, as Sampler::new leaves it (mod.rs:161). */
+int lgh_get_sampler_mu(lgh_ctx* ctx, int slot, float* mu);
 
 const char* lgh_last_error(const lgh_ctx* ctx);
 int lgh_get_stats(lgh_ctx* ctx, lgh_stats* out);
@@ -433,6 +463,10 @@ int lgh_op_kv_roundtrip(int device, uint32_t kv_cache_type, const float* row, si
  * `uniform` = the draw (ignored under a greedy config). */
 int lgh_op_sample(int device, const float* logits, size_t vocab, const lgh_sampler_config* config, const uint32_t* recent,
                   size_t n_recent, const uint32_t* counts, float uniform, uint32_t* token_out);
+/* lgh_op_sample with min-p / Mirostat (sampling/mod.rs:248-258, 304-387): mu_in = the sampler's mirostat_mu before the call
+ * (in [0, 20] under Mirostat, else InvalidArgument; ignored when Mirostat is off), *mu_out = after it (may be NULL). */
+int lgh_op_sample_ex(int device, const float* logits, size_t vocab, const lgh_sampler_config_ex* config, const uint32_t* recent,
+                     size_t n_recent, const uint32_t* counts, float uniform, float mu_in, uint32_t* token_out, float* mu_out);
 int lgh_op_silu(int device, const float* x, float* out, size_t n);
 int lgh_op_gelu(int device, const float* x, float* out, size_t n);
 int lgh_op_softmax(int device, const float* x, float* out, size_t rows, size_t last_dim);

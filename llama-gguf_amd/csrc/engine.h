@@ -77,7 +77,7 @@ struct BatchScratch {
   std::vector<size_t> pos;                            // per slot: tokens in its cache
   hipGraphExec_t graph[kMaxBatch + 1][3] = {};        // [n_seq][0 logits only, 1 + arg-max fed back, 2 + sampled token fed back]
   SampBufs samp;                                      // one sampler per slot (lgh_batch_set_sampler)
-  std::vector<lgh_sampler_config> samp_cfg;
+  std::vector<lgh_sampler_config_ex> samp_cfg;
   std::vector<uint8_t> samp_set;
 };
 
@@ -126,7 +126,7 @@ struct lgh_ctx {
   std::vector<float> tq_qjl_host;
   float* kv_shift_tmp = nullptr;               // scratch of lgh_kv_shift_left (one cache tensor), allocated at first use
   lgh::SampBufs samp;                          // single-stage contexts: the sampler of lgh_set_sampler / lgh_decode_sample
-  lgh_sampler_config samp_cfg{};
+  lgh_sampler_config_ex samp_cfg{};
   bool samp_set = false;
 };
 
@@ -184,13 +184,16 @@ int drain_prof(lgh_ctx* c);
 // sampler plumbing (sample.hip)
 int samp_alloc(lgh_ctx* c, lgh::SampBufs& B, uint32_t n_slots, uint32_t n_rows);
 int samp_check(lgh_ctx* c, const lgh_sampler_config* cfg);
-int samp_reset(lgh_ctx* c, lgh::SampBufs& B, uint32_t slot);   // zero the slot's counts
+int samp_check_ex(lgh_ctx* c, const lgh_sampler_config_ex* cfg);
+lgh_sampler_config_ex samp_plain(const lgh_sampler_config& cfg);   // cfg with min_p 0 and Mirostat off
+int samp_reset(lgh_ctx* c, lgh::SampBufs& B, uint32_t slot, const lgh_sampler_config_ex& cfg);   // Sampler::new: zero the slot's counts, mu = 2 * tau
+int samp_mu(lgh_ctx* c, lgh::SampBufs& B, uint32_t slot, float* mu);   // the slot's mirostat_mu (synchronises)
 // before the first step of a decode call: the slot's config, window, leaving tokens and draws (synchronises)
-int samp_begin(lgh_ctx* c, lgh::SampBufs& B, uint32_t slot, const lgh_sampler_config& cfg, const uint32_t* hist, size_t n_hist,
+int samp_begin(lgh_ctx* c, lgh::SampBufs& B, uint32_t slot, const lgh_sampler_config_ex& cfg, const uint32_t* hist, size_t n_hist,
                uint32_t first, size_t n_steps, const float* uni, size_t uni_stride);
 int samp_warm(lgh_ctx* c, lgh::SampBufs& B, const float* logits, uint32_t n_seq);   // eager launch of the sampling kernels (before any capture)
-int samp_one(lgh_ctx* c, lgh::SampBufs& B, const lgh_sampler_config& cfg, const uint32_t* recent, size_t n_recent, const uint32_t* counts,
-             float uniform, const float* d_logits, uint32_t* token_out);   // lgh_op_sample
+int samp_one(lgh_ctx* c, lgh::SampBufs& B, const lgh_sampler_config_ex& cfg, const uint32_t* recent, size_t n_recent, const uint32_t* counts,
+             float uniform, float mu_in, const float* d_logits, uint32_t* token_out, float* mu_out);   // lgh_op_sample(_ex)
 
 // ------------------------------------------------------------------------------------------------
 // launch recording (profiling mode: hipEvent pair per launch, on the launch stream)

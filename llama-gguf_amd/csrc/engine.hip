@@ -1558,15 +1558,35 @@ int lgh_decode_greedy(lgh_ctx* c, uint32_t first_token, size_t n_steps, uint32_t
   return LGH_OK;
 }
 
-int lgh_set_sampler(lgh_ctx* c, const lgh_sampler_config* cfg) {
+int lgh_set_sampler_ex(lgh_ctx* c, const lgh_sampler_config_ex* cfg) {
   int rc = check_ready(c);
   if (rc) return rc;
   if (!c->samp.ctl) return fail(c, LGH_INVALID_ARGUMENT, "sampling needs a single-stage context");
-  if ((rc = samp_check(c, cfg))) return rc;
-  if ((rc = samp_reset(c, c->samp, 0))) return rc;
+  if ((rc = samp_check_ex(c, cfg))) return rc;
+  if ((rc = samp_reset(c, c->samp, 0, *cfg))) return rc;
   c->samp_cfg = *cfg;
   c->samp_set = true;
   return LGH_OK;
+}
+
+int lgh_set_sampler(lgh_ctx* c, const lgh_sampler_config* cfg) {
+  if (!cfg) return lgh_set_sampler_ex(c, nullptr);   // (refused there, after the context's own checks)
+  const lgh_sampler_config_ex x = samp_plain(*cfg);
+  return lgh_set_sampler_ex(c, &x);
+}
+
+int lgh_get_sampler_mu(lgh_ctx* c, int slot, float* mu) {
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (!mu) return fail(c, LGH_INVALID_ARGUMENT, "mu is NULL");
+  if (slot < 0) {
+    if (!c->samp.ctl || !c->samp_set) return fail(c, LGH_INVALID_ARGUMENT, "lgh_set_sampler has not been called");
+    return samp_mu(c, c->samp, 0, mu);
+  }
+  BatchScratch& Bs = c->batch;
+  if (!Bs.ready || (uint32_t)slot >= Bs.max_batch || (size_t)slot >= Bs.samp_set.size() || !Bs.samp_set[slot])
+    return fail(c, LGH_INVALID_ARGUMENT, "no sampler in that slot");
+  return samp_mu(c, Bs.samp, (uint32_t)slot, mu);
 }
 
 int lgh_decode_sample(lgh_ctx* c, uint32_t first_token, const uint32_t* history, size_t n_history, size_t n_steps, const float* uniforms,
@@ -1577,7 +1597,7 @@ int lgh_decode_sample(lgh_ctx* c, uint32_t first_token, const uint32_t* history,
   if (!c->samp_set) return fail(c, LGH_INVALID_ARGUMENT, "lgh_set_sampler has not been called");
   if (n_steps && !tokens_out) return fail(c, LGH_INVALID_ARGUMENT, "tokens_out is NULL");
   if (n_history && !history) return fail(c, LGH_INVALID_ARGUMENT, "history is NULL");
-  const bool greedy = c->samp_cfg.temperature == 0.0f || c->samp_cfg.top_k == 1;
+  const bool greedy = !c->samp_cfg.mirostat && (c->samp_cfg.base.temperature == 0.0f || c->samp_cfg.base.top_k == 1);
   if (n_steps && !uniforms && !greedy) return fail(c, LGH_INVALID_ARGUMENT, "uniforms is NULL");
   if (c->pos + n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "decode would exceed max_seq_len");
   if (n_steps == 0) return LGH_OK;

@@ -508,7 +508,7 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
   Bs.pos.assign(max_batch, 0);
   // the slots' samplers (allocated before the context counts as ready: the sampler entry points index these per slot)
   if ((rc = samp_alloc(c, Bs.samp, max_batch, max_batch))) return rc;
-  Bs.samp_cfg.assign(max_batch, lgh_sampler_config{});
+  Bs.samp_cfg.assign(max_batch, lgh_sampler_config_ex{});
   Bs.samp_set.assign(max_batch, 0);
   Bs.ready = true;
   // one step through every kernel of the path, eagerly, before any of them is first launched inside a capture (engine.hip:
@@ -587,16 +587,22 @@ int lgh_decode_greedy_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* f
   return LGH_OK;
 }
 
-int lgh_batch_set_sampler(lgh_ctx* c, uint32_t slot, const lgh_sampler_config* cfg) {
+int lgh_batch_set_sampler_ex(lgh_ctx* c, uint32_t slot, const lgh_sampler_config_ex* cfg) {
   int rc = check_batch(c);
   if (rc) return rc;
   BatchScratch& Bs = c->batch;
   if (!Bs.ready || slot >= Bs.max_batch || slot >= Bs.samp_set.size()) return fail(c, LGH_INVALID_ARGUMENT, "no such slot");
-  if ((rc = samp_check(c, cfg))) return rc;
-  if ((rc = samp_reset(c, Bs.samp, slot))) return rc;
+  if ((rc = samp_check_ex(c, cfg))) return rc;
+  if ((rc = samp_reset(c, Bs.samp, slot, *cfg))) return rc;
   Bs.samp_cfg[slot] = *cfg;
   Bs.samp_set[slot] = 1;
   return LGH_OK;
+}
+
+int lgh_batch_set_sampler(lgh_ctx* c, uint32_t slot, const lgh_sampler_config* cfg) {
+  if (!cfg) return lgh_batch_set_sampler_ex(c, slot, nullptr);   // (refused there, after the context's and the slot's checks)
+  const lgh_sampler_config_ex x = samp_plain(*cfg);
+  return lgh_batch_set_sampler_ex(c, slot, &x);
 }
 
 int lgh_decode_sample_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* first_tokens, uint32_t n_seq, const uint32_t* histories,
@@ -615,8 +621,8 @@ int lgh_decode_sample_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* f
     if (slots[i] >= Bs.max_batch) return fail(c, LGH_INVALID_ARGUMENT, "slot numbers must be distinct and below max_batch");
     if (!Bs.samp_set[slots[i]]) return fail(c, LGH_INVALID_ARGUMENT, "slot " + std::to_string(slots[i]) + ": lgh_batch_set_sampler has not been called");
     if (Bs.pos[slots[i]] + n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "the steps would run past max_seq_len");
-    const lgh_sampler_config& g = Bs.samp_cfg[slots[i]];
-    if (n_steps && !uniforms && !(g.temperature == 0.0f || g.top_k == 1)) return fail(c, LGH_INVALID_ARGUMENT, "uniforms is NULL");
+    const lgh_sampler_config_ex& g = Bs.samp_cfg[slots[i]];
+    if (n_steps && !uniforms && (g.mirostat || !(g.base.temperature == 0.0f || g.base.top_k == 1))) return fail(c, LGH_INVALID_ARGUMENT, "uniforms is NULL");
     const size_t n = history_lens ? history_lens[i] : 0;
     if (n && !histories) return fail(c, LGH_INVALID_ARGUMENT, "histories is NULL");
     hist_off[i] = off;

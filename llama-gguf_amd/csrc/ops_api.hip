@@ -230,20 +230,28 @@ int lgh_op_silu_mul(int device, const float* gate, const float* up, float* out, 
 }
 
 // ---- Sampler::sample (sampling/mod.rs:188-304) through the kernels of lgh_decode_sample ----
-int lgh_op_sample(int device, const float* logits, size_t vocab, const lgh_sampler_config* config, const uint32_t* recent, size_t n_recent,
-                  const uint32_t* counts, float uniform, uint32_t* token_out) {
+int lgh_op_sample_ex(int device, const float* logits, size_t vocab, const lgh_sampler_config_ex* config, const uint32_t* recent,
+                     size_t n_recent, const uint32_t* counts, float uniform, float mu_in, uint32_t* token_out, float* mu_out) {
   Tmp t(device);
   if (t.rc) return t.rc;
   if (!logits || !token_out || vocab == 0 || vocab > 0x7FFFFFFFu || (n_recent && !recent)) return LGH_INVALID_ARGUMENT;
-  int rc = samp_check(t.c, config);
+  int rc = samp_check_ex(t.c, config);
   if (rc) return rc;
+  if (config->mirostat && !(mu_in >= 0.0f && mu_in <= 20.0f)) return LGH_INVALID_ARGUMENT;   // what the reference's clamp keeps mu in
   t.c->d.vocab_size = (uint32_t)vocab;
   t.c->d.max_seq_len = 1;
   SampBufs B;
   if ((rc = samp_alloc(t.c, B, 1, 1))) return rc;
   const float* dl = t.up(logits, vocab);
   if (!dl) return LGH_ALLOCATION_FAILED;
-  return samp_one(t.c, B, *config, recent, n_recent, counts, uniform, dl, token_out);
+  return samp_one(t.c, B, *config, recent, n_recent, counts, uniform, mu_in, dl, token_out, mu_out);
+}
+
+int lgh_op_sample(int device, const float* logits, size_t vocab, const lgh_sampler_config* config, const uint32_t* recent, size_t n_recent,
+                  const uint32_t* counts, float uniform, uint32_t* token_out) {
+  if (!config) return LGH_INVALID_ARGUMENT;
+  const lgh_sampler_config_ex x = samp_plain(*config);
+  return lgh_op_sample_ex(device, logits, vocab, &x, recent, n_recent, counts, uniform, 0.0f, token_out, nullptr);
 }
 
 // ---- Backend::add / mul / scale / silu / gelu / softmax / matmul / matvec / matvec_q / attention (backend/mod.rs:29-265) ----

@@ -2,13 +2,15 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdint>
 
 namespace lgh {
 
 // One sequence's sampler, device-resident so that a captured graph keeps working when the config changes.  The config half
-// is Sampler::new's (sampling/mod.rs:37-62, non-mirostat fields); the call half describes the repetition window of the
-// current decode call (the host writes it before the first step, the merge kernel advances it).
+// is Sampler::new's (sampling/mod.rs:37-62, 150-169); the call half describes the repetition window of the current decode
+// call (the host writes it before the first step, the merge kernel advances it).  Under Mirostat the host stores temp 1,
+// top_k 0, top_p 1 and min_p 0: sample_mirostat (mod.rs:210-213) returns before any of them is read.
 struct SampSeq {
   float temp, inv_t, top_p, rp, fp, pp;   // inv_t = 1.0f / temp in f32, as the reference computes it
   uint32_t top_k, window;                 // window 0 = every token so far
@@ -21,7 +23,14 @@ struct SampSeq {
   // S[j] is tk[j] for j < lv_h and tk[j - lv_g] for j >= L0 (lv_g = L0 - lv_h; no leaving index falls in between).
   int32_t lv_a, lv_h, lv_g;
   int32_t track;                          // 1: append the token and update the counters (decode); 0: a one-off sample
+  float min_p;                            // 0: off; ignored under a greedy config (mod.rs:248-258 come after the greedy return)
+  int32_t miro;                           // 0: off, 1 / 2: MirostatConfig::version
+  float tau, eta;
+  // Sampler::mirostat_mu, the one field a decode call does not rewrite: set_sampler stores 2 * tau, the merge kernel updates
+  // it after every Mirostat step, and the host's per-call upload ends before it.  Keep it last.
+  float mu;
 };
+constexpr size_t kSampSeqCallBytes = offsetof(SampSeq, mu);   // what a decode call uploads
 
 constexpr int kSampParts = 64;   // partial-pass workgroups per sequence
 constexpr int kSampK = 64;       // candidates per workgroup and after the merge

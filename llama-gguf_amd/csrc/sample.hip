@@ -1,19 +1,25 @@
-// sample.hip — Sampler::sample (src/sampling/mod.rs:188-304, non-mirostat path) on the device, inside the per-token graph.
+// sample.hip — Sampler::sample and sample_mirostat (src/sampling/mod.rs:188-387) on the device, inside the per-token graph.
 //
 // Two launches per step, the sequence as the grid's second dimension (merge: first):
 //   samp_partial  kSampParts workgroups per sequence.  Each applies the penalties and the temperature to a contiguous slice of
 //                 the vocabulary and leaves the slice's max, its exp-sum relative to that max, and its kSampK best candidates
 //                 by (value desc, index asc), sorted.
 //   samp_merge    one workgroup per sequence.  Global max and sum (the sum as a fixed tree, not the reference's sequential
-//                 loop), the kSampK best candidates of all slices, their probabilities sorted by (probability desc, index
-//                 asc) — the reference's stable sort — and the truncation and draw scans as sequential f32 sums, as the
-//                 reference does them.  Then the token is written, appended to the window and counted.
+//                 loop; under Mirostat, where the sum's rounding reaches mu, that sequential loop), the kSampK best
+//                 candidates of all slices, their probabilities sorted by (probability desc, index asc) — the reference's
+//                 stable sort — and the truncation and draw scans as sequential f32 sums, as the reference does them.  Then
+//                 the token is written, appended to the window and counted.
 // The candidates are a prefix of the reference's sorted order as long as their probabilities stay above the smallest one
 // among them.  When the top-k / top-p cut or the draw falls past that prefix — with top_k 0 or > kSampK that is every step
 // that keeps everything (top_p 1, or a top token alone above top_p: cutoff 0) and every flat one — the merge workgroup
 // walks the sorted order in bands instead: a radix select on the probability bits finds the next
 // <= kBandCap values, they are sorted in LDS and scanned in order; the chosen position is mapped back to its index (ties:
 // ascending index).  Exact, but not fast.
+//
+// min-p (mod.rs:248-258) cuts the sorted order at the first probability below p[order[0]] * min_p, before top-k; Mirostat
+// (mod.rs:304-387) skips the temperature and every truncation but its own, draws against the unnormalized sum and keeps mu
+// in the sequence's SampSeq.  Both are settled by the candidates as soon as one valid candidate lies past the cut (below the
+// threshold / with a surprise above mu); a cut further out, and every Mirostat v1 step, takes the band walk.
 #include "engine.h"
 
 #include <algorithm>
@@ -24,6 +30,7 @@ namespace lgh {
 namespace {
 
 constexpr int kBandCap = 4096;
+constexpr int kSeqChunk = kBandCap / 2;   // terms per half of the band buffer in Mirostat's sequential softmax sum
 typedef unsigned long long u64;
 
 __device__ __forceinline__ uint32_t f2o(float f) {   // float -> unsigned key of the same order
@@ -81,7 +88,7 @@ __device__ __forceinline__ float penalize(float x, uint32_t i, const SampSeq& c,
       x -= c.pp;
     }
   }
-  if (c.temp > 0.0f && c.temp != 1.0f) x *= c.inv_t;
+  if (c.miro == 0 && c.temp > 0.0f && c.temp != 1.0f) x *= c.inv_t;   // (sample_mirostat runs before the temperature)
   return x;
 }
 
@@ -137,11 +144,11 @@ struct MergeLds {
   u64 lists[16][64];
   float cp[64];
   int ci[64];
-  uint32_t band[kBandCap];
+  alignas(16) uint32_t band[kBandCap];
   int hist[256];
   int scan[1024];
   u64 last;
-  float gmax, gsum, r;
+  float gmax, gsum, r, psel;
   int mode, tok, done, kind, count, fin, k, nsel, cnt;
   uint32_t lo, val, prefix, mask, res_val, res_rank;
 };
@@ -246,6 +253,43 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
     L.lists[w][lane] = top;
   }
   __syncthreads();
+  // ---- Mirostat: the reference's own denominator.  The reference sums exp(x - max) in f32 in vocabulary order on every path
+  // (mod.rs:225-229 as well as sample_mirostat's 311-316), which on spiked logits rounds a large vocabulary's tail away (1.5e-4
+  // relative at 32 000 tokens).  The other configurations keep the accurate tree sum above: there the denominator only moves a
+  // decision that already sits on a boundary.  Under Mirostat mu moves by eta * log2(p_selected) at every step, so the
+  // probability's rounding is part of the sampler's state, and the tree sum would leave mu that far from the reference's.
+  // Waves 1..15 fill one half of L.band (free until the band walk) with the next kSeqChunk terms while thread 0 adds the other
+  // half in order; the padding past the vocabulary is +0, which changes no sum.
+  if (c.miro) {
+    float* buf = (float*)L.band;
+    const float gmax = L.gmax;
+    const uint32_t nch = (vocab + kSeqChunk - 1) / kSeqChunk;
+    float acc = 0.0f;
+    for (uint32_t ch = 0; ch <= nch; ch++) {
+      if (w > 0) {
+        if (ch < nch) {
+          float* dst = buf + (ch & 1u) * kSeqChunk;
+          for (uint32_t j = tid - 64; j < (uint32_t)kSeqChunk; j += blockDim.x - 64) {
+            const uint32_t i = ch * kSeqChunk + j;
+            dst[j] = i < vocab ? expf(penalize(x[i], i, c, wc, sc) - gmax) : 0.0f;
+          }
+        }
+      } else if (tid == 0 && ch > 0) {
+        const float4* src = (const float4*)(buf + ((ch - 1) & 1u) * kSeqChunk);
+#pragma unroll 4
+        for (int j = 0; j < kSeqChunk / 4; j++) {
+          const float4 v = src[j];
+          acc += v.x;
+          acc += v.y;
+          acc += v.z;
+          acc += v.w;
+        }
+      }
+      __syncthreads();
+    }
+    if (tid == 0) L.gsum = acc;
+    __syncthreads();
+  }
   if (w == 0) {
     u64 t = L.lists[0][lane];
     for (int o = 1; o < 16; o++) t = merge64(t, L.lists[o][lane]);
@@ -261,6 +305,8 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
   __syncthreads();
   // ---- the decision, when the candidates settle it
   const uint32_t nk0 = (c.top_k > 0 && c.top_k < vocab) ? c.top_k : vocab;   // top-k truncation (mod.rs:260-263)
+  // min-p (mod.rs:248-258): the order ends before the first probability below this (0: never; cp[0] is the largest of all)
+  const float thr = c.min_p > 0.0f && !c.greedy ? L.cp[0] * c.min_p : 0.0f;
   if (tid == 0) {
     const uint32_t ncand = min(vocab, (uint32_t)kSampK);
     L.r = c.greedy ? 0.0f : B.uni[(size_t)slot * B.uni_cap + min((uint32_t)c.step, B.uni_cap - 1)];
@@ -271,7 +317,30 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
       while (V < (uint32_t)kSampK && L.cp[V] > L.cp[kSampK - 1]) V++;
     }
     int mode = 0, tok = 0;
-    if (c.greedy) {   // the LAST index of the maximal probability (max_by, mod.rs:235-243)
+    float psel = 0.0f;
+    if (c.miro) {   // sample_mirostat (mod.rs:304-387)
+      // v2: the first rank whose surprise exceeds mu, at least 1.  v1: n = clamp((2^mu * vocab) as usize, 1, vocab) with
+      // mu in [0, 20] (it starts at 2 * tau with tau >= 0 and is clamped after every update), so 2^mu >= 1 and n == vocab:
+      // no truncation.
+      int trunc = -1;
+      if (c.miro == 2)
+        for (uint32_t j = 0; j < V; j++)
+          if (-log2f(L.cp[j]) > c.mu) { trunc = (int)max(j, 1u); break; }
+      if (trunc < 0 && vocab <= (uint32_t)kSampK) trunc = (int)vocab;   // (every candidate is valid: V == vocab)
+      if (trunc < 0) mode = 1;
+      else {   // the draw against the unnormalized sum; nobody above r: the TOP token (mod.rs:363-373)
+        float fsum = 0.0f, cum2 = 0.0f;
+        for (int j = 0; j < trunc; j++) fsum += L.cp[j];
+        const float rf = L.r * fsum;
+        int k = 0;
+        for (int j = 0; j < trunc; j++) {
+          cum2 += L.cp[j];
+          if (cum2 > rf) { k = j; break; }
+        }
+        tok = L.ci[k];
+        psel = L.cp[k];
+      }
+    } else if (c.greedy) {   // the LAST index of the maximal probability (max_by, mod.rs:235-243)
       if (vocab > (uint32_t)kSampK && L.cp[kSampK - 1] == L.cp[0]) mode = 2;
       else {
         tok = L.ci[0];
@@ -279,10 +348,16 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
           if (L.cp[j] == L.cp[0]) tok = max(tok, L.ci[j]);
       }
     } else {
+      // min-p, settled when a valid candidate is below the threshold: the order is exactly the candidates before it, and top-k
+      // compares against that length
+      uint32_t nkc = nk0;
+      if (thr > 0.0f)
+        for (uint32_t j = 1; j < V; j++)
+          if (L.cp[j] < thr) { nkc = min(nkc, j); break; }
       int nk = -1;
       float cum = 0.0f, sk = 0.0f;
       bool crossed = false;
-      const uint32_t lim = min(nk0, V);
+      const uint32_t lim = min(nkc, V);
       for (uint32_t j = 0; j < lim; j++) {   // top-p (mod.rs:266-277): the first position whose cumulative sum exceeds top_p
         cum += L.cp[j];
         if (c.top_p < 1.0f && !crossed && cum > c.top_p) {
@@ -290,11 +365,11 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
           if (j > 0) { nk = (int)j + 1; sk = cum; break; }   // cutoff 0 keeps everything (reference quirk)
         }
       }
-      if (nk < 0 && nk0 <= V) { nk = (int)nk0; sk = cum; }
+      if (nk < 0 && nkc <= V) { nk = (int)nkc; sk = cum; }
       // nothing is truncated inside the prefix (a cutoff at 0, or top_p 1): the kept sum is the whole order's, which the prefix
       // already settles when every later probability (<= cp[V]) is below half an ulp of it; the draw must then land inside
       bool inside = nk >= 0;
-      if (nk < 0 && L.cp[V] < half_ulp(cum)) { nk = (int)nk0; sk = cum; }
+      if (nk < 0 && L.cp[V] < half_ulp(cum)) { nk = (int)nkc; sk = cum; }
       if (nk < 0) mode = 1;
       else {   // renormalize and draw (mod.rs:279-303)
         tok = L.ci[min(nk, (int)V) - 1];
@@ -309,6 +384,7 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
     }
     L.mode = mode;
     L.tok = tok;
+    L.psel = psel;
   }
   __syncthreads();
   // ---- general path: the whole vocabulary's probabilities, walked in sorted order
@@ -330,8 +406,10 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
     } else {
       // thread 0's scan state; phase 0 finds the kept count nk and their sum sk, phase 1 the drawn position
       uint32_t pos = 0, nk = 0, prev = 0, gstart = 0, last_val = 0, last_rank = 0;
-      float cum = 0.0f, sk = 0.0f, hu = 0.0f;
+      float cum = 0.0f, sk = 0.0f, hu = 0.0f, rf = 0.0f;
+      const uint32_t top_val = __float_as_uint(L.cp[0]);   // the first of the order: the smallest index with the largest probability
       bool crossed = false;
+      const bool cut = thr > 0.0f || c.miro == 2;   // a min-p or v2 cut to look for: chosen once, the other walks skip the tests
       for (int phase = 0; phase < 2; phase++) {
         if (tid == 0) { L.last = 1ull << 32; L.done = 0; pos = 0; cum = 0.0f; prev = 0xFFFFFFFFu; }
         __syncthreads();
@@ -346,7 +424,14 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
               if (phase == 0) {
                 // the sum cannot change any more (hu: half an ulp of the sum as it was up to 64 elements ago, never above today's)
                 if ((pos & 63) == 0) hu = half_ulp(cum);
-                if (p < hu) { nk = nk0; sk = cum; L.done = 1; break; }
+                if (p < hu && thr == 0.0f) { nk = nk0; sk = cum; L.done = 1; break; }   // (under min-p the walk needs the cut itself: it ends the kept set)
+                if (cut) {
+                  if (p < thr) { nk = pos; sk = cum; L.done = 1; break; }   // min-p: the order ends here (pos > 0: thr <= cp[0])
+                  if (c.miro == 2 && -log2f(p) > c.mu) {                    // Mirostat v2: truncate at max(rank, 1)
+                    if (pos == 0) { cum = p; pos = 1; }
+                    nk = pos; sk = cum; L.done = 1; break;
+                  }
+                }
                 cum += p;
                 if (c.top_p < 1.0f && !crossed && cum > c.top_p) {
                   crossed = true;
@@ -358,10 +443,19 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
                 if (bits != prev) { prev = bits; gstart = pos; }
                 last_val = bits;
                 last_rank = pos - gstart;
-                cum += p / sk;
-                if (L.r < cum) { L.res_val = bits; L.res_rank = last_rank; L.done = 1; }
+                if (c.miro) {   // unnormalized, against r * fsum; nobody above it: the top token
+                  cum += p;
+                  if (cum > rf) { L.res_val = bits; L.res_rank = last_rank; L.done = 1; }
+                } else {
+                  cum += p / sk;
+                  if (L.r < cum) { L.res_val = bits; L.res_rank = last_rank; L.done = 1; }
+                }
                 pos++;
-                if (!L.done && pos == nk) { L.res_val = last_val; L.res_rank = last_rank; L.done = 1; }
+                if (!L.done && pos == nk) {
+                  L.res_val = c.miro ? top_val : last_val;
+                  L.res_rank = c.miro ? 0u : last_rank;
+                  L.done = 1;
+                }
               }
             }
             L.last = L.kind == 1 ? L.lo : L.val;
@@ -371,12 +465,14 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
         }
         if (tid == 0 && !L.done) {   // (the order ran out: only with non-finite values)
           if (phase == 0) { nk = pos; sk = cum; }
-          else { L.res_val = last_val; L.res_rank = last_rank; }
+          else { L.res_val = c.miro ? top_val : last_val; L.res_rank = c.miro ? 0u : last_rank; }
         }
+        if (tid == 0 && phase == 0) rf = L.r * sk;
         __syncthreads();
       }
       // position -> index: the res_rank-th smallest index whose probability has the bits res_val
       const uint32_t v = L.res_val, rank = L.res_rank;
+      if (tid == 0) L.psel = __uint_as_float(v);
       const uint32_t per = (vocab + blockDim.x - 1) / blockDim.x;
       const uint32_t a0 = min(vocab, tid * per), a1 = min(vocab, a0 + per);
       int cnt = 0;
@@ -426,6 +522,11 @@ __global__ void __launch_bounds__(1024) samp_merge(const float* __restrict__ log
         }
       }
       cs->step = nxt;
+    }
+    if (c.miro && !c.eos_done) {   // mod.rs:377-383, from the selected token's probability; frozen after eos like the counts
+      float mu = c.mu - c.eta * (-log2f(L.psel) - c.tau);
+      mu = mu < 0.0f ? 0.0f : mu > 20.0f ? 20.0f : mu;
+      B.ctl[slot].mu = mu;
     }
   }
 }
@@ -503,32 +604,72 @@ int samp_check(lgh_ctx* c, const lgh_sampler_config* s) {
   return LGH_OK;
 }
 
-int samp_reset(lgh_ctx* c, SampBufs& B, uint32_t slot) {
+int samp_check_ex(lgh_ctx* c, const lgh_sampler_config_ex* s) {
+  if (!s) return fail(c, LGH_INVALID_ARGUMENT, "sampler config is NULL");
+  if (s->struct_size != sizeof(lgh_sampler_config_ex)) return fail(c, LGH_INVALID_ARGUMENT, "lgh_sampler_config_ex.struct_size mismatch");
+  const int rc = samp_check(c, &s->base);
+  if (rc) return rc;
+  if (!(s->min_p >= 0.0f && s->min_p <= 1.0f)) return fail(c, LGH_INVALID_ARGUMENT, "min_p must be in [0, 1]");
+  if (s->mirostat > 2) return fail(c, LGH_INVALID_ARGUMENT, "mirostat must be 0, 1 or 2");
+  if (!std::isfinite(s->mirostat_tau) || !std::isfinite(s->mirostat_eta) || s->mirostat_tau < 0.0f)
+    return fail(c, LGH_INVALID_ARGUMENT, "mirostat_tau must be finite and >= 0, mirostat_eta finite");
+  return LGH_OK;
+}
+
+lgh_sampler_config_ex samp_plain(const lgh_sampler_config& s) {
+  lgh_sampler_config_ex x{};
+  x.struct_size = sizeof(x);
+  x.base = s;
+  return x;
+}
+
+// Sampler::new's mirostat_mu (mod.rs:156-161)
+static float mu_start(const lgh_sampler_config_ex& s) { return s.mirostat ? s.mirostat_tau * 2.0f : 10.0f; }
+
+int samp_reset(lgh_ctx* c, SampBufs& B, uint32_t slot, const lgh_sampler_config_ex& cfg) {
+  const float mu = mu_start(cfg);
   HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemsetAsync(B.scnt + (size_t)slot * B.vocab, 0, (size_t)B.vocab * 4, c->stream));
+  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(&B.ctl[slot].mu, &mu, 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
   return LGH_OK;
 }
 
-static SampSeq seq_of(const lgh_sampler_config& s) {
+int samp_mu(lgh_ctx* c, SampBufs& B, uint32_t slot, float* mu) {
+  HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpy(mu, &B.ctl[slot].mu, 4, hipMemcpyDeviceToHost));
+  return LGH_OK;
+}
+
+static SampSeq seq_of(const lgh_sampler_config_ex& x) {
+  lgh_sampler_config s = x.base;
   SampSeq q{};
-  q.temp = s.temperature;
-  q.inv_t = s.temperature > 0.0f ? 1.0f / s.temperature : 0.0f;
-  q.top_p = s.top_p;
   q.rp = s.repeat_penalty;
   q.fp = s.frequency_penalty;
   q.pp = s.presence_penalty;
-  q.top_k = s.top_k;
   q.window = s.repeat_window;
   q.eos = s.eos_token;
-  q.greedy = s.temperature == 0.0f || s.top_k == 1;
   q.lv_a = INT_MIN / 2;
+  q.mu = mu_start(x);
+  if (x.mirostat) {   // sample_mirostat returns before the temperature, the greedy test, min-p, top-k and top-p (mod.rs:210-213)
+    q.temp = q.inv_t = q.top_p = 1.0f;
+    q.miro = (int32_t)x.mirostat;
+    q.tau = x.mirostat_tau;
+    q.eta = x.mirostat_eta;
+    return q;
+  }
+  q.min_p = x.min_p;
+  q.temp = s.temperature;
+  q.inv_t = s.temperature > 0.0f ? 1.0f / s.temperature : 0.0f;
+  q.top_p = s.top_p;
+  q.top_k = s.top_k;
+  q.greedy = s.temperature == 0.0f || s.top_k == 1;
   return q;
 }
 
-int samp_begin(lgh_ctx* c, SampBufs& B, uint32_t slot, const lgh_sampler_config& cfg, const uint32_t* hist, size_t n_hist, uint32_t first,
+int samp_begin(lgh_ctx* c, SampBufs& B, uint32_t slot, const lgh_sampler_config_ex& cfg, const uint32_t* hist, size_t n_hist, uint32_t first,
                size_t n_steps, const float* uni, size_t uni_stride) {
   if (n_steps > B.uni_cap || n_steps + 1 > B.tk_cap / 2) return fail(c, LGH_INVALID_ARGUMENT, "too many steps");
-  const size_t W = cfg.repeat_window;
+  const size_t W = cfg.base.repeat_window;
   const size_t L0 = W ? std::min(n_hist, W) : n_hist;   // the window's history tokens
   const uint32_t* hw = hist + (n_hist - L0);
   SampSeq q = seq_of(cfg);
@@ -560,7 +701,8 @@ int samp_begin(lgh_ctx* c, SampBufs& B, uint32_t slot, const lgh_sampler_config&
   if (uni && !q.greedy)
     for (size_t i = 0; i < n_steps; i++) u[i] = uni[i * uni_stride];
   HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));   // the previous call's steps are done with these buffers
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.ctl + slot, &q, sizeof(q), hipMemcpyHostToDevice, c->stream));
+  // (everything but mu, which carries over from the previous call)
+  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.ctl + slot, &q, kSampSeqCallBytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.tk + (size_t)slot * B.tk_cap, tk.data(), tk.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.uni + (size_t)slot * B.uni_cap, u.data(), u.size() * 4, hipMemcpyHostToDevice, c->stream));
   if (!pairs.empty())
@@ -575,7 +717,7 @@ int samp_begin(lgh_ctx* c, SampBufs& B, uint32_t slot, const lgh_sampler_config&
 int samp_warm(lgh_ctx* c, SampBufs& B, const float* logits, uint32_t n_seq) {
   lgh_sampler_config g{};
   g.temperature = 0.0f; g.top_k = 1; g.top_p = 1.0f; g.repeat_penalty = 1.0f; g.eos_token = -1;
-  const SampSeq q = seq_of(g);
+  const SampSeq q = seq_of(samp_plain(g));
   std::vector<SampSeq> qs(B.n_slots, q);
   std::vector<int> slots(n_seq);
   for (uint32_t i = 0; i < n_seq; i++) slots[i] = (int)(i % B.n_slots);
@@ -590,11 +732,12 @@ int samp_warm(lgh_ctx* c, SampBufs& B, const float* logits, uint32_t n_seq) {
 }
 
 // One Sampler::sample call on device logits (lgh_op_sample): the window is the end of `recent`, counts[vocab] (or zero) the
-// sampled counts; nothing is tracked.
-int samp_one(lgh_ctx* c, SampBufs& B, const lgh_sampler_config& cfg, const uint32_t* recent, size_t n_recent, const uint32_t* counts,
-             float uniform, const float* d_logits, uint32_t* token_out) {
+// sampled counts, mu_in the sampler's mirostat_mu; nothing is tracked, *mu_out (when non-NULL) is mu after the step.
+int samp_one(lgh_ctx* c, SampBufs& B, const lgh_sampler_config_ex& cfg, const uint32_t* recent, size_t n_recent, const uint32_t* counts,
+             float uniform, float mu_in, const float* d_logits, uint32_t* token_out, float* mu_out) {
   SampSeq q = seq_of(cfg);
-  const size_t W = cfg.repeat_window, n = W ? std::min(W, n_recent) : n_recent;
+  q.mu = mu_in;
+  const size_t W = cfg.base.repeat_window, n = W ? std::min(W, n_recent) : n_recent;
   std::vector<uint32_t> win(recent + (n_recent - n), recent + n_recent);
   std::sort(win.begin(), win.end());
   std::vector<int> pairs;
@@ -614,6 +757,7 @@ int samp_one(lgh_ctx* c, SampBufs& B, const lgh_sampler_config& cfg, const uint3
   HIP_TRYS(c, LGH_OPERATION_FAILED, sample_launch(B, d_logits, B.vocab, 1, nullptr, nullptr, nullptr, d_tok, c->stream));
   int tok = 0;
   HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(&tok, d_tok, 4, hipMemcpyDeviceToHost, c->stream));
+  if (mu_out) HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(mu_out, &B.ctl[0].mu, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
   *token_out = (uint32_t)tok;
   return LGH_OK;

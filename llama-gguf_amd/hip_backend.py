@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     "lgh_set_kv_rotation_signs", "lgh_op_tq_compress", "lgh_set_kv_qjl_matrices", "lgh_op_tq_compress_qjl",
     "lgh_batch_create", "lgh_batch_reset", "lgh_batch_position", "lgh_batch_prefill", "lgh_forward_multi", "lgh_decode_greedy_multi",
     "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
+    "lgh_set_sampler_ex", "lgh_batch_set_sampler_ex", "lgh_get_sampler_mu", "lgh_op_sample_ex",
     "lgh_op_attention_decode", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
     "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts",
 )
@@ -93,10 +94,16 @@ class GgufValue(C.Structure):
 
 
 class SamplerConfig(C.Structure):
-    """lgh_sampler_config: SamplerConfig (src/sampling/mod.rs:37-62) minus seed / min_p / typical_p / mirostat."""
+    """lgh_sampler_config: SamplerConfig (src/sampling/mod.rs:37-62) minus seed / typical_p; min_p and mirostat: SamplerConfigEx."""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_uint32), ("top_p", C.c_float), ("repeat_penalty", C.c_float),
                 ("repeat_window", C.c_uint32), ("frequency_penalty", C.c_float), ("presence_penalty", C.c_float),
                 ("eos_token", C.c_int32)]
+
+
+class SamplerConfigEx(C.Structure):
+    """lgh_sampler_config_ex: lgh_sampler_config plus min_p (mod.rs:248-258) and MirostatConfig (mod.rs:15-34)."""
+    _fields_ = [("struct_size", C.c_uint32), ("base", SamplerConfig), ("min_p", C.c_float), ("mirostat", C.c_uint32),
+                ("mirostat_tau", C.c_float), ("mirostat_eta", C.c_float)]
 
 
 # SamplerConfig presets of the reference (sampling/mod.rs:64-122) and EngineConfig::default's settings (src/engine.rs:117-130)
@@ -105,6 +112,10 @@ SAMPLER_PRESETS = {
     "sampler_default": dict(temperature=0.8, top_k=40, top_p=0.95, repeat_penalty=1.1, repeat_window=64),
     "greedy": dict(temperature=0.0, top_k=1, top_p=1.0, repeat_penalty=1.0, repeat_window=0),
     "creative": dict(temperature=1.0, top_k=0, top_p=0.9, repeat_penalty=1.2, repeat_window=64),
+    # SamplerConfig::creative as the reference has it, min_p included (sampling/mod.rs:100-114)
+    "creative_ref": dict(temperature=1.0, top_k=0, top_p=0.9, repeat_penalty=1.2, repeat_window=64, min_p=0.05),
+    # SamplerConfig::mirostat_v2(5.0, 0.1) (sampling/mod.rs:116-135; MirostatConfig::default's tau and eta)
+    "mirostat_v2": dict(temperature=1.0, top_k=0, top_p=1.0, repeat_penalty=1.0, repeat_window=0, mirostat=2, tau=5.0, eta=0.1),
 }
 
 
@@ -113,6 +124,19 @@ def sampler_config(temperature: float = 0.8, top_k: int = 40, top_p: float = 0.9
                    eos_token: int = -1) -> SamplerConfig:
     """An lgh_sampler_config; the defaults are SamplerConfig::default's (sampling/mod.rs:64-80)."""
     return SamplerConfig(temperature, top_k, top_p, repeat_penalty, repeat_window, frequency_penalty, presence_penalty, eos_token)
+
+
+_EX_KEYS = ("min_p", "mirostat", "tau", "eta")
+
+
+def sampler_config_ex(min_p: float = 0.0, mirostat: int = 0, tau: float = 5.0, eta: float = 0.1, **cfg) -> SamplerConfigEx:
+    """An lgh_sampler_config_ex: `sampler_config`'s keywords plus min_p and mirostat (0 off, 1, 2) with tau / eta, whose defaults
+    are MirostatConfig::default's (sampling/mod.rs:26-34)."""
+    return SamplerConfigEx(C.sizeof(SamplerConfigEx), sampler_config(**cfg), min_p, mirostat, tau, eta)
+
+
+def _is_ex(cfg) -> bool:
+    return any(k in cfg for k in _EX_KEYS)
 
 
 class Stats(C.Structure):
@@ -196,6 +220,10 @@ def load_library() -> C.CDLL:
         "lgh_batch_set_sampler": (C.c_int, [vp, u32, C.POINTER(SamplerConfig)]),
         "lgh_decode_sample_multi": (C.c_int, [vp, vp, vp, u32, vp, vp, sz, vp, vp]),
         "lgh_op_sample": (C.c_int, [C.c_int, vp, sz, C.POINTER(SamplerConfig), vp, sz, vp, f32, C.POINTER(u32)]),
+        "lgh_set_sampler_ex": (C.c_int, [vp, C.POINTER(SamplerConfigEx)]),
+        "lgh_batch_set_sampler_ex": (C.c_int, [vp, u32, C.POINTER(SamplerConfigEx)]),
+        "lgh_get_sampler_mu": (C.c_int, [vp, C.c_int, C.POINTER(f32)]),
+        "lgh_op_sample_ex": (C.c_int, [C.c_int, vp, sz, C.POINTER(SamplerConfigEx), vp, sz, vp, f32, f32, C.POINTER(u32), C.POINTER(f32)]),
         "lgh_op_attention_decode": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
@@ -378,8 +406,18 @@ class HipGpuInference:
 
     # -- sampling on the device (Sampler::sample, src/sampling/mod.rs:188-304; include/llama_gguf_hip.h lgh_set_sampler)
     def set_sampler(self, **cfg) -> None:
-        """Sampler::new: the config (keyword arguments of `sampler_config`) and zeroed counts."""
-        self._call(load_library().lgh_set_sampler(self._h, C.byref(sampler_config(**cfg))))
+        """Sampler::new: the config (keyword arguments of `sampler_config`, or of `sampler_config_ex` when min_p / mirostat / tau /
+        eta is among them), zeroed counts and mu = 2 * tau."""
+        if _is_ex(cfg):
+            self._call(load_library().lgh_set_sampler_ex(self._h, C.byref(sampler_config_ex(**cfg))))
+        else:
+            self._call(load_library().lgh_set_sampler(self._h, C.byref(sampler_config(**cfg))))
+
+    def sampler_mu(self, slot: int = -1) -> float:
+        """Sampler::mirostat_mu of the context's sampler (slot -1) or of a batch slot."""
+        mu = C.c_float()
+        self._call(load_library().lgh_get_sampler_mu(self._h, slot, C.byref(mu)))
+        return mu.value
 
     def decode_sample(self, first_token: int, history: Sequence[int], n_steps: int, uniforms=None) -> np.ndarray:
         """n_steps sampled tokens fed back on the device; history = the context's tokens before first_token, uniforms[n_steps] =
@@ -394,7 +432,10 @@ class HipGpuInference:
         return out
 
     def batch_set_sampler(self, slot: int, **cfg) -> None:
-        self._call(load_library().lgh_batch_set_sampler(self._h, slot, C.byref(sampler_config(**cfg))))
+        if _is_ex(cfg):
+            self._call(load_library().lgh_batch_set_sampler_ex(self._h, slot, C.byref(sampler_config_ex(**cfg))))
+        else:
+            self._call(load_library().lgh_batch_set_sampler(self._h, slot, C.byref(sampler_config(**cfg))))
 
     def decode_sample_multi(self, slots: Sequence[int], first_tokens: Sequence[int], histories: Sequence[Sequence[int]], n_steps: int,
                             uniforms=None) -> np.ndarray:
@@ -818,14 +859,25 @@ def op_tq_compress_qjl(x, bits: int, signs, qjl_matrix, device: int = 0):
     return codes, qb, float(norm.value)
 
 
-def op_sample(logits, recent: Sequence[int] = (), counts=None, uniform: float = 0.0, device: int = 0, **cfg) -> int:
-    """One Sampler::sample call on the device (lgh_op_sample); cfg: keyword arguments of `sampler_config`."""
+def op_sample(logits, recent: Sequence[int] = (), counts=None, uniform: float = 0.0, device: int = 0, mu: Optional[float] = None,
+              **cfg):
+    """One Sampler::sample call on the device (lgh_op_sample); cfg: keyword arguments of `sampler_config`.  With min_p / mirostat /
+    tau / eta among them it goes through lgh_op_sample_ex; under Mirostat `mu` is the sampler's mirostat_mu before the call
+    (default 2 * tau, as Sampler::new sets it) and the result is (token, mu after the call)."""
     lg = _f32(logits)
     rc = np.ascontiguousarray(recent, dtype=np.uint32)
     cn = np.ascontiguousarray(counts, dtype=np.uint32) if counts is not None else None
     if cn is not None:
         assert cn.size == lg.size
     tok = C.c_uint32()
+    if _is_ex(cfg) or mu is not None:
+        ex = sampler_config_ex(**cfg)
+        mu_in = float(mu) if mu is not None else 2.0 * ex.mirostat_tau
+        mu_out = C.c_float()
+        _chk(load_library().lgh_op_sample_ex(device, lg.ctypes.data, lg.size, C.byref(ex), rc.ctypes.data if rc.size else None, rc.size,
+                                             cn.ctypes.data if cn is not None else None, float(uniform), mu_in, C.byref(tok),
+                                             C.byref(mu_out)), "lgh_op_sample_ex")
+        return (tok.value, mu_out.value) if ex.mirostat else tok.value
     _chk(load_library().lgh_op_sample(device, lg.ctypes.data, lg.size, C.byref(sampler_config(**cfg)),
                                       rc.ctypes.data if rc.size else None, rc.size, cn.ctypes.data if cn is not None else None,
                                       float(uniform), C.byref(tok)), "lgh_op_sample")

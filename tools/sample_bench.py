@@ -5,7 +5,9 @@ timed repetitions of a K-step decode after an N-token prompt.
 
   decode_greedy                  lgh_decode_greedy (the arg-max graph; bench.py's headline path)
   decode_sample engine_default   lgh_decode_sample with EngineConfig::default's settings (T 0.7, top-k 40, top-p 0.95, rp 1.1)
-  decode_sample creative         ... with SamplerConfig::creative (T 1.0, top-k 0, top-p 0.9, rp 1.2)
+  decode_sample creative         ... with SamplerConfig::creative (T 1.0, top-k 0, top-p 0.9, rp 1.2) without its min_p
+  decode_sample creative_ref     ... with SamplerConfig::creative as the reference has it (min_p 0.05)
+  decode_sample mirostat_v2      ... with SamplerConfig::mirostat_v2(5.0, 0.1)
   forward + host sampler         lgh_forward (full logits to the host) + the numpy restatement of Sampler::sample
                                  (tests/sampler_ref.py) on the host: the path a host with a sampling config has without this
   multi B greedy / sample        lgh_decode_greedy_multi / lgh_decode_sample_multi with B sequences (aggregate tokens/s)
@@ -24,7 +26,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as graft  # noqa: E402
-from sampler_ref import PRESETS, Sampler  # noqa: E402
+from sampler_ref import Sampler  # noqa: E402
+from sampler_ref_ex import PRESETS_EX as PRESETS  # noqa: E402
 
 
 def timed(reps, prepare, run):
@@ -74,13 +77,14 @@ def main():
 
     fresh()()
     eng.decode_greedy(prompt[-1], 8)   # graphs captured outside the timed regions
-    for preset in ("engine_default", "creative"):
+    decode_presets = ("engine_default", "creative", "creative_ref", "mirostat_v2")
+    for preset in decode_presets:
         fresh(preset)()
         eng.decode_sample(prompt[-1], prompt[:-1], 8, unis)
     m, b = timed(a.reps, fresh(), lambda: eng.decode_greedy(prompt[-1], K))
     emit("decode_greedy", m, b, K)
     greedy_ms = 1e3 * m / K
-    for preset in ("engine_default", "creative"):
+    for preset in decode_presets:
         m, b = timed(a.reps, fresh(preset), lambda: eng.decode_sample(prompt[-1], prompt[:-1], K, unis))
         emit(f"decode_sample {preset}", m, b, K, dict(extra_us_per_token=1e3 * (1e3 * m / K - greedy_ms)))
 
@@ -126,6 +130,8 @@ def main():
     p0 = min(float(Sampler(cfg.vocab_size, **PRESETS["creative"]).probs(x, []).max()) for x in peaked)
     hb = pkg.hip_backend
     for name, conf in (("engine_default", PRESETS["engine_default"]), ("creative", PRESETS["creative"]),
+                       ("creative_ref", PRESETS["creative_ref"]), ("mirostat_v2", PRESETS["mirostat_v2"]),
+                       ("mirostat_v1", dict(PRESETS["mirostat_v2"], mirostat=1)),
                        ("top_k 0 top_p 1", dict(temperature=1.0, top_k=0, top_p=1.0, repeat_penalty=1.0, repeat_window=0))):
         hb.op_sample(peaked[0], uniform=0.5, **conf)
         ts = []
