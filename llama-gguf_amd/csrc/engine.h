@@ -1,6 +1,7 @@
 // engine.h — the GPU-resident decode engine behind the lgh_* C ABI (internal).
 #pragma once
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -111,6 +112,8 @@ struct lgh_ctx {
   std::string err;
   hipGraphExec_t graph[lgh::MODE_COUNT][2] = {};   // [mode][attention variant: 0 split + combine, 1 single launch (short context)]
   bool attn_direct = false;                        // variant of the token being enqueued (chosen by the host-side position)
+  bool attn_generic = false;                       // the shape has no split kernel: every token runs attn_decode_any_kernel (a field, not
+                                                   // re-derived from the shape, so that lgh_op_attention_decode can run that kernel on any shape)
   uint32_t direct_attn_max_kv = 0;                 // contexts up to this many rows take the single-launch attention
   uint64_t graph_nodes = 0;
   // accounting
@@ -130,8 +133,18 @@ struct lgh_ctx {
   bool samp_set = false;
 };
 
-// ---- helpers shared by engine.hip and ops_api.hip ----
+// ---- what crosses the engine's files: engine_launch.hip (uploads, mat-vec launch assembly, XQ registry), engine_layer.hip (the
+// per-layer decode sequence), engine_prefill.hip (the batched prompt driver), engine.hip / engine_batch.hip / sample.hip /
+// ops_api.hip (the C ABI) ----
 #include <cstring>
+
+int fail(lgh_ctx* c, int status, const std::string& msg);
+#define HIP_TRY(c, status, expr)                                                                      \
+  do {                                                                                                \
+    hipError_t e__ = (expr);                                                                          \
+    if (e__ != hipSuccess)                                                                            \
+      return fail((c), (status), std::string(#expr) + ": " + hipGetErrorString(e__));                 \
+  } while (0)
 
 struct LayoutInfo {
   int dev_type;
@@ -158,34 +171,58 @@ struct SegSpec {
 
 // the vectors the FFN half of a layer works on (one sequence's)
 struct FfnView { float* hidden; float* act; float* act2; float* xnorm; int* moe_sel; float* moe_w; };
+// ... and the attention half: kv_tmp = the current token's K row | V row, f32 (unfused QKV, and the byte caches, whose attention launch
+// quantizes and stores them; nothing else reads it, so a caller with fused f32-cache launches only may pass nullptr)
+struct AttnView { float* hidden; float* q; float* kv_tmp; float* attn_out; };
+struct AllocSpec { void** p; size_t n; };
 
 static inline bool kv_is_tq(uint32_t t) { return t == LGH_KV_TQ2 || t == LGH_KV_TQ3 || t == LGH_KV_TQ2_QJL || t == LGH_KV_TQ3_QJL; }
 static inline bool kv_is_qjl(uint32_t t) { return t == LGH_KV_TQ2_QJL || t == LGH_KV_TQ3_QJL; }
 static inline int kv_tq_bits(uint32_t t) { return t == LGH_KV_TQ2 || t == LGH_KV_TQ2_QJL ? 2 : 3; }
-int fail(lgh_ctx* c, int status, const std::string& msg);
 int build_mv_group(lgh_ctx* c, const SegSpec* specs, int nseg, const float* norm_w, uint32_t k, bool mfma, lgh::MvLaunch& L, uint32_t& wg,
                    uint32_t& threads, uint64_t& alg, uint32_t tile_cap);
+int qkv_forward(lgh_ctx* c, lgh::LayerW& Lw, const AttnView& v);   // norm -> q, k, v -> RoPE -> cache write (or kv_tmp, byte caches)
+// attention over layer li's cache into v.attn_out, by the context's path (cache type, attn_generic, attn_direct, n_splits); xq_out: also
+// leave attn_out's XQ image, where the path's last launch can write one
+int attention_forward(lgh_ctx* c, lgh::LayerW& Lw, uint32_t li, const AttnView& v, float scale, bool xq_out);
 int ffn_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma);
 int moe_experts_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma);   // given v.moe_sel / v.moe_w
 void rope_table_host(const lgh_model_desc& d, std::vector<float>& cs);
 int engine_shape_check(const lgh_model_desc& d, std::string& why);   // LGH_OK, or the status lgh_create returns and why
 int dev_alloc(lgh_ctx* c, void** p, size_t bytes);
+// every buffer of the table with a size, in order: allocated, zeroed on the context's stream, added to `counter`
+int alloc_zeroed(lgh_ctx* c, const AllocSpec* bufs, size_t count, uint64_t& counter);
 LayoutInfo layout_for(int src_type);
 bool fused_type(int t);
 int upload_matrix(lgh_ctx* c, lgh::DevWeight& W, int src_type, uint32_t k, uint32_t n, uint32_t n_stack, int slot,
                   const void* host, size_t nbytes);
 int upload_f32(lgh_ctx* c, float** dst, int src_type, uint64_t n, const void* host, size_t nbytes);
 int launch_mv(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float* norm_w, uint32_t k);
+// matrix-core segments in formats without a common instantiation (Q4_K with Q5_K, Q8_0 / Q4_0 with anything else): one launch each
+bool mv_formats_split(const SegSpec* specs, int nseg);
 lgh::XqBuf* xq_get(lgh_ctx* c, const float* f32, uint32_t k);   // finds or registers (allocating) the image of a buffer
+lgh::XqBuf* xq_find(lgh_ctx* c, const float* f32);              // the image registered under exactly this address, or nullptr
 void xq_stale(lgh_ctx* c, const float* f32);
 int linear_any(lgh_ctx* c, int cls, const lgh::DevWeight& W, const float* x, float* out, const float* norm_w,
                const float* resid, const float* bias, int xq_next = 0, const float* xq_next_nw = nullptr);
 int drain_prof(lgh_ctx* c);
+int check_ready(lgh_ctx* c);   // what every entry point on a finalized context starts with: LGH_OK and the device bound, or the status
+// captures what `enqueue` puts on the context's stream and instantiates it into *exec; n_nodes: the graph's node count
+int capture_graph(lgh_ctx* c, hipGraphExec_t* exec, const std::function<int()>& enqueue, size_t* n_nodes = nullptr);
+int enqueue_token(lgh_ctx* c, int mode);   // everything one token needs, in stream order (eager or under capture)
+// batched prompt path (engine_prefill.hip).  The sequence a block of prompt tokens belongs to: the position of the block's first token,
+// and whose K / V rows it fills — the context's own (slot < 0: layers[li].kcache / vcache) or a slot's of the multi-sequence engine
+struct PfTarget { size_t pos0; int slot; };
+bool pf_eligible(const lgh_ctx* c);
+int pf_ensure(lgh_ctx* c);
+int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_t m);
+int prefill_own(lgh_ctx* c, const uint32_t* tokens, size_t n);   // the context's own sequence: blocks of <= 128, position and ST_NEXT moved
 // sampler plumbing (sample.hip)
 int samp_alloc(lgh_ctx* c, lgh::SampBufs& B, uint32_t n_slots, uint32_t n_rows);
 int samp_check(lgh_ctx* c, const lgh_sampler_config* cfg);
 int samp_check_ex(lgh_ctx* c, const lgh_sampler_config_ex* cfg);
 lgh_sampler_config_ex samp_plain(const lgh_sampler_config& cfg);   // cfg with min_p 0 and Mirostat off
+bool samp_needs_uniforms(const lgh_sampler_config_ex& cfg);        // anything but the greedy settings draws
 int samp_reset(lgh_ctx* c, lgh::SampBufs& B, uint32_t slot, const lgh_sampler_config_ex& cfg);   // Sampler::new: zero the slot's counts, mu = 2 * tau
 int samp_mu(lgh_ctx* c, lgh::SampBufs& B, uint32_t slot, float* mu);   // the slot's mirostat_mu (synchronises)
 // before the first step of a decode call: the slot's config, window, leaving tokens and draws (synchronises)

@@ -24,12 +24,6 @@
 
 using namespace lgh;
 
-#define HIP_TRYB(c, status, expr)                                                                 \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail((c), (status), std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 namespace lgh {
 
 __global__ void batch_advance_kernel(int* pos, int n) {
@@ -43,7 +37,7 @@ namespace {
 uint32_t xq_stride_of(uint32_t k) { return (uint32_t)xq_bytes(k); }
 uint32_t ssq_stride_of(uint32_t k) { return k / 16 + 64; }
 
-// sequence-0 view of a batch vector is registered in the context's XQ registry under its f32 address (engine.hip: xq_get), the
+// sequence-0 view of a batch vector is registered in the context's XQ registry under its f32 address (engine_launch.hip: xq_get), the
 // other sequences' views follow at the strides above: build_mv_group finds the images it needs there
 int register_views(lgh_ctx* c, float* f32, uint8_t* xq, float* ssq, uint32_t k, uint32_t n) {
   for (uint32_t s = 0; s < n; s++) {
@@ -57,18 +51,18 @@ int register_views(lgh_ctx* c, float* f32, uint8_t* xq, float* ssq, uint32_t k, 
   return LGH_OK;
 }
 
-XqBuf* view_of(lgh_ctx* c, const float* f32) {
-  for (auto& q : c->xqs)
-    if (q.f32 == f32) return &q;
-  return nullptr;
+// a launch left the images of n vectors of k floats from `base` on, multiplied with the norm weights `tag` (nullptr: none)
+void mark_fresh(lgh_ctx* c, const float* base, uint32_t k, uint32_t n, const float* tag) {
+  for (uint32_t s = 0; s < n; s++)
+    if (XqBuf* q = xq_find(c, base + (size_t)s * k)) { q->fresh = true; q->tag = tag; }
 }
 
 // after a batched launch produced / consumed the images of sequence 0's view, the other sequences' views are in the same state
 void spread_state(lgh_ctx* c, const float* f32, uint32_t k, uint32_t n) {
-  XqBuf* q0 = view_of(c, f32);
+  XqBuf* q0 = xq_find(c, f32);
   if (!q0) return;
   for (uint32_t s = 1; s < n; s++)
-    if (XqBuf* q = view_of(c, f32 + (size_t)s * k)) { q->fresh = q0->fresh; q->tag = q0->tag; }
+    if (XqBuf* q = xq_find(c, f32 + (size_t)s * k)) { q->fresh = q0->fresh; q->tag = q0->tag; }
 }
 
 // one batched quantized mat-vec launch: `specs` name sequence 0's vectors
@@ -114,7 +108,7 @@ int launch_mvb(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float*
   B.ind_nz = ind.nz;
   B.ind_stride = ind.stride;
   {   // the input vector's images lie at the strides its views were registered with
-    const XqBuf* q0 = view_of(c, specs[0].x[0]);
+    const XqBuf* q0 = xq_find(c, specs[0].x[0]);
     const uint32_t kreg = q0 ? q0->k : k;
     B.xq_stride = xq_stride_of(kreg);
     B.ssq_stride = ssq_stride_of(kreg);
@@ -139,7 +133,6 @@ bool batch_weights_ok(const lgh_ctx* c, std::string& why) {
     const LayerW& L = c->layers[i];
     for (const DevWeight* W : {&L.wq, &L.wk, &L.wv, &L.wo})
       if (!mfma_type(W->type) || W->n % 16) { why = "attention weights of layer " + std::to_string(i) + " are not in a matrix-core tile layout"; return false; }
-    if (L.bq || L.bk || L.bv) { /* biases are per row: fine */ }
     if (!L.moe()) {
       if (d.intermediate_size % 256) { why = "intermediate size must be a multiple of 256"; return false; }
       for (const DevWeight* W : {&L.gate, &L.up, &L.down})
@@ -163,16 +156,22 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
   // ---- embedding rows + the first layer's XQ image (embed_kernel's arithmetic)
   {
     LayerW& L0 = c->layers[c->l0];
-    XqBuf* qh = view_of(c, Bs.hidden);
+    XqBuf* qh = xq_find(c, Bs.hidden);
     if ((rc = run_k(c, LGH_K_EMBED, LGH_SYM_EMBED, (uint64_t)n_seq * H * blk_bytes(c->embd_type) / blk_elems(c->embd_type), [&] {
            return embed_multi_launch(c->embd_type, c->embd_raw, Bs.d_tokens, Bs.hidden, H, n_seq, qh->xq, L0.attn_norm, qh->ssq, xq_stride_of(H),
                                      ssq_stride_of(H), c->stream);
          })))
       return rc;
-    for (uint32_t s = 0; s < n_seq; s++)
-      if (XqBuf* q = view_of(c, Bs.hidden + (size_t)s * H)) { q->fresh = true; q->tag = L0.attn_norm; }
+    mark_fresh(c, Bs.hidden, H, n_seq, L0.attn_norm);
   }
   const float scale = 1.0f / std::sqrt((float)d.head_dim);
+  // the merge of a layer's attention splits: `launch(image)` writes attn_out and, for wo, its XQ image for every sequence
+  auto merge = [&](auto&& launch) -> int {
+    XqBuf* qa = xq_find(c, Bs.attn_out);
+    if (int rm = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] { return launch(qa->xq); })) return rm;
+    mark_fresh(c, Bs.attn_out, QD, n_seq, nullptr);
+    return LGH_OK;
+  };
   for (uint32_t li = c->l0; li < c->l1; li++) {
     LayerW& Lw = c->layers[li];
     const float* next_nw = li + 1 < c->l1 ? c->layers[li + 1].attn_norm : c->output_norm;
@@ -186,14 +185,7 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
       sp[1].W[0] = &Lw.wk; sp[1].x[0] = Bs.hidden; sp[1].epi = tq ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = tq ? Bs.kv_tmp : Bs.kcache[li]; sp[1].bias = Lw.bk;
       sp[2].W[0] = &Lw.wv; sp[2].x[0] = Bs.hidden; sp[2].epi = tq ? EPI_STORE : EPI_V_CACHE; sp[2].out = tq ? Bs.kv_tmp + KD : Bs.vcache[li]; sp[2].bias = Lw.bv;
       const uint32_t os[3] = {QD, tq ? 2 * KD : 0, tq ? 2 * KD : 0}, rs[3] = {0, 0, 0}, xk[3] = {0, 0, 0};
-      // (the three matrices may come in formats without a common instantiation: one launch each then, as launch_mv does)
-      bool q4 = false, q5 = false, other = false, uniform = true;
-      for (int s = 0; s < 3; s++) {
-        const int t = sp[s].W[0]->type;
-        q4 |= t == kDevQ4K_T16; q5 |= t == kDevQ5K_T16; other |= t == kDevQ80_T16 || t == kDevQ40_T16;
-        uniform &= t == sp[0].W[0]->type;
-      }
-      if (!uniform && ((q4 && q5) || other)) {
+      if (mv_formats_split(sp, 3)) {   // (one launch each then, as launch_mv does)
         for (int s = 0; s < 3; s++)
           if ((rc = launch_mvb(c, LGH_K_QKV, sp + s, 1, Lw.attn_norm, H, n_seq, os + s, rs + s, xk + s))) return rc;
       } else if ((rc = launch_mvb(c, LGH_K_QKV, sp, 3, Lw.attn_norm, H, n_seq, os, rs, xk))) {
@@ -214,30 +206,21 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
                                          Bs.part_acc, c->stream, qjl_s, qjl ? Bs.kx[li] : nullptr);
            })))
         return rc;
-      XqBuf* qa = view_of(c, Bs.attn_out);
-      if ((rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
-             return attn_tq_combine_launch(bits, Bs.part_ml, Bs.part_acc, signs, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, Bs.attn_out, qa->xq,
+      if ((rc = merge([&](uint8_t* img) {
+             return attn_tq_combine_launch(bits, Bs.part_ml, Bs.part_acc, signs, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, Bs.attn_out, img,
                                            c->stream, n_seq, (uint32_t)xq_stride_of(QD));
            })))
         return rc;
-      for (uint32_t s = 0; s < n_seq; s++)
-        if (XqBuf* q = view_of(c, Bs.attn_out + (size_t)s * QD)) { q->fresh = true; q->tag = nullptr; }
     } else {
-    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-           return attn_multi_launch(Bs.q, Bs.kcache[li], Bs.vcache[li], d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot,
-                                    Bs.cache_stride, n_seq, c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
-         })))
-      return rc;
-    {
-      XqBuf* qa = view_of(c, Bs.attn_out);
-      if ((rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
-             return attn_combine_multi_launch(Bs.part_ml, Bs.part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, n_seq, Bs.attn_out, qa->xq,
-                                              c->stream);
+      if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
+             return attn_multi_launch(Bs.q, Bs.kcache[li], Bs.vcache[li], d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot,
+                                      Bs.cache_stride, n_seq, c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
            })))
         return rc;
-      for (uint32_t s = 0; s < n_seq; s++)
-        if (XqBuf* q = view_of(c, Bs.attn_out + (size_t)s * QD)) { q->fresh = true; q->tag = nullptr; }
-    }
+      if ((rc = merge([&](uint8_t* img) {
+             return attn_combine_multi_launch(Bs.part_ml, Bs.part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, n_seq, Bs.attn_out, img, c->stream);
+           })))
+        return rc;
     }
     // ---- h = x + wo(attn)
     {
@@ -295,8 +278,7 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
         const uint32_t os[1] = {EF}, rs[1] = {0}, xk[1] = {EF};
         if ((rc = launch_mvb(c, LGH_K_GATEUP, &sp, 1, Lw.ffn_norm, H, n_seq, os, rs, xk, ind_gu))) return rc;
       }
-      for (uint32_t v = 0; v < n_seq * topk; v++)
-        if (XqBuf* q = view_of(c, Bs.moe_act + (size_t)v * EF)) { q->fresh = true; q->tag = nullptr; }
+      mark_fresh(c, Bs.moe_act, EF, n_seq * topk, nullptr);
       {
         SegSpec sp;
         sp.W[0] = &Lw.down_exps; sp.x[0] = Bs.moe_act; sp.epi = EPI_STORE; sp.out = Bs.moe_tmp;
@@ -304,13 +286,12 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
         if ((rc = launch_mvb(c, LGH_K_DOWN, &sp, 1, nullptr, Lw.down_exps.k, n_seq, os, rs, xk, ind_dn))) return rc;
       }
       {
-        XqBuf* qh = view_of(c, Bs.hidden);
+        XqBuf* qh = xq_find(c, Bs.hidden);
         if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] {
                return moe_combine_launch(Bs.moe_tmp, Bs.moe_w, topk, Bs.hidden, H, n_seq, next_nw, qh->xq, xq_stride_of(H), qh->ssq, ssq_stride_of(H), c->stream);
              })))
           return rc;
-        for (uint32_t s = 0; s < n_seq; s++)
-          if (XqBuf* q = view_of(c, Bs.hidden + (size_t)s * H)) { q->fresh = true; q->tag = next_nw; }
+        mark_fresh(c, Bs.hidden, H, n_seq, next_nw);
       }
     } else {
       for (uint32_t s = 0; s < n_seq; s++) {   // every sequence routes to its own experts: the single-sequence launches on its vectors
@@ -362,15 +343,15 @@ int stage_control(lgh_ctx* c, const uint32_t* slots, const uint32_t* tokens, uin
       return fail(c, LGH_INVALID_ARGUMENT, "slot " + std::to_string(slots[i]) + ": position " + std::to_string(Bs.pos[slots[i]]) + " >= max_seq_len");
     if (tokens && tokens[i] >= d.vocab_size) return fail(c, LGH_INVALID_ARGUMENT, "token id exceeds vocab size");
   }
-  HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));   // the pinned words below are free again
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));   // the pinned words below are free again
   for (uint32_t i = 0; i < n_seq; i++) {
     Bs.h_ctl[i] = tokens ? (int)tokens[i] : 0;
     Bs.h_ctl[kMaxBatch + i] = (int)Bs.pos[slots[i]];
     Bs.h_ctl[2 * kMaxBatch + i] = (int)slots[i];
   }
-  if (tokens) HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_tokens, Bs.h_ctl, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_pos, Bs.h_ctl + kMaxBatch, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_slot, Bs.h_ctl + 2 * kMaxBatch, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
+  if (tokens) HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_tokens, Bs.h_ctl, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_pos, Bs.h_ctl + kMaxBatch, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_slot, Bs.h_ctl + 2 * kMaxBatch, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
   return LGH_OK;
 }
 
@@ -382,25 +363,30 @@ int run_multi(lgh_ctx* c, uint32_t n_seq, int mode) {
     return c->profiling ? drain_prof(c) : LGH_OK;
   }
   hipGraphExec_t& ge = Bs.graph[n_seq][mode];
-  if (!ge) {
-    hipGraph_t g = nullptr;
-    HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_multi(c, n_seq, mode);
-    hipError_t e = hipStreamEndCapture(c->stream, &g);
-    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-    if (e != hipSuccess) return fail(c, LGH_OPERATION_FAILED, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) return fail(c, LGH_OPERATION_FAILED, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-  }
-  HIP_TRYB(c, LGH_OPERATION_FAILED, hipGraphLaunch(ge, c->stream));
+  if (!ge)
+    if (int rc = capture_graph(c, &ge, [&] { return enqueue_multi(c, n_seq, mode); })) return rc;
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipGraphLaunch(ge, c->stream));
   return LGH_OK;
 }
 
-int check_batch(lgh_ctx* c) {
-  if (!c) return LGH_INVALID_ARGUMENT;
-  if (!c->finalized) return fail(c, LGH_INVALID_ARGUMENT, "context not finalized");
-  if (hipSetDevice(c->device) != hipSuccess) return fail(c, LGH_NOT_AVAILABLE, "hipSetDevice failed");
+// n_steps steps of n_seq sequences in `mode` (1 arg-max, 2 sampler), every token fed back on the device; the steps' tokens come back
+// as [step][n_seq], and the slots' positions move on
+int decode_multi(lgh_ctx* c, const uint32_t* slots, uint32_t n_seq, int mode, size_t n_steps, uint32_t* tokens_out) {
+  BatchScratch& Bs = c->batch;
+  for (size_t st = 0; st < n_steps; st++) {
+    if (int rc = run_multi(c, n_seq, mode)) return rc;
+    if (tokens_out)
+      HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_log + st * kMaxBatch, Bs.d_tokens, (size_t)n_seq * 4, hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  if (tokens_out && n_steps) {
+    std::vector<int> log(n_steps * kMaxBatch);   // the log's rows are kMaxBatch wide
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpy(log.data(), Bs.d_log, log.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t st = 0; st < n_steps; st++)
+      for (uint32_t i = 0; i < n_seq; i++) tokens_out[st * n_seq + i] = (uint32_t)log[st * kMaxBatch + i];
+  }
+  for (uint32_t i = 0; i < n_seq; i++) Bs.pos[slots[i]] += n_steps;
+  c->stats.tokens_processed += n_steps * n_seq;
   return LGH_OK;
 }
 
@@ -409,7 +395,7 @@ int check_batch(lgh_ctx* c) {
 extern "C" {
 
 int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
-  int rc = check_batch(c);
+  int rc = check_ready(c);
   if (rc) return rc;
   BatchScratch& Bs = c->batch;
   if (Bs.ready) return Bs.max_batch == max_batch ? LGH_OK : fail(c, LGH_INVALID_ARGUMENT, "lgh_batch_create was already called with another max_batch");
@@ -430,7 +416,7 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
   Bs.mv_part_floats = B * std::max<uint64_t>({moe_part, (uint64_t)8 * 1600 * 16, (uint64_t)d.vocab_size + 16, (uint64_t)2 * ffn, (uint64_t)QD + 2 * d.num_kv_heads * d.head_dim, (uint64_t)H});
   uint8_t *xq_h = nullptr, *xq_a = nullptr, *xq_f = nullptr, *xq_f2 = nullptr;
   float *ssq_h = nullptr, *ssq_a = nullptr, *ssq_f = nullptr, *ssq_f2 = nullptr;
-  struct { void** p; size_t n; } bufs[] = {
+  const AllocSpec bufs[] = {
       {(void**)&Bs.hidden, B * H * 4},   {(void**)&Bs.xnorm, B * H * 4},   {(void**)&Bs.q, B * QD * 4},   {(void**)&Bs.attn_out, B * QD * 4},
       {(void**)&Bs.act, B * ffn * 4},    {(void**)&Bs.act2, B * ffn * 4},  {(void**)&Bs.logits, B * d.vocab_size * 4},
       {(void**)&Bs.part_ml, B * d.num_kv_heads * c->n_splits * G * 2 * 4}, {(void**)&Bs.part_acc, B * d.num_kv_heads * c->n_splits * G * d.head_dim * 4},
@@ -443,11 +429,7 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
       {(void**)&xq_f, B * xq_stride_of(ffn)}, {(void**)&ssq_f, B * ssq_stride_of(ffn) * 4},
       {(void**)&xq_f2, B * xq_stride_of(ffn)}, {(void**)&ssq_f2, B * ssq_stride_of(ffn) * 4},
   };
-  for (auto& b : bufs) {
-    if ((rc = dev_alloc(c, b.p, b.n))) return rc;
-    HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemsetAsync(*b.p, 0, b.n, c->stream));
-    c->stats.scratch_bytes += b.n;
-  }
+  if ((rc = alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes))) return rc;
   Bs.kcache.assign(d.num_layers, nullptr);
   Bs.vcache.assign(d.num_layers, nullptr);
   Bs.kq.assign(d.num_layers, nullptr);
@@ -458,26 +440,13 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
     Bs.code_stride = rows * tq_row_bytes_host(kv_tq_bits(d.kv_cache_type), d.head_dim);
     Bs.x_stride = rows * (d.head_dim / 32 + 1);
     if ((rc = dev_alloc(c, (void**)&Bs.kv_tmp, B * 2 * d.num_kv_heads * d.head_dim * 4))) return rc;
-    for (uint32_t i = c->l0; i < c->l1; i++) {
-      const size_t n = B * Bs.code_stride;
-      if ((rc = dev_alloc(c, (void**)&Bs.kq[i], n)) || (rc = dev_alloc(c, (void**)&Bs.vq[i], n))) return rc;
-      HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemsetAsync(Bs.kq[i], 0, n, c->stream));
-      HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemsetAsync(Bs.vq[i], 0, n, c->stream));
-      c->stats.kv_bytes += 2 * n;
-      if (kv_is_qjl(d.kv_cache_type)) {
-        const size_t nx = B * Bs.x_stride * 4;
-        if ((rc = dev_alloc(c, (void**)&Bs.kx[i], nx))) return rc;
-        HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemsetAsync(Bs.kx[i], 0, nx, c->stream));
-        c->stats.kv_bytes += nx;
-      }
-    }
   }
-  for (uint32_t i = c->l0; i < c->l1 && !kv_is_tq(d.kv_cache_type); i++) {   // per layer K / V of every slot: [slot][kv_head][max_seq][head_dim] f32
-    const size_t n = B * Bs.cache_stride * 4;
-    if ((rc = dev_alloc(c, (void**)&Bs.kcache[i], n)) || (rc = dev_alloc(c, (void**)&Bs.vcache[i], n))) return rc;
-    HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemsetAsync(Bs.kcache[i], 0, n, c->stream));
-    HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemsetAsync(Bs.vcache[i], 0, n, c->stream));
-    c->stats.kv_bytes += 2 * n;
+  for (uint32_t i = c->l0; i < c->l1; i++) {   // per layer, every slot's cache: code rows (+ QJL rows of K), or f32 [slot][kv_head][max_seq][head_dim]
+    const bool tq = kv_is_tq(d.kv_cache_type);
+    const size_t n = tq ? B * Bs.code_stride : 0, nf = tq ? 0 : B * Bs.cache_stride * 4;
+    const AllocSpec kv[] = {{(void**)&Bs.kq[i], n}, {(void**)&Bs.vq[i], n}, {(void**)&Bs.kx[i], kv_is_qjl(d.kv_cache_type) ? B * Bs.x_stride * 4 : 0},
+                            {(void**)&Bs.kcache[i], nf}, {(void**)&Bs.vcache[i], nf}};
+    if ((rc = alloc_zeroed(c, kv, sizeof(kv) / sizeof(kv[0]), c->stats.kv_bytes))) return rc;
   }
   {   // MoE layers: the expert-grouped step's buffers ((sequence, slot) pairs)
     bool any_moe = false;
@@ -489,18 +458,14 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
       const size_t np = B * d.num_experts_per_token;
       uint8_t* xq_m = nullptr;
       float* ssq_m = nullptr;
-      struct { void** p; size_t n; } mb[] = {
+      const AllocSpec mb[] = {
           {(void**)&Bs.moe_act, np * EI * 4}, {(void**)&Bs.moe_tmp, np * H * 4}, {(void**)&Bs.moe_cnt, 64 * 4}, {(void**)&Bs.moe_idx, 64 * kMaxBatch * 4},
           {(void**)&xq_m, np * xq_stride_of(EI)}, {(void**)&ssq_m, np * ssq_stride_of(EI) * 4}};
-      for (auto& b : mb) {
-        if ((rc = dev_alloc(c, b.p, b.n))) return rc;
-        HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemsetAsync(*b.p, 0, b.n, c->stream));
-        c->stats.scratch_bytes += b.n;
-      }
+      if ((rc = alloc_zeroed(c, mb, sizeof(mb) / sizeof(mb[0]), c->stats.scratch_bytes))) return rc;
       register_views(c, Bs.moe_act, xq_m, ssq_m, EI, (uint32_t)np);
     }
   }
-  HIP_TRYB(c, LGH_ALLOCATION_FAILED, hipHostMalloc((void**)&Bs.h_ctl, 3 * kMaxBatch * 4, hipHostMallocDefault));
+  HIP_TRY(c, LGH_ALLOCATION_FAILED, hipHostMalloc((void**)&Bs.h_ctl, 3 * kMaxBatch * 4, hipHostMallocDefault));
   register_views(c, Bs.hidden, xq_h, ssq_h, H, max_batch);
   register_views(c, Bs.attn_out, xq_a, ssq_a, QD, max_batch);
   register_views(c, Bs.act, xq_f, ssq_f, ffn, max_batch);
@@ -517,12 +482,12 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
     const uint32_t slot0 = 0, tok0 = 0;
     if ((rc = stage_control(c, &slot0, &tok0, 1))) return rc;
     if ((rc = enqueue_multi(c, 1, 1))) return rc;
-    HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
     if (max_batch >= 2) {   // ... and the kernels only a step of several sequences launches (rows 0 of slots 0 and 1)
       const uint32_t slots2[2] = {0, 1}, toks2[2] = {0, 0};
       if ((rc = stage_control(c, slots2, toks2, 2))) return rc;
       if ((rc = enqueue_multi(c, 2, 1))) return rc;
-      HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+      HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
     }
   }
   // the sampling kernels launched eagerly for every n_seq a step can have
@@ -532,7 +497,7 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
 }
 
 int lgh_batch_reset(lgh_ctx* c, uint32_t slot) {   // create_active_sequence: a fresh context for the slot (O(1): position rewind)
-  int rc = check_batch(c);
+  int rc = check_ready(c);
   if (rc) return rc;
   if (!c->batch.ready || slot >= c->batch.max_batch) return fail(c, LGH_INVALID_ARGUMENT, "no such slot");
   c->batch.pos[slot] = 0;
@@ -545,23 +510,23 @@ size_t lgh_batch_position(lgh_ctx* c, uint32_t slot) {
 }
 
 int lgh_forward_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* tokens, uint32_t n_seq, float* logits_out, uint32_t* next_tokens) {
-  int rc = check_batch(c);
+  int rc = check_ready(c);
   if (rc) return rc;
   if (!slots || !tokens) return fail(c, LGH_INVALID_ARGUMENT, "slots / tokens is NULL");
   if ((rc = stage_control(c, slots, tokens, n_seq))) return rc;
   if ((rc = run_multi(c, n_seq, next_tokens != nullptr ? 1 : 0))) return rc;
   BatchScratch& Bs = c->batch;
   if (logits_out)
-    HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(logits_out, Bs.logits, (size_t)n_seq * c->d.vocab_size * 4, hipMemcpyDeviceToHost, c->stream));
-  if (next_tokens) HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(next_tokens, Bs.d_tokens, (size_t)n_seq * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(logits_out, Bs.logits, (size_t)n_seq * c->d.vocab_size * 4, hipMemcpyDeviceToHost, c->stream));
+  if (next_tokens) HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(next_tokens, Bs.d_tokens, (size_t)n_seq * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
   for (uint32_t i = 0; i < n_seq; i++) Bs.pos[slots[i]] += 1;
   c->stats.tokens_processed += n_seq;
   return LGH_OK;
 }
 
 int lgh_decode_greedy_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* first_tokens, uint32_t n_seq, size_t n_steps, uint32_t* tokens_out) {
-  int rc = check_batch(c);
+  int rc = check_ready(c);
   if (rc) return rc;
   if (!slots || !first_tokens) return fail(c, LGH_INVALID_ARGUMENT, "slots / first_tokens is NULL");
   BatchScratch& Bs = c->batch;
@@ -570,25 +535,11 @@ int lgh_decode_greedy_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* f
       if (slots[i] < Bs.max_batch && Bs.pos[slots[i]] + n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "the steps would run past max_seq_len");
   if (n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "too many steps");
   if ((rc = stage_control(c, slots, first_tokens, n_seq))) return rc;
-  for (size_t st = 0; st < n_steps; st++) {
-    if ((rc = run_multi(c, n_seq, 1))) return rc;
-    if (tokens_out)
-      HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_log + st * kMaxBatch, Bs.d_tokens, (size_t)n_seq * 4, hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
-  if (tokens_out && n_steps) {
-    std::vector<int> log(n_steps * kMaxBatch);
-    HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpy(log.data(), Bs.d_log, log.size() * 4, hipMemcpyDeviceToHost));
-    for (size_t st = 0; st < n_steps; st++)
-      for (uint32_t i = 0; i < n_seq; i++) tokens_out[st * n_seq + i] = (uint32_t)log[st * kMaxBatch + i];
-  }
-  for (uint32_t i = 0; i < n_seq; i++) Bs.pos[slots[i]] += n_steps;
-  c->stats.tokens_processed += n_steps * n_seq;
-  return LGH_OK;
+  return decode_multi(c, slots, n_seq, 1, n_steps, tokens_out);
 }
 
 int lgh_batch_set_sampler_ex(lgh_ctx* c, uint32_t slot, const lgh_sampler_config_ex* cfg) {
-  int rc = check_batch(c);
+  int rc = check_ready(c);
   if (rc) return rc;
   BatchScratch& Bs = c->batch;
   if (!Bs.ready || slot >= Bs.max_batch || slot >= Bs.samp_set.size()) return fail(c, LGH_INVALID_ARGUMENT, "no such slot");
@@ -607,7 +558,7 @@ int lgh_batch_set_sampler(lgh_ctx* c, uint32_t slot, const lgh_sampler_config* c
 
 int lgh_decode_sample_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* first_tokens, uint32_t n_seq, const uint32_t* histories,
                             const size_t* history_lens, size_t n_steps, const float* uniforms, uint32_t* tokens_out) {
-  int rc = check_batch(c);
+  int rc = check_ready(c);
   if (rc) return rc;
   if (!slots || !first_tokens) return fail(c, LGH_INVALID_ARGUMENT, "slots / first_tokens is NULL");
   BatchScratch& Bs = c->batch;
@@ -622,7 +573,7 @@ int lgh_decode_sample_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* f
     if (!Bs.samp_set[slots[i]]) return fail(c, LGH_INVALID_ARGUMENT, "slot " + std::to_string(slots[i]) + ": lgh_batch_set_sampler has not been called");
     if (Bs.pos[slots[i]] + n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "the steps would run past max_seq_len");
     const lgh_sampler_config_ex& g = Bs.samp_cfg[slots[i]];
-    if (n_steps && !uniforms && (g.mirostat || !(g.base.temperature == 0.0f || g.base.top_k == 1))) return fail(c, LGH_INVALID_ARGUMENT, "uniforms is NULL");
+    if (n_steps && !uniforms && samp_needs_uniforms(g)) return fail(c, LGH_INVALID_ARGUMENT, "uniforms is NULL");
     const size_t n = history_lens ? history_lens[i] : 0;
     if (n && !histories) return fail(c, LGH_INVALID_ARGUMENT, "histories is NULL");
     hist_off[i] = off;
@@ -634,21 +585,7 @@ int lgh_decode_sample_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* f
     if ((rc = samp_begin(c, Bs.samp, slots[i], Bs.samp_cfg[slots[i]], histories ? histories + hist_off[i] : nullptr,
                          history_lens ? history_lens[i] : 0, first_tokens[i], n_steps, uniforms ? uniforms + i : nullptr, n_seq)))
       return rc;
-  for (size_t st = 0; st < n_steps; st++) {
-    if ((rc = run_multi(c, n_seq, 2))) return rc;
-    if (tokens_out)
-      HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_log + st * kMaxBatch, Bs.d_tokens, (size_t)n_seq * 4, hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIP_TRYB(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
-  if (tokens_out) {
-    std::vector<int> log(n_steps * kMaxBatch);
-    HIP_TRYB(c, LGH_OPERATION_FAILED, hipMemcpy(log.data(), Bs.d_log, log.size() * 4, hipMemcpyDeviceToHost));
-    for (size_t st = 0; st < n_steps; st++)
-      for (uint32_t i = 0; i < n_seq; i++) tokens_out[st * n_seq + i] = (uint32_t)log[st * kMaxBatch + i];
-  }
-  for (uint32_t i = 0; i < n_seq; i++) Bs.pos[slots[i]] += n_steps;
-  c->stats.tokens_processed += n_steps * n_seq;
-  return LGH_OK;
+  return decode_multi(c, slots, n_seq, 2, n_steps, tokens_out);
 }
 
 }  // extern "C"

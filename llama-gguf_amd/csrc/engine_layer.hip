@@ -1,0 +1,298 @@
+// engine_layer.hip — the per-token launch sequence of the single-sequence engine: one transformer layer as three steps on views of
+// one sequence's vectors (qkv_forward, attention_forward, ffn_forward; the per-op test entry points of ops_api.hip run these same
+// functions), and everything one token needs around the layers (enqueue_token).
+#include "engine.h"
+#include "xq.h"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace lgh;
+
+namespace lgh {
+hipError_t kv_store_launch(const float* k, const float* v, float* kcache, float* vcache, uint32_t n_kv, uint32_t d,
+                           uint32_t max_seq, const int* pos, hipStream_t st);
+}
+
+// RoPE table [max_seq][head_dim / 2][cos, sin] in the reference's own arithmetic (ops.rs:1303-1313): libm powf / cosf / sinf on the host
+void rope_table_host(const lgh_model_desc& d, std::vector<float>& cs) {
+  const uint32_t half = d.head_dim / 2;
+  cs.assign((size_t)d.max_seq_len * half * 2, 0.0f);
+  for (uint32_t p = 0; p < d.max_seq_len; p++) {
+    const float position = (float)p / d.rope_freq_scale;
+    for (uint32_t i = 0; i < half; i++) {
+      const float freq = 1.0f / std::pow(d.rope_freq_base, (float)(2 * i) / (float)d.head_dim);
+      const float theta = position * freq;
+      cs[((size_t)p * half + i) * 2] = std::cos(theta);
+      cs[((size_t)p * half + i) * 2 + 1] = std::sin(theta);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// the FFN half of a layer on one sequence's vectors: FeedForward::forward (layers.rs:908-929) or MoeLayer::forward
+// (moe.rs:321-413), residual included.  The single-sequence path passes the context's own buffers; the multi-sequence path
+// (engine_batch.hip) runs MoE layers through here sequence by sequence — every sequence selects its own experts.
+// ------------------------------------------------------------------------------------------------
+int ffn_forward(lgh_ctx* c, LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma) {
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size;
+  int rc;
+  // ---- FFN
+  if (!Lw.moe()) {
+    if (fused_type(Lw.gate.type) && Lw.gate.type == Lw.up.type) {  // FeedForward::forward (layers.rs:908-929)
+      SegSpec sp;
+      sp.npass = 2;
+      sp.W[0] = &Lw.gate; sp.W[1] = &Lw.up;
+      sp.x[0] = sp.x[1] = v.hidden;
+      sp.epi = EPI_SWIGLU;
+      sp.out = v.act;
+      sp.xq_next = mfma_type(Lw.down.type) ? 1 : 0;
+      if ((rc = launch_mv(c, LGH_K_GATEUP, &sp, 1, Lw.ffn_norm, H))) return rc;
+    } else {
+      if ((rc = linear_any(c, LGH_K_GATEUP, Lw.gate, v.hidden, v.act, Lw.ffn_norm, nullptr, nullptr))) return rc;
+      if ((rc = linear_any(c, LGH_K_GATEUP, Lw.up, v.hidden, v.act2, Lw.ffn_norm, nullptr, nullptr))) return rc;
+      if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] { return silu_mul_launch(v.act, v.act2, v.act, Lw.gate.n, c->stream); }))) return rc;
+      xq_stale(c, v.act);
+    }
+    return linear_any(c, LGH_K_DOWN, Lw.down, v.act, v.hidden, nullptr, v.hidden, nullptr, next_mfma ? 2 : 0, next_nw);
+  }
+  // ---- MoE (moe.rs:321-413): router + top-k on device, experts selected by device-side index
+  const uint32_t topk = d.num_experts_per_token;
+  if ((rc = run_k(c, LGH_K_ROUTER, LGH_SYM_ROUTER, (uint64_t)d.num_experts * H * 4, [&] {
+         return moe_router_launch(v.hidden, Lw.ffn_norm, d.norm_eps, Lw.router, H, d.num_experts, topk, v.moe_sel, v.moe_w, c->stream);
+       })))
+    return rc;
+  return moe_experts_forward(c, Lw, v, next_nw, next_mfma);
+}
+
+// The expert half of MoeLayer::forward: the num_experts_per_token experts in v.moe_sel (device), weighted by v.moe_w, plus the residual.
+int moe_experts_forward(lgh_ctx* c, LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma) {
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size;
+  const uint32_t topk = d.num_experts_per_token;
+  int rc;
+  if (!fused_type(Lw.gate_exps.type) || Lw.gate_exps.type != Lw.up_exps.type || !fused_type(Lw.down_exps.type) || topk > 8)
+    return fail(c, LGH_UNSUPPORTED, "MoE needs fused-format experts and top-k <= 8");
+  // The selected experts run two at a time (a launch carries up to four passes: gate and up of two experts).  Every group
+  // reads the SAME normalised h, so the running sum lives in a scratch vector until the last group writes the residual
+  // stream: tmp = 0 + w0 e0 + w1 e1; tmp = tmp + w2 e2 + w3 e3; ...; h = (tmp + ...) + h — moe.rs:363-368's order exactly:
+  // one sum over the weighted expert outputs in selection order, then the residual.
+  for (uint32_t g0 = 0; g0 < topk; g0 += 2) {
+    const uint32_t ng = std::min(2u, topk - g0);
+    const bool first_g = g0 == 0, last_g = g0 + ng >= topk;
+    {
+      SegSpec sp;
+      sp.npass = (int)(2 * ng);
+      for (uint32_t s = 0; s < ng; s++) {
+        sp.W[2 * s] = &Lw.gate_exps; sp.W[2 * s + 1] = &Lw.up_exps;
+        sp.x[2 * s] = sp.x[2 * s + 1] = v.hidden;
+        sp.sel[2 * s] = sp.sel[2 * s + 1] = v.moe_sel + g0 + s;
+      }
+      sp.epi = EPI_MOE_SWIGLU;
+      sp.out = v.act; sp.out2 = v.act2;
+      sp.xq_next = mfma_type(Lw.down_exps.type) ? 1 : 0;
+      if ((rc = launch_mv(c, LGH_K_GATEUP, &sp, 1, Lw.ffn_norm, H))) return rc;
+    }
+    {
+      SegSpec sp;
+      sp.npass = (int)ng;
+      for (uint32_t s = 0; s < ng; s++) {
+        sp.W[s] = &Lw.down_exps;
+        sp.x[s] = s == 0 ? v.act : v.act2;
+        sp.sel[s] = v.moe_sel + g0 + s;
+      }
+      sp.epi = EPI_MOE_DOWN;
+      sp.out = last_g ? v.hidden : v.xnorm;
+      sp.out2 = first_g ? nullptr : v.xnorm;     // (EPI_MOE_DOWN: the running sum of the earlier groups)
+      sp.resid = last_g ? v.hidden : nullptr;
+      sp.moe_w = v.moe_w + g0;
+      sp.xq_next = last_g && next_mfma ? 2 : 0; sp.xq_next_nw = next_nw;
+      if ((rc = launch_mv(c, LGH_K_DOWN, &sp, 1, nullptr, Lw.down_exps.k))) return rc;
+    }
+  }
+  return LGH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the attention half of a layer on one sequence's vectors, up to attn_out (layers.rs:438-600)
+// ------------------------------------------------------------------------------------------------
+int qkv_forward(lgh_ctx* c, LayerW& Lw, const AttnView& v) {
+  const lgh_model_desc& d = c->d;
+  int rc;
+  const bool kv8 = (d.flags & LGH_FLAG_KV_INT8) != 0;
+  float* const k_new = v.kv_tmp;                                                     // byte caches: the current token's rotated K row ...
+  float* const v_new = k_new ? k_new + (size_t)d.num_kv_heads * d.head_dim : nullptr;   // ... and V row, f32, quantized by the attention launch
+  const bool fused = fused_type(Lw.wq.type) && fused_type(Lw.wk.type) && fused_type(Lw.wv.type) && !d.use_neox_rope;
+  if (!k_new && (kv8 || !fused)) return fail(c, LGH_INVALID_ARGUMENT, "qkv_forward: this layer stages its K / V rows and the view has no kv_tmp");
+  if (fused) {
+    SegSpec sp[3];
+    sp[0].W[0] = &Lw.wq; sp[0].x[0] = v.hidden; sp[0].epi = EPI_ROPE_Q; sp[0].out = v.q; sp[0].bias = Lw.bq;
+    sp[1].W[0] = &Lw.wk; sp[1].x[0] = v.hidden; sp[1].epi = kv8 ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = kv8 ? k_new : Lw.kcache; sp[1].bias = Lw.bk;
+    sp[2].W[0] = &Lw.wv; sp[2].x[0] = v.hidden; sp[2].epi = kv8 ? EPI_STORE : EPI_V_CACHE; sp[2].out = kv8 ? v_new : Lw.vcache; sp[2].bias = Lw.bv;
+    return launch_mv(c, LGH_K_QKV, sp, 3, Lw.attn_norm, d.hidden_size);
+  }
+  if ((rc = linear_any(c, LGH_K_QKV, Lw.wq, v.hidden, v.q, Lw.attn_norm, nullptr, Lw.bq))) return rc;
+  if ((rc = linear_any(c, LGH_K_QKV, Lw.wk, v.hidden, k_new, Lw.attn_norm, nullptr, Lw.bk))) return rc;
+  if ((rc = linear_any(c, LGH_K_QKV, Lw.wv, v.hidden, v_new, Lw.attn_norm, nullptr, Lw.bv))) return rc;
+  xq_stale(c, v.q);
+  if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] {
+         return rope_launch(v.q, k_new, d.num_heads, d.num_kv_heads, d.head_dim, c->state + ST_POS, c->rope_cs, (int)d.use_neox_rope, c->stream);
+       })))
+    return rc;
+  if (kv8) return LGH_OK;
+  return run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] {
+    return kv_store_launch(k_new, v_new, Lw.kcache, Lw.vcache, d.num_kv_heads, d.head_dim, d.max_seq_len, c->state + ST_POS, c->stream);
+  });
+}
+
+// attention_cached (ops.rs:1479-1537) over the layer's cache, whatever its format: one branch per path, each ending in the launch
+// that writes attn_out — and, where that launch can and the caller asks, wo's input as XQ straight from it
+int attention_forward(lgh_ctx* c, LayerW& Lw, uint32_t li, const AttnView& v, float scale, bool xq_out) {
+  const lgh_model_desc& d = c->d;
+  int rc;
+  const bool kv8 = (d.flags & LGH_FLAG_KV_INT8) != 0;
+  const float* const k_new = v.kv_tmp;                                                     // (byte caches only)
+  const float* const v_new = k_new ? k_new + (size_t)d.num_kv_heads * d.head_dim : nullptr;
+  const int* const pos = c->state + ST_POS;
+  const uint64_t kv_bytes = (uint64_t)2 * d.num_kv_heads * (c->pos + 1) *
+                            (d.kv_cache_type == LGH_KV_INT8 ? d.head_dim + 4 : kv8 ? d.head_dim : d.head_dim * 4);
+  XqBuf* qa = nullptr;
+  auto image = [&]() -> uint8_t* {
+    qa = xq_out ? xq_get(c, v.attn_out, d.num_heads * d.head_dim) : nullptr;
+    return qa ? qa->xq : nullptr;
+  };
+  auto merge = [&](uint8_t* img) {
+    return run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
+      return attn_combine_launch(c->part_ml, c->part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, v.attn_out, img, c->stream);
+    });
+  };
+  if (kv_is_tq(d.kv_cache_type)) {
+    // TurboQuantKVCache (kv_turboquant.rs): write_kv + attention_layer over the codes; the merge also inverts the V rotation
+    const int bits = kv_tq_bits(d.kv_cache_type);
+    const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
+    const bool qjl = kv_is_qjl(d.kv_cache_type);
+    const float* qjl_s = qjl ? c->tq_qjl + (size_t)(li - c->l0) * d.num_kv_heads * d.head_dim * d.head_dim : nullptr;
+    const uint64_t tq_bytes = (uint64_t)d.num_kv_heads * (c->pos + 1) * (2 * tq_row_bytes_host(bits, d.head_dim) + (qjl ? d.head_dim / 8 + 4 : 0)) +
+                              (qjl ? (uint64_t)d.num_kv_heads * d.head_dim * d.head_dim * 4 : 0);
+    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, tq_bytes, [&] {
+           return attn_tq_launch(bits, v.q, (uint8_t*)Lw.k8, (uint8_t*)Lw.v8, k_new, v_new, signs, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len,
+                                 scale, pos, c->n_splits, c->part_ml, c->part_acc, c->stream, qjl_s, qjl ? Lw.kx : nullptr);
+         })))
+      return rc;
+    uint8_t* const img = image();
+    rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
+      return attn_tq_combine_launch(bits, c->part_ml, c->part_acc, signs, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, v.attn_out, img, c->stream);
+    });
+  } else if (kv8) {
+    // int8 rows + scales (kv_quantized.rs); the launch also quantizes and stores the current token's rows
+    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
+           return attn_q8_launch((int)d.kv_cache_type, v.q, Lw.k8, Lw.v8, Lw.kscale, Lw.vscale, k_new, v_new, d.num_heads, d.num_kv_heads, d.head_dim,
+                                 d.max_seq_len, scale, pos, c->n_splits, c->part_ml, c->part_acc, c->stream);
+         })))
+      return rc;
+    rc = merge(image());
+  } else if (c->attn_generic) {   // any head size / group size: f32 out, no image
+    rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
+      return attn_decode_any_launch(v.q, Lw.kcache, Lw.vcache, v.attn_out, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, c->stream);
+    });
+  } else if (c->attn_direct) {    // short context: one launch
+    uint8_t* const img = image();
+    rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
+      return attn_direct_launch(v.q, Lw.kcache, Lw.vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, v.attn_out, img, c->stream);
+    });
+  } else {                        // n_splits ranges of the context, then their merge
+    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
+           return attn_launch(v.q, Lw.kcache, Lw.vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, 0, c->n_splits, c->part_ml,
+                              c->part_acc, c->stream);
+         })))
+      return rc;
+    rc = merge(image());
+  }
+  if (rc) return rc;
+  if (qa) { qa->fresh = true; qa->tag = nullptr; }
+  else xq_stale(c, v.attn_out);
+  return LGH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// one transformer layer (TransformerLayer::forward serial-residual branch, layers.rs:1187-1244)
+// ------------------------------------------------------------------------------------------------
+// `next_nw` / `next_mfma`: the norm weights and kernel family of whatever consumes this layer's output (the next layer's
+// QKV, or the output projection)
+static int layer_forward(lgh_ctx* c, uint32_t li, const float* next_nw, bool next_mfma) {
+  LayerW& Lw = c->layers[li];
+  const AttnView av{c->hidden, c->q, c->kv_tmp, c->attn_out};
+  int rc;
+  if ((rc = qkv_forward(c, Lw, av))) return rc;
+  if ((rc = attention_forward(c, Lw, li, av, 1.0f / std::sqrt((float)c->d.head_dim), mfma_type(Lw.wo.type)))) return rc;   // scale: layers.rs:374
+  // ---- h = x + wo(attn)   (layers.rs:700-701, 1201-1208)
+  const bool ffn_mfma = Lw.moe() ? mfma_type(Lw.gate_exps.type) : mfma_type(Lw.gate.type);
+  if ((rc = linear_any(c, LGH_K_WO, Lw.wo, c->attn_out, c->hidden, nullptr, c->hidden, Lw.bo, ffn_mfma ? 2 : 0, Lw.ffn_norm))) return rc;
+  if (c->profiling) {  // an EMPTY event bracket in mid-stream: what the measurement itself adds to every sample (at the
+    // head of a token, on an idle stream, the same bracket reads differently from run to run)
+    if ((rc = run_k(c, -1, -1, 0, [&] { return hipSuccess; }))) return rc;
+  }
+  return ffn_forward(c, Lw, FfnView{c->hidden, c->act, c->act2, c->xnorm, c->moe_sel, c->moe_w}, next_nw, next_mfma);
+}
+
+// Everything one token needs, in stream order.  Used eagerly and under graph capture.
+int enqueue_token(lgh_ctx* c, int mode) {
+  const lgh_model_desc& d = c->d;
+  int rc;
+  for (auto& q : c->xqs) q.fresh = false;   // the residual stream is (re)written in f32 now (embedding / previous stage)
+  if (c->first) {
+    // the embedding row, and — when the first layer's QKV runs on the matrix cores — its XQ image with that layer's norm weights
+    XqBuf* qh = nullptr;
+    const float* nw0 = nullptr;
+    if (c->l0 < c->l1 && mfma_type(c->layers[c->l0].wq.type) && d.hidden_size % 256 == 0) {
+      qh = xq_get(c, c->hidden, d.hidden_size);
+      nw0 = c->layers[c->l0].attn_norm;
+    }
+    if ((rc = run_k(c, LGH_K_EMBED, LGH_SYM_EMBED, (uint64_t)d.hidden_size * blk_bytes(c->embd_type) / blk_elems(c->embd_type), [&] {
+           return embed_launch(c->embd_type, c->embd_raw, c->state + ST_TOKEN, c->hidden, d.hidden_size, c->state,
+                               qh ? qh->xq : nullptr, nw0, qh ? qh->ssq : nullptr, c->stream);
+         })))
+      return rc;
+    if (qh) { qh->fresh = true; qh->tag = nw0; }
+  } else {
+    if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] { return advance_launch(c->state, c->stream); }))) return rc;
+  }
+  for (uint32_t li = c->l0; li < c->l1; li++) {
+    // who consumes this layer's output: the next layer's QKV (attn_norm), the output projection (output_norm), or — at a
+    // pipeline-stage boundary and at the end of a prefill step — nobody on this device
+    const float* next_nw = nullptr;
+    bool next_mfma = false;
+    if (li + 1 < c->l1) {
+      next_nw = c->layers[li + 1].attn_norm;
+      next_mfma = mfma_type(c->layers[li + 1].wq.type);
+    } else if (c->last && mode != MODE_PREFILL) {
+      next_nw = c->output_norm;
+      next_mfma = mfma_type(c->output.type);
+    }
+    if ((rc = layer_forward(c, li, next_nw, next_mfma))) return rc;
+  }
+  if (c->last && mode != MODE_PREFILL) {
+    // compute_logits (llama.rs:247-266): final RMSNorm fused into the output projection
+    if ((rc = linear_any(c, LGH_K_OUTPUT, c->output, c->hidden, c->logits, c->output_norm, nullptr, nullptr))) return rc;
+    if (mode == MODE_GREEDY) {
+      if ((rc = run_k(c, LGH_K_ARGMAX, LGH_SYM_ARGMAX, (uint64_t)d.vocab_size * 4, [&] {
+             return argmax_launch(c->logits, d.vocab_size, c->amax_v, c->amax_i, c->state, c->tok_log, c->stream);
+           })))
+        return rc;
+    } else if (mode == MODE_SAMPLE) {   // Sampler::sample in place of the arg-max (sample.hip); the token lands where the arg-max's does
+      if ((rc = run_k(c, LGH_K_ARGMAX, LGH_SYM_OTHER, (uint64_t)d.vocab_size * 4, [&] {
+             return sample_launch(c->samp, c->logits, d.vocab_size, 1, nullptr, c->state, c->tok_log, nullptr, c->stream);
+           })))
+        return rc;
+    }
+  }
+  // in-graph hops to a stage on the same device (lgh_stage_set_forward_targets)
+  if (c->fwd_hidden && !c->last &&
+      (rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, (uint64_t)d.hidden_size * 8, [&] { return copy_words_launch(c->fwd_hidden, c->hidden, d.hidden_size, c->stream); })))
+    return rc;
+  if (c->fwd_token && c->last && mode == MODE_GREEDY &&
+      (rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 8, [&] { return copy_words_launch(c->fwd_token, c->state + ST_ARGMAX, 1, c->stream); })))
+    return rc;
+  return LGH_OK;
+}

@@ -1,0 +1,182 @@
+// engine_prefill.hip — the batched prompt driver: which contexts have the path (pf_eligible), its scratch (pf_ensure) and one block
+// of up to 128 prompt tokens through every owned layer (prefill_block), for the context's own sequence or a slot of the
+// multi-sequence engine.
+#include "engine.h"
+#include "prefill.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace lgh;
+
+// ------------------------------------------------------------------------------------------------
+// batched prompt processing (prefill.hip)
+// ------------------------------------------------------------------------------------------------
+bool pf_eligible(const lgh_ctx* c) {
+  const lgh_model_desc& d = c->d;
+  if (d.flags & (LGH_FLAG_EXACT_PREFILL | LGH_FLAG_KV_INT8)) return false;   // (the batched path writes f32 K/V rows)
+  const uint32_t QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, g = d.num_heads / d.num_kv_heads;
+  if (d.hidden_size % 256 || d.hidden_size > 2048u * kPfSsqChunks || QD % 256 || KD % 16) return false;
+  if ((d.head_dim != 64 && d.head_dim != 128) || (g != 1 && g != 2 && g != 4 && g != 8)) return false;
+  for (uint32_t i = c->l0; i < c->l1; i++) {
+    const LayerW& L = c->layers[i];
+    for (const DevWeight* W : {&L.wq, &L.wk, &L.wv, &L.wo})
+      if (!pf_supported_type(W->type) || W->n % 16) return false;
+    if (L.moe()) {   // experts: tokens are grouped by expert (prefill.hip); up to 8 selected, at most 64 experts
+      if (d.num_experts > (uint32_t)kPfMaxExperts || d.num_experts_per_token == 0 || d.num_experts_per_token > (uint32_t)kPfMaxTopK ||
+          (uint32_t)kPfTokens * d.num_experts_per_token + 15 * d.num_experts > (uint32_t)kPfMoeRows)
+        return false;
+      for (const DevWeight* W : {&L.gate_exps, &L.up_exps, &L.down_exps})
+        if (!pf_supported_type(W->type) || W->n % 16 || W->k % 256) return false;
+    } else {
+      if (d.intermediate_size % 256) return false;
+      for (const DevWeight* W : {&L.gate, &L.up, &L.down})
+        if (!pf_supported_type(W->type) || W->n % 16) return false;
+    }
+  }
+  return true;
+}
+
+int pf_ensure(lgh_ctx* c) {
+  PfScratch& P = c->pf;
+  if (P.ready) return LGH_OK;
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim;
+  bool any_moe = false, any_dense = false;
+  for (uint32_t i = c->l0; i < c->l1; i++) (c->layers[i].moe() ? any_moe : any_dense) = true;
+  const uint32_t F = any_dense ? d.intermediate_size : 0;
+  const uint32_t EI = any_moe ? (d.expert_intermediate_size ? d.expert_intermediate_size : d.intermediate_size) : 0;
+  const uint32_t qkv[3] = {QD, KD, KD}, one[1] = {H};
+  size_t pb = pf_part_bytes(qkv, 3, H);
+  pb = std::max(pb, pf_part_bytes(one, 1, QD));
+  if (F) { const uint32_t gu[2] = {F, F}; pb = std::max({pb, pf_part_bytes(gu, 2, H), pf_part_bytes(one, 1, F)}); }
+  if (EI) { const uint32_t gu[2] = {EI, EI}; pb = std::max({pb, pf_part_bytes(gu, 2, H, kPfMoeRows), pf_part_bytes(one, 1, EI, kPfMoeRows)}); }
+  const uint32_t topk = d.num_experts_per_token ? d.num_experts_per_token : 1;
+  const AllocSpec bufs[] = {
+      {(void**)&P.xh_h, xh_bytes(H)},           {(void**)&P.xh_attn, xh_bytes(QD)},
+      {(void**)&P.xh_act, xh_bytes(std::max(F, EI))}, {(void**)&P.hidden, (size_t)kPfTokens * H * 4},
+      {(void**)&P.q, (size_t)kPfTokens * QD * 4},
+      {(void**)&P.part, pb},                    {(void**)&P.tokens, (size_t)kPfTokens * 4},
+      {(void**)&P.ssq, (size_t)kPfTokens * kPfSsqChunks * 4},
+      {(void**)&P.moe_sel, any_moe ? (size_t)kPfTokens * topk * 4 : 0},  {(void**)&P.moe_w, any_moe ? (size_t)kPfTokens * topk * 4 : 0},
+      {(void**)&P.moe_cnt, any_moe ? (size_t)kPfMaxExperts * 4 : 0},    {(void**)&P.moe_list, any_moe ? (size_t)kPfMaxExperts * kPfTokens * 4 : 0},
+      {(void**)&P.moe_base, any_moe ? (size_t)kPfMaxExperts * 4 : 0},   {(void**)&P.moe_rowmap, any_moe ? (size_t)kPfMoeRows * 4 : 0},
+      {(void**)&P.moe_tokmap, any_moe ? (size_t)kPfTokens * kPfMaxTopK * 4 : 0},
+      {(void**)&P.xh_gather, any_moe ? xh_bytes(H) * d.num_experts : 0}, {(void**)&P.xh_act_e, any_moe ? xh_bytes(EI) * d.num_experts : 0},
+  };
+  if (int rc = alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes)) return rc;
+  // the zero-fills are done before anybody else (another stream, a peer's copy into the stage block) touches the buffers
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  P.part_bytes = pb;
+  P.ready = true;
+  return LGH_OK;
+}
+
+// m <= 128 prompt tokens at positions t.pos0 .. t.pos0+m-1 of the target sequence: fills every owned layer's K/V rows of that
+// sequence; the caller moves the sequence's position.  The first stage starts from the tokens' embedding rows, any other stage
+// from the block of hidden vectors its predecessor left in pf.hidden; a stage that is not the last leaves its output block there
+// (the last one stops after its final layer's K/V rows: nothing else of a prefill survives).
+int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_t m) {
+  int rc = pf_ensure(c);
+  if (rc) return rc;
+  PfScratch& P = c->pf;
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, F = d.intermediate_size;
+  const uint32_t pos0 = (uint32_t)t.pos0;
+  const size_t slot_off = t.slot < 0 ? 0 : (size_t)t.slot * c->batch.cache_stride;
+  hipStream_t st = c->stream;
+  auto K = [&](hipError_t e, const char* what) -> int {
+    return e == hipSuccess ? LGH_OK : fail(c, LGH_OPERATION_FAILED, std::string("batched prefill, ") + what + ": " + hipGetErrorString(e));
+  };
+  if (c->first) {
+    // The caller's `tokens` may be freed as soon as this returns (lgh_stage_prefill_batch does not synchronise), so the ids
+    // go through a context-owned PINNED buffer, one slot per position; a slot is only rewritten after the copy that last
+    // read it has completed (reset + a second prompt before the first one has run).
+    if (!P.tok_pinned) {
+      HIP_TRY(c, LGH_ALLOCATION_FAILED, hipHostMalloc((void**)&P.tok_pinned, (size_t)d.max_seq_len * 4, hipHostMallocDefault));
+      HIP_TRY(c, LGH_OPERATION_FAILED, hipEventCreateWithFlags(&P.tok_copied, hipEventDisableTiming));
+    } else if (pos0 < P.tok_hi && pos0 + m > P.tok_lo) {
+      // only when a slot about to be rewritten may still be read: a reset / shift / truncate followed by a new prompt.  The blocks
+      // of ONE prompt use ascending slots and never wait here (lgh_stage_prefill_batch stays asynchronous).
+      HIP_TRY(c, LGH_OPERATION_FAILED, hipEventSynchronize(P.tok_copied));
+      P.tok_lo = P.tok_hi = 0;
+    }
+    if (P.tok_hi == P.tok_lo) { P.tok_lo = pos0; P.tok_hi = pos0 + m; }
+    else { P.tok_lo = std::min(P.tok_lo, pos0); P.tok_hi = std::max(P.tok_hi, pos0 + m); }
+    std::memcpy(P.tok_pinned + pos0, tokens, (size_t)m * 4);
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(P.tokens, P.tok_pinned + pos0, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipEventRecord(P.tok_copied, st));
+    if ((rc = K(embed_batch_launch(c->embd_type, c->embd_raw, P.tokens, P.hidden, H, m, st), "embedding"))) return rc;
+  }
+  if ((rc = K(pf_row_epi_launch(nullptr, 0, 0, 0, nullptr, P.hidden, H, c->layers[c->l0].attn_norm, P.xh_h, P.ssq, m, st), "attn_norm"))) return rc;
+  const float scale = 1.0f / std::sqrt((float)d.head_dim);  // layers.rs:374
+  for (uint32_t li = c->l0; li < c->l1; li++) {
+    LayerW& L = c->layers[li];
+    float* const kcache = t.slot < 0 ? L.kcache : c->batch.kcache[li] + slot_off;
+    float* const vcache = t.slot < 0 ? L.vcache : c->batch.vcache[li] + slot_off;
+    uint32_t S = 0, nc = 0;
+    const DevWeight* qkv[3] = {&L.wq, &L.wk, &L.wv};
+    if ((rc = K(pf_gemm_launch(qkv, 3, P.xh_h, P.part, P.part_bytes, m, &S, &nc, st), "qkv GEMM"))) return rc;
+    if ((rc = K(pf_qkv_epi_launch(P.part, S, nc, QD, KD, d.head_dim, L.bq, L.bk, L.bv, c->rope_cs, pos0, d.max_seq_len, P.q, kcache, vcache, P.ssq, H,
+                                  d.norm_eps, (int)d.use_neox_rope, m, st),
+                "qkv epilogue")))
+      return rc;
+    if (li + 1 == c->l1 && c->last) break;   // the model's last layer: its K/V rows are written, its output would be discarded
+    if ((rc = K(attn_prefill_launch(P.q, kcache, vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
+                "attention")))
+      return rc;
+    const DevWeight* wo[1] = {&L.wo};
+    if ((rc = K(pf_gemm_launch(wo, 1, P.xh_attn, P.part, P.part_bytes, m, &S, &nc, st), "wo GEMM"))) return rc;
+    if ((rc = K(pf_row_epi_launch(P.part, S, nc, 0, L.bo, P.hidden, H, L.ffn_norm, P.xh_h, P.ssq, m, st), "wo epilogue"))) return rc;
+    const float* next_nw = li + 1 < c->l1 ? c->layers[li + 1].attn_norm : nullptr;   // nullptr: the block goes to the next stage as f32
+    uint8_t* next_xh = next_nw ? P.xh_h : nullptr;
+    if (!L.moe()) {
+      const DevWeight* gu[2] = {&L.gate, &L.up};
+      if ((rc = K(pf_gemm_launch(gu, 2, P.xh_h, P.part, P.part_bytes, m, &S, &nc, st), "gate/up GEMM"))) return rc;
+      if ((rc = K(pf_swiglu_launch(P.part, S, F, P.xh_act, P.ssq, H, d.norm_eps, m, st), "SwiGLU"))) return rc;
+      const DevWeight* dn[1] = {&L.down};
+      if ((rc = K(pf_gemm_launch(dn, 1, P.xh_act, P.part, P.part_bytes, m, &S, &nc, st), "down GEMM"))) return rc;
+      if ((rc = K(pf_row_epi_launch(P.part, S, nc, 0, nullptr, P.hidden, H, next_nw, next_xh, P.ssq, m, st), "down epilogue"))) return rc;
+      continue;
+    }
+    // ---- MoE (moe.rs:321-413): route every token of the block (f32, the decode router), group the (token, slot) pairs by
+    // expert, and run each expert once over its rows: gather -> gate|up GEMM -> SwiGLU -> down GEMM -> rows back to tokens
+    const uint32_t topk = d.num_experts_per_token, EI = L.gate_exps.n;
+    if ((rc = K(moe_router_launch(P.hidden, L.ffn_norm, d.norm_eps, L.router, H, d.num_experts, topk, P.moe_sel, P.moe_w, st, m), "router"))) return rc;
+    if ((rc = K(pf_moe_group_launch(P.moe_sel, m, topk, d.num_experts, P.moe_cnt, P.moe_base, P.moe_list, P.moe_rowmap, P.moe_tokmap, st), "expert grouping")))
+      return rc;
+    if ((rc = K(pf_moe_gather_launch(P.xh_h, H, P.moe_list, P.moe_cnt, P.xh_gather, d.num_experts, st), "expert gather"))) return rc;
+    for (uint32_t e = 0; e < d.num_experts; e++) {   // every expert's gate|up over its rows, partial sums side by side in one row space
+      const DevWeight* gu[2] = {&L.gate_exps, &L.up_exps};
+      if ((rc = K(pf_gemm_launch(gu, 2, P.xh_gather + (size_t)e * xh_bytes(H), P.part, P.part_bytes, kPfTokens, &S, &nc, st, e, P.moe_cnt + e, kPfMoeRows,
+                                 P.moe_base + e),
+                  "expert gate/up GEMM")))
+        return rc;
+    }
+    if ((rc = K(pf_moe_swiglu_launch(P.part, S, EI, P.xh_act_e, P.moe_rowmap, P.moe_list, P.ssq, H, d.norm_eps, st), "expert SwiGLU"))) return rc;
+    for (uint32_t e = 0; e < d.num_experts; e++) {
+      const DevWeight* dn[1] = {&L.down_exps};
+      if ((rc = K(pf_gemm_launch(dn, 1, P.xh_act_e + (size_t)e * xh_bytes(EI), P.part, P.part_bytes, kPfTokens, &S, &nc, st, e, P.moe_cnt + e, kPfMoeRows,
+                                 P.moe_base + e),
+                  "expert down GEMM")))
+        return rc;
+    }
+    // h += sum over the selected experts, in selection order, of routing weight * expert output (moe.rs:363-368), then the
+    // next layer's input
+    if ((rc = K(pf_moe_combine_launch(P.part, S, P.moe_tokmap, P.moe_w, topk, P.hidden, H, next_nw, next_xh, P.ssq, m, st), "MoE combine"))) return rc;
+  }
+  c->stats.tokens_processed += m;
+  return LGH_OK;
+}
+
+// a prompt of the context's own sequence, block by block: its caches, its position, and the device's word of the next position
+int prefill_own(lgh_ctx* c, const uint32_t* tokens, size_t n) {
+  for (size_t i = 0; i < n; i += kPfTokens) {
+    const uint32_t m = (uint32_t)std::min<size_t>(kPfTokens, n - i);
+    if (int rc = prefill_block(c, PfTarget{c->pos, -1}, tokens ? tokens + i : nullptr, m)) return rc;
+    c->pos += m;
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipMemsetD32Async((hipDeviceptr_t)(c->state + ST_NEXT), (int)c->pos, 1, c->stream));
+  }
+  return LGH_OK;
+}

@@ -507,7 +507,7 @@ static uint32_t mvqb2_min_seq() {
   return v;
 }
 
-// `L` built like a single-sequence launch (engine.hip: build_mv_group, with the batch cap on tiles per workgroup); sequences'
+// `L` built like a single-sequence launch (engine_launch.hip: build_mv_group, with the batch cap on tiles per workgroup); sequences'
 // vectors at the strides in `B`
 hipError_t mvqb_launch(const MvLaunch& L, const MvBatch& Bin, uint32_t n_wg, uint32_t threads, hipStream_t st) {
   MvBatch B = Bin;

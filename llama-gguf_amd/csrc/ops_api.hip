@@ -402,9 +402,10 @@ int lgh_op_attention(int device, const float* q, const float* k, const float* v,
   return t.down(out, dout, n_heads * seq_len * d);
 }
 
-// ---- the engine's attention launch sequences one path at a time (test surface: tests/test_gpu_attention.py holds each to a
-// float64 restatement).  The caches come from the host, the position through the device word the engine's kernels read
-// (state[ST_POS]); nothing falls back to another kernel: a shape the path has no kernel for answers LGH_UNSUPPORTED. ----
+// ---- the engine's attention step (engine_layer.hip: attention_forward) one path at a time (test surface: tests/test_gpu_attention.py
+// holds each to a float64 restatement).  The bare context's fields select the path as a real context's do; the caches come from the
+// host, the position through the device word the engine's kernels read (state[ST_POS]); nothing falls back to another kernel: a
+// shape the path has no kernel for answers LGH_UNSUPPORTED. ----
 }  // extern "C"
 
 namespace {
@@ -423,8 +424,35 @@ int down_bytes(Tmp& t, void* host, const void* dev, size_t n) {
 
 int set_pos(Tmp& t, size_t pos) {   // the engine's position word
   const int p = (int)pos;
+  t.c->pos = pos;
   if (hipMemcpyAsync(t.c->state + ST_POS, &p, 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
   return hipStreamSynchronize(t.c->stream) == hipSuccess ? LGH_OK : LGH_OPERATION_FAILED;
+}
+
+// the bare context as attention_forward reads it: shapes, the cache format, the split count and its partial-result buffers
+int attn_setup(Tmp& t, uint32_t kv_cache_type, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq, int n_splits) {
+  lgh_ctx* c = t.c;
+  c->d.num_heads = (uint32_t)n_heads;
+  c->d.num_kv_heads = (uint32_t)n_kv;
+  c->d.head_dim = (uint32_t)head_dim;
+  c->d.max_seq_len = (uint32_t)max_seq;
+  c->d.kv_cache_type = kv_cache_type;
+  if (kv_cache_type != LGH_KV_F32) c->d.flags |= LGH_FLAG_KV_INT8;   // (as lgh_create marks every byte-per-element cache)
+  c->n_splits = (uint32_t)n_splits;
+  const size_t parts = n_kv * (size_t)n_splits * (n_heads / n_kv);
+  if (!parts) return LGH_OK;   // (a one-launch path: no partial results)
+  c->part_ml = t.up(nullptr, parts * 2);
+  c->part_acc = t.up(nullptr, parts * head_dim);
+  return c->part_ml && c->part_acc ? LGH_OK : LGH_ALLOCATION_FAILED;
+}
+
+// the current token's K row | V row, side by side as the engine's kv_tmp holds them
+float* up_kv_new(Tmp& t, const float* k_new, const float* v_new, size_t kd) {
+  float* d = t.up(nullptr, 2 * kd);
+  if (!d || hipMemcpyAsync(d, k_new, kd * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+      hipMemcpyAsync(d + kd, v_new, kd * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
+    return nullptr;
+  return d;
 }
 
 float half_to_float(uint16_t h) {
@@ -457,24 +485,19 @@ int lgh_op_attention_decode(int device, int path, const float* q, const float* k
   if (path != 2 && !fast) return LGH_UNSUPPORTED;
   if (path == 0 && (n_splits < 1 || n_splits > 32)) return LGH_INVALID_ARGUMENT;
   if (path == 2 && max_seq * 4 > 150 * 1024) return LGH_UNSUPPORTED;   // the scores of a head live in LDS
-  float *dq = t.up(q, n_heads * head_dim), *dk = t.up(k_cache, cache), *dv = t.up(v_cache, cache), *dout = t.up(nullptr, n_heads * head_dim);
-  if (!dq || !dk || !dv || !dout) return LGH_ALLOCATION_FAILED;
-  int rc = set_pos(t, pos);
-  if (rc) return rc;
-  hipStream_t st = t.c->stream;
-  const int* dpos = t.c->state + ST_POS;
-  const uint32_t H = (uint32_t)n_heads, KV = (uint32_t)n_kv, D = (uint32_t)head_dim, MS = (uint32_t)max_seq;
-  if (path == 0) {   // split + merge; attn_launch picks 4 or 8 waves from max_seq, as in the engine
-    float *pml = t.up(nullptr, n_kv * n_splits * g * 2), *pacc = t.up(nullptr, n_kv * n_splits * g * head_dim);
-    if (!pml || !pacc) return LGH_ALLOCATION_FAILED;
-    if (attn_launch(dq, dk, dv, H, KV, D, MS, scale, dpos, 0, (uint32_t)n_splits, pml, pacc, st) != hipSuccess) return LGH_OPERATION_FAILED;
-    if (attn_combine_launch(pml, pacc, H, KV, D, (uint32_t)n_splits, dout, nullptr, st) != hipSuccess) return LGH_OPERATION_FAILED;
-  } else if (path == 1) {   // one launch (engine: pos + 1 <= direct_attn_max_kv)
-    if (attn_direct_launch(dq, dk, dv, H, KV, D, MS, scale, dpos, dout, nullptr, st) != hipSuccess) return LGH_OPERATION_FAILED;
-  } else if (attn_decode_any_launch(dq, dk, dv, dout, H, KV, D, MS, scale, dpos, st) != hipSuccess) {   // any head_dim / group size
-    return LGH_OPERATION_FAILED;
-  }
-  return t.down(out, dout, n_heads * head_dim);
+  LayerW Lw;
+  Lw.kcache = t.up(k_cache, cache);
+  Lw.vcache = t.up(v_cache, cache);
+  const AttnView v{nullptr, t.up(q, n_heads * head_dim), nullptr, t.up(nullptr, n_heads * head_dim)};   // (f32 cache: no staged rows)
+  if (!v.q || !Lw.kcache || !Lw.vcache || !v.attn_out) return LGH_ALLOCATION_FAILED;
+  int rc;
+  if ((rc = attn_setup(t, LGH_KV_F32, n_heads, n_kv, head_dim, max_seq, path == 0 ? n_splits : 0)) || (rc = set_pos(t, pos))) return rc;
+  // 0: split + merge (attn_launch picks 4 or 8 waves from max_seq); 1: one launch (engine: pos + 1 <= direct_attn_max_kv); 2: the
+  // kernel of the shapes the others do not cover (engine: every token of such a model), here on any head_dim / group size
+  t.c->attn_direct = path == 1;
+  t.c->attn_generic = path == 2;
+  if (attention_forward(t.c, Lw, 0, v, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  return t.down(out, v.attn_out, n_heads * head_dim);
 }
 
 int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
@@ -489,22 +512,19 @@ int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int
   if (n_kv == 0 || n_heads % n_kv || pos >= max_seq || max_seq > 0x7FFFFFFFu || n_splits < 1 || n_splits > 32) return LGH_INVALID_ARGUMENT;
   const size_t g = n_heads / n_kv, rows = n_kv * max_seq, cache = rows * head_dim;
   if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)g)) return LGH_UNSUPPORTED;
-  float *dq = t.up(q, n_heads * head_dim), *dkn = t.up(k_new, n_kv * head_dim), *dvn = t.up(v_new, n_kv * head_dim);
-  int8_t *dk = (int8_t*)up_bytes(t, k_bytes, cache), *dv = (int8_t*)up_bytes(t, v_bytes, cache);
-  float *dks = i8 ? t.up(k_scale, rows) : nullptr, *dvs = i8 ? t.up(v_scale, rows) : nullptr;
-  float *dout = t.up(nullptr, n_heads * head_dim), *pml = t.up(nullptr, n_kv * n_splits * g * 2), *pacc = t.up(nullptr, n_kv * n_splits * g * head_dim);
-  if (!dq || !dkn || !dvn || !dk || !dv || (i8 && (!dks || !dvs)) || !dout || !pml || !pacc) return LGH_ALLOCATION_FAILED;
-  int rc = set_pos(t, pos);
-  if (rc) return rc;
-  hipStream_t st = t.c->stream;
-  if (attn_q8_launch((int)kv_cache_type, dq, dk, dv, dks, dvs, dkn, dvn, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, scale,
-                     t.c->state + ST_POS, (uint32_t)n_splits, pml, pacc, st) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  if (attn_combine_launch(pml, pacc, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)n_splits, dout, nullptr, st) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  if ((rc = down_bytes(t, k_bytes, dk, cache)) || (rc = down_bytes(t, v_bytes, dv, cache))) return rc;
-  if (i8 && ((rc = t.down(k_scale, dks, rows)) || (rc = t.down(v_scale, dvs, rows)))) return rc;
-  return t.down(out, dout, n_heads * head_dim);
+  LayerW Lw;
+  Lw.k8 = (int8_t*)up_bytes(t, k_bytes, cache);
+  Lw.v8 = (int8_t*)up_bytes(t, v_bytes, cache);
+  Lw.kscale = i8 ? t.up(k_scale, rows) : nullptr;
+  Lw.vscale = i8 ? t.up(v_scale, rows) : nullptr;
+  const AttnView v{nullptr, t.up(q, n_heads * head_dim), up_kv_new(t, k_new, v_new, n_kv * head_dim), t.up(nullptr, n_heads * head_dim)};
+  if (!v.q || !v.kv_tmp || !Lw.k8 || !Lw.v8 || (i8 && (!Lw.kscale || !Lw.vscale)) || !v.attn_out) return LGH_ALLOCATION_FAILED;
+  int rc;
+  if ((rc = attn_setup(t, kv_cache_type, n_heads, n_kv, head_dim, max_seq, n_splits)) || (rc = set_pos(t, pos))) return rc;
+  if (attention_forward(t.c, Lw, 0, v, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if ((rc = down_bytes(t, k_bytes, Lw.k8, cache)) || (rc = down_bytes(t, v_bytes, Lw.v8, cache))) return rc;
+  if (i8 && ((rc = t.down(k_scale, Lw.kscale, rows)) || (rc = t.down(v_scale, Lw.vscale, rows)))) return rc;
+  return t.down(out, v.attn_out, n_heads * head_dim);
 }
 
 int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl, const float* k_new,
@@ -524,23 +544,20 @@ int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint
   for (size_t i = 0; i < n_kv * 2 * d; i++)
     if (signs[i] != 1.0f && signs[i] != -1.0f) return LGH_INVALID_ARGUMENT;
   const size_t cb = rows * tq_row_bytes_host(bits, (uint32_t)d), xw = rows * (d / 32 + 1);
-  float *dq = t.up(q, n_heads * d), *dkn = t.up(k_new, n_kv * d), *dvn = t.up(v_new, n_kv * d), *ds = t.up(signs, n_kv * 2 * d);
-  uint8_t *dk = (uint8_t*)up_bytes(t, k_codes, cb), *dv = (uint8_t*)up_bytes(t, v_codes, cb);
-  uint32_t* dx = qjl ? (uint32_t*)up_bytes(t, k_qjl, xw * 4) : nullptr;
-  float* dS = qjl ? t.up(qjl_matrices, n_kv * d * d) : nullptr;
-  float *dout = t.up(nullptr, n_heads * d), *pml = t.up(nullptr, n_kv * n_splits * g * 2), *pacc = t.up(nullptr, n_kv * n_splits * g * d);
-  if (!dq || !dkn || !dvn || !ds || !dk || !dv || (qjl && (!dx || !dS)) || !dout || !pml || !pacc) return LGH_ALLOCATION_FAILED;
-  int rc = set_pos(t, pos);
-  if (rc) return rc;
-  hipStream_t st = t.c->stream;
-  if (attn_tq_launch(bits, dq, dk, dv, dkn, dvn, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, scale, t.c->state + ST_POS,
-                     (uint32_t)n_splits, pml, pacc, st, dS, dx) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  if (attn_tq_combine_launch(bits, pml, pacc, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)n_splits, dout, nullptr, st, 0, 0) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  if ((rc = down_bytes(t, k_codes, dk, cb)) || (rc = down_bytes(t, v_codes, dv, cb))) return rc;
-  if (qjl && (rc = down_bytes(t, k_qjl, dx, xw * 4))) return rc;
-  return t.down(out, dout, n_heads * d);
+  LayerW Lw;   // (the one layer of a context that owns layer 0: its signs and matrices are the context's first)
+  Lw.k8 = (int8_t*)up_bytes(t, k_codes, cb);
+  Lw.v8 = (int8_t*)up_bytes(t, v_codes, cb);
+  Lw.kx = qjl ? (uint32_t*)up_bytes(t, k_qjl, xw * 4) : nullptr;
+  t.c->tq_signs = t.up(signs, n_kv * 2 * d);
+  t.c->tq_qjl = qjl ? t.up(qjl_matrices, n_kv * d * d) : nullptr;
+  const AttnView v{nullptr, t.up(q, n_heads * d), up_kv_new(t, k_new, v_new, n_kv * d), t.up(nullptr, n_heads * d)};
+  if (!v.q || !v.kv_tmp || !t.c->tq_signs || !Lw.k8 || !Lw.v8 || (qjl && (!Lw.kx || !t.c->tq_qjl)) || !v.attn_out) return LGH_ALLOCATION_FAILED;
+  int rc;
+  if ((rc = attn_setup(t, kv_cache_type, n_heads, n_kv, d, max_seq, n_splits)) || (rc = set_pos(t, pos))) return rc;
+  if (attention_forward(t.c, Lw, 0, v, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if ((rc = down_bytes(t, k_codes, Lw.k8, cb)) || (rc = down_bytes(t, v_codes, Lw.v8, cb))) return rc;
+  if (qjl && (rc = down_bytes(t, k_qjl, Lw.kx, xw * 4))) return rc;
+  return t.down(out, v.attn_out, n_heads * d);
 }
 
 int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads, size_t n_kv,
@@ -821,7 +838,7 @@ static size_t weight_bytes(uint32_t type, size_t k, size_t n) {
 int lgh_op_qkv_rope(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
                     float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
                     float rope_base, float rope_scale, float* q_out, float* k_cache, float* v_cache) {
-  // layer_forward's fused QKV launch: RMSNorm prologue, Q with RoPE, K with RoPE into cache row `pos`, V into cache row `pos`
+  // qkv_forward's fused QKV launch: RMSNorm prologue, Q with RoPE, K with RoPE into cache row `pos`, V into cache row `pos`
   Tmp t(device);
   if (t.rc) return t.rc;
   if (!types || !w || !x || !norm_w || !q_out || !k_cache || !v_cache || hidden == 0 || head_dim == 0 || head_dim % 2 || n_kv_heads == 0 ||
@@ -837,31 +854,31 @@ int lgh_op_qkv_rope(int device, const uint32_t* types, const void* const* w, con
   d.rope_freq_base = rope_base;
   d.rope_freq_scale = rope_scale;
   const size_t rows[3] = {n_heads * head_dim, n_kv_heads * head_dim, n_kv_heads * head_dim};
-  DevWeight W[3];
+  LayerW Lw;
+  DevWeight* const W[3] = {&Lw.wq, &Lw.wk, &Lw.wv};
   int rc;
   for (int s = 0; s < 3; s++) {
     const size_t nb = weight_bytes(types[s], hidden, rows[s]);
     if (!nb || !w[s]) return LGH_SHAPE_MISMATCH;
-    if ((rc = upload_matrix(t.c, W[s], (int)types[s], (uint32_t)hidden, (uint32_t)rows[s], 1, -1, w[s], nb))) return rc;
-    if (!fused_type(W[s].type)) return LGH_UNSUPPORTED;   // the engine runs such layers unfused
+    if ((rc = upload_matrix(t.c, *W[s], (int)types[s], (uint32_t)hidden, (uint32_t)rows[s], 1, -1, w[s], nb))) return rc;
+    if (!fused_type(W[s]->type)) return LGH_UNSUPPORTED;   // the engine runs such layers unfused
   }
   std::vector<float> cs;
   rope_table_host(d, cs);
   const size_t cache = n_kv_heads * max_seq_len * head_dim;
   t.c->rope_cs = t.up(cs.data(), cs.size());
-  float *dx = t.up(x, hidden), *dnw = t.up(norm_w, hidden), *dq = t.up(nullptr, rows[0]), *dk = t.up(k_cache, cache), *dv = t.up(v_cache, cache);
-  float* db[3] = {nullptr, nullptr, nullptr};
+  const AttnView v{t.up(x, hidden), t.up(nullptr, rows[0]), nullptr, nullptr};   // (fused launch into the f32 cache: no staged rows)
+  Lw.attn_norm = t.up(norm_w, hidden);
+  Lw.kcache = t.up(k_cache, cache);
+  Lw.vcache = t.up(v_cache, cache);
+  float** const db[3] = {&Lw.bq, &Lw.bk, &Lw.bv};
   for (int s = 0; s < 3; s++)
-    if (bias && bias[s] && !(db[s] = t.up(bias[s], rows[s]))) return LGH_ALLOCATION_FAILED;
-  if (!t.c->rope_cs || !dx || !dnw || !dq || !dk || !dv) return LGH_ALLOCATION_FAILED;
+    if (bias && bias[s] && !(*db[s] = t.up(bias[s], rows[s]))) return LGH_ALLOCATION_FAILED;
+  if (!t.c->rope_cs || !v.hidden || !Lw.attn_norm || !v.q || !Lw.kcache || !Lw.vcache) return LGH_ALLOCATION_FAILED;
   if ((rc = set_pos(t, pos))) return rc;
-  SegSpec sp[3];
-  sp[0].W[0] = &W[0]; sp[0].x[0] = dx; sp[0].epi = EPI_ROPE_Q; sp[0].out = dq; sp[0].bias = db[0];
-  sp[1].W[0] = &W[1]; sp[1].x[0] = dx; sp[1].epi = EPI_ROPE_K; sp[1].out = dk; sp[1].bias = db[1];
-  sp[2].W[0] = &W[2]; sp[2].x[0] = dx; sp[2].epi = EPI_V_CACHE; sp[2].out = dv; sp[2].bias = db[2];
-  if ((rc = launch_mv(t.c, LGH_K_QKV, sp, 3, dnw, (uint32_t)hidden))) return rc;
-  if ((rc = t.down(q_out, dq, rows[0])) || (rc = t.down(k_cache, dk, cache))) return rc;
-  return t.down(v_cache, dv, cache);
+  if ((rc = qkv_forward(t.c, Lw, v))) return rc;
+  if ((rc = t.down(q_out, v.q, rows[0])) || (rc = t.down(k_cache, Lw.kcache, cache))) return rc;
+  return t.down(v_cache, Lw.vcache, cache);
 }
 
 int lgh_op_linear_chain(int device, uint32_t type_a, const void* w_a, const void* w_a_up, const float* bias_a, size_t k, size_t n_a,

@@ -565,12 +565,6 @@ using namespace lgh;
 // ------------------------------------------------------------------------------------------------
 // host side: buffers, config checks, the per-call window set-up
 // ------------------------------------------------------------------------------------------------
-#define HIP_TRYS(c, status, expr)                                                                 \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail((c), (status), std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 int samp_alloc(lgh_ctx* c, SampBufs& B, uint32_t n_slots, uint32_t n_rows) {
   const lgh_model_desc& d = c->d;
   B.n_slots = n_slots;
@@ -579,20 +573,14 @@ int samp_alloc(lgh_ctx* c, SampBufs& B, uint32_t n_slots, uint32_t n_rows) {
   B.tk_cap = 2 * d.max_seq_len + 2;   // <= n_steps + 1 leaving history tokens, then n_steps + 1 fed tokens
   B.uni_cap = std::max(1u, d.max_seq_len);
   const size_t V = d.vocab_size;
-  struct { void** p; size_t n; } bufs[] = {
+  const AllocSpec bufs[] = {
       {(void**)&B.ctl, n_slots * sizeof(SampSeq)},          {(void**)&B.wcnt, n_slots * V * 4},
       {(void**)&B.scnt, n_slots * V * 4},                   {(void**)&B.tk, (size_t)n_slots * B.tk_cap * 4},
       {(void**)&B.uni, (size_t)n_slots * B.uni_cap * 4},    {(void**)&B.pb, n_rows * V * 4},
       {(void**)&B.part_m, (size_t)n_rows * kSampParts * 4}, {(void**)&B.part_s, (size_t)n_rows * kSampParts * 4},
       {(void**)&B.part_k, (size_t)n_rows * kSampParts * kSampK * 8}, {(void**)&B.stage, (2 * V + 2 * kMaxBatch) * 4},
   };
-  int rc;
-  for (auto& b : bufs) {
-    if ((rc = dev_alloc(c, b.p, b.n))) return rc;
-    HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemsetAsync(*b.p, 0, b.n, c->stream));
-    c->stats.scratch_bytes += b.n;
-  }
-  return LGH_OK;
+  return alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes);
 }
 
 int samp_check(lgh_ctx* c, const lgh_sampler_config* s) {
@@ -623,20 +611,22 @@ lgh_sampler_config_ex samp_plain(const lgh_sampler_config& s) {
   return x;
 }
 
+bool samp_needs_uniforms(const lgh_sampler_config_ex& s) { return s.mirostat || !(s.base.temperature == 0.0f || s.base.top_k == 1); }
+
 // Sampler::new's mirostat_mu (mod.rs:156-161)
 static float mu_start(const lgh_sampler_config_ex& s) { return s.mirostat ? s.mirostat_tau * 2.0f : 10.0f; }
 
 int samp_reset(lgh_ctx* c, SampBufs& B, uint32_t slot, const lgh_sampler_config_ex& cfg) {
   const float mu = mu_start(cfg);
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemsetAsync(B.scnt + (size_t)slot * B.vocab, 0, (size_t)B.vocab * 4, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(&B.ctl[slot].mu, &mu, 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemsetAsync(B.scnt + (size_t)slot * B.vocab, 0, (size_t)B.vocab * 4, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(&B.ctl[slot].mu, &mu, 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
   return LGH_OK;
 }
 
 int samp_mu(lgh_ctx* c, SampBufs& B, uint32_t slot, float* mu) {
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpy(mu, &B.ctl[slot].mu, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpy(mu, &B.ctl[slot].mu, 4, hipMemcpyDeviceToHost));
   return LGH_OK;
 }
 
@@ -700,15 +690,15 @@ int samp_begin(lgh_ctx* c, SampBufs& B, uint32_t slot, const lgh_sampler_config_
   std::vector<float> u(std::max<size_t>(n_steps, 1), 0.0f);
   if (uni && !q.greedy)
     for (size_t i = 0; i < n_steps; i++) u[i] = uni[i * uni_stride];
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));   // the previous call's steps are done with these buffers
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));   // the previous call's steps are done with these buffers
   // (everything but mu, which carries over from the previous call)
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.ctl + slot, &q, kSampSeqCallBytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.tk + (size_t)slot * B.tk_cap, tk.data(), tk.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.uni + (size_t)slot * B.uni_cap, u.data(), u.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.ctl + slot, &q, kSampSeqCallBytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.tk + (size_t)slot * B.tk_cap, tk.data(), tk.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.uni + (size_t)slot * B.uni_cap, u.data(), u.size() * 4, hipMemcpyHostToDevice, c->stream));
   if (!pairs.empty())
-    HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.stage, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, sample_window_launch(B, slot, (uint32_t)(pairs.size() / 2), c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.stage, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, sample_window_launch(B, slot, (uint32_t)(pairs.size() / 2), c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
   return LGH_OK;
 }
 
@@ -722,12 +712,12 @@ int samp_warm(lgh_ctx* c, SampBufs& B, const float* logits, uint32_t n_seq) {
   std::vector<int> slots(n_seq);
   for (uint32_t i = 0; i < n_seq; i++) slots[i] = (int)(i % B.n_slots);
   int* d_slots = B.stage;   // (staging words, free outside a call)
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.ctl, qs.data(), qs.size() * sizeof(SampSeq), hipMemcpyHostToDevice, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(d_slots, slots.data(), n_seq * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, sample_window_launch(B, 0, 0, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, sample_launch(B, logits, B.vocab, n_seq, d_slots, nullptr, nullptr, d_slots + kMaxBatch, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemsetAsync(B.ctl, 0, B.n_slots * sizeof(SampSeq), c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.ctl, qs.data(), qs.size() * sizeof(SampSeq), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(d_slots, slots.data(), n_seq * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, sample_window_launch(B, 0, 0, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, sample_launch(B, logits, B.vocab, n_seq, d_slots, nullptr, nullptr, d_slots + kMaxBatch, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemsetAsync(B.ctl, 0, B.n_slots * sizeof(SampSeq), c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
   return LGH_OK;
 }
 
@@ -747,18 +737,18 @@ int samp_one(lgh_ctx* c, SampBufs& B, const lgh_sampler_config_ex& cfg, const ui
     if (win[i] < B.vocab) { pairs.push_back((int)win[i]); pairs.push_back((int)(j - i)); }
     i = j;
   }
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.ctl, &q, sizeof(q), hipMemcpyHostToDevice, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.uni, &uniform, 4, hipMemcpyHostToDevice, c->stream));
-  if (counts) HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.scnt, counts, (size_t)B.vocab * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.ctl, &q, sizeof(q), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.uni, &uniform, 4, hipMemcpyHostToDevice, c->stream));
+  if (counts) HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.scnt, counts, (size_t)B.vocab * 4, hipMemcpyHostToDevice, c->stream));
   if (!pairs.empty())
-    HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.stage, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, sample_window_launch(B, 0, (uint32_t)(pairs.size() / 2), c->stream));
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(B.stage, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, sample_window_launch(B, 0, (uint32_t)(pairs.size() / 2), c->stream));
   int* d_tok = B.stage + 2 * (size_t)B.vocab;
-  HIP_TRYS(c, LGH_OPERATION_FAILED, sample_launch(B, d_logits, B.vocab, 1, nullptr, nullptr, nullptr, d_tok, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, sample_launch(B, d_logits, B.vocab, 1, nullptr, nullptr, nullptr, d_tok, c->stream));
   int tok = 0;
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(&tok, d_tok, 4, hipMemcpyDeviceToHost, c->stream));
-  if (mu_out) HIP_TRYS(c, LGH_OPERATION_FAILED, hipMemcpyAsync(mu_out, &B.ctl[0].mu, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRYS(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(&tok, d_tok, 4, hipMemcpyDeviceToHost, c->stream));
+  if (mu_out) HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(mu_out, &B.ctl[0].mu, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
   *token_out = (uint32_t)tok;
   return LGH_OK;
 }

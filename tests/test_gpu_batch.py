@@ -260,3 +260,27 @@ def test_turboquant_slots_bitwise(pkg, name, mix, B, kv):
     finally:
         multi.close()
         single.close()
+
+
+def test_slot_prompt_leaves_the_single_sequence_untouched(pkg):
+    """A slot's prompt through the batched prompt path (lgh_batch_prefill, >= 2 tokens) runs on the slot's caches and position only:
+    the context's own single sequence keeps its position, and its next token's logits equal, bit for bit, those of an engine that
+    never saw the slot's prompt."""
+    cfg = pkg.make_config("test-dense-d128", max_seq_len=64)
+    model = pkg.SynthModel(cfg, mix="Q4_K_M")
+    eng = pkg.HipGpuInference.from_model(model, 64)
+    other = pkg.HipGpuInference.from_model(model, 64)
+    try:
+        eng.batch_create(2)
+        hist = _history(cfg, 600, 5)
+        for tok in hist[:4]:
+            eng.forward(tok)
+            other.forward(tok)
+        eng.batch_prefill(1, _history(cfg, 601, 5))
+        assert eng.position() == 4
+        got, want = eng.forward(hist[4]), other.forward(hist[4])
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), float(np.abs(got - want).max())
+        assert eng.batch_position(1) == 5
+    finally:
+        eng.close()
+        other.close()
