@@ -528,6 +528,39 @@ int lgh_op_linear_chain(int device, uint32_t type_a, const void* w_a, const void
 int lgh_op_moe_experts(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down,
                        size_t n_experts, size_t hidden, size_t ffn, size_t top_k, const float* router, const int* sel, const float* sel_w,
                        const float* x, const float* norm_w, float eps, float* out, int* sel_out, float* sel_w_out);
+/* The batched prompt path's layer steps (prefill_block's own launch sequences), one at a time on a block of m_tokens <= 128 tokens,
+ * for kernel-level tests.  Test support: not part of the inference API.  Weights are native GGUF bytes, row-major [out][in], of the
+ * types the batched path takes (Q4_K, Q5_K, Q6_K, Q8_0, Q4_0); hidden_size % 256 == 0.  Before the first launch the scratch the kernels
+ * read is filled with NaN bit patterns (f32 0x7FC0BEEF, f16 0x7E5A), so that a value consumed without having been produced shows in
+ * the outputs.  The MoE index tables get in-range values instead, none of which the kernels may leave in a produced entry (a NaN
+ * pattern read as an index would address outside the buffers): lists 0x7F7F, tokmap 383, rowmap 0, selection / counts / bases 0x55.
+ *
+ * QKV step: hidden [m_tokens][hidden_size] f32 -> XH(hidden * norm_w) and sums of squares, the q|k|v GEMM, then 1/rms, bias, RoPE
+ * (neox: pairs (i, i + d/2)) at positions pos0 + t.  q_out [m_tokens][n_heads * head_dim]; the caches
+ * [n_kv_heads][max_seq_len][head_dim] are in / out (the caller's sentinels survive outside rows pos0 .. pos0 + m_tokens - 1). */
+int lgh_op_pf_qkv(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* hidden, const float* norm_w,
+                  float eps, size_t hidden_size, size_t head_dim, size_t n_heads, size_t n_kv_heads, int neox, size_t max_seq_len, size_t pos0,
+                  size_t m_tokens, float rope_base, float rope_scale, float* q_out, float* k_cache, float* v_cache);
+/* wo step: x [m_tokens][k] f32 (-> XH as the attention output arrives), hidden_out = resid + W . x (+ bias), W [hidden_size][k];
+ * xh_out [m_tokens][hidden_size] = the next XH f16(hidden_out * next_nw) widened to f32; ssq_out [m_tokens][8] = the tokens' sums of
+ * squares per 2048 columns (entries past the row's chunks are not written). */
+int lgh_op_pf_linear(int device, uint32_t type, const void* w, const float* bias, const float* x, size_t k, size_t hidden_size, const float* resid,
+                     const float* next_nw, size_t m_tokens, float* hidden_out, float* xh_out, float* ssq_out);
+/* dense FFN step: hidden_out = hidden + W_down . (silu(W_gate . x') * (W_up . x')), x' = RMSNorm(hidden) * norm_w; next_nw may be NULL
+ * (no next XH is written; xh_out is untouched).  act_out (may be NULL) [m_tokens][ffn]: the f16 SwiGLU output the down GEMM read. */
+int lgh_op_pf_ffn(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down,
+                  const float* hidden, const float* norm_w, const float* next_nw, float eps, size_t hidden_size, size_t ffn, size_t m_tokens,
+                  float* hidden_out, float* xh_out, float* ssq_out, float* act_out);
+/* MoE FFN step: the device router, the grouping of the (token, slot) pairs by expert, every expert once over its rows, the combine.
+ * Expert stacks as lgh_op_moe_experts.  sel_out / sel_w_out / tokmap_out [m_tokens][top_k]; counts_out / bases_out [n_experts];
+ * lists_out [n_experts][128] (entries past an expert's count keep the fill 0x7F7F); rowmap_out [384], the whole table (expert |
+ * row << 8, -1 written by the grouping kernel on every padding row); act_out (may be NULL) [n_experts][128][ffn]: every expert's f16 SwiGLU rows as its
+ * down GEMM read them (rows past the expert's count hold the NaN fill).  LGH_UNSUPPORTED where the batched path does not take the routing shape
+ * (128 * top_k + 15 * n_experts > 384). */
+int lgh_op_pf_moe(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down,
+                  const float* router, size_t n_experts, size_t top_k, const float* hidden, const float* norm_w, const float* next_nw, float eps,
+                  size_t hidden_size, size_t ffn, size_t m_tokens, float* hidden_out, float* xh_out, float* ssq_out, int* sel_out, float* sel_w_out,
+                  int* counts_out, int* bases_out, int* lists_out, int* rowmap_out, int* tokmap_out, float* act_out);
 /* Device-resident weights by tensor name for the per-op surface: `CudaBackend::load_model_weights` and the `b.name()`
  * lookups in its vec_mat / vec_mat_q (src/backend/cuda/mod.rs:121-146, 436-470, 511-575).  A weight is uploaded once
  * (native GGUF bytes; the library re-lays it out as lgh_upload_tensor does) and later calls name it. */

@@ -216,6 +216,13 @@ struct PfTarget { size_t pos0; int slot; };
 bool pf_eligible(const lgh_ctx* c);
 int pf_ensure(lgh_ctx* c);
 int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_t m);
+// prefill_block's steps over the m tokens in the context's scratch (c->pf, after pf_ensure); next_nw: the norm weight of the step's
+// consumer, nullptr = leave no XH
+int pf_block_input(lgh_ctx* c, const float* nw, uint32_t m);
+int pf_qkv_step(lgh_ctx* c, lgh::LayerW& L, float* kcache, float* vcache, uint32_t pos0, uint32_t m);
+int pf_wo_step(lgh_ctx* c, lgh::LayerW& L, uint32_t m);
+int pf_ffn_step(lgh_ctx* c, lgh::LayerW& L, const float* next_nw, uint32_t m);
+int pf_moe_step(lgh_ctx* c, lgh::LayerW& L, const float* next_nw, uint32_t m);
 int prefill_own(lgh_ctx* c, const uint32_t* tokens, size_t n);   // the context's own sequence: blocks of <= 128, position and ST_NEXT moved
 // sampler plumbing (sample.hip)
 int samp_alloc(lgh_ctx* c, lgh::SampBufs& B, uint32_t n_slots, uint32_t n_rows);

@@ -73,6 +73,98 @@ int pf_ensure(lgh_ctx* c) {
   return LGH_OK;
 }
 
+static int pf_k(lgh_ctx* c, hipError_t e, const char* what) {
+  return e == hipSuccess ? LGH_OK : fail(c, LGH_OPERATION_FAILED, std::string("batched prefill, ") + what + ": " + hipGetErrorString(e));
+}
+
+// the block of hidden vectors in pf.hidden as it is -> XH(h * nw) in pf.xh_h, the tokens' sums of squares in pf.ssq
+int pf_block_input(lgh_ctx* c, const float* nw, uint32_t m) {
+  PfScratch& P = c->pf;
+  return pf_k(c, pf_row_epi_launch(nullptr, 0, 0, 0, nullptr, P.hidden, c->d.hidden_size, nw, P.xh_h, P.ssq, m, c->stream), "attn_norm");
+}
+
+// ---- the steps of one layer over a block of m tokens, on the context's scratch (c->pf); prefill_block strings them together, the
+// per-step test entry points (ops_api.hip) run them one at a time ----
+// XH(h * attn_norm) in pf.xh_h + the tokens' sums of squares in pf.ssq -> q in pf.q, K / V rows pos0 .. pos0+m-1 of the given caches
+int pf_qkv_step(lgh_ctx* c, LayerW& L, float* kcache, float* vcache, uint32_t pos0, uint32_t m) {
+  PfScratch& P = c->pf;
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim;
+  hipStream_t st = c->stream;
+  int rc;
+  uint32_t S = 0, nc = 0;
+  const DevWeight* qkv[3] = {&L.wq, &L.wk, &L.wv};
+  if ((rc = pf_k(c, pf_gemm_launch(qkv, 3, P.xh_h, P.part, P.part_bytes, m, &S, &nc, st), "qkv GEMM"))) return rc;
+  return pf_k(c, pf_qkv_epi_launch(P.part, S, nc, QD, KD, d.head_dim, L.bq, L.bk, L.bv, c->rope_cs, pos0, d.max_seq_len, P.q, kcache, vcache, P.ssq, H,
+                                   d.norm_eps, (int)d.use_neox_rope, m, st),
+              "qkv epilogue");
+}
+
+// XH(attention output) in pf.xh_attn -> pf.hidden += wo . attn (+ bo), XH(h * ffn_norm) in pf.xh_h, sums of squares in pf.ssq
+int pf_wo_step(lgh_ctx* c, LayerW& L, uint32_t m) {
+  PfScratch& P = c->pf;
+  const uint32_t H = c->d.hidden_size;
+  hipStream_t st = c->stream;
+  int rc;
+  uint32_t S = 0, nc = 0;
+  const DevWeight* wo[1] = {&L.wo};
+  if ((rc = pf_k(c, pf_gemm_launch(wo, 1, P.xh_attn, P.part, P.part_bytes, m, &S, &nc, st), "wo GEMM"))) return rc;
+  return pf_k(c, pf_row_epi_launch(P.part, S, nc, 0, L.bo, P.hidden, H, L.ffn_norm, P.xh_h, P.ssq, m, st), "wo epilogue");
+}
+
+// dense FFN: XH(h * ffn_norm) in pf.xh_h -> pf.hidden += down . (silu(gate) * up); next_nw: the next layer's XH (h * next_nw) into
+// pf.xh_h, nullptr: none (the block leaves as f32)
+int pf_ffn_step(lgh_ctx* c, LayerW& L, const float* next_nw, uint32_t m) {
+  PfScratch& P = c->pf;
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size, F = d.intermediate_size;
+  hipStream_t st = c->stream;
+  uint8_t* next_xh = next_nw ? P.xh_h : nullptr;
+  int rc;
+  uint32_t S = 0, nc = 0;
+  const DevWeight* gu[2] = {&L.gate, &L.up};
+  if ((rc = pf_k(c, pf_gemm_launch(gu, 2, P.xh_h, P.part, P.part_bytes, m, &S, &nc, st), "gate/up GEMM"))) return rc;
+  if ((rc = pf_k(c, pf_swiglu_launch(P.part, S, F, P.xh_act, P.ssq, H, d.norm_eps, m, st), "SwiGLU"))) return rc;
+  const DevWeight* dn[1] = {&L.down};
+  if ((rc = pf_k(c, pf_gemm_launch(dn, 1, P.xh_act, P.part, P.part_bytes, m, &S, &nc, st), "down GEMM"))) return rc;
+  return pf_k(c, pf_row_epi_launch(P.part, S, nc, 0, nullptr, P.hidden, H, next_nw, next_xh, P.ssq, m, st), "down epilogue");
+}
+
+// MoE FFN (moe.rs:321-413): route every token of the block (f32, the decode router), group the (token, slot) pairs by
+// expert, and run each expert once over its rows: gather -> gate|up GEMM -> SwiGLU -> down GEMM -> rows back to tokens
+int pf_moe_step(lgh_ctx* c, LayerW& L, const float* next_nw, uint32_t m) {
+  PfScratch& P = c->pf;
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size;
+  hipStream_t st = c->stream;
+  uint8_t* next_xh = next_nw ? P.xh_h : nullptr;
+  int rc;
+  uint32_t S = 0, nc = 0;
+  const uint32_t topk = d.num_experts_per_token, EI = L.gate_exps.n;
+  if ((rc = pf_k(c, moe_router_launch(P.hidden, L.ffn_norm, d.norm_eps, L.router, H, d.num_experts, topk, P.moe_sel, P.moe_w, st, m), "router"))) return rc;
+  if ((rc = pf_k(c, pf_moe_group_launch(P.moe_sel, m, topk, d.num_experts, P.moe_cnt, P.moe_base, P.moe_list, P.moe_rowmap, P.moe_tokmap, st), "expert grouping")))
+    return rc;
+  if ((rc = pf_k(c, pf_moe_gather_launch(P.xh_h, H, P.moe_list, P.moe_cnt, P.xh_gather, d.num_experts, st), "expert gather"))) return rc;
+  for (uint32_t e = 0; e < d.num_experts; e++) {   // every expert's gate|up over its rows, partial sums side by side in one row space
+    const DevWeight* gu[2] = {&L.gate_exps, &L.up_exps};
+    if ((rc = pf_k(c, pf_gemm_launch(gu, 2, P.xh_gather + (size_t)e * xh_bytes(H), P.part, P.part_bytes, kPfTokens, &S, &nc, st, e, P.moe_cnt + e, kPfMoeRows,
+                                     P.moe_base + e),
+                   "expert gate/up GEMM")))
+      return rc;
+  }
+  if ((rc = pf_k(c, pf_moe_swiglu_launch(P.part, S, EI, P.xh_act_e, P.moe_rowmap, P.moe_list, P.ssq, H, d.norm_eps, st), "expert SwiGLU"))) return rc;
+  for (uint32_t e = 0; e < d.num_experts; e++) {
+    const DevWeight* dn[1] = {&L.down_exps};
+    if ((rc = pf_k(c, pf_gemm_launch(dn, 1, P.xh_act_e + (size_t)e * xh_bytes(EI), P.part, P.part_bytes, kPfTokens, &S, &nc, st, e, P.moe_cnt + e, kPfMoeRows,
+                                     P.moe_base + e),
+                   "expert down GEMM")))
+      return rc;
+  }
+  // h += sum over the selected experts, in selection order, of routing weight * expert output (moe.rs:363-368), then the
+  // next layer's input
+  return pf_k(c, pf_moe_combine_launch(P.part, S, P.moe_tokmap, P.moe_w, topk, P.hidden, H, next_nw, next_xh, P.ssq, m, st), "MoE combine");
+}
+
 // m <= 128 prompt tokens at positions t.pos0 .. t.pos0+m-1 of the target sequence: fills every owned layer's K/V rows of that
 // sequence; the caller moves the sequence's position.  The first stage starts from the tokens' embedding rows, any other stage
 // from the block of hidden vectors its predecessor left in pf.hidden; a stage that is not the last leaves its output block there
@@ -82,13 +174,10 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
   if (rc) return rc;
   PfScratch& P = c->pf;
   const lgh_model_desc& d = c->d;
-  const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, F = d.intermediate_size;
+  const uint32_t H = d.hidden_size;
   const uint32_t pos0 = (uint32_t)t.pos0;
   const size_t slot_off = t.slot < 0 ? 0 : (size_t)t.slot * c->batch.cache_stride;
   hipStream_t st = c->stream;
-  auto K = [&](hipError_t e, const char* what) -> int {
-    return e == hipSuccess ? LGH_OK : fail(c, LGH_OPERATION_FAILED, std::string("batched prefill, ") + what + ": " + hipGetErrorString(e));
-  };
   if (c->first) {
     // The caller's `tokens` may be freed as soon as this returns (lgh_stage_prefill_batch does not synchronise), so the ids
     // go through a context-owned PINNED buffer, one slot per position; a slot is only rewritten after the copy that last
@@ -107,64 +196,22 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
     std::memcpy(P.tok_pinned + pos0, tokens, (size_t)m * 4);
     HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(P.tokens, P.tok_pinned + pos0, (size_t)m * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(c, LGH_OPERATION_FAILED, hipEventRecord(P.tok_copied, st));
-    if ((rc = K(embed_batch_launch(c->embd_type, c->embd_raw, P.tokens, P.hidden, H, m, st), "embedding"))) return rc;
+    if ((rc = pf_k(c, embed_batch_launch(c->embd_type, c->embd_raw, P.tokens, P.hidden, H, m, st), "embedding"))) return rc;
   }
-  if ((rc = K(pf_row_epi_launch(nullptr, 0, 0, 0, nullptr, P.hidden, H, c->layers[c->l0].attn_norm, P.xh_h, P.ssq, m, st), "attn_norm"))) return rc;
+  if ((rc = pf_block_input(c, c->layers[c->l0].attn_norm, m))) return rc;
   const float scale = 1.0f / std::sqrt((float)d.head_dim);  // layers.rs:374
   for (uint32_t li = c->l0; li < c->l1; li++) {
     LayerW& L = c->layers[li];
     float* const kcache = t.slot < 0 ? L.kcache : c->batch.kcache[li] + slot_off;
     float* const vcache = t.slot < 0 ? L.vcache : c->batch.vcache[li] + slot_off;
-    uint32_t S = 0, nc = 0;
-    const DevWeight* qkv[3] = {&L.wq, &L.wk, &L.wv};
-    if ((rc = K(pf_gemm_launch(qkv, 3, P.xh_h, P.part, P.part_bytes, m, &S, &nc, st), "qkv GEMM"))) return rc;
-    if ((rc = K(pf_qkv_epi_launch(P.part, S, nc, QD, KD, d.head_dim, L.bq, L.bk, L.bv, c->rope_cs, pos0, d.max_seq_len, P.q, kcache, vcache, P.ssq, H,
-                                  d.norm_eps, (int)d.use_neox_rope, m, st),
-                "qkv epilogue")))
-      return rc;
+    if ((rc = pf_qkv_step(c, L, kcache, vcache, pos0, m))) return rc;
     if (li + 1 == c->l1 && c->last) break;   // the model's last layer: its K/V rows are written, its output would be discarded
-    if ((rc = K(attn_prefill_launch(P.q, kcache, vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
-                "attention")))
+    if ((rc = pf_k(c, attn_prefill_launch(P.q, kcache, vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
+                   "attention")))
       return rc;
-    const DevWeight* wo[1] = {&L.wo};
-    if ((rc = K(pf_gemm_launch(wo, 1, P.xh_attn, P.part, P.part_bytes, m, &S, &nc, st), "wo GEMM"))) return rc;
-    if ((rc = K(pf_row_epi_launch(P.part, S, nc, 0, L.bo, P.hidden, H, L.ffn_norm, P.xh_h, P.ssq, m, st), "wo epilogue"))) return rc;
+    if ((rc = pf_wo_step(c, L, m))) return rc;
     const float* next_nw = li + 1 < c->l1 ? c->layers[li + 1].attn_norm : nullptr;   // nullptr: the block goes to the next stage as f32
-    uint8_t* next_xh = next_nw ? P.xh_h : nullptr;
-    if (!L.moe()) {
-      const DevWeight* gu[2] = {&L.gate, &L.up};
-      if ((rc = K(pf_gemm_launch(gu, 2, P.xh_h, P.part, P.part_bytes, m, &S, &nc, st), "gate/up GEMM"))) return rc;
-      if ((rc = K(pf_swiglu_launch(P.part, S, F, P.xh_act, P.ssq, H, d.norm_eps, m, st), "SwiGLU"))) return rc;
-      const DevWeight* dn[1] = {&L.down};
-      if ((rc = K(pf_gemm_launch(dn, 1, P.xh_act, P.part, P.part_bytes, m, &S, &nc, st), "down GEMM"))) return rc;
-      if ((rc = K(pf_row_epi_launch(P.part, S, nc, 0, nullptr, P.hidden, H, next_nw, next_xh, P.ssq, m, st), "down epilogue"))) return rc;
-      continue;
-    }
-    // ---- MoE (moe.rs:321-413): route every token of the block (f32, the decode router), group the (token, slot) pairs by
-    // expert, and run each expert once over its rows: gather -> gate|up GEMM -> SwiGLU -> down GEMM -> rows back to tokens
-    const uint32_t topk = d.num_experts_per_token, EI = L.gate_exps.n;
-    if ((rc = K(moe_router_launch(P.hidden, L.ffn_norm, d.norm_eps, L.router, H, d.num_experts, topk, P.moe_sel, P.moe_w, st, m), "router"))) return rc;
-    if ((rc = K(pf_moe_group_launch(P.moe_sel, m, topk, d.num_experts, P.moe_cnt, P.moe_base, P.moe_list, P.moe_rowmap, P.moe_tokmap, st), "expert grouping")))
-      return rc;
-    if ((rc = K(pf_moe_gather_launch(P.xh_h, H, P.moe_list, P.moe_cnt, P.xh_gather, d.num_experts, st), "expert gather"))) return rc;
-    for (uint32_t e = 0; e < d.num_experts; e++) {   // every expert's gate|up over its rows, partial sums side by side in one row space
-      const DevWeight* gu[2] = {&L.gate_exps, &L.up_exps};
-      if ((rc = K(pf_gemm_launch(gu, 2, P.xh_gather + (size_t)e * xh_bytes(H), P.part, P.part_bytes, kPfTokens, &S, &nc, st, e, P.moe_cnt + e, kPfMoeRows,
-                                 P.moe_base + e),
-                  "expert gate/up GEMM")))
-        return rc;
-    }
-    if ((rc = K(pf_moe_swiglu_launch(P.part, S, EI, P.xh_act_e, P.moe_rowmap, P.moe_list, P.ssq, H, d.norm_eps, st), "expert SwiGLU"))) return rc;
-    for (uint32_t e = 0; e < d.num_experts; e++) {
-      const DevWeight* dn[1] = {&L.down_exps};
-      if ((rc = K(pf_gemm_launch(dn, 1, P.xh_act_e + (size_t)e * xh_bytes(EI), P.part, P.part_bytes, kPfTokens, &S, &nc, st, e, P.moe_cnt + e, kPfMoeRows,
-                                 P.moe_base + e),
-                  "expert down GEMM")))
-        return rc;
-    }
-    // h += sum over the selected experts, in selection order, of routing weight * expert output (moe.rs:363-368), then the
-    // next layer's input
-    if ((rc = K(pf_moe_combine_launch(P.part, S, P.moe_tokmap, P.moe_w, topk, P.hidden, H, next_nw, next_xh, P.ssq, m, st), "MoE combine"))) return rc;
+    if ((rc = L.moe() ? pf_moe_step(c, L, next_nw, m) : pf_ffn_step(c, L, next_nw, m))) return rc;
   }
   c->stats.tokens_processed += m;
   return LGH_OK;

@@ -149,7 +149,6 @@ int lgh_op_mat_mat(int device, uint32_t type, const void* w, const float* x, flo
   float* dout = t.up(nullptr, (size_t)kPfTokens * n);
   uint8_t* xh = nullptr;
   float *part = nullptr, *ssq = nullptr;
-  if (n > 2048u * kPfSsqChunks) return LGH_UNSUPPORTED;
   if (!dx || !dout || dev_alloc(t.c, (void**)&xh, xh_bytes((uint32_t)k)) || dev_alloc(t.c, (void**)&part, pb) ||
       dev_alloc(t.c, (void**)&ssq, (size_t)kPfTokens * kPfSsqChunks * 4))
     return LGH_ALLOCATION_FAILED;
@@ -160,7 +159,9 @@ int lgh_op_mat_mat(int device, uint32_t type, const void* w, const float* x, flo
   uint32_t S = 0, nc = 0;
   if (pf_to_xh_launch(dx, (uint32_t)k, xh, (uint32_t)m, st) != hipSuccess) return LGH_OPERATION_FAILED;
   if (pf_gemm_launch(Ws, 1, xh, part, pb, (uint32_t)m, &S, &nc, st) != hipSuccess) return LGH_OPERATION_FAILED;
-  if (pf_row_epi_launch(part, S, nc, 0, nullptr, dout, (uint32_t)n, nullptr, nullptr, ssq, (uint32_t)m, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  // (no sums of squares for rows wider than the epilogue keeps them for: the GEMM's plan, not the norm, is what such a shape is for)
+  if (pf_row_epi_launch(part, S, nc, 0, nullptr, dout, (uint32_t)n, nullptr, nullptr, n > 2048u * kPfSsqChunks ? nullptr : ssq, (uint32_t)m, st) != hipSuccess)
+    return LGH_OPERATION_FAILED;
   return t.down(out, dout, m * n);
 }
 
@@ -560,6 +561,21 @@ int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint
   return t.down(out, v.attn_out, n_heads * d);
 }
 
+// an XH matrix's first m rows, un-swizzled and widened to f32: out [m][k]
+static int xh_down(Tmp& t, const uint8_t* xh, size_t m, size_t k, float* out) {
+  const size_t xb = xh_bytes((uint32_t)k);
+  std::vector<uint8_t> host(xb);
+  int rc = down_bytes(t, host.data(), xh, xb);
+  if (rc) return rc;
+  for (size_t tk = 0; tk < m; tk++)
+    for (size_t i = 0; i < k; i++) {
+      uint16_t h;
+      std::memcpy(&h, host.data() + xh_offset((uint32_t)tk, (uint32_t)i), 2);
+      out[tk * k + i] = half_to_float(h);
+    }
+  return LGH_OK;
+}
+
 int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads, size_t n_kv,
                              size_t head_dim, size_t max_seq, float scale, size_t pos0, size_t m_tokens) {
   // causal Backend::attention (ops.rs:1353-1472) of a block of prompt tokens as the batched prefill runs it: the f16 XH matrix that
@@ -578,16 +594,7 @@ int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, c
   if (attn_prefill_launch(dq, dk, dv, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, scale, (uint32_t)pos0,
                           (uint32_t)m_tokens, xh, st) != hipSuccess)
     return LGH_UNSUPPORTED;
-  std::vector<uint8_t> host(xb);
-  int rc = down_bytes(t, host.data(), xh, xb);
-  if (rc) return rc;
-  for (size_t tk = 0; tk < m_tokens; tk++)
-    for (size_t k = 0; k < qd; k++) {
-      uint16_t h;
-      std::memcpy(&h, host.data() + xh_offset((uint32_t)tk, (uint32_t)k), 2);
-      out[tk * qd + k] = half_to_float(h);
-    }
-  return LGH_OK;
+  return xh_down(t, xh, m_tokens, qd, out);
 }
 
 // ---- device-resident weights by tensor name: CudaBackend::load_model_weights + the `b.name()` lookups of its vec_mat /
@@ -967,6 +974,195 @@ int lgh_op_moe_experts(int device, uint32_t type_gate_up, const void* w_gate, co
   if (sel_out && (rc = down_bytes(t, sel_out, v.moe_sel, top_k * 4))) return rc;
   if (sel_w_out && (rc = t.down(sel_w_out, v.moe_w, top_k))) return rc;
   return t.down(out, v.hidden, hidden);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The batched prompt path's layer steps (engine_prefill.hip: pf_block_input, pf_qkv_step, pf_wo_step, pf_ffn_step, pf_moe_step) one at
+// a time on a bare one-layer context with the path's own scratch (pf_ensure), for kernel-level tests
+// (tests/test_gpu_prefill_ref.py).  Test support: not part of the inference API.
+// Before the first launch every scratch buffer the kernels read is filled with NaN bit patterns (f32 0x7FC0BEEF, f16 0x7E5A), so that
+// anything consumed without having been produced shows in the output; the padding rows of an XH block ARE read by the MFMAs and their
+// partial sums are never consumed.  The MoE index tables get in-range sentinels instead (a NaN pattern read as an index would address
+// outside the buffers), each one a value the kernels must NOT leave there: lists 0x7F7F, tokmap kPfMoeRows - 1, rowmap 0 (expert 0,
+// row 0 — what a zero-filled table holds; the grouping kernel's own -1 on every padding row has to replace it), everything else 0x55.
+// ------------------------------------------------------------------------------------------------
+static bool pf_poison(lgh_ctx* c, void* p, size_t bytes, uint32_t word) {
+  return !p || !bytes || hipMemsetD32Async((hipDeviceptr_t)p, (int)word, bytes / 4, c->stream) == hipSuccess;
+}
+
+// the model fields, the layer and the scratch of a one-layer context; F = dense FFN width (0: none), E / top_k / EI = experts (0: none)
+static int pf_test_ctx(Tmp& t, const LayerW& Lw, size_t H, size_t head_dim, size_t n_heads, size_t n_kv, size_t F, size_t E, size_t top_k, size_t EI,
+                       float eps) {
+  lgh_ctx* c = t.c;
+  lgh_model_desc& d = c->d;
+  d.norm_eps = eps;
+  d.hidden_size = (uint32_t)H;
+  d.head_dim = (uint32_t)head_dim;
+  d.num_heads = (uint32_t)n_heads;
+  d.num_kv_heads = (uint32_t)n_kv;
+  d.intermediate_size = (uint32_t)F;
+  d.num_experts = (uint32_t)E;
+  d.num_experts_per_token = (uint32_t)top_k;
+  d.expert_intermediate_size = (uint32_t)EI;
+  c->layers.assign(1, Lw);
+  c->l0 = 0;
+  c->l1 = 1;
+  if (int rc = pf_ensure(c)) return rc;
+  const PfScratch& P = c->pf;
+  const uint32_t QD = d.num_heads * d.head_dim, kF32 = 0x7FC0BEEFu, kF16 = 0x7E5A7E5Au;
+  const bool ok =
+      pf_poison(c, P.xh_h, xh_bytes(d.hidden_size), kF16) && pf_poison(c, P.xh_attn, xh_bytes(QD), kF16) &&
+      pf_poison(c, P.xh_act, xh_bytes((uint32_t)std::max(F, EI)), kF16) && pf_poison(c, P.hidden, (size_t)kPfTokens * H * 4, kF32) &&
+      pf_poison(c, P.q, (size_t)kPfTokens * QD * 4, kF32) && pf_poison(c, P.part, P.part_bytes, kF32) &&
+      pf_poison(c, P.ssq, (size_t)kPfTokens * kPfSsqChunks * 4, kF32) && pf_poison(c, P.moe_w, E ? (size_t)kPfTokens * top_k * 4 : 0, kF32) &&
+      pf_poison(c, P.moe_sel, E ? (size_t)kPfTokens * top_k * 4 : 0, 0x55u) && pf_poison(c, P.moe_cnt, E ? (size_t)kPfMaxExperts * 4 : 0, 0x55u) &&
+      pf_poison(c, P.moe_base, E ? (size_t)kPfMaxExperts * 4 : 0, 0x55u) &&
+      pf_poison(c, P.moe_list, E ? (size_t)kPfMaxExperts * kPfTokens * 4 : 0, 0x7F7Fu) &&
+      pf_poison(c, P.moe_rowmap, E ? (size_t)kPfMoeRows * 4 : 0, 0u) &&
+      pf_poison(c, P.moe_tokmap, E ? (size_t)kPfTokens * kPfMaxTopK * 4 : 0, (uint32_t)kPfMoeRows - 1) &&
+      pf_poison(c, P.xh_gather, E ? xh_bytes(d.hidden_size) * E : 0, kF16) && pf_poison(c, P.xh_act_e, E ? xh_bytes((uint32_t)EI) * E : 0, kF16);
+  return ok ? LGH_OK : LGH_OPERATION_FAILED;
+}
+
+static int pf_up_weight(Tmp& t, DevWeight& W, uint32_t type, const void* w, size_t k, size_t n, size_t n_stack = 1) {
+  const size_t nb = weight_bytes(type, k, n);
+  if (!nb || !w) return LGH_SHAPE_MISMATCH;
+  if (int rc = upload_matrix(t.c, W, (int)type, (uint32_t)k, (uint32_t)n, (uint32_t)n_stack, -1, w, nb * n_stack)) return rc;
+  return pf_supported_type(W.type) && n % 16 == 0 ? LGH_OK : LGH_UNSUPPORTED;
+}
+
+// hidden, the next XH (when a next norm weight was given) and the sums of squares of the first m tokens
+static int pf_down_block(Tmp& t, size_t m, size_t H, bool with_xh, float* hidden_out, float* xh_out, float* ssq_out) {
+  const PfScratch& P = t.c->pf;
+  int rc;
+  if ((rc = t.down(hidden_out, P.hidden, m * H)) || (rc = t.down(ssq_out, P.ssq, m * kPfSsqChunks))) return rc;
+  return with_xh ? xh_down(t, P.xh_h, m, H, xh_out) : LGH_OK;
+}
+
+static bool pf_block_shape_ok(size_t H, size_t m) { return H && H % 256 == 0 && H <= 2048u * kPfSsqChunks && m >= 1 && m <= (size_t)kPfTokens; }
+
+int lgh_op_pf_qkv(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* hidden, const float* norm_w,
+                  float eps, size_t hidden_size, size_t head_dim, size_t n_heads, size_t n_kv_heads, int neox, size_t max_seq_len, size_t pos0,
+                  size_t m_tokens, float rope_base, float rope_scale, float* q_out, float* k_cache, float* v_cache) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!types || !w || !hidden || !norm_w || !q_out || !k_cache || !v_cache || n_kv_heads == 0 || n_heads % n_kv_heads || rope_scale == 0.0f ||
+      max_seq_len > 0x7FFFFFFFu || !pf_block_shape_ok(hidden_size, m_tokens) || pos0 + m_tokens > max_seq_len)
+    return LGH_INVALID_ARGUMENT;
+  const size_t H = hidden_size, QD = n_heads * head_dim, KD = n_kv_heads * head_dim, rows[3] = {QD, KD, KD};
+  if ((head_dim != 64 && head_dim != 128) || QD % 256 || KD % 16) return LGH_UNSUPPORTED;   // (pf_eligible's shapes)
+  LayerW Lw;
+  DevWeight* const W[3] = {&Lw.wq, &Lw.wk, &Lw.wv};
+  float** const db[3] = {&Lw.bq, &Lw.bk, &Lw.bv};
+  int rc;
+  for (int s = 0; s < 3; s++) {
+    if ((rc = pf_up_weight(t, *W[s], types[s], w[s], H, rows[s]))) return rc;
+    if (bias && bias[s] && !(*db[s] = t.up(bias[s], rows[s]))) return LGH_ALLOCATION_FAILED;
+  }
+  lgh_model_desc& d = t.c->d;
+  d.max_seq_len = (uint32_t)max_seq_len;
+  d.rope_freq_base = rope_base;
+  d.rope_freq_scale = rope_scale;
+  d.use_neox_rope = neox ? 1 : 0;
+  d.head_dim = (uint32_t)head_dim;
+  std::vector<float> cs;
+  rope_table_host(d, cs);
+  const size_t cache = n_kv_heads * max_seq_len * head_dim;
+  t.c->rope_cs = t.up(cs.data(), cs.size());
+  Lw.attn_norm = t.up(norm_w, H);
+  Lw.kcache = t.up(k_cache, cache);
+  Lw.vcache = t.up(v_cache, cache);
+  if (!t.c->rope_cs || !Lw.attn_norm || !Lw.kcache || !Lw.vcache) return LGH_ALLOCATION_FAILED;
+  if ((rc = pf_test_ctx(t, Lw, H, head_dim, n_heads, n_kv_heads, 0, 0, 0, 0, eps))) return rc;
+  if (hipMemcpyAsync(t.c->pf.hidden, hidden, m_tokens * H * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  if ((rc = pf_block_input(t.c, Lw.attn_norm, (uint32_t)m_tokens))) return rc;
+  if ((rc = pf_qkv_step(t.c, t.c->layers[0], Lw.kcache, Lw.vcache, (uint32_t)pos0, (uint32_t)m_tokens))) return rc;
+  if ((rc = t.down(q_out, t.c->pf.q, m_tokens * QD)) || (rc = t.down(k_cache, Lw.kcache, cache))) return rc;
+  return t.down(v_cache, Lw.vcache, cache);
+}
+
+int lgh_op_pf_linear(int device, uint32_t type, const void* w, const float* bias, const float* x, size_t k, size_t hidden_size, const float* resid,
+                     const float* next_nw, size_t m_tokens, float* hidden_out, float* xh_out, float* ssq_out) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w || !x || !resid || !next_nw || !hidden_out || !xh_out || !ssq_out || !pf_block_shape_ok(hidden_size, m_tokens) || k == 0 || k % 256)
+    return LGH_INVALID_ARGUMENT;
+  const size_t H = hidden_size;
+  LayerW Lw;
+  int rc;
+  if ((rc = pf_up_weight(t, Lw.wo, type, w, k, H))) return rc;
+  if (bias && !(Lw.bo = t.up(bias, H))) return LGH_ALLOCATION_FAILED;
+  Lw.ffn_norm = t.up(next_nw, H);
+  float* dx = t.up(x, m_tokens * k);
+  if (!Lw.ffn_norm || !dx) return LGH_ALLOCATION_FAILED;
+  if ((rc = pf_test_ctx(t, Lw, H, 64, k / 64, k / 64, 0, 0, 0, 0, 1e-5f))) return rc;   // (the wo input is [tokens][heads * head_dim] = k wide)
+  const PfScratch& P = t.c->pf;
+  if (hipMemcpyAsync(P.hidden, resid, m_tokens * H * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  if (pf_to_xh_launch(dx, (uint32_t)k, P.xh_attn, (uint32_t)m_tokens, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  if ((rc = pf_wo_step(t.c, t.c->layers[0], (uint32_t)m_tokens))) return rc;
+  return pf_down_block(t, m_tokens, H, true, hidden_out, xh_out, ssq_out);
+}
+
+int lgh_op_pf_ffn(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down,
+                  const float* hidden, const float* norm_w, const float* next_nw, float eps, size_t hidden_size, size_t ffn, size_t m_tokens,
+                  float* hidden_out, float* xh_out, float* ssq_out, float* act_out) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w_gate || !w_up || !w_down || !hidden || !norm_w || !hidden_out || !ssq_out || (next_nw && !xh_out) ||
+      !pf_block_shape_ok(hidden_size, m_tokens) || ffn == 0 || ffn % 256)
+    return LGH_INVALID_ARGUMENT;
+  const size_t H = hidden_size;
+  LayerW Lw;
+  int rc;
+  if ((rc = pf_up_weight(t, Lw.gate, type_gate_up, w_gate, H, ffn)) || (rc = pf_up_weight(t, Lw.up, type_gate_up, w_up, H, ffn)) ||
+      (rc = pf_up_weight(t, Lw.down, type_down, w_down, ffn, H)))
+    return rc;
+  Lw.ffn_norm = t.up(norm_w, H);
+  float* dnext = next_nw ? t.up(next_nw, H) : nullptr;
+  if (!Lw.ffn_norm || (next_nw && !dnext)) return LGH_ALLOCATION_FAILED;
+  if ((rc = pf_test_ctx(t, Lw, H, 64, H / 64, H / 64, ffn, 0, 0, 0, eps))) return rc;
+  if (hipMemcpyAsync(t.c->pf.hidden, hidden, m_tokens * H * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  if ((rc = pf_block_input(t.c, Lw.ffn_norm, (uint32_t)m_tokens))) return rc;
+  if ((rc = pf_ffn_step(t.c, t.c->layers[0], dnext, (uint32_t)m_tokens))) return rc;
+  if (act_out && (rc = xh_down(t, t.c->pf.xh_act, m_tokens, ffn, act_out))) return rc;
+  return pf_down_block(t, m_tokens, H, dnext != nullptr, hidden_out, xh_out, ssq_out);
+}
+
+int lgh_op_pf_moe(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down,
+                  const float* router, size_t n_experts, size_t top_k, const float* hidden, const float* norm_w, const float* next_nw, float eps,
+                  size_t hidden_size, size_t ffn, size_t m_tokens, float* hidden_out, float* xh_out, float* ssq_out, int* sel_out, float* sel_w_out,
+                  int* counts_out, int* bases_out, int* lists_out, int* rowmap_out, int* tokmap_out, float* act_out) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w_gate || !w_up || !w_down || !router || !hidden || !norm_w || !hidden_out || !ssq_out || (next_nw && !xh_out) || !sel_out || !sel_w_out ||
+      !counts_out || !bases_out || !lists_out || !rowmap_out || !tokmap_out || !pf_block_shape_ok(hidden_size, m_tokens) || ffn == 0 || ffn % 256 ||
+      top_k == 0 || top_k > n_experts)
+    return LGH_INVALID_ARGUMENT;
+  if (n_experts > (size_t)kPfMaxExperts || top_k > (size_t)kPfMaxTopK || (size_t)kPfTokens * top_k + 15 * n_experts > (size_t)kPfMoeRows)
+    return LGH_UNSUPPORTED;   // (pf_eligible's condition)
+  const size_t H = hidden_size, E = n_experts;
+  LayerW Lw;
+  int rc;
+  if ((rc = pf_up_weight(t, Lw.gate_exps, type_gate_up, w_gate, H, ffn, E)) || (rc = pf_up_weight(t, Lw.up_exps, type_gate_up, w_up, H, ffn, E)) ||
+      (rc = pf_up_weight(t, Lw.down_exps, type_down, w_down, ffn, H, E)))
+    return rc;
+  Lw.ffn_norm = t.up(norm_w, H);
+  Lw.router = t.up(router, E * H);
+  float* dnext = next_nw ? t.up(next_nw, H) : nullptr;
+  if (!Lw.ffn_norm || !Lw.router || (next_nw && !dnext)) return LGH_ALLOCATION_FAILED;
+  if ((rc = pf_test_ctx(t, Lw, H, 64, H / 64, H / 64, 0, E, top_k, ffn, eps))) return rc;
+  const PfScratch& P = t.c->pf;
+  if (hipMemcpyAsync(P.hidden, hidden, m_tokens * H * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  if ((rc = pf_block_input(t.c, Lw.ffn_norm, (uint32_t)m_tokens))) return rc;
+  if ((rc = pf_moe_step(t.c, t.c->layers[0], dnext, (uint32_t)m_tokens))) return rc;
+  if ((rc = down_bytes(t, sel_out, P.moe_sel, m_tokens * top_k * 4)) || (rc = t.down(sel_w_out, P.moe_w, m_tokens * top_k)) ||
+      (rc = down_bytes(t, counts_out, P.moe_cnt, E * 4)) || (rc = down_bytes(t, bases_out, P.moe_base, E * 4)) ||
+      (rc = down_bytes(t, lists_out, P.moe_list, E * kPfTokens * 4)) || (rc = down_bytes(t, rowmap_out, P.moe_rowmap, (size_t)kPfMoeRows * 4)) ||
+      (rc = down_bytes(t, tokmap_out, P.moe_tokmap, m_tokens * top_k * 4)))
+    return rc;
+  for (size_t e = 0; act_out && e < E; e++)   // every expert's SwiGLU rows as the down GEMM reads them, rows past its count included
+    if ((rc = xh_down(t, P.xh_act_e + e * xh_bytes((uint32_t)ffn), kPfTokens, ffn, act_out + e * kPfTokens * ffn))) return rc;
+  return pf_down_block(t, m_tokens, H, dnext != nullptr, hidden_out, xh_out, ssq_out);
 }
 
 }  // extern "C"

@@ -603,7 +603,19 @@ hipError_t pf_gemm_launch(const DevWeight* const* W, int nw, const uint8_t* xh, 
 // chunk `ch` (8 consecutive elements starting at 8*ch) of token t
 __device__ __forceinline__ void xh_store_chunk(uint8_t* xh, uint32_t t, uint32_t ch, const float v[8]) {
   const uint32_t b = ch >> 5, q = ch & 31;
-  h16x8 o = {(_Float16)v[0], (_Float16)v[2], (_Float16)v[1], (_Float16)v[3], (_Float16)v[4], (_Float16)v[6], (_Float16)v[5], (_Float16)v[7]};
+  // Every element is f16(f32 value), two roundings when the caller passes an f32 product.  The empty asm keeps that product an f32
+  // value: without it hipcc folds the caller's multiply into the conversion for SOME elements of the chunk (v_fma_mix{lo,hi}_f16, one
+  // rounding of the exact product; the others go through v_cvt_pk_f16_f32), and the same product is rounded differently depending on
+  // its place in the chunk (found by tests/test_gpu_prefill_ref.py: the next XH against f16(hidden * norm_w) of the returned hidden).
+  // NOT dead code: nothing checks it at build time, only the bit-exact XH checks of test_linear_step, test_ffn_step and test_moe_step
+  // on the GPU fail without it (or when a compiler finds another way to fold the product into the conversion).
+  float r[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    r[j] = v[j];
+    asm("" : "+v"(r[j]));
+  }
+  h16x8 o = {(_Float16)r[0], (_Float16)r[2], (_Float16)r[1], (_Float16)r[3], (_Float16)r[4], (_Float16)r[6], (_Float16)r[5], (_Float16)r[7]};
   *reinterpret_cast<h16x8*>(xh + (size_t)b * kPfSlabBytes + t * 512 + ((q ^ (t & 15)) << 4)) = o;
 }
 
@@ -669,7 +681,8 @@ uint32_t pf_ssq_chunks(uint32_t H) { return (H + 2047) / 2048; }
 
 hipError_t pf_row_epi_launch(const float* part, uint32_t S, uint32_t ncols, uint32_t col0, const float* bias, float* hidden, uint32_t H,
                              const float* nw, uint8_t* xh, float* ssq, uint32_t m_tokens, hipStream_t st, const float* moe_w) {
-  if (H % 8 || (xh && (!nw || !ssq)) || (S && (ncols % 4 || col0 % 4)) || pf_ssq_chunks(H) > (uint32_t)kPfSsqChunks) return hipErrorInvalidValue;
+  // (sums of squares are kept for at most kPfSsqChunks chunks; a row wider than that can be added up, not normed)
+  if (H % 8 || (xh && (!nw || !ssq)) || (S && (ncols % 4 || col0 % 4)) || (ssq && pf_ssq_chunks(H) > (uint32_t)kPfSsqChunks)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pf_resid_kernel, dim3(pf_ssq_chunks(H), m_tokens), dim3(256), 0, st, part, S, ncols, col0, bias, hidden, H, nw, xh, ssq, moe_w);
   return hipGetLastError();
 }

@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "lgh_set_sampler_ex", "lgh_batch_set_sampler_ex", "lgh_get_sampler_mu", "lgh_op_sample_ex",
     "lgh_op_attention_decode", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
     "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts",
+    "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -232,6 +233,11 @@ def load_library() -> C.CDLL:
         "lgh_op_linear_chain": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, f32, vp, C.c_int, vp, u32, vp, sz, vp, vp, vp,
                                           C.POINTER(C.c_int)]),
         "lgh_op_moe_experts": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
+        "lgh_op_pf_qkv": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, C.c_int, sz, sz, sz, f32, f32, vp, vp, vp]),
+        "lgh_op_pf_linear": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, sz, vp, vp, vp]),
+        "lgh_op_pf_ffn": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, vp, vp, vp, f32, sz, sz, sz, vp, vp, vp, vp]),
+        "lgh_op_pf_moe": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, vp, sz, sz, vp, vp, vp, f32, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -779,6 +785,84 @@ def op_moe_experts(type_gate_up: int, w_gate, w_up, type_down: int, w_down, n_ex
                                            hidden, ffn, top_k, _ptr(r), _ptr(s), _ptr(sw), x.ctypes.data, nw.ctypes.data, eps,
                                            out.ctypes.data, so.ctypes.data, swo.ctypes.data), "moe_experts")
     return out, so, swo
+
+
+PF_SSQ_CHUNKS = 8      # kPfSsqChunks: sums of squares per token, one per 2048 columns
+PF_TOKENS = 128        # kPfTokens
+PF_MOE_ROWS = 384      # kPfMoeRows
+
+
+def op_pf_qkv(types, ws, biases, hidden, norm_w, eps: float, head_dim: int, n_heads: int, n_kv: int, neox: bool, k_cache, v_cache, pos0: int,
+              rope_base: float, rope_scale: float, device: int = 0):
+    """The batched prompt path's QKV step on a block hidden [m, H]: XH(hidden * norm_w), the q|k|v GEMM, 1/rms, bias, RoPE at pos0 + t.
+    -> (q [m, n_heads * head_dim], k_cache, v_cache) after the call (copies; caches [n_kv, max_seq, head_dim])."""
+    h, nw = _f32(hidden), _f32(norm_w)
+    m, H = h.shape
+    kc, vc = np.array(k_cache, dtype=np.float32, copy=True), np.array(v_cache, dtype=np.float32, copy=True)
+    ws = [np.ascontiguousarray(w, dtype=np.uint8) for w in ws]
+    bs = [None if b is None else _f32(b) for b in biases]
+    tarr = np.array(types, dtype=np.uint32)
+    warr = (C.c_void_p * 3)(*[w.ctypes.data for w in ws])
+    barr = (C.c_void_p * 3)(*[_ptr(b) for b in bs])
+    q = np.empty((m, n_heads * head_dim), np.float32)
+    _chk(load_library().lgh_op_pf_qkv(device, tarr.ctypes.data, C.cast(warr, C.c_void_p), C.cast(barr, C.c_void_p), h.ctypes.data, nw.ctypes.data,
+                                      eps, H, head_dim, n_heads, n_kv, int(bool(neox)), kc.shape[1], pos0, m, rope_base, rope_scale,
+                                      q.ctypes.data, kc.ctypes.data, vc.ctypes.data), "pf_qkv")
+    return q, kc, vc
+
+
+def _pf_outs(m: int, H: int):
+    return np.empty((m, H), np.float32), np.full((m, H), np.nan, np.float32), np.full((m, PF_SSQ_CHUNKS), np.nan, np.float32)
+
+
+def op_pf_linear(ggml_type: int, w, x, resid, next_nw, *, bias=None, device: int = 0):
+    """The batched prompt path's wo step: resid [m, H] + W . x (+ bias), x [m, k].  -> (hidden [m, H], next XH [m, H] widened to f32,
+    ssq [m, 8])."""
+    w, x, r, nn = np.ascontiguousarray(w, dtype=np.uint8), _f32(x), _f32(resid), _f32(next_nw)
+    b = None if bias is None else _f32(bias)
+    (m, k), H = x.shape, r.shape[1]
+    ho, xo, so = _pf_outs(m, H)
+    _chk(load_library().lgh_op_pf_linear(device, ggml_type, w.ctypes.data, _ptr(b), x.ctypes.data, k, H, r.ctypes.data, nn.ctypes.data, m,
+                                         ho.ctypes.data, xo.ctypes.data, so.ctypes.data), "pf_linear")
+    return ho, xo, so
+
+
+def op_pf_ffn(type_gate_up: int, w_gate, w_up, type_down: int, w_down, hidden, norm_w, ffn: int, *, next_nw=None, eps: float = 1e-5,
+              want_act: bool = True, device: int = 0):
+    """The batched prompt path's dense FFN step on hidden [m, H].  -> (hidden, next XH (NaN without next_nw), ssq, act [m, ffn] = the
+    f16 SwiGLU output the down GEMM read, widened; None with want_act = False)."""
+    wg, wu, wd = (np.ascontiguousarray(w, dtype=np.uint8) for w in (w_gate, w_up, w_down))
+    h, nw = _f32(hidden), _f32(norm_w)
+    nn = None if next_nw is None else _f32(next_nw)
+    m, H = h.shape
+    ho, xo, so = _pf_outs(m, H)
+    act = np.empty((m, ffn), np.float32) if want_act else None
+    _chk(load_library().lgh_op_pf_ffn(device, type_gate_up, wg.ctypes.data, wu.ctypes.data, type_down, wd.ctypes.data, h.ctypes.data,
+                                      nw.ctypes.data, _ptr(nn), eps, H, ffn, m, ho.ctypes.data, xo.ctypes.data, so.ctypes.data,
+                                      _ptr(act)), "pf_ffn")
+    return ho, xo, so, act
+
+
+def op_pf_moe(type_gate_up: int, w_gate, w_up, type_down: int, w_down, router, n_experts: int, top_k: int, hidden, norm_w, ffn: int, *,
+              next_nw=None, eps: float = 1e-5, want_act: bool = True, device: int = 0):
+    """The batched prompt path's MoE step on hidden [m, H].  -> dict: hidden, xh, ssq, sel / w / tokmap [m, top_k], counts / bases [E],
+    lists [E, 128], rowmap [384], act [E, 128, ffn] (every expert's f16 SwiGLU rows as its down GEMM read them; left out with want_act = False)."""
+    wg, wu, wd = (np.ascontiguousarray(w, dtype=np.uint8) for w in (w_gate, w_up, w_down))
+    h, nw, r = _f32(hidden), _f32(norm_w), _f32(router)
+    nn = None if next_nw is None else _f32(next_nw)
+    m, H = h.shape
+    ho, xo, so = _pf_outs(m, H)
+    o = dict(hidden=ho, xh=xo, ssq=so, sel=np.empty((m, top_k), np.int32), w=np.empty((m, top_k), np.float32),
+             counts=np.empty(n_experts, np.int32), bases=np.empty(n_experts, np.int32), lists=np.empty((n_experts, PF_TOKENS), np.int32),
+             rowmap=np.empty(PF_MOE_ROWS, np.int32), tokmap=np.empty((m, top_k), np.int32))
+    act = np.empty((n_experts, PF_TOKENS, ffn), np.float32) if want_act else None
+    _chk(load_library().lgh_op_pf_moe(device, type_gate_up, wg.ctypes.data, wu.ctypes.data, type_down, wd.ctypes.data, r.ctypes.data, n_experts,
+                                      top_k, h.ctypes.data, nw.ctypes.data, _ptr(nn), eps, H, ffn, m, ho.ctypes.data, xo.ctypes.data,
+                                      so.ctypes.data, o["sel"].ctypes.data, o["w"].ctypes.data, o["counts"].ctypes.data, o["bases"].ctypes.data,
+                                      o["lists"].ctypes.data, o["rowmap"].ctypes.data, o["tokmap"].ctypes.data, _ptr(act)), "pf_moe")
+    if want_act:
+        o["act"] = act
+    return o
 
 
 def op_attention_kv8(kv_cache_type: int, q, k_bytes, v_bytes, k_scale, v_scale, k_new, v_new, scale: float, pos: int, n_splits: int = 8,

@@ -31,9 +31,11 @@ def _check_gemm(got, want):
 
 
 @pytest.mark.parametrize("tname", FUSED)
-@pytest.mark.parametrize("k,n,m", [(256, 16, 1), (1024, 272, 37), (2048, 64, 128), (5632, 80, 100), (4096, 1040, 128)])
+@pytest.mark.parametrize("k,n,m", [(256, 16, 1), (1024, 272, 37), (2048, 64, 128), (5632, 80, 100), (4096, 1040, 128), (1280, 13312, 17)])
 def test_mat_mat_matches_dequantized_product(gpu, pkg, orc, tname, k, n, m):
-    """One block / ragged token counts / uneven k-splits (22 blocks) / more than one row group and several splits."""
+    """One block / ragged token counts / 22 k-splits of one block each / more than one row group and several splits / two blocks
+    per split with a shorter last split (the only shape here whose workgroups loop over k; tests/test_gpu_prefill_ref.py holds the
+    GEMM to its f32 bound)."""
     t, raw = _weights(pkg, tname, k, n)
     x = np.random.default_rng(k + n + m).standard_normal((m, k)).astype(np.float32)
     w = orc.dequantize(t, raw, k * n).reshape(n, k).astype(np.float64)
