@@ -114,11 +114,14 @@ enum {
   LGH_FLAG_KV_INT8 = 1u << 4,        /* KV cache as the reference's QuantizedKVCache with KVCacheFormat::Int8 (src/model/kv_quantized.rs): int8
                                         rows + one f32 scale per (kv head, position), a quarter of the f32 cache.  (Same as kv_cache_type =
                                         LGH_KV_INT8; no CLI flag of the reference reaches this format, see kv_cache_type.) */
-  /* bits 1, 3, 5, 6, 7 and 24..31 selected the decode structures that round 2 built and measured SLOWER than the default graph of
+  /* bits 1, 3, 5, 6, 7 and 24..30 selected the decode structures that round 2 built and measured SLOWER than the default graph of
    * one launch per op (chained FFN with grid barriers, persistent token kernel, flag-ordered launches on two streams, flow
    * launch, split attention merged by the last split / by the output projection: profiles/r02_decode_experiments.md).  They
    * were removed in round 3; lgh_create answers LGH_UNSUPPORTED when one of them is set. */
-  LGH_FLAG_REMOVED_MASK = (1u << 1) | (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7) | (0xFFu << 24),
+  LGH_FLAG_REMOVED_MASK = (1u << 1) | (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7) | (0x7Fu << 24),
+  LGH_FLAG_MV_GENERIC = 1u << 31,    /* every matrix-core mat-vec runs the generic kernel: the table of static launch plans (compile-time
+                                        geometry for the dense 4096 / 14336 shapes, csrc/matvec_mfma.hip) is ignored and the arg-max
+                                        keeps both stages.  Same bits either way; for A/B measurements and tests. */
   LGH_FLAG_ATTN_SPLITS_SHIFT = 8,    /* bits 8..15: KV splits per kv-head in decode attention (0 = auto) */
   LGH_FLAG_ATTN_DIRECT_SHIFT = 16    /* bits 16..23: contexts of up to 64 * n rows use the single-launch decode attention (one workgroup
                                         per kv head, no split + combine pair); 0 = the tuned default, 255 = never */
@@ -521,6 +524,19 @@ int lgh_op_qkv_rope(int device, const uint32_t* types, const void* const* w, con
 int lgh_op_linear_chain(int device, uint32_t type_a, const void* w_a, const void* w_a_up, const float* bias_a, size_t k, size_t n_a,
                         const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
                         uint32_t type_b, const void* w_b, size_t n_b, float* out_a, float* out_b, float* out_b_requant, int* image_used);
+/* ONE launch as lgh_op_linear_chain's launch A, and everything it leaves: out [n]; with an XQ image left (*image_used = 1) the image
+ * (image_out, 1280 bytes per 256 elements of n) and its n / 16 sums of squares (ssq_out, xq_next == 2 only); and with want_argmax —
+ * the output projection of a greedy step — the token of the last-max arg-max that follows (*token_out), with *argmax_parts = the
+ * parts the launch itself left for the merge (0: both arg-max stages ran over `out`).  *static_launches (may be NULL) = 1 when the
+ * launch ran a static launch plan of csrc/matvec_mfma.hip, 0 when it ran the generic kernel. */
+int lgh_op_linear_image(int device, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, const float* x,
+                        const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw, int want_argmax, float* out,
+                        uint8_t* image_out, float* ssq_out, int* image_used, int* token_out, int* argmax_parts, int* static_launches);
+/* The LGH_FLAG_* bits of the bare contexts every later lgh_op_* / lgh_bench_* call of this process runs on (LGH_FLAG_MV_GENERIC: the
+ * same launch with and without the static launch plans).  Returns the previous value. */
+uint32_t lgh_op_set_flags(uint32_t flags);
+/* How many matrix-core mat-vec launches of this process ran a static launch plan so far (tests: which kernel a launch took). */
+uint64_t lgh_debug_static_launches(void);
 /* ffn_forward's MoE half: out = x + sum_p sel_w[p] * down_e(silu(gate_e . x') * (up_e . x')), e = sel[p], x' = RMSNorm(x) * norm_w.
  * Expert stacks in GGUF order: w_gate / w_up [n_experts][ffn][hidden], w_down [n_experts][hidden][ffn].  With `router`
  * ([n_experts][hidden] f32) the device router selects (sel / sel_w are ignored); otherwise sel / sel_w (top_k entries) drive the

@@ -142,7 +142,12 @@ struct MvLaunch {
   uint32_t n_ssq_part;
   uint32_t dbg_slot;         // diagnostic builds: launch sequence number mod 64 (span stamps)
   MvSeg seg[3];
+  // optional (the output projection of a greedy step, static plans only): workgroup w leaves the maximum of its rows and the
+  // last index of that maximum in amax_v[w] / amax_i[w]
+  float* amax_v;
+  int* amax_i;
 };
+constexpr uint32_t kAmaxPartsMax = 256;   // slots of amax_v / amax_i: one per workgroup of a launch that fits one workgroup per CU
 
 // Multi-sequence launch (matvec_batch.hip): where sequence s keeps its vectors.  The vectors named in MvLaunch / MvSeg are
 // sequence 0's; sequence s adds s times the stride below (XQ images in bytes, everything else in floats).  The K / V cache
@@ -192,7 +197,9 @@ hipError_t mv_launch(const MvLaunch& L, uint32_t n_wg, uint32_t threads, hipStre
 int mv_symbol(const MvLaunch& L);
 // int8-MFMA path (matvec_mfma.hip): Q4_K in the tile16 layout
 hipError_t mvq_plan(uint32_t k, uint32_t n_rows, int npass, MvPlan* plan, uint32_t launch_rows, uint32_t force_tiles = 0);
-hipError_t mvq_launch(const MvLaunch& L, uint32_t n_wg, uint32_t threads, hipStream_t st);
+// generic: ignore the table of static launch plans (LGH_FLAG_MV_GENERIC); *amax_done: the launch left the arg-max parts L.amax_v asks for
+hipError_t mvq_launch(const MvLaunch& L, uint32_t n_wg, uint32_t threads, hipStream_t st, bool generic = false, bool* amax_done = nullptr);
+uint64_t mvq_static_launches();   // launches of this process that took a static launch plan
 hipError_t repack_q4k_t16_launch(const uint8_t* raw, uint8_t* dst, uint32_t n_rows, uint32_t nblk, hipStream_t st);
 hipError_t hbm_read_launch(const uint8_t* buf, size_t bytes, float* sink, int nt, hipStream_t st);   // streaming-read probe
 // launch-uniform geometry of one int8-MFMA op, packed as the kernel takes it; returns the format mask (0 = not launchable)
@@ -235,6 +242,7 @@ hipError_t matmul_f32_launch(const float* a, const float* b, float* c, uint32_t 
 hipError_t silu_mul_launch(const float* gate, const float* up, float* out, uint32_t n, hipStream_t st);
 hipError_t argmax_launch(const float* logits, uint32_t n, float* part_val, int* part_idx, int* state, int* out_token,
                          hipStream_t st);
+hipError_t argmax_merge_launch(const float* part_val, const int* part_idx, uint32_t nparts, int* state, int* out_token, hipStream_t st);
 hipError_t advance_launch(int* state, hipStream_t st);
 hipError_t copy_words_launch(void* dst, const void* src, uint32_t n_words, hipStream_t st);
 hipError_t moe_group_launch(const int* sel, uint32_t n_seq, uint32_t top_k, uint32_t n_experts, int* cnt, int* idx, uint32_t idx_stride, hipStream_t st);

@@ -86,4 +86,25 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// arg-max with the reference's tie rule (the LAST maximal element wins): misc.hip's two stages and the output projection's
+// static plan (matvec_mfma.hip) merge with the same rule, so the result does not depend on how the rows are partitioned
+__device__ __forceinline__ void amax_merge(float& bv, int& bi, float v, int i) {
+  if (v > bv || (v == bv && i > bi)) { bv = v; bi = i; }
+}
+
+__device__ __forceinline__ void amax_block_reduce(float& bv, int& bi, float* sv, int* si) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    float ov = __shfl_xor(bv, off, 64);
+    int oi = __shfl_xor(bi, off, 64);
+    amax_merge(bv, bi, ov, oi);
+  }
+  const uint32_t tid = threadIdx.x;
+  if ((tid & 63) == 0) { sv[tid >> 6] = bv; si[tid >> 6] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (uint32_t w = 1; w < (blockDim.x >> 6); w++) amax_merge(bv, bi, sv[w], si[w]);
+  }
+}
+
 }  // namespace lgh

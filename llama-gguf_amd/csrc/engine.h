@@ -167,6 +167,11 @@ struct SegSpec {
   const float* resid = nullptr;
   const float* bias = nullptr;
   const float* moe_w = nullptr;
+  // single-segment launches: ask the launch to leave each workgroup's arg-max part (MvLaunch::amax_v / amax_i, kAmaxPartsMax slots);
+  // *amax_parts receives how many it left — 0 when it ran without a static plan and both arg-max stages are still needed
+  float* amax_v = nullptr;
+  int* amax_i = nullptr;
+  uint32_t* amax_parts = nullptr;
 };
 
 // the vectors the FFN half of a layer works on (one sequence's)
@@ -204,7 +209,8 @@ lgh::XqBuf* xq_get(lgh_ctx* c, const float* f32, uint32_t k);   // finds or regi
 lgh::XqBuf* xq_find(lgh_ctx* c, const float* f32);              // the image registered under exactly this address, or nullptr
 void xq_stale(lgh_ctx* c, const float* f32);
 int linear_any(lgh_ctx* c, int cls, const lgh::DevWeight& W, const float* x, float* out, const float* norm_w,
-               const float* resid, const float* bias, int xq_next = 0, const float* xq_next_nw = nullptr);
+               const float* resid, const float* bias, int xq_next = 0, const float* xq_next_nw = nullptr, float* amax_v = nullptr,
+               int* amax_i = nullptr, uint32_t* amax_parts = nullptr);   // amax_*: as SegSpec's
 int drain_prof(lgh_ctx* c);
 int check_ready(lgh_ctx* c);   // what every entry point on a finalized context starts with: LGH_OK and the device bound, or the status
 // captures what `enqueue` puts on the context's stream and instantiates it into *exec; n_nodes: the graph's node count

@@ -419,8 +419,8 @@ int lgh_finalize(lgh_ctx* c) {
       {(void**)&c->moe_w, 8 * 4},
       {(void**)&c->moe_sel, 8 * 4},
       {(void**)&c->state, ST_WORDS * 4},
-      {(void**)&c->amax_v, 64 * 4},
-      {(void**)&c->amax_i, 64 * 4},
+      {(void**)&c->amax_v, kAmaxPartsMax * 4},
+      {(void**)&c->amax_i, kAmaxPartsMax * 4},
       {(void**)&c->tok_log, (size_t)d.max_seq_len * 4},
   };
   if ((rc = alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes))) return rc;

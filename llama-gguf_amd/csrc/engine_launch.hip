@@ -358,7 +358,16 @@ static int launch_mv_group(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, 
   uint64_t alg;
   int rc = build_mv_group(c, specs, nseg, norm_w, k, mfma, L, wg, threads, alg, 0);
   if (rc) return rc;
-  if (mfma) return run_k(c, cls, mvq_symbol(L), alg, [&] { return mvq_launch(L, wg, threads, c->stream); });
+  if (specs[0].amax_parts) *specs[0].amax_parts = 0;
+  if (mfma) {
+    // (a static launch plan, where the table of matvec_mfma.hip has one for this geometry; asked to, the output projection of a
+    // greedy step then also leaves the arg-max parts of its workgroups)
+    if (nseg == 1) { L.amax_v = specs[0].amax_v; L.amax_i = specs[0].amax_i; }
+    bool amax_done = false;
+    rc = run_k(c, cls, mvq_symbol(L), alg, [&] { return mvq_launch(L, wg, threads, c->stream, (c->d.flags & LGH_FLAG_MV_GENERIC) != 0, &amax_done); });
+    if (!rc && amax_done && specs[0].amax_parts) *specs[0].amax_parts = wg;
+    return rc;
+  }
   return run_k(c, cls, mv_symbol(L), alg, [&] { return mv_launch(L, wg, threads, c->stream); });
 }
 
@@ -395,13 +404,15 @@ int launch_mv(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float* 
 
 // one Linear with optional norm prologue / residual epilogue, any device type
 int linear_any(lgh_ctx* c, int cls, const DevWeight& W, const float* x, float* out, const float* norm_w,
-                      const float* resid, const float* bias, int xq_next, const float* xq_next_nw) {
+                      const float* resid, const float* bias, int xq_next, const float* xq_next_nw, float* amax_v, int* amax_i, uint32_t* amax_parts) {
+  if (amax_parts) *amax_parts = 0;
   if (fused_type(W.type)) {
     SegSpec sp;
     sp.W[0] = &W; sp.x[0] = x;
     sp.epi = resid ? EPI_RESID : EPI_STORE;
     sp.out = out; sp.resid = resid; sp.bias = bias;
     sp.xq_next = xq_next; sp.xq_next_nw = xq_next_nw;
+    sp.amax_v = amax_v; sp.amax_i = amax_i; sp.amax_parts = amax_parts;
     return launch_mv(c, cls, &sp, 1, norm_w, W.k);
   }
   xq_stale(c, out);

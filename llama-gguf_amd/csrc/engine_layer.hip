@@ -274,10 +274,16 @@ int enqueue_token(lgh_ctx* c, int mode) {
   }
   if (c->last && mode != MODE_PREFILL) {
     // compute_logits (llama.rs:247-266): final RMSNorm fused into the output projection
-    if ((rc = linear_any(c, LGH_K_OUTPUT, c->output, c->hidden, c->logits, c->output_norm, nullptr, nullptr))) return rc;
+    // Greedy: a static-plan output projection leaves each workgroup's arg-max part next to the logits, and only the merge follows.
+    uint32_t parts = 0;
+    const bool greedy = mode == MODE_GREEDY;
+    if ((rc = linear_any(c, LGH_K_OUTPUT, c->output, c->hidden, c->logits, c->output_norm, nullptr, nullptr, 0, nullptr, greedy ? c->amax_v : nullptr,
+                         greedy ? c->amax_i : nullptr, greedy ? &parts : nullptr)))
+      return rc;
     if (mode == MODE_GREEDY) {
-      if ((rc = run_k(c, LGH_K_ARGMAX, LGH_SYM_ARGMAX, (uint64_t)d.vocab_size * 4, [&] {
-             return argmax_launch(c->logits, d.vocab_size, c->amax_v, c->amax_i, c->state, c->tok_log, c->stream);
+      if ((rc = run_k(c, LGH_K_ARGMAX, LGH_SYM_ARGMAX, parts ? (uint64_t)parts * 8 : (uint64_t)d.vocab_size * 4, [&] {
+             return parts ? argmax_merge_launch(c->amax_v, c->amax_i, parts, c->state, c->tok_log, c->stream)
+                          : argmax_launch(c->logits, d.vocab_size, c->amax_v, c->amax_i, c->state, c->tok_log, c->stream);
            })))
         return rc;
     } else if (mode == MODE_SAMPLE) {   // Sampler::sample in place of the arg-max (sample.hip); the token lands where the arg-max's does

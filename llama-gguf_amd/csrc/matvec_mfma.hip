@@ -22,6 +22,7 @@
 // dwords are N0 & 0x0F.., N0 >> 4 & 0x0F.., N1 & 0x0F.., N1 >> 4 & 0x0F.. and every lane loads only its own nibbles:
 //   [0, 1024) lane-major 16 B: N0,N1 of steps 0,1    [1024, 2048) steps 2,3    [2048, 2304) the 16 native 16-byte headers
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "device_utils.h"
@@ -582,6 +583,214 @@ __global__ void __launch_bounds__(kWaves * 64) mvq_kernel(uint32_t wbpack, uint3
 }
 
 // ------------------------------------------------------------------------------------------------
+// Static launch plans.  mvq_body decides everything at run time — segment, format, passes, expert selection, any T / G / Rg /
+// nbw — and pays for it twice on the critical path of every launch: a prologue of scalar bookkeeping before the first vector
+// load leaves the wave, and an epilogue that re-reads launch constants after the final barrier.  The launches of a dense
+// decode graph at hidden 4096 / FFN 14336 have one of a handful of geometries, so for those the geometry is a template
+// argument: T = 8 k-slices, G = 1, nbw = nblk / 8 blocks per wave, the passes, each segment's format and epilogue.  What stays
+// a run-time scalar is the number of tiles per workgroup (Rg) and of rows, so a 48-row test launch runs the very code of
+// the 128256-row output projection.  A workgroup branches ONCE on its segment; below that branch the format, the tile
+// stride, the wait count behind the input vector and the epilogue are constants, and the segment's fields come from the
+// kernel argument at constant offsets.
+// Same tile core (mvq_issue_tile / mvq_consume_tile), same partial-sum slots, same reduction order: same bits.
+// ------------------------------------------------------------------------------------------------
+template <uint32_t NBLK, int NPASS, bool NORM, int NSEG, int F0, int E0, int F1 = -1, int E1 = -1, int F2 = -1, int E2 = -1>
+struct MvsPlan {
+  static_assert(NBLK % kWaves == 0 && NSEG >= 1 && NSEG <= 3 && NPASS >= 1 && NPASS <= 2, "geometry of a static plan");
+  static_assert(!NORM || NBLK * 16 == 256, "wave 0 gathers the 256 partial sums of x^2 with four loads per lane");
+  static constexpr uint32_t nblk = NBLK, nbw = NBLK / kWaves;
+  static constexpr int npass = NPASS, nseg = NSEG;
+  static constexpr bool norm = NORM;
+  static constexpr int fmt(int s) { return s == 0 ? F0 : s == 1 ? F1 : F2; }
+  static constexpr int epi(int s) { return s == 0 ? E0 : s == 1 ? E1 : E2; }
+};
+
+template <int N>
+__device__ __forceinline__ void wait_vm_behind() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+template <typename P, int SEG>
+__device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, const uint32_t red_floats, const uint32_t pos_now, const MvLaunch& L,
+                                          uint8_t* smem8) {
+  constexpr int F = P::fmt(SEG), EPI = P::epi(SEG), NP = P::npass, LPT = fmt_loads_per_tile(F);
+  constexpr uint32_t MASK = 1u << F, tb = fmt_tile_bytes(F), nbw = P::nbw, nblk = P::nblk, T = kWaves;
+  constexpr int kDp = kDepth;
+  const MvSeg& S = L.seg[SEG];
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // = the k-slice
+  LGH_STAMP(0);
+  LGH_WSTAMP(0);
+  LGH_SPAN(0);
+  // ---- what the epilogue needs besides the partial sums, from the segment at constant kernarg offsets
+  const uint32_t S_rpw = 16u * Rg;
+  MvEpiOps A;
+  A.out = S.out; A.bias = S.bias; A.xq_out = S.xq_out; A.xq_ssq = S.xq_ssq; A.xq_nw = S.xq_nw;
+  A.n_rows = S.n_rows; A.rows_per_wg = S_rpw; A.max_seq = S.max_seq; A.head_dim = S.head_dim; A.pos = pos_now;
+  A.eps = L.eps;
+  const float* L_rope_cs = L.rope_cs;
+  MvEpiPre epi_pre = {0.0f, 0.0f, false};
+  const float* S_resid = S.resid;
+  const float* L_ssq_part = L.ssq_part;
+  float ssp[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  LGH_WSTAMP(1);
+  // ---- the input vector: this wave's nbw XQ records straight into its LDS region (see mvq_body)
+  const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem8;
+  const uint8_t* xrec = smem8 + wave * (nbw * kXqRecord);
+  const uint32_t xrec_lds = lds_base + wave * (nbw * kXqRecord);
+  const uint8_t* xg = S.pass[0].xq + wave * (nbw * kXqRecord);
+  LGH_WSTAMP(2);
+#pragma unroll
+  for (uint32_t b = 0; b < nbw; b++) {
+    const uint8_t* src = xg + b * kXqRecord;
+    const uint32_t dst = xrec_lds + b * kXqRecord;
+    uint32_t keep;   // (moves only: nothing here may touch SCC, which the compiler can hold live across the asm)
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %4\n\t"
+                 "s_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(src + lane * 16), "v"(src + 1024 + lane * 4), "s"(dst), "s"(dst + 1024u) : "memory");
+  }
+  // ---- geometry: G = 1, so the workgroup's Rg tiles are this wave's, blocks [wave * nbw, (wave + 1) * nbw) of each
+  const uint32_t ntiles = (S.n_rows + 15) >> 4, tile0 = wg * Rg;
+  const uint32_t ntile_w = tile0 < ntiles ? min(Rg, ntiles - tile0) : 0;
+  const uint64_t woff = ((uint64_t)tile0 * nblk + wave * nbw) * tb;
+  const uint8_t* pb0 = S.pass[0].plane[0] + woff;
+  const uint8_t* pb1 = NP > 1 ? S.pass[1].plane[0] + woff : nullptr;
+  float* red = reinterpret_cast<float*>(smem8 + kWaves * nbw * kXqRecord);
+  float* ssq = red + red_floats;
+  const uint32_t n = lane & 15, mq = lane >> 4;
+
+  struct Pos { uint32_t p, tl, b; };
+  auto issue = [&](const Pos& q, RawT16& r) {
+    const uint8_t* base = NP > 1 && q.p == 1 ? pb1 : pb0;
+    mvq_issue_tile<MASK>(F, base + ((size_t)q.tl * nblk + q.b) * tb, lane, r);
+  };
+  Pos nx = {0, 0, 0};
+  auto advance = [&]() {
+    if (++nx.b == nbw) { nx.b = 0; if (++nx.tl == ntile_w) { nx.tl = 0; ++nx.p; } }
+  };
+  float acc = 0.0f;
+  auto consume = [&](const Pos& q, const RawT16& r) {
+    mvq_consume_tile<MASK>(F, r, xrec + q.b * kXqRecord, lane, acc);
+    if (q.b + 1 == nbw) {   // last block of a (pass, tile): the four lane groups -> one partial sum per row
+      float t = acc + __shfl_xor(acc, 16, 64);
+      t += __shfl_xor(t, 32, 64);
+      if (mq == 0) red[(size_t)(q.p * T + wave) * S_rpw + q.tl * 16 + n] = t;
+      acc = 0.0f;
+    }
+  };
+  const uint32_t nitems = (uint32_t)NP * ntile_w * nbw;
+  RawT16 buf[kDp];
+  Pos pos[kDp];
+  auto run = [&](auto n_first) {
+    constexpr int NF = decltype(n_first)::value;
+#pragma unroll
+    for (int j = 0; j < NF; j++) { pos[j] = nx; issue(nx, buf[j]); advance(); }
+    // Behind the first tiles: what the epilogue needs that does not depend on the mat-vec — the residual pair, RoPE's (cos, sin)
+    // pair at the position, and in wave 0 the producer's 256 partial sums of x^2 (RMSNorm; first used after the last tile).
+    mv_epilogue_prefetch_resid_static<EPI>(S_resid, A, wg, epi_pre);
+    mv_epilogue_prefetch_rope_static<EPI>(L_rope_cs, A, wg, epi_pre);
+    if (P::norm && wave == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) ssp[j] = L_ssq_part[lane + 64 * j];
+    }
+    // The wait for x counts the NF * LPT tile loads ONLY (one instruction per ldg_nt*, the generic body's bookkeeping) and not the
+    // plain loads just issued, however many instructions the compiler made of them: vmcnt retires in order, so with K of those in
+    // flight too the wave passes once x AND the K oldest tile loads have arrived.  K <= 6 loads of tiles 0 and 1, which the very
+    // next instructions wait for in full anyway.  A count that is too SMALL can only wait longer, never let x be read early.
+    wait_vm_behind<NF * LPT>();
+    LGH_WSTAMP(4);
+    LGH_WSTAMP(5);
+    if constexpr (NF < kDp) {
+#pragma unroll
+      for (int j = 0; j < NF; j++) consume(pos[j], buf[j]);
+    } else {
+      uint32_t rem = nitems;
+      while (rem >= 2 * kDp) {
+#pragma unroll
+        for (int j = 0; j < kDp; j++) {
+          consume(pos[j], buf[j]);
+          pos[j] = nx; issue(nx, buf[j]); advance();
+        }
+        rem -= kDp;
+      }
+      const uint32_t unissued = rem - kDp;   // 0 .. kDp-1
+#pragma unroll
+      for (int j = 0; j < kDp; j++) {
+        consume(pos[j], buf[j]);
+        if ((uint32_t)j < unissued) { pos[j] = nx; issue(nx, buf[j]); advance(); }
+      }
+#pragma unroll
+      for (int j = 0; j < kDp - 1; j++)
+        if ((uint32_t)j < unissued) consume(pos[j], buf[j]);
+    }
+  };
+  // a wave has NP * nbw items per tile: at least kDp of them unless the plan is one pass over two blocks and the workgroup one tile
+  // (a workgroup without a tile — mvq_plan makes none and mvqs_match refuses launches that have one — streams nothing)
+  if (ntile_w == 0) {
+  } else if (NP * nbw >= (uint32_t)kDp || ntile_w > 1) {
+    run(std::integral_constant<int, kDp>{});
+  } else {
+    run(std::integral_constant<int, (NP * nbw < (uint32_t)kDp ? NP * nbw : 1)>{});
+  }
+  LGH_STAMP(3);
+  LGH_WSTAMP(6);
+  if (P::norm && wave == 0) {
+    float ss = (ssp[0] + ssp[1]) + (ssp[2] + ssp[3]);
+    ss = wave_sum_to_lane63(ss);
+    if (lane == 63) ssq[0] = ss;
+  }
+  // everything the epilogue reads besides LDS is in a register now, not re-read behind the barrier
+  asm volatile("" : "+s"(A.out), "+s"(A.bias), "+s"(A.xq_out), "+s"(A.xq_ssq), "+s"(A.xq_nw));
+  asm volatile("" : "+s"(A.n_rows), "+s"(A.max_seq), "+s"(A.head_dim), "+s"(A.eps));
+  float* L_amax_v = L.amax_v;
+  int* L_amax_i = L.amax_i;
+  asm volatile("" : "+s"(L_amax_v), "+s"(L_amax_i));
+  __syncthreads();
+  LGH_STAMP(4);
+  float outv;
+  uint32_t row;
+  const bool has = mv_epilogue_static<EPI, T, nblk * 256u, P::norm>(A, wg, red, ssq, epi_pre, outv, row);
+  if (EPI == EPI_STORE && P::nseg == 1 && L_amax_v) {
+    // greedy decode: this workgroup's (maximum, last index of the maximum) over its own rows; the x records are dead by now
+    float* sv = reinterpret_cast<float*>(smem8);
+    int* si = reinterpret_cast<int*>(smem8 + 64);
+    float bv = has ? outv : -INFINITY;
+    int bi = has ? (int)row : -1;
+    amax_block_reduce(bv, bi, sv, si);
+    if (tid == 0) { L_amax_v[blockIdx.x] = bv; L_amax_i[blockIdx.x] = bi; }
+  }
+  LGH_STAMP(5);
+  LGH_WSTAMP(7);
+  LGH_SPAN(1);
+}
+
+// rgpack = the tiles per workgroup of segments 0 | 1 << 8 | 2 << 16
+template <typename P>
+__global__ void __launch_bounds__(kWaves * 64) mvqs_kernel(uint32_t wbpack, uint32_t rgpack, uint32_t red_floats, const MvLaunch L) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  LGH_TL_BEGIN(mvq, lgh::TL_MVQ, P::nblk | (rgpack & 0xFFu) << 16);
+  const uint32_t bid = blockIdx.x;
+  // The position word (RoPE and cache epilogues), read first thing — before anything in this kernel can have written memory, so it
+  // is a scalar load that goes out with the first kernarg loads.  A plain load on purpose: the compiler may copy the destination of
+  // a load issued by inline asm before the wait its author placed, and the copy then holds whatever the register held.
+  constexpr auto has_pos = [](int e) { return e == EPI_ROPE_Q || e == EPI_ROPE_K || e == EPI_V_CACHE; };
+  constexpr bool kAnyPos = has_pos(P::epi(0)) || (P::nseg > 1 && has_pos(P::epi(1))) || (P::nseg > 2 && has_pos(P::epi(2)));
+  const uint32_t pos_now = kAnyPos ? (uint32_t)*L.pos : 0u;
+  if (P::nseg > 2 && bid >= (wbpack >> 16)) mvqs_body<P, (P::nseg > 2 ? 2 : 0)>(bid - (wbpack >> 16), rgpack >> 16, red_floats, pos_now, L, smem8);
+  else if (P::nseg > 1 && bid >= (wbpack & 0xFFFFu))
+    mvqs_body<P, (P::nseg > 1 ? 1 : 0)>(bid - (wbpack & 0xFFFFu), (rgpack >> 8) & 0xFFu, red_floats, pos_now, L, smem8);
+  else mvqs_body<P, 0>(bid, rgpack & 0xFFu, red_floats, pos_now, L, smem8);
+  LGH_TL_END();
+}
+
+// The table: the launches of a dense decode graph at hidden 4096 / FFN 14336, by geometry.
+using MvsQkv446 = MvsPlan<16, 1, true, 3, F_Q4K, EPI_ROPE_Q, F_Q4K, EPI_ROPE_K, F_Q6K, EPI_V_CACHE>;   // fused QKV, V in Q6_K (the "_M" mixes)
+using MvsQkv444 = MvsPlan<16, 1, true, 3, F_Q4K, EPI_ROPE_Q, F_Q4K, EPI_ROPE_K, F_Q4K, EPI_V_CACHE>;   // ... all three in Q4_K
+using MvsWo = MvsPlan<16, 1, false, 1, F_Q4K, EPI_RESID>;                                              // wo: residual, XQ image and sums of x^2 out
+using MvsGateUp = MvsPlan<16, 2, true, 1, F_Q4K, EPI_SWIGLU>;                                          // gate | up: two passes, SwiGLU, XQ out
+using MvsDown4 = MvsPlan<56, 1, false, 1, F_Q4K, EPI_RESID>;                                           // down, 14336 wide
+using MvsDown6 = MvsPlan<56, 1, false, 1, F_Q6K, EPI_RESID>;
+using MvsOutput = MvsPlan<16, 1, true, 1, F_Q6K, EPI_STORE>;                                           // output projection: norm, store (+ arg-max parts)
+
+// ------------------------------------------------------------------------------------------------
 // host: geometry and launch
 // ------------------------------------------------------------------------------------------------
 hipError_t mvq_plan(uint32_t k, uint32_t n_rows, int npass, MvPlan* plan, uint32_t launch_rows, uint32_t force_tiles) {
@@ -656,10 +865,77 @@ uint32_t mvq_pack(const MvLaunch& L, uint32_t n_wg, uint32_t threads, MvGeom* g,
   return mask;
 }
 
-hipError_t mvq_launch(const MvLaunch& L, uint32_t n_wg, uint32_t threads, hipStream_t st) {
+template <typename P>
+static hipError_t mvqs_go(const MvLaunch& L, uint32_t n_wg, size_t lds, hipStream_t st, uint32_t wbpack, uint32_t rgpack) {
+  static bool attr_set[64] = {};
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvqs_kernel<P>), 160 * 1024, attr_set); e != hipSuccess) return e;
+  hipLaunchKernelGGL((mvqs_kernel<P>), dim3(n_wg), dim3(kWaves * 64), lds, st, wbpack, rgpack, L.red_floats, L);
+  return hipGetLastError();
+}
+
+template <typename P>
+static bool mvqs_match(const MvLaunch& L, uint32_t n_wg, uint32_t threads) {
+  const MvSeg& S0 = L.seg[0];
+  if (L.nseg != P::nseg || threads != kWaves * 64 || S0.T != kWaves || S0.G != 1 || S0.nblk != P::nblk || S0.units != P::nbw ||
+      (L.do_norm != 0) != P::norm || L.k != P::nblk * 256u)
+    return false;
+  if (P::norm && (!L.ssq_part || L.n_ssq_part != 256)) return false;
+  for (int s = 0; s < P::nseg; s++) {
+    const MvSeg& S = L.seg[s];
+    const int epi = P::epi(s);
+    if (fmt_of_dev_type(S.type) != P::fmt(s) || S.epi != epi || S.npass != P::npass || S.n_rows == 0 || S.rows_per_wg % 16 ||
+        S.rows_per_wg / 16 == 0 || S.rows_per_wg > kWaves * 64 || !S.out)   // (the epilogue gives every row a thread)
+      return false;
+    // every workgroup of the segment owns at least one tile, and together they own all of them
+    const uint32_t seg_end = s + 1 < P::nseg ? L.seg[s + 1].wg_begin : n_wg, tiles = (S.n_rows + 15) / 16, R = S.rows_per_wg / 16;
+    if (seg_end <= S.wg_begin || seg_end - S.wg_begin != (tiles + R - 1) / R || (s == 0 && S.wg_begin != 0)) return false;
+    for (int p = 0; p < P::npass; p++)
+      if (S.pass[p].sel || !S.pass[p].xq || S.pass[p].xq != L.seg[0].pass[0].xq || !S.pass[p].plane[0]) return false;
+    if (epi == EPI_RESID && !S.resid) return false;
+    const bool rope = epi == EPI_ROPE_Q || epi == EPI_ROPE_K;
+    if ((rope || epi == EPI_V_CACHE) && (!L.pos || S.head_dim == 0)) return false;
+    if (rope && (!L.rope_cs || S.head_dim % 2 || S.n_rows % 2)) return false;
+  }
+  return true;
+}
+
+// how many launches of this process took a static plan (diagnostics and tests: which kernel a launch ran)
+static std::atomic<uint64_t> g_static_launches{0};
+uint64_t mvq_static_launches() { return g_static_launches.load(std::memory_order_relaxed); }
+
+// The static plan of a launch, if its geometry, formats, passes and epilogues are an entry of the table.
+template <typename P>
+static bool mvqs_try(const MvLaunch& L, uint32_t n_wg, uint32_t threads, size_t lds, hipStream_t st, uint32_t wbpack, hipError_t* e) {
+  if (!mvqs_match<P>(L, n_wg, threads)) return false;
+  uint32_t rgpack = 0;
+  for (int s = 0; s < P::nseg; s++) rgpack |= (L.seg[s].rows_per_wg / 16) << (8 * s);
+  *e = mvqs_go<P>(L, n_wg, lds, st, wbpack, rgpack);
+  g_static_launches.fetch_add(1, std::memory_order_relaxed);
+  return true;
+}
+
+hipError_t mvq_launch(const MvLaunch& L0, uint32_t n_wg, uint32_t threads, hipStream_t st, bool generic, bool* amax_done) {
   MvGeom g;
   size_t lds = 0;
+  MvLaunch L = L0;
+  const bool want_amax = L.amax_v && L.amax_i && n_wg <= kAmaxPartsMax;
+  if (amax_done) *amax_done = false;
   const uint32_t mask = mvq_pack(L, n_wg, threads, &g, &lds);
+  if (mask && !generic) {
+    hipError_t e = hipSuccess;
+    if (!want_amax) L.amax_v = nullptr;
+    if (mvqs_try<MvsOutput>(L, n_wg, threads, lds, st, g.wbpack, &e)) {
+      if (amax_done) *amax_done = want_amax && e == hipSuccess;
+      return e;
+    }
+    L.amax_v = nullptr;
+    if (mvqs_try<MvsQkv446>(L, n_wg, threads, lds, st, g.wbpack, &e) || mvqs_try<MvsQkv444>(L, n_wg, threads, lds, st, g.wbpack, &e) ||
+        mvqs_try<MvsWo>(L, n_wg, threads, lds, st, g.wbpack, &e) || mvqs_try<MvsGateUp>(L, n_wg, threads, lds, st, g.wbpack, &e) ||
+        mvqs_try<MvsDown4>(L, n_wg, threads, lds, st, g.wbpack, &e) || mvqs_try<MvsDown6>(L, n_wg, threads, lds, st, g.wbpack, &e))
+      return e;
+  }
+  L.amax_v = nullptr;
+  L.amax_i = nullptr;
   const uint32_t wbpack = g.wbpack, geom = g.geom, geom2 = g.geom2, red_off = g.lds_red_off;
 #define LGH_MVQ_CASE(M) case M: return mvq_go<M>(L, n_wg, threads, lds, st, wbpack, geom, geom2, red_off)
   switch (mask) {   // single formats and the two mixes of the "_M" quantisations (fused QKV: V in Q6_K)

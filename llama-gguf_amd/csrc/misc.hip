@@ -171,25 +171,6 @@ hipError_t matmul_f32_launch(const float* a, const float* b, float* c, uint32_t 
 // Arg-max with the reference's tie rule: Iterator::max_by returns the LAST maximal element
 // (src/main.rs:1815-1821).  Stage 1: 64 workgroups -> partials; stage 2: one workgroup -> state.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void amax_merge(float& bv, int& bi, float v, int i) {
-  if (v > bv || (v == bv && i > bi)) { bv = v; bi = i; }
-}
-
-__device__ __forceinline__ void amax_block_reduce(float& bv, int& bi, float* sv, int* si) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    float ov = __shfl_xor(bv, off, 64);
-    int oi = __shfl_xor(bi, off, 64);
-    amax_merge(bv, bi, ov, oi);
-  }
-  const uint32_t tid = threadIdx.x;
-  if ((tid & 63) == 0) { sv[tid >> 6] = bv; si[tid >> 6] = bi; }
-  __syncthreads();
-  if (tid == 0) {
-    for (uint32_t w = 1; w < (blockDim.x >> 6); w++) amax_merge(bv, bi, sv[w], si[w]);
-  }
-}
-
 constexpr int kArgmaxParts = 64;
 
 __global__ void __launch_bounds__(256) argmax_stage1(const float* __restrict__ v, uint32_t n, float* pv, int* pi) {
@@ -221,6 +202,12 @@ __global__ void __launch_bounds__(64) argmax_stage2(const float* pv, const int* 
     if (out_token) out_token[state ? state[ST_POS] : 0] = bi;      // token log, indexed by position
   }
   LGH_TL_END();
+}
+
+// the parts were left by the output projection itself (matvec_mfma.hip, static plan): only the merge runs
+hipError_t argmax_merge_launch(const float* part_val, const int* part_idx, uint32_t nparts, int* state, int* out_token, hipStream_t st) {
+  hipLaunchKernelGGL(argmax_stage2, dim3(1), dim3(64), 0, st, part_val, part_idx, (int)nparts, state, out_token);
+  return hipGetLastError();
 }
 
 hipError_t argmax_launch(const float* logits, uint32_t n, float* part_val, int* part_idx, int* state, int* out_token,

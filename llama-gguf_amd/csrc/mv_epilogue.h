@@ -147,4 +147,99 @@ __device__ __forceinline__ void mv_epilogue(const MvLaunch& L, const MvSeg& S, u
   mv_epilogue_view(L, S, MvEpiView{S.out, S.resid, S.xq_out, S.xq_ssq, L.pos}, wg, red, ssq, nslots, pre, tid);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Static launch plans (matvec_mfma.hip: mvqs_kernel).  The epilogue is a compile-time constant there, so everything a row
+// needs besides its partial sums travels as VALUES that sit in registers before the final barrier: the segment's pointers
+// and sizes from the top of the body, the position from the scalar register it was loaded into at wave start.  Same
+// operations in the same order as mv_epilogue_view, so every output bit is the generic kernel's.
+// ------------------------------------------------------------------------------------------------
+struct MvEpiOps {
+  float* out; const float* bias; uint8_t* xq_out; float* xq_ssq; const float* xq_nw;
+  uint32_t n_rows, rows_per_wg, max_seq, head_dim, pos;
+  float eps;
+};
+
+// The prefetches of the static path, issued behind a wave's first tiles.  Every lane loads (rows past the end read the last row).
+// The kernel does not count them among the loads behind its input vector (matvec_mfma.hip: the wait there holds whatever the
+// compiler makes of these plain loads); RoPE's cos / sin are still fetched as ONE 8-byte pair.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <int EPI>
+__device__ __forceinline__ void mv_epilogue_prefetch_resid_static(const float* resid, const MvEpiOps& A, uint32_t wg, MvEpiPre& pre,
+                                                                  uint32_t tid = threadIdx.x) {
+  if (EPI == EPI_RESID) {
+    const uint32_t row = min(wg * A.rows_per_wg + tid, A.n_rows - 1);
+    const float* nw = A.xq_nw ? A.xq_nw : resid;
+    const float a = resid[row], b = nw[row];
+    pre.a = a;
+    pre.b = A.xq_nw ? b : 1.0f;
+    pre.valid = true;
+  }
+}
+template <int EPI>
+__device__ __forceinline__ void mv_epilogue_prefetch_rope_static(const float* rope_cs, const MvEpiOps& A, uint32_t wg, MvEpiPre& pre,
+                                                                 uint32_t tid = threadIdx.x) {
+  if (EPI == EPI_ROPE_Q || EPI == EPI_ROPE_K) {
+    const uint32_t row = min(wg * A.rows_per_wg + 2 * tid, A.n_rows - 2);
+    const uint32_t half = A.head_dim / 2, i = (row % A.head_dim) / 2;
+    const f32x2 cs = *reinterpret_cast<const f32x2*>(rope_cs + ((size_t)A.pos * half + i) * 2);   // 8-byte aligned: pairs of a hipMalloc'ed table
+    pre.a = cs.x;
+    pre.b = cs.y;
+    pre.valid = true;
+  }
+}
+// returns whether this thread owns a row whose value went to out[row]; `outv` / `row` are that value and its index
+template <int EPI, uint32_t NSLOTS, uint32_t K, bool NORM>
+__device__ __forceinline__ bool mv_epilogue_static(const MvEpiOps& A, uint32_t wg, const float* red, const float* ssq, const MvEpiPre pre,
+                                                   float& outv, uint32_t& row, uint32_t tid = threadIdx.x) {
+  static_assert(EPI == EPI_STORE || EPI == EPI_RESID || EPI == EPI_SWIGLU || EPI == EPI_ROPE_Q || EPI == EPI_ROPE_K || EPI == EPI_V_CACHE,
+                "the MoE epilogues run in the generic kernel");
+  const uint32_t t = tid, rpw = A.rows_per_wg, rbase = wg * rpw;
+  float inv = 1.0f;
+  if (NORM) inv = 1.0f / __builtin_sqrtf(ssq[0] / (float)K + A.eps);   // (the other waves' slots hold zeros in the generic kernel)
+  auto rowval = [&](int p, uint32_t rl) {
+    float v = 0.0f;
+#pragma unroll
+    for (uint32_t ks = 0; ks < NSLOTS; ks++) v += red[(size_t)(p * NSLOTS + ks) * rpw + rl];
+    return v * inv;
+  };
+  outv = 0.0f;
+  if (EPI == EPI_ROPE_Q || EPI == EPI_ROPE_K) {
+    const uint32_t rl = 2 * t;
+    row = rbase + rl;
+    if (rl >= rpw || row >= A.n_rows) return false;
+    float x0 = rowval(0, rl), x1 = rowval(0, rl + 1);
+    if (A.bias) { x0 += A.bias[row]; x1 += A.bias[row + 1]; }
+    const uint32_t d = A.head_dim, head = row / d;
+    const float c = pre.a, s = pre.b;
+    float y0 = x0 * c - x1 * s, y1 = x0 * s + x1 * c;
+    if (EPI == EPI_ROPE_Q) {
+      A.out[row] = y0;
+      A.out[row + 1] = y1;
+    } else {
+      float* dst = A.out + ((size_t)head * A.max_seq + A.pos) * d + (row % d);
+      dst[0] = y0;
+      dst[1] = y1;
+    }
+    return false;
+  }
+  row = rbase + t;
+  if (t >= rpw || row >= A.n_rows) return false;
+  float v0 = rowval(0, t);
+  if (A.bias) v0 += A.bias[row];
+  if (EPI == EPI_V_CACHE) {
+    const uint32_t d = A.head_dim;
+    A.out[((size_t)(row / d) * A.max_seq + A.pos) * d + (row % d)] = v0;
+    return false;
+  }
+  if (EPI == EPI_STORE) outv = v0;
+  else if (EPI == EPI_RESID) outv = v0 + pre.a;
+  else outv = silu_f(v0) * rowval(1, t);
+  A.out[row] = outv;
+  if (A.xq_out) {
+    const float w = !A.xq_nw ? 1.0f : EPI == EPI_RESID ? pre.b : A.xq_nw[row];
+    xq_store_chunk(A.xq_out, row >> 4, outv * w, A.xq_ssq, outv, tid);
+  }
+  return true;
+}
+
 }  // namespace lgh

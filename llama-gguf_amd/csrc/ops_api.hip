@@ -3,6 +3,7 @@
 // micro-benchmark.  They run the SAME kernels the engine runs, on a throw-away context, so that each
 // kernel can be checked against the CPU backend in isolation.
 #include "engine.h"
+#include "xq.h"
 #include "prefill.h"
 
 #include <cmath>
@@ -30,6 +31,8 @@ extern "C" long long lgh_debug_timeline(int which, void* out) {
 
 namespace {
 
+uint32_t g_op_flags = 0;   // lgh_op_set_flags: the LGH_FLAG_* bits of the bare contexts the lgh_op_* / lgh_bench_* entry points run on
+
 struct Tmp {  // bare context: stream, device state words, tracked allocations
   lgh_ctx* c = nullptr;
   int rc = LGH_OK;
@@ -39,6 +42,7 @@ struct Tmp {  // bare context: stream, device state words, tracked allocations
     c = new lgh_ctx();
     c->device = device;
     c->d.norm_eps = 1e-5f;
+    c->d.flags = g_op_flags;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
       rc = LGH_INITIALIZATION_FAILED;
       delete c;
@@ -701,7 +705,10 @@ int lgh_bench_vec_mat(int device, uint32_t type, const void* w, const void* w2, 
   std::vector<float> hx(k), hw(k, 1.0f);
   for (size_t i = 0; i < k; i++) hx[i] = 0.001f * (float)((i * 2654435761u) % 2001) - 1.0f;
   float *dx = t.up(hx.data(), k), *dnw = t.up(hw.data(), k), *dout = t.up(nullptr, n);
-  if (!dx || !dnw || !dout) return LGH_ALLOCATION_FAILED;
+  std::vector<float> hn(n, 1.0f);
+  float* dnext = mode == 3 ? t.up(hn.data(), n) : nullptr;
+  if (!dx || !dnw || !dout || (mode == 3 && (!dnext || !xq_get(t.c, dout, (uint32_t)n)))) return LGH_ALLOCATION_FAILED;
+  if (mode == 3 && hipMemsetAsync(dout, 0, n * 4, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
   auto once = [&]() -> int {
     DevWeight& W = Ws[cur];
     DevWeight& W2 = W2s[cur];
@@ -716,6 +723,8 @@ int lgh_bench_vec_mat(int device, uint32_t type, const void* w, const void* w2, 
       sp.out = dout;
       return launch_mv(t.c, LGH_K_GATEUP, &sp, 1, dnw, (uint32_t)k);
     }
+    // mode 3: wo / down as the engine launches them — residual in place, XQ image of the output times the next norm's weights
+    if (mode == 3) return linear_any(t.c, LGH_K_MISC, W, dx, dout, nullptr, dout, nullptr, 2, dnext);
     return linear_any(t.c, LGH_K_MISC, W, dx, dout, mode == 1 ? dnw : nullptr, nullptr, nullptr);
   };
   for (int i = 0; i < 3; i++)
@@ -933,6 +942,77 @@ int lgh_op_linear_chain(int device, uint32_t type_a, const void* w_a, const void
   if ((rc = linear_any(t.c, LGH_K_MISC, WB, da, db2, bnw, nullptr, nullptr))) return rc;
   if ((rc = t.down(out_a, da, n_a)) || (rc = t.down(out_b, db, n_b))) return rc;
   return t.down(out_b_requant, db2, n_b);
+}
+
+// Test surface: the context flags of every later lgh_op_* / lgh_bench_* call of this process (LGH_FLAG_MV_GENERIC: the same launch
+// with and without the static launch plans).  Returns the previous value.
+uint64_t lgh_debug_static_launches(void) { return lgh::mvq_static_launches(); }
+
+uint32_t lgh_op_set_flags(uint32_t flags) {
+  const uint32_t prev = g_op_flags;
+  g_op_flags = flags;
+  return prev;
+}
+
+int lgh_op_linear_image(int device, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, const float* x,
+                        const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw, int want_argmax, float* out,
+                        uint8_t* image_out, float* ssq_out, int* image_used, int* token_out, int* argmax_parts, int* static_launches) {
+  // ONE launch as the engine assembles it (linear_any: STORE / RESID with bias; or the SWIGLU gate-up launch) and everything it leaves:
+  // the f32 output, its XQ image (xq_bytes(n) bytes) and the image's sums of squares (n / 16), and — want_argmax, the greedy step's
+  // output projection — the token the arg-max that follows picks, with the number of parts the launch itself left (0: two stages)
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w || !x || !out || xq_next < 0 || xq_next > 2 || (xq_next == 2 && !next_nw) || (w_up && (resid || bias)) || (want_argmax && !token_out))
+    return LGH_INVALID_ARGUMENT;
+  t.c->d.norm_eps = eps;
+  const size_t nb = weight_bytes(type, k, n);
+  if (!nb) return LGH_SHAPE_MISMATCH;
+  DevWeight WA, WU;
+  int rc;
+  if ((rc = upload_matrix(t.c, WA, (int)type, (uint32_t)k, (uint32_t)n, 1, -1, w, nb))) return rc;
+  if (w_up && (rc = upload_matrix(t.c, WU, (int)type, (uint32_t)k, (uint32_t)n, 1, -1, w_up, nb))) return rc;
+  if (w_up && !fused_type(WA.type)) return LGH_UNSUPPORTED;
+  float *dx = t.up(x, k), *dnw = norm_w ? t.up(norm_w, k) : nullptr, *dres = resid ? t.up(resid, n) : nullptr;
+  float *dbias = bias ? t.up(bias, n) : nullptr, *dnext = next_nw ? t.up(next_nw, n) : nullptr, *da = t.up(nullptr, n);
+  if (!dx || (norm_w && !dnw) || (resid && !dres) || (bias && !dbias) || (next_nw && !dnext) || !da) return LGH_ALLOCATION_FAILED;
+  XqBuf* qa = n % 256 == 0 || n % 16 == 0 ? xq_get(t.c, da, (uint32_t)n) : nullptr;
+  if (qa) {   // what the launch does not write must not look written
+    if (hipMemsetAsync(qa->xq, 0xA5, xq_bytes(n), t.c->stream) != hipSuccess || hipMemsetAsync(qa->ssq, 0xA5, (n / 16) * 4, t.c->stream) != hipSuccess)
+      return LGH_OPERATION_FAILED;
+  }
+  if (want_argmax) {
+    if (dev_alloc(t.c, (void**)&t.c->amax_v, kAmaxPartsMax * 4) || dev_alloc(t.c, (void**)&t.c->amax_i, kAmaxPartsMax * 4)) return LGH_ALLOCATION_FAILED;
+  }
+  uint32_t parts = 0;
+  const uint64_t static_before = lgh::mvq_static_launches();
+  if (w_up) {
+    SegSpec sp;
+    sp.npass = 2;
+    sp.W[0] = &WA; sp.W[1] = &WU;
+    sp.x[0] = sp.x[1] = dx;
+    sp.epi = EPI_SWIGLU;
+    sp.out = da;
+    sp.xq_next = xq_next; sp.xq_next_nw = dnext;
+    rc = launch_mv(t.c, LGH_K_GATEUP, &sp, 1, dnw, (uint32_t)k);
+  } else {
+    rc = linear_any(t.c, LGH_K_MISC, WA, dx, da, dnw, dres, dbias, xq_next, dnext, want_argmax ? t.c->amax_v : nullptr,
+                    want_argmax ? t.c->amax_i : nullptr, want_argmax ? &parts : nullptr);
+  }
+  if (rc) return rc;
+  if (static_launches) *static_launches = (int)(lgh::mvq_static_launches() - static_before);
+  if (want_argmax) {
+    hipError_t e = parts ? argmax_merge_launch(t.c->amax_v, t.c->amax_i, parts, t.c->state, nullptr, t.c->stream)
+                         : argmax_launch(da, (uint32_t)n, t.c->amax_v, t.c->amax_i, t.c->state, nullptr, t.c->stream);
+    if (e != hipSuccess) return LGH_OPERATION_FAILED;
+    if (argmax_parts) *argmax_parts = (int)parts;
+    if (hipMemcpyAsync(token_out, t.c->state + ST_ARGMAX, 4, hipMemcpyDeviceToHost, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  }
+  qa = xq_find(t.c, da);
+  const bool used = qa && qa->fresh;
+  if (image_used) *image_used = used ? 1 : 0;
+  if (used && image_out && hipMemcpyAsync(image_out, qa->xq, xq_bytes(n), hipMemcpyDeviceToHost, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  if (used && ssq_out && hipMemcpyAsync(ssq_out, qa->ssq, (n / 16) * 4, hipMemcpyDeviceToHost, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  return t.down(out, da, n);
 }
 
 int lgh_op_moe_experts(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down,

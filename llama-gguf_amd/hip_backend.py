@@ -40,7 +40,7 @@ ABI_SYMBOLS = (
     "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
     "lgh_set_sampler_ex", "lgh_batch_set_sampler_ex", "lgh_get_sampler_mu", "lgh_op_sample_ex",
     "lgh_op_attention_decode", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
-    "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts",
+    "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches",
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
 )
 
@@ -59,7 +59,8 @@ KV_F32, KV_INT8, KV_FP8_E4M3, KV_FP8_E5M2 = 0, 1, 2, 3   # lgh_model_desc.kv_cac
 KV_TQ2, KV_TQ3 = 4, 5   # KVCacheType::TurboQuantMSE { bits: 2 | 3 }: what `--kv-cache-type tq2 | tq3` selects (src/config.rs:808-817)
 KV_TQ2_QJL, KV_TQ3_QJL = 6, 7   # KVCacheType::TurboQuantProd { bits: 2 | 3 }: `tq2-qjl | tq3-qjl`
 FLAG_KV_INT8 = 16   # KV cache in the reference's int8 format (kv_quantized.rs: int8 rows + one scale per head and position)
-FLAG_REMOVED_MASK = 2 | 8 | 32 | 64 | 128 | (0xFF << 24)   # round-2 decode experiments, removed in round 3: lgh_create answers Unsupported
+FLAG_MV_GENERIC = 1 << 31   # matrix-core mat-vecs ignore the static launch plans (A/B runs, tests); same bits
+FLAG_REMOVED_MASK = 2 | 8 | 32 | 64 | 128 | (0x7F << 24)   # round-2 decode experiments, removed in round 3: lgh_create answers Unsupported
 
 
 class BackendError(RuntimeError):
@@ -230,6 +231,10 @@ def load_library() -> C.CDLL:
         "lgh_op_attention_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_prefill": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
         "lgh_op_qkv_rope": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, sz, sz, f32, f32, vp, vp, vp]),
+        "lgh_op_linear_image": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, f32, vp, C.c_int, vp, C.c_int, vp, vp, vp,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "lgh_op_set_flags": (u32, [u32]),
+        "lgh_debug_static_launches": (C.c_uint64, []),
         "lgh_op_linear_chain": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, f32, vp, C.c_int, vp, u32, vp, sz, vp, vp, vp,
                                           C.POINTER(C.c_int)]),
         "lgh_op_moe_experts": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
@@ -769,6 +774,35 @@ def op_linear_chain(type_a: int, w_a, k: int, n_a: int, x, type_b: int, w_b, n_b
                                             _ptr(rs), xq_next, _ptr(nn), type_b, wb.ctypes.data, n_b, oa.ctypes.data, ob.ctypes.data,
                                             ob2.ctypes.data, C.byref(used)), "linear_chain")
     return oa, ob, ob2, bool(used.value)
+
+
+def op_set_flags(flags: int) -> int:
+    """Context flags (FLAG_*) of every later op_* / bench_* call of this process; returns the previous value."""
+    return int(load_library().lgh_op_set_flags(int(flags)))
+
+
+def static_launches() -> int:
+    """Matrix-core mat-vec launches of this process that ran a static launch plan so far."""
+    return int(load_library().lgh_debug_static_launches())
+
+
+def op_linear_image(ggml_type: int, w, k: int, n: int, x, *, w_up=None, bias=None, norm_w=None, eps: float = 1e-5, resid=None,
+                    xq_next: int = 0, next_nw=None, want_argmax: bool = False, device: int = 0):
+    """One launch as the engine assembles it (STORE / RESID + bias, or SwiGLU with w_up) and everything it leaves.
+    -> dict(out, image (uint8 or None), ssq (f32 or None), token, parts, static = 1 if the launch ran a static launch plan)."""
+    x = _f32(x)
+    wa = np.ascontiguousarray(w, dtype=np.uint8)
+    wu = None if w_up is None else np.ascontiguousarray(w_up, dtype=np.uint8)
+    ba, nw, rs, nn = (None if v is None else _f32(v) for v in (bias, norm_w, resid, next_nw))
+    out = np.empty(n, np.float32)
+    img = np.zeros((n + 255) // 256 * 1280, np.uint8)
+    ssq = np.zeros(max(n // 16, 1), np.float32)
+    used, tok, parts, static = C.c_int(0), C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    _chk(load_library().lgh_op_linear_image(device, ggml_type, wa.ctypes.data, _ptr(wu), _ptr(ba), k, n, x.ctypes.data, _ptr(nw), eps, _ptr(rs),
+                                            xq_next, _ptr(nn), int(want_argmax), out.ctypes.data, img.ctypes.data, ssq.ctypes.data,
+                                            C.byref(used), C.byref(tok), C.byref(parts), C.byref(static)), "linear_image")
+    return {"out": out, "image": img if used.value else None, "ssq": ssq if used.value and xq_next == 2 else None,
+            "token": tok.value, "parts": parts.value, "static": static.value}
 
 
 def op_moe_experts(type_gate_up: int, w_gate, w_up, type_down: int, w_down, n_experts: int, hidden: int, ffn: int, top_k: int, x,

@@ -25,6 +25,21 @@ def short(name: str) -> str:
     return name.split("(")[0]
 
 
+def symbol_of(kernel: str):
+    """The LGH_SYM_* name bench.py reports for a matrix-core mat-vec kernel: the generic instantiation of its format mask.  The
+    static launch plans (mvqs_kernel<MvsPlan<nblk, npass, norm, nseg, F0, E0, F1, E1, F2, E2>>) share a symbol per format mask."""
+    import re
+    m = re.match(r"lgh::mvqs_kernel<lgh::MvsPlan<(.*?)>\s*>$", kernel)
+    if not m:
+        return None
+    a = [x.strip().rstrip("u") for x in m.group(1).split(",")]
+    mask = 0
+    for f in (a[4], a[6], a[8]):
+        if int(f) >= 0:
+            mask |= 1 << int(f)
+    return f"lgh::mvq_kernel<{mask}u>"
+
+
 def pmc_means(path: Path, counter: str):
     acc = defaultdict(lambda: [0, 0.0])
     if not path.exists():
@@ -59,6 +74,17 @@ def main():
         nf, f_kb = fetch.get(k, (0, 0.0))
         nw, w_kb = write.get(k, (0, 0.0))
         rows.append((k, nf, f_kb, nw, w_kb, f_kb * 1024 * 2 + w_kb * 1024))
+    # one row per bench.py symbol as well: the launch-weighted mean over the static plans (and the generic kernel) that share it
+    agg = defaultdict(lambda: [0, 0.0, 0, 0.0])
+    for k, nf, f_kb, nw, w_kb, _ in rows:
+        sym = symbol_of(k) or (k if k.startswith("lgh::mvq_kernel<") else None)
+        if sym:
+            a = agg[sym]
+            a[0] += nf; a[1] += nf * f_kb; a[2] += nw; a[3] += nw * w_kb
+    have = {r[0] for r in rows}
+    for sym, (nf, fs, nw, ws) in sorted(agg.items()):
+        if sym not in have and nf and nw:
+            rows.append((sym, nf, fs / nf, nw, ws / nw, fs / nf * 1024 * 2 + ws / nw * 1024))
     with open(dst / f"{tag}_pmc_traffic.csv", "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["kernel", "launches_fetch_pass", "FETCH_SIZE_KB_mean_raw", "launches_write_pass", "WRITE_SIZE_KB_mean_raw",
