@@ -110,7 +110,9 @@ enum {
 
 enum {
   LGH_FLAG_NO_GRAPH = 1u << 0,       /* launch kernels eagerly instead of replaying a hipGraph */
-  LGH_FLAG_EXACT_PREFILL = 1u << 2,  /* lgh_prefill_batch feeds the tokens one by one (f32 throughout) instead of the batched f16 GEMM path */
+  LGH_FLAG_EXACT_PREFILL = 1u << 2,  /* lgh_prefill_batch feeds the tokens one by one (f32 throughout) instead of the batched f16 GEMM path
+                                        (f32 and TurboQuantMSE tq2 / tq3 caches have that path; with this flag a tq2 / tq3 context is
+                                        bit-identical to lgh_prefill_token) */
   LGH_FLAG_KV_INT8 = 1u << 4,        /* KV cache as the reference's QuantizedKVCache with KVCacheFormat::Int8 (src/model/kv_quantized.rs): int8
                                         rows + one f32 scale per (kv head, position), a quarter of the f32 cache.  (Same as kv_cache_type =
                                         LGH_KV_INT8; no CLI flag of the reference reaches this format, see kv_cache_type.) */
@@ -221,8 +223,9 @@ int lgh_prefill_token(lgh_ctx* ctx, uint32_t token_id);
  * (dense or MoE) whose 2-D weights are all in matrix-core tile layouts (Q4_K, Q5_K, Q6_K, Q8_0, Q4_0 with k % 256 == 0)
  * take the batched path: blocks of up to 128 tokens, one f16-MFMA GEMM per weight (MoE: per expert, over
  * the tokens routed to it), causal attention over the block; the KV cache it leaves equals the token-by-token one within
- * 1e-2 relative (f16 operands, f32 accumulation).  Everything else (pipeline stages, other formats), and any
- * context created with LGH_FLAG_EXACT_PREFILL, runs n exact prefill_tokens. */
+ * 1e-2 relative (f16 operands, f32 accumulation).  KV caches: f32, and TurboQuantMSE (LGH_KV_TQ2 / TQ3), whose rows are compressed as
+ * write_kv does and attended through their codes, the block's own rows included.  Everything else (pipeline stages, other formats,
+ * the QJL, int8 and FP8 caches), and any context created with LGH_FLAG_EXACT_PREFILL, runs n exact prefill_tokens. */
 int lgh_prefill_batch(lgh_ctx* ctx, const uint32_t* tokens, size_t n);
 /* 1 when lgh_prefill_batch will take the batched GEMM path for this (finalized) context, else 0 */
 int lgh_prefill_is_batched(lgh_ctx* ctx);
@@ -506,6 +509,20 @@ int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint
  * kernel's f16 results widened to f32.  m_tokens <= 128, n_heads * head_dim % 256 == 0, pos0 + m_tokens <= max_seq_len. */
 int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
                              size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos0, size_t m_tokens);
+/* TurboQuantKVCache::write_kv (kv_turboquant.rs:88-122) for a block of m <= 128 prompt rows as the batched prefill over a
+ * TurboQuantMSE cache runs it: kv_cache_type LGH_KV_TQ2 / TQ3; k_rows / v_rows [n_kv_heads][m][head_dim] are the block's RoPE'd f32 rows;
+ * k_codes / v_codes [n_kv_heads][max_seq_len][row bytes] are in / out: rows pos0 .. pos0+m-1 come back as the launch compressed them
+ * (the bits of lgh_op_tq_compress), every other row as it was.  signs [n_kv_heads][k, v][head_dim] (+1 / -1). */
+int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv_heads, size_t head_dim,
+                       size_t max_seq_len, size_t pos0, const float* signs, uint8_t* k_codes, uint8_t* v_codes);
+/* TurboQuantKVCache::attention_layer (kv_turboquant.rs:127-201) for m_tokens prompt tokens at positions pos0.. as the batched prefill
+ * over a TurboQuantMSE cache runs it: the code caches already hold rows 0..pos0 + m_tokens - 1; they are expanded into a NaN-filled f32
+ * scratch, q [m_tokens][n_heads][head_dim] is rotated, and the block attention's TurboQuant variant runs over the scratch.
+ * out [m_tokens][n_heads * head_dim] = the kernel's f16 results widened to f32.  Limits as lgh_op_attention_prefill; head_dim 64 / 128,
+ * n_heads / n_kv_heads in {1, 2, 4, 8}. */
+int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes,
+                                const float* signs, float* out, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_seq_len,
+                                float scale, size_t pos0, size_t m_tokens);
 /* The engine's quantized mat-vec launches (launch_mv), one call site at a time, for kernel-level tests.  Test surface: these
  * exist to hold the kernels to a reference and are not part of the inference API.  Weights are native GGUF bytes, row-major
  * [out][in]; the library re-lays them out as lgh_upload_tensor does, so each weight runs on the kernel family the engine picks.

@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "device_utils.h"
+#include "tq_fwht.h"
 #include "xq.h"
 #include "prefill.h"
 #include "timeline.h"
@@ -568,11 +569,17 @@ hipError_t attn_direct_launch(const float* q, const float* kcache, const float* 
 // layer of a 128-token Llama-3-8B prompt, bound by vector issue (four workgroups of four waves per CU); this one 10.7 us
 // (8 waves, the next tile's fragments in flight during a tile; 11.7 us with 4 waves), and the 512-token prompt 19.0 instead
 // of 21.8 ms.
+// TQ (the prompt pass over a TurboQuantMSE cache, attention_tq.hip tq_pf_rows_kernel): q holds rotated queries and kc / vc the rows'
+// centroids in the rotated space, so the scores are the reference's and the merged accumulator is sum_p w_p c[V_p] in the rotated
+// space; the epilogue inverts the rotation per (token, head) in f32 — attn_tq_combine_kernel's expression, with the V signs
+// tq_signs [kv head][k, v][D] — and only then rounds to f16.
 // ------------------------------------------------------------------------------------------------
-template <int D, int NW>
+struct PfTqEpi { const float* signs; float inv_scale, inv_d; };   // (unused without TQ)
+
+template <int D, int NW, bool TQ>
 __global__ void __launch_bounds__(NW * 64) attn_pf_mfma_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc,
                                                                uint32_t n_heads, uint32_t g_per_kv, uint32_t max_seq, float scale, uint32_t pos0,
-                                                               uint32_t m_tokens, uint8_t* __restrict__ xh_out) {
+                                                               uint32_t m_tokens, uint8_t* __restrict__ xh_out, const PfTqEpi tq) {
   constexpr int DJ = D / 4;    // contraction steps of S^T (dims per lane group)
   constexpr int DQ = D / 16;   // output dims per M index
   constexpr int DP = D + 4;    // padded row of the merge buffer
@@ -681,20 +688,37 @@ __global__ void __launch_bounds__(NW * 64) attn_pf_mfma_kernel(const float* __re
       lsum += s_l[w][t] * f;
       a += s_o[w][t][dim] * f;
     }
+    if (TQ) {   // (this thread alone reads s_o[.][t][dim]: the merged value may take wave 0's place)
+      s_o[0][t][dim] = (a * (1.0f / lsum)) * tq.inv_scale;                // x * sqrt(d), as attn_tq_combine_kernel
+      continue;
+    }
     const _Float16 o = (_Float16)(a * (1.0f / lsum));   // simd.rs:718-720: multiply by 1/sum
     *reinterpret_cast<_Float16*>(xh_out + xh_offset(tt * 16 + t, head * D + dim)) = o;
   }
+  if (TQ) {
+    // the inverse rotation (rotation.rs:80-96): out = signs * (1 / d) * H (sqrt(d) * o), a wave per token, butterflies in registers
+    __syncthreads();
+    const float* sv = tq.signs + (size_t)(kvh * 2 + 1) * D;
+    for (uint32_t t = wave; t < 16u; t += NW) {
+      if (tt * 16 + t >= m_tokens) continue;   // wave-uniform
+      float x0 = s_o[0][t][lane], x1 = 0.0f;
+      if (D == 128) x1 = s_o[0][t][lane + 64];
+      tq_fwht_wave<D>(x0, x1, lane);
+      *reinterpret_cast<_Float16*>(xh_out + xh_offset(tt * 16 + t, head * D + lane)) = (_Float16)(x0 * tq.inv_d * sv[lane]);
+      if (D == 128) *reinterpret_cast<_Float16*>(xh_out + xh_offset(tt * 16 + t, head * D + lane + 64)) = (_Float16)(x1 * tq.inv_d * sv[lane + 64]);
+    }
+  }
 }
 
-template <int D>
+template <int D, bool TQ>
 static hipError_t attn_pf_mfma_go(const float* q, const float* kc, const float* vc, uint32_t n_heads, uint32_t g, uint32_t max_seq, float scale,
-                                  uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st) {
+                                  uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st, const PfTqEpi& tq) {
   constexpr int NW = 8;   // (4 waves: 11.7 us per layer of a 128-token Llama-3-8B prompt, the last token tile's waves take two kv tiles each)
   constexpr size_t lds = (size_t)(NW * 16 * (D + 4) + 2 * NW * 16) * 4;
   static bool attr_set[64] = {};
-  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&attn_pf_mfma_kernel<D, NW>), (int)lds, attr_set); e != hipSuccess) return e;
-  hipLaunchKernelGGL((attn_pf_mfma_kernel<D, NW>), dim3(n_heads, (m_tokens + 15) / 16), dim3(NW * 64), lds, st, q, kc, vc, n_heads, g, max_seq, scale,
-                     pos0, m_tokens, xh_out);
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&attn_pf_mfma_kernel<D, NW, TQ>), (int)lds, attr_set); e != hipSuccess) return e;
+  hipLaunchKernelGGL((attn_pf_mfma_kernel<D, NW, TQ>), dim3(n_heads, (m_tokens + 15) / 16), dim3(NW * 64), lds, st, q, kc, vc, n_heads, g, max_seq, scale,
+                     pos0, m_tokens, xh_out, tq);
   return hipGetLastError();
 }
 
@@ -715,8 +739,8 @@ hipError_t attn_prefill_launch(const float* q, const float* kcache, const float*
   const uint32_t g = n_heads / n_kv;
   static const bool valu = [] { const char* e = std::getenv("LGH_PF_ATTN_VALU"); return e && std::atoi(e) != 0; }();   // (A/B switch: the VALU kernel)
   if (!valu && (head_dim == 128 || head_dim == 64)) {
-    return head_dim == 128 ? attn_pf_mfma_go<128>(q, kcache, vcache, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st)
-                           : attn_pf_mfma_go<64>(q, kcache, vcache, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st);
+    return head_dim == 128 ? attn_pf_mfma_go<128, false>(q, kcache, vcache, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, PfTqEpi{})
+                           : attn_pf_mfma_go<64, false>(q, kcache, vcache, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, PfTqEpi{});
   }
 #define LGH_ATTN_CASE(DD, GG) \
   if (head_dim == DD && g == GG) return attn_pf_go<DD, GG>(q, kcache, vcache, n_kv, max_seq, scale, pos0, m_tokens, xh_out, st);
@@ -724,6 +748,19 @@ hipError_t attn_prefill_launch(const float* q, const float* kcache, const float*
   LGH_ATTN_CASE(64, 1) LGH_ATTN_CASE(64, 2) LGH_ATTN_CASE(64, 4) LGH_ATTN_CASE(64, 8)
 #undef LGH_ATTN_CASE
   return hipErrorInvalidValue;
+}
+
+// the block attention over the TurboQuantMSE prompt pass's scratch (tq_pf_rows_launch filled it and rotated q): head_dim 64 / 128 only,
+// no VALU variant.  signs: this layer's [n_kv][k, v][head_dim]
+void tq_inverse_factors(uint32_t head_dim, float* inv_scale, float* inv_d);   // attention_tq.hip
+hipError_t attn_prefill_tq_launch(const float* q, const float* kscr, const float* vscr, const float* signs, uint32_t n_heads, uint32_t n_kv,
+                                  uint32_t head_dim, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st) {
+  if (n_kv == 0 || n_heads % n_kv || m_tokens == 0 || !signs || (head_dim != 64 && head_dim != 128)) return hipErrorInvalidValue;
+  PfTqEpi tq{signs, 0.0f, 0.0f};
+  tq_inverse_factors(head_dim, &tq.inv_scale, &tq.inv_d);
+  const uint32_t g = n_heads / n_kv;
+  return head_dim == 128 ? attn_pf_mfma_go<128, true>(q, kscr, vscr, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, tq)
+                         : attn_pf_mfma_go<64, true>(q, kscr, vscr, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, tq);
 }
 
 // Backend::attention for any head_dim / group size (per-op surface only; the engine's shapes take the kernels above):

@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "device_utils.h"
+#include "tq_fwht.h"
 #include "xq.h"
 
 namespace lgh {
@@ -63,66 +64,28 @@ __device__ __forceinline__ uint32_t tq_index(const uint8_t* row, uint32_t i) {  
 template <int BITS>
 __host__ __device__ constexpr uint32_t tq_row_bytes(uint32_t d) { return BITS == 2 ? d / 4 : d / 8 * 3; }
 
-// In-place Walsh-Hadamard butterflies over `rows` vectors of D floats in LDS (rotation.rs:113-130): stage `half` combines (i, i +
-// half) exactly as the reference's loop does; all threads of the workgroup take part (barriers inside).
-template <int D>
-__device__ __forceinline__ void tq_fwht_rows(float* buf, uint32_t rows) {
-  for (uint32_t half = 1; half < (uint32_t)D; half <<= 1) {
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < rows * (D / 2); j += blockDim.x) {
-      const uint32_t r = j / (D / 2), jj = j % (D / 2);
-      const uint32_t i = (jj / half) * 2 * half + (jj % half);
-      float* v = buf + r * D;
-      const float a = v[i], b = v[i + half];
-      v[i] = a + b;
-      v[i + half] = a - b;
-    }
-  }
-  __syncthreads();
-}
-
-// The same butterflies for ONE vector per wave, in registers: lane l holds elements l (and l + 64 when D = 128).  Stage `half`
-// pairs (i, i + half), i without bit `half`: new[i] = a + b, new[i + half] = a - b with a the lower element — the partner comes
-// through a cross-lane exchange, the operations and their operands are the reference's (rotation.rs:113-130): bit-identical to
-// tq_fwht_rows, without its barrier per stage.
-template <int D>
-__device__ __forceinline__ void tq_fwht_wave(float& x0, float& x1, uint32_t lane) {
-#pragma unroll
-  for (uint32_t half = 1; half < 64 && half < (uint32_t)D; half <<= 1) {
-    const bool upper = (lane & half) != 0;
-    const float p0 = __shfl_xor(x0, (int)half, 64);
-    x0 = upper ? p0 - x0 : x0 + p0;
-    if (D == 128) {
-      const float p1 = __shfl_xor(x1, (int)half, 64);
-      x1 = upper ? p1 - x1 : x1 + p1;
-    }
-  }
-  if (D == 128) {   // half = 64: the lane's own two elements
-    const float a = x0, b = x1;
-    x0 = a + b;
-    x1 = a - b;
-  }
-}
-
-// codes of the D floats at `y` (already rotated) -> row bytes, by the first D / 4 (2 bits) or D / 8 (3 bits) threads
+// codes of the D floats at `y` (already rotated) -> row bytes, by the threads with tid < D / 4 (2 bits) or D / 8 (3 bits); tid: the
+// thread's index among those that share `y` (the workgroup's threads, or the lanes of the wave that owns the row)
 template <int D, int BITS>
-__device__ __forceinline__ void tq_pack_row(const TqTables& T, const float* y, uint8_t* out) {
+__device__ __forceinline__ void tq_pack_row(const TqTables& T, const float* y, uint8_t* out, uint32_t tid) {
   if (BITS == 2) {
-    if (threadIdx.x < D / 4) {
+    if (tid < D / 4) {
       uint32_t byte = 0;
 #pragma unroll
-      for (int i = 0; i < 4; i++) byte |= tq_quantize<2>(T, y[threadIdx.x * 4 + i]) << (i * 2);
-      out[threadIdx.x] = (uint8_t)byte;
+      for (int i = 0; i < 4; i++) byte |= tq_quantize<2>(T, y[tid * 4 + i]) << (i * 2);
+      out[tid] = (uint8_t)byte;
     }
-  } else if (threadIdx.x < D / 8) {
+  } else if (tid < D / 8) {
     uint32_t acc = 0;
 #pragma unroll
-    for (int i = 0; i < 8; i++) acc |= tq_quantize<3>(T, y[threadIdx.x * 8 + i]) << (i * 3);
-    out[threadIdx.x * 3] = (uint8_t)(acc & 0xFF);
-    out[threadIdx.x * 3 + 1] = (uint8_t)((acc >> 8) & 0xFF);
-    out[threadIdx.x * 3 + 2] = (uint8_t)((acc >> 16) & 0xFF);
+    for (int i = 0; i < 8; i++) acc |= tq_quantize<3>(T, y[tid * 8 + i]) << (i * 3);
+    out[tid * 3] = (uint8_t)(acc & 0xFF);
+    out[tid * 3 + 1] = (uint8_t)((acc >> 8) & 0xFF);
+    out[tid * 3 + 2] = (uint8_t)((acc >> 16) & 0xFF);
   }
 }
+template <int D, int BITS>
+__device__ __forceinline__ void tq_pack_row(const TqTables& T, const float* y, uint8_t* out) { tq_pack_row<D, BITS>(T, y, out, threadIdx.x); }
 
 // QJL side of a new K row and of `nq` rotated queries (all 256 threads; LDS in, LDS out):
 //   res = y - dequantized codes of y (quant.rs:85-89);  newx = sign bits of S res, then |res| (QjlProjector::compress, qjl.rs:36-62);
@@ -487,6 +450,72 @@ __global__ void __launch_bounds__(256) tq_compress_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// The prompt pass over a TurboQuantMSE cache (engine_prefill.hip): the block attention (attention.hip, attn_pf_mfma_kernel) reads f32
+// rows, so one layer's rows go through an f32 scratch with the layout of a layer's f32 cache, kscr / vscr [kv head][max_seq][D], in
+// the ROTATED space: row p = centroid[code] of cache row p.  One launch, a wave per row, does a block's three kinds of row work:
+//   store   (kv head, K | V, block row t < m_store): the RoPE'd f32 row the QKV epilogue left at scratch row pos0 + t -> D x, H,
+//           1 / sqrt(d) (tq_fwht_wave: the decode path's operations in its order), tq_pack_row -> the code cache's row pos0 + t
+//           (TurboQuantKVCache::write_kv, kv_turboquant.rs:88-122; the bits of lgh_op_tq_compress); the scratch row becomes the
+//           centroids of those codes, so the block's own rows take part through their codes like every other row
+//   query   (block token t < m_q, head h): q row -> H D q / sqrt(d) with its kv head's K signs, in place (attention_layer,
+//           kv_turboquant.rs:127-172: the rotated query against the K centroids is the reference's score)
+//   expand  (kv head, K | V, row p < n_expand): cached codes -> centroids into scratch row p
+// Jobs are numbered store, query, expand; grid = ceil(jobs / 4), 256 threads.  The rows of different jobs are disjoint.
+// ------------------------------------------------------------------------------------------------
+template <int D, int BITS>
+__global__ void __launch_bounds__(256) tq_pf_rows_kernel(float* __restrict__ kscr, float* __restrict__ vscr, uint8_t* __restrict__ kq,
+                                                         uint8_t* __restrict__ vq, float* __restrict__ q, const float* __restrict__ signs,
+                                                         const TqTables T, uint32_t n_kv, uint32_t g_per_kv, uint32_t max_seq, uint32_t pos0,
+                                                         uint32_t m_store, uint32_t m_q, uint32_t n_expand) {
+  constexpr uint32_t RB = tq_row_bytes<BITS>(D);
+  __shared__ float s_y[4][D];
+  __shared__ __attribute__((aligned(4))) uint8_t s_code[4][64];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t n_store = n_kv * 2 * m_store, n_query = m_q * n_kv * g_per_kv, n_exp = n_kv * 2 * n_expand;
+  const uint32_t job = blockIdx.x * 4 + wave;
+  const int kind = job < n_store ? 0 : job < n_store + n_query ? 1 : job < n_store + n_query + n_exp ? 2 : 3;   // wave-uniform
+  float* row = nullptr;        // the f32 row this wave works on
+  uint8_t* crow = nullptr;     // its code row
+  const float* sg = nullptr;
+  if (kind == 0 || kind == 2) {
+    const uint32_t j = kind == 0 ? job : job - n_store - n_query, per = kind == 0 ? m_store : n_expand;
+    const uint32_t kvh = j / (2 * per), kv = (j / per) & 1u, r = (kind == 0 ? pos0 : 0u) + j % per;
+    const size_t ri = (size_t)kvh * max_seq + r;
+    row = (kv ? vscr : kscr) + ri * D;
+    crow = (kv ? vq : kq) + ri * RB;
+    sg = signs + (size_t)(kvh * 2 + kv) * D;
+  } else if (kind == 1) {
+    const uint32_t j = job - n_store;                       // (token, head)
+    row = q + (size_t)j * D;
+    sg = signs + (size_t)((j % (n_kv * g_per_kv)) / g_per_kv * 2) * D;
+  }
+  if (kind <= 1) {
+    float x0 = row[lane] * sg[lane], x1 = 0.0f;
+    if (D == 128) x1 = row[lane + 64] * sg[lane + 64];
+    tq_fwht_wave<D>(x0, x1, lane);
+    x0 *= T.norm;
+    x1 *= T.norm;
+    if (kind == 1) {
+      row[lane] = x0;
+      if (D == 128) row[lane + 64] = x1;
+    } else {
+      s_y[wave][lane] = x0;
+      if (D == 128) s_y[wave][lane + 64] = x1;
+      row[lane] = tq_centroid<BITS>(T, tq_quantize<BITS>(T, x0));
+      if (D == 128) row[lane + 64] = tq_centroid<BITS>(T, tq_quantize<BITS>(T, x1));
+    }
+  }
+  __syncthreads();
+  if (kind == 0) tq_pack_row<D, BITS>(T, s_y[wave], s_code[wave], lane);
+  __syncthreads();
+  if (kind == 0 && lane < RB / 4) reinterpret_cast<uint32_t*>(crow)[lane] = reinterpret_cast<const uint32_t*>(s_code[wave])[lane];
+  if (kind == 2) {
+    row[lane] = tq_centroid<BITS>(T, tq_index<BITS>(crow, lane));
+    if (D == 128) row[lane + 64] = tq_centroid<BITS>(T, tq_index<BITS>(crow, lane + 64));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
 static TqTables tq_tables(uint32_t d, int bits) {
@@ -598,6 +627,38 @@ hipError_t tq_compress_launch(int bits, const float* x, uint32_t dim, const floa
   else if (bits == 2) hipLaunchKernelGGL((tq_compress_kernel<64, 2>), dim3(1), dim3(256), 0, st, x, signs, T, out, qjl_s, qjl_out);
   else hipLaunchKernelGGL((tq_compress_kernel<64, 3>), dim3(1), dim3(256), 0, st, x, signs, T, out, qjl_s, qjl_out);
   return hipGetLastError();
+}
+
+// the TurboQuantMSE prompt pass's row work (tq_pf_rows_kernel): store m_store block rows at pos0 (kscr / vscr rows -> kq / vq codes, rows
+// -> centroids), rotate the m_q x n_heads query rows of q in place (q may be NULL with m_q 0), expand code rows 0 .. n_expand-1 into
+// the scratch.  signs: this layer's [n_kv][k, v][head_dim]
+hipError_t tq_pf_rows_launch(int bits, float* kscr, float* vscr, uint8_t* kq, uint8_t* vq, float* q, const float* signs, uint32_t n_heads,
+                             uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, uint32_t pos0, uint32_t m_store, uint32_t m_q, uint32_t n_expand,
+                             hipStream_t st) {
+  if ((bits != 2 && bits != 3) || (head_dim != 64 && head_dim != 128) || n_kv == 0 || n_heads % n_kv || (m_q && !q) ||
+      (uint64_t)pos0 + m_store > max_seq || n_expand > max_seq)
+    return hipErrorInvalidValue;
+  const uint64_t jobs = (uint64_t)n_kv * 2 * m_store + (uint64_t)m_q * n_heads + (uint64_t)n_kv * 2 * n_expand;
+  if (jobs == 0) return hipSuccess;
+  if (jobs > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  const TqTables T = tq_tables(head_dim, bits);
+  const dim3 grid((uint32_t)((jobs + 3) / 4));
+  const uint32_t g = n_heads / n_kv;
+#define LGH_TQ_PF(DD, BB) \
+  hipLaunchKernelGGL((tq_pf_rows_kernel<DD, BB>), grid, dim3(256), 0, st, kscr, vscr, kq, vq, q, signs, T, n_kv, g, max_seq, pos0, m_store, m_q, n_expand)
+  if (head_dim == 128 && bits == 2) LGH_TQ_PF(128, 2);
+  else if (head_dim == 128) LGH_TQ_PF(128, 3);
+  else if (bits == 2) LGH_TQ_PF(64, 2);
+  else LGH_TQ_PF(64, 3);
+#undef LGH_TQ_PF
+  return hipGetLastError();
+}
+
+// the rotation's factors for the prompt pass's TurboQuant epilogue (attention.hip): sqrt(d), 1 / d — tq_tables' values
+void tq_inverse_factors(uint32_t head_dim, float* inv_scale, float* inv_d) {
+  const TqTables T = tq_tables(head_dim, 2);
+  *inv_scale = T.inv_scale;
+  *inv_d = T.inv_d;
 }
 
 }  // namespace lgh

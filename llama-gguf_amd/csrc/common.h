@@ -278,6 +278,13 @@ hipError_t attn_tq_multi_launch(int bits, const float* q, uint8_t* kq, uint8_t* 
 hipError_t tq_compress_launch(int bits, const float* x, uint32_t dim, const float* signs, uint8_t* out, hipStream_t st, const float* qjl_s = nullptr,
                               uint32_t* qjl_out = nullptr);
 uint32_t tq_row_bytes_host(int bits, uint32_t d);
+// the prompt pass over a TurboQuantMSE cache: the block's row work on the f32 scratch (attention_tq.hip) and the block attention over it
+// (attention.hip)
+hipError_t tq_pf_rows_launch(int bits, float* kscr, float* vscr, uint8_t* kq, uint8_t* vq, float* q, const float* signs, uint32_t n_heads,
+                             uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, uint32_t pos0, uint32_t m_store, uint32_t m_q, uint32_t n_expand,
+                             hipStream_t st);
+hipError_t attn_prefill_tq_launch(const float* q, const float* kscr, const float* vscr, const float* signs, uint32_t n_heads, uint32_t n_kv,
+                                  uint32_t head_dim, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st);
 hipError_t attn_decode_any_launch(const float* q, const float* kcache, const float* vcache, float* out, uint32_t n_heads, uint32_t n_kv,
                                   uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, hipStream_t st);
 hipError_t attn_generic_launch(const float* q, const float* k, const float* v, float* out, uint32_t n_heads, uint32_t n_kv, uint32_t seq_len,

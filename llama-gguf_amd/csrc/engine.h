@@ -47,6 +47,9 @@ struct PfScratch {
   int *moe_sel = nullptr, *moe_cnt = nullptr, *moe_base = nullptr, *moe_list = nullptr, *moe_rowmap = nullptr, *moe_tokmap = nullptr;
   float* moe_w = nullptr;
   uint8_t *xh_gather = nullptr, *xh_act_e = nullptr;   // per expert: gathered inputs [E][xh_bytes(H)], activations [E][xh_bytes(EI)]
+  // TurboQuantMSE caches: one layer's rows as f32 in the rotated space (centroids of the codes), K then V, each [kv head][max_seq][head_dim];
+  // rebuilt by every layer of every block (attention_tq.hip tq_pf_rows_kernel)
+  float* tq_kv = nullptr;
 };
 
 struct ProfRec { int cls; int sym; uint64_t bytes; hipEvent_t a, b; };
@@ -219,7 +222,8 @@ int enqueue_token(lgh_ctx* c, int mode);   // everything one token needs, in str
 // batched prompt path (engine_prefill.hip).  The sequence a block of prompt tokens belongs to: the position of the block's first token,
 // and whose K / V rows it fills — the context's own (slot < 0: layers[li].kcache / vcache) or a slot's of the multi-sequence engine
 struct PfTarget { size_t pos0; int slot; };
-bool pf_eligible(const lgh_ctx* c);
+// slot: the target is a slot of the multi-sequence engine (TurboQuant slots stay token by token: bit-identical to the single-sequence engine)
+bool pf_eligible(const lgh_ctx* c, bool slot = false);
 int pf_ensure(lgh_ctx* c);
 int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_t m);
 // prefill_block's steps over the m tokens in the context's scratch (c->pf, after pf_ensure); next_nw: the norm weight of the step's

@@ -568,7 +568,7 @@ int lgh_batch_prefill(lgh_ctx* c, uint32_t slot, const uint32_t* tokens, size_t 
   for (size_t i = 0; i < n; i++)
     if (tokens[i] >= c->d.vocab_size) return fail(c, LGH_INVALID_ARGUMENT, "token id exceeds vocab size");
   if (n == 0) return LGH_OK;
-  if (!pf_eligible(c)) {   // no batched prompt path for this model: token by token through the multi-sequence step
+  if (!pf_eligible(c, true)) {   // no batched prompt path for this model or cache: token by token through the multi-sequence step
     for (size_t i = 0; i < n; i++)
       if ((rc = lgh_forward_multi(c, &slot, tokens + i, 1, nullptr, nullptr))) return rc;
     return LGH_OK;

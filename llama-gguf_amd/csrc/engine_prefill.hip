@@ -13,9 +13,16 @@ using namespace lgh;
 // ------------------------------------------------------------------------------------------------
 // batched prompt processing (prefill.hip)
 // ------------------------------------------------------------------------------------------------
-bool pf_eligible(const lgh_ctx* c) {
+bool pf_eligible(const lgh_ctx* c, bool slot) {
   const lgh_model_desc& d = c->d;
-  if (d.flags & (LGH_FLAG_EXACT_PREFILL | LGH_FLAG_KV_INT8)) return false;   // (the batched path writes f32 K/V rows)
+  if (d.flags & LGH_FLAG_EXACT_PREFILL) return false;
+  // The batched path writes f32 K/V rows.  The f32 cache takes them as they are; a TurboQuantMSE cache (tq2 / tq3) takes them through an
+  // f32 scratch (pf_tq_rows below), for the own sequence of a context that owns every layer.  The QJL formats, int8 and FP8, slots of
+  // the multi-sequence engine and stage contexts with a TurboQuant cache stay token by token.
+  if (d.flags & LGH_FLAG_KV_INT8) {
+    if (d.kv_cache_type != LGH_KV_TQ2 && d.kv_cache_type != LGH_KV_TQ3) return false;
+    if (slot || !c->first || !c->last) return false;
+  }
   const uint32_t QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, g = d.num_heads / d.num_kv_heads;
   if (d.hidden_size % 256 || d.hidden_size > 2048u * kPfSsqChunks || QD % 256 || KD % 16) return false;
   if ((d.head_dim != 64 && d.head_dim != 128) || (g != 1 && g != 2 && g != 4 && g != 8)) return false;
@@ -64,6 +71,7 @@ int pf_ensure(lgh_ctx* c) {
       {(void**)&P.moe_base, any_moe ? (size_t)kPfMaxExperts * 4 : 0},   {(void**)&P.moe_rowmap, any_moe ? (size_t)kPfMoeRows * 4 : 0},
       {(void**)&P.moe_tokmap, any_moe ? (size_t)kPfTokens * kPfMaxTopK * 4 : 0},
       {(void**)&P.xh_gather, any_moe ? xh_bytes(H) * d.num_experts : 0}, {(void**)&P.xh_act_e, any_moe ? xh_bytes(EI) * d.num_experts : 0},
+      {(void**)&P.tq_kv, kv_is_tq(d.kv_cache_type) ? (size_t)2 * d.num_kv_heads * d.max_seq_len * d.head_dim * 4 : 0},   // (scratch, not KV bytes)
   };
   if (int rc = alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes)) return rc;
   // the zero-fills are done before anybody else (another stream, a peer's copy into the stage block) touches the buffers
@@ -98,6 +106,19 @@ int pf_qkv_step(lgh_ctx* c, LayerW& L, float* kcache, float* vcache, uint32_t po
   return pf_k(c, pf_qkv_epi_launch(P.part, S, nc, QD, KD, d.head_dim, L.bq, L.bk, L.bv, c->rope_cs, pos0, d.max_seq_len, P.q, kcache, vcache, P.ssq, H,
                                    d.norm_eps, (int)d.use_neox_rope, m, st),
               "qkv epilogue");
+}
+
+// TurboQuantMSE cache, after pf_qkv_step has left the block's f32 K / V rows in the scratch pf.tq_kv: their codes into layer li's code
+// cache and their centroids back into the scratch (TurboQuantKVCache::write_kv); with `attend`, also the block's queries rotated in
+// place and rows 0 .. pos0-1 of the scratch filled from the cached codes, which is what the block attention reads
+static int pf_tq_rows(lgh_ctx* c, LayerW& L, uint32_t li, uint32_t pos0, uint32_t m, bool attend) {
+  PfScratch& P = c->pf;
+  const lgh_model_desc& d = c->d;
+  const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
+  float* const vscr = P.tq_kv + (size_t)d.num_kv_heads * d.max_seq_len * d.head_dim;
+  return pf_k(c, tq_pf_rows_launch(kv_tq_bits(d.kv_cache_type), P.tq_kv, vscr, (uint8_t*)L.k8, (uint8_t*)L.v8, attend ? P.q : nullptr, signs, d.num_heads,
+                                   d.num_kv_heads, d.head_dim, d.max_seq_len, pos0, m, attend ? m : 0, attend ? pos0 : 0, c->stream),
+              "TurboQuant rows");
 }
 
 // XH(attention output) in pf.xh_attn -> pf.hidden += wo . attn (+ bo), XH(h * ffn_norm) in pf.xh_h, sums of squares in pf.ssq
@@ -200,15 +221,26 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
   }
   if ((rc = pf_block_input(c, c->layers[c->l0].attn_norm, m))) return rc;
   const float scale = 1.0f / std::sqrt((float)d.head_dim);  // layers.rs:374
+  const bool tq = kv_is_tq(d.kv_cache_type);
+  if (tq && t.slot >= 0) return fail(c, LGH_UNSUPPORTED, "TurboQuant slots have no batched prompt path");
   for (uint32_t li = c->l0; li < c->l1; li++) {
     LayerW& L = c->layers[li];
-    float* const kcache = t.slot < 0 ? L.kcache : c->batch.kcache[li] + slot_off;
-    float* const vcache = t.slot < 0 ? L.vcache : c->batch.vcache[li] + slot_off;
+    // (a TurboQuant cache: the scratch stands in for the layer's f32 cache; pf_eligible admits the context's own sequence only)
+    float* const kcache = tq ? P.tq_kv : t.slot < 0 ? L.kcache : c->batch.kcache[li] + slot_off;
+    float* const vcache = tq ? P.tq_kv + (size_t)d.num_kv_heads * d.max_seq_len * d.head_dim : t.slot < 0 ? L.vcache : c->batch.vcache[li] + slot_off;
+    const bool attend = !(li + 1 == c->l1 && c->last);   // the model's last layer: its K/V rows are written, its output would be discarded
     if ((rc = pf_qkv_step(c, L, kcache, vcache, pos0, m))) return rc;
-    if (li + 1 == c->l1 && c->last) break;   // the model's last layer: its K/V rows are written, its output would be discarded
-    if ((rc = pf_k(c, attn_prefill_launch(P.q, kcache, vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
-                   "attention")))
-      return rc;
+    if (tq && (rc = pf_tq_rows(c, L, li, pos0, m, attend))) return rc;
+    if (!attend) break;
+    if (tq) {
+      const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
+      rc = pf_k(c, attn_prefill_tq_launch(P.q, kcache, vcache, signs, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
+                "attention");
+    } else {
+      rc = pf_k(c, attn_prefill_launch(P.q, kcache, vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
+                "attention");
+    }
+    if (rc) return rc;
     if ((rc = pf_wo_step(c, L, m))) return rc;
     const float* next_nw = li + 1 < c->l1 ? c->layers[li + 1].attn_norm : nullptr;   // nullptr: the block goes to the next stage as f32
     if ((rc = L.moe() ? pf_moe_step(c, L, next_nw, m) : pf_ffn_step(c, L, next_nw, m))) return rc;

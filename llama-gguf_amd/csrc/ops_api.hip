@@ -601,6 +601,80 @@ int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, c
   return xh_down(t, xh, m_tokens, qd, out);
 }
 
+// the f32 scratch of the TurboQuant prompt pass, NaN-filled: K then V, each [n_kv][max_seq][head_dim]
+static float* pf_tq_scratch(Tmp& t, size_t cache) {
+  float* s = t.up(nullptr, 2 * cache);
+  if (s && hipMemsetD32Async((hipDeviceptr_t)s, (int)0x7FC00000u, 2 * cache, t.c->stream) != hipSuccess) return nullptr;
+  return s;
+}
+
+static bool pf_tq_signs_ok(const float* signs, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (signs[i] != 1.0f && signs[i] != -1.0f) return false;
+  return true;
+}
+
+int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv, size_t head_dim,
+                       size_t max_seq, size_t pos0, const float* signs, uint8_t* k_codes, uint8_t* v_codes) {
+  // TurboQuantKVCache::write_kv (kv_turboquant.rs:88-122) for a block of prompt rows, as the batched prefill runs it
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (kv_cache_type != LGH_KV_TQ2 && kv_cache_type != LGH_KV_TQ3) return LGH_UNSUPPORTED;
+  if (head_dim != 64 && head_dim != 128) return LGH_UNSUPPORTED;
+  if (!k_rows || !v_rows || !signs || !k_codes || !v_codes || n_kv == 0 || max_seq > 0x7FFFFFFFu) return LGH_INVALID_ARGUMENT;
+  if (m == 0 || m > (size_t)kPfTokens || pos0 + m > max_seq || !pf_tq_signs_ok(signs, n_kv * 2 * head_dim)) return LGH_INVALID_ARGUMENT;
+  const int bits = kv_tq_bits(kv_cache_type);
+  const size_t d = head_dim, cache = n_kv * max_seq * d, cb = n_kv * max_seq * tq_row_bytes_host(bits, (uint32_t)d);
+  float* scr = pf_tq_scratch(t, cache);
+  uint8_t *dk = (uint8_t*)up_bytes(t, k_codes, cb), *dv = (uint8_t*)up_bytes(t, v_codes, cb);
+  float* ds = t.up(signs, n_kv * 2 * d);
+  if (!scr || !dk || !dv || !ds) return LGH_ALLOCATION_FAILED;
+  hipStream_t st = t.c->stream;
+  // the block's rows where the QKV epilogue leaves them: rows pos0 .. pos0+m-1 of every kv head
+  for (size_t h = 0; h < n_kv; h++) {
+    if (hipMemcpyAsync(scr + (h * max_seq + pos0) * d, k_rows + h * m * d, m * d * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(scr + cache + (h * max_seq + pos0) * d, v_rows + h * m * d, m * d * 4, hipMemcpyHostToDevice, st) != hipSuccess)
+      return LGH_OPERATION_FAILED;
+  }
+  if (tq_pf_rows_launch(bits, scr, scr + cache, dk, dv, nullptr, ds, (uint32_t)n_kv, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, (uint32_t)pos0,
+                        (uint32_t)m, 0, 0, st) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  int rc;
+  if ((rc = down_bytes(t, k_codes, dk, cb))) return rc;
+  return down_bytes(t, v_codes, dv, cb);
+}
+
+int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes, const float* signs,
+                                float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq, float scale, size_t pos0, size_t m_tokens) {
+  // TurboQuantKVCache::attention_layer (kv_turboquant.rs:127-201) for a block of prompt tokens, as the batched prefill runs it
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (kv_cache_type != LGH_KV_TQ2 && kv_cache_type != LGH_KV_TQ3) return LGH_UNSUPPORTED;
+  if (head_dim != 64 && head_dim != 128) return LGH_UNSUPPORTED;
+  if (!q || !k_codes || !v_codes || !signs || !out || n_kv == 0 || n_heads % n_kv || max_seq > 0x7FFFFFFFu) return LGH_INVALID_ARGUMENT;
+  const size_t g = n_heads / n_kv;
+  if (g != 1 && g != 2 && g != 4 && g != 8) return LGH_UNSUPPORTED;   // (pf_eligible's group sizes)
+  const size_t d = head_dim, qd = n_heads * d, cache = n_kv * max_seq * d;
+  if (m_tokens == 0 || m_tokens > (size_t)kPfTokens || qd % 256 || pos0 + m_tokens > max_seq || !pf_tq_signs_ok(signs, n_kv * 2 * d))
+    return LGH_INVALID_ARGUMENT;
+  const int bits = kv_tq_bits(kv_cache_type);
+  const size_t cb = n_kv * max_seq * tq_row_bytes_host(bits, (uint32_t)d);
+  float *dq = t.up(q, m_tokens * qd), *ds = t.up(signs, n_kv * 2 * d), *scr = pf_tq_scratch(t, cache);
+  uint8_t *dk = (uint8_t*)up_bytes(t, k_codes, cb), *dv = (uint8_t*)up_bytes(t, v_codes, cb);
+  const size_t xb = xh_bytes((uint32_t)qd);
+  uint8_t* xh = (uint8_t*)up_bytes(t, nullptr, xb);
+  if (!dq || !ds || !scr || !dk || !dv || !xh) return LGH_ALLOCATION_FAILED;
+  hipStream_t st = t.c->stream;
+  if (hipMemsetAsync(xh, 0, xb, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  if (tq_pf_rows_launch(bits, scr, scr + cache, dk, dv, dq, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, (uint32_t)pos0, 0,
+                        (uint32_t)m_tokens, (uint32_t)(pos0 + m_tokens), st) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  if (attn_prefill_tq_launch(dq, scr, scr + cache, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, scale, (uint32_t)pos0,
+                             (uint32_t)m_tokens, xh, st) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  return xh_down(t, xh, m_tokens, qd, out);
+}
+
 // ---- device-resident weights by tensor name: CudaBackend::load_model_weights + the `b.name()` lookups of its vec_mat /
 // vec_mat_q (src/backend/cuda/mod.rs:121-146, 436-470, 511-575; store: cuda/dequant_weights.rs) ----
 }  // extern "C"

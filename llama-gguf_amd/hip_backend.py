@@ -42,6 +42,7 @@ ABI_SYMBOLS = (
     "lgh_op_attention_decode", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
     "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches",
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
+    "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -230,6 +231,8 @@ def load_library() -> C.CDLL:
         "lgh_op_attention_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_prefill": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
+        "lgh_op_pf_tq_store": (C.c_int, [C.c_int, u32, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp]),
+        "lgh_op_attention_prefill_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
         "lgh_op_qkv_rope": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, sz, sz, f32, f32, vp, vp, vp]),
         "lgh_op_linear_image": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, f32, vp, C.c_int, vp, C.c_int, vp, vp, vp,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -943,6 +946,30 @@ def op_attention_prefill(q, k_cache, v_cache, scale: float, pos0: int, device: i
     out = np.empty((m, nh * d), dtype=np.float32)
     _chk(load_library().lgh_op_attention_prefill(device, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, out.ctypes.data, nh, kc.shape[0], d,
                                                  kc.shape[1], scale, pos0, m), "attention_prefill")
+    return out
+
+
+def op_pf_tq_store(kv_cache_type: int, k_rows, v_rows, pos0: int, signs, k_codes, v_codes, device: int = 0):
+    """The batched prefill's TurboQuant row store (KV_TQ2 / KV_TQ3): k_rows / v_rows [nkv, m, d] f32 are compressed into rows
+    pos0..pos0+m-1 of the code caches [nkv, max_seq, row bytes]; signs [nkv, 2, d].  -> (k_codes, v_codes) after the call (copies)."""
+    kr, vr, sg = _f32(k_rows), _f32(v_rows), _f32(signs)
+    kc, vc = np.array(k_codes, dtype=np.uint8, copy=True), np.array(v_codes, dtype=np.uint8, copy=True)
+    nkv, m, d = kr.shape
+    _chk(load_library().lgh_op_pf_tq_store(device, kv_cache_type, kr.ctypes.data, vr.ctypes.data, m, nkv, d, kc.shape[1], pos0,
+                                           sg.ctypes.data, kc.ctypes.data, vc.ctypes.data), "pf_tq_store")
+    return kc, vc
+
+
+def op_attention_prefill_tq(kv_cache_type: int, q, k_codes, v_codes, signs, scale: float, pos0: int, device: int = 0) -> np.ndarray:
+    """Causal attention of a block of prompt tokens over a TurboQuantMSE cache (KV_TQ2 / KV_TQ3) as the batched prefill runs it: q
+    [m, nh, d] at positions pos0..pos0+m-1; the code caches [nkv, max_seq, row bytes] hold rows 0..pos0+m-1; signs [nkv, 2, d].
+    -> [m, nh * d]: the kernel's f16 outputs widened to f32."""
+    q, sg = _f32(q), _f32(signs)
+    kc, vc = np.ascontiguousarray(k_codes, dtype=np.uint8), np.ascontiguousarray(v_codes, dtype=np.uint8)
+    m, nh, d = q.shape
+    out = np.empty((m, nh * d), dtype=np.float32)
+    _chk(load_library().lgh_op_attention_prefill_tq(device, kv_cache_type, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, sg.ctypes.data,
+                                                    out.ctypes.data, nh, kc.shape[0], d, kc.shape[1], scale, pos0, m), "attention_prefill_tq")
     return out
 
 

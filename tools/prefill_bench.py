@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times lgh_prefill_batch alone (the batched f16-GEMM prompt path): `python tools/prefill_bench.py [--model M --mix X
---prompt N --iters I]`; run it under `rocprofv3 --kernel-trace --stats` for the per-kernel split."""
+--prompt N --iters I --kv f32|tq2|tq3|...]`; run it under `rocprofv3 --kernel-trace --stats` for the per-kernel split.
+--kv selects the KV cache type (f32 and the TurboQuantMSE types tq2 / tq3 have the batched path; the others run token by token)."""
 import argparse
 import os
 import sys
@@ -16,22 +17,28 @@ def main():
     ap.add_argument("--mix", default="Q4_K_M")
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--kv", default="f32", choices=["f32", "int8", "fp8-e4m3", "fp8-e5m2", "tq2", "tq3", "tq2-qjl", "tq3-qjl"])
     a = ap.parse_args()
     pkg = graft.load_package()
+    hb = pkg.hip_backend
+    kv = {"f32": hb.KV_F32, "int8": hb.KV_INT8, "fp8-e4m3": hb.KV_FP8_E4M3, "fp8-e5m2": hb.KV_FP8_E5M2, "tq2": hb.KV_TQ2, "tq3": hb.KV_TQ3,
+          "tq2-qjl": hb.KV_TQ2_QJL, "tq3-qjl": hb.KV_TQ3_QJL}[a.kv]
     cfg = pkg.make_config(a.model, max_seq_len=max(512, a.prompt + 16))
-    eng = pkg.HipGpuInference.from_model(pkg.SynthModel(cfg, mix=a.mix), cfg.max_seq_len)
+    eng = pkg.HipGpuInference.from_model(pkg.SynthModel(cfg, mix=a.mix), cfg.max_seq_len, kv_cache_type=kv)
     prompt = [i % 32000 % cfg.vocab_size for i in range(a.prompt)]
     eng.forward_batch(prompt)
-    best = 1e9
+    times = []
     for _ in range(a.iters):
         eng.reset()
         eng.synchronize()
         t0 = time.perf_counter()
         eng.forward_batch(prompt)
         eng.synchronize()
-        best = min(best, time.perf_counter() - t0)
-    print(f"{a.model} {a.mix}: {a.prompt} prompt tokens, batched={eng.prefill_is_batched()}, best {1e3 * best:.3f} ms "
-          f"= {a.prompt / best:.0f} tokens/s")
+        times.append(time.perf_counter() - t0)
+    times.sort()
+    best = times[0]
+    print(f"{a.model} {a.mix} kv={a.kv}: {a.prompt} prompt tokens, batched={eng.prefill_is_batched()}, best {1e3 * best:.3f} ms "
+          f"= {a.prompt / best:.0f} tokens/s (median {1e3 * times[len(times) // 2]:.3f}, max {1e3 * times[-1]:.3f} ms over {a.iters})")
     eng.close()
 
 
