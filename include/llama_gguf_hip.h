@@ -491,6 +491,11 @@ int lgh_op_attention(int device, const float* q, const float* k, const float* v,
  * size (max_seq_len <= 38400). */
 int lgh_op_attention_decode(int device, int path, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
                             size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos, int n_splits);
+/* The same split + merge as the multi-sequence decode step runs it: sequence s of n_seq (<= 16) attends, with q [n_seq][n_heads][head_dim],
+ * to rows 0..pos[s] of cache slot slot[s]; caches [n_slots][n_kv_heads][max_seq_len][head_dim]; out [n_seq][n_heads][head_dim]. */
+int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
+                                  size_t n_kv_heads, size_t head_dim, size_t max_seq_len, size_t n_slots, size_t n_seq, const int* pos,
+                                  const int* slot, float scale, int n_splits);
 /* QuantizedKVCache (kv_quantized.rs:143-300, 385-565): kv_cache_type LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2.  k_bytes / v_bytes
  * [n_kv_heads][max_seq_len][head_dim] and (int8 only; may be NULL otherwise) k_scale / v_scale [n_kv_heads][max_seq_len] are in / out:
  * rows 0..pos-1 are read, row `pos` comes back as the launch quantized and stored k_new / v_new [n_kv_heads][head_dim]. */

@@ -609,8 +609,8 @@ template <int N>
 __device__ __forceinline__ void wait_vm_behind() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <typename P, int SEG>
-__device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, const uint32_t red_floats, const uint32_t pos_now, const MvLaunch& L,
-                                          uint8_t* smem8) {
+__device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, const uint32_t ntile_w, const uint8_t* xq, const uint8_t* plane0,
+                                          const uint8_t* plane1, const uint32_t red_floats, const uint32_t pos_now, const MvLaunch& L, uint8_t* smem8) {
   constexpr int F = P::fmt(SEG), EPI = P::epi(SEG), NP = P::npass, LPT = fmt_loads_per_tile(F);
   constexpr uint32_t MASK = 1u << F, tb = fmt_tile_bytes(F), nbw = P::nbw, nblk = P::nblk, T = kWaves;
   constexpr int kDp = kDepth;
@@ -636,7 +636,7 @@ __device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, 
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem8;
   const uint8_t* xrec = smem8 + wave * (nbw * kXqRecord);
   const uint32_t xrec_lds = lds_base + wave * (nbw * kXqRecord);
-  const uint8_t* xg = S.pass[0].xq + wave * (nbw * kXqRecord);
+  const uint8_t* xg = xq + wave * (nbw * kXqRecord);
   LGH_WSTAMP(2);
 #pragma unroll
   for (uint32_t b = 0; b < nbw; b++) {
@@ -647,12 +647,13 @@ __device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, 
                  "s_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(src + lane * 16), "v"(src + 1024 + lane * 4), "s"(dst), "s"(dst + 1024u) : "memory");
   }
-  // ---- geometry: G = 1, so the workgroup's Rg tiles are this wave's, blocks [wave * nbw, (wave + 1) * nbw) of each
-  const uint32_t ntiles = (S.n_rows + 15) >> 4, tile0 = wg * Rg;
-  const uint32_t ntile_w = tile0 < ntiles ? min(Rg, ntiles - tile0) : 0;
+  // ---- geometry: G = 1, so the workgroup's ntile_w tiles (Rg, fewer in the segment's last workgroup; never none: mvqs_match)
+  // are this wave's, blocks [wave * nbw, (wave + 1) * nbw) of each.  The input vector, the planes and the tile count are
+  // leading kernel arguments (mvqs_kernel): nothing up to the first tile loads waits for the argument segment.
+  const uint32_t tile0 = wg * Rg;
   const uint64_t woff = ((uint64_t)tile0 * nblk + wave * nbw) * tb;
-  const uint8_t* pb0 = S.pass[0].plane[0] + woff;
-  const uint8_t* pb1 = NP > 1 ? S.pass[1].plane[0] + woff : nullptr;
+  const uint8_t* pb0 = plane0 + woff;
+  const uint8_t* pb1 = NP > 1 ? plane1 + woff : nullptr;
   float* red = reinterpret_cast<float*>(smem8 + kWaves * nbw * kXqRecord);
   float* ssq = red + red_floats;
   const uint32_t n = lane & 15, mq = lane >> 4;
@@ -723,9 +724,8 @@ __device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, 
     }
   };
   // a wave has NP * nbw items per tile: at least kDp of them unless the plan is one pass over two blocks and the workgroup one tile
-  // (a workgroup without a tile — mvq_plan makes none and mvqs_match refuses launches that have one — streams nothing)
-  if (ntile_w == 0) {
-  } else if (NP * nbw >= (uint32_t)kDp || ntile_w > 1) {
+  // (every workgroup has a tile: mvq_plan makes none without and mvqs_match refuses launches that have one)
+  if (NP * nbw >= (uint32_t)kDp || ntile_w > 1) {
     run(std::integral_constant<int, kDp>{});
   } else {
     run(std::integral_constant<int, (NP * nbw < (uint32_t)kDp ? NP * nbw : 1)>{});
@@ -762,22 +762,45 @@ __device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, 
   LGH_SPAN(1);
 }
 
-// rgpack = the tiles per workgroup of segments 0 | 1 << 8 | 2 << 16
+// The leading arguments are the ones the first loads of a wave need, and they arrive preloaded in SGPRs (with red_floats 13 of the
+// 14 user SGPRs a kernel can have preloaded; MvLaunch, by value, never is), so the x request and the first weight tiles leave
+// without a round trip to the argument segment; the epilogue's operands, further into L, have the whole weight stream to arrive in:
+//   xq      the input vector's XQ image (all passes and segments share it: mvqs_match)
+//   plane0  the weight plane of segment 0, pass 0
+//   plane1 / plane2   the plane of pass 1 (two-pass plans) or of segments 1 / 2 (fused launches)
+//   pos     the position word's address (RoPE and cache epilogues), so that its load is not behind one of the argument segment
+//   wbpack  first workgroup of segment 1 | of segment 2 << 10 | workgroups of the launch << 20
+//   tlpack  per segment s, bits [10 s, 10 s + 10): tiles per workgroup - 1 | (tiles of the segment's LAST workgroup - 1) << 5
 template <typename P>
-__global__ void __launch_bounds__(kWaves * 64) mvqs_kernel(uint32_t wbpack, uint32_t rgpack, uint32_t red_floats, const MvLaunch L) {
+__global__ void __launch_bounds__(kWaves * 64) mvqs_kernel(const uint8_t* xq, const uint8_t* plane0, const uint8_t* plane1, const uint8_t* plane2,
+                                                           const int* pos, uint32_t wbpack, uint32_t tlpack, uint32_t red_floats, const MvLaunch L) {
+  static_assert(P::nseg == 1 || P::npass == 1, "plane1 is the second pass's plane or the second segment's");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
-  LGH_TL_BEGIN(mvq, lgh::TL_MVQ, P::nblk | (rgpack & 0xFFu) << 16);
+  LGH_TL_BEGIN(mvq, lgh::TL_MVQ, P::nblk | ((tlpack & 31u) + 1u) << 16);
   const uint32_t bid = blockIdx.x;
   // The position word (RoPE and cache epilogues), read first thing — before anything in this kernel can have written memory, so it
-  // is a scalar load that goes out with the first kernarg loads.  A plain load on purpose: the compiler may copy the destination of
+  // is a scalar load that goes out at once.  A plain load on purpose: the compiler may copy the destination of
   // a load issued by inline asm before the wait its author placed, and the copy then holds whatever the register held.
   constexpr auto has_pos = [](int e) { return e == EPI_ROPE_Q || e == EPI_ROPE_K || e == EPI_V_CACHE; };
   constexpr bool kAnyPos = has_pos(P::epi(0)) || (P::nseg > 1 && has_pos(P::epi(1))) || (P::nseg > 2 && has_pos(P::epi(2)));
-  const uint32_t pos_now = kAnyPos ? (uint32_t)*L.pos : 0u;
-  if (P::nseg > 2 && bid >= (wbpack >> 16)) mvqs_body<P, (P::nseg > 2 ? 2 : 0)>(bid - (wbpack >> 16), rgpack >> 16, red_floats, pos_now, L, smem8);
-  else if (P::nseg > 1 && bid >= (wbpack & 0xFFFFu))
-    mvqs_body<P, (P::nseg > 1 ? 1 : 0)>(bid - (wbpack & 0xFFFFu), (rgpack >> 8) & 0xFFu, red_floats, pos_now, L, smem8);
-  else mvqs_body<P, 0>(bid, rgpack & 0xFFu, red_floats, pos_now, L, smem8);
+  const uint32_t pos_now = kAnyPos ? (uint32_t)*pos : 0u;
+  const uint32_t wb1 = wbpack & 0x3FFu, wb2 = (wbpack >> 10) & 0x3FFu, n_wg = wbpack >> 20;
+  auto tiles = [&](int s, uint32_t wg_end, uint32_t& Rg) {   // of this workgroup, in segment s that ends before workgroup wg_end
+    const uint32_t t = tlpack >> (10 * s);
+    Rg = (t & 31u) + 1u;
+    return bid + 1 == wg_end ? ((t >> 5) & 31u) + 1u : Rg;
+  };
+  uint32_t Rg;
+  if (P::nseg > 2 && bid >= wb2) {
+    const uint32_t nt = tiles(2, n_wg, Rg);
+    mvqs_body<P, (P::nseg > 2 ? 2 : 0)>(bid - wb2, Rg, nt, xq, plane2, nullptr, red_floats, pos_now, L, smem8);
+  } else if (P::nseg > 1 && bid >= wb1) {
+    const uint32_t nt = tiles(1, P::nseg > 2 ? wb2 : n_wg, Rg);
+    mvqs_body<P, (P::nseg > 1 ? 1 : 0)>(bid - wb1, Rg, nt, xq, plane1, nullptr, red_floats, pos_now, L, smem8);
+  } else {
+    const uint32_t nt = tiles(0, P::nseg > 1 ? wb1 : n_wg, Rg);
+    mvqs_body<P, 0>(bid, Rg, nt, xq, plane0, plane1, red_floats, pos_now, L, smem8);
+  }
   LGH_TL_END();
 }
 
@@ -865,11 +888,32 @@ uint32_t mvq_pack(const MvLaunch& L, uint32_t n_wg, uint32_t threads, MvGeom* g,
   return mask;
 }
 
+// the leading arguments of mvqs_kernel; false = the launch does not fit them (the generic kernel takes it)
+struct MvsArgs { const uint8_t *xq, *plane0, *plane1, *plane2; uint32_t wbpack, tlpack; };
 template <typename P>
-static hipError_t mvqs_go(const MvLaunch& L, uint32_t n_wg, size_t lds, hipStream_t st, uint32_t wbpack, uint32_t rgpack) {
+static bool mvqs_args(const MvLaunch& L, uint32_t n_wg, MvsArgs* a) {
+  a->xq = L.seg[0].pass[0].xq;
+  a->plane0 = L.seg[0].pass[0].plane[0];
+  a->plane1 = P::npass > 1 ? L.seg[0].pass[1].plane[0] : P::nseg > 1 ? L.seg[1].pass[0].plane[0] : nullptr;
+  a->plane2 = P::nseg > 2 ? L.seg[2].pass[0].plane[0] : nullptr;
+  if (n_wg > 0xFFFu) return false;
+  a->wbpack = n_wg << 20;
+  a->tlpack = 0;
+  for (int s = 0; s < P::nseg; s++) {
+    const MvSeg& S = L.seg[s];
+    const uint32_t R = S.rows_per_wg / 16, tiles = (S.n_rows + 15) / 16, last = tiles - (tiles - 1) / R * R;   // 1 .. R
+    if (R > 32 || (s > 0 && S.wg_begin > 0x3FFu)) return false;
+    a->tlpack |= ((R - 1) | (last - 1) << 5) << (10 * s);
+    if (s > 0) a->wbpack |= S.wg_begin << (10 * (s - 1));
+  }
+  return true;
+}
+
+template <typename P>
+static hipError_t mvqs_go(const MvLaunch& L, uint32_t n_wg, size_t lds, hipStream_t st, const MvsArgs& a) {
   static bool attr_set[64] = {};
   if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvqs_kernel<P>), 160 * 1024, attr_set); e != hipSuccess) return e;
-  hipLaunchKernelGGL((mvqs_kernel<P>), dim3(n_wg), dim3(kWaves * 64), lds, st, wbpack, rgpack, L.red_floats, L);
+  hipLaunchKernelGGL((mvqs_kernel<P>), dim3(n_wg), dim3(kWaves * 64), lds, st, a.xq, a.plane0, a.plane1, a.plane2, L.pos, a.wbpack, a.tlpack, L.red_floats, L);
   return hipGetLastError();
 }
 
@@ -905,11 +949,10 @@ uint64_t mvq_static_launches() { return g_static_launches.load(std::memory_order
 
 // The static plan of a launch, if its geometry, formats, passes and epilogues are an entry of the table.
 template <typename P>
-static bool mvqs_try(const MvLaunch& L, uint32_t n_wg, uint32_t threads, size_t lds, hipStream_t st, uint32_t wbpack, hipError_t* e) {
-  if (!mvqs_match<P>(L, n_wg, threads)) return false;
-  uint32_t rgpack = 0;
-  for (int s = 0; s < P::nseg; s++) rgpack |= (L.seg[s].rows_per_wg / 16) << (8 * s);
-  *e = mvqs_go<P>(L, n_wg, lds, st, wbpack, rgpack);
+static bool mvqs_try(const MvLaunch& L, uint32_t n_wg, uint32_t threads, size_t lds, hipStream_t st, hipError_t* e) {
+  MvsArgs a;
+  if (!mvqs_match<P>(L, n_wg, threads) || !mvqs_args<P>(L, n_wg, &a)) return false;
+  *e = mvqs_go<P>(L, n_wg, lds, st, a);
   g_static_launches.fetch_add(1, std::memory_order_relaxed);
   return true;
 }
@@ -924,14 +967,14 @@ hipError_t mvq_launch(const MvLaunch& L0, uint32_t n_wg, uint32_t threads, hipSt
   if (mask && !generic) {
     hipError_t e = hipSuccess;
     if (!want_amax) L.amax_v = nullptr;
-    if (mvqs_try<MvsOutput>(L, n_wg, threads, lds, st, g.wbpack, &e)) {
+    if (mvqs_try<MvsOutput>(L, n_wg, threads, lds, st, &e)) {
       if (amax_done) *amax_done = want_amax && e == hipSuccess;
       return e;
     }
     L.amax_v = nullptr;
-    if (mvqs_try<MvsQkv446>(L, n_wg, threads, lds, st, g.wbpack, &e) || mvqs_try<MvsQkv444>(L, n_wg, threads, lds, st, g.wbpack, &e) ||
-        mvqs_try<MvsWo>(L, n_wg, threads, lds, st, g.wbpack, &e) || mvqs_try<MvsGateUp>(L, n_wg, threads, lds, st, g.wbpack, &e) ||
-        mvqs_try<MvsDown4>(L, n_wg, threads, lds, st, g.wbpack, &e) || mvqs_try<MvsDown6>(L, n_wg, threads, lds, st, g.wbpack, &e))
+    if (mvqs_try<MvsQkv446>(L, n_wg, threads, lds, st, &e) || mvqs_try<MvsQkv444>(L, n_wg, threads, lds, st, &e) ||
+        mvqs_try<MvsWo>(L, n_wg, threads, lds, st, &e) || mvqs_try<MvsGateUp>(L, n_wg, threads, lds, st, &e) ||
+        mvqs_try<MvsDown4>(L, n_wg, threads, lds, st, &e) || mvqs_try<MvsDown6>(L, n_wg, threads, lds, st, &e))
       return e;
   }
   L.amax_v = nullptr;

@@ -460,6 +460,18 @@ float* up_kv_new(Tmp& t, const float* k_new, const float* v_new, size_t kd) {
   return d;
 }
 
+// an f32 KV cache with kAttnSlackRows rows of NaN behind the last head: a decode attention kernel whose row clamp is off by up to a
+// first batch of rows (32 splits x 8 waves x 4 rows) reads those, not whatever follows the allocation
+constexpr size_t kAttnSlackRows = 1024;
+float* up_cache(Tmp& t, const float* host, size_t n, size_t head_dim) {
+  const size_t slack = kAttnSlackRows * head_dim;
+  float* d = t.up(nullptr, n + slack);
+  if (!d || hipMemcpyAsync(d, host, n * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+      hipMemsetAsync(d + n, 0xFF, slack * 4, t.c->stream) != hipSuccess)
+    return nullptr;
+  return d;
+}
+
 float half_to_float(uint16_t h) {
   const uint32_t s = (uint32_t)(h >> 15) << 31, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
   float v;
@@ -491,8 +503,8 @@ int lgh_op_attention_decode(int device, int path, const float* q, const float* k
   if (path == 0 && (n_splits < 1 || n_splits > 32)) return LGH_INVALID_ARGUMENT;
   if (path == 2 && max_seq * 4 > 150 * 1024) return LGH_UNSUPPORTED;   // the scores of a head live in LDS
   LayerW Lw;
-  Lw.kcache = t.up(k_cache, cache);
-  Lw.vcache = t.up(v_cache, cache);
+  Lw.kcache = up_cache(t, k_cache, cache, head_dim);
+  Lw.vcache = up_cache(t, v_cache, cache, head_dim);
   const AttnView v{nullptr, t.up(q, n_heads * head_dim), nullptr, t.up(nullptr, n_heads * head_dim)};   // (f32 cache: no staged rows)
   if (!v.q || !Lw.kcache || !Lw.vcache || !v.attn_out) return LGH_ALLOCATION_FAILED;
   int rc;
@@ -503,6 +515,38 @@ int lgh_op_attention_decode(int device, int path, const float* q, const float* k
   t.c->attn_generic = path == 2;
   if (attention_forward(t.c, Lw, 0, v, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
   return t.down(out, v.attn_out, n_heads * head_dim);
+}
+
+int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads, size_t n_kv,
+                                  size_t head_dim, size_t max_seq, size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale,
+                                  int n_splits) {
+  // the multi-sequence decode step's attention (engine_batch.hip: attn_multi_launch + attn_combine_multi_launch) over f32 cache slots
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!q || !k_cache || !v_cache || !out || !pos || !slot || n_kv == 0 || n_heads % n_kv || head_dim == 0 || max_seq == 0 || max_seq > 0x7FFFFFFFu ||
+      n_slots == 0 || n_seq == 0 || n_seq > (size_t)kMaxBatch || n_splits < 1 || n_splits > 32)
+    return LGH_INVALID_ARGUMENT;
+  for (size_t s = 0; s < n_seq; s++)
+    if (pos[s] < 0 || (size_t)pos[s] >= max_seq || slot[s] < 0 || (size_t)slot[s] >= n_slots) return LGH_INVALID_ARGUMENT;
+  if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
+  const size_t per_slot = n_kv * max_seq * head_dim, QD = n_heads * head_dim, parts = n_seq * n_heads * (size_t)n_splits;
+  const float* dk = up_cache(t, k_cache, n_slots * per_slot, head_dim);
+  const float* dv = up_cache(t, v_cache, n_slots * per_slot, head_dim);
+  const float* dq = t.up(q, n_seq * QD);
+  float* dout = t.up(nullptr, n_seq * QD);
+  float* part_ml = t.up(nullptr, parts * 2);
+  float* part_acc = t.up(nullptr, parts * head_dim);
+  int* dps = (int*)up_bytes(t, nullptr, 2 * n_seq * 4);
+  if (!dk || !dv || !dq || !dout || !part_ml || !part_acc || !dps) return LGH_ALLOCATION_FAILED;
+  if (hipMemcpyAsync(dps, pos, n_seq * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+      hipMemcpyAsync(dps + n_seq, slot, n_seq * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  if (attn_multi_launch(dq, dk, dv, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, scale, dps, dps + n_seq, per_slot,
+                        (uint32_t)n_seq, (uint32_t)n_splits, part_ml, part_acc, t.c->stream) != hipSuccess ||
+      attn_combine_multi_launch(part_ml, part_acc, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)n_splits, (uint32_t)n_seq, dout,
+                                nullptr, t.c->stream) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  return t.down(out, dout, n_seq * QD);
 }
 
 int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,

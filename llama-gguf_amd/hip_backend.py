@@ -39,7 +39,7 @@ ABI_SYMBOLS = (
     "lgh_batch_create", "lgh_batch_reset", "lgh_batch_position", "lgh_batch_prefill", "lgh_forward_multi", "lgh_decode_greedy_multi",
     "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
     "lgh_set_sampler_ex", "lgh_batch_set_sampler_ex", "lgh_get_sampler_mu", "lgh_op_sample_ex",
-    "lgh_op_attention_decode", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
+    "lgh_op_attention_decode", "lgh_op_attention_decode_multi", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
     "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches",
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
     "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq",
@@ -228,6 +228,7 @@ def load_library() -> C.CDLL:
         "lgh_get_sampler_mu": (C.c_int, [vp, C.c_int, C.POINTER(f32)]),
         "lgh_op_sample_ex": (C.c_int, [C.c_int, vp, sz, C.POINTER(SamplerConfigEx), vp, sz, vp, f32, f32, C.POINTER(u32), C.POINTER(f32)]),
         "lgh_op_attention_decode": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
+        "lgh_op_attention_decode_multi": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, f32, C.c_int]),
         "lgh_op_attention_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_prefill": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
@@ -737,6 +738,18 @@ def op_attention_decode(path: int, q, k_cache, v_cache, scale: float, pos: int, 
     out = np.empty_like(q)
     _chk(load_library().lgh_op_attention_decode(device, path, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, out.ctypes.data, q.shape[0],
                                                 kc.shape[0], q.shape[1], kc.shape[1], scale, pos, n_splits), "attention_decode")
+    return out
+
+
+def op_attention_decode_multi(q, k_cache, v_cache, scale: float, pos, slot, n_splits: int = 8, device: int = 0) -> np.ndarray:
+    """The multi-sequence decode step's split + merge attention: sequence s attends to rows 0..pos[s] of cache slot slot[s].
+    q [n_seq, nh, d]; caches [n_slots, nkv, max_seq, d]; -> [n_seq, nh, d]."""
+    q, kc, vc = _f32(q), _f32(k_cache), _f32(v_cache)
+    pos, slot = np.ascontiguousarray(pos, dtype=np.int32), np.ascontiguousarray(slot, dtype=np.int32)
+    out = np.empty_like(q)
+    _chk(load_library().lgh_op_attention_decode_multi(device, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, out.ctypes.data, q.shape[1],
+                                                      kc.shape[1], q.shape[2], kc.shape[2], kc.shape[0], q.shape[0], pos.ctypes.data,
+                                                      slot.ctypes.data, scale, n_splits), "attention_decode_multi")
     return out
 
 
