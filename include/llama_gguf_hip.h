@@ -271,14 +271,15 @@ int lgh_op_tq_compress_qjl(int device, int bits, const float* x, size_t dim, con
 /* ---- multi-sequence decode: the device side of BatchedEngine (src/engine_batched.rs:23-194, 200-330, 355-400) ----
  * The reference keeps one InferenceContext (KV cache + position) per ActiveSequence (engine_batched.rs:84-100, 332-353) and every
  * iteration of its loop calls model.forward for each active sequence in turn (236-290 -> step_sequence 355-400): B sequences read
- * the weights B times.  Here a finalized single-stage context owns `max_batch` <= 16 SLOTS (a slot = one sequence's f32 KV caches
+ * the weights B times.  Here a finalized single-stage context owns `max_batch` <= 16 SLOTS (a slot = one sequence's KV caches
  * + position), and one step feeds one token to each listed slot while reading every weight tile ONCE.  Every sequence's
  * logits are bit-identical to what lgh_forward returns for the same token history (same arithmetic, same summation orders).
  * Dense and MoE models whose matrices are in the matrix-core tile layouts (Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0, k % 256 == 0);
- * anything else answers LGH_UNSUPPORTED.  The slots' caches have the context's kv_cache_type: f32, or the TurboQuant formats
- * (LGH_KV_TQ2 / TQ3 / TQ2_QJL / TQ3_QJL: per slot the packed code rows (+ QJL rows); the reference's BatchedEngine itself only
- * ever creates f32 caches, engine_batched.rs:355-357); int8 / FP8 caches are not batched.  The single-sequence entry points keep
- * working on the context's own cache.  (A serving context is better created with 8 attention splits — flags bits 8..15 — than with
+ * anything else answers LGH_UNSUPPORTED.  The slots' caches have the context's kv_cache_type: f32, int8 / FP8
+ * (LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2: per slot a byte per element, + one f32 scale per int8 row: about a quarter of the f32 slots'
+ * memory) or the TurboQuant formats (LGH_KV_TQ2 / TQ3 / TQ2_QJL / TQ3_QJL: per slot the packed code rows (+ QJL rows)); the
+ * reference's BatchedEngine itself only ever creates f32 caches, engine_batched.rs:355-357.  Slots with a quantized cache take
+ * their prompt token by token (lgh_batch_prefill).  The single-sequence entry points keep working on the context's own cache.  (A serving context is better created with 8 attention splits — flags bits 8..15 — than with
  * the single-sequence default: the split count also sizes the multi-sequence attention launch, profiles/r03e_batched_decode.md.) */
 int lgh_batch_create(lgh_ctx* ctx, uint32_t max_batch);                 /* BatchedEngineConfig::max_batch_size (engine_batched.rs:23-41) */
 int lgh_batch_reset(lgh_ctx* ctx, uint32_t slot);                       /* create_active_sequence: model.create_context (332-353); O(1) */
@@ -502,6 +503,17 @@ int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cac
 int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
                          const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv_heads, size_t head_dim,
                          size_t max_seq_len, float scale, size_t pos, int n_splits);
+/* The same over the byte-cache slots of a multi-sequence decode step: sequence s of n_seq (1..16) attends, with q [n_seq][n_heads][head_dim],
+ * to rows 0..pos[s]-1 of slot slot[s] and to its own k_new / v_new [n_seq][n_kv_heads][head_dim], which the launch quantizes and stores
+ * at row pos[s] of that slot.  k_bytes / v_bytes [n_slots][n_kv_heads][max_seq_len][head_dim] and (int8 only; may be NULL otherwise)
+ * k_scale / v_scale [n_slots][n_kv_heads][max_seq_len] are in / out; out [n_seq][n_heads][head_dim].  Every sequence's output is
+ * bit-identical to lgh_op_attention_kv8 on its slot alone with the same n_splits.  LGH_UNSUPPORTED: a kv_cache_type outside int8 /
+ * FP8, a shape without a kernel; LGH_INVALID_ARGUMENT: pos[s] >= max_seq_len, slot[s] >= n_slots, a slot listed twice, n_seq or
+ * n_slots outside 1..16. */
+int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale,
+                               float* v_scale, const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv_heads,
+                               size_t head_dim, size_t max_seq_len, size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale,
+                               int n_splits);
 /* TurboQuantKVCache::write_kv + attention_layer (kv_turboquant.rs:88-201): kv_cache_type LGH_KV_TQ2 / TQ3 / TQ2_QJL / TQ3_QJL.
  * k_codes / v_codes [n_kv_heads][max_seq_len][row bytes] and, for the QJL types, k_qjl [n_kv_heads][max_seq_len][head_dim / 32 + 1]
  * words (sign bits, then the residual norm's bits) are in / out: row `pos` comes back as the launch compressed k_new / v_new.

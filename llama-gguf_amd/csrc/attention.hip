@@ -271,20 +271,36 @@ __device__ __forceinline__ f32x4 unpack_kv4(uint32_t w, float scale) {
   return r;
 }
 
-template <int D, int G, int NW, int FMT>
+// MULTI (multi-sequence decode, engine_batch.hip): blockIdx.y = sequence s of the step; its query is q + s * n_heads * D, its position
+// pos_ptr[s], its cache the slot slot[s] of [slot][kv_head][max_seq][D] bytes (and [slot][kv_head][max_seq] scales), its staged rows
+// k_new / v_new + s * x_stride, its partials the s-th block of part_ml / part_acc.  Per sequence the arithmetic is the single-sequence
+// kernel's (same NW, same split strides, same merges): the outputs are bit-identical.
+template <int D, int G, int NW, int FMT, bool MULTI = false>
 __global__ void __launch_bounds__(NW * 64) attn_partial_q8_kernel(const float* __restrict__ q, int8_t* __restrict__ k8, int8_t* __restrict__ v8,
                                                                   float* __restrict__ kscale, float* __restrict__ vscale,
                                                                   const float* __restrict__ k_new, const float* __restrict__ v_new,
                                                                   uint32_t max_seq, float scale, const int* pos_ptr, uint32_t n_splits,
-                                                                  float* __restrict__ part_ml, float* __restrict__ part_acc) {
+                                                                  float* __restrict__ part_ml, float* __restrict__ part_acc,
+                                                                  const int* __restrict__ slot = nullptr, uint32_t x_stride = 0) {
   constexpr int LPR = D / 4, RPW = 64 / LPR;
   __shared__ float s_ml[NW][G][2];
   __shared__ float s_acc[NW][G][D];
   const uint32_t kvh = blockIdx.x / n_splits, sp = blockIdx.x % n_splits;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t sub = lane / LPR, li = lane % LPR;
-  uint32_t pw;
-  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pw) : "s"(pos_ptr) : "memory");
+  uint32_t pw, sl = 0;
+  if (MULTI) {   // position and slot by scalar loads, as attn_partial_kernel<MULTI> reads them
+    const uint32_t sq = blockIdx.y, n_kv = gridDim.x / n_splits;
+    asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(pw), "=&s"(sl) : "s"(pos_ptr + sq), "s"(slot + sq) : "memory");
+    q += (size_t)sq * n_kv * G * D;
+    k_new += (size_t)sq * x_stride;
+    v_new += (size_t)sq * x_stride;
+    part_ml += (size_t)sq * gridDim.x * G * 2;
+    part_acc += (size_t)sq * gridDim.x * G * D;
+    sl *= n_kv;   // the slot's first kv head, in heads
+  } else {
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pw) : "s"(pos_ptr) : "memory");
+  }
   const uint32_t pos = pw;   // rows [0, pos) come from the cache, row `pos` from the staging vectors
   f32x4 qv[G];
 #pragma unroll
@@ -314,7 +330,7 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_q8_kernel(const float* _
       m[g] = mn;
     }
   };
-  const size_t hrow = (size_t)kvh * max_seq;
+  const size_t hrow = MULTI ? ((size_t)sl + kvh) * max_seq : (size_t)kvh * max_seq;   // first row of this kv head (of this slot)
   const uint32_t stride = n_splits * NW * RPW;
   constexpr int kAhead = 4;
   for (uint32_t base = (sp * NW + wave) * RPW; base < pos; base += kAhead * stride) {
@@ -416,6 +432,41 @@ hipError_t attn_q8_launch(int fmt, const float* q, int8_t* k8, int8_t* v8, float
   const uint32_t g = n_heads / n_kv;
 #define LGH_ATTN_CASE(DD, GG) \
   if (head_dim == DD && g == GG) return attn_q8_go<DD, GG>(fmt, q, k8, v8, kscale, vscale, k_new, v_new, n_kv, max_seq, scale, pos, n_splits, part_ml, part_acc, st);
+  LGH_ATTN_CASE(128, 1) LGH_ATTN_CASE(128, 2) LGH_ATTN_CASE(128, 4) LGH_ATTN_CASE(128, 8)
+  LGH_ATTN_CASE(64, 1) LGH_ATTN_CASE(64, 2) LGH_ATTN_CASE(64, 4) LGH_ATTN_CASE(64, 8)
+#undef LGH_ATTN_CASE
+  return hipErrorInvalidValue;
+}
+
+// ---- multi-sequence decode over byte-cache slots (engine_batch.hip): the n_seq sequences of a step in one launch.  NW = 4 whatever
+// max_seq is, as attn_q8_go launches the single sequence: with another wave count the rows would be dealt differently and the
+// sums would differ in their last bits.
+template <int D, int G>
+static hipError_t attn_q8_multi_go(int fmt, const float* q, int8_t* k8, int8_t* v8, float* ks, float* vs, const float* k_new, const float* v_new,
+                                   uint32_t x_stride, uint32_t n_kv, uint32_t max_seq, float scale, const int* pos, const int* slot, uint32_t n_seq,
+                                   uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
+#define LGH_Q8_GO(FMT)                                                                                                                        \
+  hipLaunchKernelGGL((attn_partial_q8_kernel<D, G, 4, FMT, true>), dim3(n_kv * n_splits, n_seq), dim3(256), 0, st, q, k8, v8, ks, vs, k_new, \
+                     v_new, max_seq, scale, pos, n_splits, part_ml, part_acc, slot, x_stride)
+  if (fmt == 1) LGH_Q8_GO(1);
+  else if (fmt == 2) LGH_Q8_GO(2);
+  else if (fmt == 3) LGH_Q8_GO(3);
+  else return hipErrorInvalidValue;
+#undef LGH_Q8_GO
+  return hipGetLastError();
+}
+
+// caches [slot][n_kv][max_seq][D] bytes, scales (int8) [slot][n_kv][max_seq]; k_new / v_new of sequence s at + s * x_stride floats;
+// pos / slot: n_seq device words each
+hipError_t attn_q8_multi_launch(int fmt, const float* q, int8_t* k8, int8_t* v8, float* kscale, float* vscale, const float* k_new, const float* v_new,
+                                uint32_t x_stride, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos,
+                                const int* slot, uint32_t n_seq, uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
+  if (n_kv == 0 || n_heads % n_kv || !pos || !slot || n_seq == 0 || n_splits == 0 || n_splits > 32) return hipErrorInvalidValue;
+  if (fmt == 1 && (!kscale || !vscale)) return hipErrorInvalidValue;
+  const uint32_t g = n_heads / n_kv;
+#define LGH_ATTN_CASE(DD, GG)    \
+  if (head_dim == DD && g == GG) \
+    return attn_q8_multi_go<DD, GG>(fmt, q, k8, v8, kscale, vscale, k_new, v_new, x_stride, n_kv, max_seq, scale, pos, slot, n_seq, n_splits, part_ml, part_acc, st);
   LGH_ATTN_CASE(128, 1) LGH_ATTN_CASE(128, 2) LGH_ATTN_CASE(128, 4) LGH_ATTN_CASE(128, 8)
   LGH_ATTN_CASE(64, 1) LGH_ATTN_CASE(64, 2) LGH_ATTN_CASE(64, 4) LGH_ATTN_CASE(64, 8)
 #undef LGH_ATTN_CASE

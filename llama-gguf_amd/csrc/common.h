@@ -264,6 +264,11 @@ hipError_t kv_roundtrip_launch(int fmt, const float* x, uint32_t n, uint8_t* byt
 hipError_t attn_q8_launch(int fmt, const float* q, int8_t* k8, int8_t* v8, float* kscale, float* vscale, const float* k_new, const float* v_new,
                           uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, uint32_t n_splits,
                           float* part_ml, float* part_acc, hipStream_t st);
+// ... for the n_seq sequences of a multi-sequence step: caches [slot][n_kv][max_seq][D], scales [slot][n_kv][max_seq], sequence s's staged
+// rows at k_new / v_new + s * x_stride floats, its position pos[s] and slot slot[s] (device words)
+hipError_t attn_q8_multi_launch(int fmt, const float* q, int8_t* k8, int8_t* v8, float* kscale, float* vscale, const float* k_new, const float* v_new,
+                                uint32_t x_stride, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos,
+                                const int* slot, uint32_t n_seq, uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st);
 // decode attention over the TurboQuant code caches (attention_tq.hip); signs: the layer's [n_kv][2][head_dim]
 hipError_t attn_tq_launch(int bits, const float* q, uint8_t* kq, uint8_t* vq, const float* k_new, const float* v_new, const float* signs,
                           uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, uint32_t n_splits,

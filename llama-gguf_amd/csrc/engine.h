@@ -74,6 +74,10 @@ struct BatchScratch {
   std::vector<uint32_t*> kx;
   float* kv_tmp = nullptr;
   uint64_t code_stride = 0, x_stride = 0;             // bytes / words between two slots
+  // int8 / FP8 caches (LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2): kq / vq hold the slots' rows [slot][kv_head][max_seq][head_dim], one byte per
+  // element, and (int8) kscale / vscale the rows' scales [slot][kv_head][max_seq]; kv_tmp as above (K row after RoPE | V row), quantized
+  // and stored by the attention launch
+  std::vector<float*> kscale, vscale;
   // MoE layers, experts read once per step (top-k <= 2): the (sequence, slot) pairs' activations [pair][ffn] (+ XQ views) and expert
   // outputs [pair][hidden]; per expert the number of pairs that chose it and their list
   float *moe_act = nullptr, *moe_tmp = nullptr;

@@ -5,8 +5,8 @@
 // `model.forward` for each active sequence in turn: B sequences read the weights B times.  Here a context owns `max_batch`
 // SLOTS — a slot = one sequence's KV caches + position — and lgh_forward_multi feeds one token to each listed slot in ONE pass
 // over the weights: every quantized mat-vec launch reads its tiles once and multiplies them with all n_seq input vectors
-// (matvec_batch.hip), attention / its merge / embedding / arg-max run with the sequence as the grid's second dimension (over f32 or
-// TurboQuant slots); MoE layers route every sequence to its own experts: from 3 sequences on (moe_group_min) the step's (sequence,
+// (matvec_batch.hip), attention / its merge / embedding / arg-max run with the sequence as the grid's second dimension (over f32,
+// int8 / FP8 or TurboQuant slots); MoE layers route every sequence to its own experts: from 3 sequences on (moe_group_min) the step's (sequence,
 // slot) pairs are grouped by expert and each selected expert is read once — all experts of a layer in one gate | up and one down
 // launch, the expert as the grid's third dimension — below that the FFN runs sequence by sequence.  Every sequence's logits are
 // bit-identical to what the single-sequence engine computes for the same tokens (tests/test_gpu_batch.py): same kernels'
@@ -127,7 +127,6 @@ bool batch_weights_ok(const lgh_ctx* c, std::string& why) {
   if (d.hidden_size % 256 || (d.num_heads * d.head_dim) % 256) { why = "hidden size and heads x head_dim must be multiples of 256"; return false; }
   if (d.use_neox_rope) { why = "NeoX RoPE is not fused into the QKV launch"; return false; }
   if (!attn_shape_has_fast_kernel(d.head_dim, d.num_heads / d.num_kv_heads)) { why = "attention shape outside the split kernels"; return false; }
-  if ((d.flags & LGH_FLAG_KV_INT8) && !kv_is_tq(d.kv_cache_type)) { why = "the int8 / FP8 KV caches are not batched (f32 and TurboQuant are)"; return false; }
   if (!(c->first && c->last)) { why = "pipeline stages are not batched"; return false; }
   for (uint32_t i = c->l0; i < c->l1; i++) {
     const LayerW& L = c->layers[i];
@@ -177,11 +176,11 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
     const float* next_nw = li + 1 < c->l1 ? c->layers[li + 1].attn_norm : c->output_norm;
     // ---- Q, K, V (+ RoPE at every sequence's own position, K / V rows into its own cache slot)
     {
-      const bool tq = kv_is_tq(d.kv_cache_type);
+      const bool tq = (d.flags & LGH_FLAG_KV_INT8) != 0;   // every quantized cache (TurboQuant, int8, FP8) stages its rows
       const uint32_t KD = d.num_kv_heads * d.head_dim;
       SegSpec sp[3];
       sp[0].W[0] = &Lw.wq; sp[0].x[0] = Bs.hidden; sp[0].epi = EPI_ROPE_Q; sp[0].out = Bs.q; sp[0].bias = Lw.bq;
-      // (TurboQuant: the rotated K row and the V row stay f32 in a staging vector per sequence; the attention launch compresses them)
+      // (quantized caches: the rotated K row and the V row stay f32 in a staging vector per sequence; the attention launch compresses them)
       sp[1].W[0] = &Lw.wk; sp[1].x[0] = Bs.hidden; sp[1].epi = tq ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = tq ? Bs.kv_tmp : Bs.kcache[li]; sp[1].bias = Lw.bk;
       sp[2].W[0] = &Lw.wv; sp[2].x[0] = Bs.hidden; sp[2].epi = tq ? EPI_STORE : EPI_V_CACHE; sp[2].out = tq ? Bs.kv_tmp + KD : Bs.vcache[li]; sp[2].bias = Lw.bv;
       const uint32_t os[3] = {QD, tq ? 2 * KD : 0, tq ? 2 * KD : 0}, rs[3] = {0, 0, 0}, xk[3] = {0, 0, 0};
@@ -209,6 +208,20 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
       if ((rc = merge([&](uint8_t* img) {
              return attn_tq_combine_launch(bits, Bs.part_ml, Bs.part_acc, signs, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, Bs.attn_out, img,
                                            c->stream, n_seq, (uint32_t)xq_stride_of(QD));
+           })))
+        return rc;
+    } else if (d.flags & LGH_FLAG_KV_INT8) {
+      // QuantizedKVCache (kv_quantized.rs) per sequence: the launch quantizes and stores each sequence's staged rows into its slot; the
+      // partials merge as f32 ones do (as in the single-sequence engine)
+      const uint32_t KD = d.num_kv_heads * d.head_dim;
+      if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
+             return attn_q8_multi_launch((int)d.kv_cache_type, Bs.q, (int8_t*)Bs.kq[li], (int8_t*)Bs.vq[li], Bs.kscale[li], Bs.vscale[li], Bs.kv_tmp,
+                                         Bs.kv_tmp + KD, 2 * KD, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, n_seq,
+                                         c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
+           })))
+        return rc;
+      if ((rc = merge([&](uint8_t* img) {
+             return attn_combine_multi_launch(Bs.part_ml, Bs.part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, n_seq, Bs.attn_out, img, c->stream);
            })))
         return rc;
     } else {
@@ -435,17 +448,25 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
   Bs.kq.assign(d.num_layers, nullptr);
   Bs.vq.assign(d.num_layers, nullptr);
   Bs.kx.assign(d.num_layers, nullptr);
+  Bs.kscale.assign(d.num_layers, nullptr);
+  Bs.vscale.assign(d.num_layers, nullptr);
+  const bool kv8 = (d.flags & LGH_FLAG_KV_INT8) && !kv_is_tq(d.kv_cache_type);   // int8 / FP8: a byte per element (+ a scale per int8 row)
+  if (kv8) {   // QuantizedKVCache::new per slot (kv_quantized.rs:143-300)
+    Bs.code_stride = (uint64_t)d.num_kv_heads * d.max_seq_len * d.head_dim;
+    if ((rc = dev_alloc(c, (void**)&Bs.kv_tmp, B * 2 * d.num_kv_heads * d.head_dim * 4))) return rc;
+  }
   if (kv_is_tq(d.kv_cache_type)) {   // TurboQuantKVCache::new per slot (kv_turboquant.rs:36-86): packed codes (+ QJL rows of K)
     const size_t rows = (size_t)d.num_kv_heads * d.max_seq_len;
     Bs.code_stride = rows * tq_row_bytes_host(kv_tq_bits(d.kv_cache_type), d.head_dim);
     Bs.x_stride = rows * (d.head_dim / 32 + 1);
     if ((rc = dev_alloc(c, (void**)&Bs.kv_tmp, B * 2 * d.num_kv_heads * d.head_dim * 4))) return rc;
   }
-  for (uint32_t i = c->l0; i < c->l1; i++) {   // per layer, every slot's cache: code rows (+ QJL rows of K), or f32 [slot][kv_head][max_seq][head_dim]
+  for (uint32_t i = c->l0; i < c->l1; i++) {   // per layer, every slot's cache: code rows (+ QJL rows of K), byte rows (+ int8 scales), or f32 [slot][kv_head][max_seq][head_dim]
     const bool tq = kv_is_tq(d.kv_cache_type);
-    const size_t n = tq ? B * Bs.code_stride : 0, nf = tq ? 0 : B * Bs.cache_stride * 4;
+    const size_t n = tq || kv8 ? B * Bs.code_stride : 0, nf = tq || kv8 ? 0 : B * Bs.cache_stride * 4;
+    const size_t ns = d.kv_cache_type == LGH_KV_INT8 ? B * d.num_kv_heads * d.max_seq_len * 4 : 0;
     const AllocSpec kv[] = {{(void**)&Bs.kq[i], n}, {(void**)&Bs.vq[i], n}, {(void**)&Bs.kx[i], kv_is_qjl(d.kv_cache_type) ? B * Bs.x_stride * 4 : 0},
-                            {(void**)&Bs.kcache[i], nf}, {(void**)&Bs.vcache[i], nf}};
+                            {(void**)&Bs.kscale[i], ns}, {(void**)&Bs.vscale[i], ns}, {(void**)&Bs.kcache[i], nf}, {(void**)&Bs.vcache[i], nf}};
     if ((rc = alloc_zeroed(c, kv, sizeof(kv) / sizeof(kv[0]), c->stats.kv_bytes))) return rc;
   }
   {   // MoE layers: the expert-grouped step's buffers ((sequence, slot) pairs)

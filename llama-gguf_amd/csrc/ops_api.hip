@@ -576,6 +576,56 @@ int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int
   return t.down(out, v.attn_out, n_heads * head_dim);
 }
 
+int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
+                               const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq,
+                               size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale, int n_splits) {
+  // the multi-sequence decode step's attention over byte-cache slots (engine_batch.hip: attn_q8_multi_launch + attn_combine_multi_launch)
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (kv_cache_type < LGH_KV_INT8 || kv_cache_type > LGH_KV_FP8_E5M2) return LGH_UNSUPPORTED;
+  const bool i8 = kv_cache_type == LGH_KV_INT8;
+  if (!q || !k_bytes || !v_bytes || !k_new || !v_new || !out || !pos || !slot || (i8 && (!k_scale || !v_scale))) return LGH_INVALID_ARGUMENT;
+  if (n_kv == 0 || n_heads % n_kv || head_dim == 0 || max_seq == 0 || max_seq > 0x7FFFFFFFu || n_slots == 0 || n_slots > (size_t)kMaxBatch ||
+      n_seq == 0 || n_seq > (size_t)kMaxBatch || n_splits < 1 || n_splits > 32)
+    return LGH_INVALID_ARGUMENT;
+  bool seen[kMaxBatch] = {};
+  for (size_t s = 0; s < n_seq; s++) {   // (two sequences on one slot would both store a row into it)
+    if (pos[s] < 0 || (size_t)pos[s] >= max_seq || slot[s] < 0 || (size_t)slot[s] >= n_slots || seen[slot[s]]) return LGH_INVALID_ARGUMENT;
+    seen[slot[s]] = true;
+  }
+  if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
+  const size_t rows = n_slots * n_kv * max_seq, cache = rows * head_dim, QD = n_heads * head_dim, KD = n_kv * head_dim;
+  const size_t parts = n_seq * n_heads * (size_t)n_splits;
+  int8_t* dk = (int8_t*)up_bytes(t, k_bytes, cache);
+  int8_t* dv = (int8_t*)up_bytes(t, v_bytes, cache);
+  float* dks = i8 ? t.up(k_scale, rows) : nullptr;
+  float* dvs = i8 ? t.up(v_scale, rows) : nullptr;
+  const float* dq = t.up(q, n_seq * QD);
+  float* dkv = t.up(nullptr, n_seq * 2 * KD);   // [sequence][K row | V row], as the engine's staging vector
+  float* dout = t.up(nullptr, n_seq * QD);
+  float* part_ml = t.up(nullptr, parts * 2);
+  float* part_acc = t.up(nullptr, parts * head_dim);
+  int* dps = (int*)up_bytes(t, nullptr, 2 * n_seq * 4);
+  if (!dk || !dv || (i8 && (!dks || !dvs)) || !dq || !dkv || !dout || !part_ml || !part_acc || !dps) return LGH_ALLOCATION_FAILED;
+  for (size_t s = 0; s < n_seq; s++)
+    if (hipMemcpyAsync(dkv + s * 2 * KD, k_new + s * KD, KD * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+        hipMemcpyAsync(dkv + s * 2 * KD + KD, v_new + s * KD, KD * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
+      return LGH_OPERATION_FAILED;
+  if (hipMemcpyAsync(dps, pos, n_seq * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+      hipMemcpyAsync(dps + n_seq, slot, n_seq * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  if (attn_q8_multi_launch((int)kv_cache_type, dq, dk, dv, dks, dvs, dkv, dkv + KD, (uint32_t)(2 * KD), (uint32_t)n_heads, (uint32_t)n_kv,
+                           (uint32_t)head_dim, (uint32_t)max_seq, scale, dps, dps + n_seq, (uint32_t)n_seq, (uint32_t)n_splits, part_ml, part_acc,
+                           t.c->stream) != hipSuccess ||
+      attn_combine_multi_launch(part_ml, part_acc, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)n_splits, (uint32_t)n_seq, dout,
+                                nullptr, t.c->stream) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  int rc;
+  if ((rc = down_bytes(t, k_bytes, dk, cache)) || (rc = down_bytes(t, v_bytes, dv, cache))) return rc;
+  if (i8 && ((rc = t.down(k_scale, dks, rows)) || (rc = t.down(v_scale, dvs, rows)))) return rc;
+  return t.down(out, dout, n_seq * QD);
+}
+
 int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl, const float* k_new,
                         const float* v_new, const float* signs, const float* qjl_matrices, float* out, size_t n_heads, size_t n_kv, size_t head_dim,
                         size_t max_seq, float scale, size_t pos, int n_splits) {

@@ -42,7 +42,7 @@ ABI_SYMBOLS = (
     "lgh_op_attention_decode", "lgh_op_attention_decode_multi", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
     "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches",
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
-    "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq",
+    "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_attention_kv8_multi",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -230,6 +230,7 @@ def load_library() -> C.CDLL:
         "lgh_op_attention_decode": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_decode_multi": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, f32, C.c_int]),
         "lgh_op_attention_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
+        "lgh_op_attention_kv8_multi": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, f32, C.c_int]),
         "lgh_op_attention_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
         "lgh_op_attention_prefill": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
         "lgh_op_pf_tq_store": (C.c_int, [C.c_int, u32, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp]),
@@ -930,6 +931,28 @@ def op_attention_kv8(kv_cache_type: int, q, k_bytes, v_bytes, k_scale, v_scale, 
                                              ks.ctypes.data if i8 else None, vs.ctypes.data if i8 else None, kn.ctypes.data, vn.ctypes.data,
                                              out.ctypes.data, q.shape[0], kb.shape[0], q.shape[1], kb.shape[1], scale, pos, n_splits),
          "attention_kv8")
+    return out, kb, vb, ks, vs
+
+
+def op_attention_kv8_multi(kv_cache_type: int, q, k_bytes, v_bytes, k_scale, v_scale, k_new, v_new, scale: float, pos, slot, n_splits: int = 8,
+                           device: int = 0):
+    """The multi-sequence decode step's attention over int8 / FP8 cache slots: sequence s attends to rows 0..pos[s]-1 of slot slot[s]
+    and to its own k_new[s] / v_new[s], which the launch stores at row pos[s] of that slot.  q [n_seq, nh, d]; bytes
+    [n_slots, nkv, max_seq, d]; scales [n_slots, nkv, max_seq] (int8 only, else None); k_new / v_new [n_seq, nkv, d].
+    -> (out [n_seq, nh, d], k_bytes, v_bytes, k_scale, v_scale) after the call (copies; the inputs are untouched)."""
+    q, kn, vn = _f32(q), _f32(k_new), _f32(v_new)
+    kb, vb = np.array(k_bytes, dtype=np.uint8, copy=True), np.array(v_bytes, dtype=np.uint8, copy=True)
+    pos, slot = np.ascontiguousarray(pos, dtype=np.int32), np.ascontiguousarray(slot, dtype=np.int32)
+    if not (len(pos) == len(slot) == q.shape[0] == kn.shape[0] == vn.shape[0]):
+        raise ValueError("op_attention_kv8_multi: q, k_new, v_new, pos and slot must name the same number of sequences")
+    i8 = kv_cache_type == KV_INT8
+    ks = np.array(k_scale, dtype=np.float32, copy=True) if i8 else None
+    vs = np.array(v_scale, dtype=np.float32, copy=True) if i8 else None
+    out = np.empty_like(q)
+    _chk(load_library().lgh_op_attention_kv8_multi(device, kv_cache_type, q.ctypes.data, kb.ctypes.data, vb.ctypes.data, _ptr(ks), _ptr(vs),
+                                                   kn.ctypes.data, vn.ctypes.data, out.ctypes.data, q.shape[1], kb.shape[1], q.shape[2],
+                                                   kb.shape[2], kb.shape[0], len(pos), pos.ctypes.data, slot.ctypes.data, scale, n_splits),
+         "attention_kv8_multi")
     return out, kb, vb, ks, vs
 
 
