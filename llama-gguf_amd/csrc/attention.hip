@@ -19,7 +19,7 @@
 // kernel this one does not (each skipped term is < 1e-8 of the output scale).
 #include <cstdlib>
 
-#include "device_utils.h"
+#include "attn_split.h"
 #include "tq_fwht.h"
 #include "xq.h"
 #include "prefill.h"
@@ -28,8 +28,6 @@
 LGH_TL_DEFINE(attn)
 
 namespace lgh {
-
-constexpr float kNegBig = -1e30f;
 
 // NW waves per workgroup (positions are dealt round-robin over splits x waves): 4 is faster at short context (608 vs 600
 // tokens/s at kv 272), 8 at long (543 vs 524 at kv 4000); the launcher picks by the cache capacity.
@@ -50,8 +48,8 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_kernel(const float* __re
                                                            const int* __restrict__ slot = nullptr, uint64_t slot_stride = 0) {
   constexpr int LPR = D / 4;       // lanes per row
   constexpr int RPW = 64 / LPR;    // rows per wave-instruction
-  __shared__ float s_ml[NW][G][2];
-  __shared__ float s_acc[NW][G][D];
+  __shared__ float s_ml[NW * G * 2];
+  __shared__ __attribute__((aligned(16))) float s_acc[NW * G * D];
   LGH_TL_BEGIN(attn, lgh::TL_ATTN, n_splits);
 
   const uint32_t kvh = blockIdx.x / n_splits, sp = blockIdx.x % n_splits;
@@ -66,7 +64,7 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_kernel(const float* __re
   } else if (MULTI) {
     const uint32_t sq = blockIdx.y;
     uint32_t pw, sl;
-    asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(pw), "=&s"(sl) : "s"(pos_ptr + sq), "s"(slot + sq) : "memory");
+    sload_u32x2(pos_ptr + sq, slot + sq, pw, sl);
     kv_len = pw + 1;
     q += (size_t)sq * (gridDim.x / n_splits) * G * D;
     kc += (size_t)sl * slot_stride;
@@ -74,9 +72,7 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_kernel(const float* __re
     part_ml += (size_t)sq * gridDim.x * G * 2;
     part_acc += (size_t)sq * gridDim.x * G * D;
   } else if (pos_ptr) {
-    uint32_t pw;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pw) : "s"(pos_ptr) : "memory");
-    kv_len = pw + 1;
+    kv_len = sload_u32(pos_ptr) + 1;
   }
 
   f32x4 qv[G];
@@ -92,30 +88,8 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_kernel(const float* __re
   const float* vbase = vc + (size_t)kvh * max_seq * D + li * 4;
   const uint32_t stride = n_splits * NW * RPW;
   auto row_of = [&](uint32_t base) { const uint32_t p = base + sub; return p < kv_len ? p : kv_len - 1; };   // clamped: loads are unconditional
-  auto step = [&](uint32_t base, f32x4 k4, f32x4 v4) {
-    const bool valid = base + sub < kv_len;
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      float s = qv[g].x * k4.x;
-      s = __builtin_fmaf(qv[g].y, k4.y, s);
-      s = __builtin_fmaf(qv[g].z, k4.z, s);
-      s = __builtin_fmaf(qv[g].w, k4.w, s);
-      // sum over the LPR lanes of the row, in every lane: DPP inside a 16-lane row (no LDS crossbar), one cross-row
-      // exchange when a row spans 32 lanes
-      s += dpp_f<0xB1>(s);
-      s += dpp_f<0x4E>(s);
-      s += dpp_f<0x141>(s);
-      s += dpp_f<0x140>(s);
-      if (LPR == 32) s += __shfl_xor(s, 16, 64);
-      s *= scale;
-      const float mn = valid ? fmaxf(m[g], s) : m[g];
-      const float a = __expf(m[g] - mn);            // v_exp_f32: ~2 ulp, far inside the attention tolerance
-      const float pe = valid ? __expf(s - mn) : 0.0f;
-      l[g] = __builtin_fmaf(l[g], a, pe);
-      acc[g] = acc[g] * a + v4 * pe;
-      m[g] = mn;
-    }
-  };
+  // (through this lambda, not called in the loop directly: that cost the <128, 4, *> instantiations a wave of occupancy, 97-98 VGPRs for 94-96)
+  auto step = [&](uint32_t base, f32x4 k4, f32x4 v4) { attn_step4<G, LPR>(qv, k4, v4, scale, base + sub < kv_len, m, l, acc); };
   // Batches of kAhead iterations: all their K/V rows are requested before the first one is used (clamped when past the
   // end, so the loads are unconditional).  At decode lengths a workgroup has 1-3 iterations and everything is in flight
   // at once; at 4K context it has ~30, and with a single iteration ahead the kernel ran at 1 TB/s (latency-bound).
@@ -133,44 +107,15 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_kernel(const float* __re
       if (base + j * stride < kv_len) step(base + j * stride, kk[j], vv[j]);   // wave-uniform
   }
 
-  // merge the RPW row slots of the wave (lanes with equal li hold the same output dims)
-#pragma unroll
-  for (int off = LPR; off < 64; off <<= 1) {
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      const float om = __shfl_xor(m[g], off, 64), ol = __shfl_xor(l[g], off, 64);
-      f32x4 oa;
-      oa.x = __shfl_xor(acc[g].x, off, 64); oa.y = __shfl_xor(acc[g].y, off, 64);
-      oa.z = __shfl_xor(acc[g].z, off, 64); oa.w = __shfl_xor(acc[g].w, off, 64);
-      const float mn = fmaxf(m[g], om);
-      const float a = expf(m[g] - mn), b = expf(om - mn);
-      l[g] = l[g] * a + ol * b;
-      acc[g] = acc[g] * a + oa * b;
-      m[g] = mn;
-    }
-  }
-  if (sub == 0) {
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      if (li == 0) { s_ml[wave][g][0] = m[g]; s_ml[wave][g][1] = l[g]; }
-      *reinterpret_cast<f32x4*>(&s_acc[wave][g][li * 4]) = acc[g];
-    }
-  }
+  attn_merge_rows<G, LPR>(m, l, acc);
+  attn_stash<G, 4, LPR>(s_ml, s_acc, wave, sub, li, m, l, acc);
   __syncthreads();
   // merge the NW waves; thread t handles output elements t, t + 64 NW, ...
   const size_t pbase = ((size_t)kvh * n_splits + sp) * G;
   for (uint32_t e = threadIdx.x; e < (uint32_t)(G * D); e += NW * 64) {
     const uint32_t g = e / D, dim = e % D;
-    float mn = s_ml[0][g][0];
-#pragma unroll
-    for (int w = 1; w < NW; w++) mn = fmaxf(mn, s_ml[w][g][0]);
-    float lsum = 0.0f, a = 0.0f;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-      const float f = expf(s_ml[w][g][0] - mn);
-      lsum += s_ml[w][g][1] * f;
-      a += s_acc[w][g][dim] * f;
-    }
+    float mn, lsum, a;
+    attn_merge_waves<NW, G, D>(s_ml, s_acc, g, dim, mn, lsum, a);
     if (DIRECT) {
       const float o = a * (1.0f / lsum);   // simd.rs:718-720: multiply by 1/sum
       part_acc[(pbase + g) * D + dim] = o;
@@ -179,8 +124,7 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_kernel(const float* __re
       const _Float16 o = (_Float16)(a * (1.0f / lsum));   // simd.rs:718-720: multiply by 1/sum
       *reinterpret_cast<_Float16*>(reinterpret_cast<uint8_t*>(part_acc) + xh_offset(blockIdx.y, (uint32_t)(pbase + g) * D + dim)) = o;
     } else {
-      part_acc[(pbase + g) * D + dim] = a;
-      if (dim == 0) { part_ml[(pbase + g) * 2] = mn; part_ml[(pbase + g) * 2 + 1] = lsum; }
+      attn_store_partial<D>(part_ml, part_acc, pbase + g, dim, mn, lsum, a);
     }
   }
   LGH_TL_END();
@@ -193,7 +137,7 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_kernel(const float* __re
 // back scale * q.  The QKV launch leaves the current token's rows as f32 in a staging vector; every attention workgroup of
 // a kv head quantizes that row itself (D values, the same bits everywhere), split 0 also stores it into the cache, and the
 // row takes part in the softmax through its dequantized values — exactly what a later token will read.
-// Same split / online-softmax structure as attn_partial_kernel; a row is D bytes (one dword per lane).
+// The split / online-softmax structure is attn_partial_kernel's (attn_split.h); a row is D bytes (one dword per lane).
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ f32x4 unpack_i8x4(uint32_t w, float scale) {
   f32x4 r;
@@ -202,6 +146,14 @@ __device__ __forceinline__ f32x4 unpack_i8x4(uint32_t w, float scale) {
   r.z = (float)(int)(int8_t)((w >> 16) & 0xFFu) * scale;
   r.w = (float)(int)(int8_t)(w >> 24) * scale;
   return r;
+}
+
+// quantize_int8: the scale of a row whose largest magnitude is amax, and one value's byte
+__device__ __forceinline__ float i8_row_scale(float amax) { return amax > 1e-10f ? amax / 127.0f : 1.0f; }
+__device__ __forceinline__ uint32_t i8_quantize(float v, float scale) {
+  float r = roundf(v / scale);                           // f32::round: halves away from zero
+  r = r < -128.0f ? -128.0f : (r > 127.0f ? 127.0f : r);
+  return (uint32_t)(int)r & 0xFFu;
 }
 
 // quantizes the f32 row held 4 elements per lane by the LPR lanes of a row group; returns the packed int8 word and the scale
@@ -213,13 +165,8 @@ __device__ __forceinline__ uint32_t quantize_row_i8(f32x4 x, float& scale) {
   amax = fmaxf(amax, dpp_f<0x141>(amax));
   amax = fmaxf(amax, dpp_f<0x140>(amax));
   if (LPR == 32) amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-  scale = amax > 1e-10f ? amax / 127.0f : 1.0f;
-  auto qz = [&](float v) -> uint32_t {
-    float r = roundf(v / scale);                           // f32::round: halves away from zero
-    r = r < -128.0f ? -128.0f : (r > 127.0f ? 127.0f : r);
-    return (uint32_t)(int)r & 0xFFu;
-  };
-  return qz(x.x) | qz(x.y) << 8 | qz(x.z) << 16 | qz(x.w) << 24;
+  scale = i8_row_scale(amax);
+  return i8_quantize(x.x, scale) | i8_quantize(x.y, scale) << 8 | i8_quantize(x.z, scale) << 16 | i8_quantize(x.w, scale) << 24;
 }
 
 // ---- the reference's FP8 KV formats (kv_quantized.rs:413-565; FMT 2 = E4M3, 3 = E5M2): one byte per element, no scales ----
@@ -283,15 +230,15 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_q8_kernel(const float* _
                                                                   float* __restrict__ part_ml, float* __restrict__ part_acc,
                                                                   const int* __restrict__ slot = nullptr, uint32_t x_stride = 0) {
   constexpr int LPR = D / 4, RPW = 64 / LPR;
-  __shared__ float s_ml[NW][G][2];
-  __shared__ float s_acc[NW][G][D];
+  __shared__ float s_ml[NW * G * 2];
+  __shared__ __attribute__((aligned(16))) float s_acc[NW * G * D];
   const uint32_t kvh = blockIdx.x / n_splits, sp = blockIdx.x % n_splits;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t sub = lane / LPR, li = lane % LPR;
   uint32_t pw, sl = 0;
-  if (MULTI) {   // position and slot by scalar loads, as attn_partial_kernel<MULTI> reads them
+  if (MULTI) {
     const uint32_t sq = blockIdx.y, n_kv = gridDim.x / n_splits;
-    asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(pw), "=&s"(sl) : "s"(pos_ptr + sq), "s"(slot + sq) : "memory");
+    sload_u32x2(pos_ptr + sq, slot + sq, pw, sl);
     q += (size_t)sq * n_kv * G * D;
     k_new += (size_t)sq * x_stride;
     v_new += (size_t)sq * x_stride;
@@ -299,7 +246,7 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_q8_kernel(const float* _
     part_acc += (size_t)sq * gridDim.x * G * D;
     sl *= n_kv;   // the slot's first kv head, in heads
   } else {
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pw) : "s"(pos_ptr) : "memory");
+    pw = sload_u32(pos_ptr);
   }
   const uint32_t pos = pw;   // rows [0, pos) come from the cache, row `pos` from the staging vectors
   f32x4 qv[G];
@@ -309,27 +256,7 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_q8_kernel(const float* _
   f32x4 acc[G];
 #pragma unroll
   for (int g = 0; g < G; g++) { m[g] = kNegBig; l[g] = 0.0f; acc[g] = (f32x4)(0.0f); }
-  auto step = [&](bool valid, f32x4 k4, f32x4 v4) {
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      float s = qv[g].x * k4.x;
-      s = __builtin_fmaf(qv[g].y, k4.y, s);
-      s = __builtin_fmaf(qv[g].z, k4.z, s);
-      s = __builtin_fmaf(qv[g].w, k4.w, s);
-      s += dpp_f<0xB1>(s);
-      s += dpp_f<0x4E>(s);
-      s += dpp_f<0x141>(s);
-      s += dpp_f<0x140>(s);
-      if (LPR == 32) s += __shfl_xor(s, 16, 64);
-      s *= scale;
-      const float mn = valid ? fmaxf(m[g], s) : m[g];
-      const float a = __expf(m[g] - mn);
-      const float pe = valid ? __expf(s - mn) : 0.0f;
-      l[g] = __builtin_fmaf(l[g], a, pe);
-      acc[g] = acc[g] * a + v4 * pe;
-      m[g] = mn;
-    }
-  };
+  auto step = [&](bool valid, f32x4 k4, f32x4 v4) { attn_step4<G, LPR>(qv, k4, v4, scale, valid, m, l, acc); };
   const size_t hrow = MULTI ? ((size_t)sl + kvh) * max_seq : (size_t)kvh * max_seq;   // first row of this kv head (of this slot)
   const uint32_t stride = n_splits * NW * RPW;
   constexpr int kAhead = 4;
@@ -369,59 +296,48 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_q8_kernel(const float* _
       step(sub == 0, unpack_kv4<FMT>(kq, ksc), unpack_kv4<FMT>(vq, vsc));
     }
   }
-#pragma unroll
-  for (int off = LPR; off < 64; off <<= 1) {
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      const float om = __shfl_xor(m[g], off, 64), ol = __shfl_xor(l[g], off, 64);
-      f32x4 oa;
-      oa.x = __shfl_xor(acc[g].x, off, 64); oa.y = __shfl_xor(acc[g].y, off, 64);
-      oa.z = __shfl_xor(acc[g].z, off, 64); oa.w = __shfl_xor(acc[g].w, off, 64);
-      const float mn = fmaxf(m[g], om);
-      const float a = expf(m[g] - mn), b = expf(om - mn);
-      l[g] = l[g] * a + ol * b;
-      acc[g] = acc[g] * a + oa * b;
-      m[g] = mn;
-    }
-  }
+  attn_merge_rows<G, LPR>(m, l, acc);
+  // (attn_stash spelled out: through the shared function attn_partial_q8_kernel<64, 8, 4, 1, true> takes 130 VGPRs instead of 127 and
+  // loses a wave of occupancy, 4 -> 3)
   if (sub == 0) {
 #pragma unroll
     for (int g = 0; g < G; g++) {
-      if (li == 0) { s_ml[wave][g][0] = m[g]; s_ml[wave][g][1] = l[g]; }
-      *reinterpret_cast<f32x4*>(&s_acc[wave][g][li * 4]) = acc[g];
+      if (li == 0) { s_ml[(wave * G + g) * 2] = m[g]; s_ml[(wave * G + g) * 2 + 1] = l[g]; }
+      *reinterpret_cast<f32x4*>(&s_acc[((size_t)wave * G + g) * D + li * 4]) = acc[g];
     }
   }
   __syncthreads();
-  const size_t pbase = ((size_t)kvh * n_splits + sp) * G;
-  for (uint32_t e = threadIdx.x; e < (uint32_t)(G * D); e += NW * 64) {
-    const uint32_t g = e / D, dim = e % D;
-    float mn = s_ml[0][g][0];
-#pragma unroll
-    for (int w = 1; w < NW; w++) mn = fmaxf(mn, s_ml[w][g][0]);
-    float lsum = 0.0f, a = 0.0f;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-      const float f = expf(s_ml[w][g][0] - mn);
-      lsum += s_ml[w][g][1] * f;
-      a += s_acc[w][g][dim] * f;
-    }
-    part_acc[(pbase + g) * D + dim] = a;
-    if (dim == 0) { part_ml[(pbase + g) * 2] = mn; part_ml[(pbase + g) * 2 + 1] = lsum; }
-  }
+  attn_merge_store<NW, G, D>(s_ml, s_acc, part_ml, part_acc, ((size_t)kvh * n_splits + sp) * G);
 }
 
-template <int D, int G>
-static hipError_t attn_q8_go(int fmt, const float* q, int8_t* k8, int8_t* v8, float* ks, float* vs, const float* k_new, const float* v_new, uint32_t n_kv,
-                             uint32_t max_seq, float scale, const int* pos, uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
-#define LGH_Q8_GO(FMT)                                                                                                                          \
-  hipLaunchKernelGGL((attn_partial_q8_kernel<D, G, 4, FMT>), dim3(n_kv * n_splits), dim3(256), 0, st, q, k8, v8, ks, vs, k_new, v_new, max_seq, \
-                     scale, pos, n_splits, part_ml, part_acc)
-  if (fmt == 1) LGH_Q8_GO(1);
-  else if (fmt == 2) LGH_Q8_GO(2);
-  else if (fmt == 3) LGH_Q8_GO(3);
-  else return hipErrorInvalidValue;
-#undef LGH_Q8_GO
+// n_seq 0: the single-sequence launch; else grid y = the sequences of a step over cache slots (engine_batch.hip).  NW = 4 whatever
+// max_seq is, for both: with another wave count the rows would be dealt differently and the sums would differ in their last bits.
+struct Q8Args {
+  int fmt; const float* q; int8_t *k8, *v8; float *ks, *vs; const float *k_new, *v_new; uint32_t n_kv, max_seq; float scale; const int* pos;
+  uint32_t n_splits; float *part_ml, *part_acc; hipStream_t st;
+  uint32_t n_seq; const int* slot; uint32_t x_stride;
+};
+
+template <int D, int G, int FMT>
+static hipError_t attn_q8_go(const Q8Args& a) {
+  const dim3 grid(a.n_kv * a.n_splits, a.n_seq ? a.n_seq : 1);
+  if (a.n_seq)
+    hipLaunchKernelGGL((attn_partial_q8_kernel<D, G, 4, FMT, true>), grid, dim3(256), 0, a.st, a.q, a.k8, a.v8, a.ks, a.vs, a.k_new, a.v_new, a.max_seq,
+                       a.scale, a.pos, a.n_splits, a.part_ml, a.part_acc, a.slot, a.x_stride);
+  else
+    hipLaunchKernelGGL((attn_partial_q8_kernel<D, G, 4, FMT>), grid, dim3(256), 0, a.st, a.q, a.k8, a.v8, a.ks, a.vs, a.k_new, a.v_new, a.max_seq,
+                       a.scale, a.pos, a.n_splits, a.part_ml, a.part_acc);
   return hipGetLastError();
+}
+
+static hipError_t attn_q8_dispatch(uint32_t head_dim, uint32_t g, const Q8Args& a) {
+  return attn_dispatch(head_dim, g, [&](auto d, auto gg) {
+    constexpr int D = decltype(d)::value, G = decltype(gg)::value;
+    if (a.fmt == 1) return attn_q8_go<D, G, 1>(a);
+    if (a.fmt == 2) return attn_q8_go<D, G, 2>(a);
+    if (a.fmt == 3) return attn_q8_go<D, G, 3>(a);
+    return hipErrorInvalidValue;
+  });
 }
 
 // fmt: lgh_model_desc.kv_cache_type (1 = int8 + scales, 2 = FP8 E4M3, 3 = FP8 E5M2; the scale arrays are unused for 2 and 3)
@@ -429,31 +345,8 @@ hipError_t attn_q8_launch(int fmt, const float* q, int8_t* k8, int8_t* v8, float
                           uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, uint32_t n_splits,
                           float* part_ml, float* part_acc, hipStream_t st) {
   if (n_kv == 0 || n_heads % n_kv || !pos) return hipErrorInvalidValue;
-  const uint32_t g = n_heads / n_kv;
-#define LGH_ATTN_CASE(DD, GG) \
-  if (head_dim == DD && g == GG) return attn_q8_go<DD, GG>(fmt, q, k8, v8, kscale, vscale, k_new, v_new, n_kv, max_seq, scale, pos, n_splits, part_ml, part_acc, st);
-  LGH_ATTN_CASE(128, 1) LGH_ATTN_CASE(128, 2) LGH_ATTN_CASE(128, 4) LGH_ATTN_CASE(128, 8)
-  LGH_ATTN_CASE(64, 1) LGH_ATTN_CASE(64, 2) LGH_ATTN_CASE(64, 4) LGH_ATTN_CASE(64, 8)
-#undef LGH_ATTN_CASE
-  return hipErrorInvalidValue;
-}
-
-// ---- multi-sequence decode over byte-cache slots (engine_batch.hip): the n_seq sequences of a step in one launch.  NW = 4 whatever
-// max_seq is, as attn_q8_go launches the single sequence: with another wave count the rows would be dealt differently and the
-// sums would differ in their last bits.
-template <int D, int G>
-static hipError_t attn_q8_multi_go(int fmt, const float* q, int8_t* k8, int8_t* v8, float* ks, float* vs, const float* k_new, const float* v_new,
-                                   uint32_t x_stride, uint32_t n_kv, uint32_t max_seq, float scale, const int* pos, const int* slot, uint32_t n_seq,
-                                   uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
-#define LGH_Q8_GO(FMT)                                                                                                                        \
-  hipLaunchKernelGGL((attn_partial_q8_kernel<D, G, 4, FMT, true>), dim3(n_kv * n_splits, n_seq), dim3(256), 0, st, q, k8, v8, ks, vs, k_new, \
-                     v_new, max_seq, scale, pos, n_splits, part_ml, part_acc, slot, x_stride)
-  if (fmt == 1) LGH_Q8_GO(1);
-  else if (fmt == 2) LGH_Q8_GO(2);
-  else if (fmt == 3) LGH_Q8_GO(3);
-  else return hipErrorInvalidValue;
-#undef LGH_Q8_GO
-  return hipGetLastError();
+  return attn_q8_dispatch(head_dim, n_heads / n_kv,
+                          Q8Args{fmt, q, k8, v8, kscale, vscale, k_new, v_new, n_kv, max_seq, scale, pos, n_splits, part_ml, part_acc, st, 0, nullptr, 0});
 }
 
 // caches [slot][n_kv][max_seq][D] bytes, scales (int8) [slot][n_kv][max_seq]; k_new / v_new of sequence s at + s * x_stride floats;
@@ -463,14 +356,8 @@ hipError_t attn_q8_multi_launch(int fmt, const float* q, int8_t* k8, int8_t* v8,
                                 const int* slot, uint32_t n_seq, uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
   if (n_kv == 0 || n_heads % n_kv || !pos || !slot || n_seq == 0 || n_splits == 0 || n_splits > 32) return hipErrorInvalidValue;
   if (fmt == 1 && (!kscale || !vscale)) return hipErrorInvalidValue;
-  const uint32_t g = n_heads / n_kv;
-#define LGH_ATTN_CASE(DD, GG)    \
-  if (head_dim == DD && g == GG) \
-    return attn_q8_multi_go<DD, GG>(fmt, q, k8, v8, kscale, vscale, k_new, v_new, x_stride, n_kv, max_seq, scale, pos, slot, n_seq, n_splits, part_ml, part_acc, st);
-  LGH_ATTN_CASE(128, 1) LGH_ATTN_CASE(128, 2) LGH_ATTN_CASE(128, 4) LGH_ATTN_CASE(128, 8)
-  LGH_ATTN_CASE(64, 1) LGH_ATTN_CASE(64, 2) LGH_ATTN_CASE(64, 4) LGH_ATTN_CASE(64, 8)
-#undef LGH_ATTN_CASE
-  return hipErrorInvalidValue;
+  return attn_q8_dispatch(head_dim, n_heads / n_kv,
+                          Q8Args{fmt, q, k8, v8, kscale, vscale, k_new, v_new, n_kv, max_seq, scale, pos, n_splits, part_ml, part_acc, st, n_seq, slot, x_stride});
 }
 
 // one row of n values through a byte KV format and back (the quantizers of attn_partial_q8_kernel, stand-alone): bytes and,
@@ -484,15 +371,13 @@ __global__ void __launch_bounds__(64) kv_roundtrip_kernel(const float* __restric
     float amax = 0.0f;
     for (uint32_t i = lane; i < n; i += 64) amax = fmaxf(amax, fabsf(x[i]));
     amax = wave_max(amax);
-    scale = amax > 1e-10f ? amax / 127.0f : 1.0f;
+    scale = i8_row_scale(amax);
     if (lane == 0) *scale_out = scale;
   }
   for (uint32_t i = lane; i < n; i += 64) {
     uint32_t b;
     if (FMT == 1) {
-      float r = roundf(x[i] / scale);
-      r = r < -128.0f ? -128.0f : (r > 127.0f ? 127.0f : r);
-      b = (uint32_t)(int)r & 0xFFu;
+      b = i8_quantize(x[i], scale);
       back[i] = (float)(int)(int8_t)b * scale;
     } else {
       b = fp8_encode<FMT>(x[i]);
@@ -510,8 +395,7 @@ hipError_t kv_roundtrip_launch(int fmt, const float* x, uint32_t n, uint8_t* byt
   return hipGetLastError();
 }
 
-// out[h][dim] = sum_s acc_s * e^{m_s - m*} / sum_s l_s * e^{m_s - m*}.  Lane s of the first wave owns split s
-// (all loads of a phase are independent and in flight together: the kernel is two memory round trips long).
+// out[h][dim] = the merge of head h's splits (attn_split.h: attn_combine_splits), and wo's input as XQ records
 template <bool MULTI>
 __global__ void __launch_bounds__(128) attn_combine_kernel(const float* __restrict__ part_ml, const float* __restrict__ part_acc,
                                                            uint32_t g_per_kv, uint32_t head_dim, uint32_t n_splits,
@@ -528,83 +412,60 @@ __global__ void __launch_bounds__(128) attn_combine_kernel(const float* __restri
   }
   const uint32_t h = blockIdx.x, kvh = h / g_per_kv, g = h % g_per_kv;
   const size_t p0 = (size_t)kvh * n_splits * g_per_kv + g;   // split s lives at p0 + s * g_per_kv
-  // every partial this thread will need is requested up front (one dim per thread: blockDim == head_dim <= 128), so the
-  // kernel is ONE memory round trip long instead of two dependent ones (m/l first, accumulators after the barrier)
-  const uint32_t dim = threadIdx.x;
-  float pa[32];
-#pragma unroll
-  for (uint32_t sidx = 0; sidx < 32; sidx++)
-    pa[sidx] = (sidx < n_splits && dim < head_dim) ? part_acc[(p0 + (size_t)sidx * g_per_kv) * head_dim + dim] : 0.0f;
-  if (threadIdx.x < 64) {
-    const uint32_t sidx = threadIdx.x;
-    const bool ok = sidx < n_splits;
-    const float m = ok ? part_ml[(p0 + (size_t)sidx * g_per_kv) * 2] : kNegBig;
-    const float l = ok ? part_ml[(p0 + (size_t)sidx * g_per_kv) * 2 + 1] : 0.0f;
-    const float mn = wave_max(m);
-    const float f = expf(m - mn);
-    const float lsum = wave_sum(l * f);
-    s_f[sidx] = f;
-    if (sidx == 0) s_linv = 1.0f / lsum;  // simd.rs:718-720: multiply by 1/sum
-  }
-  __syncthreads();
+  const uint32_t dim = threadIdx.x;   // one dim per thread: blockDim >= head_dim
+  const float o = attn_combine_splits(part_ml, part_acc, p0, g_per_kv, head_dim, n_splits, dim, dim < head_dim, s_f, &s_linv);
   if (dim < head_dim) {
-    float a = 0.0f;
-#pragma unroll
-    for (uint32_t sidx = 0; sidx < 32; sidx++) a += pa[sidx] * s_f[sidx];   // s_f of absent splits is exp(-1e30 - m) = 0
-    const float o = a * s_linv;
     out[(size_t)h * head_dim + dim] = o;
     if (xq_out) xq_store_chunk(xq_out, (h * head_dim + dim) >> 4, o);   // wo's input as XQ records (head_dim % 16 == 0)
   }
   LGH_TL_END();
 }
 
-template <int D, int G>
-static hipError_t attn_go(const float* q, const float* kc, const float* vc, uint32_t n_kv, uint32_t max_seq, float scale,
-                          const int* pos, int kv_len_fixed, uint32_t n_splits, float* part_ml, float* part_acc,
-                          hipStream_t st) {
-  const bool long_ctx = (pos ? max_seq : (uint32_t)kv_len_fixed) >= 2048;
-  if (long_ctx)
-    hipLaunchKernelGGL((attn_partial_kernel<D, G, 8>), dim3(n_kv * n_splits), dim3(512), 0, st, q, kc, vc, max_seq, scale, pos,
-                       kv_len_fixed, n_splits, part_ml, part_acc);
+// n_seq 0: the single-sequence launch; else grid y = the sequences of a step over cache slots (engine_batch.hip).  The wave count
+// follows the cache capacity alone, so a sequence's rows are dealt the same way in both and its partials are the same bits.
+struct AttnArgs {
+  const float *q, *kc, *vc; uint32_t n_kv, max_seq; float scale; const int* pos; int kv_len_fixed; uint32_t n_splits; float *part_ml, *part_acc;
+  hipStream_t st;
+  uint32_t n_seq; const int* slot; uint64_t slot_stride;
+};
+
+template <int D, int G, int NW>
+static hipError_t attn_go(const AttnArgs& a) {
+  const dim3 grid(a.n_kv * a.n_splits, a.n_seq ? a.n_seq : 1);
+  if (a.n_seq)
+    hipLaunchKernelGGL((attn_partial_kernel<D, G, NW, false, false, true>), grid, dim3(NW * 64), 0, a.st, a.q, a.kc, a.vc, a.max_seq, a.scale, a.pos, 0,
+                       a.n_splits, a.part_ml, a.part_acc, a.slot, a.slot_stride);
   else
-    hipLaunchKernelGGL((attn_partial_kernel<D, G, 4>), dim3(n_kv * n_splits), dim3(256), 0, st, q, kc, vc, max_seq, scale, pos,
-                       kv_len_fixed, n_splits, part_ml, part_acc);
+    hipLaunchKernelGGL((attn_partial_kernel<D, G, NW>), grid, dim3(NW * 64), 0, a.st, a.q, a.kc, a.vc, a.max_seq, a.scale, a.pos, a.kv_len_fixed,
+                       a.n_splits, a.part_ml, a.part_acc);
   return hipGetLastError();
+}
+
+static hipError_t attn_split_dispatch(uint32_t head_dim, uint32_t g, const AttnArgs& a) {
+  const bool long_ctx = (a.pos ? a.max_seq : (uint32_t)a.kv_len_fixed) >= 2048;
+  return attn_dispatch(head_dim, g, [&](auto d, auto gg) {
+    constexpr int D = decltype(d)::value, G = decltype(gg)::value;
+    return long_ctx ? attn_go<D, G, 8>(a) : attn_go<D, G, 4>(a);
+  });
 }
 
 hipError_t attn_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv,
                        uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, int kv_len_fixed,
                        uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
   if (n_kv == 0 || n_heads % n_kv) return hipErrorInvalidValue;
-  const uint32_t g = n_heads / n_kv;
-#define LGH_ATTN_CASE(DD, GG) \
-  if (head_dim == DD && g == GG)  \
-    return attn_go<DD, GG>(q, kcache, vcache, n_kv, max_seq, scale, pos, kv_len_fixed, n_splits, part_ml, part_acc, st);
-  LGH_ATTN_CASE(128, 1) LGH_ATTN_CASE(128, 2) LGH_ATTN_CASE(128, 4) LGH_ATTN_CASE(128, 8)
-  LGH_ATTN_CASE(64, 1) LGH_ATTN_CASE(64, 2) LGH_ATTN_CASE(64, 4) LGH_ATTN_CASE(64, 8)
-#undef LGH_ATTN_CASE
-  return hipErrorInvalidValue;
-}
-
-template <int D, int G>
-static hipError_t attn_direct_go(const float* q, const float* kc, const float* vc, uint32_t n_kv, uint32_t max_seq, float scale, const int* pos,
-                                 float* out, uint8_t* xq_out, hipStream_t st) {
-  hipLaunchKernelGGL((attn_partial_kernel<D, G, 16, false, true>), dim3(n_kv), dim3(1024), 0, st, q, kc, vc, max_seq, scale, pos, 0, 1u,
-                     reinterpret_cast<float*>(xq_out), out);
-  return hipGetLastError();
+  return attn_split_dispatch(head_dim, n_heads / n_kv,
+                             AttnArgs{q, kcache, vcache, n_kv, max_seq, scale, pos, kv_len_fixed, n_splits, part_ml, part_acc, st, 0, nullptr, 0});
 }
 
 // single-launch decode attention for short contexts (engine.hip picks it by the host-side position)
 hipError_t attn_direct_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
                               uint32_t max_seq, float scale, const int* pos, float* out, uint8_t* xq_out, hipStream_t st) {
   if (n_kv == 0 || n_heads % n_kv || !pos) return hipErrorInvalidValue;
-  const uint32_t g = n_heads / n_kv;
-#define LGH_ATTN_CASE(DD, GG) \
-  if (head_dim == DD && g == GG) return attn_direct_go<DD, GG>(q, kcache, vcache, n_kv, max_seq, scale, pos, out, xq_out, st);
-  LGH_ATTN_CASE(128, 1) LGH_ATTN_CASE(128, 2) LGH_ATTN_CASE(128, 4) LGH_ATTN_CASE(128, 8)
-  LGH_ATTN_CASE(64, 1) LGH_ATTN_CASE(64, 2) LGH_ATTN_CASE(64, 4) LGH_ATTN_CASE(64, 8)
-#undef LGH_ATTN_CASE
-  return hipErrorInvalidValue;
+  return attn_dispatch(head_dim, n_heads / n_kv, [&](auto d, auto gg) {
+    hipLaunchKernelGGL((attn_partial_kernel<decltype(d)::value, decltype(gg)::value, 16, false, true>), dim3(n_kv), dim3(1024), 0, st, q, kcache, vcache,
+                       max_seq, scale, pos, 0, 1u, reinterpret_cast<float*>(xq_out), out);
+    return hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -773,16 +634,6 @@ static hipError_t attn_pf_mfma_go(const float* q, const float* kc, const float* 
   return hipGetLastError();
 }
 
-// 4 waves per (kv head, token) workgroup: 8 and 16 waves measured slower on the 128-token Llama-3-8B prompt (4.79 / 5.07 vs
-// 4.74 ms per prompt pass) — the grid is already 1024 workgroups wide.
-template <int D, int G>
-static hipError_t attn_pf_go(const float* q, const float* kc, const float* vc, uint32_t n_kv, uint32_t max_seq, float scale, uint32_t pos0,
-                             uint32_t m_tokens, uint8_t* xh_out, hipStream_t st) {
-  hipLaunchKernelGGL((attn_partial_kernel<D, G, 4, true>), dim3(n_kv, m_tokens), dim3(256), 0, st, q, kc, vc, max_seq, scale,
-                     (const int*)nullptr, (int)(pos0 + 1), 1u, (float*)nullptr, reinterpret_cast<float*>(xh_out));
-  return hipGetLastError();
-}
-
 hipError_t attn_prefill_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv,
                                uint32_t head_dim, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out,
                                hipStream_t st) {
@@ -793,12 +644,13 @@ hipError_t attn_prefill_launch(const float* q, const float* kcache, const float*
     return head_dim == 128 ? attn_pf_mfma_go<128, false>(q, kcache, vcache, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, PfTqEpi{})
                            : attn_pf_mfma_go<64, false>(q, kcache, vcache, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, PfTqEpi{});
   }
-#define LGH_ATTN_CASE(DD, GG) \
-  if (head_dim == DD && g == GG) return attn_pf_go<DD, GG>(q, kcache, vcache, n_kv, max_seq, scale, pos0, m_tokens, xh_out, st);
-  LGH_ATTN_CASE(128, 1) LGH_ATTN_CASE(128, 2) LGH_ATTN_CASE(128, 4) LGH_ATTN_CASE(128, 8)
-  LGH_ATTN_CASE(64, 1) LGH_ATTN_CASE(64, 2) LGH_ATTN_CASE(64, 4) LGH_ATTN_CASE(64, 8)
-#undef LGH_ATTN_CASE
-  return hipErrorInvalidValue;
+  // 4 waves per (kv head, token) workgroup: 8 and 16 waves measured slower on the 128-token Llama-3-8B prompt (4.79 / 5.07 vs
+  // 4.74 ms per prompt pass) — the grid is already 1024 workgroups wide.
+  return attn_dispatch(head_dim, g, [&](auto d, auto gg) {
+    hipLaunchKernelGGL((attn_partial_kernel<decltype(d)::value, decltype(gg)::value, 4, true>), dim3(n_kv, m_tokens), dim3(256), 0, st, q, kcache, vcache,
+                       max_seq, scale, (const int*)nullptr, (int)(pos0 + 1), 1u, (float*)nullptr, reinterpret_cast<float*>(xh_out));
+    return hipGetLastError();
+  });
 }
 
 // the block attention over the TurboQuantMSE prompt pass's scratch (tq_pf_rows_launch filled it and rotated q): head_dim 64 / 128 only,
@@ -814,20 +666,10 @@ hipError_t attn_prefill_tq_launch(const float* q, const float* kscr, const float
                          : attn_pf_mfma_go<64, true>(q, kscr, vscr, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, tq);
 }
 
-// Backend::attention for any head_dim / group size (per-op surface only; the engine's shapes take the kernels above):
-// one workgroup per (head, query position), scores in LDS, the arithmetic of ops.rs:1353-1472 — sequential dot per score,
-// max, exp, sum, weights times 1/sum, then V accumulated in position order.
-__global__ void __launch_bounds__(256) attn_generic_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                           float* __restrict__ out, uint32_t per_kv, uint32_t seq_len, uint32_t kv_len,
-                                                           uint32_t kv_rows, uint32_t d, float scale) {
-  extern __shared__ float sc[];
-  __shared__ float s_red[4];
-  const uint32_t head = blockIdx.x, s = blockIdx.y, kvh = head / per_kv;
-  const uint32_t q_abs = (kv_len >= seq_len ? kv_len - seq_len : 0) + s;
-  const uint32_t visible = q_abs + 1 < kv_len ? q_abs + 1 : kv_len;
-  const float* qv = q + ((size_t)head * seq_len + s) * d;
-  const float* kb = k + (size_t)kvh * kv_rows * d;   // kv_rows: rows per kv head in memory (a cache: max_seq_len)
-  const float* vb = v + (size_t)kvh * kv_rows * d;
+// Attention of one query row for any head_dim (256 threads): scores of the `visible` rows in LDS (sc), the arithmetic of
+// ops.rs:1353-1472 / 1479-1537 — sequential dot per score, max, exp, sum, weights times 1/sum, then V accumulated in position order.
+__device__ __forceinline__ void attn_naive_row(const float* __restrict__ qv, const float* __restrict__ kb, const float* __restrict__ vb,
+                                               float* __restrict__ out, uint32_t visible, uint32_t d, float scale, float* sc, float* s_red) {
   float m = -INFINITY;
   for (uint32_t p = threadIdx.x; p < visible; p += 256) {
     float dot = 0.0f;
@@ -853,8 +695,23 @@ __global__ void __launch_bounds__(256) attn_generic_kernel(const float* __restri
   for (uint32_t i = threadIdx.x; i < d; i += 256) {
     float o = 0.0f;
     for (uint32_t p = 0; p < visible; p++) o += (sc[p] * inv) * vb[(size_t)p * d + i];
-    out[((size_t)head * seq_len + s) * d + i] = o;
+    out[i] = o;
   }
+}
+
+// Backend::attention for any head_dim / group size (per-op surface only; the engine's shapes take the kernels above):
+// one workgroup per (head, query position), causal
+__global__ void __launch_bounds__(256) attn_generic_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                           float* __restrict__ out, uint32_t per_kv, uint32_t seq_len, uint32_t kv_len,
+                                                           uint32_t kv_rows, uint32_t d, float scale) {
+  extern __shared__ float sc[];
+  __shared__ float s_red[4];
+  const uint32_t head = blockIdx.x, s = blockIdx.y, kvh = head / per_kv;
+  const uint32_t q_abs = (kv_len >= seq_len ? kv_len - seq_len : 0) + s;
+  const uint32_t visible = q_abs + 1 < kv_len ? q_abs + 1 : kv_len;
+  const size_t qrow = ((size_t)head * seq_len + s) * d;
+  // kv_rows: rows per kv head in memory (a cache: max_seq_len)
+  attn_naive_row(q + qrow, k + (size_t)kvh * kv_rows * d, v + (size_t)kvh * kv_rows * d, out + qrow, visible, d, scale, sc, s_red);
 }
 
 hipError_t attn_generic_launch(const float* q, const float* k, const float* v, float* out, uint32_t n_heads, uint32_t n_kv, uint32_t seq_len,
@@ -867,8 +724,7 @@ hipError_t attn_generic_launch(const float* q, const float* k, const float* v, f
 
 // Decode attention for ANY head_dim / query-heads-per-kv-head inside the engine (the templated kernels above cover
 // head_dim 64 / 128 with 1, 2, 4, 8 heads per kv head): one workgroup per query head, kv_len = *pos + 1 from the device,
-// scores in LDS (max_seq floats), the arithmetic of ops.rs:1479-1537 (dot per score, max, exp, sum, weights x 1/sum, V
-// accumulated in position order).  Slower than the split kernels, correct for every shape the reference's kernel takes
+// scores in LDS (max_seq floats).  Slower than the split kernels, correct for every shape the reference's kernel takes
 // (kernels.rs:1395-1458).
 __global__ void __launch_bounds__(256) attn_decode_any_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc,
                                                               float* __restrict__ out, uint32_t per_kv, uint32_t max_seq, uint32_t d, float scale,
@@ -876,40 +732,12 @@ __global__ void __launch_bounds__(256) attn_decode_any_kernel(const float* __res
   extern __shared__ float sc[];
   __shared__ float s_red[4];
   const uint32_t head = blockIdx.x, kvh = head / per_kv, kv_len = (uint32_t)*pos_ptr + 1;
-  const float* qv = q + (size_t)head * d;
-  const float* kb = kc + (size_t)kvh * max_seq * d;
-  const float* vb = vc + (size_t)kvh * max_seq * d;
-  float m = -INFINITY;
-  for (uint32_t p = threadIdx.x; p < kv_len; p += 256) {
-    float dot = 0.0f;
-    for (uint32_t i = 0; i < d; i++) dot += qv[i] * kb[(size_t)p * d + i];
-    sc[p] = dot * scale;
-    m = fmaxf(m, sc[p]);
-  }
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-  __syncthreads();
-  float sum = 0.0f;
-  for (uint32_t p = threadIdx.x; p < kv_len; p += 256) {
-    const float e = expf(sc[p] - m);
-    sc[p] = e;
-    sum += e;
-  }
-  sum = wave_sum(sum);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  const float inv = 1.0f / ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
-  for (uint32_t i = threadIdx.x; i < d; i += 256) {
-    float o = 0.0f;
-    for (uint32_t p = 0; p < kv_len; p++) o += (sc[p] * inv) * vb[(size_t)p * d + i];
-    out[(size_t)head * d + i] = o;
-  }
+  attn_naive_row(q + (size_t)head * d, kc + (size_t)kvh * max_seq * d, vc + (size_t)kvh * max_seq * d, out + (size_t)head * d, kv_len, d, scale, sc,
+                 s_red);
 }
 
 bool attn_shape_has_fast_kernel(uint32_t head_dim, uint32_t group) {
-  return (head_dim == 64 || head_dim == 128) && (group == 1 || group == 2 || group == 4 || group == 8);
+  return attn_dispatch(head_dim, group, [](auto, auto) { return hipSuccess; }) == hipSuccess;
 }
 
 hipError_t attn_decode_any_launch(const float* q, const float* kcache, const float* vcache, float* out, uint32_t n_heads, uint32_t n_kv,
@@ -931,31 +759,12 @@ hipError_t attn_combine_launch(const float* part_ml, const float* part_acc, uint
 }
 
 // ---- multi-sequence decode (engine_batch.hip): the split attention and its merge for n_seq sequences in one launch each
-template <int D, int G>
-static hipError_t attn_multi_go(const float* q, const float* kc, const float* vc, uint32_t n_kv, uint32_t max_seq, float scale, const int* pos,
-                                const int* slot, uint64_t slot_stride, uint32_t n_seq, uint32_t n_splits, float* part_ml, float* part_acc,
-                                hipStream_t st) {
-  if (max_seq >= 2048)
-    hipLaunchKernelGGL((attn_partial_kernel<D, G, 8, false, false, true>), dim3(n_kv * n_splits, n_seq), dim3(512), 0, st, q, kc, vc, max_seq, scale,
-                       pos, 0, n_splits, part_ml, part_acc, slot, slot_stride);
-  else
-    hipLaunchKernelGGL((attn_partial_kernel<D, G, 4, false, false, true>), dim3(n_kv * n_splits, n_seq), dim3(256), 0, st, q, kc, vc, max_seq, scale,
-                       pos, 0, n_splits, part_ml, part_acc, slot, slot_stride);
-  return hipGetLastError();
-}
-
 hipError_t attn_multi_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
                              uint32_t max_seq, float scale, const int* pos, const int* slot, uint64_t slot_stride, uint32_t n_seq,
                              uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
   if (n_kv == 0 || n_heads % n_kv || !pos || !slot || n_seq == 0 || n_splits == 0 || n_splits > 32) return hipErrorInvalidValue;
-  const uint32_t g = n_heads / n_kv;
-#define LGH_ATTN_CASE(DD, GG) \
-  if (head_dim == DD && g == GG)  \
-    return attn_multi_go<DD, GG>(q, kcache, vcache, n_kv, max_seq, scale, pos, slot, slot_stride, n_seq, n_splits, part_ml, part_acc, st);
-  LGH_ATTN_CASE(128, 1) LGH_ATTN_CASE(128, 2) LGH_ATTN_CASE(128, 4) LGH_ATTN_CASE(128, 8)
-  LGH_ATTN_CASE(64, 1) LGH_ATTN_CASE(64, 2) LGH_ATTN_CASE(64, 4) LGH_ATTN_CASE(64, 8)
-#undef LGH_ATTN_CASE
-  return hipErrorInvalidValue;
+  return attn_split_dispatch(head_dim, n_heads / n_kv,
+                             AttnArgs{q, kcache, vcache, n_kv, max_seq, scale, pos, 0, n_splits, part_ml, part_acc, st, n_seq, slot, slot_stride});
 }
 
 hipError_t attn_combine_multi_launch(const float* part_ml, const float* part_acc, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,

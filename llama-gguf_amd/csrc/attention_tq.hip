@@ -28,7 +28,7 @@
 // itself (identical bits everywhere), split 0 stores the codes at row `pos`, and the row takes part through its codes.
 #include <cmath>
 
-#include "device_utils.h"
+#include "attn_split.h"
 #include "tq_fwht.h"
 #include "xq.h"
 
@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(256) attn_tq_partial_kernel(const float* __res
   if (MULTI) {
     const uint32_t sq = blockIdx.y;
     uint32_t sl;
-    asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(pw), "=&s"(sl) : "s"(pos_ptr + sq), "s"(ms.slot + sq) : "memory");
+    sload_u32x2(pos_ptr + sq, ms.slot + sq, pw, sl);
     q += (size_t)sq * (gridDim.x / n_splits) * G * D;
     k_new += (size_t)sq * ms.kv_stride;
     v_new += (size_t)sq * ms.kv_stride;
@@ -198,7 +198,7 @@ __global__ void __launch_bounds__(256) attn_tq_partial_kernel(const float* __res
     part_ml += (size_t)sq * gridDim.x * G * 2;
     part_acc += (size_t)sq * gridDim.x * G * D;
   } else {
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pw) : "s"(pos_ptr) : "memory");
+    pw = sload_u32(pos_ptr);
   }
   const uint32_t pos = pw, kv_len = pw + 1;
   const float* sk = signs + (size_t)(kvh * 2) * D;
@@ -262,14 +262,14 @@ __global__ void __launch_bounds__(256) attn_tq_partial_kernel(const float* __res
     tq_qjl_rows<D, BITS>(T, qjl_s + (size_t)kvh * D * D, G, rot, rot + G * D, newk, res, pq, newx);
     if (sp == 0 && tid < XW) xrow0[(size_t)pos * XW + tid] = newx[tid];
   }
-  // ---- one pass over this split's positions, online softmax (the structure of the f32 cache's attn_partial_kernel): LPR lanes share
+  // ---- one pass over this split's positions, online softmax (attn_split.h, as over the f32 cache): LPR lanes share
   // a cached row, 16 coordinates each — their codes are 4 bytes (2 bits) or 6 bytes (3 bits) of the row, decoded to centroids in
   // registers; a lane's partial dot products are summed over the row's lanes by DPP.  (The reference sums a row's 128 products one
   // after the other, codebook.rs:228-248; this sum is the same products in another order.)  V: sum_p w_p c[V_p] in the rotated space.
   float m[G], l[G], acc[G][16];
 #pragma unroll
   for (int g = 0; g < G; g++) {
-    m[g] = -1e30f; l[g] = 0.0f;
+    m[g] = kNegBig; l[g] = 0.0f;
 #pragma unroll
     for (int c = 0; c < 16; c++) acc[g][c] = 0.0f;
   }
@@ -304,13 +304,7 @@ __global__ void __launch_bounds__(256) attn_tq_partial_kernel(const float* __res
       sg += dpp_f<0x4E>(sg);
       if (LPR >= 8) sg += dpp_f<0x141>(sg);
       sg *= scale;
-      const float mn = valid ? fmaxf(m[g], sg) : m[g];
-      const float a = __expf(m[g] - mn);
-      const float pe = valid ? __expf(sg - mn) : 0.0f;
-      l[g] = __builtin_fmaf(l[g], a, pe);
-      m[g] = mn;
-      s[g] = pe;
-      tq_[g] = a;
+      tq_[g] = osm_update(m[g], l[g], sg, valid, s[g]);   // s: the row's weight, tq_: the factor for what is accumulated
     }
 #pragma unroll
     for (int c = 0; c < 16; c++) {
@@ -341,30 +335,11 @@ __global__ void __launch_bounds__(256) attn_tq_partial_kernel(const float* __res
     for (int j = 0; j < kAhead; j++)
       if (base + j * stride < kv_len) step(base + j * stride, kk[j], vv[j], sg[j], rn[j]);   // wave-uniform
   }
-  // merge the RPW row slots of the wave (lanes with equal li hold the same coordinates)
-#pragma unroll
-  for (int off = LPR; off < 64; off <<= 1) {
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      const float om = __shfl_xor(m[g], off, 64), ol = __shfl_xor(l[g], off, 64);
-      const float mn = fmaxf(m[g], om);
-      const float a = expf(m[g] - mn), b = expf(om - mn);
-      l[g] = l[g] * a + ol * b;
-#pragma unroll
-      for (int c = 0; c < 16; c++) acc[g][c] = acc[g][c] * a + __shfl_xor(acc[g][c], off, 64) * b;
-      m[g] = mn;
-    }
-  }
-  if (sub == 0) {
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      if (li == 0) { s_ml[(wave * G + g) * 2] = m[g]; s_ml[(wave * G + g) * 2 + 1] = l[g]; }
-#pragma unroll
-      for (int c = 0; c < 16; c++) s_acc[((size_t)wave * G + g) * D + li * 16 + c] = acc[g][c];
-    }
-  }
+  attn_merge_rows<G, LPR>(m, l, acc);
+  attn_stash<G, 16, LPR>(s_ml, s_acc, wave, sub, li, m, l, acc);
   __syncthreads();
-  // merge the waves; thread t handles output elements t, t + 256, ...
+  // merge the waves; thread t handles output elements t, t + 256, ...  This is attn_merge_store (attn_split.h) spelled out: through
+  // the shared function attn_tq_partial_kernel<64, 2, 2, false, *> takes 132 VGPRs instead of 127 and loses a wave of occupancy (4 -> 3).
   const size_t pbase = ((size_t)kvh * n_splits + sp) * G;
   for (uint32_t e = tid; e < (uint32_t)(G * D); e += 256) {
     const uint32_t g = e / D, dim = e % D;
@@ -383,7 +358,7 @@ __global__ void __launch_bounds__(256) attn_tq_partial_kernel(const float* __res
   }
 }
 
-// merge of the splits (as attn_combine_kernel) + the inverse rotation (rotation.rs:80-96): out = signs * (1 / d) * H (sqrt(d) * o)
+// merge of the splits (attn_split.h: attn_combine_splits) + the inverse rotation (rotation.rs:80-96): out = signs * (1 / d) * H (sqrt(d) * o)
 // MULTI: blockIdx.y = the sequence (partials of gridDim.x heads per sequence; outputs n_heads * D floats / xq_stride bytes apart)
 template <int D, bool MULTI>
 __global__ void __launch_bounds__(D) attn_tq_combine_kernel(const float* __restrict__ part_ml, const float* __restrict__ part_acc,
@@ -403,25 +378,7 @@ __global__ void __launch_bounds__(D) attn_tq_combine_kernel(const float* __restr
   const uint32_t h = blockIdx.x, kvh = h / g_per_kv, g = h % g_per_kv;
   const size_t p0 = (size_t)kvh * n_splits * g_per_kv + g;
   const uint32_t dim = threadIdx.x;
-  float pa[32];
-#pragma unroll
-  for (uint32_t s = 0; s < 32; s++) pa[s] = s < n_splits ? part_acc[(p0 + (size_t)s * g_per_kv) * D + dim] : 0.0f;
-  if (threadIdx.x < 64) {
-    const uint32_t s = threadIdx.x;
-    const bool ok = s < n_splits;
-    const float m = ok ? part_ml[(p0 + (size_t)s * g_per_kv) * 2] : -1e30f;
-    const float l = ok ? part_ml[(p0 + (size_t)s * g_per_kv) * 2 + 1] : 0.0f;
-    const float mn = wave_max(m);
-    const float f = expf(m - mn);
-    const float lsum = wave_sum(l * f);
-    s_f[s] = f;
-    if (s == 0) s_linv = 1.0f / lsum;
-  }
-  __syncthreads();
-  float a = 0.0f;
-#pragma unroll
-  for (uint32_t s = 0; s < 32; s++) a += pa[s] * s_f[s];
-  buf[dim] = (a * s_linv) * T.inv_scale;                              // x * sqrt(d)
+  buf[dim] = attn_combine_splits(part_ml, part_acc, p0, g_per_kv, D, n_splits, dim, true, s_f, &s_linv) * T.inv_scale;   // x * sqrt(d)
   tq_fwht_rows<D>(buf, 1);
   const float o = buf[dim] * T.inv_d * signs[(size_t)(kvh * 2 + 1) * D + dim];
   out[(size_t)h * D + dim] = o;
@@ -564,15 +521,11 @@ static hipError_t attn_tq_go(const TqArgs& a) {
 }
 
 static hipError_t attn_tq_dispatch(int bits, uint32_t head_dim, uint32_t g, const TqArgs& a) {
-#define LGH_TQ_CASE(DD, GG)                                                                              \
-  if (head_dim == DD && g == GG) {                                                                       \
-    if (a.qjl_s) return bits == 2 ? attn_tq_go<DD, GG, 2, true>(a) : attn_tq_go<DD, GG, 3, true>(a);     \
-    return bits == 2 ? attn_tq_go<DD, GG, 2, false>(a) : attn_tq_go<DD, GG, 3, false>(a);                \
-  }
-  LGH_TQ_CASE(128, 1) LGH_TQ_CASE(128, 2) LGH_TQ_CASE(128, 4) LGH_TQ_CASE(128, 8)
-  LGH_TQ_CASE(64, 1) LGH_TQ_CASE(64, 2) LGH_TQ_CASE(64, 4) LGH_TQ_CASE(64, 8)
-#undef LGH_TQ_CASE
-  return hipErrorInvalidValue;
+  return attn_dispatch(head_dim, g, [&](auto d, auto gg) {
+    constexpr int D = decltype(d)::value, G = decltype(gg)::value;
+    if (a.qjl_s) return bits == 2 ? attn_tq_go<D, G, 2, true>(a) : attn_tq_go<D, G, 3, true>(a);
+    return bits == 2 ? attn_tq_go<D, G, 2, false>(a) : attn_tq_go<D, G, 3, false>(a);
+  });
 }
 
 // bits 2 / 3; signs: this layer's [n_kv][2][head_dim]; qjl_s (TurboQuantProd; NULL = TurboQuantMSE): this layer's [n_kv][head_dim][head_dim],

@@ -56,6 +56,17 @@ __device__ __forceinline__ float fma4z(uint32_t v, const float* x) {
   return acc;
 }
 
+// A wave-uniform word (a position, a slot, a count) by SCALAR load, waited for: what follows (loop bounds, base addresses) depends on
+// it, and a vector load would be a full memory round trip into VGPRs first.  The second form requests two words and waits once.
+__device__ __forceinline__ uint32_t sload_u32(const void* p) {
+  uint32_t w;
+  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(p) : "memory");
+  return w;
+}
+__device__ __forceinline__ void sload_u32x2(const void* pa, const void* pb, uint32_t& a, uint32_t& b) {
+  asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a), "=&s"(b) : "s"(pa), "s"(pb) : "memory");
+}
+
 // full-wave (64 lanes) sum; every lane gets the result; fixed order -> deterministic
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -253,8 +253,7 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb2_kernel(const Mvqb2Geom Gm,
   const uint32_t ez = blockIdx.z;                                 // expert (indirect launches over a layer's experts; else 0)
   const int* ind_idx = nullptr;
   if (B.ind_cnt) {   // indirect entries (MoE expert launch): how many (sequence, slot) pairs chose this expert — possibly none
-    uint32_t cw;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(cw) : "s"(B.ind_cnt + ez) : "memory");
+    const uint32_t cw = sload_u32(B.ind_cnt + ez);
     n_seq = min(cw, n_seq);
     if (n_seq == 0) return;
     ind_idx = B.ind_idx + (size_t)ez * B.ind_stride;
@@ -439,8 +438,7 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb2_epilogue_kernel(uint32_t w
   uint32_t n_seq = B.n_seq;
   const int* ind_idx = nullptr;
   if (B.ind_cnt) {
-    uint32_t cw;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(cw) : "s"(B.ind_cnt + blockIdx.z) : "memory");
+    const uint32_t cw = sload_u32(B.ind_cnt + blockIdx.z);
     n_seq = min(cw, n_seq);
     if (n_seq == 0) return;
     ind_idx = B.ind_idx + (size_t)blockIdx.z * B.ind_stride;

@@ -325,7 +325,7 @@ __device__ __forceinline__ void pf_body(const PfGemm& G, const PfSeg& sg, uint32
   }
   // partial sums: lane holds, per (row tile, token tile), rows 4c .. 4c+3 of token n
   uint32_t row0 = 0;
-  if (G.row_base) asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(row0) : "s"(G.row_base) : "memory");
+  if (G.row_base) row0 = sload_u32(G.row_base);
   float* part = G.part + ((size_t)ks * G.part_rows + row0) * G.ncols;
 #pragma unroll
   for (int r = 0; r < kPfRT; r++) {
@@ -453,7 +453,7 @@ __device__ __forceinline__ void pf_body32(const PfGemm& G, const PfSeg& sg, uint
   }
   // partial sums: lane holds, per (32-row tile, 32-token tile), rows 8i + 4g .. + 3 (i = 0..3) of token l & 31
   uint32_t row0 = 0;
-  if (G.row_base) asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(row0) : "s"(G.row_base) : "memory");
+  if (G.row_base) row0 = sload_u32(G.row_base);
   float* part = G.part + ((size_t)ks * G.part_rows + row0) * G.ncols;
 #pragma unroll
   for (int v = 0; v < kVT; v++) {
@@ -489,8 +489,7 @@ __global__ void __launch_bounds__(kPfWaves * 64) pf_gemm_kernel(const PfGemm G) 
   auto is = [&](int f) { return (MASK & (1u << f)) && (MASK == (1u << f) || sg.fmt == f); };
   uint32_t m_tiles = G.m_tiles;
   if (G.m_count) {   // MoE: this expert's row count lives on the device (no host round trip per layer)
-    uint32_t cnt;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(cnt) : "s"(G.m_count) : "memory");
+    const uint32_t cnt = sload_u32(G.m_count);
     if (cnt == 0) return;
     m_tiles = (cnt + 15) / 16;
   }
