@@ -578,6 +578,49 @@ uint64_t lgh_debug_static_launches(void);
 int lgh_op_moe_experts(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down,
                        size_t n_experts, size_t hidden, size_t ffn, size_t top_k, const float* router, const int* sel, const float* sel_w,
                        const float* x, const float* norm_w, float eps, float* out, int* sel_out, float* sel_w_out);
+/* The multi-sequence step's mat-vec launches (lgh_forward_multi's own assembly), one at a time on n_seq <= max_batch <= 16 sequences,
+ * for kernel-level tests.  Test support: not part of the inference API.  They run on the scratch lgh_batch_create allocates (the same
+ * sizing rules) for a one-layer model whose widths follow from the launch; before the first launch every vector, XQ image,
+ * partial-sum and cache buffer holds the NaN pattern 0x7FC0BEEF, the MoE tables in-range values: counts and selections 0x55, entry
+ * lists max_batch * top_k - 1.  Every sequence's input image is made by the engine's converter, as the step's producers leave it.
+ * Buffers come back for all max_batch sequences, so that rows no sequence of the call owns show the pattern.  Weights are native GGUF
+ * bytes in the five matrix-core formats; a k that does not plan to 8-wave workgroups: LGH_UNSUPPORTED.  structures (int[3], may be
+ * NULL): how many launches of the call ran as mvqb, as mvqb2 with the k-slices in the grid, and as mvqb2 SEQ.
+ *
+ * One launch on x [n_seq][k].  w_up: the SwiGLU gate | up pair (norm prologue, the step's hidden -> act); resid [n_seq][n]: a residual
+ * launch with bias (wo, down: attn_out -> hidden); neither: a store (the output projection: hidden -> logits, any n; xq_next must be 0).
+ * out [max_batch][n] — a store's rows lie n rounded up to a multiple of 16 apart, [max_batch][(n + 15) / 16 * 16], so that floats past
+ * row n of every sequence show the pattern; image_out [max_batch][1280 bytes per 256 elements of n] and ssq_out [max_batch][n / 16 + 64] when the output has
+ * image slots (the first two kinds), *image_used = 1 when the launch left them. */
+int lgh_op_linear_multi(int device, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, size_t n_seq,
+                        size_t max_batch, const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
+                        float* out, uint8_t* image_out, float* ssq_out, int* image_used, int* structures);
+/* lgh_op_linear_chain for n_seq sequences: launch A (the SwiGLU pair or a residual launch, xq_next 1 or 2) leaves every sequence's
+ * image; B (a store, [n_b][n_a]) runs on A's outputs from those images, then again after they were marked stale and converted afresh.
+ * out_a [n_seq][n_a]; out_b, out_b_requant [n_seq][n_b]. */
+int lgh_op_linear_chain_multi(int device, uint32_t type_a, const void* w_a, const void* w_a_up, const float* bias_a, size_t k, size_t n_a, size_t n_seq,
+                              size_t max_batch, const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
+                              uint32_t type_b, const void* w_b, size_t n_b, float* out_a, float* out_b, float* out_b_requant, int* image_used);
+/* The step's fused QKV launch (three launches for formats without a common instantiation) on x [n_seq][hidden]: sequence s is rotated
+ * at pos[s] and writes row pos[s] of cache slot slot[s] (distinct, < max_batch).  q_out [max_batch][n_heads * head_dim]; k_cache /
+ * v_cache [max_batch][n_kv_heads][max_seq_len][head_dim] (out only); staged != 0: the quantized caches' variant — the rotated K row and
+ * the V row of every sequence in staged_out [max_batch][2 * n_kv_heads * head_dim], the caches untouched (may be NULL). */
+int lgh_op_qkv_rope_multi(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                          float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t n_seq,
+                          size_t max_batch, const int* pos, const int* slot, float rope_base, float rope_scale, int staged, float* q_out,
+                          float* k_cache, float* v_cache, float* staged_out, int* structures);
+/* The grouped MoE half of a step on x [n_seq][hidden] (also the residual), n_seq >= 2: router (or the given sel / sel_w
+ * [n_seq][top_k], a sequence's experts distinct), grouping, every expert's gate | up and down over its pairs, combine.  Expert stacks
+ * as lgh_op_moe_experts.  out [max_batch][hidden]; image_out / ssq_out: the rows' XQ images (times next_nw) and sums of squares as
+ * the combine launch left them, image_requant / ssq_requant: as the engine's converter makes them from `out` (same sizes as
+ * lgh_op_linear_multi's); cnt_out [64], idx_out [64][16]: the grouping tables.  A shape the engine would not group: LGH_UNSUPPORTED. */
+int lgh_op_moe_multi(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down, size_t n_experts,
+                     size_t hidden, size_t ffn, size_t top_k, size_t n_seq, size_t max_batch, const float* router, const int* sel, const float* sel_w,
+                     const float* x, const float* norm_w, const float* next_nw, float eps, float* out, uint8_t* image_out, float* ssq_out,
+                     uint8_t* image_requant, float* ssq_requant, int* sel_out, float* sel_w_out, int* cnt_out, int* idx_out, int* structures);
+/* Multi-sequence mat-vec launches of this process per structure so far: out[0] mvqb, out[1] mvqb2 with the k-slices in the grid,
+ * out[2] mvqb2 SEQ (tests: a launch whose partial-sum buffer is too small falls back to mvqb without a word). */
+void lgh_debug_mvqb_structures(uint64_t* out);
 /* The batched prompt path's layer steps (prefill_block's own launch sequences), one at a time on a block of m_tokens <= 128 tokens,
  * for kernel-level tests.  Test support: not part of the inference API.  Weights are native GGUF bytes, row-major [out][in], of the
  * types the batched path takes (Q4_K, Q5_K, Q6_K, Q8_0, Q4_0); hidden_size % 256 == 0.  Before the first launch the scratch the kernels

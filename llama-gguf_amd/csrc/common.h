@@ -208,6 +208,10 @@ uint32_t mvq_format_mask(const MvLaunch& L);
 uint32_t mvq_tile_bytes(int dev_type);   // bytes of one 16-row x 256-element tile in the device layout of this type (0: not a tile16 type)
 hipError_t mvqb_launch(const MvLaunch& L, const MvBatch& B, uint32_t n_wg, uint32_t threads, hipStream_t st);   // matvec_batch.hip
 size_t mvqb_lds_bytes(uint32_t n_seq, uint32_t red_floats);
+// floats of MvBatch::part a launch over [.., k] matrices with n_units (row tile, pass) units asks for: n_seq sequences, nz experts
+uint64_t mvqb_part_floats(uint32_t k, uint32_t n_units, uint32_t n_seq, uint32_t nz);
+// launches of this process per structure: [0] mvqb, [1] mvqb2 with the k-slices as the grid's second dimension, [2] mvqb2 SEQ
+void mvqb_structure_launches(uint64_t out[3]);
 hipError_t xq_quantize_launch(const float* x, const float* nw, uint8_t* xq, float* ssq_part, uint32_t k, hipStream_t st);
 hipError_t repack_t16_launch(int dev_type, const uint8_t* raw, uint8_t* dst, uint32_t n_rows, uint32_t nblk, hipStream_t st);
 hipError_t repack_q6k_t16_launch(const uint8_t* raw, uint8_t* dst, uint32_t n_rows, uint32_t nblk, hipStream_t st);  // LGH_SYM_MV_* of the instantiation mv_launch will pick

@@ -210,6 +210,21 @@ int upload_matrix(lgh_ctx* c, lgh::DevWeight& W, int src_type, uint32_t k, uint3
                   const void* host, size_t nbytes);
 int upload_f32(lgh_ctx* c, float** dst, int src_type, uint64_t n, const void* host, size_t nbytes);
 int launch_mv(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float* norm_w, uint32_t k);
+// ---- multi-sequence decode (engine_batch.hip).  One batched quantized mat-vec launch over the context's batch scratch: `specs` name
+// sequence 0's vectors, sequence s follows at the strides (floats; xq_out_k: the k its output's views were registered with, 0 = no image).
+// ind: the launch works on indirect (sequence, top-k slot) entries, one list per expert (MvBatch::ind_*)
+struct MvIndirect { const int* cnt = nullptr; const int* idx = nullptr; uint32_t div = 0, nz = 0, stride = 0; };
+int launch_mvb(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float* norm_w, uint32_t k, uint32_t n_seq, const uint32_t* out_stride,
+               const uint32_t* resid_stride, const uint32_t* xq_out_k, const MvIndirect ind = MvIndirect{});
+bool mvb_k_ok(uint32_t k);                           // a [.., k] matrix plans to the 8-wave workgroups the multi-sequence kernels run
+uint32_t xq_stride_of(uint32_t k);                   // bytes / floats between two sequences' images and sum-of-squares partials
+uint32_t ssq_stride_of(uint32_t k);
+void mark_fresh(lgh_ctx* c, const float* base, uint32_t k, uint32_t n, const float* tag);
+void spread_state(lgh_ctx* c, const float* f32, uint32_t k, uint32_t n);
+uint64_t batch_part_floats(const lgh_ctx* c, uint32_t max_batch);
+int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch);
+int qkv_forward_multi(lgh_ctx* c, lgh::LayerW& Lw, uint32_t li, uint32_t n_seq);
+int moe_grouped_forward(lgh_ctx* c, lgh::LayerW& Lw, uint32_t n_seq, const float* next_nw, bool route);
 // matrix-core segments in formats without a common instantiation (Q4_K with Q5_K, Q8_0 / Q4_0 with anything else): one launch each
 bool mv_formats_split(const SegSpec* specs, int nseg);
 lgh::XqBuf* xq_get(lgh_ctx* c, const float* f32, uint32_t k);   // finds or registers (allocating) the image of a buffer

@@ -32,8 +32,7 @@ __global__ void batch_advance_kernel(int* pos, int n) {
 
 }  // namespace lgh
 
-namespace {
-
+// ---- shared with the per-launch entry points of ops_api.hip (engine.h)
 uint32_t xq_stride_of(uint32_t k) { return (uint32_t)xq_bytes(k); }
 uint32_t ssq_stride_of(uint32_t k) { return k / 16 + 64; }
 
@@ -65,9 +64,6 @@ void spread_state(lgh_ctx* c, const float* f32, uint32_t k, uint32_t n) {
     if (XqBuf* q = xq_find(c, f32 + (size_t)s * k)) { q->fresh = q0->fresh; q->tag = q0->tag; }
 }
 
-// one batched quantized mat-vec launch: `specs` name sequence 0's vectors
-struct MvIndirect { const int* cnt = nullptr; const int* idx = nullptr; uint32_t div = 0, nz = 0, stride = 0; };
-
 // MoE layers: from how many sequences on a step reads every selected expert ONCE (one router launch, a grouping launch, gate | up
 // and down over all experts with the expert as the grid's third dimension + their epilogue launches, one combine: 7 per layer
 // whatever the step's size) instead of running the FFN sequence by sequence (3 launches per sequence).  Measured on Mixtral-8x7B
@@ -78,9 +74,18 @@ uint32_t moe_group_min() {
   return v;
 }
 
+// the multi-sequence kernels run 8-wave workgroups: the single-sequence plan of a [.., k] matrix must have T x G = 8
+bool mvb_k_ok(uint32_t k) {
+  MvPlan p{};
+  return mvq_plan(k, 16, 1, &p, 16) == hipSuccess && p.threads == 512;
+}
+
+// one batched quantized mat-vec launch: `specs` name sequence 0's vectors
 int launch_mvb(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float* norm_w, uint32_t k, uint32_t n_seq, const uint32_t* out_stride,
-               const uint32_t* resid_stride, const uint32_t* xq_out_k, const MvIndirect ind = MvIndirect{}) {
+               const uint32_t* resid_stride, const uint32_t* xq_out_k, const MvIndirect ind) {
   BatchScratch& Bs = c->batch;
+  if (!mvb_k_ok(k))
+    return fail(c, LGH_UNSUPPORTED, "multi-sequence mat-vec: k=" + std::to_string(k) + " does not plan to 8-wave workgroups");
   MvLaunch L;
   uint32_t wg = 0, threads = 0;
   uint64_t alg = 0;
@@ -122,14 +127,92 @@ int launch_mvb(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float*
   return run_k(c, cls, LGH_SYM_OTHER, alg, [&] { return mvqb_launch(L, B, wg, threads, c->stream); });
 }
 
+// Q, K, V of layer li for the step's sequences: RoPE at every sequence's own position, K / V rows into its own cache slot
+int qkv_forward_multi(lgh_ctx* c, LayerW& Lw, uint32_t li, uint32_t n_seq) {
+  BatchScratch& Bs = c->batch;
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim;
+  const bool tq = (d.flags & LGH_FLAG_KV_INT8) != 0;   // every quantized cache (TurboQuant, int8, FP8) stages its rows
+  const uint32_t KD = d.num_kv_heads * d.head_dim;
+  int rc;
+  SegSpec sp[3];
+  sp[0].W[0] = &Lw.wq; sp[0].x[0] = Bs.hidden; sp[0].epi = EPI_ROPE_Q; sp[0].out = Bs.q; sp[0].bias = Lw.bq;
+  // (quantized caches: the rotated K row and the V row stay f32 in a staging vector per sequence; the attention launch compresses them)
+  sp[1].W[0] = &Lw.wk; sp[1].x[0] = Bs.hidden; sp[1].epi = tq ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = tq ? Bs.kv_tmp : Bs.kcache[li]; sp[1].bias = Lw.bk;
+  sp[2].W[0] = &Lw.wv; sp[2].x[0] = Bs.hidden; sp[2].epi = tq ? EPI_STORE : EPI_V_CACHE; sp[2].out = tq ? Bs.kv_tmp + KD : Bs.vcache[li]; sp[2].bias = Lw.bv;
+  const uint32_t os[3] = {QD, tq ? 2 * KD : 0, tq ? 2 * KD : 0}, rs[3] = {0, 0, 0}, xk[3] = {0, 0, 0};
+  if (mv_formats_split(sp, 3)) {   // (one launch each then, as launch_mv does)
+    for (int s = 0; s < 3; s++)
+      if ((rc = launch_mvb(c, LGH_K_QKV, sp + s, 1, Lw.attn_norm, H, n_seq, os + s, rs + s, xk + s))) return rc;
+    return LGH_OK;
+  }
+  return launch_mvb(c, LGH_K_QKV, sp, 3, Lw.attn_norm, H, n_seq, os, rs, xk);
+}
+
+// MoE, every selected expert's matrices read ONCE for the step (MoeLayer::forward per sequence, moe.rs:321-413, regrouped):
+// router (route; else the selections and weights already in the scratch) -> the (sequence, slot) pairs grouped by expert -> a gate|up
+// launch, every expert over its pairs (SwiGLU, activation + XQ image per pair), and a down launch (output per pair) ->
+// h += sum_p w_p * down_p in selection order
+int moe_grouped_forward(lgh_ctx* c, LayerW& Lw, uint32_t n_seq, const float* next_nw, bool route) {
+  BatchScratch& Bs = c->batch;
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size;
+  const uint32_t topk = d.num_experts_per_token, ne = d.num_experts, EF = Lw.gate_exps.n;
+  int rc;
+  // (the router for all sequences in one launch: selections and weights packed [sequence][top_k])
+  if (route && (rc = run_k(c, LGH_K_ROUTER, LGH_SYM_ROUTER, (uint64_t)ne * H * 4, [&] {
+                  return moe_router_launch(Bs.hidden, Lw.ffn_norm, d.norm_eps, Lw.router, H, ne, topk, Bs.moe_sel, Bs.moe_w, c->stream, n_seq);
+                })))
+    return rc;
+  if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] { return moe_group_launch(Bs.moe_sel, n_seq, topk, ne, Bs.moe_cnt, Bs.moe_idx, kMaxBatch, c->stream); })))
+    return rc;
+  // all experts of the layer in one launch each (grid z = expert: its count, its entry list, its slice of the stacked matrices)
+  const MvIndirect ind_gu{Bs.moe_cnt, Bs.moe_idx, topk, ne, (uint32_t)kMaxBatch}, ind_dn{Bs.moe_cnt, Bs.moe_idx, 1, ne, (uint32_t)kMaxBatch};
+  {
+    SegSpec sp;
+    sp.npass = 2;
+    sp.W[0] = &Lw.gate_exps; sp.W[1] = &Lw.up_exps;
+    sp.x[0] = sp.x[1] = Bs.hidden;
+    sp.epi = EPI_SWIGLU;
+    sp.out = Bs.moe_act;
+    sp.xq_next = 1;
+    const uint32_t os[1] = {EF}, rs[1] = {0}, xk[1] = {EF};
+    if ((rc = launch_mvb(c, LGH_K_GATEUP, &sp, 1, Lw.ffn_norm, H, n_seq, os, rs, xk, ind_gu))) return rc;
+  }
+  mark_fresh(c, Bs.moe_act, EF, n_seq * topk, nullptr);
+  {
+    SegSpec sp;
+    sp.W[0] = &Lw.down_exps; sp.x[0] = Bs.moe_act; sp.epi = EPI_STORE; sp.out = Bs.moe_tmp;
+    const uint32_t os[1] = {H}, rs[1] = {0}, xk[1] = {0};
+    if ((rc = launch_mvb(c, LGH_K_DOWN, &sp, 1, nullptr, Lw.down_exps.k, n_seq, os, rs, xk, ind_dn))) return rc;
+  }
+  XqBuf* qh = xq_find(c, Bs.hidden);
+  if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] {
+         return moe_combine_launch(Bs.moe_tmp, Bs.moe_w, topk, Bs.hidden, H, n_seq, next_nw, qh->xq, xq_stride_of(H), qh->ssq, ssq_stride_of(H), c->stream);
+       })))
+    return rc;
+  mark_fresh(c, Bs.hidden, H, n_seq, next_nw);
+  return LGH_OK;
+}
+
+namespace {
+
 bool batch_weights_ok(const lgh_ctx* c, std::string& why) {
   const lgh_model_desc& d = c->d;
   if (d.hidden_size % 256 || (d.num_heads * d.head_dim) % 256) { why = "hidden size and heads x head_dim must be multiples of 256"; return false; }
   if (d.use_neox_rope) { why = "NeoX RoPE is not fused into the QKV launch"; return false; }
   if (!attn_shape_has_fast_kernel(d.head_dim, d.num_heads / d.num_kv_heads)) { why = "attention shape outside the split kernels"; return false; }
   if (!(c->first && c->last)) { why = "pipeline stages are not batched"; return false; }
+  // (what launch_mvb would refuse at the first step: the widths every launch of a step multiplies along)
+  auto plans = [&](uint32_t k, const char* what) {
+    if (mvb_k_ok(k)) return true;
+    why = std::string(what) + " " + std::to_string(k) + " does not plan to 8-wave workgroups";
+    return false;
+  };
+  if (!plans(d.hidden_size, "hidden size") || !plans(d.num_heads * d.head_dim, "heads x head_dim")) return false;
   for (uint32_t i = c->l0; i < c->l1; i++) {
     const LayerW& L = c->layers[i];
+    if (!L.moe() && d.intermediate_size % 256 == 0 && !plans(d.intermediate_size, "intermediate size")) return false;
     for (const DevWeight* W : {&L.wq, &L.wk, &L.wv, &L.wo})
       if (!mfma_type(W->type) || W->n % 16) { why = "attention weights of layer " + std::to_string(i) + " are not in a matrix-core tile layout"; return false; }
     if (!L.moe()) {
@@ -175,22 +258,7 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
     LayerW& Lw = c->layers[li];
     const float* next_nw = li + 1 < c->l1 ? c->layers[li + 1].attn_norm : c->output_norm;
     // ---- Q, K, V (+ RoPE at every sequence's own position, K / V rows into its own cache slot)
-    {
-      const bool tq = (d.flags & LGH_FLAG_KV_INT8) != 0;   // every quantized cache (TurboQuant, int8, FP8) stages its rows
-      const uint32_t KD = d.num_kv_heads * d.head_dim;
-      SegSpec sp[3];
-      sp[0].W[0] = &Lw.wq; sp[0].x[0] = Bs.hidden; sp[0].epi = EPI_ROPE_Q; sp[0].out = Bs.q; sp[0].bias = Lw.bq;
-      // (quantized caches: the rotated K row and the V row stay f32 in a staging vector per sequence; the attention launch compresses them)
-      sp[1].W[0] = &Lw.wk; sp[1].x[0] = Bs.hidden; sp[1].epi = tq ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = tq ? Bs.kv_tmp : Bs.kcache[li]; sp[1].bias = Lw.bk;
-      sp[2].W[0] = &Lw.wv; sp[2].x[0] = Bs.hidden; sp[2].epi = tq ? EPI_STORE : EPI_V_CACHE; sp[2].out = tq ? Bs.kv_tmp + KD : Bs.vcache[li]; sp[2].bias = Lw.bv;
-      const uint32_t os[3] = {QD, tq ? 2 * KD : 0, tq ? 2 * KD : 0}, rs[3] = {0, 0, 0}, xk[3] = {0, 0, 0};
-      if (mv_formats_split(sp, 3)) {   // (one launch each then, as launch_mv does)
-        for (int s = 0; s < 3; s++)
-          if ((rc = launch_mvb(c, LGH_K_QKV, sp + s, 1, Lw.attn_norm, H, n_seq, os + s, rs + s, xk + s))) return rc;
-      } else if ((rc = launch_mvb(c, LGH_K_QKV, sp, 3, Lw.attn_norm, H, n_seq, os, rs, xk))) {
-        return rc;
-      }
-    }
+    if ((rc = qkv_forward_multi(c, Lw, li, n_seq))) return rc;
     // ---- attention_cached per sequence (ops.rs:1479-1537): split + merge, the sequence as the grid's second dimension
     if (kv_is_tq(d.kv_cache_type)) {
       // TurboQuantKVCache (kv_turboquant.rs) per sequence: write_kv + attention over the slot's codes; the merge inverts the V rotation
@@ -267,45 +335,7 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
         spread_state(c, Bs.hidden, H, n_seq);
       }
     } else if (Bs.moe_act && n_seq >= moe_group_min()) {
-      // ---- MoE, every selected expert's matrices read ONCE for the step (MoeLayer::forward per sequence, moe.rs:321-413, regrouped):
-      // router -> the (sequence, slot) pairs grouped by expert -> a gate|up launch, every expert over its pairs (SwiGLU, activation
-      // + XQ image per pair), and a down launch (output per pair) -> h += sum_p w_p * down_p in selection order
-      const uint32_t topk = d.num_experts_per_token, ne = d.num_experts, EF = Lw.gate_exps.n;
-      // (the router for all sequences in one launch: selections and weights packed [sequence][top_k])
-      if ((rc = run_k(c, LGH_K_ROUTER, LGH_SYM_ROUTER, (uint64_t)ne * H * 4, [&] {
-             return moe_router_launch(Bs.hidden, Lw.ffn_norm, d.norm_eps, Lw.router, H, ne, topk, Bs.moe_sel, Bs.moe_w, c->stream, n_seq);
-           })))
-        return rc;
-      if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] { return moe_group_launch(Bs.moe_sel, n_seq, topk, ne, Bs.moe_cnt, Bs.moe_idx, kMaxBatch, c->stream); })))
-        return rc;
-      // all experts of the layer in one launch each (grid z = expert: its count, its entry list, its slice of the stacked matrices)
-      const MvIndirect ind_gu{Bs.moe_cnt, Bs.moe_idx, topk, ne, (uint32_t)kMaxBatch}, ind_dn{Bs.moe_cnt, Bs.moe_idx, 1, ne, (uint32_t)kMaxBatch};
-      {
-        SegSpec sp;
-        sp.npass = 2;
-        sp.W[0] = &Lw.gate_exps; sp.W[1] = &Lw.up_exps;
-        sp.x[0] = sp.x[1] = Bs.hidden;
-        sp.epi = EPI_SWIGLU;
-        sp.out = Bs.moe_act;
-        sp.xq_next = 1;
-        const uint32_t os[1] = {EF}, rs[1] = {0}, xk[1] = {EF};
-        if ((rc = launch_mvb(c, LGH_K_GATEUP, &sp, 1, Lw.ffn_norm, H, n_seq, os, rs, xk, ind_gu))) return rc;
-      }
-      mark_fresh(c, Bs.moe_act, EF, n_seq * topk, nullptr);
-      {
-        SegSpec sp;
-        sp.W[0] = &Lw.down_exps; sp.x[0] = Bs.moe_act; sp.epi = EPI_STORE; sp.out = Bs.moe_tmp;
-        const uint32_t os[1] = {H}, rs[1] = {0}, xk[1] = {0};
-        if ((rc = launch_mvb(c, LGH_K_DOWN, &sp, 1, nullptr, Lw.down_exps.k, n_seq, os, rs, xk, ind_dn))) return rc;
-      }
-      {
-        XqBuf* qh = xq_find(c, Bs.hidden);
-        if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] {
-               return moe_combine_launch(Bs.moe_tmp, Bs.moe_w, topk, Bs.hidden, H, n_seq, next_nw, qh->xq, xq_stride_of(H), qh->ssq, ssq_stride_of(H), c->stream);
-             })))
-          return rc;
-        mark_fresh(c, Bs.hidden, H, n_seq, next_nw);
-      }
+      if ((rc = moe_grouped_forward(c, Lw, n_seq, next_nw, true))) return rc;
     } else {
       for (uint32_t s = 0; s < n_seq; s++) {   // every sequence routes to its own experts: the single-sequence launches on its vectors
         const FfnView v{Bs.hidden + (size_t)s * H, Bs.act + (size_t)s * Bs.ffn, Bs.act2 + (size_t)s * Bs.ffn, Bs.xnorm + (size_t)s * H,
@@ -403,18 +433,47 @@ int decode_multi(lgh_ctx* c, const uint32_t* slots, uint32_t n_seq, int mode, si
   return LGH_OK;
 }
 
+// the grouped MoE step needs both expert shapes on 8-wave workgroups (as Mixtral's are) and its tables bound top-k and the experts
+bool moe_grouped_ok(const lgh_model_desc& d, uint32_t EI) {
+  return d.num_experts && EI && EI % 256 == 0 && mvb_k_ok(d.hidden_size) && mvb_k_ok(EI) && d.num_experts_per_token <= 8 && d.num_experts <= 64;
+}
+
 }  // namespace
 
-extern "C" {
+// Partial sums between the two launches of a multi-sequence mat-vec (matvec_batch.hip, mvqb2): the largest region any launch of a
+// step of max_batch sequences asks for — mvqb_part_floats knows, per launch, whether the grid keeps one value per (sequence, row) or
+// one per k-slice, and an expert launch has a region per expert.  (A launch that finds the buffer too small falls back to the first
+// structure, and an expert launch fails.  mvqb_launch lays the buffer out and checks its size with the rule behind mvqb_part_floats
+// — matvec_batch.hip: mvqb2_part — and refuses a launch whose k-slices are not the ones mvqb_part_floats assumes for its k.)
+uint64_t batch_part_floats(const lgh_ctx* c, uint32_t max_batch) {
+  const lgh_model_desc& d = c->d;
+  const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim;
+  const uint32_t EI = d.expert_intermediate_size ? d.expert_intermediate_size : d.intermediate_size;
+  auto tiles = [](uint32_t n) { return (n + 15) / 16; };
+  uint64_t need = 0;
+  auto launch = [&](uint32_t k, uint32_t units, uint32_t nz) {
+    if (k && k % 256 == 0 && units) need = std::max(need, mvqb_part_floats(k, units, max_batch, nz));
+  };
+  launch(H, tiles(QD) + 2 * tiles(KD), 1);                     // fused Q | K | V ...
+  launch(H, tiles(QD), 1);                                     // ... or, split by format, one launch each: fewer units, but a launch
+  launch(H, tiles(KD), 1);                                     // of its own may keep a value per k-slice where the fused one keeps one per row
+  launch(QD, tiles(H), 1);                                     // wo
+  launch(H, 2 * tiles(d.intermediate_size), 1);                // gate | up
+  launch(d.intermediate_size, tiles(H), 1);                    // down
+  launch(H, tiles(d.vocab_size), 1);                           // output projection
+  if (moe_grouped_ok(d, EI)) {
+    launch(H, 2 * tiles(EI), d.num_experts);                   // every expert's gate | up over its pairs
+    launch(EI, tiles(H), d.num_experts);                       // ... and down
+  }
+  return need;
+}
 
-int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
-  int rc = check_ready(c);
-  if (rc) return rc;
+// the scratch of the multi-sequence engine for max_batch slots on a context whose model fields and layers are set: the vectors of the
+// sequences side by side with their registered XQ views, the control words, the partial-sum buffer, every slot's caches and the
+// grouped MoE step's buffers (lgh_batch_create; the per-launch entry points of ops_api.hip)
+int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch) {
+  int rc;
   BatchScratch& Bs = c->batch;
-  if (Bs.ready) return Bs.max_batch == max_batch ? LGH_OK : fail(c, LGH_INVALID_ARGUMENT, "lgh_batch_create was already called with another max_batch");
-  if (max_batch == 0 || max_batch > (uint32_t)kMaxBatch) return fail(c, LGH_INVALID_ARGUMENT, "max_batch must be 1 .. 16");
-  std::string why;
-  if (!batch_weights_ok(c, why)) return fail(c, LGH_UNSUPPORTED, "multi-sequence decode: " + why);
   const lgh_model_desc& d = c->d;
   const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim, G = d.num_heads / d.num_kv_heads;
   const uint32_t EI = d.expert_intermediate_size ? d.expert_intermediate_size : d.intermediate_size;
@@ -423,10 +482,7 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
   Bs.ffn = ffn;
   Bs.cache_stride = (uint64_t)d.num_kv_heads * d.max_seq_len * d.head_dim;
   const size_t B = max_batch;
-  // partial sums between the two launches of a multi-sequence mat-vec (matvec_batch.hip, mvqb2): per sequence either one value per
-  // launch row (any matrix) or 8 slices x the rows of a matrix with fewer than 1600 row tiles
-  const uint64_t moe_part = d.num_experts ? (uint64_t)d.num_experts * std::max<uint64_t>((uint64_t)2 * EI, (uint64_t)8 * H) : 0;   // every expert's region
-  Bs.mv_part_floats = B * std::max<uint64_t>({moe_part, (uint64_t)8 * 1600 * 16, (uint64_t)d.vocab_size + 16, (uint64_t)2 * ffn, (uint64_t)QD + 2 * d.num_kv_heads * d.head_dim, (uint64_t)H});
+  Bs.mv_part_floats = batch_part_floats(c, max_batch);
   uint8_t *xq_h = nullptr, *xq_a = nullptr, *xq_f = nullptr, *xq_f2 = nullptr;
   float *ssq_h = nullptr, *ssq_a = nullptr, *ssq_f = nullptr, *ssq_f2 = nullptr;
   const AllocSpec bufs[] = {
@@ -472,10 +528,7 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
   {   // MoE layers: the expert-grouped step's buffers ((sequence, slot) pairs)
     bool any_moe = false;
     for (uint32_t i = c->l0; i < c->l1; i++) any_moe = any_moe || c->layers[i].moe();
-    // (the multi-sequence kernels run 8-wave workgroups: both expert shapes must plan to T x G = 8, as Mixtral's do)
-    MvPlan pg{}, pd{};
-    const bool plans = mvq_plan(H, EI, 2, &pg, EI) == hipSuccess && mvq_plan(EI, H, 1, &pd, H) == hipSuccess && pg.threads == 512 && pd.threads == 512;
-    if (any_moe && plans && d.num_experts_per_token <= 8 && d.num_experts <= 64 && EI % 256 == 0) {
+    if (any_moe && moe_grouped_ok(d, EI)) {
       const size_t np = B * d.num_experts_per_token;
       uint8_t* xq_m = nullptr;
       float* ssq_m = nullptr;
@@ -492,6 +545,20 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
   register_views(c, Bs.act, xq_f, ssq_f, ffn, max_batch);
   register_views(c, Bs.act2, xq_f2, ssq_f2, ffn, max_batch);
   Bs.pos.assign(max_batch, 0);
+  return LGH_OK;
+}
+
+extern "C" {
+
+int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
+  int rc = check_ready(c);
+  if (rc) return rc;
+  BatchScratch& Bs = c->batch;
+  if (Bs.ready) return Bs.max_batch == max_batch ? LGH_OK : fail(c, LGH_INVALID_ARGUMENT, "lgh_batch_create was already called with another max_batch");
+  if (max_batch == 0 || max_batch > (uint32_t)kMaxBatch) return fail(c, LGH_INVALID_ARGUMENT, "max_batch must be 1 .. 16");
+  std::string why;
+  if (!batch_weights_ok(c, why)) return fail(c, LGH_UNSUPPORTED, "multi-sequence decode: " + why);
+  if ((rc = batch_scratch_alloc(c, max_batch))) return rc;
   // the slots' samplers (allocated before the context counts as ready: the sampler entry points index these per slot)
   if ((rc = samp_alloc(c, Bs.samp, max_batch, max_batch))) return rc;
   Bs.samp_cfg.assign(max_batch, lgh_sampler_config_ex{});

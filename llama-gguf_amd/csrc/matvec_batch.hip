@@ -19,6 +19,7 @@
 // entry list (MvBatch::ind_*: the (sequence, top-k slot) pairs that chose the expert, their number read from device memory), so
 // that an expert's matrices are read once per step; below 7 sequences engine_batch.hip runs the FFN sequence by sequence instead.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #include "device_utils.h"
@@ -469,10 +470,17 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb2_epilogue_kernel(uint32_t w
 // ------------------------------------------------------------------------------------------------
 size_t mvqb_lds_bytes(uint32_t n_seq, uint32_t red_floats) { return ((size_t)n_seq * red_floats + (size_t)n_seq * 8) * 4 + 64; }
 
+// which structure a launch took (a launch whose partial buffer is too small falls back to the first one without a word: tests read this)
+static std::atomic<uint64_t> g_structure_launches[3];
+void mvqb_structure_launches(uint64_t out[3]) {
+  for (int i = 0; i < 3; i++) out[i] = g_structure_launches[i].load(std::memory_order_relaxed);
+}
+
 template <uint32_t MASK, int NB>
 static hipError_t mvqb_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g, uint32_t threads, size_t lds, hipStream_t st) {
   static bool attr_set[64] = {};
   if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvqb_kernel<MASK, NB>), 160 * 1024, attr_set); e != hipSuccess) return e;
+  g_structure_launches[0].fetch_add(1, std::memory_order_relaxed);
   hipLaunchKernelGGL((mvqb_kernel<MASK, NB>), dim3(g.n_wg), dim3(threads), lds, st, g.wbpack, g.geom, g.geom2, L.red_floats, L, B);
   return hipGetLastError();
 }
@@ -482,6 +490,7 @@ static hipError_t mvqb2_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g,
                            size_t lds_e, uint32_t threads, hipStream_t st) {
   static bool attr_set[3][64] = {};
   const uint32_t nz = B.ind_cnt && B.ind_nz > 1 ? B.ind_nz : 1;   // a layer's experts as the grid's third dimension
+  g_structure_launches[seq ? 2 : 1].fetch_add(1, std::memory_order_relaxed);
   if (seq) {
     if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvqb2_kernel<MASK, NB, true>), 160 * 1024, attr_set[0]); e != hipSuccess) return e;
     hipLaunchKernelGGL((mvqb2_kernel<MASK, NB, true>), dim3(groups, 1, nz), dim3(kBWaves * 64), lds_x, st, Gm, L, B, B.part);
@@ -503,6 +512,32 @@ static uint32_t mvqb2_min_seq() {
     return e ? (uint32_t)std::atoi(e) : 2u;
   }();
   return v;
+}
+
+// mvqb2's grid for a launch of `groups` workgroups' worth of units over T k-slices: SEQ (a workgroup walks all slices of its units)
+// when there are enough units to fill the chip with whole rows per workgroup, or a single slice
+static bool mvqb2_seq_grid(uint32_t groups, uint32_t T) {
+  static const uint32_t seq_min_groups = [] { const char* e = std::getenv("LGH_MVQB2_SEQ_GROUPS"); return e ? (uint32_t)std::atoi(e) : 160u; }();
+  return groups >= seq_min_groups || T == 1;
+}
+
+// What a launch of n_units (row tile, pass) units over T k-slices keeps in MvBatch::part between its two launches, for n_seq sequences
+// and nz experts: the grid, the partial sums per (sequence, row), the floats of one expert's region and of all.  THE rule: mvqb_launch
+// lays the buffer out and checks its size with it, and the engine sizes the buffer with it (mvqb_part_floats).
+struct Mvqb2Part { bool seq; uint32_t nslots; uint64_t z_floats, floats; };
+static Mvqb2Part mvqb2_part(uint32_t T, uint32_t n_units, uint32_t n_seq, uint32_t nz) {
+  Mvqb2Part P;
+  P.seq = mvqb2_seq_grid((n_units + kBWaves - 1) / kBWaves, T);
+  P.nslots = P.seq ? 1u : T;
+  P.z_floats = (uint64_t)P.nslots * n_seq * n_units * 16;
+  P.floats = P.z_floats * std::max(nz, 1u);
+  return P;
+}
+
+uint64_t mvqb_part_floats(uint32_t k, uint32_t n_units, uint32_t n_seq, uint32_t nz) {
+  MvPlan p{};
+  if (mvq_plan(k, 16, 1, &p, 16) != hipSuccess) return 0;   // (the k-slices of a plan depend on k alone: mvqb_launch holds its launch to that)
+  return mvqb2_part(p.T, n_units, n_seq, nz).floats;
 }
 
 // `L` built like a single-sequence launch (engine_launch.hip: build_mv_group, with the batch cap on tiles per workgroup); sequences'
@@ -531,14 +566,16 @@ hipError_t mvqb_launch(const MvLaunch& L, const MvBatch& Bin, uint32_t n_wg, uin
     Gm.ub1 = L.nseg > 1 ? ub[1] : Gm.n_units;
     Gm.ub2 = L.nseg > 2 ? ub[2] : Gm.n_units;
     const uint32_t groups = (Gm.n_units + kBWaves - 1) / kBWaves;
-    static const uint32_t seq_min_groups = [] { const char* e = std::getenv("LGH_MVQB2_SEQ_GROUPS"); return e ? (uint32_t)std::atoi(e) : 160u; }();
-    const bool seq = groups >= seq_min_groups || Gm.T == 1;  // enough units to fill the chip with whole rows per workgroup
-    Gm.nslots = seq ? 1 : Gm.T;
+    const uint32_t nz = B.ind_cnt && B.ind_nz > 1 ? B.ind_nz : 1;
+    const Mvqb2Part P = mvqb2_part(Gm.T, Gm.n_units, B.n_seq, nz);
+    if (P.floats != mvqb_part_floats(L.k, Gm.n_units, B.n_seq, nz)) return hipErrorInvalidValue;   // (the buffer was sized for other k-slices)
+    const bool seq = P.seq;
+    Gm.nslots = P.nslots;
     const int nb_inst = B.n_seq <= 4 ? 4 : B.n_seq <= 8 ? 8 : 16;
     Gm.cb = std::max(1u, std::min(Gm.nbw, mvqb2_stage_bytes((mask & (mask - 1)) == 0, nb_inst) / (B.n_seq * (uint32_t)kXqRecord)));
     const size_t lds_x = (size_t)2 * Gm.cb * B.n_seq * kXqRecord + kXZeroBytes + kXSelBytes;
-    B.part_z_floats = (uint64_t)Gm.nslots * B.n_seq * Gm.n_units * 16;
-    if (B.part_z_floats * (B.ind_cnt && B.ind_nz > 1 ? B.ind_nz : 1) <= B.part_floats) {
+    B.part_z_floats = P.z_floats;
+    if (P.floats <= B.part_floats) {
 #define LGH_MVQB2_CASE(M)                                                                         \
   case M:                                                                                         \
     if (B.n_seq <= 4) return mvqb2_go<M, 4>(L, B, g, Gm, seq, groups, lds_x, lds, threads, st);  \

@@ -57,6 +57,7 @@ struct Tmp {  // bare context: stream, device state words, tracked allocations
     if (!c) return;
     (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
+    if (c->batch.h_ctl) (void)hipHostFree(c->batch.h_ctl);   // (the multi-sequence entry points: batch_scratch_alloc's pinned words)
     (void)hipStreamDestroy(c->own_stream);
     delete c;
   }
@@ -1411,6 +1412,323 @@ int lgh_op_pf_moe(int device, uint32_t type_gate_up, const void* w_gate, const v
   for (size_t e = 0; act_out && e < E; e++)   // every expert's SwiGLU rows as the down GEMM reads them, rows past its count included
     if ((rc = xh_down(t, P.xh_act_e + e * xh_bytes((uint32_t)ffn), kPfTokens, ffn, act_out + e * kPfTokens * ffn))) return rc;
   return pf_down_block(t, m_tokens, H, dnext != nullptr, hidden_out, xh_out, ssq_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The multi-sequence step's mat-vec launches (engine_batch.hip: launch_mvb -> build_mv_group -> mvqb_launch, qkv_forward_multi,
+// moe_grouped_forward) one at a time on a bare one-layer context with the engine's own batch scratch (batch_scratch_alloc), for
+// kernel-level tests (tests/test_gpu_matvec_multi.py).  Test support: not part of the inference API.
+// Before the first launch every vector, image, partial-sum and cache buffer of the scratch holds the NaN pattern 0x7FC0BEEF; the MoE
+// tables hold in-range sentinels the kernels must not leave: counts 0x55, entry lists max_batch * top_k - 1 (the last pair), selections 0x55.
+// ------------------------------------------------------------------------------------------------
+struct MbShape { size_t H = 256, head_dim = 64, n_heads = 4, n_kv = 4, F = 0, vocab = 16, max_seq = 1, E = 0, top_k = 0, EI = 0; };
+
+static int mb_test_ctx(Tmp& t, const LayerW& Lw, const MbShape& s, float eps, size_t max_batch, bool staged_kv) {
+  lgh_ctx* c = t.c;
+  lgh_model_desc& d = c->d;
+  d.norm_eps = eps;
+  d.hidden_size = (uint32_t)s.H;
+  d.head_dim = (uint32_t)s.head_dim;
+  d.num_heads = (uint32_t)s.n_heads;
+  d.num_kv_heads = (uint32_t)s.n_kv;
+  d.intermediate_size = (uint32_t)s.F;
+  d.vocab_size = (uint32_t)s.vocab;
+  d.max_seq_len = (uint32_t)s.max_seq;
+  d.num_layers = 1;
+  d.num_experts = (uint32_t)s.E;
+  d.num_experts_per_token = (uint32_t)s.top_k;
+  d.expert_intermediate_size = (uint32_t)s.EI;
+  if (staged_kv) { d.flags |= LGH_FLAG_KV_INT8; d.kv_cache_type = LGH_KV_INT8; }
+  c->layers.assign(1, Lw);
+  c->l0 = 0;
+  c->l1 = 1;
+  if (int rc = batch_scratch_alloc(c, (uint32_t)max_batch)) return rc;
+  const BatchScratch& Bs = c->batch;
+  const size_t B = max_batch, H = s.H, QD = s.n_heads * s.head_dim, KD = s.n_kv * s.head_dim, np = B * s.top_k;
+  const uint32_t kF32 = 0x7FC0BEEFu;
+  bool ok = pf_poison(c, Bs.hidden, B * H * 4, kF32) && pf_poison(c, Bs.xnorm, B * H * 4, kF32) && pf_poison(c, Bs.q, B * QD * 4, kF32) &&
+            pf_poison(c, Bs.attn_out, B * QD * 4, kF32) && pf_poison(c, Bs.act, B * Bs.ffn * 4, kF32) && pf_poison(c, Bs.act2, B * Bs.ffn * 4, kF32) &&
+            pf_poison(c, Bs.logits, B * s.vocab * 4, kF32) && pf_poison(c, Bs.mv_part, Bs.mv_part_floats * 4, kF32) &&
+            pf_poison(c, Bs.moe_w, B * 8 * 4, kF32) && pf_poison(c, Bs.moe_sel, B * 8 * 4, 0x55u) && pf_poison(c, Bs.kv_tmp, B * 2 * KD * 4, kF32) &&
+            pf_poison(c, Bs.kcache[0], B * Bs.cache_stride * 4, kF32) && pf_poison(c, Bs.vcache[0], B * Bs.cache_stride * 4, kF32) &&
+            pf_poison(c, Bs.moe_act, np * s.EI * 4, kF32) && pf_poison(c, Bs.moe_tmp, np * H * 4, kF32) && pf_poison(c, Bs.moe_cnt, 64 * 4, 0x55u) &&
+            pf_poison(c, Bs.moe_idx, (size_t)64 * kMaxBatch * 4, np ? (uint32_t)np - 1 : 0u);
+  for (const XqBuf& q : c->xqs) ok = ok && pf_poison(c, q.xq, xq_bytes(q.k), kF32) && pf_poison(c, q.ssq, (size_t)ssq_stride_of(q.k) * 4, kF32);
+  return ok ? LGH_OK : LGH_OPERATION_FAILED;
+}
+
+// the step's control words: positions and cache slots of its sequences
+static int mb_control(Tmp& t, const int* pos, const int* slot, size_t n_seq) {
+  int p[kMaxBatch] = {}, sl[kMaxBatch];
+  for (size_t i = 0; i < (size_t)kMaxBatch; i++) { sl[i] = (int)i; if (i < n_seq && pos) p[i] = pos[i]; if (i < n_seq && slot) sl[i] = slot[i]; }
+  const BatchScratch& Bs = t.c->batch;
+  if (hipMemcpyAsync(Bs.d_pos, p, sizeof(p), hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+      hipMemcpyAsync(Bs.d_slot, sl, sizeof(sl), hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  return hipStreamSynchronize(t.c->stream) == hipSuccess ? LGH_OK : LGH_OPERATION_FAILED;
+}
+
+// n vectors of k floats from `base` on: the images their producers in the step would have left (the engine's own producer on each
+// registered view, multiplied with `tag`), marked fresh
+static int mb_produce_images(lgh_ctx* c, const float* base, uint32_t k, size_t n, const float* tag) {
+  for (size_t s = 0; s < n; s++) {
+    XqBuf* q = xq_find(c, base + s * k);
+    if (!q) return LGH_OPERATION_FAILED;
+    if (xq_quantize_launch(q->f32, tag, q->xq, tag ? q->ssq : nullptr, k, c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+    q->fresh = true;
+    q->tag = tag;
+  }
+  return LGH_OK;
+}
+
+static void mb_structures(int* out, const uint64_t before[3]) {
+  uint64_t now[3];
+  lgh::mvqb_structure_launches(now);
+  for (int i = 0; out && i < 3; i++) out[i] = (int)(now[i] - before[i]);
+}
+
+void lgh_debug_mvqb_structures(uint64_t* out) { lgh::mvqb_structure_launches(out); }
+
+// What a launch of the step multiplies: A = the SwiGLU gate | up pair (w_up: hidden -> act), a residual launch (resid: attn_out -> hidden,
+// wo and down) or a plain store (hidden -> logits, the output projection).  The model fields follow from the launch's k and n.
+struct MbLinear {
+  DevWeight WA, WU;
+  float *dnw = nullptr, *dbias = nullptr, *dnext = nullptr;
+  float *in = nullptr, *out = nullptr;
+  // floats between two sequences' outputs: n — or, for a store, n rounded up to a whole tile, so that whatever a launch writes past
+  // row n of ANY sequence lands in floats nobody owns (the step's logits rows lie n apart; the stride is the launch's parameter)
+  size_t out_stride = 0;
+  int role = 0;   // 0 store, 1 residual, 2 SwiGLU
+};
+
+static int mb_linear_setup(Tmp& t, MbLinear& M, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, size_t n_seq,
+                           size_t max_batch, const float* x, const float* norm_w, float eps, const float* resid, const float* next_nw, size_t vocab) {
+  if (k == 0 || k % 256 || !mvb_k_ok((uint32_t)k)) return LGH_UNSUPPORTED;   // (what lgh_batch_create refuses: batch_weights_ok)
+  const size_t nb = weight_bytes(type, k, n);
+  if (!nb) return LGH_SHAPE_MISMATCH;
+  int rc;
+  if ((rc = upload_matrix(t.c, M.WA, (int)type, (uint32_t)k, (uint32_t)n, 1, -1, w, nb))) return rc;
+  if (w_up && (rc = upload_matrix(t.c, M.WU, (int)type, (uint32_t)k, (uint32_t)n, 1, -1, w_up, nb))) return rc;
+  if (!mfma_type(M.WA.type)) return LGH_UNSUPPORTED;
+  M.role = w_up ? 2 : resid ? 1 : 0;
+  if (M.role && n % 256) return LGH_UNSUPPORTED;   // (hidden and ffn widths)
+  M.dnw = norm_w ? t.up(norm_w, k) : nullptr;
+  M.dbias = bias ? t.up(bias, n) : nullptr;
+  M.dnext = next_nw ? t.up(next_nw, n) : nullptr;
+  if ((norm_w && !M.dnw) || (bias && !M.dbias) || (next_nw && !M.dnext)) return LGH_ALLOCATION_FAILED;
+  MbShape s;
+  s.vocab = vocab;
+  if (M.role == 2) { s.H = k; s.F = n; }
+  else if (M.role == 1) { s.H = n; s.n_heads = s.n_kv = k / 64; }   // (the launch's input is [sequence][heads x head_dim] wide)
+  else { s.H = k; s.vocab = (n + 15) / 16 * 16; }
+  M.out_stride = M.role ? n : s.vocab;
+  if ((rc = mb_test_ctx(t, LayerW{}, s, eps, max_batch, false)) || (rc = mb_control(t, nullptr, nullptr, n_seq))) return rc;
+  const BatchScratch& Bs = t.c->batch;
+  M.in = M.role == 1 ? Bs.attn_out : Bs.hidden;
+  M.out = M.role == 2 ? Bs.act : M.role == 1 ? Bs.hidden : Bs.logits;
+  if (hipMemcpyAsync(M.in, x, n_seq * k * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  if (resid && hipMemcpyAsync(Bs.hidden, resid, n_seq * n * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  return mb_produce_images(t.c, M.in, (uint32_t)k, n_seq, M.dnw);
+}
+
+// launch A as enqueue_multi makes it
+static int mb_linear_launch(Tmp& t, MbLinear& M, size_t k, size_t n, size_t n_seq, int xq_next) {
+  SegSpec sp;
+  sp.W[0] = &M.WA; sp.x[0] = M.in; sp.out = M.out;
+  sp.xq_next = xq_next; sp.xq_next_nw = xq_next == 2 ? M.dnext : nullptr;
+  const bool img = xq_next != 0 && M.role != 0;
+  const uint32_t os[1] = {(uint32_t)M.out_stride}, rs[1] = {M.role == 1 ? (uint32_t)n : 0u}, xk[1] = {img ? (uint32_t)n : 0u};
+  int cls = LGH_K_OUTPUT;
+  if (M.role == 2) {
+    sp.npass = 2;
+    sp.W[1] = &M.WU;
+    sp.x[1] = M.in;
+    sp.epi = EPI_SWIGLU;
+    cls = LGH_K_GATEUP;
+  } else if (M.role == 1) {
+    sp.epi = EPI_RESID; sp.resid = M.out; sp.bias = M.dbias;
+    cls = LGH_K_WO;
+  } else {
+    sp.epi = EPI_STORE; sp.bias = M.dbias;
+  }
+  if (int rc = launch_mvb(t.c, cls, &sp, 1, M.dnw, (uint32_t)k, (uint32_t)n_seq, os, rs, xk)) return rc;
+  if (M.role) spread_state(t.c, M.out, (uint32_t)n, (uint32_t)n_seq);
+  return LGH_OK;
+}
+
+int lgh_op_linear_multi(int device, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, size_t n_seq,
+                        size_t max_batch, const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
+                        float* out, uint8_t* image_out, float* ssq_out, int* image_used, int* structures) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w || !x || !out || n_seq == 0 || n_seq > max_batch || max_batch > (size_t)kMaxBatch || xq_next < 0 || xq_next > 2 || (xq_next == 2 && !next_nw) ||
+      (w_up && (resid || bias)) || (!w_up && !resid && xq_next))
+    return LGH_INVALID_ARGUMENT;
+  MbLinear M;
+  int rc;
+  if ((rc = mb_linear_setup(t, M, type, w, w_up, bias, k, n, n_seq, max_batch, x, norm_w, eps, resid, next_nw, 16))) return rc;
+  uint64_t before[3];
+  lgh::mvqb_structure_launches(before);
+  if ((rc = mb_linear_launch(t, M, k, n, n_seq, xq_next))) return rc;
+  mb_structures(structures, before);
+  const XqBuf* qo = M.role ? xq_find(t.c, M.out) : nullptr;
+  const bool used = qo && qo->fresh;
+  if (image_used) *image_used = used ? 1 : 0;
+  // (the views of the sequences lie side by side: all max_batch of them come back, written or not)
+  if (qo && image_out && (rc = down_bytes(t, image_out, qo->xq, max_batch * xq_stride_of((uint32_t)n)))) return rc;
+  if (qo && ssq_out && (rc = t.down(ssq_out, qo->ssq, max_batch * ssq_stride_of((uint32_t)n)))) return rc;
+  return t.down(out, M.out, max_batch * M.out_stride);
+}
+
+int lgh_op_linear_chain_multi(int device, uint32_t type_a, const void* w_a, const void* w_a_up, const float* bias_a, size_t k, size_t n_a, size_t n_seq,
+                              size_t max_batch, const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
+                              uint32_t type_b, const void* w_b, size_t n_b, float* out_a, float* out_b, float* out_b_requant, int* image_used) {
+  // launch A (the SwiGLU pair, or a residual launch) leaving every sequence's image; then the store launch B on A's outputs twice: from
+  // A's images, then after marking them stale and producing them again with the engine's converter
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w_a || !x || !w_b || !out_a || !out_b || !out_b_requant || n_seq == 0 || n_seq > max_batch || max_batch > (size_t)kMaxBatch || xq_next < 1 ||
+      xq_next > 2 || (xq_next == 2 && !next_nw) || (w_a_up && (resid || bias_a)) || (!w_a_up && !resid))
+    return LGH_INVALID_ARGUMENT;
+  MbLinear M;
+  int rc;
+  if ((rc = mb_linear_setup(t, M, type_a, w_a, w_a_up, bias_a, k, n_a, n_seq, max_batch, x, norm_w, eps, resid, next_nw, n_b))) return rc;
+  const size_t nbb = weight_bytes(type_b, n_a, n_b);
+  if (!nbb) return LGH_SHAPE_MISMATCH;
+  DevWeight WB;
+  if ((rc = upload_matrix(t.c, WB, (int)type_b, (uint32_t)n_a, (uint32_t)n_b, 1, -1, w_b, nbb))) return rc;
+  if (!mfma_type(WB.type)) return LGH_UNSUPPORTED;
+  if ((rc = mb_linear_launch(t, M, k, n_a, n_seq, xq_next))) return rc;
+  const XqBuf* qa = xq_find(t.c, M.out);
+  if (image_used) *image_used = qa && qa->fresh ? 1 : 0;
+  const BatchScratch& Bs = t.c->batch;
+  const float* bnw = xq_next == 2 ? M.dnext : nullptr;
+  SegSpec sp;
+  sp.W[0] = &WB; sp.x[0] = M.out; sp.epi = EPI_STORE; sp.out = Bs.logits;
+  const uint32_t os[1] = {(uint32_t)n_b}, rs[1] = {0}, xk[1] = {0};
+  if ((rc = launch_mvb(t.c, LGH_K_OUTPUT, &sp, 1, bnw, (uint32_t)n_a, (uint32_t)n_seq, os, rs, xk))) return rc;
+  if ((rc = t.down(out_b, Bs.logits, n_seq * n_b))) return rc;
+  for (size_t s = 0; s < n_seq; s++) xq_stale(t.c, M.out + s * n_a);
+  if ((rc = mb_produce_images(t.c, M.out, (uint32_t)n_a, n_seq, bnw))) return rc;
+  if ((rc = launch_mvb(t.c, LGH_K_OUTPUT, &sp, 1, bnw, (uint32_t)n_a, (uint32_t)n_seq, os, rs, xk))) return rc;
+  if ((rc = t.down(out_b_requant, Bs.logits, n_seq * n_b))) return rc;
+  return t.down(out_a, M.out, n_seq * n_a);
+}
+
+int lgh_op_qkv_rope_multi(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                          float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t n_seq,
+                          size_t max_batch, const int* pos, const int* slot, float rope_base, float rope_scale, int staged, float* q_out,
+                          float* k_cache, float* v_cache, float* staged_out, int* structures) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!types || !w || !x || !norm_w || !pos || !slot || !q_out || (staged ? !staged_out : (!k_cache || !v_cache)) || hidden == 0 || head_dim == 0 ||
+      head_dim % 2 || n_kv_heads == 0 || n_heads % n_kv_heads || max_seq_len == 0 || max_seq_len > 0x7FFFFFFFu || rope_scale == 0.0f || n_seq == 0 ||
+      n_seq > max_batch || max_batch > (size_t)kMaxBatch)
+    return LGH_INVALID_ARGUMENT;
+  bool seen[kMaxBatch] = {};
+  for (size_t s = 0; s < n_seq; s++) {
+    if (pos[s] < 0 || (size_t)pos[s] >= max_seq_len || slot[s] < 0 || (size_t)slot[s] >= max_batch || seen[slot[s]]) return LGH_INVALID_ARGUMENT;
+    seen[slot[s]] = true;
+  }
+  const size_t QD = n_heads * head_dim, KD = n_kv_heads * head_dim, rows[3] = {QD, KD, KD};
+  if (hidden % 256 || QD % 256 || KD % 16 || !mvb_k_ok((uint32_t)hidden)) return LGH_UNSUPPORTED;
+  LayerW Lw;
+  DevWeight* const W[3] = {&Lw.wq, &Lw.wk, &Lw.wv};
+  float** const db[3] = {&Lw.bq, &Lw.bk, &Lw.bv};
+  int rc;
+  for (int s = 0; s < 3; s++) {
+    const size_t nb = weight_bytes(types[s], hidden, rows[s]);
+    if (!nb || !w[s]) return LGH_SHAPE_MISMATCH;
+    if ((rc = upload_matrix(t.c, *W[s], (int)types[s], (uint32_t)hidden, (uint32_t)rows[s], 1, -1, w[s], nb))) return rc;
+    if (!mfma_type(W[s]->type)) return LGH_UNSUPPORTED;
+    if (bias && bias[s] && !(*db[s] = t.up(bias[s], rows[s]))) return LGH_ALLOCATION_FAILED;
+  }
+  Lw.attn_norm = t.up(norm_w, hidden);
+  if (!Lw.attn_norm) return LGH_ALLOCATION_FAILED;
+  MbShape sh;
+  sh.H = hidden; sh.head_dim = head_dim; sh.n_heads = n_heads; sh.n_kv = n_kv_heads; sh.max_seq = max_seq_len;
+  if ((rc = mb_test_ctx(t, Lw, sh, eps, max_batch, staged != 0)) || (rc = mb_control(t, pos, slot, n_seq))) return rc;
+  lgh_model_desc& d = t.c->d;
+  d.rope_freq_base = rope_base;
+  d.rope_freq_scale = rope_scale;
+  std::vector<float> cs;
+  rope_table_host(d, cs);
+  if (!(t.c->rope_cs = t.up(cs.data(), cs.size()))) return LGH_ALLOCATION_FAILED;
+  const BatchScratch& Bs = t.c->batch;
+  if (hipMemcpyAsync(Bs.hidden, x, n_seq * hidden * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  if ((rc = mb_produce_images(t.c, Bs.hidden, (uint32_t)hidden, n_seq, Lw.attn_norm))) return rc;
+  uint64_t before[3];
+  lgh::mvqb_structure_launches(before);
+  if ((rc = qkv_forward_multi(t.c, t.c->layers[0], 0, (uint32_t)n_seq))) return rc;
+  mb_structures(structures, before);
+  if ((rc = t.down(q_out, Bs.q, max_batch * QD))) return rc;
+  if (staged) return t.down(staged_out, Bs.kv_tmp, max_batch * 2 * KD);
+  if ((rc = t.down(k_cache, Bs.kcache[0], max_batch * Bs.cache_stride))) return rc;
+  return t.down(v_cache, Bs.vcache[0], max_batch * Bs.cache_stride);
+}
+
+int lgh_op_moe_multi(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down, size_t n_experts,
+                     size_t hidden, size_t ffn, size_t top_k, size_t n_seq, size_t max_batch, const float* router, const int* sel, const float* sel_w,
+                     const float* x, const float* norm_w, const float* next_nw, float eps, float* out, uint8_t* image_out, float* ssq_out,
+                     uint8_t* image_requant, float* ssq_requant, int* sel_out, float* sel_w_out, int* cnt_out, int* idx_out, int* structures) {
+  // the grouped MoE half of a step on x [n_seq][hidden] (also the residual): with `router` the device router picks every sequence's
+  // experts, otherwise the given selections and weights [n_seq][top_k] drive the same launches
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w_gate || !w_up || !w_down || !x || !norm_w || !next_nw || !out || !image_out || !ssq_out || !image_requant || !ssq_requant || !cnt_out ||
+      !idx_out || (!router && (!sel || !sel_w)) || top_k == 0 || top_k > 8 || top_k > n_experts || n_experts > 64 || n_seq < 2 || n_seq > max_batch ||
+      max_batch > (size_t)kMaxBatch)
+    return LGH_INVALID_ARGUMENT;
+  for (size_t s = 0; sel && !router && s < n_seq; s++)   // (a sequence selects an expert at most once: an expert's list holds <= n_seq pairs)
+    for (size_t i = 0; i < top_k; i++) {
+      if (sel[s * top_k + i] < 0 || (size_t)sel[s * top_k + i] >= n_experts) return LGH_INVALID_ARGUMENT;
+      for (size_t j = 0; j < i; j++)
+        if (sel[s * top_k + j] == sel[s * top_k + i]) return LGH_INVALID_ARGUMENT;
+    }
+  const size_t H = hidden, E = n_experts;
+  if (H % 256 || ffn % 256) return LGH_UNSUPPORTED;
+  const size_t ngu = weight_bytes(type_gate_up, H, ffn), nd = weight_bytes(type_down, ffn, H);
+  if (!ngu || !nd) return LGH_SHAPE_MISMATCH;
+  LayerW Lw;
+  int rc;
+  if ((rc = upload_matrix(t.c, Lw.gate_exps, (int)type_gate_up, (uint32_t)H, (uint32_t)ffn, (uint32_t)E, -1, w_gate, ngu * E)) ||
+      (rc = upload_matrix(t.c, Lw.up_exps, (int)type_gate_up, (uint32_t)H, (uint32_t)ffn, (uint32_t)E, -1, w_up, ngu * E)) ||
+      (rc = upload_matrix(t.c, Lw.down_exps, (int)type_down, (uint32_t)ffn, (uint32_t)H, (uint32_t)E, -1, w_down, nd * E)))
+    return rc;
+  if (!mfma_type(Lw.gate_exps.type) || !mfma_type(Lw.down_exps.type)) return LGH_UNSUPPORTED;
+  Lw.ffn_norm = t.up(norm_w, H);
+  Lw.router = t.up(router, E * H);   // (without a router matrix: what makes the layer an MoE layer for the scratch; never read)
+  float* dnext = t.up(next_nw, H);
+  if (!Lw.ffn_norm || !Lw.router || !dnext) return LGH_ALLOCATION_FAILED;
+  MbShape sh;
+  sh.H = H; sh.n_heads = sh.n_kv = H / 64; sh.E = E; sh.top_k = top_k; sh.EI = ffn;
+  if ((rc = mb_test_ctx(t, Lw, sh, eps, max_batch, false)) || (rc = mb_control(t, nullptr, nullptr, n_seq))) return rc;
+  const BatchScratch& Bs = t.c->batch;
+  if (!Bs.moe_act) return LGH_UNSUPPORTED;   // (the shape does not group: the engine runs such layers sequence by sequence)
+  if (hipMemcpyAsync(Bs.hidden, x, n_seq * H * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  if (!router && (hipMemcpyAsync(Bs.moe_sel, sel, n_seq * top_k * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+                  hipMemcpyAsync(Bs.moe_w, sel_w, n_seq * top_k * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess))
+    return LGH_OPERATION_FAILED;
+  if ((rc = mb_produce_images(t.c, Bs.hidden, (uint32_t)H, n_seq, Lw.ffn_norm))) return rc;   // (as wo's epilogue leaves them)
+  uint64_t before[3];
+  lgh::mvqb_structure_launches(before);
+  if ((rc = moe_grouped_forward(t.c, t.c->layers[0], (uint32_t)n_seq, dnext, router != nullptr))) return rc;
+  mb_structures(structures, before);
+  // the new rows' images once more, by the engine's converter, for comparison with what the combine launch left
+  const size_t xs = xq_stride_of((uint32_t)H), ss = ssq_stride_of((uint32_t)H);
+  uint8_t* xq2 = (uint8_t*)up_bytes(t, nullptr, max_batch * xs);
+  float* ssq2 = t.up(nullptr, max_batch * ss);
+  if (!xq2 || !ssq2 || !pf_poison(t.c, xq2, max_batch * xs, 0x7FC0BEEFu) || !pf_poison(t.c, ssq2, max_batch * ss * 4, 0x7FC0BEEFu)) return LGH_ALLOCATION_FAILED;
+  for (size_t s = 0; s < n_seq; s++)
+    if (xq_quantize_launch(Bs.hidden + s * H, dnext, xq2 + s * xs, ssq2 + s * ss, (uint32_t)H, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
+  const XqBuf* qh = xq_find(t.c, Bs.hidden);
+  if ((rc = down_bytes(t, image_out, qh->xq, max_batch * xs)) || (rc = t.down(ssq_out, qh->ssq, max_batch * ss)) ||
+      (rc = down_bytes(t, image_requant, xq2, max_batch * xs)) || (rc = t.down(ssq_requant, ssq2, max_batch * ss)) ||
+      (rc = down_bytes(t, cnt_out, Bs.moe_cnt, 64 * 4)) || (rc = down_bytes(t, idx_out, Bs.moe_idx, (size_t)64 * kMaxBatch * 4)))
+    return rc;
+  if (sel_out && (rc = down_bytes(t, sel_out, Bs.moe_sel, n_seq * top_k * 4))) return rc;
+  if (sel_w_out && (rc = t.down(sel_w_out, Bs.moe_w, n_seq * top_k))) return rc;
+  return t.down(out, Bs.hidden, max_batch * H);
 }
 
 }  // extern "C"

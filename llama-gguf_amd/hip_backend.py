@@ -42,6 +42,7 @@ ABI_SYMBOLS = (
     "lgh_op_attention_decode", "lgh_op_attention_decode_multi", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
     "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches",
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
+    "lgh_op_linear_multi", "lgh_op_linear_chain_multi", "lgh_op_qkv_rope_multi", "lgh_op_moe_multi", "lgh_debug_mvqb_structures",
     "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_attention_kv8_multi",
 )
 
@@ -243,6 +244,13 @@ def load_library() -> C.CDLL:
         "lgh_op_linear_chain": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, f32, vp, C.c_int, vp, u32, vp, sz, vp, vp, vp,
                                           C.POINTER(C.c_int)]),
         "lgh_op_moe_experts": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
+        "lgh_op_linear_multi": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, sz, sz, vp, vp, f32, vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
+        "lgh_op_linear_chain_multi": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, sz, sz, vp, vp, f32, vp, C.c_int, vp, u32, vp, sz, vp, vp, vp,
+                                                C.POINTER(C.c_int)]),
+        "lgh_op_qkv_rope_multi": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, sz, sz, sz, vp, vp, f32, f32, C.c_int, vp, vp, vp, vp, vp]),
+        "lgh_op_moe_multi": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, sz, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp,
+                                       vp, vp, vp]),
+        "lgh_debug_mvqb_structures": (None, [vp]),
         "lgh_op_pf_qkv": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, C.c_int, sz, sz, sz, f32, f32, vp, vp, vp]),
         "lgh_op_pf_linear": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, sz, vp, vp, vp]),
         "lgh_op_pf_ffn": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, vp, vp, vp, f32, sz, sz, sz, vp, vp, vp, vp]),
@@ -836,6 +844,119 @@ def op_moe_experts(type_gate_up: int, w_gate, w_up, type_down: int, w_down, n_ex
                                            hidden, ffn, top_k, _ptr(r), _ptr(s), _ptr(sw), x.ctypes.data, nw.ctypes.data, eps,
                                            out.ctypes.data, so.ctypes.data, swo.ctypes.data), "moe_experts")
     return out, so, swo
+
+
+# ---- the multi-sequence step's launches, one at a time (lgh_op_*_multi)
+MAX_BATCH = 16                                       # kMaxBatch
+MV_STRUCTURES = ("mvqb", "mvqb2 split", "mvqb2 seq")  # lgh_debug_mvqb_structures' order
+
+
+def _structure(counts) -> str:
+    """The one structure the launches of a call ran as ('mixed: ...' when they differ)."""
+    ran = [MV_STRUCTURES[i] for i in range(3) if counts[i]]
+    return ran[0] if len(ran) == 1 else "mixed: %s" % list(counts)
+
+
+def _xq_bytes(n: int) -> int:
+    return (n + 255) // 256 * 1280
+
+
+def mvqb_structures():
+    """Multi-sequence mat-vec launches of this process so far, per structure (MV_STRUCTURES' order)."""
+    out = np.zeros(3, np.uint64)
+    load_library().lgh_debug_mvqb_structures(out.ctypes.data)
+    return [int(v) for v in out]
+
+
+def op_linear_multi(ggml_type: int, w, k: int, n: int, x, *, max_batch: int = MAX_BATCH, w_up=None, bias=None, norm_w=None, eps: float = 1e-5,
+                    resid=None, xq_next: int = 0, next_nw=None, device: int = 0):
+    """One multi-sequence launch on x [n_seq, k] as the step assembles it: the SwiGLU pair (w_up), a residual launch (resid [n_seq, n], + bias)
+    or a store.  -> dict(out [max_batch, n], pad (a store: the floats between row n and the next sequence's row 0), image [max_batch, bytes] / ssq [max_batch, n / 16] (None without image slots), used,
+    structure, counts); rows of sequences >= n_seq come back as the scratch held them (the NaN pattern 0x7FC0BEEF)."""
+    x = _f32(x)
+    n_seq = x.shape[0]
+    wa = np.ascontiguousarray(w, dtype=np.uint8)
+    wu = None if w_up is None else np.ascontiguousarray(w_up, dtype=np.uint8)
+    ba, nw, rs, nn = (None if v is None else _f32(v) for v in (bias, norm_w, resid, next_nw))
+    slots = w_up is not None or resid is not None
+    out = np.empty((max_batch, n if slots else (n + 15) // 16 * 16), np.float32)   # (a store's rows lie a whole number of tiles apart)
+    img = np.zeros((max_batch, _xq_bytes(n)), np.uint8) if slots else None
+    ssq = np.zeros((max_batch, n // 16 + 64), np.float32) if slots else None
+    used, counts = C.c_int(0), np.zeros(3, np.int32)
+    _chk(load_library().lgh_op_linear_multi(device, ggml_type, wa.ctypes.data, _ptr(wu), _ptr(ba), k, n, n_seq, max_batch, x.ctypes.data, _ptr(nw),
+                                            eps, _ptr(rs), xq_next, _ptr(nn), out.ctypes.data, _ptr(img), _ptr(ssq), C.byref(used),
+                                            counts.ctypes.data), "linear_multi")
+    return {"out": out[:, :n], "pad": out[:, n:], "image": img, "ssq": None if ssq is None else ssq[:, :n // 16], "used": bool(used.value),
+            "structure": _structure(counts), "counts": [int(v) for v in counts]}
+
+
+def op_linear_chain_multi(type_a: int, w_a, k: int, n_a: int, x, type_b: int, w_b, n_b: int, *, max_batch: int = MAX_BATCH, w_a_up=None,
+                          bias_a=None, norm_w=None, eps: float = 1e-5, resid=None, xq_next: int = 1, next_nw=None, device: int = 0):
+    """op_linear_chain for x [n_seq, k]: A (SwiGLU pair or residual launch) leaves every sequence's image, B (store) runs from them and again
+    after a fresh conversion.  -> (out_a [n_seq, n_a], out_b, out_b_requant [n_seq, n_b], image_used)."""
+    x = _f32(x)
+    n_seq = x.shape[0]
+    wa, wb = np.ascontiguousarray(w_a, dtype=np.uint8), np.ascontiguousarray(w_b, dtype=np.uint8)
+    wu = None if w_a_up is None else np.ascontiguousarray(w_a_up, dtype=np.uint8)
+    ba, nw, rs, nn = (None if v is None else _f32(v) for v in (bias_a, norm_w, resid, next_nw))
+    oa, ob, ob2 = np.empty((n_seq, n_a), np.float32), np.empty((n_seq, n_b), np.float32), np.empty((n_seq, n_b), np.float32)
+    used = C.c_int(-1)
+    _chk(load_library().lgh_op_linear_chain_multi(device, type_a, wa.ctypes.data, _ptr(wu), _ptr(ba), k, n_a, n_seq, max_batch, x.ctypes.data,
+                                                  _ptr(nw), eps, _ptr(rs), xq_next, _ptr(nn), type_b, wb.ctypes.data, n_b, oa.ctypes.data,
+                                                  ob.ctypes.data, ob2.ctypes.data, C.byref(used)), "linear_chain_multi")
+    return oa, ob, ob2, bool(used.value)
+
+
+def op_qkv_rope_multi(types, ws, biases, x, norm_w, eps: float, head_dim: int, n_heads: int, n_kv: int, max_seq: int, pos, slot,
+                      rope_base: float, rope_scale: float, *, max_batch: int = MAX_BATCH, staged: bool = False, device: int = 0):
+    """The step's QKV launch(es) on x [n_seq, hidden]: sequence s rotated at pos[s], its K / V rows into row pos[s] of cache slot slot[s].
+    -> dict(q [max_batch, n_heads * head_dim], k / v [max_batch, n_kv, max_seq, head_dim] (f32 caches) or staged [max_batch, 2, n_kv *
+    head_dim] (the quantized caches' variant), structure, counts)."""
+    x, nw = _f32(x), _f32(norm_w)
+    n_seq, hidden = x.shape
+    ws = [np.ascontiguousarray(w, dtype=np.uint8) for w in ws]
+    bs = [None if b is None else _f32(b) for b in biases]
+    tarr = np.array(types, dtype=np.uint32)
+    warr = (C.c_void_p * 3)(*[w.ctypes.data for w in ws])
+    barr = (C.c_void_p * 3)(*[_ptr(b) for b in bs])
+    p, s = np.ascontiguousarray(pos, dtype=np.int32), np.ascontiguousarray(slot, dtype=np.int32)
+    q = np.empty((max_batch, n_heads * head_dim), np.float32)
+    kc = vc = st = None
+    if staged:
+        st = np.empty((max_batch, 2, n_kv * head_dim), np.float32)
+    else:
+        kc, vc = np.empty((max_batch, n_kv, max_seq, head_dim), np.float32), np.empty((max_batch, n_kv, max_seq, head_dim), np.float32)
+    counts = np.zeros(3, np.int32)
+    _chk(load_library().lgh_op_qkv_rope_multi(device, tarr.ctypes.data, C.cast(warr, C.c_void_p), C.cast(barr, C.c_void_p), x.ctypes.data,
+                                              nw.ctypes.data, eps, hidden, head_dim, n_heads, n_kv, max_seq, n_seq, max_batch, p.ctypes.data,
+                                              s.ctypes.data, rope_base, rope_scale, int(staged), q.ctypes.data, _ptr(kc), _ptr(vc), _ptr(st),
+                                              counts.ctypes.data), "qkv_rope_multi")
+    return {"q": q, "k": kc, "v": vc, "staged": st, "structure": _structure(counts), "counts": [int(v) for v in counts]}
+
+
+def op_moe_multi(type_gate_up: int, w_gate, w_up, type_down: int, w_down, n_experts: int, hidden: int, ffn: int, top_k: int, x, norm_w, next_nw,
+                 eps: float, *, max_batch: int = MAX_BATCH, router=None, sel=None, sel_w=None, device: int = 0):
+    """The grouped MoE half of a step on x [n_seq, hidden]: device router (router [E, hidden]) or the given sel / sel_w [n_seq, top_k].
+    -> dict(out [max_batch, hidden], image / ssq as the combine launch left them, image_requant / ssq_requant as the engine's converter
+    makes them from out, sel, sel_w [n_seq, top_k], cnt [64], idx [64, 16], counts)."""
+    x, nw, nn = _f32(x), _f32(norm_w), _f32(next_nw)
+    n_seq = x.shape[0]
+    wg, wu, wd = (np.ascontiguousarray(w, dtype=np.uint8) for w in (w_gate, w_up, w_down))
+    r = None if router is None else _f32(router)
+    s = None if sel is None else np.ascontiguousarray(sel, dtype=np.int32)
+    sw = None if sel_w is None else _f32(sel_w)
+    out = np.empty((max_batch, hidden), np.float32)
+    img, img2 = (np.zeros((max_batch, _xq_bytes(hidden)), np.uint8) for _ in range(2))
+    ssq, ssq2 = (np.zeros((max_batch, hidden // 16 + 64), np.float32) for _ in range(2))
+    so, swo = np.empty((n_seq, top_k), np.int32), np.empty((n_seq, top_k), np.float32)
+    cnt, idx, counts = np.empty(64, np.int32), np.empty((64, MAX_BATCH), np.int32), np.zeros(3, np.int32)
+    _chk(load_library().lgh_op_moe_multi(device, type_gate_up, wg.ctypes.data, wu.ctypes.data, type_down, wd.ctypes.data, n_experts, hidden, ffn,
+                                         top_k, n_seq, max_batch, _ptr(r), _ptr(s), _ptr(sw), x.ctypes.data, nw.ctypes.data, nn.ctypes.data, eps,
+                                         out.ctypes.data, img.ctypes.data, ssq.ctypes.data, img2.ctypes.data, ssq2.ctypes.data, so.ctypes.data,
+                                         swo.ctypes.data, cnt.ctypes.data, idx.ctypes.data, counts.ctypes.data), "moe_multi")
+    h16 = hidden // 16
+    return {"out": out, "image": img, "ssq": ssq[:, :h16], "image_requant": img2, "ssq_requant": ssq2[:, :h16], "sel": so, "sel_w": swo,
+            "cnt": cnt, "idx": idx, "counts": [int(v) for v in counts]}
 
 
 PF_SSQ_CHUNKS = 8      # kPfSsqChunks: sums of squares per token, one per 2048 columns

@@ -20,6 +20,10 @@ def _engines(pkg, name, mix, max_seq=96, n_single=1, **kw):
         name, kw = "test-moe", dict(kw, expert_intermediate_size=1024)
     if name == "test-moe-e1024-k4":   # four of eight experts per token (the grouped step's entry lists hold up to 4 pairs per sequence)
         name, kw = "test-moe", dict(kw, expert_intermediate_size=1024, num_experts=8, num_experts_per_token=4)
+    if name == "test-moe-h2048":
+        # hidden 2048 (8 k-slices) with 8 experts of 2048 on the split grid: the widest partial-sum region per sequence an expert-grouped
+        # gate | up launch asks for (8 experts x 8 slices x 2 x 2048), at a full batch; one layer, small vocabulary
+        name, kw = "test-moe", dict(kw, hidden_size=2048, expert_intermediate_size=2048, num_experts=8, num_layers=1, vocab_size=256)
     if name == "mixtral-8x7b-3l":
         # Mixtral's own widths (8 experts of 14336, hidden 4096, vocabulary cut to 4096 for the test's run time), three layers — one
         # Q6_K and two Q5_K down projections under Q5_K_M: the expert-grouped step on the launch plans the full model runs with
@@ -46,6 +50,7 @@ def _history(cfg, seq, n):
                                         ("test-moe", "Q5_K_M", 3), ("test-moe", "Q4_K_M", 16),
                                         ("test-moe-e1024", "Q5_K_M", 3), ("test-moe-e1024", "Q4_K_M", 16), ("test-moe-e1024", "Q8_0", 7),
                                         ("test-moe-e1024-k4", "Q5_K_M", 5), ("test-moe-e1024-k4", "Q4_K_M", 16),
+                                        ("test-moe-h2048", "Q4_K_M", 16),
                                         ("mixtral-8x7b-3l", "Q5_K_M", 6), ("mixtral-8x7b-3l", "Q5_K_M", 16)])
 def test_every_sequence_gets_the_single_sequence_logits_bitwise(pkg, name, mix, B):
     """B sequences with different histories and RAGGED lengths, token by token through lgh_forward_multi; each sequence's logits
