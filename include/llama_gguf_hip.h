@@ -434,6 +434,54 @@ int lgh_pipeline_kv_truncate(lgh_pipeline* p, size_t new_len);                  
 int lgh_pipeline_stages(const lgh_pipeline* p);
 const char* lgh_pipeline_last_error(const lgh_pipeline* p);
 
+/* ---- tensor-parallel decode inside the library: ONE process, n_ranks (1..8) rank contexts on the given devices (device_ids may
+ * repeat a device — the single-device rehearsal; NULL: all on desc->device_id).  The scheme is the reference's
+ * (src/backend/tensor_parallel.rs:1-6): attention heads split over the ranks, ffn_gate / ffn_up by output rows, attn_output /
+ * ffn_down by input (k), a sum over the ranks after each — here one kernel per rank that also adds the residual
+ * (layers.rs:1201-1208) and leaves the next mat-vec's input image.  Every rank reads 1/N of a layer's weight bytes for the same
+ * token, so this is the structure in which more GPUs make ONE stream faster.  Ranks on one device share one stream and the token
+ * is one linear captured graph; ranks on distinct devices run eagerly on their own streams with events and peer-mapped buffers
+ * (NOT executed so far: the development box has one GPU).  The entry points mirror the single-context ones (GpuInference,
+ * src/backend/mod.rs:283-296), so GpuModelWrapper drives a handle unchanged.
+ *
+ * lgh_tp_create is ShardingPlan::from_config (tensor_parallel.rs:69-106): InvalidArgument "num_heads (..) must be divisible by
+ * world_size (..)" (likewise num_kv_heads, ffn_dim), n_ranks outside 1..8, or a layer_begin / layer_end range; Unsupported for
+ * MoE models, a kv_cache_type other than f32, and widths (num_heads / N) * head_dim, intermediate_size / N or hidden_size that
+ * are not multiples of 256 (the k-shards are whole 256-element blocks).  lgh_tp_upload_tensor answers Unsupported for a 2-D
+ * weight outside the matrix-core tile layouts (Q4_K, Q5_K, Q6_K, Q8_0, Q4_0 with k % 256 == 0).  Why a create failed:
+ * lgh_tp_last_error(NULL), per thread.  Quantized caches, MoE, the batched prompt pass, sampling and multi-sequence slots over
+ * tensor parallelism are not built. ---- */
+typedef struct lgh_tp lgh_tp;
+int lgh_tp_create(const lgh_model_desc* desc, const int* device_ids, int n_ranks, lgh_tp** out);   /* TPConfig + ShardingPlan::from_config */
+/* the WHOLE tensor, as lgh_pipeline_upload_tensor takes it; every rank gets its part through lgh_tp_shard (in place of
+ * shard_weight, tensor_parallel.rs:115-, which refuses quantized tensors) */
+int lgh_tp_upload_tensor(lgh_tp* tp, const char* gguf_name, uint32_t ggml_type, const uint64_t ne[4], const void* data, size_t nbytes);
+int lgh_tp_finalize(lgh_tp* tp);
+void lgh_tp_destroy(lgh_tp* tp);
+int lgh_tp_forward(lgh_tp* tp, uint32_t token_id, float* logits_out);          /* GpuInference::forward */
+int lgh_tp_prefill_token(lgh_tp* tp, uint32_t token_id);                       /* GpuInference::prefill_token */
+int lgh_tp_decode_greedy(lgh_tp* tp, uint32_t first_token, size_t n_steps, uint32_t* tokens_out);   /* lgh_decode_greedy over the ranks */
+void lgh_tp_reset(lgh_tp* tp);                                                 /* GpuInference::reset */
+size_t lgh_tp_position(const lgh_tp* tp);                                      /* GpuInference::position */
+int lgh_tp_kv_truncate(lgh_tp* tp, size_t new_len);                            /* KVCache::truncate on every rank */
+int lgh_tp_ranks(const lgh_tp* tp);                                            /* TensorParallel::world_size */
+uint64_t lgh_tp_graph_nodes(const lgh_tp* tp);   /* nodes of the captured token graph (0 before the first replay, and on distinct devices) */
+const char* lgh_tp_last_error(const lgh_tp* tp);
+/* Host only, no device needed: rank `rank`'s shard of a [ne1 rows][ne0 elements] tensor in GGUF order (shard_weight's job, for
+ * quantized payloads too).  axis 0 = rows (out features): a contiguous row range — ne1 / n_ranks rows where n_ranks divides ne1
+ * (whole heads, FFN columns), otherwise the same number of whole 16-row tiles for every rank and the remainder to the last one
+ * (output.weight).  axis 1 = k (in features): blocks [rank * k / (n * bs), (rank + 1) * k / (n * bs)) of every row; k must hold
+ * whole 256-element blocks per rank (Unsupported otherwise).  rank >= n_ranks or dst_bytes too small: InvalidArgument.
+ * *written = the shard's bytes; nothing past them is touched, and nothing at all when the call is refused. */
+int lgh_tp_shard(uint32_t ggml_type, const uint64_t ne[4], int axis, int rank, int n_ranks, const void* src, size_t src_bytes, void* dst,
+                 size_t dst_bytes, size_t* written);
+/* The synchronisation-point kernel on its own (TensorParallel::all_reduce_sum + the residual add, host tensors in and out):
+ * out = resid + (((p0 + p1) + p2) ...) over the n partial vectors [n][H] in rank order (resid NULL: the sum alone); with
+ * xq_image also the matrix-core input image of out * norm_w (norm_w NULL: of out), and with ssq_parts the H / 16 per-chunk sums
+ * of out^2.  H % 16 == 0.  out, xq_image and ssq_parts are in / out: bytes the kernel does not write keep the caller's. */
+int lgh_op_tp_reduce(int device, const float* partials, uint32_t n, const float* resid, const float* norm_w, size_t H, float* out,
+                     uint8_t* xq_image, float* ssq_parts);
+
 /* ---- per-op surface: the `Backend` trait ops on the path (src/backend/mod.rs:29-265), host tensors
  * in / host tensors out, for parity tests of each kernel against the CPU backend. ---- */
 int lgh_op_dequantize(int device, uint32_t ggml_type, const void* src, size_t n_elems, float* dst);

@@ -198,6 +198,8 @@ int qkv_forward(lgh_ctx* c, lgh::LayerW& Lw, const AttnView& v);   // norm -> q,
 // leave attn_out's XQ image, where the path's last launch can write one
 int attention_forward(lgh_ctx* c, lgh::LayerW& Lw, uint32_t li, const AttnView& v, float scale, bool xq_out);
 int ffn_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma);
+int ffn_gateup_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v);   // the dense FFN up to v.act (gate | up + SwiGLU), no down projection
+int embed_forward(lgh_ctx* c);   // the token's embedding row into c->hidden, the position advanced
 int moe_experts_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma);   // given v.moe_sel / v.moe_w
 void rope_table_host(const lgh_model_desc& d, std::vector<float>& cs);
 int engine_shape_check(const lgh_model_desc& d, std::string& why);   // LGH_OK, or the status lgh_create returns and why

@@ -34,27 +34,34 @@ void rope_table_host(const lgh_model_desc& d, std::vector<float>& cs) {
 // (moe.rs:321-413), residual included.  The single-sequence path passes the context's own buffers; the multi-sequence path
 // (engine_batch.hip) runs MoE layers through here sequence by sequence — every sequence selects its own experts.
 // ------------------------------------------------------------------------------------------------
+// The dense FFN up to its activation: v.act = silu(gate x') * (up x'), x' = RMSNorm(v.hidden) with ffn_norm (layers.rs:908-925).  What
+// follows is the down projection — ffn_forward's, with the residual, or a tensor-parallel rank's over its k-shard (tensor_parallel.hip).
+int ffn_gateup_forward(lgh_ctx* c, LayerW& Lw, const FfnView& v) {
+  int rc;
+  if (fused_type(Lw.gate.type) && Lw.gate.type == Lw.up.type) {  // FeedForward::forward (layers.rs:908-929)
+    SegSpec sp;
+    sp.npass = 2;
+    sp.W[0] = &Lw.gate; sp.W[1] = &Lw.up;
+    sp.x[0] = sp.x[1] = v.hidden;
+    sp.epi = EPI_SWIGLU;
+    sp.out = v.act;
+    sp.xq_next = mfma_type(Lw.down.type) ? 1 : 0;
+    return launch_mv(c, LGH_K_GATEUP, &sp, 1, Lw.ffn_norm, c->d.hidden_size);
+  }
+  if ((rc = linear_any(c, LGH_K_GATEUP, Lw.gate, v.hidden, v.act, Lw.ffn_norm, nullptr, nullptr))) return rc;
+  if ((rc = linear_any(c, LGH_K_GATEUP, Lw.up, v.hidden, v.act2, Lw.ffn_norm, nullptr, nullptr))) return rc;
+  if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] { return silu_mul_launch(v.act, v.act2, v.act, Lw.gate.n, c->stream); }))) return rc;
+  xq_stale(c, v.act);
+  return LGH_OK;
+}
+
 int ffn_forward(lgh_ctx* c, LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma) {
   const lgh_model_desc& d = c->d;
   const uint32_t H = d.hidden_size;
   int rc;
   // ---- FFN
   if (!Lw.moe()) {
-    if (fused_type(Lw.gate.type) && Lw.gate.type == Lw.up.type) {  // FeedForward::forward (layers.rs:908-929)
-      SegSpec sp;
-      sp.npass = 2;
-      sp.W[0] = &Lw.gate; sp.W[1] = &Lw.up;
-      sp.x[0] = sp.x[1] = v.hidden;
-      sp.epi = EPI_SWIGLU;
-      sp.out = v.act;
-      sp.xq_next = mfma_type(Lw.down.type) ? 1 : 0;
-      if ((rc = launch_mv(c, LGH_K_GATEUP, &sp, 1, Lw.ffn_norm, H))) return rc;
-    } else {
-      if ((rc = linear_any(c, LGH_K_GATEUP, Lw.gate, v.hidden, v.act, Lw.ffn_norm, nullptr, nullptr))) return rc;
-      if ((rc = linear_any(c, LGH_K_GATEUP, Lw.up, v.hidden, v.act2, Lw.ffn_norm, nullptr, nullptr))) return rc;
-      if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] { return silu_mul_launch(v.act, v.act2, v.act, Lw.gate.n, c->stream); }))) return rc;
-      xq_stale(c, v.act);
-    }
+    if ((rc = ffn_gateup_forward(c, Lw, v))) return rc;
     return linear_any(c, LGH_K_DOWN, Lw.down, v.act, v.hidden, nullptr, v.hidden, nullptr, next_mfma ? 2 : 0, next_nw);
   }
   // ---- MoE (moe.rs:321-413): router + top-k on device, experts selected by device-side index
@@ -236,25 +243,32 @@ static int layer_forward(lgh_ctx* c, uint32_t li, const float* next_nw, bool nex
   return ffn_forward(c, Lw, FfnView{c->hidden, c->act, c->act2, c->xnorm, c->moe_sel, c->moe_w}, next_nw, next_mfma);
 }
 
+// Opens a token on a context that holds the embedding table: the row of the token in the device state into c->hidden (and the position
+// advanced), and — when the first layer's QKV runs on the matrix cores — its XQ image with that layer's norm weights
+int embed_forward(lgh_ctx* c) {
+  const lgh_model_desc& d = c->d;
+  XqBuf* qh = nullptr;
+  const float* nw0 = nullptr;
+  if (c->l0 < c->l1 && mfma_type(c->layers[c->l0].wq.type) && d.hidden_size % 256 == 0) {
+    qh = xq_get(c, c->hidden, d.hidden_size);
+    nw0 = c->layers[c->l0].attn_norm;
+  }
+  if (int rc = run_k(c, LGH_K_EMBED, LGH_SYM_EMBED, (uint64_t)d.hidden_size * blk_bytes(c->embd_type) / blk_elems(c->embd_type), [&] {
+        return embed_launch(c->embd_type, c->embd_raw, c->state + ST_TOKEN, c->hidden, d.hidden_size, c->state,
+                            qh ? qh->xq : nullptr, nw0, qh ? qh->ssq : nullptr, c->stream);
+      }))
+    return rc;
+  if (qh) { qh->fresh = true; qh->tag = nw0; }
+  return LGH_OK;
+}
+
 // Everything one token needs, in stream order.  Used eagerly and under graph capture.
 int enqueue_token(lgh_ctx* c, int mode) {
   const lgh_model_desc& d = c->d;
   int rc;
   for (auto& q : c->xqs) q.fresh = false;   // the residual stream is (re)written in f32 now (embedding / previous stage)
   if (c->first) {
-    // the embedding row, and — when the first layer's QKV runs on the matrix cores — its XQ image with that layer's norm weights
-    XqBuf* qh = nullptr;
-    const float* nw0 = nullptr;
-    if (c->l0 < c->l1 && mfma_type(c->layers[c->l0].wq.type) && d.hidden_size % 256 == 0) {
-      qh = xq_get(c, c->hidden, d.hidden_size);
-      nw0 = c->layers[c->l0].attn_norm;
-    }
-    if ((rc = run_k(c, LGH_K_EMBED, LGH_SYM_EMBED, (uint64_t)d.hidden_size * blk_bytes(c->embd_type) / blk_elems(c->embd_type), [&] {
-           return embed_launch(c->embd_type, c->embd_raw, c->state + ST_TOKEN, c->hidden, d.hidden_size, c->state,
-                               qh ? qh->xq : nullptr, nw0, qh ? qh->ssq : nullptr, c->stream);
-         })))
-      return rc;
-    if (qh) { qh->fresh = true; qh->tag = nw0; }
+    if ((rc = embed_forward(c))) return rc;
   } else {
     if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] { return advance_launch(c->state, c->stream); }))) return rc;
   }

@@ -35,6 +35,8 @@ ABI_SYMBOLS = (
     "lgh_pipeline_create", "lgh_pipeline_upload_tensor", "lgh_pipeline_finalize", "lgh_pipeline_destroy", "lgh_pipeline_forward",
     "lgh_pipeline_prefill_token", "lgh_pipeline_decode_greedy", "lgh_pipeline_reset", "lgh_pipeline_position", "lgh_pipeline_kv_truncate", "lgh_pipeline_stages",
     "lgh_pipeline_last_error",
+    "lgh_tp_create", "lgh_tp_upload_tensor", "lgh_tp_finalize", "lgh_tp_destroy", "lgh_tp_forward", "lgh_tp_prefill_token", "lgh_tp_decode_greedy",
+    "lgh_tp_reset", "lgh_tp_position", "lgh_tp_kv_truncate", "lgh_tp_ranks", "lgh_tp_graph_nodes", "lgh_tp_last_error", "lgh_tp_shard", "lgh_op_tp_reduce",
     "lgh_set_kv_rotation_signs", "lgh_op_tq_compress", "lgh_set_kv_qjl_matrices", "lgh_op_tq_compress_qjl",
     "lgh_batch_create", "lgh_batch_reset", "lgh_batch_position", "lgh_batch_prefill", "lgh_forward_multi", "lgh_decode_greedy_multi",
     "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
@@ -214,6 +216,15 @@ def load_library() -> C.CDLL:
         "lgh_pipeline_forward": (C.c_int, [vp, u32, vp]), "lgh_pipeline_prefill_token": (C.c_int, [vp, u32]),
         "lgh_pipeline_decode_greedy": (C.c_int, [vp, u32, sz, vp]), "lgh_pipeline_reset": (None, [vp]),
         "lgh_pipeline_position": (sz, [vp]), "lgh_pipeline_kv_truncate": (C.c_int, [vp, sz]), "lgh_pipeline_stages": (C.c_int, [vp]), "lgh_pipeline_last_error": (C.c_char_p, [vp]),
+        "lgh_tp_create": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]),
+        "lgh_tp_upload_tensor": (C.c_int, [vp, C.c_char_p, u32, C.POINTER(C.c_uint64), vp, sz]),
+        "lgh_tp_finalize": (C.c_int, [vp]), "lgh_tp_destroy": (None, [vp]),
+        "lgh_tp_forward": (C.c_int, [vp, u32, vp]), "lgh_tp_prefill_token": (C.c_int, [vp, u32]),
+        "lgh_tp_decode_greedy": (C.c_int, [vp, u32, sz, vp]), "lgh_tp_reset": (None, [vp]),
+        "lgh_tp_position": (sz, [vp]), "lgh_tp_kv_truncate": (C.c_int, [vp, sz]), "lgh_tp_ranks": (C.c_int, [vp]),
+        "lgh_tp_graph_nodes": (C.c_uint64, [vp]), "lgh_tp_last_error": (C.c_char_p, [vp]),
+        "lgh_tp_shard": (C.c_int, [u32, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, vp, sz, vp, sz, C.POINTER(sz)]),
+        "lgh_op_tp_reduce": (C.c_int, [C.c_int, vp, u32, vp, vp, sz, vp, vp, vp]),
         "lgh_set_kv_rotation_signs": (C.c_int, [vp, vp, sz]), "lgh_op_tq_compress": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp]),
         "lgh_set_kv_qjl_matrices": (C.c_int, [vp, vp, sz]), "lgh_op_tq_compress_qjl": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, vp]),
         "lgh_batch_create": (C.c_int, [vp, u32]), "lgh_batch_reset": (C.c_int, [vp, u32]), "lgh_batch_position": (sz, [vp, u32]),
@@ -639,6 +650,97 @@ class HipPipeline:
             pass
 
 
+class HipTensorParallel:
+    """Tensor-parallel decode behind the GpuInference surface (lgh_tp_*): one process, `n_ranks` rank contexts on `devices`
+    (default: all on device 0 — the single-device rehearsal), every rank holding 1/N of the heads and of the FFN.
+    `GpuModelWrapper` drives it like a single HipGpuInference."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        self.config = None
+        self.vocab_size = 0
+
+    @classmethod
+    def from_model(cls, model, max_seq_len: int, n_ranks: int, devices: Optional[Sequence[int]] = None, flags: int = 0,
+                   kv_cache_type: int = 0, layer_range: Optional[Sequence[int]] = None) -> "HipTensorParallel":
+        """`kv_cache_type` / `layer_range` exist to be refused: tensor parallelism runs whole models over the f32 cache."""
+        L = load_library()
+        self = cls()
+        cfg = model.config
+        d = ModelDesc()
+        d.struct_size = C.sizeof(ModelDesc)
+        for k in ("hidden_size", "intermediate_size", "num_layers", "num_heads", "num_kv_heads", "head_dim",
+                  "vocab_size", "num_experts", "num_experts_per_token", "expert_intermediate_size"):
+            setattr(d, k, int(getattr(cfg, k)))
+        d.max_seq_len = int(max_seq_len)
+        d.use_neox_rope = int(cfg.use_neox_rope)
+        d.norm_eps, d.rope_freq_base, d.rope_freq_scale = cfg.norm_eps, cfg.rope_freq_base, cfg.rope_freq_scale
+        d.device_id, d.flags, d.kv_cache_type = 0, flags, int(kv_cache_type)
+        if layer_range is not None:
+            d.layer_begin, d.layer_end = layer_range
+        if devices is not None and len(devices) != n_ranks:
+            raise ValueError("one device per rank")
+        devs = (C.c_int * n_ranks)(*devices) if devices is not None else None
+        status = L.lgh_tp_create(C.byref(d), devs, n_ranks, C.byref(self._h))
+        if status != 0:
+            raise BackendError(status, (L.lgh_tp_last_error(None) or b"").decode() or "lgh_tp_create (is a HIP device visible?)")
+        self.config, self.vocab_size, self.hidden_size = cfg, cfg.vocab_size, cfg.hidden_size
+        try:
+            for name, t, ne, data in model.tensors():
+                data = np.ascontiguousarray(data)
+                ne = list(ne)
+                ne4 = (C.c_uint64 * 4)(*(ne + [0] * (4 - len(ne))))
+                self._call(L.lgh_tp_upload_tensor(self._h, name.encode(), t, ne4, data.ctypes.data, data.nbytes))
+            self._call(L.lgh_tp_finalize(self._h))
+        except Exception:
+            self.close()
+            raise
+        return self
+
+    def _call(self, status: int) -> None:
+        if status != 0:
+            raise BackendError(status, load_library().lgh_tp_last_error(self._h).decode())
+
+    def forward(self, token_id: int) -> np.ndarray:
+        logits = np.empty(self.vocab_size, dtype=np.float32)
+        self._call(load_library().lgh_tp_forward(self._h, token_id, logits.ctypes.data))
+        return logits
+
+    def prefill_token(self, token_id: int) -> None:
+        self._call(load_library().lgh_tp_prefill_token(self._h, token_id))
+
+    def decode_greedy(self, first_token: int, n_steps: int) -> np.ndarray:
+        out = np.zeros(n_steps, dtype=np.uint32)
+        self._call(load_library().lgh_tp_decode_greedy(self._h, first_token, n_steps, out.ctypes.data))
+        return out
+
+    def reset(self) -> None:
+        load_library().lgh_tp_reset(self._h)
+
+    def position(self) -> int:
+        return load_library().lgh_tp_position(self._h)
+
+    def kv_truncate(self, new_len: int) -> None:
+        self._call(load_library().lgh_tp_kv_truncate(self._h, int(new_len)))
+
+    def ranks(self) -> int:
+        return load_library().lgh_tp_ranks(self._h)
+
+    def graph_nodes(self) -> int:
+        return int(load_library().lgh_tp_graph_nodes(self._h))
+
+    def close(self) -> None:
+        if self._h:
+            load_library().lgh_tp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class InferenceContext:
     """The fields of the reference's InferenceContext that GpuModelWrapper touches (model/mod.rs:222-326)."""
 
@@ -799,6 +901,32 @@ def op_linear_chain(type_a: int, w_a, k: int, n_a: int, x, type_b: int, w_b, n_b
                                             _ptr(rs), xq_next, _ptr(nn), type_b, wb.ctypes.data, n_b, oa.ctypes.data, ob.ctypes.data,
                                             ob2.ctypes.data, C.byref(used)), "linear_chain")
     return oa, ob, ob2, bool(used.value)
+
+
+def tp_shard(ggml_type: int, ne: Sequence[int], axis: int, rank: int, n_ranks: int, raw, dst: Optional[np.ndarray] = None):
+    """lgh_tp_shard (host only): rank `rank`'s shard of a [ne[1] rows][ne[0] elements] GGUF payload, axis 0 = rows, 1 = k.
+    -> the shard's bytes; with `dst` (a uint8 buffer) -> the number of bytes written into it."""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    ne = list(ne)
+    ne4 = (C.c_uint64 * 4)(*(ne + [0] * (4 - len(ne))))
+    buf = np.empty(raw.size, np.uint8) if dst is None else dst
+    written = C.c_size_t(0)
+    _chk(load_library().lgh_tp_shard(ggml_type, ne4, axis, rank, n_ranks, raw.ctypes.data, raw.nbytes, buf.ctypes.data, buf.nbytes,
+                                     C.byref(written)), "tp_shard")
+    return buf[:written.value].copy() if dst is None else written.value
+
+
+def op_tp_reduce(partials, resid=None, norm_w=None, *, image: bool = False, ssq: bool = False, fill: int = 0, device: int = 0):
+    """tp_reduce_kernel on its own: out = resid + (((p0 + p1) + p2) ...) over partials [n, H] in rank order.
+    -> dict(out, image (uint8 or None), ssq (f32 or None)); every output buffer starts filled with the byte `fill`."""
+    p = _f32(partials)
+    n, H = p.shape
+    rs, nw = (None if v is None else _f32(v) for v in (resid, norm_w))
+    out = np.full(H * 4, fill, np.uint8).view(np.float32)
+    img = np.full((H + 255) // 256 * 1280, fill, np.uint8) if image else None
+    sq = np.full(max(H // 16, 1) * 4, fill, np.uint8).view(np.float32) if ssq else None
+    _chk(load_library().lgh_op_tp_reduce(device, p.ctypes.data, n, _ptr(rs), _ptr(nw), H, out.ctypes.data, _ptr(img), _ptr(sq)), "tp_reduce")
+    return {"out": out, "image": img, "ssq": sq}
 
 
 def op_set_flags(flags: int) -> int:
