@@ -221,12 +221,34 @@ int launch_mvb(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float*
 bool mvb_k_ok(uint32_t k);                           // a [.., k] matrix plans to the 8-wave workgroups the multi-sequence kernels run
 uint32_t xq_stride_of(uint32_t k);                   // bytes / floats between two sequences' images and sum-of-squares partials
 uint32_t ssq_stride_of(uint32_t k);
-void mark_fresh(lgh_ctx* c, const float* base, uint32_t k, uint32_t n, const float* tag);
-void spread_state(lgh_ctx* c, const float* f32, uint32_t k, uint32_t n);
 uint64_t batch_part_floats(const lgh_ctx* c, uint32_t max_batch);
+void batch_cache_layout(lgh_ctx* c);                 // the distances between two slots' caches of a layer, its (empty) per-layer cache tables
 int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch);
+// the step of a layer over the batch scratch (c->batch), one function each, shared by enqueue_multi and the per-launch entry points
 int qkv_forward_multi(lgh_ctx* c, lgh::LayerW& Lw, uint32_t li, uint32_t n_seq);
+int attention_forward_multi(lgh_ctx* c, uint32_t li, uint32_t n_seq, float scale, bool xq_out);   // Bs.q -> Bs.attn_out (+ its images)
+int linear_multi(lgh_ctx* c, int cls, const lgh::DevWeight& W, const lgh::DevWeight* W_up, const float* x, float* out, uint32_t out_stride,
+                 uint32_t n_seq, const float* norm_w, const float* resid = nullptr, const float* bias = nullptr, int xq_next = 0,
+                 const float* xq_next_nw = nullptr, const MvIndirect ind = MvIndirect{});
+int ffn_forward_multi(lgh_ctx* c, lgh::LayerW& Lw, uint32_t n_seq, const float* next_nw);
 int moe_grouped_forward(lgh_ctx* c, lgh::LayerW& Lw, uint32_t n_seq, const float* next_nw, bool route);
+// What every entry point asks of a step's sequences: n_seq in 1 .. max_n; every slot number in [0, n_slots) and, with `distinct`, listed
+// once; every position — pos(i), sequence i's; an empty function: not checked — in [0, max_seq).  The first condition that fails, and
+// in *at which sequence it failed for
+enum SeqFault { SEQ_OK = 0, SEQ_COUNT, SEQ_SLOT, SEQ_POS };
+template <class T>
+inline SeqFault check_seqs(size_t n_seq, size_t max_n, const T* slot, size_t n_slots, bool distinct, const std::function<uint64_t(size_t)>& pos,
+                           size_t max_seq, size_t* at = nullptr) {
+  if (n_seq == 0 || n_seq > max_n) return SEQ_COUNT;
+  for (size_t i = 0; i < n_seq; i++) {
+    if (at) *at = i;
+    if ((uint64_t)(int64_t)slot[i] >= n_slots) return SEQ_SLOT;   // (a negative number: far above)
+    for (size_t j = 0; distinct && j < i; j++)
+      if (slot[j] == slot[i]) return SEQ_SLOT;
+    if (pos && pos(i) >= max_seq) return SEQ_POS;
+  }
+  return SEQ_OK;
+}
 // matrix-core segments in formats without a common instantiation (Q4_K with Q5_K, Q8_0 / Q4_0 with anything else): one launch each
 bool mv_formats_split(const SegSpec* specs, int nseg);
 lgh::XqBuf* xq_get(lgh_ctx* c, const float* f32, uint32_t k);   // finds or registers (allocating) the image of a buffer

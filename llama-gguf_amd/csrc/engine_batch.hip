@@ -51,13 +51,13 @@ int register_views(lgh_ctx* c, float* f32, uint8_t* xq, float* ssq, uint32_t k, 
 }
 
 // a launch left the images of n vectors of k floats from `base` on, multiplied with the norm weights `tag` (nullptr: none)
-void mark_fresh(lgh_ctx* c, const float* base, uint32_t k, uint32_t n, const float* tag) {
+static void mark_fresh(lgh_ctx* c, const float* base, uint32_t k, uint32_t n, const float* tag) {
   for (uint32_t s = 0; s < n; s++)
     if (XqBuf* q = xq_find(c, base + (size_t)s * k)) { q->fresh = true; q->tag = tag; }
 }
 
 // after a batched launch produced / consumed the images of sequence 0's view, the other sequences' views are in the same state
-void spread_state(lgh_ctx* c, const float* f32, uint32_t k, uint32_t n) {
+static void spread_state(lgh_ctx* c, const float* f32, uint32_t k, uint32_t n) {
   XqBuf* q0 = xq_find(c, f32);
   if (!q0) return;
   for (uint32_t s = 1; s < n; s++)
@@ -132,21 +132,39 @@ int qkv_forward_multi(lgh_ctx* c, LayerW& Lw, uint32_t li, uint32_t n_seq) {
   BatchScratch& Bs = c->batch;
   const lgh_model_desc& d = c->d;
   const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim;
-  const bool tq = (d.flags & LGH_FLAG_KV_INT8) != 0;   // every quantized cache (TurboQuant, int8, FP8) stages its rows
+  const bool staged = (d.flags & LGH_FLAG_KV_INT8) != 0;   // every quantized cache (TurboQuant, int8, FP8) stages its rows
   const uint32_t KD = d.num_kv_heads * d.head_dim;
   int rc;
   SegSpec sp[3];
   sp[0].W[0] = &Lw.wq; sp[0].x[0] = Bs.hidden; sp[0].epi = EPI_ROPE_Q; sp[0].out = Bs.q; sp[0].bias = Lw.bq;
   // (quantized caches: the rotated K row and the V row stay f32 in a staging vector per sequence; the attention launch compresses them)
-  sp[1].W[0] = &Lw.wk; sp[1].x[0] = Bs.hidden; sp[1].epi = tq ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = tq ? Bs.kv_tmp : Bs.kcache[li]; sp[1].bias = Lw.bk;
-  sp[2].W[0] = &Lw.wv; sp[2].x[0] = Bs.hidden; sp[2].epi = tq ? EPI_STORE : EPI_V_CACHE; sp[2].out = tq ? Bs.kv_tmp + KD : Bs.vcache[li]; sp[2].bias = Lw.bv;
-  const uint32_t os[3] = {QD, tq ? 2 * KD : 0, tq ? 2 * KD : 0}, rs[3] = {0, 0, 0}, xk[3] = {0, 0, 0};
+  sp[1].W[0] = &Lw.wk; sp[1].x[0] = Bs.hidden; sp[1].epi = staged ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = staged ? Bs.kv_tmp : Bs.kcache[li]; sp[1].bias = Lw.bk;
+  sp[2].W[0] = &Lw.wv; sp[2].x[0] = Bs.hidden; sp[2].epi = staged ? EPI_STORE : EPI_V_CACHE; sp[2].out = staged ? Bs.kv_tmp + KD : Bs.vcache[li]; sp[2].bias = Lw.bv;
+  const uint32_t os[3] = {QD, staged ? 2 * KD : 0, staged ? 2 * KD : 0}, rs[3] = {0, 0, 0}, xk[3] = {0, 0, 0};
   if (mv_formats_split(sp, 3)) {   // (one launch each then, as launch_mv does)
     for (int s = 0; s < 3; s++)
       if ((rc = launch_mvb(c, LGH_K_QKV, sp + s, 1, Lw.attn_norm, H, n_seq, os + s, rs + s, xk + s))) return rc;
     return LGH_OK;
   }
   return launch_mvb(c, LGH_K_QKV, sp, 3, Lw.attn_norm, H, n_seq, os, rs, xk);
+}
+
+// one Linear of the step for all its sequences (linear_any's counterpart): W — or the SwiGLU pair W | W_up — over sequence 0's vectors
+// x -> out, sequence s's output out_stride floats on; a residual lies at the output's stride, and so do the views of an output that
+// leaves its image (xq_next / xq_next_nw as SegSpec's); ind: as launch_mvb's.  wo, gate | up, down — dense or the experts' — and the
+// output projection of a step are calls of this
+int linear_multi(lgh_ctx* c, int cls, const DevWeight& W, const DevWeight* W_up, const float* x, float* out, uint32_t out_stride, uint32_t n_seq,
+                 const float* norm_w, const float* resid, const float* bias, int xq_next, const float* xq_next_nw, const MvIndirect ind) {
+  SegSpec sp;
+  sp.W[0] = &W; sp.x[0] = x;
+  if (W_up) { sp.npass = 2; sp.W[1] = W_up; sp.x[1] = x; }
+  sp.epi = W_up ? EPI_SWIGLU : resid ? EPI_RESID : EPI_STORE;
+  sp.out = out; sp.resid = resid; sp.bias = bias;
+  sp.xq_next = xq_next; sp.xq_next_nw = xq_next_nw;
+  const uint32_t rs = resid ? out_stride : 0, xk = xq_next ? out_stride : 0;
+  if (int rc = launch_mvb(c, cls, &sp, 1, norm_w, W.k, n_seq, &out_stride, &rs, &xk, ind)) return rc;
+  spread_state(c, out, out_stride, n_seq);   // (the launch set sequence 0's view: fresh with an image, stale without; no view, nothing to do)
+  return LGH_OK;
 }
 
 // MoE, every selected expert's matrices read ONCE for the step (MoeLayer::forward per sequence, moe.rs:321-413, regrouped):
@@ -168,30 +186,89 @@ int moe_grouped_forward(lgh_ctx* c, LayerW& Lw, uint32_t n_seq, const float* nex
     return rc;
   // all experts of the layer in one launch each (grid z = expert: its count, its entry list, its slice of the stacked matrices)
   const MvIndirect ind_gu{Bs.moe_cnt, Bs.moe_idx, topk, ne, (uint32_t)kMaxBatch}, ind_dn{Bs.moe_cnt, Bs.moe_idx, 1, ne, (uint32_t)kMaxBatch};
-  {
-    SegSpec sp;
-    sp.npass = 2;
-    sp.W[0] = &Lw.gate_exps; sp.W[1] = &Lw.up_exps;
-    sp.x[0] = sp.x[1] = Bs.hidden;
-    sp.epi = EPI_SWIGLU;
-    sp.out = Bs.moe_act;
-    sp.xq_next = 1;
-    const uint32_t os[1] = {EF}, rs[1] = {0}, xk[1] = {EF};
-    if ((rc = launch_mvb(c, LGH_K_GATEUP, &sp, 1, Lw.ffn_norm, H, n_seq, os, rs, xk, ind_gu))) return rc;
-  }
-  mark_fresh(c, Bs.moe_act, EF, n_seq * topk, nullptr);
-  {
-    SegSpec sp;
-    sp.W[0] = &Lw.down_exps; sp.x[0] = Bs.moe_act; sp.epi = EPI_STORE; sp.out = Bs.moe_tmp;
-    const uint32_t os[1] = {H}, rs[1] = {0}, xk[1] = {0};
-    if ((rc = launch_mvb(c, LGH_K_DOWN, &sp, 1, nullptr, Lw.down_exps.k, n_seq, os, rs, xk, ind_dn))) return rc;
-  }
+  if ((rc = linear_multi(c, LGH_K_GATEUP, Lw.gate_exps, &Lw.up_exps, Bs.hidden, Bs.moe_act, EF, n_seq, Lw.ffn_norm, nullptr, nullptr, 1, nullptr, ind_gu)))
+    return rc;
+  mark_fresh(c, Bs.moe_act, EF, n_seq * topk, nullptr);   // (a view per pair, not per sequence)
+  if ((rc = linear_multi(c, LGH_K_DOWN, Lw.down_exps, nullptr, Bs.moe_act, Bs.moe_tmp, H, n_seq, nullptr, nullptr, nullptr, 0, nullptr, ind_dn))) return rc;
   XqBuf* qh = xq_find(c, Bs.hidden);
   if ((rc = run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] {
          return moe_combine_launch(Bs.moe_tmp, Bs.moe_w, topk, Bs.hidden, H, n_seq, next_nw, qh->xq, xq_stride_of(H), qh->ssq, ssq_stride_of(H), c->stream);
        })))
     return rc;
   mark_fresh(c, Bs.hidden, H, n_seq, next_nw);
+  return LGH_OK;
+}
+
+// attention_cached per sequence (ops.rs:1479-1537) over layer li's cache slots, whatever their format: split + merge, the sequence as
+// the grid's second dimension, Bs.q -> Bs.attn_out.  The one place that knows which of the scratch's strides goes to which launcher.
+// xq_out: the merge also leaves every sequence's XQ image of attn_out for wo (where its views are registered)
+int attention_forward_multi(lgh_ctx* c, uint32_t li, uint32_t n_seq, float scale, bool xq_out) {
+  BatchScratch& Bs = c->batch;
+  const lgh_model_desc& d = c->d;
+  const uint32_t QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim;
+  int rc;
+  XqBuf* const qa = xq_out ? xq_find(c, Bs.attn_out) : nullptr;
+  uint8_t* const img = qa ? qa->xq : nullptr;
+  if (kv_is_tq(d.kv_cache_type)) {
+    // TurboQuantKVCache (kv_turboquant.rs) per sequence: write_kv + attention over the slot's codes; the merge inverts the V rotation
+    const int bits = kv_tq_bits(d.kv_cache_type);
+    const bool qjl = kv_is_qjl(d.kv_cache_type);
+    const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
+    const float* qjl_s = qjl ? c->tq_qjl + (size_t)(li - c->l0) * d.num_kv_heads * d.head_dim * d.head_dim : nullptr;
+    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
+           return attn_tq_multi_launch(bits, Bs.q, Bs.kq[li], Bs.vq[li], Bs.kv_tmp, Bs.kv_tmp + KD, signs, d.num_heads, d.num_kv_heads, d.head_dim,
+                                       d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, Bs.code_stride, Bs.x_stride, 2 * KD, n_seq, c->n_splits, Bs.part_ml,
+                                       Bs.part_acc, c->stream, qjl_s, qjl ? Bs.kx[li] : nullptr);
+         })))
+      return rc;
+    rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
+      return attn_tq_combine_launch(bits, Bs.part_ml, Bs.part_acc, signs, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, Bs.attn_out, img,
+                                    c->stream, n_seq, (uint32_t)xq_stride_of(QD));
+    });
+  } else {
+    if (d.flags & LGH_FLAG_KV_INT8) {
+      // QuantizedKVCache (kv_quantized.rs) per sequence: the launch quantizes and stores each sequence's staged rows into its slot; the
+      // partials merge as f32 ones do (as in the single-sequence engine)
+      rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
+        return attn_q8_multi_launch((int)d.kv_cache_type, Bs.q, (int8_t*)Bs.kq[li], (int8_t*)Bs.vq[li], Bs.kscale[li], Bs.vscale[li], Bs.kv_tmp,
+                                    Bs.kv_tmp + KD, 2 * KD, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, n_seq,
+                                    c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
+      });
+    } else {
+      rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
+        return attn_multi_launch(Bs.q, Bs.kcache[li], Bs.vcache[li], d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot,
+                                 Bs.cache_stride, n_seq, c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
+      });
+    }
+    if (rc) return rc;
+    rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
+      return attn_combine_multi_launch(Bs.part_ml, Bs.part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, n_seq, Bs.attn_out, img, c->stream);
+    });
+  }
+  if (rc) return rc;
+  if (img) mark_fresh(c, Bs.attn_out, QD, n_seq, nullptr);
+  else
+    for (uint32_t s = 0; s < n_seq; s++) xq_stale(c, Bs.attn_out + (size_t)s * QD);
+  return LGH_OK;
+}
+
+// the FFN half of a layer for the step's sequences, Bs.hidden -> Bs.hidden (+ its image with next_nw): the dense pair of launches; MoE
+// layers from moe_group_min() sequences on every selected expert once (moe_grouped_forward), below that — or where the expert shapes
+// do not group — sequence by sequence, every sequence routed to its own experts by the single-sequence launches on its vectors
+int ffn_forward_multi(lgh_ctx* c, LayerW& Lw, uint32_t n_seq, const float* next_nw) {
+  BatchScratch& Bs = c->batch;
+  const uint32_t H = c->d.hidden_size;
+  int rc;
+  if (!Lw.moe()) {
+    if ((rc = linear_multi(c, LGH_K_GATEUP, Lw.gate, &Lw.up, Bs.hidden, Bs.act, Bs.ffn, n_seq, Lw.ffn_norm, nullptr, nullptr, 1))) return rc;
+    return linear_multi(c, LGH_K_DOWN, Lw.down, nullptr, Bs.act, Bs.hidden, H, n_seq, nullptr, Bs.hidden, nullptr, 2, next_nw);
+  }
+  if (Bs.moe_act && n_seq >= moe_group_min()) return moe_grouped_forward(c, Lw, n_seq, next_nw, true);
+  for (uint32_t s = 0; s < n_seq; s++) {
+    const FfnView v{Bs.hidden + (size_t)s * H, Bs.act + (size_t)s * Bs.ffn, Bs.act2 + (size_t)s * Bs.ffn, Bs.xnorm + (size_t)s * H,
+                    Bs.moe_sel + s * 8, Bs.moe_w + s * 8};
+    if ((rc = ffn_forward(c, Lw, v, next_nw, true))) return rc;
+  }
   return LGH_OK;
 }
 
@@ -231,7 +308,7 @@ bool batch_weights_ok(const lgh_ctx* c, std::string& why) {
 int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits only, 1 + arg-max, 2 + sampled token
   BatchScratch& Bs = c->batch;
   const lgh_model_desc& d = c->d;
-  const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim;
+  const uint32_t H = d.hidden_size;
   int rc;
   auto stale_all = [&] { for (auto& q : c->xqs) q.fresh = false; };
   stale_all();
@@ -247,110 +324,19 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
     mark_fresh(c, Bs.hidden, H, n_seq, L0.attn_norm);
   }
   const float scale = 1.0f / std::sqrt((float)d.head_dim);
-  // the merge of a layer's attention splits: `launch(image)` writes attn_out and, for wo, its XQ image for every sequence
-  auto merge = [&](auto&& launch) -> int {
-    XqBuf* qa = xq_find(c, Bs.attn_out);
-    if (int rm = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] { return launch(qa->xq); })) return rm;
-    mark_fresh(c, Bs.attn_out, QD, n_seq, nullptr);
-    return LGH_OK;
-  };
   for (uint32_t li = c->l0; li < c->l1; li++) {
     LayerW& Lw = c->layers[li];
     const float* next_nw = li + 1 < c->l1 ? c->layers[li + 1].attn_norm : c->output_norm;
-    // ---- Q, K, V (+ RoPE at every sequence's own position, K / V rows into its own cache slot)
+    // ---- Q, K, V (+ RoPE at every sequence's own position, K / V rows into its own cache slot), attention over every sequence's slot
     if ((rc = qkv_forward_multi(c, Lw, li, n_seq))) return rc;
-    // ---- attention_cached per sequence (ops.rs:1479-1537): split + merge, the sequence as the grid's second dimension
-    if (kv_is_tq(d.kv_cache_type)) {
-      // TurboQuantKVCache (kv_turboquant.rs) per sequence: write_kv + attention over the slot's codes; the merge inverts the V rotation
-      const int bits = kv_tq_bits(d.kv_cache_type);
-      const bool qjl = kv_is_qjl(d.kv_cache_type);
-      const uint32_t KD = d.num_kv_heads * d.head_dim;
-      const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
-      const float* qjl_s = qjl ? c->tq_qjl + (size_t)(li - c->l0) * d.num_kv_heads * d.head_dim * d.head_dim : nullptr;
-      if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-             return attn_tq_multi_launch(bits, Bs.q, Bs.kq[li], Bs.vq[li], Bs.kv_tmp, Bs.kv_tmp + KD, signs, d.num_heads, d.num_kv_heads, d.head_dim,
-                                         d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, Bs.code_stride, Bs.x_stride, 2 * KD, n_seq, c->n_splits, Bs.part_ml,
-                                         Bs.part_acc, c->stream, qjl_s, qjl ? Bs.kx[li] : nullptr);
-           })))
-        return rc;
-      if ((rc = merge([&](uint8_t* img) {
-             return attn_tq_combine_launch(bits, Bs.part_ml, Bs.part_acc, signs, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, Bs.attn_out, img,
-                                           c->stream, n_seq, (uint32_t)xq_stride_of(QD));
-           })))
-        return rc;
-    } else if (d.flags & LGH_FLAG_KV_INT8) {
-      // QuantizedKVCache (kv_quantized.rs) per sequence: the launch quantizes and stores each sequence's staged rows into its slot; the
-      // partials merge as f32 ones do (as in the single-sequence engine)
-      const uint32_t KD = d.num_kv_heads * d.head_dim;
-      if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-             return attn_q8_multi_launch((int)d.kv_cache_type, Bs.q, (int8_t*)Bs.kq[li], (int8_t*)Bs.vq[li], Bs.kscale[li], Bs.vscale[li], Bs.kv_tmp,
-                                         Bs.kv_tmp + KD, 2 * KD, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, n_seq,
-                                         c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
-           })))
-        return rc;
-      if ((rc = merge([&](uint8_t* img) {
-             return attn_combine_multi_launch(Bs.part_ml, Bs.part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, n_seq, Bs.attn_out, img, c->stream);
-           })))
-        return rc;
-    } else {
-      if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-             return attn_multi_launch(Bs.q, Bs.kcache[li], Bs.vcache[li], d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot,
-                                      Bs.cache_stride, n_seq, c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
-           })))
-        return rc;
-      if ((rc = merge([&](uint8_t* img) {
-             return attn_combine_multi_launch(Bs.part_ml, Bs.part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, n_seq, Bs.attn_out, img, c->stream);
-           })))
-        return rc;
-    }
+    if ((rc = attention_forward_multi(c, li, n_seq, scale, true))) return rc;
     // ---- h = x + wo(attn)
-    {
-      SegSpec sp;
-      sp.W[0] = &Lw.wo; sp.x[0] = Bs.attn_out; sp.epi = EPI_RESID; sp.out = Bs.hidden; sp.resid = Bs.hidden; sp.bias = Lw.bo;
-      sp.xq_next = 2; sp.xq_next_nw = Lw.ffn_norm;
-      const uint32_t os[1] = {H}, rs[1] = {H}, xk[1] = {H};
-      if ((rc = launch_mvb(c, LGH_K_WO, &sp, 1, nullptr, Lw.wo.k, n_seq, os, rs, xk))) return rc;
-      spread_state(c, Bs.hidden, H, n_seq);
-    }
+    if ((rc = linear_multi(c, LGH_K_WO, Lw.wo, nullptr, Bs.attn_out, Bs.hidden, H, n_seq, nullptr, Bs.hidden, Lw.bo, 2, Lw.ffn_norm))) return rc;
     // ---- FFN
-    if (!Lw.moe()) {
-      {
-        SegSpec sp;
-        sp.npass = 2;
-        sp.W[0] = &Lw.gate; sp.W[1] = &Lw.up;
-        sp.x[0] = sp.x[1] = Bs.hidden;
-        sp.epi = EPI_SWIGLU;
-        sp.out = Bs.act;
-        sp.xq_next = 1;
-        const uint32_t os[1] = {Bs.ffn}, rs[1] = {0}, xk[1] = {Bs.ffn};
-        if ((rc = launch_mvb(c, LGH_K_GATEUP, &sp, 1, Lw.ffn_norm, H, n_seq, os, rs, xk))) return rc;
-        spread_state(c, Bs.act, Bs.ffn, n_seq);
-      }
-      {
-        SegSpec sp;
-        sp.W[0] = &Lw.down; sp.x[0] = Bs.act; sp.epi = EPI_RESID; sp.out = Bs.hidden; sp.resid = Bs.hidden;
-        sp.xq_next = 2; sp.xq_next_nw = next_nw;
-        const uint32_t os[1] = {H}, rs[1] = {H}, xk[1] = {H};
-        if ((rc = launch_mvb(c, LGH_K_DOWN, &sp, 1, nullptr, Lw.down.k, n_seq, os, rs, xk))) return rc;
-        spread_state(c, Bs.hidden, H, n_seq);
-      }
-    } else if (Bs.moe_act && n_seq >= moe_group_min()) {
-      if ((rc = moe_grouped_forward(c, Lw, n_seq, next_nw, true))) return rc;
-    } else {
-      for (uint32_t s = 0; s < n_seq; s++) {   // every sequence routes to its own experts: the single-sequence launches on its vectors
-        const FfnView v{Bs.hidden + (size_t)s * H, Bs.act + (size_t)s * Bs.ffn, Bs.act2 + (size_t)s * Bs.ffn, Bs.xnorm + (size_t)s * H,
-                        Bs.moe_sel + s * 8, Bs.moe_w + s * 8};
-        if ((rc = ffn_forward(c, Lw, v, next_nw, true))) return rc;
-      }
-    }
+    if ((rc = ffn_forward_multi(c, Lw, n_seq, next_nw))) return rc;
   }
   // ---- compute_logits: final RMSNorm fused into the output projection
-  {
-    SegSpec sp;
-    sp.W[0] = &c->output; sp.x[0] = Bs.hidden; sp.epi = EPI_STORE; sp.out = Bs.logits;
-    const uint32_t os[1] = {d.vocab_size}, rs[1] = {0}, xk[1] = {0};
-    if ((rc = launch_mvb(c, LGH_K_OUTPUT, &sp, 1, c->output_norm, H, n_seq, os, rs, xk))) return rc;
-  }
+  if ((rc = linear_multi(c, LGH_K_OUTPUT, c->output, nullptr, Bs.hidden, Bs.logits, d.vocab_size, n_seq, c->output_norm))) return rc;
   if (mode == 1) {
     // arg-max per sequence (last maximal index), fed back as the next step's token; the positions move on
     if ((rc = run_k(c, LGH_K_ARGMAX, LGH_SYM_ARGMAX, (uint64_t)n_seq * d.vocab_size * 4, [&] {
@@ -377,15 +363,16 @@ int stage_control(lgh_ctx* c, const uint32_t* slots, const uint32_t* tokens, uin
   BatchScratch& Bs = c->batch;
   const lgh_model_desc& d = c->d;
   if (!Bs.ready) return fail(c, LGH_INVALID_ARGUMENT, "lgh_batch_create has not been called");
-  if (n_seq == 0 || n_seq > Bs.max_batch) return fail(c, LGH_INVALID_ARGUMENT, "n_seq must be 1 .. max_batch");
-  bool seen[kMaxBatch] = {};
-  for (uint32_t i = 0; i < n_seq; i++) {
-    if (slots[i] >= Bs.max_batch || seen[slots[i]]) return fail(c, LGH_INVALID_ARGUMENT, "slot numbers must be distinct and below max_batch");
-    seen[slots[i]] = true;
-    if (Bs.pos[slots[i]] >= d.max_seq_len)
-      return fail(c, LGH_INVALID_ARGUMENT, "slot " + std::to_string(slots[i]) + ": position " + std::to_string(Bs.pos[slots[i]]) + " >= max_seq_len");
-    if (tokens && tokens[i] >= d.vocab_size) return fail(c, LGH_INVALID_ARGUMENT, "token id exceeds vocab size");
+  size_t at = 0;
+  switch (check_seqs(n_seq, Bs.max_batch, slots, Bs.max_batch, true, [&](size_t i) { return Bs.pos[slots[i]]; }, d.max_seq_len, &at)) {
+    case SEQ_OK: break;
+    case SEQ_COUNT: return fail(c, LGH_INVALID_ARGUMENT, "n_seq must be 1 .. max_batch");
+    case SEQ_SLOT: return fail(c, LGH_INVALID_ARGUMENT, "slot numbers must be distinct and below max_batch");
+    case SEQ_POS:
+      return fail(c, LGH_INVALID_ARGUMENT, "slot " + std::to_string(slots[at]) + ": position " + std::to_string(Bs.pos[slots[at]]) + " >= max_seq_len");
   }
+  for (uint32_t i = 0; tokens && i < n_seq; i++)
+    if (tokens[i] >= d.vocab_size) return fail(c, LGH_INVALID_ARGUMENT, "token id exceeds vocab size");
   HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));   // the pinned words below are free again
   for (uint32_t i = 0; i < n_seq; i++) {
     Bs.h_ctl[i] = tokens ? (int)tokens[i] : 0;
@@ -468,6 +455,26 @@ uint64_t batch_part_floats(const lgh_ctx* c, uint32_t max_batch) {
   return need;
 }
 
+// How a layer's cache slots lie, from the model fields: the distances between two slots — f32 rows [kv_head][max_seq][head_dim];
+// QuantizedKVCache::new per slot (kv_quantized.rs:143-300), a byte per element; TurboQuantKVCache::new per slot (kv_turboquant.rs:36-86),
+// packed codes (+ QJL rows of K) — and the per-layer tables of the caches, still empty
+void batch_cache_layout(lgh_ctx* c) {
+  BatchScratch& Bs = c->batch;
+  const lgh_model_desc& d = c->d;
+  const size_t rows = (size_t)d.num_kv_heads * d.max_seq_len;
+  const bool tq = kv_is_tq(d.kv_cache_type);
+  Bs.cache_stride = rows * d.head_dim;
+  Bs.code_stride = tq ? rows * tq_row_bytes_host(kv_tq_bits(d.kv_cache_type), d.head_dim) : (d.flags & LGH_FLAG_KV_INT8) ? rows * d.head_dim : 0;
+  Bs.x_stride = tq ? rows * (d.head_dim / 32 + 1) : 0;
+  Bs.kcache.assign(d.num_layers, nullptr);
+  Bs.vcache.assign(d.num_layers, nullptr);
+  Bs.kq.assign(d.num_layers, nullptr);
+  Bs.vq.assign(d.num_layers, nullptr);
+  Bs.kx.assign(d.num_layers, nullptr);
+  Bs.kscale.assign(d.num_layers, nullptr);
+  Bs.vscale.assign(d.num_layers, nullptr);
+}
+
 // the scratch of the multi-sequence engine for max_batch slots on a context whose model fields and layers are set: the vectors of the
 // sequences side by side with their registered XQ views, the control words, the partial-sum buffer, every slot's caches and the
 // grouped MoE step's buffers (lgh_batch_create; the per-launch entry points of ops_api.hip)
@@ -480,7 +487,7 @@ int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch) {
   const uint32_t ffn = std::max(d.intermediate_size, EI);
   Bs.max_batch = max_batch;
   Bs.ffn = ffn;
-  Bs.cache_stride = (uint64_t)d.num_kv_heads * d.max_seq_len * d.head_dim;
+  batch_cache_layout(c);
   const size_t B = max_batch;
   Bs.mv_part_floats = batch_part_floats(c, max_batch);
   uint8_t *xq_h = nullptr, *xq_a = nullptr, *xq_f = nullptr, *xq_f2 = nullptr;
@@ -499,24 +506,8 @@ int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch) {
       {(void**)&xq_f2, B * xq_stride_of(ffn)}, {(void**)&ssq_f2, B * ssq_stride_of(ffn) * 4},
   };
   if ((rc = alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes))) return rc;
-  Bs.kcache.assign(d.num_layers, nullptr);
-  Bs.vcache.assign(d.num_layers, nullptr);
-  Bs.kq.assign(d.num_layers, nullptr);
-  Bs.vq.assign(d.num_layers, nullptr);
-  Bs.kx.assign(d.num_layers, nullptr);
-  Bs.kscale.assign(d.num_layers, nullptr);
-  Bs.vscale.assign(d.num_layers, nullptr);
   const bool kv8 = (d.flags & LGH_FLAG_KV_INT8) && !kv_is_tq(d.kv_cache_type);   // int8 / FP8: a byte per element (+ a scale per int8 row)
-  if (kv8) {   // QuantizedKVCache::new per slot (kv_quantized.rs:143-300)
-    Bs.code_stride = (uint64_t)d.num_kv_heads * d.max_seq_len * d.head_dim;
-    if ((rc = dev_alloc(c, (void**)&Bs.kv_tmp, B * 2 * d.num_kv_heads * d.head_dim * 4))) return rc;
-  }
-  if (kv_is_tq(d.kv_cache_type)) {   // TurboQuantKVCache::new per slot (kv_turboquant.rs:36-86): packed codes (+ QJL rows of K)
-    const size_t rows = (size_t)d.num_kv_heads * d.max_seq_len;
-    Bs.code_stride = rows * tq_row_bytes_host(kv_tq_bits(d.kv_cache_type), d.head_dim);
-    Bs.x_stride = rows * (d.head_dim / 32 + 1);
-    if ((rc = dev_alloc(c, (void**)&Bs.kv_tmp, B * 2 * d.num_kv_heads * d.head_dim * 4))) return rc;
-  }
+  if ((d.flags & LGH_FLAG_KV_INT8) && (rc = dev_alloc(c, (void**)&Bs.kv_tmp, B * 2 * d.num_kv_heads * d.head_dim * 4))) return rc;
   for (uint32_t i = c->l0; i < c->l1; i++) {   // per layer, every slot's cache: code rows (+ QJL rows of K), byte rows (+ int8 scales), or f32 [slot][kv_head][max_seq][head_dim]
     const bool tq = kv_is_tq(d.kv_cache_type);
     const size_t n = tq || kv8 ? B * Bs.code_stride : 0, nf = tq || kv8 ? 0 : B * Bs.cache_stride * 4;
@@ -651,13 +642,14 @@ int lgh_decode_sample_multi(lgh_ctx* c, const uint32_t* slots, const uint32_t* f
   if (!slots || !first_tokens) return fail(c, LGH_INVALID_ARGUMENT, "slots / first_tokens is NULL");
   BatchScratch& Bs = c->batch;
   if (!Bs.ready) return fail(c, LGH_INVALID_ARGUMENT, "lgh_batch_create has not been called");
-  if (n_seq == 0 || n_seq > Bs.max_batch) return fail(c, LGH_INVALID_ARGUMENT, "n_seq must be 1 .. max_batch");
+  // (the count and the slot numbers' range, before the slots' samplers are looked at; stage_control below checks the rest)
+  if (const SeqFault f = check_seqs(n_seq, Bs.max_batch, slots, Bs.max_batch, false, nullptr, 0))
+    return fail(c, LGH_INVALID_ARGUMENT, f == SEQ_COUNT ? "n_seq must be 1 .. max_batch" : "slot numbers must be distinct and below max_batch");
   if (n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "too many steps");
   if (Bs.samp_set.size() != Bs.max_batch || Bs.samp_cfg.size() != Bs.max_batch) return fail(c, LGH_INVALID_ARGUMENT, "no samplers");
   size_t hist_off[kMaxBatch];
   size_t off = 0;
   for (uint32_t i = 0; i < n_seq; i++) {
-    if (slots[i] >= Bs.max_batch) return fail(c, LGH_INVALID_ARGUMENT, "slot numbers must be distinct and below max_batch");
     if (!Bs.samp_set[slots[i]]) return fail(c, LGH_INVALID_ARGUMENT, "slot " + std::to_string(slots[i]) + ": lgh_batch_set_sampler has not been called");
     if (Bs.pos[slots[i]] + n_steps > c->d.max_seq_len) return fail(c, LGH_INVALID_ARGUMENT, "the steps would run past max_seq_len");
     const lgh_sampler_config_ex& g = Bs.samp_cfg[slots[i]];

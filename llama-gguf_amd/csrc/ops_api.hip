@@ -411,7 +411,8 @@ int lgh_op_attention(int device, const float* q, const float* k, const float* v,
 // ---- the engine's attention step (engine_layer.hip: attention_forward) one path at a time (test surface: tests/test_gpu_attention.py
 // holds each to a float64 restatement).  The bare context's fields select the path as a real context's do; the caches come from the
 // host, the position through the device word the engine's kernels read (state[ST_POS]); nothing falls back to another kernel: a
-// shape the path has no kernel for answers LGH_UNSUPPORTED. ----
+// shape the path has no kernel for answers LGH_UNSUPPORTED.  The *_multi entry points do the same with the multi-sequence step's
+// attention (engine_batch.hip: attention_forward_multi) on the batch scratch of a bare context (attn_multi_setup). ----
 }  // extern "C"
 
 namespace {
@@ -435,8 +436,9 @@ int set_pos(Tmp& t, size_t pos) {   // the engine's position word
   return hipStreamSynchronize(t.c->stream) == hipSuccess ? LGH_OK : LGH_OPERATION_FAILED;
 }
 
-// the bare context as attention_forward reads it: shapes, the cache format, the split count and its partial-result buffers
-int attn_setup(Tmp& t, uint32_t kv_cache_type, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq, int n_splits) {
+// the bare context as attention_forward reads it: shapes, the cache format, the split count and its partial-result buffers (of n_seq
+// sequences)
+int attn_setup(Tmp& t, uint32_t kv_cache_type, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq, int n_splits, size_t n_seq = 1) {
   lgh_ctx* c = t.c;
   c->d.num_heads = (uint32_t)n_heads;
   c->d.num_kv_heads = (uint32_t)n_kv;
@@ -445,11 +447,53 @@ int attn_setup(Tmp& t, uint32_t kv_cache_type, size_t n_heads, size_t n_kv, size
   c->d.kv_cache_type = kv_cache_type;
   if (kv_cache_type != LGH_KV_F32) c->d.flags |= LGH_FLAG_KV_INT8;   // (as lgh_create marks every byte-per-element cache)
   c->n_splits = (uint32_t)n_splits;
-  const size_t parts = n_kv * (size_t)n_splits * (n_heads / n_kv);
+  const size_t parts = n_seq * n_kv * (size_t)n_splits * (n_heads / n_kv);
   if (!parts) return LGH_OK;   // (a one-launch path: no partial results)
   c->part_ml = t.up(nullptr, parts * 2);
   c->part_acc = t.up(nullptr, parts * head_dim);
   return c->part_ml && c->part_acc ? LGH_OK : LGH_ALLOCATION_FAILED;
+}
+
+// a step's control words in the batch scratch: positions and cache slots of its sequences (nullptr: position 0, slot = sequence)
+int mb_control(Tmp& t, const int* pos, const int* slot, size_t n_seq) {
+  int p[kMaxBatch] = {}, sl[kMaxBatch];
+  for (size_t i = 0; i < (size_t)kMaxBatch; i++) { sl[i] = (int)i; if (i < n_seq && pos) p[i] = pos[i]; if (i < n_seq && slot) sl[i] = slot[i]; }
+  const BatchScratch& Bs = t.c->batch;
+  if (hipMemcpyAsync(Bs.d_pos, p, sizeof(p), hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+      hipMemcpyAsync(Bs.d_slot, sl, sizeof(sl), hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  return hipStreamSynchronize(t.c->stream) == hipSuccess ? LGH_OK : LGH_OPERATION_FAILED;
+}
+
+// what the multi-sequence entry points ask of their sequences (engine.h: check_seqs), positions and slots as the caller's ints
+bool seqs_ok(size_t n_seq, size_t max_n, const int* slot, size_t n_slots, bool distinct, const int* pos, size_t max_seq) {
+  return check_seqs(n_seq, max_n, slot, n_slots, distinct, [&](size_t i) { return (uint64_t)(int64_t)pos[i]; }, max_seq) == SEQ_OK;
+}
+
+// the bare context as attention_forward_multi reads it, for one layer (0) of cache slots: attn_setup's fields, and of the batch scratch
+// the slots' layout, the sequences' queries, staged rows ([sequence][K row | V row]; k_new: byte caches only) and outputs, the partial
+// results and the control words.  The caller puts its caches into the layer's tables
+int attn_multi_setup(Tmp& t, uint32_t kv_cache_type, const float* q, const float* k_new, const float* v_new, size_t n_heads, size_t n_kv,
+                     size_t head_dim, size_t max_seq, size_t n_seq, const int* pos, const int* slot, int n_splits) {
+  lgh_ctx* c = t.c;
+  BatchScratch& Bs = c->batch;
+  if (int rc = attn_setup(t, kv_cache_type, n_heads, n_kv, head_dim, max_seq, n_splits, n_seq)) return rc;
+  c->d.num_layers = 1;
+  batch_cache_layout(c);
+  const size_t QD = n_heads * head_dim, KD = n_kv * head_dim;
+  Bs.part_ml = c->part_ml;
+  Bs.part_acc = c->part_acc;
+  Bs.q = t.up(q, n_seq * QD);
+  Bs.attn_out = t.up(nullptr, n_seq * QD);
+  Bs.kv_tmp = k_new ? t.up(nullptr, n_seq * 2 * KD) : nullptr;
+  Bs.d_pos = (int*)up_bytes(t, nullptr, kMaxBatch * 4);
+  Bs.d_slot = (int*)up_bytes(t, nullptr, kMaxBatch * 4);
+  if (!Bs.q || !Bs.attn_out || (k_new && !Bs.kv_tmp) || !Bs.d_pos || !Bs.d_slot) return LGH_ALLOCATION_FAILED;
+  for (size_t s = 0; k_new && s < n_seq; s++)
+    if (hipMemcpyAsync(Bs.kv_tmp + s * 2 * KD, k_new + s * KD, KD * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(Bs.kv_tmp + s * 2 * KD + KD, v_new + s * KD, KD * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+      return LGH_OPERATION_FAILED;
+  return mb_control(t, pos, slot, n_seq);
 }
 
 // the current token's K row | V row, side by side as the engine's kv_tmp holds them
@@ -521,33 +565,22 @@ int lgh_op_attention_decode(int device, int path, const float* q, const float* k
 int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads, size_t n_kv,
                                   size_t head_dim, size_t max_seq, size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale,
                                   int n_splits) {
-  // the multi-sequence decode step's attention (engine_batch.hip: attn_multi_launch + attn_combine_multi_launch) over f32 cache slots
+  // the multi-sequence decode step's attention (engine_batch.hip: attention_forward_multi) over f32 cache slots
   Tmp t(device);
   if (t.rc) return t.rc;
   if (!q || !k_cache || !v_cache || !out || !pos || !slot || n_kv == 0 || n_heads % n_kv || head_dim == 0 || max_seq == 0 || max_seq > 0x7FFFFFFFu ||
-      n_slots == 0 || n_seq == 0 || n_seq > (size_t)kMaxBatch || n_splits < 1 || n_splits > 32)
+      n_slots == 0 || n_splits < 1 || n_splits > 32 || !seqs_ok(n_seq, kMaxBatch, slot, n_slots, false, pos, max_seq))
     return LGH_INVALID_ARGUMENT;
-  for (size_t s = 0; s < n_seq; s++)
-    if (pos[s] < 0 || (size_t)pos[s] >= max_seq || slot[s] < 0 || (size_t)slot[s] >= n_slots) return LGH_INVALID_ARGUMENT;
   if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
-  const size_t per_slot = n_kv * max_seq * head_dim, QD = n_heads * head_dim, parts = n_seq * n_heads * (size_t)n_splits;
-  const float* dk = up_cache(t, k_cache, n_slots * per_slot, head_dim);
-  const float* dv = up_cache(t, v_cache, n_slots * per_slot, head_dim);
-  const float* dq = t.up(q, n_seq * QD);
-  float* dout = t.up(nullptr, n_seq * QD);
-  float* part_ml = t.up(nullptr, parts * 2);
-  float* part_acc = t.up(nullptr, parts * head_dim);
-  int* dps = (int*)up_bytes(t, nullptr, 2 * n_seq * 4);
-  if (!dk || !dv || !dq || !dout || !part_ml || !part_acc || !dps) return LGH_ALLOCATION_FAILED;
-  if (hipMemcpyAsync(dps, pos, n_seq * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
-      hipMemcpyAsync(dps + n_seq, slot, n_seq * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  if (attn_multi_launch(dq, dk, dv, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, scale, dps, dps + n_seq, per_slot,
-                        (uint32_t)n_seq, (uint32_t)n_splits, part_ml, part_acc, t.c->stream) != hipSuccess ||
-      attn_combine_multi_launch(part_ml, part_acc, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)n_splits, (uint32_t)n_seq, dout,
-                                nullptr, t.c->stream) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  return t.down(out, dout, n_seq * QD);
+  const size_t cache = n_slots * n_kv * max_seq * head_dim, QD = n_heads * head_dim;
+  int rc;
+  if ((rc = attn_multi_setup(t, LGH_KV_F32, q, nullptr, nullptr, n_heads, n_kv, head_dim, max_seq, n_seq, pos, slot, n_splits))) return rc;
+  BatchScratch& Bs = t.c->batch;
+  Bs.kcache[0] = up_cache(t, k_cache, cache, head_dim);
+  Bs.vcache[0] = up_cache(t, v_cache, cache, head_dim);
+  if (!Bs.kcache[0] || !Bs.vcache[0]) return LGH_ALLOCATION_FAILED;
+  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  return t.down(out, Bs.attn_out, n_seq * QD);
 }
 
 int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
@@ -580,51 +613,30 @@ int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int
 int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
                                const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq,
                                size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale, int n_splits) {
-  // the multi-sequence decode step's attention over byte-cache slots (engine_batch.hip: attn_q8_multi_launch + attn_combine_multi_launch)
+  // the multi-sequence decode step's attention (engine_batch.hip: attention_forward_multi) over byte-cache slots
   Tmp t(device);
   if (t.rc) return t.rc;
   if (kv_cache_type < LGH_KV_INT8 || kv_cache_type > LGH_KV_FP8_E5M2) return LGH_UNSUPPORTED;
   const bool i8 = kv_cache_type == LGH_KV_INT8;
   if (!q || !k_bytes || !v_bytes || !k_new || !v_new || !out || !pos || !slot || (i8 && (!k_scale || !v_scale))) return LGH_INVALID_ARGUMENT;
+  // (two sequences on one slot would both store a row into it)
   if (n_kv == 0 || n_heads % n_kv || head_dim == 0 || max_seq == 0 || max_seq > 0x7FFFFFFFu || n_slots == 0 || n_slots > (size_t)kMaxBatch ||
-      n_seq == 0 || n_seq > (size_t)kMaxBatch || n_splits < 1 || n_splits > 32)
+      n_splits < 1 || n_splits > 32 || !seqs_ok(n_seq, kMaxBatch, slot, n_slots, true, pos, max_seq))
     return LGH_INVALID_ARGUMENT;
-  bool seen[kMaxBatch] = {};
-  for (size_t s = 0; s < n_seq; s++) {   // (two sequences on one slot would both store a row into it)
-    if (pos[s] < 0 || (size_t)pos[s] >= max_seq || slot[s] < 0 || (size_t)slot[s] >= n_slots || seen[slot[s]]) return LGH_INVALID_ARGUMENT;
-    seen[slot[s]] = true;
-  }
   if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
-  const size_t rows = n_slots * n_kv * max_seq, cache = rows * head_dim, QD = n_heads * head_dim, KD = n_kv * head_dim;
-  const size_t parts = n_seq * n_heads * (size_t)n_splits;
-  int8_t* dk = (int8_t*)up_bytes(t, k_bytes, cache);
-  int8_t* dv = (int8_t*)up_bytes(t, v_bytes, cache);
-  float* dks = i8 ? t.up(k_scale, rows) : nullptr;
-  float* dvs = i8 ? t.up(v_scale, rows) : nullptr;
-  const float* dq = t.up(q, n_seq * QD);
-  float* dkv = t.up(nullptr, n_seq * 2 * KD);   // [sequence][K row | V row], as the engine's staging vector
-  float* dout = t.up(nullptr, n_seq * QD);
-  float* part_ml = t.up(nullptr, parts * 2);
-  float* part_acc = t.up(nullptr, parts * head_dim);
-  int* dps = (int*)up_bytes(t, nullptr, 2 * n_seq * 4);
-  if (!dk || !dv || (i8 && (!dks || !dvs)) || !dq || !dkv || !dout || !part_ml || !part_acc || !dps) return LGH_ALLOCATION_FAILED;
-  for (size_t s = 0; s < n_seq; s++)
-    if (hipMemcpyAsync(dkv + s * 2 * KD, k_new + s * KD, KD * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
-        hipMemcpyAsync(dkv + s * 2 * KD + KD, v_new + s * KD, KD * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
-      return LGH_OPERATION_FAILED;
-  if (hipMemcpyAsync(dps, pos, n_seq * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
-      hipMemcpyAsync(dps + n_seq, slot, n_seq * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  if (attn_q8_multi_launch((int)kv_cache_type, dq, dk, dv, dks, dvs, dkv, dkv + KD, (uint32_t)(2 * KD), (uint32_t)n_heads, (uint32_t)n_kv,
-                           (uint32_t)head_dim, (uint32_t)max_seq, scale, dps, dps + n_seq, (uint32_t)n_seq, (uint32_t)n_splits, part_ml, part_acc,
-                           t.c->stream) != hipSuccess ||
-      attn_combine_multi_launch(part_ml, part_acc, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)n_splits, (uint32_t)n_seq, dout,
-                                nullptr, t.c->stream) != hipSuccess)
-    return LGH_OPERATION_FAILED;
+  const size_t rows = n_slots * n_kv * max_seq, cache = rows * head_dim, QD = n_heads * head_dim;
   int rc;
-  if ((rc = down_bytes(t, k_bytes, dk, cache)) || (rc = down_bytes(t, v_bytes, dv, cache))) return rc;
-  if (i8 && ((rc = t.down(k_scale, dks, rows)) || (rc = t.down(v_scale, dvs, rows)))) return rc;
-  return t.down(out, dout, n_seq * QD);
+  if ((rc = attn_multi_setup(t, kv_cache_type, q, k_new, v_new, n_heads, n_kv, head_dim, max_seq, n_seq, pos, slot, n_splits))) return rc;
+  BatchScratch& Bs = t.c->batch;
+  Bs.kq[0] = (uint8_t*)up_bytes(t, k_bytes, cache);
+  Bs.vq[0] = (uint8_t*)up_bytes(t, v_bytes, cache);
+  Bs.kscale[0] = i8 ? t.up(k_scale, rows) : nullptr;
+  Bs.vscale[0] = i8 ? t.up(v_scale, rows) : nullptr;
+  if (!Bs.kq[0] || !Bs.vq[0] || (i8 && (!Bs.kscale[0] || !Bs.vscale[0]))) return LGH_ALLOCATION_FAILED;
+  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if ((rc = down_bytes(t, k_bytes, Bs.kq[0], cache)) || (rc = down_bytes(t, v_bytes, Bs.vq[0], cache))) return rc;
+  if (i8 && ((rc = t.down(k_scale, Bs.kscale[0], rows)) || (rc = t.down(v_scale, Bs.vscale[0], rows)))) return rc;
+  return t.down(out, Bs.attn_out, n_seq * QD);
 }
 
 int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl, const float* k_new,
@@ -1415,8 +1427,8 @@ int lgh_op_pf_moe(int device, uint32_t type_gate_up, const void* w_gate, const v
 }
 
 // ------------------------------------------------------------------------------------------------
-// The multi-sequence step's mat-vec launches (engine_batch.hip: launch_mvb -> build_mv_group -> mvqb_launch, qkv_forward_multi,
-// moe_grouped_forward) one at a time on a bare one-layer context with the engine's own batch scratch (batch_scratch_alloc), for
+// The multi-sequence step's mat-vec launches (engine_batch.hip: linear_multi, qkv_forward_multi, moe_grouped_forward, each through
+// launch_mvb -> build_mv_group -> mvqb_launch) one at a time on a bare one-layer context with the engine's own batch scratch (batch_scratch_alloc), for
 // kernel-level tests (tests/test_gpu_matvec_multi.py).  Test support: not part of the inference API.
 // Before the first launch every vector, image, partial-sum and cache buffer of the scratch holds the NaN pattern 0x7FC0BEEF; the MoE
 // tables hold in-range sentinels the kernels must not leave: counts 0x55, entry lists max_batch * top_k - 1 (the last pair), selections 0x55.
@@ -1455,17 +1467,6 @@ static int mb_test_ctx(Tmp& t, const LayerW& Lw, const MbShape& s, float eps, si
             pf_poison(c, Bs.moe_idx, (size_t)64 * kMaxBatch * 4, np ? (uint32_t)np - 1 : 0u);
   for (const XqBuf& q : c->xqs) ok = ok && pf_poison(c, q.xq, xq_bytes(q.k), kF32) && pf_poison(c, q.ssq, (size_t)ssq_stride_of(q.k) * 4, kF32);
   return ok ? LGH_OK : LGH_OPERATION_FAILED;
-}
-
-// the step's control words: positions and cache slots of its sequences
-static int mb_control(Tmp& t, const int* pos, const int* slot, size_t n_seq) {
-  int p[kMaxBatch] = {}, sl[kMaxBatch];
-  for (size_t i = 0; i < (size_t)kMaxBatch; i++) { sl[i] = (int)i; if (i < n_seq && pos) p[i] = pos[i]; if (i < n_seq && slot) sl[i] = slot[i]; }
-  const BatchScratch& Bs = t.c->batch;
-  if (hipMemcpyAsync(Bs.d_pos, p, sizeof(p), hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
-      hipMemcpyAsync(Bs.d_slot, sl, sizeof(sl), hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  return hipStreamSynchronize(t.c->stream) == hipSuccess ? LGH_OK : LGH_OPERATION_FAILED;
 }
 
 // n vectors of k floats from `base` on: the images their producers in the step would have left (the engine's own producer on each
@@ -1531,29 +1532,11 @@ static int mb_linear_setup(Tmp& t, MbLinear& M, uint32_t type, const void* w, co
   return mb_produce_images(t.c, M.in, (uint32_t)k, n_seq, M.dnw);
 }
 
-// launch A as enqueue_multi makes it
-static int mb_linear_launch(Tmp& t, MbLinear& M, size_t k, size_t n, size_t n_seq, int xq_next) {
-  SegSpec sp;
-  sp.W[0] = &M.WA; sp.x[0] = M.in; sp.out = M.out;
-  sp.xq_next = xq_next; sp.xq_next_nw = xq_next == 2 ? M.dnext : nullptr;
-  const bool img = xq_next != 0 && M.role != 0;
-  const uint32_t os[1] = {(uint32_t)M.out_stride}, rs[1] = {M.role == 1 ? (uint32_t)n : 0u}, xk[1] = {img ? (uint32_t)n : 0u};
-  int cls = LGH_K_OUTPUT;
-  if (M.role == 2) {
-    sp.npass = 2;
-    sp.W[1] = &M.WU;
-    sp.x[1] = M.in;
-    sp.epi = EPI_SWIGLU;
-    cls = LGH_K_GATEUP;
-  } else if (M.role == 1) {
-    sp.epi = EPI_RESID; sp.resid = M.out; sp.bias = M.dbias;
-    cls = LGH_K_WO;
-  } else {
-    sp.epi = EPI_STORE; sp.bias = M.dbias;
-  }
-  if (int rc = launch_mvb(t.c, cls, &sp, 1, M.dnw, (uint32_t)k, (uint32_t)n_seq, os, rs, xk)) return rc;
-  if (M.role) spread_state(t.c, M.out, (uint32_t)n, (uint32_t)n_seq);
-  return LGH_OK;
+// launch A by the step's own linear_multi, as enqueue_multi makes gate | up (SwiGLU), wo (residual) and the output projection (store)
+static int mb_linear_launch(Tmp& t, MbLinear& M, size_t n_seq, int xq_next) {
+  const int cls = M.role == 2 ? LGH_K_GATEUP : M.role == 1 ? LGH_K_WO : LGH_K_OUTPUT;
+  return linear_multi(t.c, cls, M.WA, M.role == 2 ? &M.WU : nullptr, M.in, M.out, (uint32_t)M.out_stride, (uint32_t)n_seq, M.dnw,
+                      M.role == 1 ? M.out : nullptr, M.dbias, xq_next, xq_next == 2 ? M.dnext : nullptr);
 }
 
 int lgh_op_linear_multi(int device, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, size_t n_seq,
@@ -1569,7 +1552,7 @@ int lgh_op_linear_multi(int device, uint32_t type, const void* w, const void* w_
   if ((rc = mb_linear_setup(t, M, type, w, w_up, bias, k, n, n_seq, max_batch, x, norm_w, eps, resid, next_nw, 16))) return rc;
   uint64_t before[3];
   lgh::mvqb_structure_launches(before);
-  if ((rc = mb_linear_launch(t, M, k, n, n_seq, xq_next))) return rc;
+  if ((rc = mb_linear_launch(t, M, n_seq, xq_next))) return rc;
   mb_structures(structures, before);
   const XqBuf* qo = M.role ? xq_find(t.c, M.out) : nullptr;
   const bool used = qo && qo->fresh;
@@ -1598,19 +1581,17 @@ int lgh_op_linear_chain_multi(int device, uint32_t type_a, const void* w_a, cons
   DevWeight WB;
   if ((rc = upload_matrix(t.c, WB, (int)type_b, (uint32_t)n_a, (uint32_t)n_b, 1, -1, w_b, nbb))) return rc;
   if (!mfma_type(WB.type)) return LGH_UNSUPPORTED;
-  if ((rc = mb_linear_launch(t, M, k, n_a, n_seq, xq_next))) return rc;
+  if ((rc = mb_linear_launch(t, M, n_seq, xq_next))) return rc;
   const XqBuf* qa = xq_find(t.c, M.out);
   if (image_used) *image_used = qa && qa->fresh ? 1 : 0;
   const BatchScratch& Bs = t.c->batch;
   const float* bnw = xq_next == 2 ? M.dnext : nullptr;
-  SegSpec sp;
-  sp.W[0] = &WB; sp.x[0] = M.out; sp.epi = EPI_STORE; sp.out = Bs.logits;
-  const uint32_t os[1] = {(uint32_t)n_b}, rs[1] = {0}, xk[1] = {0};
-  if ((rc = launch_mvb(t.c, LGH_K_OUTPUT, &sp, 1, bnw, (uint32_t)n_a, (uint32_t)n_seq, os, rs, xk))) return rc;
+  auto store_b = [&] { return linear_multi(t.c, LGH_K_OUTPUT, WB, nullptr, M.out, Bs.logits, (uint32_t)n_b, (uint32_t)n_seq, bnw); };
+  if ((rc = store_b())) return rc;
   if ((rc = t.down(out_b, Bs.logits, n_seq * n_b))) return rc;
   for (size_t s = 0; s < n_seq; s++) xq_stale(t.c, M.out + s * n_a);
   if ((rc = mb_produce_images(t.c, M.out, (uint32_t)n_a, n_seq, bnw))) return rc;
-  if ((rc = launch_mvb(t.c, LGH_K_OUTPUT, &sp, 1, bnw, (uint32_t)n_a, (uint32_t)n_seq, os, rs, xk))) return rc;
+  if ((rc = store_b())) return rc;
   if ((rc = t.down(out_b_requant, Bs.logits, n_seq * n_b))) return rc;
   return t.down(out_a, M.out, n_seq * n_a);
 }
@@ -1622,14 +1603,9 @@ int lgh_op_qkv_rope_multi(int device, const uint32_t* types, const void* const* 
   Tmp t(device);
   if (t.rc) return t.rc;
   if (!types || !w || !x || !norm_w || !pos || !slot || !q_out || (staged ? !staged_out : (!k_cache || !v_cache)) || hidden == 0 || head_dim == 0 ||
-      head_dim % 2 || n_kv_heads == 0 || n_heads % n_kv_heads || max_seq_len == 0 || max_seq_len > 0x7FFFFFFFu || rope_scale == 0.0f || n_seq == 0 ||
-      n_seq > max_batch || max_batch > (size_t)kMaxBatch)
+      head_dim % 2 || n_kv_heads == 0 || n_heads % n_kv_heads || max_seq_len == 0 || max_seq_len > 0x7FFFFFFFu || rope_scale == 0.0f ||
+      max_batch > (size_t)kMaxBatch || !seqs_ok(n_seq, max_batch, slot, max_batch, true, pos, max_seq_len))
     return LGH_INVALID_ARGUMENT;
-  bool seen[kMaxBatch] = {};
-  for (size_t s = 0; s < n_seq; s++) {
-    if (pos[s] < 0 || (size_t)pos[s] >= max_seq_len || slot[s] < 0 || (size_t)slot[s] >= max_batch || seen[slot[s]]) return LGH_INVALID_ARGUMENT;
-    seen[slot[s]] = true;
-  }
   const size_t QD = n_heads * head_dim, KD = n_kv_heads * head_dim, rows[3] = {QD, KD, KD};
   if (hidden % 256 || QD % 256 || KD % 16 || !mvb_k_ok((uint32_t)hidden)) return LGH_UNSUPPORTED;
   LayerW Lw;

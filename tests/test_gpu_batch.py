@@ -173,6 +173,31 @@ def test_errors_leave_the_slots_unchanged(pkg):
     single.close()
 
 
+def test_step_launch_sequence_by_class(pkg):
+    """The launches of one dense step of 3 sequences, by profiling class (as tests/test_gpu_model.py::test_profiling_stats does for
+    the single-sequence token): per layer one attention + its merge, wo, gate | up and down — whatever the number of sequences —
+    one to three QKV launches (one per kernel family of its matrices), and one embedding, output projection and arg-max per step."""
+    cfg = pkg.make_config("test-dense", max_seq_len=32)
+    eng = pkg.HipGpuInference.from_model(pkg.SynthModel(cfg, mix="Q4_K_M"), 32)
+    try:
+        eng.batch_create(3)
+        eng.forward_multi([0, 1, 2], [5, 6, 7])
+        eng.set_profiling(True)
+        eng.forward_multi([0, 1, 2], [8, 9, 10], want_logits=False, greedy=True)
+        eng.set_profiling(False)
+        k = {name: v["launches"] for name, v in eng.stats()["kernels"].items()}
+        print("launches by class:", k)
+        L = cfg.num_layers
+        for name in ("attn", "attn_combine", "wo", "gate_up", "down"):
+            assert k.get(name) == L, (name, k)
+        assert L <= k.get("qkv", 0) <= 3 * L, k
+        for name in ("embed", "output", "argmax"):
+            assert k.get(name) == 1, (name, k)
+        assert "router" not in k, k
+    finally:
+        eng.close()
+
+
 def test_short_context_variant_of_the_single_engine_agrees_to_rounding(pkg):
     """Below 64 rows the DEFAULT single-sequence engine runs its one-launch attention; the batched step (split attention + merge)
     then differs from it by summation order only."""
