@@ -639,6 +639,7 @@ hipError_t attn_prefill_launch(const float* q, const float* kcache, const float*
                                hipStream_t st) {
   if (n_kv == 0 || n_heads % n_kv || m_tokens == 0) return hipErrorInvalidValue;
   const uint32_t g = n_heads / n_kv;
+  // (read once per process: tests/test_gpu_fresh_env.py::test_valu_prompt_attention holds the VALU kernel to test_prefill's bound)
   static const bool valu = [] { const char* e = std::getenv("LGH_PF_ATTN_VALU"); return e && std::atoi(e) != 0; }();   // (A/B switch: the VALU kernel)
   if (!valu && (head_dim == 128 || head_dim == 64)) {
     return head_dim == 128 ? attn_pf_mfma_go<128, false>(q, kcache, vcache, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, PfTqEpi{})

@@ -78,7 +78,7 @@ struct BatchScratch {
   // element, and (int8) kscale / vscale the rows' scales [slot][kv_head][max_seq]; kv_tmp as above (K row after RoPE | V row), quantized
   // and stored by the attention launch
   std::vector<float*> kscale, vscale;
-  // MoE layers, experts read once per step (top-k <= 2): the (sequence, slot) pairs' activations [pair][ffn] (+ XQ views) and expert
+  // MoE layers, experts read once per step (top-k <= 8): the (sequence, slot) pairs' activations [pair][ffn] (+ XQ views) and expert
   // outputs [pair][hidden]; per expert the number of pairs that chose it and their list
   float *moe_act = nullptr, *moe_tmp = nullptr;
   int *moe_cnt = nullptr, *moe_idx = nullptr;

@@ -69,6 +69,7 @@ static void spread_state(lgh_ctx* c, const float* f32, uint32_t k, uint32_t n) {
 // whatever the step's size) instead of running the FFN sequence by sequence (3 launches per sequence).  Measured on Mixtral-8x7B
 // Q5_K_M, tokens/s grouped vs sequence by sequence: 2 sequences 363 vs 392, 3: 447 vs 421, 4: 520 vs 436, 8: 764 vs 468,
 // 16: 1 030 vs 480 (profiles/r03e_batched_decode.md).
+// (LGH_MOE_GROUP_MIN is read once per process: tests/test_gpu_fresh_env.py runs the sequence-by-sequence form at 3 and 16 sequences)
 uint32_t moe_group_min() {
   static const uint32_t v = [] { const char* e = std::getenv("LGH_MOE_GROUP_MIN"); return e ? (uint32_t)std::max(2, std::atoi(e)) : 3u; }();
   return v;
@@ -359,6 +360,21 @@ int enqueue_multi(lgh_ctx* c, uint32_t n_seq, int mode) {   // mode 0 logits onl
   return LGH_OK;
 }
 
+// the step's control words (tokens, positions, slots) of checked sequences to the device
+static int stage_words(lgh_ctx* c, const uint32_t* slots, const uint32_t* tokens, uint32_t n_seq) {
+  BatchScratch& Bs = c->batch;
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));   // the pinned words below are free again
+  for (uint32_t i = 0; i < n_seq; i++) {
+    Bs.h_ctl[i] = tokens ? (int)tokens[i] : 0;
+    Bs.h_ctl[kMaxBatch + i] = (int)Bs.pos[slots[i]];
+    Bs.h_ctl[2 * kMaxBatch + i] = (int)slots[i];
+  }
+  if (tokens) HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_tokens, Bs.h_ctl, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_pos, Bs.h_ctl + kMaxBatch, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_slot, Bs.h_ctl + 2 * kMaxBatch, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
+  return LGH_OK;
+}
+
 int stage_control(lgh_ctx* c, const uint32_t* slots, const uint32_t* tokens, uint32_t n_seq) {
   BatchScratch& Bs = c->batch;
   const lgh_model_desc& d = c->d;
@@ -373,16 +389,7 @@ int stage_control(lgh_ctx* c, const uint32_t* slots, const uint32_t* tokens, uin
   }
   for (uint32_t i = 0; tokens && i < n_seq; i++)
     if (tokens[i] >= d.vocab_size) return fail(c, LGH_INVALID_ARGUMENT, "token id exceeds vocab size");
-  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));   // the pinned words below are free again
-  for (uint32_t i = 0; i < n_seq; i++) {
-    Bs.h_ctl[i] = tokens ? (int)tokens[i] : 0;
-    Bs.h_ctl[kMaxBatch + i] = (int)Bs.pos[slots[i]];
-    Bs.h_ctl[2 * kMaxBatch + i] = (int)slots[i];
-  }
-  if (tokens) HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_tokens, Bs.h_ctl, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_pos, Bs.h_ctl + kMaxBatch, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(Bs.d_slot, Bs.h_ctl + 2 * kMaxBatch, (size_t)n_seq * 4, hipMemcpyHostToDevice, c->stream));
-  return LGH_OK;
+  return stage_words(c, slots, tokens, n_seq);
 }
 
 int run_multi(lgh_ctx* c, uint32_t n_seq, int mode) {
@@ -546,6 +553,7 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
   if (rc) return rc;
   BatchScratch& Bs = c->batch;
   if (Bs.ready) return Bs.max_batch == max_batch ? LGH_OK : fail(c, LGH_INVALID_ARGUMENT, "lgh_batch_create was already called with another max_batch");
+  if (Bs.max_batch) return fail(c, LGH_OPERATION_FAILED, "an earlier lgh_batch_create failed on this context");   // (its scratch is allocated, not warm)
   if (max_batch == 0 || max_batch > (uint32_t)kMaxBatch) return fail(c, LGH_INVALID_ARGUMENT, "max_batch must be 1 .. 16");
   std::string why;
   if (!batch_weights_ok(c, why)) return fail(c, LGH_UNSUPPORTED, "multi-sequence decode: " + why);
@@ -554,24 +562,37 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
   if ((rc = samp_alloc(c, Bs.samp, max_batch, max_batch))) return rc;
   Bs.samp_cfg.assign(max_batch, lgh_sampler_config_ex{});
   Bs.samp_set.assign(max_batch, 0);
-  Bs.ready = true;
-  // one step through every kernel of the path, eagerly, before any of them is first launched inside a capture (engine.hip:
-  // warm_kernels explains the ROCm trap); it writes row 0 of slot 0's caches, which that slot's first real token overwrites
+  // Every kernel instantiation a captured step of 1 .. max_batch sequences can launch is launched here once, eagerly (engine.hip:
+  // warm_kernels explains the ROCm trap: a kernel first launched inside a capture is not replayed with the graph, and the result is
+  // wrong tokens, not an error).  One sequence; two (the kernels only a step of several sequences launches); then one step per
+  // sequence bucket of the multi-sequence mat-vec (matvec_batch.hip: mvqb2_kernel<MASK, NB, *>, NB = 4 up to 4 sequences, 8 up to 8,
+  // 16 beyond) that max_batch reaches.  Where MoE layers group their pairs by expert (Bs.moe_act), a bucket's step has at least
+  // moe_group_min() sequences if the bucket holds such a count: below it the FFN runs sequence by sequence, and moe_group_kernel,
+  // moe_combine_kernel, the multi-token router and the experts' mat-vec instantiations of that bucket would stay cold.  Mode 1
+  // launches a superset of mode 0's kernels.  A step of n sequences writes row 0 of the caches of slots 0 .. n - 1, which each slot's
+  // first real token overwrites; Bs.pos stays 0.  (tests/test_gpu_fresh_capture.py: captured steps as a process's first GPU work)
   {
-    const uint32_t slot0 = 0, tok0 = 0;
-    if ((rc = stage_control(c, &slot0, &tok0, 1))) return rc;
-    if ((rc = enqueue_multi(c, 1, 1))) return rc;
-    HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
-    if (max_batch >= 2) {   // ... and the kernels only a step of several sequences launches (rows 0 of slots 0 and 1)
-      const uint32_t slots2[2] = {0, 1}, toks2[2] = {0, 0};
-      if ((rc = stage_control(c, slots2, toks2, 2))) return rc;
-      if ((rc = enqueue_multi(c, 2, 1))) return rc;
+    uint32_t slots[kMaxBatch], toks[kMaxBatch];
+    for (uint32_t i = 0; i < (uint32_t)kMaxBatch; i++) { slots[i] = i; toks[i] = 0; }
+    uint32_t warm[5];
+    int n_warm = 0;
+    warm[n_warm++] = 1;
+    const uint32_t lo[3] = {2, 5, 9}, hi[3] = {4, 8, (uint32_t)kMaxBatch};
+    for (int b = 0; b < 3 && max_batch >= lo[b]; b++) {
+      const uint32_t top = std::min(hi[b], max_batch), g = moe_group_min();
+      if (b == 0 || !(Bs.moe_act && lo[b] < g && g <= top)) warm[n_warm++] = lo[b];
+      if (Bs.moe_act && lo[b] < g && g <= top) warm[n_warm++] = g;
+    }
+    for (int i = 0; i < n_warm; i++) {
+      if ((rc = stage_words(c, slots, toks, warm[i]))) return rc;
+      if ((rc = enqueue_multi(c, warm[i], 1))) return rc;
       HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
     }
   }
   // the sampling kernels launched eagerly for every n_seq a step can have
   for (uint32_t n = 1; n <= max_batch; n++)
     if ((rc = samp_warm(c, Bs.samp, Bs.logits, n))) return rc;
+  Bs.ready = true;   // (only now: a context whose warm-up failed takes no step)
   return LGH_OK;
 }
 

@@ -17,7 +17,8 @@
 // Epilogues: store, +residual, SwiGLU pair, RoPE (every sequence at its own position) and the K / V rows into the sequence's
 // own cache slot; optional XQ image of the output for the next launch.  MoE layers: an expert launch works on an INDIRECT
 // entry list (MvBatch::ind_*: the (sequence, top-k slot) pairs that chose the expert, their number read from device memory), so
-// that an expert's matrices are read once per step; below 7 sequences engine_batch.hip runs the FFN sequence by sequence instead.
+// that an expert's matrices are read once per step; below 3 sequences (engine_batch.hip: moe_group_min) the FFN runs sequence by
+// sequence instead.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -505,7 +506,9 @@ static hipError_t mvqb2_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g,
   return hipGetLastError();
 }
 
-// 0: the records-through-LDS structure (mvqb2) from LGH_MVQB2_MIN sequences on (default: measured crossover), 1: never, 2: always
+// A threshold on n_seq: launches of at least LGH_MVQB2_MIN sequences take the records-through-LDS structure (mvqb2), fewer take mvqb.
+// Default 2, the measured crossover: every launch of several sequences; 17 (> kMaxBatch): none.
+// (read once per process: tests/test_gpu_fresh_env.py runs every launch family on mvqb with LGH_MVQB2_MIN=17)
 static uint32_t mvqb2_min_seq() {
   static const uint32_t v = [] {
     const char* e = std::getenv("LGH_MVQB2_MIN");
@@ -516,6 +519,7 @@ static uint32_t mvqb2_min_seq() {
 
 // mvqb2's grid for a launch of `groups` workgroups' worth of units over T k-slices: SEQ (a workgroup walks all slices of its units)
 // when there are enough units to fill the chip with whole rows per workgroup, or a single slice
+// (LGH_MVQB2_SEQ_GROUPS is read once per process: tests/test_gpu_fresh_env.py forces either grid on shapes that default to the other)
 static bool mvqb2_seq_grid(uint32_t groups, uint32_t T) {
   static const uint32_t seq_min_groups = [] { const char* e = std::getenv("LGH_MVQB2_SEQ_GROUPS"); return e ? (uint32_t)std::atoi(e) : 160u; }();
   return groups >= seq_min_groups || T == 1;

@@ -264,6 +264,12 @@ def _pf_kv(d, g):
 @pytest.mark.parametrize("d,g", SHAPES)
 def test_prefill(gpu, d, g):
     """attn_pf_mfma_kernel: token t of the block sees rows <= pos0 + t; its f16 output within the f32 bound plus one f16 rounding."""
+    prefill_case(gpu, d, g)
+
+
+def prefill_case(gpu, d, g, keep=None):
+    """(the test above; returns the output of the case keep = (pos0, m, kind), for tests/fresh_scenarios.py)"""
+    kept = None
     n_kv = _pf_kv(d, g)
     nh = n_kv * g
     max_seq = 2176
@@ -294,7 +300,10 @@ def test_prefill(gpu, d, g):
                 S, vmax = ar.magnitude(q, k, scale, n), float(np.abs(v[:, :n]).max())
                 got = gpu.op_attention_prefill(q, k, v, scale, pos0)
                 W.add("pf_mfma", ar.worst_ratio(got, ref, S, vmax, n, f16=True), f"kind={kind} pos0={pos0} m={m}")
+                if keep == (pos0, m, kind):
+                    kept = got
     W.check()
+    return kept
 
 
 def test_entry_points_refuse(gpu, pkg):

@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _engines(pkg, name, mix, max_seq=96, n_single=1, **kw):
+def _model(pkg, name, mix, max_seq=96, **kw):
     if name == "test-moe-e1024":
         # expert width 1024 (4 blocks of 256 -> 8-wave plans, like Mixtral's 14336): the step reads every selected expert ONCE for
         # all sequences that chose it (engine_batch.hip); "test-moe" (768: 3 blocks) stays on the sequence-by-sequence MoE path
@@ -29,7 +29,11 @@ def _engines(pkg, name, mix, max_seq=96, n_single=1, **kw):
         # Q6_K and two Q5_K down projections under Q5_K_M: the expert-grouped step on the launch plans the full model runs with
         name, kw = "mixtral-8x7b", dict(kw, num_layers=3, vocab_size=4096)
     cfg = pkg.make_config(name, max_seq_len=max_seq, **kw)
-    model = pkg.SynthModel(cfg, mix=mix)
+    return cfg, pkg.SynthModel(cfg, mix=mix)
+
+
+def _engines(pkg, name, mix, max_seq=96, n_single=1, **kw):
+    cfg, model = _model(pkg, name, mix, max_seq, **kw)
     multi = pkg.HipGpuInference.from_model(model, max_seq)
     # attn_direct=255: the single-sequence engine switches to a one-launch attention (another summation tree) for contexts of up
     # to 64 rows; the multi-sequence step always runs the split attention + merge, the structure of every longer context.  The
@@ -55,6 +59,11 @@ def _history(cfg, seq, n):
 def test_every_sequence_gets_the_single_sequence_logits_bitwise(pkg, name, mix, B):
     """B sequences with different histories and RAGGED lengths, token by token through lgh_forward_multi; each sequence's logits
     at every step equal, bit for bit, those of a single-sequence engine fed the same history."""
+    bitwise_logits_case(pkg, name, mix, B)
+
+
+def bitwise_logits_case(pkg, name, mix, B):
+    """(the test above; tests/fresh_scenarios.py runs it in processes whose environment selects other kernels)"""
     cfg, model, multi, (single,) = _engines(pkg, name, mix)
     multi.batch_create(B)
     lens = [3 + (5 * s) % 11 for s in range(B)]                   # sequence s joins the batch `lens[s]` steps before the end
