@@ -537,20 +537,27 @@ int lgh_op_attention(int device, const float* q, const float* k, const float* v,
  * Backend::attention_cached (ops.rs:1479-1537) over the f32 cache [n_kv_heads][max_seq_len][head_dim], rows 0..pos already
  * stored (as after the engine's kv_store).  path 0: split + merge (4 or 8 waves per workgroup, chosen from max_seq_len as in
  * the engine; n_splits 1..32); path 1: the single-launch kernel of short contexts; path 2: the kernel of any head_dim / group
- * size (max_seq_len <= 38400). */
+ * size (max_seq_len <= 38400).
+ *
+ * image_out (every entry point of this group; may be NULL): wo's input as the launch that writes `out` leaves it for the mat-vec, the XQ
+ * image of `out` (1280 bytes per 256 elements, rounded up).  One sequence: (n_heads * head_dim + 255) / 256 * 1280 bytes; path 2
+ * writes none and answers LGH_INVALID_ARGUMENT when asked.  The *_multi entry points: n_seq + 1 images, one per sequence at the
+ * step's stride (the size of one image), over a buffer filled with the word 0x7FC0BEEF first: the image behind the last sequence
+ * comes back as that pattern.  Without image_out the launches are those of a caller that wants no image, and `out` has the same bits. */
 int lgh_op_attention_decode(int device, int path, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
-                            size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos, int n_splits);
+                            size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos, int n_splits,
+                            uint8_t* image_out);
 /* The same split + merge as the multi-sequence decode step runs it: sequence s of n_seq (<= 16) attends, with q [n_seq][n_heads][head_dim],
  * to rows 0..pos[s] of cache slot slot[s]; caches [n_slots][n_kv_heads][max_seq_len][head_dim]; out [n_seq][n_heads][head_dim]. */
 int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
                                   size_t n_kv_heads, size_t head_dim, size_t max_seq_len, size_t n_slots, size_t n_seq, const int* pos,
-                                  const int* slot, float scale, int n_splits);
+                                  const int* slot, float scale, int n_splits, uint8_t* image_out);
 /* QuantizedKVCache (kv_quantized.rs:143-300, 385-565): kv_cache_type LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2.  k_bytes / v_bytes
  * [n_kv_heads][max_seq_len][head_dim] and (int8 only; may be NULL otherwise) k_scale / v_scale [n_kv_heads][max_seq_len] are in / out:
  * rows 0..pos-1 are read, row `pos` comes back as the launch quantized and stored k_new / v_new [n_kv_heads][head_dim]. */
 int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
                          const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv_heads, size_t head_dim,
-                         size_t max_seq_len, float scale, size_t pos, int n_splits);
+                         size_t max_seq_len, float scale, size_t pos, int n_splits, uint8_t* image_out);
 /* The same over the byte-cache slots of a multi-sequence decode step: sequence s of n_seq (1..16) attends, with q [n_seq][n_heads][head_dim],
  * to rows 0..pos[s]-1 of slot slot[s] and to its own k_new / v_new [n_seq][n_kv_heads][head_dim], which the launch quantizes and stores
  * at row pos[s] of that slot.  k_bytes / v_bytes [n_slots][n_kv_heads][max_seq_len][head_dim] and (int8 only; may be NULL otherwise)
@@ -561,14 +568,25 @@ int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int
 int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale,
                                float* v_scale, const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv_heads,
                                size_t head_dim, size_t max_seq_len, size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale,
-                               int n_splits);
+                               int n_splits, uint8_t* image_out);
 /* TurboQuantKVCache::write_kv + attention_layer (kv_turboquant.rs:88-201): kv_cache_type LGH_KV_TQ2 / TQ3 / TQ2_QJL / TQ3_QJL.
  * k_codes / v_codes [n_kv_heads][max_seq_len][row bytes] and, for the QJL types, k_qjl [n_kv_heads][max_seq_len][head_dim / 32 + 1]
  * words (sign bits, then the residual norm's bits) are in / out: row `pos` comes back as the launch compressed k_new / v_new.
  * signs [n_kv_heads][k, v][head_dim] (+1 / -1); qjl_matrices [n_kv_heads][head_dim][head_dim] (QJL types; NULL otherwise). */
 int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl,
                         const float* k_new, const float* v_new, const float* signs, const float* qjl_matrices, float* out, size_t n_heads,
-                        size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos, int n_splits);
+                        size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos, int n_splits, uint8_t* image_out);
+/* The same over the TurboQuant cache slots of a multi-sequence decode step: sequence s of n_seq (1..16) attends, with q [n_seq][n_heads][head_dim],
+ * to rows 0..pos[s]-1 of slot slot[s] and to its own k_new / v_new [n_seq][n_kv_heads][head_dim], which the launch compresses into row
+ * pos[s] of that slot.  k_codes / v_codes [n_slots][n_kv_heads][max_seq_len][row bytes] and (QJL types) k_qjl
+ * [n_slots][n_kv_heads][max_seq_len][head_dim / 32 + 1] are in / out; signs and qjl_matrices as above; out [n_seq][n_heads][head_dim].
+ * Every sequence's output is bit-identical to lgh_op_attention_tq on its slot alone with the same n_splits.  LGH_UNSUPPORTED: a
+ * kv_cache_type that is not TurboQuant, a shape without a kernel; LGH_INVALID_ARGUMENT: pos[s] >= max_seq_len, slot[s] >= n_slots, a
+ * slot listed twice, n_seq or n_slots outside 1..16, n_splits outside 1..32, a sign other than +1 / -1. */
+int lgh_op_attention_tq_multi(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl,
+                              const float* k_new, const float* v_new, const float* signs, const float* qjl_matrices, float* out, size_t n_heads,
+                              size_t n_kv_heads, size_t head_dim, size_t max_seq_len, size_t n_slots, size_t n_seq, const int* pos,
+                              const int* slot, float scale, int n_splits, uint8_t* image_out);
 /* Causal Backend::attention (ops.rs:1353-1472) of m_tokens prompt tokens at positions pos0.. as the batched prefill runs it:
  * q [m_tokens][n_heads][head_dim]; the f32 caches hold rows 0..pos0 + m_tokens - 1; out [m_tokens][n_heads * head_dim] = the
  * kernel's f16 results widened to f32.  m_tokens <= 128, n_heads * head_dim % 256 == 0, pos0 + m_tokens <= max_seq_len. */

@@ -221,6 +221,7 @@ int launch_mvb(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float*
 bool mvb_k_ok(uint32_t k);                           // a [.., k] matrix plans to the 8-wave workgroups the multi-sequence kernels run
 uint32_t xq_stride_of(uint32_t k);                   // bytes / floats between two sequences' images and sum-of-squares partials
 uint32_t ssq_stride_of(uint32_t k);
+int register_views(lgh_ctx* c, float* f32, uint8_t* xq, float* ssq, uint32_t k, uint32_t n);   // n sequences' views of a batch vector, at those strides
 uint64_t batch_part_floats(const lgh_ctx* c, uint32_t max_batch);
 void batch_cache_layout(lgh_ctx* c);                 // the distances between two slots' caches of a layer, its (empty) per-layer cache tables
 int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch);

@@ -517,6 +517,33 @@ float* up_cache(Tmp& t, const float* host, size_t n, size_t head_dim) {
   return d;
 }
 
+// wo's input as the merge leaves it (xq.h), when an attention entry point is asked for it.  One sequence: attention_forward registered
+// the image of attn_out through xq_get; its xq_bytes(qd) bytes come back
+int attn_image_down(Tmp& t, const float* attn_out, size_t qd, uint8_t* image_out) {
+  const XqBuf* qa = xq_find(t.c, attn_out);
+  if (!qa || !qa->fresh) return LGH_OPERATION_FAILED;
+  return down_bytes(t, image_out, qa->xq, xq_bytes(qd));
+}
+
+// Several sequences: views of Bs.attn_out for n_seq + 1 sequences at the step's stride, as batch_scratch_alloc registers them for
+// max_batch, every byte the scratch poison 0x7FC0BEEF: the view behind the last sequence must come back untouched
+int attn_multi_images(Tmp& t, size_t n_seq, size_t qd) {
+  const size_t n = n_seq + 1, xb = n * xq_stride_of((uint32_t)qd), sf = n * ssq_stride_of((uint32_t)qd);
+  uint8_t* xq = (uint8_t*)up_bytes(t, nullptr, xb);
+  float* ssq = t.up(nullptr, sf);
+  if (!xq || !ssq) return LGH_ALLOCATION_FAILED;
+  if (hipMemsetD32Async((hipDeviceptr_t)xq, (int)0x7FC0BEEFu, xb / 4, t.c->stream) != hipSuccess ||
+      hipMemsetD32Async((hipDeviceptr_t)ssq, (int)0x7FC0BEEFu, sf, t.c->stream) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  return register_views(t.c, t.c->batch.attn_out, xq, ssq, (uint32_t)qd, (uint32_t)n);
+}
+
+int attn_multi_images_down(Tmp& t, size_t n_seq, size_t qd, uint8_t* image_out) {
+  const XqBuf* qa = xq_find(t.c, t.c->batch.attn_out);
+  if (!qa || !qa->fresh) return LGH_OPERATION_FAILED;
+  return down_bytes(t, image_out, qa->xq, (n_seq + 1) * xq_stride_of((uint32_t)qd));
+}
+
 float half_to_float(uint16_t h) {
   const uint32_t s = (uint32_t)(h >> 15) << 31, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
   float v;
@@ -535,13 +562,13 @@ float half_to_float(uint16_t h) {
 extern "C" {
 
 int lgh_op_attention_decode(int device, int path, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads,
-                            size_t n_kv, size_t head_dim, size_t max_seq, float scale, size_t pos, int n_splits) {
+                            size_t n_kv, size_t head_dim, size_t max_seq, float scale, size_t pos, int n_splits, uint8_t* image_out) {
   // Backend::attention_cached (ops.rs:1479-1537) as the engine's decode step runs it over the f32 cache
   Tmp t(device);
   if (t.rc) return t.rc;
   if (!q || !k_cache || !v_cache || !out || n_kv == 0 || n_heads % n_kv || head_dim == 0 || pos >= max_seq || max_seq > 0x7FFFFFFFu)
     return LGH_INVALID_ARGUMENT;
-  if (path < 0 || path > 2) return LGH_INVALID_ARGUMENT;
+  if (path < 0 || path > 2 || (path == 2 && image_out)) return LGH_INVALID_ARGUMENT;   // (the any-shape kernel leaves no image)
   const size_t g = n_heads / n_kv, cache = n_kv * max_seq * head_dim;
   const bool fast = attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)g);
   if (path != 2 && !fast) return LGH_UNSUPPORTED;
@@ -558,13 +585,14 @@ int lgh_op_attention_decode(int device, int path, const float* q, const float* k
   // kernel of the shapes the others do not cover (engine: every token of such a model), here on any head_dim / group size
   t.c->attn_direct = path == 1;
   t.c->attn_generic = path == 2;
-  if (attention_forward(t.c, Lw, 0, v, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (attention_forward(t.c, Lw, 0, v, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_image_down(t, v.attn_out, n_heads * head_dim, image_out))) return rc;
   return t.down(out, v.attn_out, n_heads * head_dim);
 }
 
 int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads, size_t n_kv,
                                   size_t head_dim, size_t max_seq, size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale,
-                                  int n_splits) {
+                                  int n_splits, uint8_t* image_out) {
   // the multi-sequence decode step's attention (engine_batch.hip: attention_forward_multi) over f32 cache slots
   Tmp t(device);
   if (t.rc) return t.rc;
@@ -579,13 +607,15 @@ int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cac
   Bs.kcache[0] = up_cache(t, k_cache, cache, head_dim);
   Bs.vcache[0] = up_cache(t, v_cache, cache, head_dim);
   if (!Bs.kcache[0] || !Bs.vcache[0]) return LGH_ALLOCATION_FAILED;
-  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_multi_images(t, n_seq, QD))) return rc;
+  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_multi_images_down(t, n_seq, QD, image_out))) return rc;
   return t.down(out, Bs.attn_out, n_seq * QD);
 }
 
 int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
                          const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq,
-                         float scale, size_t pos, int n_splits) {
+                         float scale, size_t pos, int n_splits, uint8_t* image_out) {
   // QuantizedKVCache (kv_quantized.rs:143-300): the attention launch also quantizes the current rows and stores them at `pos`
   Tmp t(device);
   if (t.rc) return t.rc;
@@ -604,7 +634,8 @@ int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int
   if (!v.q || !v.kv_tmp || !Lw.k8 || !Lw.v8 || (i8 && (!Lw.kscale || !Lw.vscale)) || !v.attn_out) return LGH_ALLOCATION_FAILED;
   int rc;
   if ((rc = attn_setup(t, kv_cache_type, n_heads, n_kv, head_dim, max_seq, n_splits)) || (rc = set_pos(t, pos))) return rc;
-  if (attention_forward(t.c, Lw, 0, v, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (attention_forward(t.c, Lw, 0, v, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_image_down(t, v.attn_out, n_heads * head_dim, image_out))) return rc;
   if ((rc = down_bytes(t, k_bytes, Lw.k8, cache)) || (rc = down_bytes(t, v_bytes, Lw.v8, cache))) return rc;
   if (i8 && ((rc = t.down(k_scale, Lw.kscale, rows)) || (rc = t.down(v_scale, Lw.vscale, rows)))) return rc;
   return t.down(out, v.attn_out, n_heads * head_dim);
@@ -612,7 +643,7 @@ int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int
 
 int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
                                const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq,
-                               size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale, int n_splits) {
+                               size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale, int n_splits, uint8_t* image_out) {
   // the multi-sequence decode step's attention (engine_batch.hip: attention_forward_multi) over byte-cache slots
   Tmp t(device);
   if (t.rc) return t.rc;
@@ -633,7 +664,9 @@ int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* 
   Bs.kscale[0] = i8 ? t.up(k_scale, rows) : nullptr;
   Bs.vscale[0] = i8 ? t.up(v_scale, rows) : nullptr;
   if (!Bs.kq[0] || !Bs.vq[0] || (i8 && (!Bs.kscale[0] || !Bs.vscale[0]))) return LGH_ALLOCATION_FAILED;
-  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_multi_images(t, n_seq, QD))) return rc;
+  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_multi_images_down(t, n_seq, QD, image_out))) return rc;
   if ((rc = down_bytes(t, k_bytes, Bs.kq[0], cache)) || (rc = down_bytes(t, v_bytes, Bs.vq[0], cache))) return rc;
   if (i8 && ((rc = t.down(k_scale, Bs.kscale[0], rows)) || (rc = t.down(v_scale, Bs.vscale[0], rows)))) return rc;
   return t.down(out, Bs.attn_out, n_seq * QD);
@@ -641,7 +674,7 @@ int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* 
 
 int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl, const float* k_new,
                         const float* v_new, const float* signs, const float* qjl_matrices, float* out, size_t n_heads, size_t n_kv, size_t head_dim,
-                        size_t max_seq, float scale, size_t pos, int n_splits) {
+                        size_t max_seq, float scale, size_t pos, int n_splits, uint8_t* image_out) {
   // TurboQuantKVCache::write_kv + attention_layer (kv_turboquant.rs:88-201): the split launch compresses and stores the current
   // rows, the merge inverts the V rotation
   Tmp t(device);
@@ -666,10 +699,48 @@ int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint
   if (!v.q || !v.kv_tmp || !t.c->tq_signs || !Lw.k8 || !Lw.v8 || (qjl && (!Lw.kx || !t.c->tq_qjl)) || !v.attn_out) return LGH_ALLOCATION_FAILED;
   int rc;
   if ((rc = attn_setup(t, kv_cache_type, n_heads, n_kv, d, max_seq, n_splits)) || (rc = set_pos(t, pos))) return rc;
-  if (attention_forward(t.c, Lw, 0, v, scale, false)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (attention_forward(t.c, Lw, 0, v, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_image_down(t, v.attn_out, n_heads * d, image_out))) return rc;
   if ((rc = down_bytes(t, k_codes, Lw.k8, cb)) || (rc = down_bytes(t, v_codes, Lw.v8, cb))) return rc;
   if (qjl && (rc = down_bytes(t, k_qjl, Lw.kx, xw * 4))) return rc;
   return t.down(out, v.attn_out, n_heads * d);
+}
+
+int lgh_op_attention_tq_multi(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl,
+                              const float* k_new, const float* v_new, const float* signs, const float* qjl_matrices, float* out, size_t n_heads,
+                              size_t n_kv, size_t head_dim, size_t max_seq, size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale,
+                              int n_splits, uint8_t* image_out) {
+  // the multi-sequence decode step's attention (engine_batch.hip: attention_forward_multi) over TurboQuant cache slots
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!kv_is_tq(kv_cache_type)) return LGH_UNSUPPORTED;
+  const bool qjl = kv_is_qjl(kv_cache_type);
+  const int bits = kv_tq_bits(kv_cache_type);
+  if (!q || !k_codes || !v_codes || !k_new || !v_new || !signs || !out || !pos || !slot || (qjl && (!k_qjl || !qjl_matrices))) return LGH_INVALID_ARGUMENT;
+  // (two sequences on one slot would both store a row into it)
+  if (n_kv == 0 || n_heads % n_kv || head_dim == 0 || max_seq == 0 || max_seq > 0x7FFFFFFFu || n_slots == 0 || n_slots > (size_t)kMaxBatch ||
+      n_splits < 1 || n_splits > 32 || !seqs_ok(n_seq, kMaxBatch, slot, n_slots, true, pos, max_seq))
+    return LGH_INVALID_ARGUMENT;
+  const size_t d = head_dim, rows = n_slots * n_kv * max_seq, QD = n_heads * d;
+  if (!attn_shape_has_fast_kernel((uint32_t)d, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
+  for (size_t i = 0; i < n_kv * 2 * d; i++)
+    if (signs[i] != 1.0f && signs[i] != -1.0f) return LGH_INVALID_ARGUMENT;
+  const size_t cb = rows * tq_row_bytes_host(bits, (uint32_t)d), xw = rows * (d / 32 + 1);
+  int rc;
+  if ((rc = attn_multi_setup(t, kv_cache_type, q, k_new, v_new, n_heads, n_kv, d, max_seq, n_seq, pos, slot, n_splits))) return rc;
+  BatchScratch& Bs = t.c->batch;
+  Bs.kq[0] = (uint8_t*)up_bytes(t, k_codes, cb);
+  Bs.vq[0] = (uint8_t*)up_bytes(t, v_codes, cb);
+  Bs.kx[0] = qjl ? (uint32_t*)up_bytes(t, k_qjl, xw * 4) : nullptr;
+  t.c->tq_signs = t.up(signs, n_kv * 2 * d);   // (the one layer of a context that owns layer 0: its signs and matrices are the context's first)
+  t.c->tq_qjl = qjl ? t.up(qjl_matrices, n_kv * d * d) : nullptr;
+  if (!Bs.kq[0] || !Bs.vq[0] || !t.c->tq_signs || (qjl && (!Bs.kx[0] || !t.c->tq_qjl))) return LGH_ALLOCATION_FAILED;
+  if (image_out && (rc = attn_multi_images(t, n_seq, QD))) return rc;
+  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_multi_images_down(t, n_seq, QD, image_out))) return rc;
+  if ((rc = down_bytes(t, k_codes, Bs.kq[0], cb)) || (rc = down_bytes(t, v_codes, Bs.vq[0], cb))) return rc;
+  if (qjl && (rc = down_bytes(t, k_qjl, Bs.kx[0], xw * 4))) return rc;
+  return t.down(out, Bs.attn_out, n_seq * QD);
 }
 
 // an XH matrix's first m rows, un-swizzled and widened to f32: out [m][k]

@@ -45,7 +45,7 @@ ABI_SYMBOLS = (
     "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches",
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
     "lgh_op_linear_multi", "lgh_op_linear_chain_multi", "lgh_op_qkv_rope_multi", "lgh_op_moe_multi", "lgh_debug_mvqb_structures",
-    "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_attention_kv8_multi",
+    "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_attention_kv8_multi", "lgh_op_attention_tq_multi",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -239,11 +239,12 @@ def load_library() -> C.CDLL:
         "lgh_batch_set_sampler_ex": (C.c_int, [vp, u32, C.POINTER(SamplerConfigEx)]),
         "lgh_get_sampler_mu": (C.c_int, [vp, C.c_int, C.POINTER(f32)]),
         "lgh_op_sample_ex": (C.c_int, [C.c_int, vp, sz, C.POINTER(SamplerConfigEx), vp, sz, vp, f32, f32, C.POINTER(u32), C.POINTER(f32)]),
-        "lgh_op_attention_decode": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
-        "lgh_op_attention_decode_multi": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, f32, C.c_int]),
-        "lgh_op_attention_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
-        "lgh_op_attention_kv8_multi": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, f32, C.c_int]),
-        "lgh_op_attention_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int]),
+        "lgh_op_attention_decode": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int, vp]),
+        "lgh_op_attention_decode_multi": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, f32, C.c_int, vp]),
+        "lgh_op_attention_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int, vp]),
+        "lgh_op_attention_kv8_multi": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, f32, C.c_int, vp]),
+        "lgh_op_attention_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, C.c_int, vp]),
+        "lgh_op_attention_tq_multi": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, f32, C.c_int, vp]),
         "lgh_op_attention_prefill": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
         "lgh_op_pf_tq_store": (C.c_int, [C.c_int, u32, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp]),
         "lgh_op_attention_prefill_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
@@ -842,26 +843,37 @@ def op_attention_cached(q, k_cache, v_cache, scale: float, kv_len: int, n_splits
 ATTN_SPLIT, ATTN_DIRECT, ATTN_ANY = 0, 1, 2   # lgh_op_attention_decode paths
 
 
-def op_attention_decode(path: int, q, k_cache, v_cache, scale: float, pos: int, n_splits: int = 8, device: int = 0) -> np.ndarray:
+def _attn_image(q, n_images: int = 1):
+    """The buffer for the XQ images of attention outputs of q's last two axes [nh, d]: [n_images, bytes] (one image: [bytes])."""
+    nb = _xq_bytes(q.shape[-2] * q.shape[-1])
+    return np.zeros(nb if n_images == 1 else (n_images, nb), np.uint8)
+
+
+def op_attention_decode(path: int, q, k_cache, v_cache, scale: float, pos: int, n_splits: int = 8, device: int = 0, *, image: bool = False):
     """One decode step's attention over the f32 cache (rows 0..pos stored) on the engine path `path`: ATTN_SPLIT (split + merge),
-    ATTN_DIRECT (one launch) or ATTN_ANY (any head_dim / group size).  q [nh, d]; caches [nkv, max_seq, d]; pos via the device word."""
+    ATTN_DIRECT (one launch) or ATTN_ANY (any head_dim / group size).  q [nh, d]; caches [nkv, max_seq, d]; pos via the device word.
+    image: -> (out, wo's input as the launch leaves it: the XQ image of out, uint8 [bytes]); ATTN_ANY writes none (InvalidArgument)."""
     q, kc, vc = _f32(q), _f32(k_cache), _f32(v_cache)
     out = np.empty_like(q)
+    img = _attn_image(q) if image else None
     _chk(load_library().lgh_op_attention_decode(device, path, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, out.ctypes.data, q.shape[0],
-                                                kc.shape[0], q.shape[1], kc.shape[1], scale, pos, n_splits), "attention_decode")
-    return out
+                                                kc.shape[0], q.shape[1], kc.shape[1], scale, pos, n_splits, _ptr(img)), "attention_decode")
+    return (out, img) if image else out
 
 
-def op_attention_decode_multi(q, k_cache, v_cache, scale: float, pos, slot, n_splits: int = 8, device: int = 0) -> np.ndarray:
+def op_attention_decode_multi(q, k_cache, v_cache, scale: float, pos, slot, n_splits: int = 8, device: int = 0, *, image: bool = False):
     """The multi-sequence decode step's split + merge attention: sequence s attends to rows 0..pos[s] of cache slot slot[s].
-    q [n_seq, nh, d]; caches [n_slots, nkv, max_seq, d]; -> [n_seq, nh, d]."""
+    q [n_seq, nh, d]; caches [n_slots, nkv, max_seq, d]; -> [n_seq, nh, d].
+    image: -> (out, images uint8 [n_seq + 1, bytes]): every sequence's XQ image of its output, and the one behind the last sequence,
+    which no launch may touch (the buffer held the word 0x7FC0BEEF throughout before the launch)."""
     q, kc, vc = _f32(q), _f32(k_cache), _f32(v_cache)
     pos, slot = np.ascontiguousarray(pos, dtype=np.int32), np.ascontiguousarray(slot, dtype=np.int32)
     out = np.empty_like(q)
+    img = _attn_image(q, q.shape[0] + 1) if image else None
     _chk(load_library().lgh_op_attention_decode_multi(device, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, out.ctypes.data, q.shape[1],
                                                       kc.shape[1], q.shape[2], kc.shape[2], kc.shape[0], q.shape[0], pos.ctypes.data,
-                                                      slot.ctypes.data, scale, n_splits), "attention_decode_multi")
-    return out
+                                                      slot.ctypes.data, scale, n_splits, _ptr(img)), "attention_decode_multi")
+    return (out, img) if image else out
 
 
 def _ptr(a):
@@ -1166,29 +1178,32 @@ def op_pf_moe(type_gate_up: int, w_gate, w_up, type_down: int, w_down, router, n
 
 
 def op_attention_kv8(kv_cache_type: int, q, k_bytes, v_bytes, k_scale, v_scale, k_new, v_new, scale: float, pos: int, n_splits: int = 8,
-                     device: int = 0):
+                     device: int = 0, *, image: bool = False):
     """One decode step's attention over an int8 / FP8 cache (KV_INT8 / KV_FP8_E4M3 / KV_FP8_E5M2): bytes [nkv, max_seq, d] (uint8 or
     int8), scales [nkv, max_seq] (int8 only, else None); the launch stores k_new / v_new [nkv, d] at row `pos`.
-    -> (out [nh, d], k_bytes, v_bytes, k_scale, v_scale) after the call (copies; the inputs are untouched)."""
+    -> (out [nh, d], k_bytes, v_bytes, k_scale, v_scale) after the call (copies; the inputs are untouched); image: and the XQ image of
+    out (op_attention_decode) as a last element."""
     q, kn, vn = _f32(q), _f32(k_new), _f32(v_new)
     kb, vb = np.array(k_bytes, dtype=np.uint8, copy=True), np.array(v_bytes, dtype=np.uint8, copy=True)
     i8 = kv_cache_type == KV_INT8
     ks = np.array(k_scale, dtype=np.float32, copy=True) if i8 else None
     vs = np.array(v_scale, dtype=np.float32, copy=True) if i8 else None
     out = np.empty_like(q)
+    img = _attn_image(q) if image else None
     _chk(load_library().lgh_op_attention_kv8(device, kv_cache_type, q.ctypes.data, kb.ctypes.data, vb.ctypes.data,
                                              ks.ctypes.data if i8 else None, vs.ctypes.data if i8 else None, kn.ctypes.data, vn.ctypes.data,
-                                             out.ctypes.data, q.shape[0], kb.shape[0], q.shape[1], kb.shape[1], scale, pos, n_splits),
+                                             out.ctypes.data, q.shape[0], kb.shape[0], q.shape[1], kb.shape[1], scale, pos, n_splits, _ptr(img)),
          "attention_kv8")
-    return out, kb, vb, ks, vs
+    return (out, kb, vb, ks, vs, img) if image else (out, kb, vb, ks, vs)
 
 
 def op_attention_kv8_multi(kv_cache_type: int, q, k_bytes, v_bytes, k_scale, v_scale, k_new, v_new, scale: float, pos, slot, n_splits: int = 8,
-                           device: int = 0):
+                           device: int = 0, *, image: bool = False):
     """The multi-sequence decode step's attention over int8 / FP8 cache slots: sequence s attends to rows 0..pos[s]-1 of slot slot[s]
     and to its own k_new[s] / v_new[s], which the launch stores at row pos[s] of that slot.  q [n_seq, nh, d]; bytes
     [n_slots, nkv, max_seq, d]; scales [n_slots, nkv, max_seq] (int8 only, else None); k_new / v_new [n_seq, nkv, d].
-    -> (out [n_seq, nh, d], k_bytes, v_bytes, k_scale, v_scale) after the call (copies; the inputs are untouched)."""
+    -> (out [n_seq, nh, d], k_bytes, v_bytes, k_scale, v_scale) after the call (copies; the inputs are untouched); image: and the
+    n_seq + 1 XQ images (op_attention_decode_multi) as a last element."""
     q, kn, vn = _f32(q), _f32(k_new), _f32(v_new)
     kb, vb = np.array(k_bytes, dtype=np.uint8, copy=True), np.array(v_bytes, dtype=np.uint8, copy=True)
     pos, slot = np.ascontiguousarray(pos, dtype=np.int32), np.ascontiguousarray(slot, dtype=np.int32)
@@ -1198,29 +1213,57 @@ def op_attention_kv8_multi(kv_cache_type: int, q, k_bytes, v_bytes, k_scale, v_s
     ks = np.array(k_scale, dtype=np.float32, copy=True) if i8 else None
     vs = np.array(v_scale, dtype=np.float32, copy=True) if i8 else None
     out = np.empty_like(q)
+    img = _attn_image(q, q.shape[0] + 1) if image else None
     _chk(load_library().lgh_op_attention_kv8_multi(device, kv_cache_type, q.ctypes.data, kb.ctypes.data, vb.ctypes.data, _ptr(ks), _ptr(vs),
                                                    kn.ctypes.data, vn.ctypes.data, out.ctypes.data, q.shape[1], kb.shape[1], q.shape[2],
-                                                   kb.shape[2], kb.shape[0], len(pos), pos.ctypes.data, slot.ctypes.data, scale, n_splits),
-         "attention_kv8_multi")
-    return out, kb, vb, ks, vs
+                                                   kb.shape[2], kb.shape[0], len(pos), pos.ctypes.data, slot.ctypes.data, scale, n_splits,
+                                                   _ptr(img)), "attention_kv8_multi")
+    return (out, kb, vb, ks, vs, img) if image else (out, kb, vb, ks, vs)
 
 
 def op_attention_tq(kv_cache_type: int, q, k_codes, v_codes, k_qjl, k_new, v_new, signs, qjl_matrices, scale: float, pos: int,
-                    n_splits: int = 8, device: int = 0):
+                    n_splits: int = 8, device: int = 0, *, image: bool = False):
     """One decode step's attention over a TurboQuant cache (KV_TQ2 / TQ3 / TQ2_QJL / TQ3_QJL): codes [nkv, max_seq, row bytes];
     k_qjl [nkv, max_seq, d / 32 + 1] uint32 words (QJL types, else None); signs [nkv, 2, d]; qjl_matrices [nkv, d, d] (QJL types).
-    The launch compresses k_new / v_new [nkv, d] into row `pos`.  -> (out [nh, d], k_codes, v_codes, k_qjl) after the call (copies)."""
+    The launch compresses k_new / v_new [nkv, d] into row `pos`.  -> (out [nh, d], k_codes, v_codes, k_qjl) after the call (copies);
+    image: and the XQ image of out (op_attention_decode) as a last element."""
     q, kn, vn, sg = _f32(q), _f32(k_new), _f32(v_new), _f32(signs)
     kc, vc = np.array(k_codes, dtype=np.uint8, copy=True), np.array(v_codes, dtype=np.uint8, copy=True)
     qjl = kv_cache_type in (KV_TQ2_QJL, KV_TQ3_QJL)
     kx = np.array(k_qjl, dtype=np.uint32, copy=True) if qjl else None
     S = _f32(qjl_matrices) if qjl else None
     out = np.empty_like(q)
+    img = _attn_image(q) if image else None
     _chk(load_library().lgh_op_attention_tq(device, kv_cache_type, q.ctypes.data, kc.ctypes.data, vc.ctypes.data,
                                             kx.ctypes.data if qjl else None, kn.ctypes.data, vn.ctypes.data, sg.ctypes.data,
                                             S.ctypes.data if qjl else None, out.ctypes.data, q.shape[0], kc.shape[0], q.shape[1],
-                                            kc.shape[1], scale, pos, n_splits), "attention_tq")
-    return out, kc, vc, kx
+                                            kc.shape[1], scale, pos, n_splits, _ptr(img)), "attention_tq")
+    return (out, kc, vc, kx, img) if image else (out, kc, vc, kx)
+
+
+def op_attention_tq_multi(kv_cache_type: int, q, k_codes, v_codes, k_qjl, k_new, v_new, signs, qjl_matrices, scale: float, pos, slot,
+                          n_splits: int = 8, device: int = 0, *, image: bool = False):
+    """The multi-sequence decode step's attention over TurboQuant cache slots: sequence s attends to rows 0..pos[s]-1 of slot slot[s] and
+    to its own k_new[s] / v_new[s], which the launch compresses into row pos[s] of that slot.  q [n_seq, nh, d]; codes
+    [n_slots, nkv, max_seq, row bytes]; k_qjl [n_slots, nkv, max_seq, d / 32 + 1] uint32 words (QJL types, else None); k_new / v_new
+    [n_seq, nkv, d]; signs [nkv, 2, d]; qjl_matrices [nkv, d, d] (QJL types).
+    -> (out [n_seq, nh, d], k_codes, v_codes, k_qjl) after the call (copies; the inputs are untouched); image: and the n_seq + 1 XQ
+    images (op_attention_decode_multi) as a last element."""
+    q, kn, vn, sg = _f32(q), _f32(k_new), _f32(v_new), _f32(signs)
+    kc, vc = np.array(k_codes, dtype=np.uint8, copy=True), np.array(v_codes, dtype=np.uint8, copy=True)
+    pos, slot = np.ascontiguousarray(pos, dtype=np.int32), np.ascontiguousarray(slot, dtype=np.int32)
+    if not (len(pos) == len(slot) == q.shape[0] == kn.shape[0] == vn.shape[0]):
+        raise ValueError("op_attention_tq_multi: q, k_new, v_new, pos and slot must name the same number of sequences")
+    qjl = kv_cache_type in (KV_TQ2_QJL, KV_TQ3_QJL)
+    kx = np.array(k_qjl, dtype=np.uint32, copy=True) if qjl else None
+    S = _f32(qjl_matrices) if qjl else None
+    out = np.empty_like(q)
+    img = _attn_image(q, q.shape[0] + 1) if image else None
+    _chk(load_library().lgh_op_attention_tq_multi(device, kv_cache_type, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, _ptr(kx), kn.ctypes.data,
+                                                  vn.ctypes.data, sg.ctypes.data, _ptr(S), out.ctypes.data, q.shape[1], kc.shape[1], q.shape[2],
+                                                  kc.shape[2], kc.shape[0], len(pos), pos.ctypes.data, slot.ctypes.data, scale, n_splits,
+                                                  _ptr(img)), "attention_tq_multi")
+    return (out, kc, vc, kx, img) if image else (out, kc, vc, kx)
 
 
 def op_attention_prefill(q, k_cache, v_cache, scale: float, pos0: int, device: int = 0) -> np.ndarray:

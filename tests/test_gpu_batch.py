@@ -275,7 +275,8 @@ def test_turboquant_slots_bitwise(pkg, name, mix, B, kv):
         lens = [4 + (3 * s) % 7 for s in range(B)]
         hist = [_history(cfg, 500 + s, lens[s]) for s in range(B)]
         for s in range(B):
-            multi.batch_prefill(s, hist[s][:-1])                           # (token by token: no batched prompt path over a code cache)
+            multi.batch_prefill(s, hist[s][:-1])                           # (token by token: the batched prompt path over a tq2 / tq3 cache
+                                                                           # serves a context's own sequence only, never a slot)
             assert multi.batch_position(s) == lens[s] - 1
         toks = [h[-1] for h in hist]
         got = []
@@ -296,6 +297,53 @@ def test_turboquant_slots_bitwise(pkg, name, mix, B, kv):
         f32.batch_create(B)
         assert multi.stats()["kv_bytes"] < f32.stats()["kv_bytes"] // 4       # the slots' caches are the compressed ones
         f32.close()
+    finally:
+        multi.close()
+        single.close()
+
+
+@pytest.mark.parametrize("kv", ["tq3", "tq2-qjl"])
+def test_turboquant_long_and_short_slots_bitwise(pkg, kv):
+    """TurboQuant, max_seq 384: slot 2 with a prompt of 300 rows and slot 0 with 5 (both token by token through lgh_batch_prefill), then
+    4 steps of both in one captured step, with 4 attention splits: a pass of all workgroups of a kv head is 4 x 4 x 8 = 128 rows and a
+    batch two passes (with the default 32 splits a pass is 1024 rows and nothing of this context leaves the first batch).  The long
+    sequence's first workgroups go past their first batch and read later rows from memory, the short one's see the staged row and
+    clamped rows only; the slots are not the identity and the merge writes wo's input as images.  Each sequence's logits equal the
+    single-sequence engine's (same split count) bit for bit."""
+    hb = pkg.hip_backend
+    kvt = {"tq3": hb.KV_TQ3, "tq2-qjl": hb.KV_TQ2_QJL}[kv]
+    cfg = pkg.make_config("test-dense-d128", max_seq_len=384)
+    model = pkg.SynthModel(cfg, mix="Q4_K_M")
+    rng = np.random.default_rng(29)
+    signs = np.where(rng.integers(0, 2, cfg.num_layers * cfg.num_kv_heads * 2 * cfg.head_dim) == 1, 1.0, -1.0).astype(np.float32)
+    qjl = rng.standard_normal(cfg.num_layers * cfg.num_kv_heads * cfg.head_dim * cfg.head_dim).astype(np.float32) if "qjl" in kv else None
+    multi = pkg.HipGpuInference.from_model(model, 384, attn_splits=4, kv_cache_type=kvt, kv_rotation_signs=signs, kv_qjl_matrices=qjl)
+    single = pkg.HipGpuInference.from_model(model, 384, attn_splits=4, kv_cache_type=kvt, kv_rotation_signs=signs, kv_qjl_matrices=qjl)
+    try:
+        multi.batch_create(3)
+        slots = [2, 0]
+        prompts = [_history(cfg, 320, 301), _history(cfg, 321, 6)]
+        for sl, p in zip(slots, prompts):
+            multi.batch_prefill(sl, p[:-1])
+            assert multi.batch_position(sl) == len(p) - 1
+        assert multi.batch_position(1) == 0
+        toks = [p[-1] for p in prompts]
+        got = []
+        for step in range(4):
+            logits, nxt = multi.forward_multi(slots, toks, want_logits=True, greedy=True)
+            got.append(logits.copy())
+            toks = [int(t) for t in nxt]
+        for s in range(2):
+            single.reset()
+            for t in prompts[s][:-1]:
+                single.prefill_token(t)
+            tok = prompts[s][-1]
+            for step in range(4):
+                want = single.forward(tok)
+                assert np.array_equal(got[step][s].view(np.uint32), want.view(np.uint32)), (kv, s, step, float(np.abs(got[step][s] - want).max()))
+                tok = int(np.flatnonzero(want == want.max())[-1])
+            assert multi.batch_position(slots[s]) == len(prompts[s]) - 1 + 4
+        assert multi.batch_position(1) == 0
     finally:
         multi.close()
         single.close()
