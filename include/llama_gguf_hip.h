@@ -684,6 +684,34 @@ int lgh_op_moe_multi(int device, uint32_t type_gate_up, const void* w_gate, cons
                      size_t hidden, size_t ffn, size_t top_k, size_t n_seq, size_t max_batch, const float* router, const int* sel, const float* sel_w,
                      const float* x, const float* norm_w, const float* next_nw, float eps, float* out, uint8_t* image_out, float* ssq_out,
                      uint8_t* image_requant, float* ssq_requant, int* sel_out, float* sel_w_out, int* cnt_out, int* idx_out, int* structures);
+/* The launches of a step around the fused mat-vecs, one at a time, for kernel-level tests.  Test support: not part of the inference API.
+ *
+ * The embedding launches on a table of `type` (any type with a block size: F32, F16, BF16 and the quantized types), native GGUF bytes
+ * [vocab][hidden].  mode 0: the single-sequence launch through embed_forward — state_io (8 ints, in / out) are the device state words
+ * (token, position, next position, arg-max) before and after it; the token is state_io[0]; n = 1.  mode 1: the multi-sequence step's
+ * launch over tokens[0..n), n <= 16.  mode 2: the batched prompt path's over tokens[0..n), n <= 128.  norm_w (may be NULL): the first
+ * layer's QKV weights run on the matrix cores and this is their norm weight — modes 0 and 1 then also leave each row's XQ image
+ * (times norm_w) and sums of squares when hidden % 256 == 0, as the engine asks for them (*image_used = 1).  Every output buffer starts
+ * filled with the byte `fill`.  Modes 1 and 2 return n + 1 sequences' buffers (mode 0: one): rows_out [n + 1][hidden], image_out
+ * [n + 1][1280 bytes per 256 elements of hidden], ssq_out [n + 1][hidden / 16 + 64]; the last one belongs to no sequence of the launch. */
+int lgh_op_embed(int device, int mode, uint32_t type, const void* table, size_t vocab, size_t hidden, const int* tokens, size_t n,
+                 const float* norm_w, int fill, int* state_io, float* rows_out, uint8_t* image_out, float* ssq_out, int* image_used);
+/* qkv_forward, every branch: arguments as lgh_op_qkv_rope's, with weights of any type lgh_upload_tensor takes (the fused launch, or
+ * three launches + RoPE + the cache store when a type is expanded to f32 or neox != 0: pairs (i, i + head_dim / 2)).  staged != 0: the
+ * byte and TurboQuant caches' variant — the rotated K row and the V row stay in staged_out [2 * n_kv_heads * head_dim] for the
+ * attention launch and the caches (in / out) are not written.  Otherwise staged_out holds what the branch staged on its way to the
+ * caches (the fused launch: nothing, the NaN pattern 0x7FC0BEEF).  A refusal's message goes to err (errlen bytes; may be NULL). */
+int lgh_op_qkv_forward(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                       float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
+                       float rope_base, float rope_scale, int neox, int staged, float* q_out, float* k_cache, float* v_cache, float* staged_out,
+                       char* err, size_t errlen);
+/* ffn_gateup_forward: act_out [ffn] = silu(W_gate . x') * (W_up . x'), x' = RMSNorm(x) * norm_w, gate and up [ffn][hidden] of independent
+ * types: one fused launch when both are the same fused type, else two launches and silu_mul in place on the gate's output. */
+int lgh_op_ffn_gateup(int device, uint32_t type_gate, const void* w_gate, uint32_t type_up, const void* w_up, const float* x, const float* norm_w,
+                      float eps, size_t hidden, size_t ffn, float* act_out);
+/* The two-stage arg-max (the last maximal index wins).  n_seq == 0: the greedy step's launch over logits [n], tokens_out[0] = the token
+ * it leaves in the state words; n_seq in 1 .. 16: the multi-sequence step's over logits [n_seq][n], tokens_out [n_seq]. */
+int lgh_op_argmax(int device, const float* logits, size_t n, size_t n_seq, int* tokens_out);
 /* Multi-sequence mat-vec launches of this process per structure so far: out[0] mvqb, out[1] mvqb2 with the k-slices in the grid,
  * out[2] mvqb2 SEQ (tests: a launch whose partial-sum buffer is too small falls back to mvqb without a word). */
 void lgh_debug_mvqb_structures(uint64_t* out);

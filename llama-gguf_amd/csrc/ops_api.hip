@@ -1778,4 +1778,178 @@ int lgh_op_moe_multi(int device, uint32_t type_gate_up, const void* w_gate, cons
   return t.down(out, Bs.hidden, max_batch * H);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The launches of a step AROUND the fused mat-vecs, one at a time (tests/test_gpu_step_launches.py): the three embedding launches,
+// qkv_forward with everything it branches on (NeoX, expanded types, staged rows), ffn_gateup_forward's unfused pair with silu_mul in
+// place, and the two-stage arg-max of one row and of n_seq rows.  Test surface: not part of the inference API.
+// ------------------------------------------------------------------------------------------------
+int lgh_op_embed(int device, int mode, uint32_t type, const void* table, size_t vocab, size_t hidden, const int* tokens, size_t n,
+                 const float* norm_w, int fill, int* state_io, float* rows_out, uint8_t* image_out, float* ssq_out, int* image_used) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!table || !rows_out || vocab == 0 || hidden == 0 || hidden > 0x7FFFFFFFu || mode < 0 || mode > 2 || n == 0) return LGH_INVALID_ARGUMENT;
+  if (mode == 0 ? (n != 1 || !state_io) : !tokens) return LGH_INVALID_ARGUMENT;
+  if ((mode == 1 && n > (size_t)kMaxBatch) || (mode == 2 && n > (size_t)kPfTokens)) return LGH_INVALID_ARGUMENT;
+  for (size_t i = 0; i < n; i++) {
+    const int tok = mode == 0 ? state_io[ST_TOKEN] : tokens[i];
+    if (tok < 0 || (size_t)tok >= vocab) return LGH_INVALID_ARGUMENT;
+  }
+  const size_t tb = weight_bytes(type, hidden, vocab);
+  if (!tb) return LGH_SHAPE_MISMATCH;
+  lgh_ctx* c = t.c;
+  const uint32_t H = (uint32_t)hidden;
+  // mode 0: one sequence's buffers; modes 1 and 2: one sequence more than the launch covers, which must come back untouched
+  const size_t nb = mode == 0 ? 1 : n + 1, xs = xq_stride_of(H), ss = ssq_stride_of(H);
+  c->d.hidden_size = H;
+  c->embd_type = (int)type;
+  c->embd_raw = (uint8_t*)up_bytes(t, table, tb);
+  c->embd_bytes = tb;
+  c->hidden = t.up(nullptr, nb * hidden);
+  int* d_tok = mode ? (int*)up_bytes(t, tokens, n * 4) : nullptr;
+  // norm_w: the first layer's QKV weights run on the matrix cores, which is when the engine asks the embedding for their input's image
+  // (embed_forward looks at the weight's device type and at hidden % 256; enqueue_multi runs only where batch_weights_ok held both)
+  c->layers.resize(1);
+  c->l0 = 0; c->l1 = 1;
+  LayerW& L0 = c->layers[0];
+  if (norm_w) {
+    L0.wq.type = kDevQ4K_T16;
+    if (!(L0.attn_norm = t.up(norm_w, hidden))) return LGH_ALLOCATION_FAILED;
+  }
+  const bool want_img = mode != 2 && norm_w && hidden % 256 == 0;
+  if (want_img && (!image_out || !ssq_out)) return LGH_INVALID_ARGUMENT;
+  if (!c->embd_raw || !c->hidden || (mode && !d_tok)) return LGH_ALLOCATION_FAILED;
+  uint8_t* xq = nullptr;
+  float* ssq = nullptr;
+  hipStream_t st = c->stream;
+  if (hipMemsetAsync(c->hidden, fill, nb * hidden * 4, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  if (want_img) {
+    xq = (uint8_t*)up_bytes(t, nullptr, nb * xs);
+    ssq = t.up(nullptr, nb * ss);
+    if (!xq || !ssq) return LGH_ALLOCATION_FAILED;
+    if (hipMemsetAsync(xq, fill, nb * xs, st) != hipSuccess || hipMemsetAsync(ssq, fill, nb * ss * 4, st) != hipSuccess) return LGH_OPERATION_FAILED;
+    register_views(c, c->hidden, xq, ssq, H, (uint32_t)nb);
+  }
+  int rc;
+  bool used = false;
+  if (mode == 0) {
+    if (hipMemcpyAsync(c->state, state_io, ST_WORDS * 4, hipMemcpyHostToDevice, st) != hipSuccess) return LGH_OPERATION_FAILED;
+    if ((rc = embed_forward(c))) return rc;
+    const XqBuf* qh = xq_find(c, c->hidden);
+    used = qh && qh->fresh;
+    if ((rc = down_bytes(t, state_io, c->state, ST_WORDS * 4))) return rc;
+  } else if (mode == 1) {   // as enqueue_multi launches it
+    if (embed_multi_launch(c->embd_type, c->embd_raw, d_tok, c->hidden, H, (uint32_t)n, xq, want_img ? L0.attn_norm : nullptr, ssq, (uint32_t)xs,
+                           (uint32_t)ss, st) != hipSuccess)
+      return LGH_OPERATION_FAILED;
+    used = want_img;
+  } else {                  // as prefill_block launches it
+    if (embed_batch_launch(c->embd_type, c->embd_raw, d_tok, c->hidden, H, (uint32_t)n, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  }
+  if (image_used) *image_used = used ? 1 : 0;
+  if (want_img && ((rc = down_bytes(t, image_out, xq, nb * xs)) || (rc = t.down(ssq_out, ssq, nb * ss)))) return rc;
+  return t.down(rows_out, c->hidden, nb * hidden);
+}
+
+int lgh_op_qkv_forward(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                       float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
+                       float rope_base, float rope_scale, int neox, int staged, float* q_out, float* k_cache, float* v_cache, float* staged_out,
+                       char* err, size_t errlen) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (err && errlen) err[0] = 0;
+  if (!types || !w || !x || !norm_w || !q_out || !k_cache || !v_cache || !staged_out || hidden == 0 || head_dim == 0 || head_dim % 2 ||
+      n_kv_heads == 0 || n_heads % n_kv_heads || pos >= max_seq_len || max_seq_len > 0x7FFFFFFFu || rope_scale == 0.0f)
+    return LGH_INVALID_ARGUMENT;
+  lgh_model_desc& d = t.c->d;
+  d.norm_eps = eps;
+  d.hidden_size = (uint32_t)hidden;
+  d.head_dim = (uint32_t)head_dim;
+  d.num_heads = (uint32_t)n_heads;
+  d.num_kv_heads = (uint32_t)n_kv_heads;
+  d.max_seq_len = (uint32_t)max_seq_len;
+  d.rope_freq_base = rope_base;
+  d.rope_freq_scale = rope_scale;
+  d.use_neox_rope = neox ? 1 : 0;
+  if (staged) d.flags |= LGH_FLAG_KV_INT8;   // (as every byte-per-element and TurboQuant cache: the rows stay in kv_tmp for the attention launch)
+  const size_t rows[3] = {n_heads * head_dim, n_kv_heads * head_dim, n_kv_heads * head_dim}, KD = rows[1];
+  LayerW Lw;
+  DevWeight* const W[3] = {&Lw.wq, &Lw.wk, &Lw.wv};
+  int rc;
+  for (int s = 0; s < 3; s++) {
+    const size_t nb = weight_bytes(types[s], hidden, rows[s]);
+    if (!nb || !w[s]) return LGH_SHAPE_MISMATCH;
+    if ((rc = upload_matrix(t.c, *W[s], (int)types[s], (uint32_t)hidden, (uint32_t)rows[s], 1, -1, w[s], nb))) return rc;
+  }
+  std::vector<float> cs;
+  rope_table_host(d, cs);
+  const size_t cache = n_kv_heads * max_seq_len * head_dim;
+  t.c->rope_cs = t.up(cs.data(), cs.size());
+  // the view has staged rows as the engine's always has (c->kv_tmp); q and the rows start as the NaN pattern
+  const AttnView v{t.up(x, hidden), t.up(nullptr, rows[0]), t.up(nullptr, 2 * KD), nullptr};
+  Lw.attn_norm = t.up(norm_w, hidden);
+  Lw.kcache = t.up(k_cache, cache);
+  Lw.vcache = t.up(v_cache, cache);
+  float** const db[3] = {&Lw.bq, &Lw.bk, &Lw.bv};
+  for (int s = 0; s < 3; s++)
+    if (bias && bias[s] && !(*db[s] = t.up(bias[s], rows[s]))) return LGH_ALLOCATION_FAILED;
+  if (!t.c->rope_cs || !v.hidden || !Lw.attn_norm || !v.q || !v.kv_tmp || !Lw.kcache || !Lw.vcache) return LGH_ALLOCATION_FAILED;
+  if (!pf_poison(t.c, v.q, rows[0] * 4, 0x7FC0BEEFu) || !pf_poison(t.c, v.kv_tmp, 2 * KD * 4, 0x7FC0BEEFu)) return LGH_OPERATION_FAILED;
+  if ((rc = set_pos(t, pos))) return rc;
+  if ((rc = qkv_forward(t.c, Lw, v))) {
+    if (err && errlen) { std::strncpy(err, t.c->err.c_str(), errlen - 1); err[errlen - 1] = 0; }
+    return rc;
+  }
+  if ((rc = t.down(q_out, v.q, rows[0])) || (rc = t.down(staged_out, v.kv_tmp, 2 * KD)) || (rc = t.down(k_cache, Lw.kcache, cache))) return rc;
+  return t.down(v_cache, Lw.vcache, cache);
+}
+
+int lgh_op_ffn_gateup(int device, uint32_t type_gate, const void* w_gate, uint32_t type_up, const void* w_up, const float* x, const float* norm_w,
+                      float eps, size_t hidden, size_t ffn, float* act_out) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!w_gate || !w_up || !x || !norm_w || !act_out || hidden == 0 || ffn == 0) return LGH_INVALID_ARGUMENT;
+  t.c->d.norm_eps = eps;
+  t.c->d.hidden_size = (uint32_t)hidden;
+  const size_t ng = weight_bytes(type_gate, hidden, ffn), nu = weight_bytes(type_up, hidden, ffn);
+  if (!ng || !nu) return LGH_SHAPE_MISMATCH;
+  LayerW Lw;   // (no down projection: nobody asks the fused launch for act's image)
+  int rc;
+  if ((rc = upload_matrix(t.c, Lw.gate, (int)type_gate, (uint32_t)hidden, (uint32_t)ffn, 1, -1, w_gate, ng)) ||
+      (rc = upload_matrix(t.c, Lw.up, (int)type_up, (uint32_t)hidden, (uint32_t)ffn, 1, -1, w_up, nu)))
+    return rc;
+  Lw.ffn_norm = t.up(norm_w, hidden);
+  const FfnView v{t.up(x, hidden), t.up(nullptr, ffn), t.up(nullptr, ffn), nullptr, nullptr, nullptr};
+  if (!Lw.ffn_norm || !v.hidden || !v.act || !v.act2) return LGH_ALLOCATION_FAILED;
+  if (!pf_poison(t.c, v.act, ffn * 4, 0x7FC0BEEFu) || !pf_poison(t.c, v.act2, ffn * 4, 0x7FC0BEEFu)) return LGH_OPERATION_FAILED;
+  if ((rc = ffn_gateup_forward(t.c, Lw, v))) return rc;
+  return t.down(act_out, v.act, ffn);
+}
+
+int lgh_op_argmax(int device, const float* logits, size_t n, size_t n_seq, int* tokens_out) {
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (!logits || !tokens_out || n == 0 || n > 0x7FFFFFFFu || n_seq > (size_t)kMaxBatch) return LGH_INVALID_ARGUMENT;
+  const size_t rows = n_seq ? n_seq : 1;
+  const float* dl = t.up(logits, rows * n);
+  // parts: 64 per row (misc.hip: kArgmaxParts), as lgh_finalize / batch_scratch_alloc size amax_v / amax_i
+  float* pv = t.up(nullptr, rows * 64);
+  int* pi = (int*)up_bytes(t, nullptr, rows * 64 * 4);
+  int* next = (int*)up_bytes(t, nullptr, rows * 4);
+  if (!dl || !pv || !pi || !next) return LGH_ALLOCATION_FAILED;
+  hipStream_t st = t.c->stream;
+  if (!pf_poison(t.c, pv, rows * 64 * 4, 0x7FC0BEEFu) || hipMemsetAsync(pi, 0xFF, rows * 64 * 4, st) != hipSuccess ||
+      hipMemsetAsync(next, 0xFF, rows * 4, st) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  if (n_seq == 0) {   // the greedy step's: the token goes to the state words
+    if (argmax_launch(dl, (uint32_t)n, pv, pi, t.c->state, nullptr, st) != hipSuccess) return LGH_OPERATION_FAILED;
+    int words[ST_WORDS];
+    if (int rc = down_bytes(t, words, t.c->state, sizeof(words))) return rc;
+    if (words[ST_TOKEN] != words[ST_ARGMAX]) return LGH_OPERATION_FAILED;   // (the token fed back is the arg-max)
+    tokens_out[0] = words[ST_ARGMAX];
+    return LGH_OK;
+  }
+  if (argmax_multi_launch(dl, (uint32_t)n, (uint32_t)n_seq, pv, pi, next, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  return down_bytes(t, tokens_out, next, n_seq * 4);
+}
+
 }  // extern "C"

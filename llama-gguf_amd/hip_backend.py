@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
     "lgh_op_linear_multi", "lgh_op_linear_chain_multi", "lgh_op_qkv_rope_multi", "lgh_op_moe_multi", "lgh_debug_mvqb_structures",
     "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_attention_kv8_multi", "lgh_op_attention_tq_multi",
+    "lgh_op_embed", "lgh_op_qkv_forward", "lgh_op_ffn_gateup", "lgh_op_argmax",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -268,6 +269,11 @@ def load_library() -> C.CDLL:
         "lgh_op_pf_ffn": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, vp, vp, vp, f32, sz, sz, sz, vp, vp, vp, vp]),
         "lgh_op_pf_moe": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, vp, sz, sz, vp, vp, vp, f32, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                     vp, vp]),
+        "lgh_op_embed": (C.c_int, [C.c_int, C.c_int, u32, vp, sz, sz, vp, sz, vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int)]),
+        "lgh_op_qkv_forward": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, sz, sz, f32, f32, C.c_int, C.c_int, vp, vp, vp, vp,
+                                         C.c_char_p, sz]),
+        "lgh_op_ffn_gateup": (C.c_int, [C.c_int, u32, vp, u32, vp, vp, vp, f32, sz, sz, vp]),
+        "lgh_op_argmax": (C.c_int, [C.c_int, vp, sz, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -897,6 +903,71 @@ def op_qkv_rope(types, ws, biases, x, norm_w, eps: float, head_dim: int, n_heads
                                         nw.ctypes.data, eps, x.size, head_dim, n_heads, n_kv, kc.shape[1], pos, rope_base, rope_scale,
                                         q.ctypes.data, kc.ctypes.data, vc.ctypes.data), "qkv_rope")
     return q, kc, vc
+
+
+def op_qkv_forward(types, ws, biases, x, norm_w, eps: float, head_dim: int, n_heads: int, n_kv: int, k_cache, v_cache, pos: int,
+                   rope_base: float, rope_scale: float, *, neox: bool = False, staged: bool = False, device: int = 0):
+    """qkv_forward, whichever branch the types / neox / staged select (op_qkv_rope's arguments; any uploadable weight type).
+    -> (q, k_cache, v_cache, staged rows [2, n_kv * head_dim]: K row | V row as kv_tmp holds them after the call).  A refusal raises
+    BackendError with the engine's message."""
+    x, nw = _f32(x), _f32(norm_w)
+    kc, vc = np.array(k_cache, dtype=np.float32, copy=True), np.array(v_cache, dtype=np.float32, copy=True)
+    ws = [np.ascontiguousarray(w, dtype=np.uint8) for w in ws]
+    bs = [None if b is None else _f32(b) for b in biases]
+    tarr = np.array(types, dtype=np.uint32)
+    warr = (C.c_void_p * 3)(*[w.ctypes.data for w in ws])
+    barr = (C.c_void_p * 3)(*[_ptr(b) for b in bs])
+    q = np.empty(n_heads * head_dim, np.float32)
+    st = np.empty((2, n_kv * head_dim), np.float32)
+    err = C.create_string_buffer(512)
+    rc = load_library().lgh_op_qkv_forward(device, tarr.ctypes.data, C.cast(warr, C.c_void_p), C.cast(barr, C.c_void_p), x.ctypes.data,
+                                           nw.ctypes.data, eps, x.size, head_dim, n_heads, n_kv, kc.shape[1], pos, rope_base, rope_scale,
+                                           int(neox), int(staged), q.ctypes.data, kc.ctypes.data, vc.ctypes.data, st.ctypes.data, err, 512)
+    _chk(rc, err.value.decode(errors="replace") or "qkv_forward")
+    return q, kc, vc, st
+
+
+def op_ffn_gateup(type_gate: int, w_gate, type_up: int, w_up, x, norm_w, eps: float, ffn: int, device: int = 0) -> np.ndarray:
+    """ffn_gateup_forward: silu(W_gate x') * (W_up x'), x' = RMSNorm(x) * norm_w, gate and up of independent types -> act [ffn]."""
+    x, nw = _f32(x), _f32(norm_w)
+    wg, wu = np.ascontiguousarray(w_gate, dtype=np.uint8), np.ascontiguousarray(w_up, dtype=np.uint8)
+    out = np.empty(ffn, np.float32)
+    _chk(load_library().lgh_op_ffn_gateup(device, type_gate, wg.ctypes.data, type_up, wu.ctypes.data, x.ctypes.data, nw.ctypes.data, eps,
+                                          x.size, ffn, out.ctypes.data), "ffn_gateup")
+    return out
+
+
+def op_argmax(logits, multi: bool = False, device: int = 0) -> np.ndarray:
+    """The two-stage arg-max: logits [n] through the greedy step's launch, or (multi) logits [n_seq, n] through the multi-sequence
+    step's.  -> tokens int32 [1] or [n_seq]."""
+    lg = _f32(logits)
+    n_seq = lg.shape[0] if multi else 0
+    out = np.full(max(n_seq, 1), -2, np.int32)
+    _chk(load_library().lgh_op_argmax(device, lg.ctypes.data, lg.shape[-1], n_seq, out.ctypes.data), "argmax")
+    return out
+
+
+def op_embed(mode: int, ggml_type: int, table, vocab: int, hidden: int, tokens, *, norm_w=None, fill: int = 0x5A, state=None,
+             device: int = 0):
+    """The embedding launches on a [vocab, hidden] table of native GGUF bytes.  mode 0: embed_forward (one token; state = (token,
+    next position) preset in the device state words, the position word a sentinel); 1: the multi-sequence launch; 2: the batched
+    prompt path's.  -> dict(rows f32 [nb, hidden], image uint8 [nb, 1280 per 256 elements] or None, ssq f32 [nb, hidden / 16 + 64] or
+    None, state int32 [8] (mode 0)), nb = 1 (mode 0) or len(tokens) + 1; every buffer starts filled with the byte `fill`."""
+    tb = np.ascontiguousarray(table, dtype=np.uint8)
+    toks = None if mode == 0 else np.ascontiguousarray(tokens, dtype=np.int32)
+    n = 1 if mode == 0 else toks.size
+    nb = 1 if mode == 0 else n + 1
+    nw = None if norm_w is None else _f32(norm_w)
+    words = np.zeros(8, np.int32)
+    if mode == 0:
+        words[0], words[1], words[2] = state[0], -0x5A5A5A5B, state[1]
+    rows = np.full(nb * hidden * 4, fill, np.uint8).view(np.float32).reshape(nb, hidden)
+    img = np.full((nb, _xq_bytes(hidden)), fill, np.uint8)
+    ssq = np.full(nb * (hidden // 16 + 64) * 4, fill, np.uint8).view(np.float32).reshape(nb, -1)
+    used = C.c_int(0)
+    _chk(load_library().lgh_op_embed(device, mode, ggml_type, tb.ctypes.data, vocab, hidden, _ptr(toks), n, _ptr(nw), fill, words.ctypes.data,
+                                     rows.ctypes.data, img.ctypes.data, ssq.ctypes.data, C.byref(used)), "embed")
+    return {"rows": rows, "image": img if used.value else None, "ssq": ssq if used.value else None, "state": words}
 
 
 def op_linear_chain(type_a: int, w_a, k: int, n_a: int, x, type_b: int, w_b, n_b: int, *, w_a_up=None, bias_a=None, norm_w=None,
