@@ -200,6 +200,22 @@ int lgh_device_count(void);
 /* CudaDevice::new + scratch/KV allocation (gpu_only.rs:438-440, 527-598). */
 int lgh_create(const lgh_model_desc* desc, lgh_ctx** out);
 
+/* The KV cache a descriptor asks for, without a device (a host sizes its memory with it): bytes per (kv head, position) and the
+ * bytes of one slot (one sequence of max_seq_len positions) of one layer.  A context holds num_layers such slots for its own
+ * sequence, lgh_batch_create(max_batch) adds max_batch per layer; lgh_stats.kv_bytes counts exactly these.  Reads kv_cache_type,
+ * flags, num_kv_heads, max_seq_len and head_dim of the descriptors lgh_create takes (LGH_FLAG_KV_INT8 with type 0 included);
+ * InvalidArgument for a kv_cache_type above LGH_KV_TQ3_QJL. */
+typedef struct lgh_kv_layout {
+  uint32_t kv_cache_type;            /* LGH_KV_*, the flag spelling resolved */
+  uint32_t row_bytes;                /* one K or V row: 4 * head_dim (f32), head_dim (int8 / FP8), head_dim / 4 or head_dim / 8 * 3 (TQ codes) */
+  uint32_t scale_bytes;              /* per K and per V row: 4 (int8), else 0 */
+  uint32_t qjl_bytes;                /* per K row: head_dim / 8 + 4 (the QJL formats: sign bits + residual norm), else 0 */
+  uint64_t rows;                     /* num_kv_heads * max_seq_len */
+  uint64_t k_bytes, v_bytes, k_scale_bytes, v_scale_bytes, k_qjl_bytes;   /* one slot's tensors: rows * the per-position bytes */
+  uint64_t slot_bytes;               /* their sum */
+} lgh_kv_layout;
+int lgh_kv_cache_layout(const lgh_model_desc* desc, lgh_kv_layout* out);
+
 /* upload_model_weights (src/backend/cuda/dequant_weights.rs:244-505): one call per tensor, GGUF name
  * (`token_embd.weight`, `blk.{i}.attn_q.weight`, ... `blk.{i}.ffn_gate_exps.weight` or the loader's
  * per-expert `blk.{i}.ffn_gate.{e}.weight`, `output_norm.weight`, `output.weight`), GGML dims (dim 0

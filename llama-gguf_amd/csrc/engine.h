@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.h"
+#include "kv_cache.h"
 #include "sample.h"
 
 namespace lgh {
@@ -18,12 +19,7 @@ struct LayerW {
   float* ffn_norm = nullptr;
   float* router = nullptr;                            // [n_experts][hidden] f32
   float* bq = nullptr; float* bk = nullptr; float* bv = nullptr; float* bo = nullptr;
-  float* kcache = nullptr;
-  float* vcache = nullptr;
-  // LGH_FLAG_KV_INT8: int8 rows [kv_head][max_seq][head_dim] + one f32 scale per (kv_head, position) instead of the f32 caches
-  int8_t *k8 = nullptr, *v8 = nullptr;
-  float *kscale = nullptr, *vscale = nullptr;
-  uint32_t* kx = nullptr;   // TurboQuantProd: QJL rows of the K cache, [kv head][max_seq][head_dim / 32 + 1] words (sign bits, residual norm)
+  KvCache kv;   // the own sequence's cache (one slot), in the context's format (lgh_ctx::kvl)
   bool moe() const { return router != nullptr; }
 };
 
@@ -59,25 +55,14 @@ struct ProfRec { int cls; int sym; uint64_t bytes; hipEvent_t a, b; };
 struct BatchScratch {
   bool ready = false;
   uint32_t max_batch = 0, ffn = 0;
-  uint64_t cache_stride = 0;                          // floats between two slots' caches of one layer
   float *hidden = nullptr, *xnorm = nullptr, *q = nullptr, *attn_out = nullptr, *act = nullptr, *act2 = nullptr, *logits = nullptr,
         *part_ml = nullptr, *part_acc = nullptr, *amax_v = nullptr, *moe_w = nullptr, *mv_part = nullptr;
   uint64_t mv_part_floats = 0;
   int *amax_i = nullptr, *moe_sel = nullptr;
   int *d_tokens = nullptr, *d_pos = nullptr, *d_slot = nullptr, *d_log = nullptr;   // the step's control words (device), the greedy token log
   int* h_ctl = nullptr;                               // pinned staging of the control words
-  std::vector<float*> kcache, vcache;                 // per layer: [slot][kv_head][max_seq][head_dim]
-  // TurboQuant caches (kv_cache_type LGH_KV_TQ*): per layer the slots' code rows [slot][kv_head][max_seq][row bytes] (K, V) and, with
-  // QJL, the K rows' sign bits + norms [slot][kv_head][max_seq][head_dim / 32 + 1]; kv_tmp = the step's rotated K / V rows, f32,
-  // [sequence][K row | V row]
-  std::vector<uint8_t*> kq, vq;
-  std::vector<uint32_t*> kx;
-  float* kv_tmp = nullptr;
-  uint64_t code_stride = 0, x_stride = 0;             // bytes / words between two slots
-  // int8 / FP8 caches (LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2): kq / vq hold the slots' rows [slot][kv_head][max_seq][head_dim], one byte per
-  // element, and (int8) kscale / vscale the rows' scales [slot][kv_head][max_seq]; kv_tmp as above (K row after RoPE | V row), quantized
-  // and stored by the attention launch
-  std::vector<float*> kscale, vscale;
+  std::vector<KvCache> kv;                            // per layer: the max_batch slots' caches, in the context's format (lgh_ctx::kvl)
+  float* kv_tmp = nullptr;                            // staged formats: the step's K rows after RoPE | V rows, f32, [sequence][K row | V row]
   // MoE layers, experts read once per step (top-k <= 8): the (sequence, slot) pairs' activations [pair][ffn] (+ XQ views) and expert
   // outputs [pair][hidden]; per expert the number of pairs that chose it and their list
   float *moe_act = nullptr, *moe_tmp = nullptr;
@@ -93,6 +78,7 @@ struct BatchScratch {
 
 struct lgh_ctx {
   lgh_model_desc d{};
+  lgh::KvLayout kvl;   // d's cache format and its sizes (lgh_create; the bare contexts of ops_api.hip set it with the fields it is made of)
   int device = 0;
   uint32_t l0 = 0, l1 = 0;
   bool first = true, last = true;
@@ -188,12 +174,9 @@ struct FfnView { float* hidden; float* act; float* act2; float* xnorm; int* moe_
 struct AttnView { float* hidden; float* q; float* kv_tmp; float* attn_out; };
 struct AllocSpec { void** p; size_t n; };
 
-static inline bool kv_is_tq(uint32_t t) { return t == LGH_KV_TQ2 || t == LGH_KV_TQ3 || t == LGH_KV_TQ2_QJL || t == LGH_KV_TQ3_QJL; }
-static inline bool kv_is_qjl(uint32_t t) { return t == LGH_KV_TQ2_QJL || t == LGH_KV_TQ3_QJL; }
-static inline int kv_tq_bits(uint32_t t) { return t == LGH_KV_TQ2 || t == LGH_KV_TQ2_QJL ? 2 : 3; }
 int build_mv_group(lgh_ctx* c, const SegSpec* specs, int nseg, const float* norm_w, uint32_t k, bool mfma, lgh::MvLaunch& L, uint32_t& wg,
                    uint32_t& threads, uint64_t& alg, uint32_t tile_cap);
-int qkv_forward(lgh_ctx* c, lgh::LayerW& Lw, const AttnView& v);   // norm -> q, k, v -> RoPE -> cache write (or kv_tmp, byte caches)
+int qkv_forward(lgh_ctx* c, lgh::LayerW& Lw, const AttnView& v);   // norm -> q, k, v -> RoPE -> cache write (or kv_tmp, staged formats)
 // attention over layer li's cache into v.attn_out, by the context's path (cache type, attn_generic, attn_direct, n_splits); xq_out: also
 // leave attn_out's XQ image, where the path's last launch can write one
 int attention_forward(lgh_ctx* c, lgh::LayerW& Lw, uint32_t li, const AttnView& v, float scale, bool xq_out);
@@ -223,7 +206,12 @@ uint32_t xq_stride_of(uint32_t k);                   // bytes / floats between t
 uint32_t ssq_stride_of(uint32_t k);
 int register_views(lgh_ctx* c, float* f32, uint8_t* xq, float* ssq, uint32_t k, uint32_t n);   // n sequences' views of a batch vector, at those strides
 uint64_t batch_part_floats(const lgh_ctx* c, uint32_t max_batch);
-void batch_cache_layout(lgh_ctx* c);                 // the distances between two slots' caches of a layer, its (empty) per-layer cache tables
+// one layer's cache for n_slots sequences in the context's format: allocated, zeroed, counted as KV bytes
+int kv_alloc(lgh_ctx* c, size_t n_slots, lgh::KvCache& kv);
+// layer li's cache of slot `slot` of the multi-sequence engine (slot < 0: the context's own)
+inline lgh::KvCache kv_of(const lgh_ctx* c, uint32_t li, int slot) {
+  return slot < 0 ? c->layers[li].kv : c->batch.kv[li].slot(c->kvl, (size_t)slot);
+}
 int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch);
 // the step of a layer over the batch scratch (c->batch), one function each, shared by enqueue_multi and the per-launch entry points
 int qkv_forward_multi(lgh_ctx* c, lgh::LayerW& Lw, uint32_t li, uint32_t n_seq);
@@ -264,7 +252,7 @@ int check_ready(lgh_ctx* c);   // what every entry point on a finalized context 
 int capture_graph(lgh_ctx* c, hipGraphExec_t* exec, const std::function<int()>& enqueue, size_t* n_nodes = nullptr);
 int enqueue_token(lgh_ctx* c, int mode);   // everything one token needs, in stream order (eager or under capture)
 // batched prompt path (engine_prefill.hip).  The sequence a block of prompt tokens belongs to: the position of the block's first token,
-// and whose K / V rows it fills — the context's own (slot < 0: layers[li].kcache / vcache) or a slot's of the multi-sequence engine
+// and whose K / V rows it fills — the context's own (slot < 0) or a slot's of the multi-sequence engine (kv_of)
 struct PfTarget { size_t pos0; int slot; };
 // slot: the target is a slot of the multi-sequence engine (TurboQuant slots stay token by token: bit-identical to the single-sequence engine)
 bool pf_eligible(const lgh_ctx* c, bool slot = false);

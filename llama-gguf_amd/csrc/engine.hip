@@ -124,7 +124,24 @@ static int set_token(lgh_ctx* c, uint32_t token) {
 // ------------------------------------------------------------------------------------------------
 // What the engine's kernels are built for, checked BEFORE anything is allocated or uploaded (a Qwen2-7B, 28 / 4 = 7 query
 // heads per kv head, used to fail only in lgh_finalize's warm-up with a generic launch error).
+// The cache format a descriptor asks for (type F32 with LGH_FLAG_KV_INT8 is the older spelling of int8; nothing else reads the flag)
+static uint32_t desc_kv_type(const lgh_model_desc& d) {
+  return d.kv_cache_type == LGH_KV_F32 && (d.flags & LGH_FLAG_KV_INT8) ? (uint32_t)LGH_KV_INT8 : d.kv_cache_type;
+}
+
+// A caller's descriptor as lgh_create reads it (one from before kv_cache_type was appended is still taken), the cache type resolved
+static int desc_normalize(const lgh_model_desc* desc, lgh_model_desc& d) {
+  if (!desc || (desc->struct_size != sizeof(lgh_model_desc) && desc->struct_size != offsetof(lgh_model_desc, kv_cache_type))) return LGH_INVALID_ARGUMENT;
+  d = lgh_model_desc{};
+  std::memcpy(&d, desc, desc->struct_size);
+  d.struct_size = sizeof(lgh_model_desc);
+  if (d.kv_cache_type > LGH_KV_TQ3_QJL) return LGH_INVALID_ARGUMENT;
+  d.kv_cache_type = desc_kv_type(d);
+  return LGH_OK;
+}
+
 int engine_shape_check(const lgh_model_desc& d, std::string& why) {
+  const KvLayout kvl(desc_kv_type(d), d.num_kv_heads, d.max_seq_len, d.head_dim);
   if (!d.hidden_size || !d.num_layers || !d.num_heads || !d.num_kv_heads || !d.head_dim || !d.vocab_size || !d.max_seq_len) {
     why = "a model dimension is zero";
     return LGH_INVALID_ARGUMENT;
@@ -141,11 +158,11 @@ int engine_shape_check(const lgh_model_desc& d, std::string& why) {
           "kernel, which holds max_seq_len scores in LDS: max_seq_len must be <= 38400 for it (got " + std::to_string(d.max_seq_len) + ")";
     return LGH_UNSUPPORTED;
   }
-  if ((d.flags & LGH_FLAG_KV_INT8) && !attn_shape_has_fast_kernel(d.head_dim, g)) {
+  if (kvl.staged() && !attn_shape_has_fast_kernel(d.head_dim, g)) {
     why = "the int8 KV cache runs on the split attention kernels (head_dim 64 / 128; 1, 2, 4 or 8 query heads per kv head) of the default decode path";
     return LGH_UNSUPPORTED;
   }
-  if (kv_is_tq(d.kv_cache_type) && (d.head_dim != 64 && d.head_dim != 128)) {
+  if (kvl.tq() && (d.head_dim != 64 && d.head_dim != 128)) {
     why = "the TurboQuant KV cache rotates rows of 64 or 128 values (head_dim a power of two)";
     return LGH_UNSUPPORTED;
   }
@@ -166,25 +183,18 @@ int lgh_device_count(void) {
 }
 
 int lgh_create(const lgh_model_desc* desc, lgh_ctx** out) {
-  // (a descriptor from before kv_cache_type was appended is still taken: its cache type comes from the flags alone)
-  if (!desc || !out || (desc->struct_size != sizeof(lgh_model_desc) && desc->struct_size != offsetof(lgh_model_desc, kv_cache_type)))
-    return LGH_INVALID_ARGUMENT;
+  if (!out) return LGH_INVALID_ARGUMENT;
+  lgh_model_desc d;
+  if (int rc = desc_normalize(desc, d)) return rc;
   *out = nullptr;
-  lgh_model_desc d{};
-  std::memcpy(&d, desc, desc->struct_size);
-  d.struct_size = sizeof(lgh_model_desc);
-  if (d.kv_cache_type > LGH_KV_TQ3_QJL) return LGH_INVALID_ARGUMENT;
   if (d.flags & LGH_FLAG_REMOVED_MASK) return LGH_UNSUPPORTED;   // the decode structures removed in round 3 (llama_gguf_hip.h)
-  if (d.kv_cache_type == LGH_KV_F32 && (d.flags & LGH_FLAG_KV_INT8)) d.kv_cache_type = LGH_KV_INT8;
-  // every byte-per-element cache shares the int8 cache's structure (staged f32 rows, the attention launch quantizes and stores
-  // the current token's rows): the flag marks all of them from here on, kv_cache_type tells them apart
-  if (d.kv_cache_type != LGH_KV_F32) d.flags |= LGH_FLAG_KV_INT8;
   std::string why;
   if (int rc = engine_shape_check(d, why)) return rc;
   int ndev = lgh_device_count();
   if (ndev <= 0 || d.device_id < 0 || d.device_id >= ndev) return LGH_NOT_AVAILABLE;
   lgh_ctx* c = new lgh_ctx();
   c->d = d;
+  c->kvl = KvLayout(d);
   c->device = d.device_id;
   c->l0 = d.layer_begin;
   c->l1 = d.layer_end == 0 ? d.num_layers : d.layer_end;
@@ -209,8 +219,19 @@ int lgh_create(const lgh_model_desc* desc, lgh_ctx** out) {
   const uint32_t dsel = (d.flags >> LGH_FLAG_ATTN_DIRECT_SHIFT) & 0xFFu;
   c->direct_attn_max_kv = dsel == 255 ? 0 : dsel ? dsel * 64 : kDirectAttnDefaultKv;
   c->attn_generic = !attn_shape_has_fast_kernel(d.head_dim, d.num_heads / d.num_kv_heads);
-  if (d.flags & LGH_FLAG_KV_INT8) c->direct_attn_max_kv = 0;   // the byte caches have one attention structure: splits + combine
+  if (c->kvl.staged()) c->direct_attn_max_kv = 0;   // the staged formats have one attention structure: splits + combine
   *out = c;
+  return LGH_OK;
+}
+
+int lgh_kv_cache_layout(const lgh_model_desc* desc, lgh_kv_layout* out) {
+  lgh_model_desc d;
+  if (int rc = desc_normalize(desc, d)) return rc;
+  if (!out) return LGH_INVALID_ARGUMENT;
+  const KvLayout l(d);
+  *out = lgh_kv_layout{l.type, (uint32_t)l.row_bytes(), (uint32_t)l.scale_bytes(), (uint32_t)l.qjl_bytes(), l.rows(),
+                       l.slot_bytes(KV_K), l.slot_bytes(KV_V), l.slot_bytes(KV_KSCALE), l.slot_bytes(KV_VSCALE), l.slot_bytes(KV_KX),
+                       l.slot_bytes()};
   return LGH_OK;
 }
 
@@ -220,7 +241,7 @@ int lgh_create(const lgh_model_desc* desc, lgh_ctx** out) {
 int lgh_set_kv_rotation_signs(lgh_ctx* c, const float* signs, size_t n) {
   if (!c) return LGH_INVALID_ARGUMENT;
   if (c->finalized) return fail(c, LGH_INVALID_ARGUMENT, "the rotation signs must be given before lgh_finalize");
-  if (!kv_is_tq(c->d.kv_cache_type)) return fail(c, LGH_INVALID_ARGUMENT, "this context has no TurboQuant KV cache");
+  if (!c->kvl.tq()) return fail(c, LGH_INVALID_ARGUMENT, "this context has no TurboQuant KV cache");
   const size_t want = (size_t)(c->l1 - c->l0) * c->d.num_kv_heads * 2 * c->d.head_dim;
   if (!signs || n != want) return fail(c, LGH_INVALID_ARGUMENT, "expected " + std::to_string(want) + " sign values");
   for (size_t i = 0; i < n; i++)
@@ -234,7 +255,7 @@ int lgh_set_kv_rotation_signs(lgh_ctx* c, const float* signs, size_t n) {
 int lgh_set_kv_qjl_matrices(lgh_ctx* c, const float* m, size_t n) {
   if (!c) return LGH_INVALID_ARGUMENT;
   if (c->finalized) return fail(c, LGH_INVALID_ARGUMENT, "the QJL matrices must be given before lgh_finalize");
-  if (!kv_is_qjl(c->d.kv_cache_type)) return fail(c, LGH_INVALID_ARGUMENT, "this context has no TurboQuantProd (QJL) KV cache");
+  if (!c->kvl.qjl()) return fail(c, LGH_INVALID_ARGUMENT, "this context has no TurboQuantProd (QJL) KV cache");
   const size_t want = (size_t)(c->l1 - c->l0) * c->d.num_kv_heads * c->d.head_dim * c->d.head_dim;
   if (!m || n != want) return fail(c, LGH_INVALID_ARGUMENT, "expected " + std::to_string(want) + " matrix elements");
   for (size_t i = 0; i < n; i++)
@@ -362,7 +383,6 @@ int lgh_finalize(lgh_ctx* c) {
     c->embd_host.clear();
     c->embd_host.shrink_to_fit();
   }
-  const size_t kv_elems = (size_t)d.num_kv_heads * d.max_seq_len * d.head_dim;
   for (uint32_t i = c->l0; i < c->l1; i++) {
     LayerW& L = c->layers[i];
     const std::string p = "blk." + std::to_string(i) + ".";
@@ -383,23 +403,7 @@ int lgh_finalize(lgh_ctx* c) {
     } else if (!L.gate.present() || !L.up.present() || !L.down.present()) {
       return fail(c, LGH_INITIALIZATION_FAILED, "missing FFN weights of " + p);
     }
-    // the layer's cache, by format (a size of 0: the format has no such tensor):
-    //   f32     per-layer K/V [kv_heads, max_seq, head_dim] (gpu_only.rs:555-572)
-    //   int8    QuantizedKVCache::new (kv_quantized.rs:57-102): byte rows + a scale per (kv head, position); the FP8 formats have no
-    //           scales (kv_quantized.rs:31-35)
-    //   TQ      TurboQuantKVCache::new (kv_turboquant.rs:36-86): packed codes, no scales, no norms; with QJL + per K row the sign bits
-    //           of the projected residual and its norm (quant.rs:176-186)
-    const size_t n_rows = (size_t)d.num_kv_heads * d.max_seq_len;
-    const bool f32 = !(d.flags & LGH_FLAG_KV_INT8), tq = kv_is_tq(d.kv_cache_type);
-    const size_t row_bytes = tq ? n_rows * tq_row_bytes_host(kv_tq_bits(d.kv_cache_type), d.head_dim) : f32 ? 0 : kv_elems;
-    const size_t scale_bytes = d.kv_cache_type == LGH_KV_INT8 ? n_rows * 4 : 0;
-    const AllocSpec kv[] = {
-        {(void**)&L.kcache, f32 ? kv_elems * 4 : 0}, {(void**)&L.vcache, f32 ? kv_elems * 4 : 0},
-        {(void**)&L.k8, row_bytes},                  {(void**)&L.v8, row_bytes},
-        {(void**)&L.kscale, scale_bytes},            {(void**)&L.vscale, scale_bytes},
-        {(void**)&L.kx, kv_is_qjl(d.kv_cache_type) ? n_rows * (d.head_dim / 32 + 1) * 4 : 0},
-    };
-    if ((rc = alloc_zeroed(c, kv, sizeof(kv) / sizeof(kv[0]), c->stats.kv_bytes))) return rc;
+    if ((rc = kv_alloc(c, 1, L.kv))) return rc;   // the own sequence's cache
   }
   const uint32_t EI = d.expert_intermediate_size ? d.expert_intermediate_size : d.intermediate_size;
   const size_t ffn = std::max<size_t>(d.intermediate_size, EI);
@@ -424,7 +428,7 @@ int lgh_finalize(lgh_ctx* c) {
       {(void**)&c->tok_log, (size_t)d.max_seq_len * 4},
   };
   if ((rc = alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes))) return rc;
-  if (kv_is_tq(d.kv_cache_type)) {
+  if (c->kvl.tq()) {
     // the rotations' sign vectors, [owned layer][kv head][k, v][head_dim]: given through lgh_set_kv_rotation_signs (the Rust host
     // passes every engine's HadamardRotation::signs()), otherwise a deterministic stand-in — NOT the reference's StdRng stream
     const size_t n = (size_t)(c->l1 - c->l0) * d.num_kv_heads * 2 * d.head_dim;
@@ -440,7 +444,7 @@ int lgh_finalize(lgh_ctx* c) {
     if (c->tq_signs_host.size() != n) return fail(c, LGH_INVALID_ARGUMENT, "the rotation sign vector has the wrong length for this context");
     if ((rc = dev_alloc(c, (void**)&c->tq_signs, n * 4))) return rc;
     HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpy(c->tq_signs, c->tq_signs_host.data(), n * 4, hipMemcpyHostToDevice));
-    if (kv_is_qjl(d.kv_cache_type)) {
+    if (c->kvl.qjl()) {
       // the K engines' projection matrices, [owned layer][kv head][head_dim][head_dim]: given through lgh_set_kv_qjl_matrices, otherwise
       // a deterministic stand-in (Box-Muller over a counter hash: i.i.d. N(0, 1), NOT the reference's StdRng / ziggurat stream)
       const size_t nm = (size_t)(c->l1 - c->l0) * d.num_kv_heads * d.head_dim * d.head_dim;
@@ -610,28 +614,18 @@ int lgh_kv_shift_left(lgh_ctx* c, size_t amount) {
     // tensor goes through a scratch buffer: two strided device-to-device copies instead of the host's memmove.
     const size_t new_len = c->pos - amount, row = (size_t)d.head_dim * 4;
     if (!c->kv_shift_tmp && (rc = dev_alloc(c, (void**)&c->kv_shift_tmp, (size_t)d.num_kv_heads * d.max_seq_len * row))) return rc;
-    // (base, bytes per position): the f32 caches, or the int8 rows and their scales (QuantizedKVCache::shift_left, kv_quantized.rs:330-372)
-    auto shift = [&](void* base, size_t rb) -> int {
-      uint8_t* b = (uint8_t*)base;
-      HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpy2DAsync(c->kv_shift_tmp, new_len * rb, b + amount * rb, (size_t)d.max_seq_len * rb, new_len * rb,
-                                                        d.num_kv_heads, hipMemcpyDeviceToDevice, c->stream));
-      HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpy2DAsync(b, (size_t)d.max_seq_len * rb, c->kv_shift_tmp, new_len * rb, new_len * rb, d.num_kv_heads,
-                                                        hipMemcpyDeviceToDevice, c->stream));
-      return LGH_OK;
-    };
-    for (uint32_t li = c->l0; li < c->l1; li++) {
-      LayerW& L = c->layers[li];
-      if (kv_is_tq(d.kv_cache_type)) {   // TurboQuantKVCache::shift_left (kv_turboquant.rs:245-266): code rows
-        const size_t rb = tq_row_bytes_host(kv_tq_bits(d.kv_cache_type), d.head_dim);
-        if ((rc = shift(L.k8, rb)) || (rc = shift(L.v8, rb))) return rc;
-        if (kv_is_qjl(d.kv_cache_type) && (rc = shift(L.kx, (size_t)(d.head_dim / 32 + 1) * 4))) return rc;
-      } else if (d.flags & LGH_FLAG_KV_INT8) {
-        if ((rc = shift(L.k8, d.head_dim)) || (rc = shift(L.v8, d.head_dim))) return rc;
-        if (d.kv_cache_type == LGH_KV_INT8 && ((rc = shift(L.kscale, 4)) || (rc = shift(L.vscale, 4)))) return rc;
-      } else if ((rc = shift(L.kcache, row)) || (rc = shift(L.vcache, row))) {
-        return rc;
+    // (base, bytes per position) of every tensor the format has: KVCache::shift_left, QuantizedKVCache::shift_left (kv_quantized.rs:
+    // 330-372: rows and scales), TurboQuantKVCache::shift_left (kv_turboquant.rs:245-266: code rows)
+    for (uint32_t li = c->l0; li < c->l1; li++)
+      for (int kind = 0; kind < KV_KINDS; kind++) {
+        uint8_t* const b = (uint8_t*)c->layers[li].kv.t[kind];
+        const size_t rb = c->kvl.pos_bytes(kind);
+        if (!rb) continue;
+        HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpy2DAsync(c->kv_shift_tmp, new_len * rb, b + amount * rb, (size_t)d.max_seq_len * rb, new_len * rb,
+                                                          d.num_kv_heads, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpy2DAsync(b, (size_t)d.max_seq_len * rb, c->kv_shift_tmp, new_len * rb, new_len * rb, d.num_kv_heads,
+                                                          hipMemcpyDeviceToDevice, c->stream));
       }
-    }
     c->pos = new_len;
   }
   HIP_TRY(c, LGH_OPERATION_FAILED, hipMemsetD32Async((hipDeviceptr_t)(c->state + ST_NEXT), (int)c->pos, 1, c->stream));
@@ -725,11 +719,7 @@ int lgh_get_stats(lgh_ctx* c, lgh_stats* out) {
       if (L.moe()) b += (uint64_t)d.num_experts_per_token * (L.gate_exps.bytes + L.up_exps.bytes + L.down_exps.bytes) + (uint64_t)d.num_experts * d.hidden_size * 4;
       else b += L.gate.bytes + L.up.bytes + L.down.bytes;
       b += (uint64_t)2 * d.hidden_size * 4;                                       // norm weights
-      const uint64_t kv_row = kv_is_tq(d.kv_cache_type) ? tq_row_bytes_host(kv_tq_bits(d.kv_cache_type), d.head_dim)
-                              : d.kv_cache_type == LGH_KV_INT8 ? d.head_dim + 4                                // int8 row + its scale
-                              : d.kv_cache_type != LGH_KV_F32 ? d.head_dim : (uint64_t)d.head_dim * 4;
-      b += (uint64_t)2 * d.num_kv_heads * (c->pos + 1) * kv_row;                  // KV read (kv_len = pos+1)
-      b += (uint64_t)2 * d.num_kv_heads * kv_row;                                 // KV write
+      b += c->kvl.step_alg_bytes(c->pos + 1);                                     // KV read (kv_len = pos+1) + write
     }
     if (c->last) b += c->output.bytes + (uint64_t)d.hidden_size * 4 + (uint64_t)d.vocab_size * 4;
   }

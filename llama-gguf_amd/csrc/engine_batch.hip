@@ -105,7 +105,7 @@ int launch_mvb(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float*
   B.n_seq = n_seq;
   B.pos = Bs.d_pos;
   B.slot = Bs.d_slot;
-  B.cache_stride = Bs.cache_stride;
+  B.cache_stride = c->kvl.stride_floats();
   B.part = Bs.mv_part;
   B.part_floats = Bs.mv_part_floats;
   B.ind_cnt = ind.cnt;
@@ -133,14 +133,14 @@ int qkv_forward_multi(lgh_ctx* c, LayerW& Lw, uint32_t li, uint32_t n_seq) {
   BatchScratch& Bs = c->batch;
   const lgh_model_desc& d = c->d;
   const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim;
-  const bool staged = (d.flags & LGH_FLAG_KV_INT8) != 0;   // every quantized cache (TurboQuant, int8, FP8) stages its rows
+  const bool staged = c->kvl.staged();   // every quantized cache (TurboQuant, int8, FP8) stages its rows
   const uint32_t KD = d.num_kv_heads * d.head_dim;
   int rc;
   SegSpec sp[3];
   sp[0].W[0] = &Lw.wq; sp[0].x[0] = Bs.hidden; sp[0].epi = EPI_ROPE_Q; sp[0].out = Bs.q; sp[0].bias = Lw.bq;
   // (quantized caches: the rotated K row and the V row stay f32 in a staging vector per sequence; the attention launch compresses them)
-  sp[1].W[0] = &Lw.wk; sp[1].x[0] = Bs.hidden; sp[1].epi = staged ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = staged ? Bs.kv_tmp : Bs.kcache[li]; sp[1].bias = Lw.bk;
-  sp[2].W[0] = &Lw.wv; sp[2].x[0] = Bs.hidden; sp[2].epi = staged ? EPI_STORE : EPI_V_CACHE; sp[2].out = staged ? Bs.kv_tmp + KD : Bs.vcache[li]; sp[2].bias = Lw.bv;
+  sp[1].W[0] = &Lw.wk; sp[1].x[0] = Bs.hidden; sp[1].epi = staged ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = staged ? Bs.kv_tmp : Bs.kv[li].k_f32(); sp[1].bias = Lw.bk;
+  sp[2].W[0] = &Lw.wv; sp[2].x[0] = Bs.hidden; sp[2].epi = staged ? EPI_STORE : EPI_V_CACHE; sp[2].out = staged ? Bs.kv_tmp + KD : Bs.kv[li].v_f32(); sp[2].bias = Lw.bv;
   const uint32_t os[3] = {QD, staged ? 2 * KD : 0, staged ? 2 * KD : 0}, rs[3] = {0, 0, 0}, xk[3] = {0, 0, 0};
   if (mv_formats_split(sp, 3)) {   // (one launch each then, as launch_mv does)
     for (int s = 0; s < 3; s++)
@@ -201,25 +201,27 @@ int moe_grouped_forward(lgh_ctx* c, LayerW& Lw, uint32_t n_seq, const float* nex
 }
 
 // attention_cached per sequence (ops.rs:1479-1537) over layer li's cache slots, whatever their format: split + merge, the sequence as
-// the grid's second dimension, Bs.q -> Bs.attn_out.  The one place that knows which of the scratch's strides goes to which launcher.
+// the grid's second dimension, Bs.q -> Bs.attn_out.  The one place that knows which of the layout's strides goes to which launcher.
 // xq_out: the merge also leaves every sequence's XQ image of attn_out for wo (where its views are registered)
 int attention_forward_multi(lgh_ctx* c, uint32_t li, uint32_t n_seq, float scale, bool xq_out) {
   BatchScratch& Bs = c->batch;
   const lgh_model_desc& d = c->d;
+  const KvLayout& kvl = c->kvl;
+  const KvCache& kv = Bs.kv[li];
   const uint32_t QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim;
   int rc;
   XqBuf* const qa = xq_out ? xq_find(c, Bs.attn_out) : nullptr;
   uint8_t* const img = qa ? qa->xq : nullptr;
-  if (kv_is_tq(d.kv_cache_type)) {
+  if (kvl.tq()) {
     // TurboQuantKVCache (kv_turboquant.rs) per sequence: write_kv + attention over the slot's codes; the merge inverts the V rotation
-    const int bits = kv_tq_bits(d.kv_cache_type);
-    const bool qjl = kv_is_qjl(d.kv_cache_type);
+    const int bits = kvl.tq_bits();
+    const bool qjl = kvl.qjl();
     const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
     const float* qjl_s = qjl ? c->tq_qjl + (size_t)(li - c->l0) * d.num_kv_heads * d.head_dim * d.head_dim : nullptr;
     if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-           return attn_tq_multi_launch(bits, Bs.q, Bs.kq[li], Bs.vq[li], Bs.kv_tmp, Bs.kv_tmp + KD, signs, d.num_heads, d.num_kv_heads, d.head_dim,
-                                       d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, Bs.code_stride, Bs.x_stride, 2 * KD, n_seq, c->n_splits, Bs.part_ml,
-                                       Bs.part_acc, c->stream, qjl_s, qjl ? Bs.kx[li] : nullptr);
+           return attn_tq_multi_launch(bits, Bs.q, kv.k_bytes(), kv.v_bytes(), Bs.kv_tmp, Bs.kv_tmp + KD, signs, d.num_heads, d.num_kv_heads, d.head_dim,
+                                       d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, kvl.stride_bytes(), kvl.stride_words(), 2 * KD, n_seq, c->n_splits, Bs.part_ml,
+                                       Bs.part_acc, c->stream, qjl_s, qjl ? kv.kx() : nullptr);
          })))
       return rc;
     rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
@@ -227,18 +229,18 @@ int attention_forward_multi(lgh_ctx* c, uint32_t li, uint32_t n_seq, float scale
                                     c->stream, n_seq, (uint32_t)xq_stride_of(QD));
     });
   } else {
-    if (d.flags & LGH_FLAG_KV_INT8) {
+    if (kvl.staged()) {
       // QuantizedKVCache (kv_quantized.rs) per sequence: the launch quantizes and stores each sequence's staged rows into its slot; the
       // partials merge as f32 ones do (as in the single-sequence engine)
       rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-        return attn_q8_multi_launch((int)d.kv_cache_type, Bs.q, (int8_t*)Bs.kq[li], (int8_t*)Bs.vq[li], Bs.kscale[li], Bs.vscale[li], Bs.kv_tmp,
+        return attn_q8_multi_launch((int)d.kv_cache_type, Bs.q, kv.k_i8(), kv.v_i8(), kv.kscale(), kv.vscale(), Bs.kv_tmp,
                                     Bs.kv_tmp + KD, 2 * KD, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, n_seq,
                                     c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
       });
     } else {
       rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-        return attn_multi_launch(Bs.q, Bs.kcache[li], Bs.vcache[li], d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot,
-                                 Bs.cache_stride, n_seq, c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
+        return attn_multi_launch(Bs.q, kv.k_f32(), kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot,
+                                 kvl.stride_floats(), n_seq, c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
       });
     }
     if (rc) return rc;
@@ -462,26 +464,6 @@ uint64_t batch_part_floats(const lgh_ctx* c, uint32_t max_batch) {
   return need;
 }
 
-// How a layer's cache slots lie, from the model fields: the distances between two slots — f32 rows [kv_head][max_seq][head_dim];
-// QuantizedKVCache::new per slot (kv_quantized.rs:143-300), a byte per element; TurboQuantKVCache::new per slot (kv_turboquant.rs:36-86),
-// packed codes (+ QJL rows of K) — and the per-layer tables of the caches, still empty
-void batch_cache_layout(lgh_ctx* c) {
-  BatchScratch& Bs = c->batch;
-  const lgh_model_desc& d = c->d;
-  const size_t rows = (size_t)d.num_kv_heads * d.max_seq_len;
-  const bool tq = kv_is_tq(d.kv_cache_type);
-  Bs.cache_stride = rows * d.head_dim;
-  Bs.code_stride = tq ? rows * tq_row_bytes_host(kv_tq_bits(d.kv_cache_type), d.head_dim) : (d.flags & LGH_FLAG_KV_INT8) ? rows * d.head_dim : 0;
-  Bs.x_stride = tq ? rows * (d.head_dim / 32 + 1) : 0;
-  Bs.kcache.assign(d.num_layers, nullptr);
-  Bs.vcache.assign(d.num_layers, nullptr);
-  Bs.kq.assign(d.num_layers, nullptr);
-  Bs.vq.assign(d.num_layers, nullptr);
-  Bs.kx.assign(d.num_layers, nullptr);
-  Bs.kscale.assign(d.num_layers, nullptr);
-  Bs.vscale.assign(d.num_layers, nullptr);
-}
-
 // the scratch of the multi-sequence engine for max_batch slots on a context whose model fields and layers are set: the vectors of the
 // sequences side by side with their registered XQ views, the control words, the partial-sum buffer, every slot's caches and the
 // grouped MoE step's buffers (lgh_batch_create; the per-launch entry points of ops_api.hip)
@@ -494,7 +476,7 @@ int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch) {
   const uint32_t ffn = std::max(d.intermediate_size, EI);
   Bs.max_batch = max_batch;
   Bs.ffn = ffn;
-  batch_cache_layout(c);
+  Bs.kv.assign(d.num_layers, KvCache{});
   const size_t B = max_batch;
   Bs.mv_part_floats = batch_part_floats(c, max_batch);
   uint8_t *xq_h = nullptr, *xq_a = nullptr, *xq_f = nullptr, *xq_f2 = nullptr;
@@ -513,16 +495,9 @@ int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch) {
       {(void**)&xq_f2, B * xq_stride_of(ffn)}, {(void**)&ssq_f2, B * ssq_stride_of(ffn) * 4},
   };
   if ((rc = alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes))) return rc;
-  const bool kv8 = (d.flags & LGH_FLAG_KV_INT8) && !kv_is_tq(d.kv_cache_type);   // int8 / FP8: a byte per element (+ a scale per int8 row)
-  if ((d.flags & LGH_FLAG_KV_INT8) && (rc = dev_alloc(c, (void**)&Bs.kv_tmp, B * 2 * d.num_kv_heads * d.head_dim * 4))) return rc;
-  for (uint32_t i = c->l0; i < c->l1; i++) {   // per layer, every slot's cache: code rows (+ QJL rows of K), byte rows (+ int8 scales), or f32 [slot][kv_head][max_seq][head_dim]
-    const bool tq = kv_is_tq(d.kv_cache_type);
-    const size_t n = tq || kv8 ? B * Bs.code_stride : 0, nf = tq || kv8 ? 0 : B * Bs.cache_stride * 4;
-    const size_t ns = d.kv_cache_type == LGH_KV_INT8 ? B * d.num_kv_heads * d.max_seq_len * 4 : 0;
-    const AllocSpec kv[] = {{(void**)&Bs.kq[i], n}, {(void**)&Bs.vq[i], n}, {(void**)&Bs.kx[i], kv_is_qjl(d.kv_cache_type) ? B * Bs.x_stride * 4 : 0},
-                            {(void**)&Bs.kscale[i], ns}, {(void**)&Bs.vscale[i], ns}, {(void**)&Bs.kcache[i], nf}, {(void**)&Bs.vcache[i], nf}};
-    if ((rc = alloc_zeroed(c, kv, sizeof(kv) / sizeof(kv[0]), c->stats.kv_bytes))) return rc;
-  }
+  if (c->kvl.staged() && (rc = dev_alloc(c, (void**)&Bs.kv_tmp, B * 2 * d.num_kv_heads * d.head_dim * 4))) return rc;
+  for (uint32_t i = c->l0; i < c->l1; i++)   // per layer, every slot's cache
+    if ((rc = kv_alloc(c, B, Bs.kv[i]))) return rc;
   {   // MoE layers: the expert-grouped step's buffers ((sequence, slot) pairs)
     bool any_moe = false;
     for (uint32_t i = c->l0; i < c->l1; i++) any_moe = any_moe || c->layers[i].moe();

@@ -39,6 +39,14 @@ int alloc_zeroed(lgh_ctx* c, const AllocSpec* bufs, size_t count, uint64_t& coun
   return LGH_OK;
 }
 
+// The tensors the format has (KvLayout), each for n_slots sequences; the others stay null.  lgh_finalize: the own sequence's,
+// batch_scratch_alloc: the slots'
+int kv_alloc(lgh_ctx* c, size_t n_slots, KvCache& kv) {
+  AllocSpec bufs[KV_KINDS];
+  for (int kind = 0; kind < KV_KINDS; kind++) bufs[kind] = {&kv.t[kind], n_slots * c->kvl.slot_bytes(kind)};
+  return alloc_zeroed(c, bufs, KV_KINDS, c->stats.kv_bytes);
+}
+
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ------------------------------------------------------------------------------------------------

@@ -127,16 +127,16 @@ int moe_experts_forward(lgh_ctx* c, LayerW& Lw, const FfnView& v, const float* n
 int qkv_forward(lgh_ctx* c, LayerW& Lw, const AttnView& v) {
   const lgh_model_desc& d = c->d;
   int rc;
-  const bool kv8 = (d.flags & LGH_FLAG_KV_INT8) != 0;
-  float* const k_new = v.kv_tmp;                                                     // byte caches: the current token's rotated K row ...
+  const bool staged = c->kvl.staged();
+  float* const k_new = v.kv_tmp;                                                     // staged formats: the current token's rotated K row ...
   float* const v_new = k_new ? k_new + (size_t)d.num_kv_heads * d.head_dim : nullptr;   // ... and V row, f32, quantized by the attention launch
   const bool fused = fused_type(Lw.wq.type) && fused_type(Lw.wk.type) && fused_type(Lw.wv.type) && !d.use_neox_rope;
-  if (!k_new && (kv8 || !fused)) return fail(c, LGH_INVALID_ARGUMENT, "qkv_forward: this layer stages its K / V rows and the view has no kv_tmp");
+  if (!k_new && (staged || !fused)) return fail(c, LGH_INVALID_ARGUMENT, "qkv_forward: this layer stages its K / V rows and the view has no kv_tmp");
   if (fused) {
     SegSpec sp[3];
     sp[0].W[0] = &Lw.wq; sp[0].x[0] = v.hidden; sp[0].epi = EPI_ROPE_Q; sp[0].out = v.q; sp[0].bias = Lw.bq;
-    sp[1].W[0] = &Lw.wk; sp[1].x[0] = v.hidden; sp[1].epi = kv8 ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = kv8 ? k_new : Lw.kcache; sp[1].bias = Lw.bk;
-    sp[2].W[0] = &Lw.wv; sp[2].x[0] = v.hidden; sp[2].epi = kv8 ? EPI_STORE : EPI_V_CACHE; sp[2].out = kv8 ? v_new : Lw.vcache; sp[2].bias = Lw.bv;
+    sp[1].W[0] = &Lw.wk; sp[1].x[0] = v.hidden; sp[1].epi = staged ? EPI_ROPE_Q : EPI_ROPE_K; sp[1].out = staged ? k_new : Lw.kv.k_f32(); sp[1].bias = Lw.bk;
+    sp[2].W[0] = &Lw.wv; sp[2].x[0] = v.hidden; sp[2].epi = staged ? EPI_STORE : EPI_V_CACHE; sp[2].out = staged ? v_new : Lw.kv.v_f32(); sp[2].bias = Lw.bv;
     return launch_mv(c, LGH_K_QKV, sp, 3, Lw.attn_norm, d.hidden_size);
   }
   if ((rc = linear_any(c, LGH_K_QKV, Lw.wq, v.hidden, v.q, Lw.attn_norm, nullptr, Lw.bq))) return rc;
@@ -147,9 +147,9 @@ int qkv_forward(lgh_ctx* c, LayerW& Lw, const AttnView& v) {
          return rope_launch(v.q, k_new, d.num_heads, d.num_kv_heads, d.head_dim, c->state + ST_POS, c->rope_cs, (int)d.use_neox_rope, c->stream);
        })))
     return rc;
-  if (kv8) return LGH_OK;
+  if (staged) return LGH_OK;
   return run_k(c, LGH_K_MISC, LGH_SYM_OTHER, 0, [&] {
-    return kv_store_launch(k_new, v_new, Lw.kcache, Lw.vcache, d.num_kv_heads, d.head_dim, d.max_seq_len, c->state + ST_POS, c->stream);
+    return kv_store_launch(k_new, v_new, Lw.kv.k_f32(), Lw.kv.v_f32(), d.num_kv_heads, d.head_dim, d.max_seq_len, c->state + ST_POS, c->stream);
   });
 }
 
@@ -158,12 +158,12 @@ int qkv_forward(lgh_ctx* c, LayerW& Lw, const AttnView& v) {
 int attention_forward(lgh_ctx* c, LayerW& Lw, uint32_t li, const AttnView& v, float scale, bool xq_out) {
   const lgh_model_desc& d = c->d;
   int rc;
-  const bool kv8 = (d.flags & LGH_FLAG_KV_INT8) != 0;
-  const float* const k_new = v.kv_tmp;                                                     // (byte caches only)
+  const KvLayout& kvl = c->kvl;
+  const KvCache& kv = Lw.kv;
+  const float* const k_new = v.kv_tmp;                                                     // (staged formats only)
   const float* const v_new = k_new ? k_new + (size_t)d.num_kv_heads * d.head_dim : nullptr;
   const int* const pos = c->state + ST_POS;
-  const uint64_t kv_bytes = (uint64_t)2 * d.num_kv_heads * (c->pos + 1) *
-                            (d.kv_cache_type == LGH_KV_INT8 ? d.head_dim + 4 : kv8 ? d.head_dim : d.head_dim * 4);
+  const uint64_t kv_bytes = kvl.launch_bytes(c->pos + 1);
   XqBuf* qa = nullptr;
   auto image = [&]() -> uint8_t* {
     qa = xq_out ? xq_get(c, v.attn_out, d.num_heads * d.head_dim) : nullptr;
@@ -174,43 +174,41 @@ int attention_forward(lgh_ctx* c, LayerW& Lw, uint32_t li, const AttnView& v, fl
       return attn_combine_launch(c->part_ml, c->part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, v.attn_out, img, c->stream);
     });
   };
-  if (kv_is_tq(d.kv_cache_type)) {
+  if (kvl.tq()) {
     // TurboQuantKVCache (kv_turboquant.rs): write_kv + attention_layer over the codes; the merge also inverts the V rotation
-    const int bits = kv_tq_bits(d.kv_cache_type);
+    const int bits = kvl.tq_bits();
     const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
-    const bool qjl = kv_is_qjl(d.kv_cache_type);
+    const bool qjl = kvl.qjl();
     const float* qjl_s = qjl ? c->tq_qjl + (size_t)(li - c->l0) * d.num_kv_heads * d.head_dim * d.head_dim : nullptr;
-    const uint64_t tq_bytes = (uint64_t)d.num_kv_heads * (c->pos + 1) * (2 * tq_row_bytes_host(bits, d.head_dim) + (qjl ? d.head_dim / 8 + 4 : 0)) +
-                              (qjl ? (uint64_t)d.num_kv_heads * d.head_dim * d.head_dim * 4 : 0);
-    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, tq_bytes, [&] {
-           return attn_tq_launch(bits, v.q, (uint8_t*)Lw.k8, (uint8_t*)Lw.v8, k_new, v_new, signs, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len,
-                                 scale, pos, c->n_splits, c->part_ml, c->part_acc, c->stream, qjl_s, qjl ? Lw.kx : nullptr);
+    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
+           return attn_tq_launch(bits, v.q, kv.k_bytes(), kv.v_bytes(), k_new, v_new, signs, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len,
+                                 scale, pos, c->n_splits, c->part_ml, c->part_acc, c->stream, qjl_s, qjl ? kv.kx() : nullptr);
          })))
       return rc;
     uint8_t* const img = image();
     rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
       return attn_tq_combine_launch(bits, c->part_ml, c->part_acc, signs, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, v.attn_out, img, c->stream);
     });
-  } else if (kv8) {
+  } else if (kvl.staged()) {
     // int8 rows + scales (kv_quantized.rs); the launch also quantizes and stores the current token's rows
     if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-           return attn_q8_launch((int)d.kv_cache_type, v.q, Lw.k8, Lw.v8, Lw.kscale, Lw.vscale, k_new, v_new, d.num_heads, d.num_kv_heads, d.head_dim,
+           return attn_q8_launch((int)d.kv_cache_type, v.q, kv.k_i8(), kv.v_i8(), kv.kscale(), kv.vscale(), k_new, v_new, d.num_heads, d.num_kv_heads, d.head_dim,
                                  d.max_seq_len, scale, pos, c->n_splits, c->part_ml, c->part_acc, c->stream);
          })))
       return rc;
     rc = merge(image());
   } else if (c->attn_generic) {   // any head size / group size: f32 out, no image
     rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-      return attn_decode_any_launch(v.q, Lw.kcache, Lw.vcache, v.attn_out, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, c->stream);
+      return attn_decode_any_launch(v.q, kv.k_f32(), kv.v_f32(), v.attn_out, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, c->stream);
     });
   } else if (c->attn_direct) {    // short context: one launch
     uint8_t* const img = image();
     rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-      return attn_direct_launch(v.q, Lw.kcache, Lw.vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, v.attn_out, img, c->stream);
+      return attn_direct_launch(v.q, kv.k_f32(), kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, v.attn_out, img, c->stream);
     });
   } else {                        // n_splits ranges of the context, then their merge
     if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-           return attn_launch(v.q, Lw.kcache, Lw.vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, 0, c->n_splits, c->part_ml,
+           return attn_launch(v.q, kv.k_f32(), kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, 0, c->n_splits, c->part_ml,
                               c->part_acc, c->stream);
          })))
       return rc;

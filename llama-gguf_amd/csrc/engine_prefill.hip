@@ -19,7 +19,7 @@ bool pf_eligible(const lgh_ctx* c, bool slot) {
   // The batched path writes f32 K/V rows.  The f32 cache takes them as they are; a TurboQuantMSE cache (tq2 / tq3) takes them through an
   // f32 scratch (pf_tq_rows below), for the own sequence of a context that owns every layer.  The QJL formats, int8 and FP8, slots of
   // the multi-sequence engine and stage contexts with a TurboQuant cache stay token by token.
-  if (d.flags & LGH_FLAG_KV_INT8) {
+  if (c->kvl.staged()) {
     if (d.kv_cache_type != LGH_KV_TQ2 && d.kv_cache_type != LGH_KV_TQ3) return false;
     if (slot || !c->first || !c->last) return false;
   }
@@ -71,7 +71,7 @@ int pf_ensure(lgh_ctx* c) {
       {(void**)&P.moe_base, any_moe ? (size_t)kPfMaxExperts * 4 : 0},   {(void**)&P.moe_rowmap, any_moe ? (size_t)kPfMoeRows * 4 : 0},
       {(void**)&P.moe_tokmap, any_moe ? (size_t)kPfTokens * kPfMaxTopK * 4 : 0},
       {(void**)&P.xh_gather, any_moe ? xh_bytes(H) * d.num_experts : 0}, {(void**)&P.xh_act_e, any_moe ? xh_bytes(EI) * d.num_experts : 0},
-      {(void**)&P.tq_kv, kv_is_tq(d.kv_cache_type) ? (size_t)2 * d.num_kv_heads * d.max_seq_len * d.head_dim * 4 : 0},   // (scratch, not KV bytes)
+      {(void**)&P.tq_kv, c->kvl.tq() ? (size_t)2 * c->kvl.stride_floats() * 4 : 0},   // (scratch, not KV bytes)
   };
   if (int rc = alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes)) return rc;
   // the zero-fills are done before anybody else (another stream, a peer's copy into the stage block) touches the buffers
@@ -115,8 +115,8 @@ static int pf_tq_rows(lgh_ctx* c, LayerW& L, uint32_t li, uint32_t pos0, uint32_
   PfScratch& P = c->pf;
   const lgh_model_desc& d = c->d;
   const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
-  float* const vscr = P.tq_kv + (size_t)d.num_kv_heads * d.max_seq_len * d.head_dim;
-  return pf_k(c, tq_pf_rows_launch(kv_tq_bits(d.kv_cache_type), P.tq_kv, vscr, (uint8_t*)L.k8, (uint8_t*)L.v8, attend ? P.q : nullptr, signs, d.num_heads,
+  float* const vscr = P.tq_kv + c->kvl.stride_floats();
+  return pf_k(c, tq_pf_rows_launch(c->kvl.tq_bits(), P.tq_kv, vscr, L.kv.k_bytes(), L.kv.v_bytes(), attend ? P.q : nullptr, signs, d.num_heads,
                                    d.num_kv_heads, d.head_dim, d.max_seq_len, pos0, m, attend ? m : 0, attend ? pos0 : 0, c->stream),
               "TurboQuant rows");
 }
@@ -197,7 +197,6 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
   const lgh_model_desc& d = c->d;
   const uint32_t H = d.hidden_size;
   const uint32_t pos0 = (uint32_t)t.pos0;
-  const size_t slot_off = t.slot < 0 ? 0 : (size_t)t.slot * c->batch.cache_stride;
   hipStream_t st = c->stream;
   if (c->first) {
     // The caller's `tokens` may be freed as soon as this returns (lgh_stage_prefill_batch does not synchronise), so the ids
@@ -221,13 +220,14 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
   }
   if ((rc = pf_block_input(c, c->layers[c->l0].attn_norm, m))) return rc;
   const float scale = 1.0f / std::sqrt((float)d.head_dim);  // layers.rs:374
-  const bool tq = kv_is_tq(d.kv_cache_type);
+  const bool tq = c->kvl.tq();
   if (tq && t.slot >= 0) return fail(c, LGH_UNSUPPORTED, "TurboQuant slots have no batched prompt path");
   for (uint32_t li = c->l0; li < c->l1; li++) {
     LayerW& L = c->layers[li];
     // (a TurboQuant cache: the scratch stands in for the layer's f32 cache; pf_eligible admits the context's own sequence only)
-    float* const kcache = tq ? P.tq_kv : t.slot < 0 ? L.kcache : c->batch.kcache[li] + slot_off;
-    float* const vcache = tq ? P.tq_kv + (size_t)d.num_kv_heads * d.max_seq_len * d.head_dim : t.slot < 0 ? L.vcache : c->batch.vcache[li] + slot_off;
+    const KvCache kv = kv_of(c, li, t.slot);
+    float* const kcache = tq ? P.tq_kv : kv.k_f32();
+    float* const vcache = tq ? P.tq_kv + c->kvl.stride_floats() : kv.v_f32();
     const bool attend = !(li + 1 == c->l1 && c->last);   // the model's last layer: its K/V rows are written, its output would be discarded
     if ((rc = pf_qkv_step(c, L, kcache, vcache, pos0, m))) return rc;
     if (tq && (rc = pf_tq_rows(c, L, li, pos0, m, attend))) return rc;

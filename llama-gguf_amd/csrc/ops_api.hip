@@ -73,6 +73,12 @@ struct Tmp {  // bare context: stream, device state words, tracked allocations
   }
 };
 
+bool signs_ok(const float* signs, size_t n) {   // rotation signs: +1 or -1
+  for (size_t i = 0; i < n; i++)
+    if (signs[i] != 1.0f && signs[i] != -1.0f) return false;
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -308,49 +314,40 @@ int lgh_op_kv_roundtrip(int device, uint32_t kv_cache_type, const float* row, si
   return t.down(back_out, dback, n);
 }
 
-int lgh_op_tq_compress(int device, int bits, const float* x, size_t dim, const float* signs, uint8_t* codes) {
+// One row through TurboQuantMSE::compress; qjl: also the QJL sign bits and the residual norm of TurboQuantProd
+static int tq_compress_op(int device, int bits, const float* x, size_t dim, const float* signs, bool qjl, const float* qjl_matrix, uint8_t* codes,
+                          uint64_t* qjl_bits, float* residual_norm) {
   Tmp t(device);
   if (t.rc) return t.rc;
-  if (!x || !signs || !codes) return LGH_INVALID_ARGUMENT;
+  if (!x || !signs || !codes || (qjl && (!qjl_matrix || !qjl_bits || !residual_norm))) return LGH_INVALID_ARGUMENT;
   if ((bits != 2 && bits != 3) || (dim != 64 && dim != 128)) return LGH_UNSUPPORTED;
-  for (size_t i = 0; i < dim; i++)
-    if (signs[i] != 1.0f && signs[i] != -1.0f) return LGH_INVALID_ARGUMENT;
-  float *dx = t.up(x, dim), *ds = t.up(signs, dim);
-  const size_t rb = tq_row_bytes_host(bits, (uint32_t)dim);
-  uint8_t* dc = reinterpret_cast<uint8_t*>(t.up(nullptr, (rb + 3) / 4));
-  if (!dx || !ds || !dc) return LGH_ALLOCATION_FAILED;
-  if (tq_compress_launch(bits, dx, (uint32_t)dim, ds, dc, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
-  std::vector<float> tmp((rb + 3) / 4);
-  int rc = t.down(tmp.data(), reinterpret_cast<float*>(dc), (rb + 3) / 4);
-  if (rc) return rc;
-  std::memcpy(codes, tmp.data(), rb);
-  return LGH_OK;
-}
-
-int lgh_op_tq_compress_qjl(int device, int bits, const float* x, size_t dim, const float* signs, const float* qjl_matrix, uint8_t* codes,
-                           uint64_t* qjl_bits, float* residual_norm) {
-  Tmp t(device);
-  if (t.rc) return t.rc;
-  if (!x || !signs || !codes || !qjl_matrix || !qjl_bits || !residual_norm) return LGH_INVALID_ARGUMENT;
-  if ((bits != 2 && bits != 3) || (dim != 64 && dim != 128)) return LGH_UNSUPPORTED;
-  for (size_t i = 0; i < dim; i++)
-    if (signs[i] != 1.0f && signs[i] != -1.0f) return LGH_INVALID_ARGUMENT;
-  float *dx = t.up(x, dim), *ds = t.up(signs, dim), *dS = t.up(qjl_matrix, dim * dim);
+  if (!signs_ok(signs, dim)) return LGH_INVALID_ARGUMENT;
+  float *dx = t.up(x, dim), *ds = t.up(signs, dim), *dS = qjl ? t.up(qjl_matrix, dim * dim) : nullptr;
   const size_t rb = tq_row_bytes_host(bits, (uint32_t)dim), xw = dim / 32 + 1;
   uint8_t* dc = reinterpret_cast<uint8_t*>(t.up(nullptr, (rb + 3) / 4));
-  uint32_t* dq = reinterpret_cast<uint32_t*>(t.up(nullptr, xw));
-  if (!dx || !ds || !dS || !dc || !dq) return LGH_ALLOCATION_FAILED;
+  uint32_t* dq = qjl ? reinterpret_cast<uint32_t*>(t.up(nullptr, xw)) : nullptr;
+  if (!dx || !ds || !dc || (qjl && (!dS || !dq))) return LGH_ALLOCATION_FAILED;
   if (tq_compress_launch(bits, dx, (uint32_t)dim, ds, dc, t.c->stream, dS, dq) != hipSuccess) return LGH_OPERATION_FAILED;
   std::vector<float> tmp((rb + 3) / 4), tq(xw);
   int rc = t.down(tmp.data(), reinterpret_cast<float*>(dc), (rb + 3) / 4);
   if (rc) return rc;
-  if ((rc = t.down(tq.data(), reinterpret_cast<float*>(dq), xw))) return rc;
   std::memcpy(codes, tmp.data(), rb);
+  if (!qjl) return LGH_OK;
+  if ((rc = t.down(tq.data(), reinterpret_cast<float*>(dq), xw))) return rc;
   uint32_t w[8] = {};
   std::memcpy(w, tq.data(), xw * 4);
   for (size_t i = 0; i < dim / 64; i++) qjl_bits[i] = (uint64_t)w[2 * i] | (uint64_t)w[2 * i + 1] << 32;
   std::memcpy(residual_norm, &w[dim / 32], 4);
   return LGH_OK;
+}
+
+int lgh_op_tq_compress(int device, int bits, const float* x, size_t dim, const float* signs, uint8_t* codes) {
+  return tq_compress_op(device, bits, x, dim, signs, false, nullptr, codes, nullptr, nullptr);
+}
+
+int lgh_op_tq_compress_qjl(int device, int bits, const float* x, size_t dim, const float* signs, const float* qjl_matrix, uint8_t* codes,
+                           uint64_t* qjl_bits, float* residual_norm) {
+  return tq_compress_op(device, bits, x, dim, signs, true, qjl_matrix, codes, qjl_bits, residual_norm);
 }
 
 int lgh_op_matmul(int device, const float* a, const float* b, float* out, size_t m, size_t k, size_t n) {
@@ -445,7 +442,7 @@ int attn_setup(Tmp& t, uint32_t kv_cache_type, size_t n_heads, size_t n_kv, size
   c->d.head_dim = (uint32_t)head_dim;
   c->d.max_seq_len = (uint32_t)max_seq;
   c->d.kv_cache_type = kv_cache_type;
-  if (kv_cache_type != LGH_KV_F32) c->d.flags |= LGH_FLAG_KV_INT8;   // (as lgh_create marks every byte-per-element cache)
+  c->kvl = KvLayout(c->d);
   c->n_splits = (uint32_t)n_splits;
   const size_t parts = n_seq * n_kv * (size_t)n_splits * (n_heads / n_kv);
   if (!parts) return LGH_OK;   // (a one-launch path: no partial results)
@@ -470,51 +467,61 @@ bool seqs_ok(size_t n_seq, size_t max_n, const int* slot, size_t n_slots, bool d
   return check_seqs(n_seq, max_n, slot, n_slots, distinct, [&](size_t i) { return (uint64_t)(int64_t)pos[i]; }, max_seq) == SEQ_OK;
 }
 
+// the step's K row | V row per sequence, side by side as the engine's kv_tmp holds them, from k_new / v_new [n_seq][kd]
+float* up_kv_new(Tmp& t, const float* k_new, const float* v_new, size_t kd, size_t n_seq = 1) {
+  float* d = t.up(nullptr, n_seq * 2 * kd);
+  for (size_t s = 0; d && s < n_seq; s++)
+    if (hipMemcpyAsync(d + s * 2 * kd, k_new + s * kd, kd * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+        hipMemcpyAsync(d + s * 2 * kd + kd, v_new + s * kd, kd * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
+      return nullptr;
+  return d;
+}
+
 // the bare context as attention_forward_multi reads it, for one layer (0) of cache slots: attn_setup's fields, and of the batch scratch
-// the slots' layout, the sequences' queries, staged rows ([sequence][K row | V row]; k_new: byte caches only) and outputs, the partial
-// results and the control words.  The caller puts its caches into the layer's tables
+// the sequences' queries, staged rows ([sequence][K row | V row]; k_new: staged formats only) and outputs, the partial results and the
+// control words.  The caller puts its caches into the layer's entry (Bs.kv[0])
 int attn_multi_setup(Tmp& t, uint32_t kv_cache_type, const float* q, const float* k_new, const float* v_new, size_t n_heads, size_t n_kv,
                      size_t head_dim, size_t max_seq, size_t n_seq, const int* pos, const int* slot, int n_splits) {
   lgh_ctx* c = t.c;
   BatchScratch& Bs = c->batch;
   if (int rc = attn_setup(t, kv_cache_type, n_heads, n_kv, head_dim, max_seq, n_splits, n_seq)) return rc;
   c->d.num_layers = 1;
-  batch_cache_layout(c);
+  Bs.kv.assign(1, KvCache{});
   const size_t QD = n_heads * head_dim, KD = n_kv * head_dim;
   Bs.part_ml = c->part_ml;
   Bs.part_acc = c->part_acc;
   Bs.q = t.up(q, n_seq * QD);
   Bs.attn_out = t.up(nullptr, n_seq * QD);
-  Bs.kv_tmp = k_new ? t.up(nullptr, n_seq * 2 * KD) : nullptr;
+  Bs.kv_tmp = k_new ? up_kv_new(t, k_new, v_new, KD, n_seq) : nullptr;
   Bs.d_pos = (int*)up_bytes(t, nullptr, kMaxBatch * 4);
   Bs.d_slot = (int*)up_bytes(t, nullptr, kMaxBatch * 4);
   if (!Bs.q || !Bs.attn_out || (k_new && !Bs.kv_tmp) || !Bs.d_pos || !Bs.d_slot) return LGH_ALLOCATION_FAILED;
-  for (size_t s = 0; k_new && s < n_seq; s++)
-    if (hipMemcpyAsync(Bs.kv_tmp + s * 2 * KD, k_new + s * KD, KD * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(Bs.kv_tmp + s * 2 * KD + KD, v_new + s * KD, KD * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-      return LGH_OPERATION_FAILED;
   return mb_control(t, pos, slot, n_seq);
 }
 
-// the current token's K row | V row, side by side as the engine's kv_tmp holds them
-float* up_kv_new(Tmp& t, const float* k_new, const float* v_new, size_t kd) {
-  float* d = t.up(nullptr, 2 * kd);
-  if (!d || hipMemcpyAsync(d, k_new, kd * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
-      hipMemcpyAsync(d + kd, v_new, kd * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess)
-    return nullptr;
-  return d;
+// A cache's tensors for n_slots slots of one layer, between the caller's host arrays (in KvKind order) and the device.  Up: every
+// tensor the format has.  An f32 cache gets kAttnSlackRows rows of NaN behind its last head: a decode attention kernel whose row
+// clamp is off by up to a first batch of rows (32 splits x 8 waves x 4 rows) reads those, not whatever follows the allocation
+constexpr size_t kAttnSlackRows = 1024;
+int kv_upload(Tmp& t, const KvLayout& l, size_t n_slots, const void* const* host, KvCache& kv) {
+  const size_t slack = l.f32() ? kAttnSlackRows * l.row_bytes() : 0;
+  for (int kind = 0; kind < KV_KINDS; kind++) {
+    const size_t n = n_slots * l.slot_bytes(kind);
+    if (!n) continue;
+    if (dev_alloc(t.c, &kv.t[kind], n + slack)) return LGH_ALLOCATION_FAILED;
+    if (hipMemcpyAsync(kv.t[kind], host[kind], n, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
+        (slack && hipMemsetAsync((uint8_t*)kv.t[kind] + n, 0xFF, slack, t.c->stream) != hipSuccess))
+      return LGH_OPERATION_FAILED;
+  }
+  return LGH_OK;
 }
 
-// an f32 KV cache with kAttnSlackRows rows of NaN behind the last head: a decode attention kernel whose row clamp is off by up to a
-// first batch of rows (32 splits x 8 waves x 4 rows) reads those, not whatever follows the allocation
-constexpr size_t kAttnSlackRows = 1024;
-float* up_cache(Tmp& t, const float* host, size_t n, size_t head_dim) {
-  const size_t slack = kAttnSlackRows * head_dim;
-  float* d = t.up(nullptr, n + slack);
-  if (!d || hipMemcpyAsync(d, host, n * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess ||
-      hipMemsetAsync(d + n, 0xFF, slack * 4, t.c->stream) != hipSuccess)
-    return nullptr;
-  return d;
+// ... and down: every tensor the format has and the caller gave an array for
+int kv_download(Tmp& t, const KvLayout& l, size_t n_slots, void* const* host, const KvCache& kv) {
+  for (int kind = 0; kind < KV_KINDS; kind++)
+    if (host[kind] && l.pos_bytes(kind))
+      if (int rc = down_bytes(t, host[kind], kv.t[kind], n_slots * l.slot_bytes(kind))) return rc;
+  return LGH_OK;
 }
 
 // wo's input as the merge leaves it (xq.h), when an attention entry point is asked for it.  One sequence: attention_forward registered
@@ -544,6 +551,32 @@ int attn_multi_images_down(Tmp& t, size_t n_seq, size_t qd, uint8_t* image_out) 
   return down_bytes(t, image_out, qa->xq, (n_seq + 1) * xq_stride_of((uint32_t)qd));
 }
 
+// The single-sequence step on the context attn_setup has shaped: the cache from the caller's arrays, attention_forward over it; back
+// come the output, wo's input where asked for and (down: its arrays) the cache with the row the launch stored
+int attn_run(Tmp& t, const AttnView& v, const void* const* up, void* const* down, float scale, float* out, uint8_t* image_out) {
+  const size_t qd = (size_t)t.c->d.num_heads * t.c->d.head_dim;
+  LayerW Lw;   // (the one layer of a context that owns layer 0: its signs and matrices are the context's first)
+  int rc;
+  if ((rc = kv_upload(t, t.c->kvl, 1, up, Lw.kv))) return rc;
+  if (attention_forward(t.c, Lw, 0, v, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_image_down(t, v.attn_out, qd, image_out))) return rc;
+  if (down && (rc = kv_download(t, t.c->kvl, 1, down, Lw.kv))) return rc;
+  return t.down(out, v.attn_out, qd);
+}
+
+// ... and the multi-sequence step on the context attn_multi_setup has shaped, over n_slots slots
+int attn_multi_run(Tmp& t, size_t n_slots, size_t n_seq, const void* const* up, void* const* down, float scale, float* out, uint8_t* image_out) {
+  BatchScratch& Bs = t.c->batch;
+  const size_t qd = (size_t)t.c->d.num_heads * t.c->d.head_dim;
+  int rc;
+  if ((rc = kv_upload(t, t.c->kvl, n_slots, up, Bs.kv[0]))) return rc;
+  if (image_out && (rc = attn_multi_images(t, n_seq, qd))) return rc;
+  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
+  if (image_out && (rc = attn_multi_images_down(t, n_seq, qd, image_out))) return rc;
+  if (down && (rc = kv_download(t, t.c->kvl, n_slots, down, Bs.kv[0]))) return rc;
+  return t.down(out, Bs.attn_out, n_seq * qd);
+}
+
 float half_to_float(uint16_t h) {
   const uint32_t s = (uint32_t)(h >> 15) << 31, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
   float v;
@@ -569,25 +602,21 @@ int lgh_op_attention_decode(int device, int path, const float* q, const float* k
   if (!q || !k_cache || !v_cache || !out || n_kv == 0 || n_heads % n_kv || head_dim == 0 || pos >= max_seq || max_seq > 0x7FFFFFFFu)
     return LGH_INVALID_ARGUMENT;
   if (path < 0 || path > 2 || (path == 2 && image_out)) return LGH_INVALID_ARGUMENT;   // (the any-shape kernel leaves no image)
-  const size_t g = n_heads / n_kv, cache = n_kv * max_seq * head_dim;
+  const size_t g = n_heads / n_kv;
   const bool fast = attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)g);
   if (path != 2 && !fast) return LGH_UNSUPPORTED;
   if (path == 0 && (n_splits < 1 || n_splits > 32)) return LGH_INVALID_ARGUMENT;
   if (path == 2 && max_seq * 4 > 150 * 1024) return LGH_UNSUPPORTED;   // the scores of a head live in LDS
-  LayerW Lw;
-  Lw.kcache = up_cache(t, k_cache, cache, head_dim);
-  Lw.vcache = up_cache(t, v_cache, cache, head_dim);
   const AttnView v{nullptr, t.up(q, n_heads * head_dim), nullptr, t.up(nullptr, n_heads * head_dim)};   // (f32 cache: no staged rows)
-  if (!v.q || !Lw.kcache || !Lw.vcache || !v.attn_out) return LGH_ALLOCATION_FAILED;
+  if (!v.q || !v.attn_out) return LGH_ALLOCATION_FAILED;
   int rc;
   if ((rc = attn_setup(t, LGH_KV_F32, n_heads, n_kv, head_dim, max_seq, path == 0 ? n_splits : 0)) || (rc = set_pos(t, pos))) return rc;
   // 0: split + merge (attn_launch picks 4 or 8 waves from max_seq); 1: one launch (engine: pos + 1 <= direct_attn_max_kv); 2: the
   // kernel of the shapes the others do not cover (engine: every token of such a model), here on any head_dim / group size
   t.c->attn_direct = path == 1;
   t.c->attn_generic = path == 2;
-  if (attention_forward(t.c, Lw, 0, v, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
-  if (image_out && (rc = attn_image_down(t, v.attn_out, n_heads * head_dim, image_out))) return rc;
-  return t.down(out, v.attn_out, n_heads * head_dim);
+  const void* const caches[KV_KINDS] = {k_cache, v_cache};
+  return attn_run(t, v, caches, nullptr, scale, out, image_out);
 }
 
 int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads, size_t n_kv,
@@ -600,17 +629,9 @@ int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cac
       n_slots == 0 || n_splits < 1 || n_splits > 32 || !seqs_ok(n_seq, kMaxBatch, slot, n_slots, false, pos, max_seq))
     return LGH_INVALID_ARGUMENT;
   if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
-  const size_t cache = n_slots * n_kv * max_seq * head_dim, QD = n_heads * head_dim;
-  int rc;
-  if ((rc = attn_multi_setup(t, LGH_KV_F32, q, nullptr, nullptr, n_heads, n_kv, head_dim, max_seq, n_seq, pos, slot, n_splits))) return rc;
-  BatchScratch& Bs = t.c->batch;
-  Bs.kcache[0] = up_cache(t, k_cache, cache, head_dim);
-  Bs.vcache[0] = up_cache(t, v_cache, cache, head_dim);
-  if (!Bs.kcache[0] || !Bs.vcache[0]) return LGH_ALLOCATION_FAILED;
-  if (image_out && (rc = attn_multi_images(t, n_seq, QD))) return rc;
-  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
-  if (image_out && (rc = attn_multi_images_down(t, n_seq, QD, image_out))) return rc;
-  return t.down(out, Bs.attn_out, n_seq * QD);
+  if (int rc = attn_multi_setup(t, LGH_KV_F32, q, nullptr, nullptr, n_heads, n_kv, head_dim, max_seq, n_seq, pos, slot, n_splits)) return rc;
+  const void* const caches[KV_KINDS] = {k_cache, v_cache};
+  return attn_multi_run(t, n_slots, n_seq, caches, nullptr, scale, out, image_out);
 }
 
 int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
@@ -623,22 +644,13 @@ int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int
   const bool i8 = kv_cache_type == LGH_KV_INT8;
   if (!q || !k_bytes || !v_bytes || !k_new || !v_new || !out || (i8 && (!k_scale || !v_scale))) return LGH_INVALID_ARGUMENT;
   if (n_kv == 0 || n_heads % n_kv || pos >= max_seq || max_seq > 0x7FFFFFFFu || n_splits < 1 || n_splits > 32) return LGH_INVALID_ARGUMENT;
-  const size_t g = n_heads / n_kv, rows = n_kv * max_seq, cache = rows * head_dim;
-  if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)g)) return LGH_UNSUPPORTED;
-  LayerW Lw;
-  Lw.k8 = (int8_t*)up_bytes(t, k_bytes, cache);
-  Lw.v8 = (int8_t*)up_bytes(t, v_bytes, cache);
-  Lw.kscale = i8 ? t.up(k_scale, rows) : nullptr;
-  Lw.vscale = i8 ? t.up(v_scale, rows) : nullptr;
+  if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
   const AttnView v{nullptr, t.up(q, n_heads * head_dim), up_kv_new(t, k_new, v_new, n_kv * head_dim), t.up(nullptr, n_heads * head_dim)};
-  if (!v.q || !v.kv_tmp || !Lw.k8 || !Lw.v8 || (i8 && (!Lw.kscale || !Lw.vscale)) || !v.attn_out) return LGH_ALLOCATION_FAILED;
+  if (!v.q || !v.kv_tmp || !v.attn_out) return LGH_ALLOCATION_FAILED;
   int rc;
   if ((rc = attn_setup(t, kv_cache_type, n_heads, n_kv, head_dim, max_seq, n_splits)) || (rc = set_pos(t, pos))) return rc;
-  if (attention_forward(t.c, Lw, 0, v, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
-  if (image_out && (rc = attn_image_down(t, v.attn_out, n_heads * head_dim, image_out))) return rc;
-  if ((rc = down_bytes(t, k_bytes, Lw.k8, cache)) || (rc = down_bytes(t, v_bytes, Lw.v8, cache))) return rc;
-  if (i8 && ((rc = t.down(k_scale, Lw.kscale, rows)) || (rc = t.down(v_scale, Lw.vscale, rows)))) return rc;
-  return t.down(out, v.attn_out, n_heads * head_dim);
+  void* const caches[KV_KINDS] = {k_bytes, v_bytes, k_scale, v_scale};
+  return attn_run(t, v, caches, caches, scale, out, image_out);
 }
 
 int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
@@ -655,21 +667,9 @@ int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* 
       n_splits < 1 || n_splits > 32 || !seqs_ok(n_seq, kMaxBatch, slot, n_slots, true, pos, max_seq))
     return LGH_INVALID_ARGUMENT;
   if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
-  const size_t rows = n_slots * n_kv * max_seq, cache = rows * head_dim, QD = n_heads * head_dim;
-  int rc;
-  if ((rc = attn_multi_setup(t, kv_cache_type, q, k_new, v_new, n_heads, n_kv, head_dim, max_seq, n_seq, pos, slot, n_splits))) return rc;
-  BatchScratch& Bs = t.c->batch;
-  Bs.kq[0] = (uint8_t*)up_bytes(t, k_bytes, cache);
-  Bs.vq[0] = (uint8_t*)up_bytes(t, v_bytes, cache);
-  Bs.kscale[0] = i8 ? t.up(k_scale, rows) : nullptr;
-  Bs.vscale[0] = i8 ? t.up(v_scale, rows) : nullptr;
-  if (!Bs.kq[0] || !Bs.vq[0] || (i8 && (!Bs.kscale[0] || !Bs.vscale[0]))) return LGH_ALLOCATION_FAILED;
-  if (image_out && (rc = attn_multi_images(t, n_seq, QD))) return rc;
-  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
-  if (image_out && (rc = attn_multi_images_down(t, n_seq, QD, image_out))) return rc;
-  if ((rc = down_bytes(t, k_bytes, Bs.kq[0], cache)) || (rc = down_bytes(t, v_bytes, Bs.vq[0], cache))) return rc;
-  if (i8 && ((rc = t.down(k_scale, Bs.kscale[0], rows)) || (rc = t.down(v_scale, Bs.vscale[0], rows)))) return rc;
-  return t.down(out, Bs.attn_out, n_seq * QD);
+  if (int rc = attn_multi_setup(t, kv_cache_type, q, k_new, v_new, n_heads, n_kv, head_dim, max_seq, n_seq, pos, slot, n_splits)) return rc;
+  void* const caches[KV_KINDS] = {k_bytes, v_bytes, k_scale, v_scale};
+  return attn_multi_run(t, n_slots, n_seq, caches, caches, scale, out, image_out);
 }
 
 int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl, const float* k_new,
@@ -679,31 +679,22 @@ int lgh_op_attention_tq(int device, uint32_t kv_cache_type, const float* q, uint
   // rows, the merge inverts the V rotation
   Tmp t(device);
   if (t.rc) return t.rc;
-  if (!kv_is_tq(kv_cache_type)) return LGH_UNSUPPORTED;
-  const bool qjl = kv_is_qjl(kv_cache_type);
-  const int bits = kv_tq_bits(kv_cache_type);
+  const KvLayout l(kv_cache_type, n_kv, max_seq, head_dim);
+  if (!l.tq()) return LGH_UNSUPPORTED;
+  const bool qjl = l.qjl();
   if (!q || !k_codes || !v_codes || !k_new || !v_new || !signs || !out || (qjl && (!k_qjl || !qjl_matrices))) return LGH_INVALID_ARGUMENT;
   if (n_kv == 0 || n_heads % n_kv || pos >= max_seq || max_seq > 0x7FFFFFFFu || n_splits < 1 || n_splits > 32) return LGH_INVALID_ARGUMENT;
-  const size_t g = n_heads / n_kv, rows = n_kv * max_seq, d = head_dim;
-  if (!attn_shape_has_fast_kernel((uint32_t)d, (uint32_t)g)) return LGH_UNSUPPORTED;
-  for (size_t i = 0; i < n_kv * 2 * d; i++)
-    if (signs[i] != 1.0f && signs[i] != -1.0f) return LGH_INVALID_ARGUMENT;
-  const size_t cb = rows * tq_row_bytes_host(bits, (uint32_t)d), xw = rows * (d / 32 + 1);
-  LayerW Lw;   // (the one layer of a context that owns layer 0: its signs and matrices are the context's first)
-  Lw.k8 = (int8_t*)up_bytes(t, k_codes, cb);
-  Lw.v8 = (int8_t*)up_bytes(t, v_codes, cb);
-  Lw.kx = qjl ? (uint32_t*)up_bytes(t, k_qjl, xw * 4) : nullptr;
+  const size_t d = head_dim;
+  if (!attn_shape_has_fast_kernel((uint32_t)d, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
+  if (!signs_ok(signs, n_kv * 2 * d)) return LGH_INVALID_ARGUMENT;
   t.c->tq_signs = t.up(signs, n_kv * 2 * d);
   t.c->tq_qjl = qjl ? t.up(qjl_matrices, n_kv * d * d) : nullptr;
   const AttnView v{nullptr, t.up(q, n_heads * d), up_kv_new(t, k_new, v_new, n_kv * d), t.up(nullptr, n_heads * d)};
-  if (!v.q || !v.kv_tmp || !t.c->tq_signs || !Lw.k8 || !Lw.v8 || (qjl && (!Lw.kx || !t.c->tq_qjl)) || !v.attn_out) return LGH_ALLOCATION_FAILED;
+  if (!v.q || !v.kv_tmp || !t.c->tq_signs || (qjl && !t.c->tq_qjl) || !v.attn_out) return LGH_ALLOCATION_FAILED;
   int rc;
   if ((rc = attn_setup(t, kv_cache_type, n_heads, n_kv, d, max_seq, n_splits)) || (rc = set_pos(t, pos))) return rc;
-  if (attention_forward(t.c, Lw, 0, v, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
-  if (image_out && (rc = attn_image_down(t, v.attn_out, n_heads * d, image_out))) return rc;
-  if ((rc = down_bytes(t, k_codes, Lw.k8, cb)) || (rc = down_bytes(t, v_codes, Lw.v8, cb))) return rc;
-  if (qjl && (rc = down_bytes(t, k_qjl, Lw.kx, xw * 4))) return rc;
-  return t.down(out, v.attn_out, n_heads * d);
+  void* const caches[KV_KINDS] = {k_codes, v_codes, nullptr, nullptr, k_qjl};
+  return attn_run(t, v, caches, caches, scale, out, image_out);
 }
 
 int lgh_op_attention_tq_multi(int device, uint32_t kv_cache_type, const float* q, uint8_t* k_codes, uint8_t* v_codes, uint32_t* k_qjl,
@@ -713,34 +704,23 @@ int lgh_op_attention_tq_multi(int device, uint32_t kv_cache_type, const float* q
   // the multi-sequence decode step's attention (engine_batch.hip: attention_forward_multi) over TurboQuant cache slots
   Tmp t(device);
   if (t.rc) return t.rc;
-  if (!kv_is_tq(kv_cache_type)) return LGH_UNSUPPORTED;
-  const bool qjl = kv_is_qjl(kv_cache_type);
-  const int bits = kv_tq_bits(kv_cache_type);
+  const KvLayout l(kv_cache_type, n_kv, max_seq, head_dim);
+  if (!l.tq()) return LGH_UNSUPPORTED;
+  const bool qjl = l.qjl();
   if (!q || !k_codes || !v_codes || !k_new || !v_new || !signs || !out || !pos || !slot || (qjl && (!k_qjl || !qjl_matrices))) return LGH_INVALID_ARGUMENT;
   // (two sequences on one slot would both store a row into it)
   if (n_kv == 0 || n_heads % n_kv || head_dim == 0 || max_seq == 0 || max_seq > 0x7FFFFFFFu || n_slots == 0 || n_slots > (size_t)kMaxBatch ||
       n_splits < 1 || n_splits > 32 || !seqs_ok(n_seq, kMaxBatch, slot, n_slots, true, pos, max_seq))
     return LGH_INVALID_ARGUMENT;
-  const size_t d = head_dim, rows = n_slots * n_kv * max_seq, QD = n_heads * d;
+  const size_t d = head_dim;
   if (!attn_shape_has_fast_kernel((uint32_t)d, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
-  for (size_t i = 0; i < n_kv * 2 * d; i++)
-    if (signs[i] != 1.0f && signs[i] != -1.0f) return LGH_INVALID_ARGUMENT;
-  const size_t cb = rows * tq_row_bytes_host(bits, (uint32_t)d), xw = rows * (d / 32 + 1);
-  int rc;
-  if ((rc = attn_multi_setup(t, kv_cache_type, q, k_new, v_new, n_heads, n_kv, d, max_seq, n_seq, pos, slot, n_splits))) return rc;
-  BatchScratch& Bs = t.c->batch;
-  Bs.kq[0] = (uint8_t*)up_bytes(t, k_codes, cb);
-  Bs.vq[0] = (uint8_t*)up_bytes(t, v_codes, cb);
-  Bs.kx[0] = qjl ? (uint32_t*)up_bytes(t, k_qjl, xw * 4) : nullptr;
+  if (!signs_ok(signs, n_kv * 2 * d)) return LGH_INVALID_ARGUMENT;
+  if (int rc = attn_multi_setup(t, kv_cache_type, q, k_new, v_new, n_heads, n_kv, d, max_seq, n_seq, pos, slot, n_splits)) return rc;
   t.c->tq_signs = t.up(signs, n_kv * 2 * d);   // (the one layer of a context that owns layer 0: its signs and matrices are the context's first)
   t.c->tq_qjl = qjl ? t.up(qjl_matrices, n_kv * d * d) : nullptr;
-  if (!Bs.kq[0] || !Bs.vq[0] || !t.c->tq_signs || (qjl && (!Bs.kx[0] || !t.c->tq_qjl))) return LGH_ALLOCATION_FAILED;
-  if (image_out && (rc = attn_multi_images(t, n_seq, QD))) return rc;
-  if (attention_forward_multi(t.c, 0, (uint32_t)n_seq, scale, image_out != nullptr)) return LGH_OPERATION_FAILED;   // (a failed launch, as these entry points always answered)
-  if (image_out && (rc = attn_multi_images_down(t, n_seq, QD, image_out))) return rc;
-  if ((rc = down_bytes(t, k_codes, Bs.kq[0], cb)) || (rc = down_bytes(t, v_codes, Bs.vq[0], cb))) return rc;
-  if (qjl && (rc = down_bytes(t, k_qjl, Bs.kx[0], xw * 4))) return rc;
-  return t.down(out, Bs.attn_out, n_seq * QD);
+  if (!t.c->tq_signs || (qjl && !t.c->tq_qjl)) return LGH_ALLOCATION_FAILED;
+  void* const caches[KV_KINDS] = {k_codes, v_codes, nullptr, nullptr, k_qjl};
+  return attn_multi_run(t, n_slots, n_seq, caches, caches, scale, out, image_out);
 }
 
 // an XH matrix's first m rows, un-swizzled and widened to f32: out [m][k]
@@ -786,12 +766,6 @@ static float* pf_tq_scratch(Tmp& t, size_t cache) {
   return s;
 }
 
-static bool pf_tq_signs_ok(const float* signs, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (signs[i] != 1.0f && signs[i] != -1.0f) return false;
-  return true;
-}
-
 int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv, size_t head_dim,
                        size_t max_seq, size_t pos0, const float* signs, uint8_t* k_codes, uint8_t* v_codes) {
   // TurboQuantKVCache::write_kv (kv_turboquant.rs:88-122) for a block of prompt rows, as the batched prefill runs it
@@ -800,13 +774,15 @@ int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, 
   if (kv_cache_type != LGH_KV_TQ2 && kv_cache_type != LGH_KV_TQ3) return LGH_UNSUPPORTED;
   if (head_dim != 64 && head_dim != 128) return LGH_UNSUPPORTED;
   if (!k_rows || !v_rows || !signs || !k_codes || !v_codes || n_kv == 0 || max_seq > 0x7FFFFFFFu) return LGH_INVALID_ARGUMENT;
-  if (m == 0 || m > (size_t)kPfTokens || pos0 + m > max_seq || !pf_tq_signs_ok(signs, n_kv * 2 * head_dim)) return LGH_INVALID_ARGUMENT;
-  const int bits = kv_tq_bits(kv_cache_type);
-  const size_t d = head_dim, cache = n_kv * max_seq * d, cb = n_kv * max_seq * tq_row_bytes_host(bits, (uint32_t)d);
+  if (m == 0 || m > (size_t)kPfTokens || pos0 + m > max_seq || !signs_ok(signs, n_kv * 2 * head_dim)) return LGH_INVALID_ARGUMENT;
+  const KvLayout l(kv_cache_type, n_kv, max_seq, head_dim);
+  const size_t d = head_dim, cache = l.stride_floats();
   float* scr = pf_tq_scratch(t, cache);
-  uint8_t *dk = (uint8_t*)up_bytes(t, k_codes, cb), *dv = (uint8_t*)up_bytes(t, v_codes, cb);
+  KvCache kv;
+  void* const codes[KV_KINDS] = {k_codes, v_codes};
+  if (int rc = kv_upload(t, l, 1, codes, kv)) return rc;
   float* ds = t.up(signs, n_kv * 2 * d);
-  if (!scr || !dk || !dv || !ds) return LGH_ALLOCATION_FAILED;
+  if (!scr || !ds) return LGH_ALLOCATION_FAILED;
   hipStream_t st = t.c->stream;
   // the block's rows where the QKV epilogue leaves them: rows pos0 .. pos0+m-1 of every kv head
   for (size_t h = 0; h < n_kv; h++) {
@@ -814,12 +790,10 @@ int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, 
         hipMemcpyAsync(scr + cache + (h * max_seq + pos0) * d, v_rows + h * m * d, m * d * 4, hipMemcpyHostToDevice, st) != hipSuccess)
       return LGH_OPERATION_FAILED;
   }
-  if (tq_pf_rows_launch(bits, scr, scr + cache, dk, dv, nullptr, ds, (uint32_t)n_kv, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, (uint32_t)pos0,
+  if (tq_pf_rows_launch(l.tq_bits(), scr, scr + cache, kv.k_bytes(), kv.v_bytes(), nullptr, ds, (uint32_t)n_kv, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, (uint32_t)pos0,
                         (uint32_t)m, 0, 0, st) != hipSuccess)
     return LGH_OPERATION_FAILED;
-  int rc;
-  if ((rc = down_bytes(t, k_codes, dk, cb))) return rc;
-  return down_bytes(t, v_codes, dv, cb);
+  return kv_download(t, l, 1, codes, kv);
 }
 
 int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes, const float* signs,
@@ -832,19 +806,20 @@ int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float*
   if (!q || !k_codes || !v_codes || !signs || !out || n_kv == 0 || n_heads % n_kv || max_seq > 0x7FFFFFFFu) return LGH_INVALID_ARGUMENT;
   const size_t g = n_heads / n_kv;
   if (g != 1 && g != 2 && g != 4 && g != 8) return LGH_UNSUPPORTED;   // (pf_eligible's group sizes)
-  const size_t d = head_dim, qd = n_heads * d, cache = n_kv * max_seq * d;
-  if (m_tokens == 0 || m_tokens > (size_t)kPfTokens || qd % 256 || pos0 + m_tokens > max_seq || !pf_tq_signs_ok(signs, n_kv * 2 * d))
+  const KvLayout l(kv_cache_type, n_kv, max_seq, head_dim);
+  const size_t d = head_dim, qd = n_heads * d, cache = l.stride_floats();
+  if (m_tokens == 0 || m_tokens > (size_t)kPfTokens || qd % 256 || pos0 + m_tokens > max_seq || !signs_ok(signs, n_kv * 2 * d))
     return LGH_INVALID_ARGUMENT;
-  const int bits = kv_tq_bits(kv_cache_type);
-  const size_t cb = n_kv * max_seq * tq_row_bytes_host(bits, (uint32_t)d);
   float *dq = t.up(q, m_tokens * qd), *ds = t.up(signs, n_kv * 2 * d), *scr = pf_tq_scratch(t, cache);
-  uint8_t *dk = (uint8_t*)up_bytes(t, k_codes, cb), *dv = (uint8_t*)up_bytes(t, v_codes, cb);
+  KvCache kv;
+  const void* const codes[KV_KINDS] = {k_codes, v_codes};
+  if (int rc = kv_upload(t, l, 1, codes, kv)) return rc;
   const size_t xb = xh_bytes((uint32_t)qd);
   uint8_t* xh = (uint8_t*)up_bytes(t, nullptr, xb);
-  if (!dq || !ds || !scr || !dk || !dv || !xh) return LGH_ALLOCATION_FAILED;
+  if (!dq || !ds || !scr || !xh) return LGH_ALLOCATION_FAILED;
   hipStream_t st = t.c->stream;
   if (hipMemsetAsync(xh, 0, xb, st) != hipSuccess) return LGH_OPERATION_FAILED;
-  if (tq_pf_rows_launch(bits, scr, scr + cache, dk, dv, dq, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, (uint32_t)pos0, 0,
+  if (tq_pf_rows_launch(l.tq_bits(), scr, scr + cache, kv.k_bytes(), kv.v_bytes(), dq, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, (uint32_t)pos0, 0,
                         (uint32_t)m_tokens, (uint32_t)(pos0 + m_tokens), st) != hipSuccess)
     return LGH_OPERATION_FAILED;
   if (attn_prefill_tq_launch(dq, scr, scr + cache, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, scale, (uint32_t)pos0,
@@ -1103,52 +1078,6 @@ static size_t weight_bytes(uint32_t type, size_t k, size_t n) {
   return be && k % be == 0 ? n * (k / be) * blk_bytes((int)type) : 0;
 }
 
-int lgh_op_qkv_rope(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
-                    float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
-                    float rope_base, float rope_scale, float* q_out, float* k_cache, float* v_cache) {
-  // qkv_forward's fused QKV launch: RMSNorm prologue, Q with RoPE, K with RoPE into cache row `pos`, V into cache row `pos`
-  Tmp t(device);
-  if (t.rc) return t.rc;
-  if (!types || !w || !x || !norm_w || !q_out || !k_cache || !v_cache || hidden == 0 || head_dim == 0 || head_dim % 2 || n_kv_heads == 0 ||
-      n_heads % n_kv_heads || pos >= max_seq_len || max_seq_len > 0x7FFFFFFFu || rope_scale == 0.0f)
-    return LGH_INVALID_ARGUMENT;
-  lgh_model_desc& d = t.c->d;
-  d.norm_eps = eps;
-  d.hidden_size = (uint32_t)hidden;
-  d.head_dim = (uint32_t)head_dim;
-  d.num_heads = (uint32_t)n_heads;
-  d.num_kv_heads = (uint32_t)n_kv_heads;
-  d.max_seq_len = (uint32_t)max_seq_len;
-  d.rope_freq_base = rope_base;
-  d.rope_freq_scale = rope_scale;
-  const size_t rows[3] = {n_heads * head_dim, n_kv_heads * head_dim, n_kv_heads * head_dim};
-  LayerW Lw;
-  DevWeight* const W[3] = {&Lw.wq, &Lw.wk, &Lw.wv};
-  int rc;
-  for (int s = 0; s < 3; s++) {
-    const size_t nb = weight_bytes(types[s], hidden, rows[s]);
-    if (!nb || !w[s]) return LGH_SHAPE_MISMATCH;
-    if ((rc = upload_matrix(t.c, *W[s], (int)types[s], (uint32_t)hidden, (uint32_t)rows[s], 1, -1, w[s], nb))) return rc;
-    if (!fused_type(W[s]->type)) return LGH_UNSUPPORTED;   // the engine runs such layers unfused
-  }
-  std::vector<float> cs;
-  rope_table_host(d, cs);
-  const size_t cache = n_kv_heads * max_seq_len * head_dim;
-  t.c->rope_cs = t.up(cs.data(), cs.size());
-  const AttnView v{t.up(x, hidden), t.up(nullptr, rows[0]), nullptr, nullptr};   // (fused launch into the f32 cache: no staged rows)
-  Lw.attn_norm = t.up(norm_w, hidden);
-  Lw.kcache = t.up(k_cache, cache);
-  Lw.vcache = t.up(v_cache, cache);
-  float** const db[3] = {&Lw.bq, &Lw.bk, &Lw.bv};
-  for (int s = 0; s < 3; s++)
-    if (bias && bias[s] && !(*db[s] = t.up(bias[s], rows[s]))) return LGH_ALLOCATION_FAILED;
-  if (!t.c->rope_cs || !v.hidden || !Lw.attn_norm || !v.q || !Lw.kcache || !Lw.vcache) return LGH_ALLOCATION_FAILED;
-  if ((rc = set_pos(t, pos))) return rc;
-  if ((rc = qkv_forward(t.c, Lw, v))) return rc;
-  if ((rc = t.down(q_out, v.q, rows[0])) || (rc = t.down(k_cache, Lw.kcache, cache))) return rc;
-  return t.down(v_cache, Lw.vcache, cache);
-}
-
 int lgh_op_linear_chain(int device, uint32_t type_a, const void* w_a, const void* w_a_up, const float* bias_a, size_t k, size_t n_a,
                         const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
                         uint32_t type_b, const void* w_b, size_t n_b, float* out_a, float* out_b, float* out_b_requant, int* image_used) {
@@ -1399,18 +1328,18 @@ int lgh_op_pf_qkv(int device, const uint32_t* types, const void* const* w, const
   d.head_dim = (uint32_t)head_dim;
   std::vector<float> cs;
   rope_table_host(d, cs);
-  const size_t cache = n_kv_heads * max_seq_len * head_dim;
   t.c->rope_cs = t.up(cs.data(), cs.size());
   Lw.attn_norm = t.up(norm_w, H);
-  Lw.kcache = t.up(k_cache, cache);
-  Lw.vcache = t.up(v_cache, cache);
-  if (!t.c->rope_cs || !Lw.attn_norm || !Lw.kcache || !Lw.vcache) return LGH_ALLOCATION_FAILED;
+  const KvLayout l(LGH_KV_F32, n_kv_heads, max_seq_len, head_dim);
+  void* const caches[KV_KINDS] = {k_cache, v_cache};
+  if ((rc = kv_upload(t, l, 1, caches, Lw.kv))) return rc;
+  if (!t.c->rope_cs || !Lw.attn_norm) return LGH_ALLOCATION_FAILED;
   if ((rc = pf_test_ctx(t, Lw, H, head_dim, n_heads, n_kv_heads, 0, 0, 0, 0, eps))) return rc;
   if (hipMemcpyAsync(t.c->pf.hidden, hidden, m_tokens * H * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
   if ((rc = pf_block_input(t.c, Lw.attn_norm, (uint32_t)m_tokens))) return rc;
-  if ((rc = pf_qkv_step(t.c, t.c->layers[0], Lw.kcache, Lw.vcache, (uint32_t)pos0, (uint32_t)m_tokens))) return rc;
-  if ((rc = t.down(q_out, t.c->pf.q, m_tokens * QD)) || (rc = t.down(k_cache, Lw.kcache, cache))) return rc;
-  return t.down(v_cache, Lw.vcache, cache);
+  if ((rc = pf_qkv_step(t.c, t.c->layers[0], Lw.kv.k_f32(), Lw.kv.v_f32(), (uint32_t)pos0, (uint32_t)m_tokens))) return rc;
+  if ((rc = t.down(q_out, t.c->pf.q, m_tokens * QD))) return rc;
+  return kv_download(t, l, 1, caches, Lw.kv);
 }
 
 int lgh_op_pf_linear(int device, uint32_t type, const void* w, const float* bias, const float* x, size_t k, size_t hidden_size, const float* resid,
@@ -1521,7 +1450,8 @@ static int mb_test_ctx(Tmp& t, const LayerW& Lw, const MbShape& s, float eps, si
   d.num_experts = (uint32_t)s.E;
   d.num_experts_per_token = (uint32_t)s.top_k;
   d.expert_intermediate_size = (uint32_t)s.EI;
-  if (staged_kv) { d.flags |= LGH_FLAG_KV_INT8; d.kv_cache_type = LGH_KV_INT8; }
+  if (staged_kv) d.kv_cache_type = LGH_KV_INT8;
+  c->kvl = KvLayout(d);
   c->layers.assign(1, Lw);
   c->l0 = 0;
   c->l1 = 1;
@@ -1533,7 +1463,8 @@ static int mb_test_ctx(Tmp& t, const LayerW& Lw, const MbShape& s, float eps, si
             pf_poison(c, Bs.attn_out, B * QD * 4, kF32) && pf_poison(c, Bs.act, B * Bs.ffn * 4, kF32) && pf_poison(c, Bs.act2, B * Bs.ffn * 4, kF32) &&
             pf_poison(c, Bs.logits, B * s.vocab * 4, kF32) && pf_poison(c, Bs.mv_part, Bs.mv_part_floats * 4, kF32) &&
             pf_poison(c, Bs.moe_w, B * 8 * 4, kF32) && pf_poison(c, Bs.moe_sel, B * 8 * 4, 0x55u) && pf_poison(c, Bs.kv_tmp, B * 2 * KD * 4, kF32) &&
-            pf_poison(c, Bs.kcache[0], B * Bs.cache_stride * 4, kF32) && pf_poison(c, Bs.vcache[0], B * Bs.cache_stride * 4, kF32) &&
+            pf_poison(c, Bs.kv[0].t[KV_K], c->kvl.f32() ? B * c->kvl.slot_bytes(KV_K) : 0, kF32) &&
+            pf_poison(c, Bs.kv[0].t[KV_V], c->kvl.f32() ? B * c->kvl.slot_bytes(KV_V) : 0, kF32) &&
             pf_poison(c, Bs.moe_act, np * s.EI * 4, kF32) && pf_poison(c, Bs.moe_tmp, np * H * 4, kF32) && pf_poison(c, Bs.moe_cnt, 64 * 4, 0x55u) &&
             pf_poison(c, Bs.moe_idx, (size_t)64 * kMaxBatch * 4, np ? (uint32_t)np - 1 : 0u);
   for (const XqBuf& q : c->xqs) ok = ok && pf_poison(c, q.xq, xq_bytes(q.k), kF32) && pf_poison(c, q.ssq, (size_t)ssq_stride_of(q.k) * 4, kF32);
@@ -1710,8 +1641,8 @@ int lgh_op_qkv_rope_multi(int device, const uint32_t* types, const void* const* 
   mb_structures(structures, before);
   if ((rc = t.down(q_out, Bs.q, max_batch * QD))) return rc;
   if (staged) return t.down(staged_out, Bs.kv_tmp, max_batch * 2 * KD);
-  if ((rc = t.down(k_cache, Bs.kcache[0], max_batch * Bs.cache_stride))) return rc;
-  return t.down(v_cache, Bs.vcache[0], max_batch * Bs.cache_stride);
+  void* const caches[KV_KINDS] = {k_cache, v_cache};
+  return kv_download(t, t.c->kvl, max_batch, caches, Bs.kv[0]);
 }
 
 int lgh_op_moe_multi(int device, uint32_t type_gate_up, const void* w_gate, const void* w_up, uint32_t type_down, const void* w_down, size_t n_experts,
@@ -1850,14 +1781,16 @@ int lgh_op_embed(int device, int mode, uint32_t type, const void* table, size_t 
   return t.down(rows_out, c->hidden, nb * hidden);
 }
 
-int lgh_op_qkv_forward(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
-                       float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
-                       float rope_base, float rope_scale, int neox, int staged, float* q_out, float* k_cache, float* v_cache, float* staged_out,
-                       char* err, size_t errlen) {
+// qkv_forward on one layer's weights and a view of its own.  fused_only (lgh_op_qkv_rope): the fused launch alone — another layout is
+// refused, the view has no staged rows and none come back
+static int qkv_forward_op(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                          float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
+                          float rope_base, float rope_scale, int neox, int staged, bool fused_only, float* q_out, float* k_cache, float* v_cache,
+                          float* staged_out, char* err, size_t errlen) {
   Tmp t(device);
   if (t.rc) return t.rc;
   if (err && errlen) err[0] = 0;
-  if (!types || !w || !x || !norm_w || !q_out || !k_cache || !v_cache || !staged_out || hidden == 0 || head_dim == 0 || head_dim % 2 ||
+  if (!types || !w || !x || !norm_w || !q_out || !k_cache || !v_cache || (!fused_only && !staged_out) || hidden == 0 || head_dim == 0 || head_dim % 2 ||
       n_kv_heads == 0 || n_heads % n_kv_heads || pos >= max_seq_len || max_seq_len > 0x7FFFFFFFu || rope_scale == 0.0f)
     return LGH_INVALID_ARGUMENT;
   lgh_model_desc& d = t.c->d;
@@ -1870,7 +1803,11 @@ int lgh_op_qkv_forward(int device, const uint32_t* types, const void* const* w, 
   d.rope_freq_base = rope_base;
   d.rope_freq_scale = rope_scale;
   d.use_neox_rope = neox ? 1 : 0;
-  if (staged) d.flags |= LGH_FLAG_KV_INT8;   // (as every byte-per-element and TurboQuant cache: the rows stay in kv_tmp for the attention launch)
+  // staged: the path of every byte-per-element and TurboQuant cache, whose rows stay in kv_tmp for the attention launch; the int8
+  // format stands for them.  The f32 caches are uploaded either way and come back untouched then
+  if (staged) d.kv_cache_type = LGH_KV_INT8;
+  t.c->kvl = KvLayout(d);
+  const KvLayout f32l(LGH_KV_F32, n_kv_heads, max_seq_len, head_dim);
   const size_t rows[3] = {n_heads * head_dim, n_kv_heads * head_dim, n_kv_heads * head_dim}, KD = rows[1];
   LayerW Lw;
   DevWeight* const W[3] = {&Lw.wq, &Lw.wk, &Lw.wv};
@@ -1879,28 +1816,44 @@ int lgh_op_qkv_forward(int device, const uint32_t* types, const void* const* w, 
     const size_t nb = weight_bytes(types[s], hidden, rows[s]);
     if (!nb || !w[s]) return LGH_SHAPE_MISMATCH;
     if ((rc = upload_matrix(t.c, *W[s], (int)types[s], (uint32_t)hidden, (uint32_t)rows[s], 1, -1, w[s], nb))) return rc;
+    if (fused_only && !fused_type(W[s]->type)) return LGH_UNSUPPORTED;   // the engine runs such layers unfused
   }
   std::vector<float> cs;
   rope_table_host(d, cs);
-  const size_t cache = n_kv_heads * max_seq_len * head_dim;
   t.c->rope_cs = t.up(cs.data(), cs.size());
   // the view has staged rows as the engine's always has (c->kv_tmp); q and the rows start as the NaN pattern
-  const AttnView v{t.up(x, hidden), t.up(nullptr, rows[0]), t.up(nullptr, 2 * KD), nullptr};
+  const AttnView v{t.up(x, hidden), t.up(nullptr, rows[0]), fused_only ? nullptr : t.up(nullptr, 2 * KD), nullptr};
   Lw.attn_norm = t.up(norm_w, hidden);
-  Lw.kcache = t.up(k_cache, cache);
-  Lw.vcache = t.up(v_cache, cache);
+  void* const caches[KV_KINDS] = {k_cache, v_cache};
+  if ((rc = kv_upload(t, f32l, 1, caches, Lw.kv))) return rc;
   float** const db[3] = {&Lw.bq, &Lw.bk, &Lw.bv};
   for (int s = 0; s < 3; s++)
     if (bias && bias[s] && !(*db[s] = t.up(bias[s], rows[s]))) return LGH_ALLOCATION_FAILED;
-  if (!t.c->rope_cs || !v.hidden || !Lw.attn_norm || !v.q || !v.kv_tmp || !Lw.kcache || !Lw.vcache) return LGH_ALLOCATION_FAILED;
+  if (!t.c->rope_cs || !v.hidden || !Lw.attn_norm || !v.q || (!fused_only && !v.kv_tmp)) return LGH_ALLOCATION_FAILED;
   if (!pf_poison(t.c, v.q, rows[0] * 4, 0x7FC0BEEFu) || !pf_poison(t.c, v.kv_tmp, 2 * KD * 4, 0x7FC0BEEFu)) return LGH_OPERATION_FAILED;
   if ((rc = set_pos(t, pos))) return rc;
   if ((rc = qkv_forward(t.c, Lw, v))) {
     if (err && errlen) { std::strncpy(err, t.c->err.c_str(), errlen - 1); err[errlen - 1] = 0; }
     return rc;
   }
-  if ((rc = t.down(q_out, v.q, rows[0])) || (rc = t.down(staged_out, v.kv_tmp, 2 * KD)) || (rc = t.down(k_cache, Lw.kcache, cache))) return rc;
-  return t.down(v_cache, Lw.vcache, cache);
+  if ((rc = t.down(q_out, v.q, rows[0])) || (staged_out && (rc = t.down(staged_out, v.kv_tmp, 2 * KD)))) return rc;
+  return kv_download(t, f32l, 1, caches, Lw.kv);
+}
+
+int lgh_op_qkv_forward(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                       float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
+                       float rope_base, float rope_scale, int neox, int staged, float* q_out, float* k_cache, float* v_cache, float* staged_out,
+                       char* err, size_t errlen) {
+  return qkv_forward_op(device, types, w, bias, x, norm_w, eps, hidden, head_dim, n_heads, n_kv_heads, max_seq_len, pos, rope_base, rope_scale, neox,
+                        staged, false, q_out, k_cache, v_cache, staged_out, err, errlen);
+}
+
+int lgh_op_qkv_rope(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                    float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t pos,
+                    float rope_base, float rope_scale, float* q_out, float* k_cache, float* v_cache) {
+  // qkv_forward's fused QKV launch: RMSNorm prologue, Q with RoPE, K with RoPE into cache row `pos`, V into cache row `pos`
+  return qkv_forward_op(device, types, w, bias, x, norm_w, eps, hidden, head_dim, n_heads, n_kv_heads, max_seq_len, pos, rope_base, rope_scale, 0, 0,
+                        true, q_out, k_cache, v_cache, nullptr, nullptr, 0);
 }
 
 int lgh_op_ffn_gateup(int device, uint32_t type_gate, const void* w_gate, uint32_t type_up, const void* w_up, const float* x, const float* norm_w,

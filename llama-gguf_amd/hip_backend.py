@@ -46,7 +46,7 @@ ABI_SYMBOLS = (
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
     "lgh_op_linear_multi", "lgh_op_linear_chain_multi", "lgh_op_qkv_rope_multi", "lgh_op_moe_multi", "lgh_debug_mvqb_structures",
     "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_attention_kv8_multi", "lgh_op_attention_tq_multi",
-    "lgh_op_embed", "lgh_op_qkv_forward", "lgh_op_ffn_gateup", "lgh_op_argmax",
+    "lgh_op_embed", "lgh_op_qkv_forward", "lgh_op_ffn_gateup", "lgh_op_argmax", "lgh_kv_cache_layout",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -88,6 +88,12 @@ class ModelDesc(C.Structure):
                 + [(n, C.c_float) for n in ("norm_eps", "rope_freq_base", "rope_freq_scale")]
                 + [("device_id", C.c_int32), ("layer_begin", C.c_uint32), ("layer_end", C.c_uint32),
                    ("flags", C.c_uint32), ("kv_cache_type", C.c_uint32)])
+
+
+class KvLayout(C.Structure):
+    """lgh_kv_layout: a KV cache format's bytes per (kv head, position) and per slot of one layer."""
+    _fields_ = ([(n, C.c_uint32) for n in ("kv_cache_type", "row_bytes", "scale_bytes", "qjl_bytes")]
+                + [(n, C.c_uint64) for n in ("rows", "k_bytes", "v_bytes", "k_scale_bytes", "v_scale_bytes", "k_qjl_bytes", "slot_bytes")])
 
 
 class GgufInfo(C.Structure):
@@ -274,6 +280,7 @@ def load_library() -> C.CDLL:
                                          C.c_char_p, sz]),
         "lgh_op_ffn_gateup": (C.c_int, [C.c_int, u32, vp, u32, vp, vp, vp, f32, sz, sz, vp]),
         "lgh_op_argmax": (C.c_int, [C.c_int, vp, sz, sz, vp]),
+        "lgh_kv_cache_layout": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(KvLayout)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -997,6 +1004,16 @@ def tp_shard(ggml_type: int, ne: Sequence[int], axis: int, rank: int, n_ranks: i
     _chk(load_library().lgh_tp_shard(ggml_type, ne4, axis, rank, n_ranks, raw.ctypes.data, raw.nbytes, buf.ctypes.data, buf.nbytes,
                                      C.byref(written)), "tp_shard")
     return buf[:written.value].copy() if dst is None else written.value
+
+
+def kv_cache_layout(kv_cache_type: int, num_kv_heads: int, max_seq_len: int, head_dim: int, flags: int = 0) -> KvLayout:
+    """lgh_kv_cache_layout (host only): the sizes of the KV cache a descriptor with these fields asks for."""
+    d = ModelDesc()
+    d.struct_size = C.sizeof(ModelDesc)
+    d.kv_cache_type, d.num_kv_heads, d.max_seq_len, d.head_dim, d.flags = int(kv_cache_type), num_kv_heads, max_seq_len, head_dim, flags
+    out = KvLayout()
+    _chk(load_library().lgh_kv_cache_layout(C.byref(d), C.byref(out)), "kv_cache_layout")
+    return out
 
 
 def op_tp_reduce(partials, resid=None, norm_w=None, *, image: bool = False, ssq: bool = False, fill: int = 0, device: int = 0):

@@ -810,3 +810,19 @@ def test_turboquant_sign_vector_contract(pkg):
         pkg.HipGpuInference.from_model(pkg.SynthModel(pkg.make_config("test-dense", max_seq_len=16, head_dim=96), mix="Q4_K_M"), 16,
                                        kv_cache_type=hb.KV_TQ2)
     assert ei.value.variant in ("Unsupported", "InvalidArgument")
+
+
+@pytest.mark.parametrize("kv", range(8), ids=["f32", "int8", "fp8_e4m3", "fp8_e5m2", "tq2", "tq3", "tq2_qjl", "tq3_qjl"])
+def test_kv_bytes_are_the_layout_querys_slots(pkg, kv):
+    """What a context allocates for its caches is what lgh_kv_cache_layout says a host should expect, to the byte: one slot per layer
+    for the context's own sequence, and max_batch more per layer for the multi-sequence engine's."""
+    cfg = pkg.make_config("test-dense", max_seq_len=64)
+    slot = pkg.hip_backend.kv_cache_layout(kv, cfg.num_kv_heads, 64, cfg.head_dim).slot_bytes
+    eng = pkg.HipGpuInference.from_model(pkg.SynthModel(cfg, mix="Q4_K_M"), 64, kv_cache_type=kv)
+    try:
+        own = eng.stats()["kv_bytes"]
+        assert own == cfg.num_layers * slot
+        eng.batch_create(3)
+        assert eng.stats()["kv_bytes"] - own == 3 * cfg.num_layers * slot
+    finally:
+        eng.close()
