@@ -126,7 +126,7 @@ enum {
                                         keeps both stages.  Same bits either way; for A/B measurements and tests. */
   LGH_FLAG_ATTN_SPLITS_SHIFT = 8,    /* bits 8..15: KV splits per kv-head in decode attention (0 = auto) */
   LGH_FLAG_ATTN_DIRECT_SHIFT = 16    /* bits 16..23: contexts of up to 64 * n rows use the single-launch decode attention (one workgroup
-                                        per kv head, no split + combine pair); 0 = the tuned default, 255 = never */
+                                        per query head, no split + combine pair); 0 = the tuned default, 255 = never */
 };
 
 typedef struct lgh_ctx lgh_ctx;
@@ -552,8 +552,8 @@ int lgh_op_attention(int device, const float* q, const float* k, const float* v,
  *
  * Backend::attention_cached (ops.rs:1479-1537) over the f32 cache [n_kv_heads][max_seq_len][head_dim], rows 0..pos already
  * stored (as after the engine's kv_store).  path 0: split + merge (4 or 8 waves per workgroup, chosen from max_seq_len as in
- * the engine; n_splits 1..32); path 1: the single-launch kernel of short contexts; path 2: the kernel of any head_dim / group
- * size (max_seq_len <= 38400).
+ * the engine; n_splits 1..32); path 1: the single-launch kernel with one workgroup per kv head; path 2: the kernel of any head_dim / group
+ * size (max_seq_len <= 38400); path 3: the engine's single-launch kernel, one workgroup per query head (max_seq_len <= 16384).
  *
  * image_out (every entry point of this group; may be NULL): wo's input as the launch that writes `out` leaves it for the mat-vec, the XQ
  * image of `out` (1280 bytes per 256 elements, rounded up).  One sequence: (n_heads * head_dim + 255) / 256 * 1280 bytes; path 2

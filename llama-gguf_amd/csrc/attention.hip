@@ -35,8 +35,9 @@ namespace lgh {
 // query is q + t * n_heads * D, there is one split, and the normalised output goes, as f16, into the XH matrix at
 // `part_acc` (prefill.h: the wo GEMM's input).
 // DIRECT: one workgroup of NW = 16 waves per kv head and no second kernel: the workgroup merges its waves and writes the
-// normalised output (f32 at part_acc, XQ records at part_ml when not null) itself.  It saves one launch floor per layer
-// but pulls a kv head's whole K/V through one CU, so it only pays below ~100 rows (engine.hip: kDirectAttnDefaultKv).
+// normalised output (f32 at part_acc, XQ records at part_ml when not null) itself.  It saves one launch floor per layer but
+// every lane of a row repeats the online-softmax update and every merge is full of exponentials: bound by vector issue, it only
+// paid below ~100 rows.  The engine's single launch is attn_head_kernel below; this one stays for lgh_op_attention_decode path 1.
 // MULTI (multi-sequence decode, engine_batch.hip): blockIdx.y = sequence s of the step; its query is q + s * n_heads * D, its
 // position pos_ptr[s], its K / V the cache slot slot[s] (slot_stride floats apart), its partials the s-th block of
 // part_ml / part_acc.  Per sequence the arithmetic is the single-sequence kernel's.
@@ -126,6 +127,185 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_kernel(const float* __re
     } else {
       attn_store_partial<D>(part_ml, part_acc, pbase + g, dim, mn, lsum, a);
     }
+  }
+  LGH_TL_END();
+}
+
+// ------------------------------------------------------------------------------------------------
+// HEAD: decode attention in one launch, one workgroup of 16 waves per QUERY head (grid x = kv head, y = head of the group: the
+// G workgroups that re-read a kv head's K / V follow each other n_kv apart in dispatch order, so with n_kv % 8 == 0 they share
+// an XCD's L2 — for speed only).  A softmax in two passes instead of an online one per row:
+//   1. scores: a K row is spread over 8 lanes (D / 8 floats each, every load instruction covers 128-byte pieces of 8 rows), the
+//      lane sum is 3 DPP steps, the score goes to LDS, one float per visible row.  The score is (q * scale) . k, the query scaled
+//      once at entry, where the split kernels compute (q . k) * scale: one rounding per term apart, so the bits of the two differ;
+//   2. every wave takes the maximum over all scores itself (no barrier), the workgroup computes p = exp(s - max) once per row
+//      into LDS and each wave leaves the sum of the p it computed;
+//   3. out[d] = sum_r p_r V[r][d] with V rows spread over D / 4 lanes as in attn_partial_kernel, p_r from LDS;
+//   4. row slots (xor shuffles) and waves (LDS) merge by plain additions in a fixed order: one maximum for the whole head, so
+//      no exponential in any merge; the result times 1 / sum goes out as f32 and as wo's XQ image.
+// Rows are dealt in chunks of 128 (K: 8 per wave; V: D / 32 sweeps of 64 / (D / 4) per wave) and a thread has four chunk buffers.
+// Up to 256 rows, two chunks of K and two of V — everything the head needs — are requested before the first is used.  Longer
+// contexts keep four chunks in flight: four of K at entry, and every buffer is refilled as soon as it has been consumed, with the K
+// chunk four ahead or, after the last group of four, with V chunk 0..3, so that V streams in under the remaining scores and the
+// softmax; the V loop refills the same way.  Every request is clamped to the last visible row (unconditional requests keep the
+// counted waits in front of their uses exact); a row past the end has no score stored and p = 0, so nothing of it reaches the result.
+// cap_rows (a multiple of 128): the rows the LDS arrays hold.  A position past it would be attended to as cap_rows rows (the clamp
+// below keeps every LDS index inside the arrays); no caller lets it happen: attention_forward refuses such a position on the host.
+// ------------------------------------------------------------------------------------------------
+template <int D, int G>
+__global__ void __launch_bounds__(1024) attn_head_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc,
+                                                         const int* pos_ptr, float* __restrict__ out, uint8_t* __restrict__ xq_out, uint32_t max_seq,
+                                                         float scale, uint32_t cap_rows) {
+  constexpr int NW = 16, CH = 128;             // waves; rows per chunk
+  constexpr int NB = D / 32;                   // f32x4 per lane and chunk (K: the pieces of its row; V: sweeps)
+  constexpr int LPR = D / 4, RPW = 64 / LPR;   // V: lanes per row, rows per wave-instruction
+  static_assert(NW * RPW * NB == CH && NW * 8 == CH, "a chunk is one K sweep and NB V sweeps");
+  extern __shared__ __attribute__((aligned(16))) float ah_lds[];
+  float* const s_sc = ah_lds;                  // [cap_rows] scaled score
+  float* const s_p = s_sc + cap_rows;          // [cap_rows] exp(score - max), 0 from kv_len to the end of its chunk
+  float* const s_acc = s_p + cap_rows;         // [NW][D]
+  float* const s_sum = s_acc + NW * D;         // [NW]
+  LGH_TL_BEGIN(attn, lgh::TL_ATTN, 1);
+
+  const uint32_t kvh = blockIdx.x, head = kvh * G + blockIdx.y;
+  const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t kl = lane & 7, ksub = lane >> 3;      // K: piece of the row, row of the wave's 8
+  const uint32_t li = lane % LPR, vsub = lane / LPR;   // V: as attn_partial_kernel
+  f32x4 qv[NB];
+#pragma unroll
+  for (int j = 0; j < NB; j++) qv[j] = *reinterpret_cast<const f32x4*>(q + (size_t)head * D + j * 32 + kl * 4);
+  uint32_t kv_len = sload_u32(pos_ptr) + 1;   // scalar: the loop bounds and the row clamp depend on it
+  kv_len = kv_len < cap_rows ? kv_len : cap_rows;
+  const uint32_t n_ch = (kv_len + CH - 1) / CH, last = kv_len - 1;
+
+  // byte offsets inside the kv head (< cap_rows * D * 4 <= 2^23): scalar base + 32-bit lane offset
+  const char* const kbase = reinterpret_cast<const char*>(kc + (size_t)kvh * max_seq * D);
+  const char* const vbase = reinterpret_cast<const char*>(vc + (size_t)kvh * max_seq * D);
+  const uint32_t krow0 = wave * 8 + ksub, vrow0 = wave * RPW + vsub;
+  auto k_has = [&](uint32_t c) { return c * CH + wave * 8 < kv_len; };                         // wave-uniform
+  // (the requests are unconditional, so that the waits in front of their uses are counted exactly: a row group wholly past the end
+  // asks for the last row in every lane, one cache line per instruction)
+  auto load_k = [&](f32x4 (&k)[NB], uint32_t c) {
+    const uint32_t r = c * CH + krow0, off = (r < last ? r : last) * (D * 4) + kl * 16;
+#pragma unroll
+    for (int j = 0; j < NB; j++) k[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(kbase + off + j * 128));
+  };
+  auto load_v = [&](f32x4 (&v)[NB], uint32_t c) {
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      const uint32_t r = c * CH + j * (NW * RPW) + vrow0, off = (r < last ? r : last) * (D * 4) + li * 16;
+      v[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(vbase + off));
+    }
+  };
+  // a long context's K chunk kch or, up to 256 rows, V chunk vch: picked by address, not by a branch (a branch around requests makes
+  // every wait behind it count for its worse side)
+  const bool longc = n_ch > 2;
+  auto load_k_or_v = [&](f32x4 (&b)[NB], uint32_t kch, uint32_t vch) {
+    const char* const base = longc ? kbase : vbase;
+    const uint32_t rk = kch * CH + krow0, offk = (rk < last ? rk : last) * (D * 4) + kl * 16;
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      const uint32_t rv = vch * CH + j * (NW * RPW) + vrow0, offv = (rv < last ? rv : last) * (D * 4) + li * 16;
+      b[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base + (longc ? offk + j * 128 : offv)));
+    }
+  };
+  f32x4 buf[4][NB];
+  load_k(buf[0], 0);
+  load_k(buf[1], 1);
+  // the query takes the scale here, behind the first requests: every later wait then stands behind the query's arrival on every path
+#pragma unroll
+  for (int j = 0; j < NB; j++) qv[j] = qv[j] * scale;
+
+  // ---- 1. scores
+  auto score = [&](const f32x4 (&k)[NB], uint32_t c) {
+    if (!k_has(c)) return;
+    float s = qv[0].x * k[0].x;
+    s = __builtin_fmaf(qv[0].y, k[0].y, s); s = __builtin_fmaf(qv[0].z, k[0].z, s); s = __builtin_fmaf(qv[0].w, k[0].w, s);
+#pragma unroll
+    for (int j = 1; j < NB; j++) {
+      s = __builtin_fmaf(qv[j].x, k[j].x, s); s = __builtin_fmaf(qv[j].y, k[j].y, s);
+      s = __builtin_fmaf(qv[j].z, k[j].z, s); s = __builtin_fmaf(qv[j].w, k[j].w, s);
+    }
+    s += dpp_f<0xB1>(s);    // the 8 lanes of the row: quad_perm x2, row_half_mirror
+    s += dpp_f<0x4E>(s);
+    s += dpp_f<0x141>(s);
+    const uint32_t r = c * CH + krow0;
+    if (kl == 0 && r < kv_len) s_sc[r] = s;
+  };
+  load_k_or_v(buf[2], 2, 0);
+  load_k_or_v(buf[3], 3, 1);
+  uint32_t c = 0;
+  for (; c + 4 < n_ch; c += 4) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) { score(buf[i], c + i); load_k(buf[i], c + 4 + i); }
+  }
+  score(buf[0], c);
+  score(buf[1], c + 1);
+  if (longc) {   // the last group: V 0..3 take the buffers, in the order the V loop consumes them (2, 3, 0, 1)
+    score(buf[2], c + 2);
+    load_v(buf[2], 0);
+    score(buf[3], c + 3);
+    load_v(buf[3], 1);
+    load_v(buf[0], 2);
+    load_v(buf[1], 3);
+  }
+  __syncthreads();
+
+  // ---- 2. the head's maximum (every wave for itself), then p and its sum, each row once
+  float mx = kNegBig;
+  for (uint32_t b = 0; b < kv_len; b += 64) {
+    const uint32_t r = b + lane;
+    const float s = s_sc[r < last ? r : last];
+    mx = s > mx ? s : mx;   // (finite scores: no need for fmaxf's NaN rules)
+  }
+  mx = wave_max_dpp(mx);
+  float ps = 0.0f;
+  for (uint32_t b = wave * 64; b < n_ch * CH; b += NW * 64) {
+    const uint32_t r = b + lane;
+    const float p = r < kv_len ? __expf(s_sc[r < last ? r : last] - mx) : 0.0f;
+    s_p[r] = p;
+    ps += p;
+  }
+  ps = wave_sum_to_lane63(ps);
+  if (lane == 63) s_sum[wave] = ps;
+  __syncthreads();
+
+  // ---- 3. out = sum_r p_r V[r]
+  f32x4 acc = (f32x4)(0.0f);
+  auto accum = [&](const f32x4 (&v)[NB], uint32_t c) {
+    if (c >= n_ch) return;   // (s_p ends with the last chunk that has a visible row; in it rows past the end have p = 0)
+    float p[NB];
+#pragma unroll
+    for (int j = 0; j < NB; j++) p[j] = s_p[c * CH + j * (NW * RPW) + vrow0];
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      acc.x = __builtin_fmaf(p[j], v[j].x, acc.x); acc.y = __builtin_fmaf(p[j], v[j].y, acc.y);
+      acc.z = __builtin_fmaf(p[j], v[j].z, acc.z); acc.w = __builtin_fmaf(p[j], v[j].w, acc.w);
+    }
+  };
+  for (c = 0; c + 4 < n_ch; c += 4) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) { accum(buf[(i + 2) & 3], c + i); load_v(buf[(i + 2) & 3], c + 4 + i); }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) accum(buf[(i + 2) & 3], c + i);
+
+  // ---- 4. row slots, then waves: additions in a fixed order
+#pragma unroll
+  for (int off = LPR; off < 64; off <<= 1) {
+    acc.x += __shfl_xor(acc.x, off, 64); acc.y += __shfl_xor(acc.y, off, 64);
+    acc.z += __shfl_xor(acc.z, off, 64); acc.w += __shfl_xor(acc.w, off, 64);
+  }
+  if (vsub == 0) *reinterpret_cast<f32x4*>(&s_acc[wave * D + li * 4]) = acc;
+  __syncthreads();
+  if (threadIdx.x < (uint32_t)D) {   // whole waves
+    const uint32_t dim = threadIdx.x;
+    float o = s_acc[dim], sum = s_sum[0];
+#pragma unroll
+    for (int w = 1; w < NW; w++) { o += s_acc[w * D + dim]; sum += s_sum[w]; }
+    o = o * (1.0f / sum);   // simd.rs:718-720: multiply by 1/sum
+    out[(size_t)head * D + dim] = o;
+    if (xq_out) xq_store_chunk(xq_out, (head * D + dim) >> 4, o);   // wo's input as XQ records
   }
   LGH_TL_END();
 }
@@ -465,6 +645,29 @@ hipError_t attn_direct_launch(const float* q, const float* kcache, const float* 
     hipLaunchKernelGGL((attn_partial_kernel<decltype(d)::value, decltype(gg)::value, 16, false, true>), dim3(n_kv), dim3(1024), 0, st, q, kcache, vcache,
                        max_seq, scale, pos, 0, 1u, reinterpret_cast<float*>(xq_out), out);
     return hipGetLastError();
+  });
+}
+
+template <int D, int G>
+static hipError_t attn_head_go(const float* q, const float* kc, const float* vc, uint32_t n_kv, uint32_t max_seq, float scale, const int* pos,
+                               uint32_t cap_rows, float* out, uint8_t* xq_out, hipStream_t st) {
+  auto lds = [](uint32_t rows) { return (size_t)(2 * rows + 16 * D + 16) * 4; };
+  static bool attr_set[64] = {};
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&attn_head_kernel<D, G>), (int)lds(kAttnHeadMaxRows), attr_set); e != hipSuccess) return e;
+  hipLaunchKernelGGL((attn_head_kernel<D, G>), dim3(n_kv, G), dim3(1024), lds(cap_rows), st, q, kc, vc, pos, out, xq_out, max_seq, scale, cap_rows);
+  return hipGetLastError();
+}
+
+// single-launch decode attention, one workgroup per query head (engine.hip picks it by the host-side position).  The position word
+// must not exceed min(max_seq, max_rows) - 1: the kernel keeps a head's scores in LDS and attends to no row past that capacity.
+hipError_t attn_head_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
+                            uint32_t max_seq, float scale, const int* pos, uint32_t max_rows, float* out, uint8_t* xq_out, hipStream_t st) {
+  if (n_kv == 0 || n_heads % n_kv || !pos || max_rows == 0 || max_seq == 0) return hipErrorInvalidValue;
+  const uint32_t rows = max_rows < max_seq ? max_rows : max_seq;
+  if (rows > kAttnHeadMaxRows) return hipErrorInvalidValue;
+  const uint32_t cap_rows = (rows + 127) / 128 * 128;
+  return attn_dispatch(head_dim, n_heads / n_kv, [&](auto d, auto gg) {
+    return attn_head_go<decltype(d)::value, decltype(gg)::value>(q, kcache, vcache, n_kv, max_seq, scale, pos, cap_rows, out, xq_out, st);
   });
 }
 

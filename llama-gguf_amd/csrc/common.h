@@ -261,6 +261,11 @@ hipError_t attn_launch(const float* q, const float* kcache, const float* vcache,
                        uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st);
 hipError_t attn_direct_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
                               uint32_t max_seq, float scale, const int* pos, float* out, uint8_t* xq_out, hipStream_t st);
+// one workgroup per query head (attention.hip: attn_head_kernel); max_rows: the longest context the caller will launch it at —
+// its scores live in LDS, kAttnHeadMaxRows at the most
+constexpr uint32_t kAttnHeadMaxRows = 16384;
+hipError_t attn_head_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
+                            uint32_t max_seq, float scale, const int* pos, uint32_t max_rows, float* out, uint8_t* xq_out, hipStream_t st);
 bool attn_shape_has_fast_kernel(uint32_t head_dim, uint32_t group);
 // decode attention over the int8 KV cache (kv_quantized.rs); k_new / v_new: the current token's f32 rows [n_kv][D]
 // one row through a byte KV format (lgh_model_desc.kv_cache_type 1..3) and back

@@ -91,6 +91,22 @@ __device__ __forceinline__ float wave_sum_to_lane63(float v) {
   return v;
 }
 
+// 64-lane maximum by DPP (the steps of wave_sum_to_lane63; a row the mask leaves out keeps its own value), lane 63's total to every lane
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ float dpp_max(float v) {
+  const int b = __builtin_bit_cast(int, v);
+  return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, CTRL, ROW_MASK, 0xF, false)));
+}
+__device__ __forceinline__ float wave_max_dpp(float v) {
+  v = dpp_max<0xB1>(v);
+  v = dpp_max<0x4E>(v);
+  v = dpp_max<0x141>(v);
+  v = dpp_max<0x140>(v);
+  v = dpp_max<0x142, 0xA>(v);
+  v = dpp_max<0x143, 0xC>(v);
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));

@@ -23,6 +23,9 @@ struct LayerW {
   bool moe() const { return router != nullptr; }
 };
 
+// decode attention over the f32 cache: splits + combine, attn_partial_kernel<.., DIRECT> (one workgroup per kv head; the per-op surface only)
+// or attn_head_kernel (one workgroup per query head: the engine's single launch)
+enum AttnVariant : uint8_t { ATTN_VAR_SPLIT = 0, ATTN_VAR_DIRECT = 1, ATTN_VAR_HEAD = 2 };
 enum TokenMode { MODE_PREFILL = 0, MODE_FORWARD = 1, MODE_GREEDY = 2, MODE_SAMPLE = 3, MODE_COUNT = 4 };   // SAMPLE: GREEDY with the sampler (sample.hip) for the arg-max
 
 // The XQ image (xq.h) of an f32 activation buffer, for int8-MFMA consumers.  `fresh` = the image matches the buffer's
@@ -103,8 +106,8 @@ struct lgh_ctx {
   bool finalized = false;
   bool profiling = false;
   std::string err;
-  hipGraphExec_t graph[lgh::MODE_COUNT][2] = {};   // [mode][attention variant: 0 split + combine, 1 single launch (short context)]
-  bool attn_direct = false;                        // variant of the token being enqueued (chosen by the host-side position)
+  hipGraphExec_t graph[lgh::MODE_COUNT][2] = {};   // [mode][attention variant: 0 split + combine, 1 single launch (contexts up to direct_attn_max_kv rows)]
+  lgh::AttnVariant attn_direct = lgh::ATTN_VAR_SPLIT;   // variant of the token being enqueued (chosen by the host-side position)
   bool attn_generic = false;                       // the shape has no split kernel: every token runs attn_decode_any_kernel (a field, not
                                                    // re-derived from the shape, so that lgh_op_attention_decode can run that kernel on any shape)
   uint32_t direct_attn_max_kv = 0;                 // contexts up to this many rows take the single-launch attention

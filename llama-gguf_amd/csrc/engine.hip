@@ -26,10 +26,13 @@
 
 using namespace lgh;
 
-// Contexts up to this many rows run the single-launch decode attention (attention.hip, DIRECT) unless the flags say
-// otherwise.  Measured on Llama-3-8B Q4_K_M: 640 vs 618 tokens/s at kv <= 64, equal at kv 69..128, 581 vs 614 at kv
-// 137..272 — one workgroup per kv head fetches that head's whole K/V (1 KB per row) through ONE CU's memory path.
-constexpr uint32_t kDirectAttnDefaultKv = 64;
+// Contexts up to this many rows run the single-launch decode attention (attention.hip: attn_head_kernel, one workgroup per
+// query head) unless the flags say otherwise: the largest multiple of 64 rows at which it beats split + combine by more than
+// the run-to-run spread.  Measured on Llama-3-8B Q4_K_M (profiles/r06_attn_head.md): 743 vs 694 tokens/s at kv 65..128,
+// 730 vs 693 at 129..192, 718 vs 692 at 193..256, 685 vs 685 at 257..320, 668 vs 683 at 321..384.  (The kernel it replaced
+// here, one workgroup per KV head with an online softmax per row, lost from 128 rows on: it was bound by vector issue, about
+// 16 vector instructions per row and head and merges full of exponentials, not by one CU's memory path as this comment said.)
+constexpr uint32_t kDirectAttnDefaultKv = 256;
 
 // One token through the context's kernels, launched eagerly, before any of them is first launched inside a stream
 // capture.  Measured on ROCm 7.0 / MI355X: a kernel whose FIRST launch in the process happens during a capture is not
@@ -40,10 +43,10 @@ constexpr uint32_t kDirectAttnDefaultKv = 64;
 static int warm_kernels(lgh_ctx* c) {
   if (c->d.flags & LGH_FLAG_NO_GRAPH) return LGH_OK;
   int rc = LGH_OK;
-  const bool keep_direct = c->attn_direct;
+  const AttnVariant keep_direct = c->attn_direct;
   for (int v = 0; v < 2 && !rc; v++) {
     if (v == 1 && c->direct_attn_max_kv == 0) continue;
-    c->attn_direct = v == 1;
+    c->attn_direct = v == 1 ? ATTN_VAR_HEAD : ATTN_VAR_SPLIT;
     HIP_TRY(c, LGH_OPERATION_FAILED, hipMemsetAsync(c->state, 0, ST_WORDS * 4, c->stream));
     for (int mode : {c->last ? MODE_GREEDY : MODE_PREFILL, MODE_PREFILL})   // the last stage: with and without the output head
       if (!rc) rc = enqueue_token(c, mode);
@@ -71,7 +74,7 @@ static int step(lgh_ctx* c, int mode) {
   if (c->pos >= c->d.max_seq_len)  // the reference has no such check: OOB write past the KV capacity
     return fail(c, LGH_INVALID_ARGUMENT, "position " + std::to_string(c->pos) + " >= max_seq_len " + std::to_string(c->d.max_seq_len));
   int rc;
-  c->attn_direct = c->pos + 1 <= c->direct_attn_max_kv;   // the token at position pos attends to pos + 1 rows
+  c->attn_direct = c->pos + 1 <= c->direct_attn_max_kv ? ATTN_VAR_HEAD : ATTN_VAR_SPLIT;   // the token at position pos attends to pos + 1 rows
   if (c->profiling || (c->d.flags & LGH_FLAG_NO_GRAPH)) {
     if ((rc = enqueue_token(c, mode))) return rc;
     if (c->profiling && (rc = drain_prof(c))) return rc;

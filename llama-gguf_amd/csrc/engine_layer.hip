@@ -201,7 +201,16 @@ int attention_forward(lgh_ctx* c, LayerW& Lw, uint32_t li, const AttnView& v, fl
     rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
       return attn_decode_any_launch(v.q, kv.k_f32(), kv.v_f32(), v.attn_out, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, c->stream);
     });
-  } else if (c->attn_direct) {    // short context: one launch
+  } else if (c->attn_direct == ATTN_VAR_HEAD) {   // contexts up to direct_attn_max_kv rows: one launch, a workgroup per query head
+    if (c->pos + 1 > c->direct_attn_max_kv)   // (the kernel's LDS arrays end there: it would attend to a truncated context)
+      return fail(c, LGH_INVALID_ARGUMENT, "single-launch attention at position " + std::to_string(c->pos) + " past its " +
+                                               std::to_string(c->direct_attn_max_kv) + " rows");
+    uint8_t* const img = image();
+    rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
+      return attn_head_launch(v.q, kv.k_f32(), kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, c->direct_attn_max_kv,
+                              v.attn_out, img, c->stream);
+    });
+  } else if (c->attn_direct == ATTN_VAR_DIRECT) {   // one launch, a workgroup per kv head
     uint8_t* const img = image();
     rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
       return attn_direct_launch(v.q, kv.k_f32(), kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, v.attn_out, img, c->stream);

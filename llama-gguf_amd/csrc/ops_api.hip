@@ -601,19 +601,22 @@ int lgh_op_attention_decode(int device, int path, const float* q, const float* k
   if (t.rc) return t.rc;
   if (!q || !k_cache || !v_cache || !out || n_kv == 0 || n_heads % n_kv || head_dim == 0 || pos >= max_seq || max_seq > 0x7FFFFFFFu)
     return LGH_INVALID_ARGUMENT;
-  if (path < 0 || path > 2 || (path == 2 && image_out)) return LGH_INVALID_ARGUMENT;   // (the any-shape kernel leaves no image)
+  if (path < 0 || path > 3 || (path == 2 && image_out)) return LGH_INVALID_ARGUMENT;   // (the any-shape kernel leaves no image)
   const size_t g = n_heads / n_kv;
   const bool fast = attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)g);
   if (path != 2 && !fast) return LGH_UNSUPPORTED;
   if (path == 0 && (n_splits < 1 || n_splits > 32)) return LGH_INVALID_ARGUMENT;
   if (path == 2 && max_seq * 4 > 150 * 1024) return LGH_UNSUPPORTED;   // the scores of a head live in LDS
+  if (path == 3 && max_seq > kAttnHeadMaxRows) return LGH_UNSUPPORTED;   // (here too)
   const AttnView v{nullptr, t.up(q, n_heads * head_dim), nullptr, t.up(nullptr, n_heads * head_dim)};   // (f32 cache: no staged rows)
   if (!v.q || !v.attn_out) return LGH_ALLOCATION_FAILED;
   int rc;
   if ((rc = attn_setup(t, LGH_KV_F32, n_heads, n_kv, head_dim, max_seq, path == 0 ? n_splits : 0)) || (rc = set_pos(t, pos))) return rc;
   // 0: split + merge (attn_launch picks 4 or 8 waves from max_seq); 1: one launch (engine: pos + 1 <= direct_attn_max_kv); 2: the
-  // kernel of the shapes the others do not cover (engine: every token of such a model), here on any head_dim / group size
-  t.c->attn_direct = path == 1;
+  // kernel of the shapes the others do not cover (engine: every token of such a model), here on any head_dim / group size; 3: one launch,
+  // a workgroup per query head (engine: pos + 1 <= direct_attn_max_kv)
+  t.c->attn_direct = path == 1 ? ATTN_VAR_DIRECT : path == 3 ? ATTN_VAR_HEAD : ATTN_VAR_SPLIT;
+  if (path == 3) t.c->direct_attn_max_kv = (uint32_t)max_seq;   // the launch sizes its LDS arrays by it: any pos < max_seq fits
   t.c->attn_generic = path == 2;
   const void* const caches[KV_KINDS] = {k_cache, v_cache};
   return attn_run(t, v, caches, nullptr, scale, out, image_out);

@@ -423,8 +423,8 @@ int tp_step(lgh_tp* t, int mode) {
   bool direct = false;
   for (lgh_ctx* c : t->rank) {   // (every rank has the same thresholds: one attention variant per token)
     c->pos = t->pos;
-    c->attn_direct = c->pos + 1 <= c->direct_attn_max_kv;
-    direct = c->attn_direct;
+    c->attn_direct = c->pos + 1 <= c->direct_attn_max_kv ? ATTN_VAR_HEAD : ATTN_VAR_SPLIT;
+    direct = c->attn_direct != ATTN_VAR_SPLIT;
   }
   int rc;
   TP_HIP(t, hipSetDevice(t->device[0]));
@@ -558,7 +558,7 @@ int lgh_tp_finalize(lgh_tp* t) {
       for (int mode : {MODE_GREEDY, MODE_PREFILL}) {
         for (lgh_ctx* c : t->rank) {
           c->pos = 0;
-          c->attn_direct = v == 1;
+          c->attn_direct = v == 1 ? ATTN_VAR_HEAD : ATTN_VAR_SPLIT;
           TP_HIP(t, hipMemsetAsync(c->state, 0, ST_WORDS * 4, c->stream));
         }
         if ((rc = tp_enqueue(t, mode))) return rc;

@@ -853,7 +853,7 @@ def op_attention_cached(q, k_cache, v_cache, scale: float, kv_len: int, n_splits
     return out
 
 
-ATTN_SPLIT, ATTN_DIRECT, ATTN_ANY = 0, 1, 2   # lgh_op_attention_decode paths
+ATTN_SPLIT, ATTN_DIRECT, ATTN_ANY, ATTN_HEAD = 0, 1, 2, 3   # lgh_op_attention_decode paths
 
 
 def _attn_image(q, n_images: int = 1):
@@ -864,7 +864,9 @@ def _attn_image(q, n_images: int = 1):
 
 def op_attention_decode(path: int, q, k_cache, v_cache, scale: float, pos: int, n_splits: int = 8, device: int = 0, *, image: bool = False):
     """One decode step's attention over the f32 cache (rows 0..pos stored) on the engine path `path`: ATTN_SPLIT (split + merge),
-    ATTN_DIRECT (one launch) or ATTN_ANY (any head_dim / group size).  q [nh, d]; caches [nkv, max_seq, d]; pos via the device word.
+    ATTN_DIRECT (one launch, a workgroup per kv head), ATTN_HEAD (one launch, a workgroup per query head: the engine's single launch;
+    max_seq <= 16384, its scores live in LDS) or ATTN_ANY (any head_dim / group size).  q [nh, d]; caches [nkv, max_seq, d]; pos via the
+    device word.
     image: -> (out, wo's input as the launch leaves it: the XQ image of out, uint8 [bytes]); ATTN_ANY writes none (InvalidArgument)."""
     q, kc, vc = _f32(q), _f32(k_cache), _f32(v_cache)
     out = np.empty_like(q)
