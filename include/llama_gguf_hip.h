@@ -465,8 +465,8 @@ const char* lgh_pipeline_last_error(const lgh_pipeline* p);
  * MoE models, a kv_cache_type other than f32, and widths (num_heads / N) * head_dim, intermediate_size / N or hidden_size that
  * are not multiples of 256 (the k-shards are whole 256-element blocks).  lgh_tp_upload_tensor answers Unsupported for a 2-D
  * weight outside the matrix-core tile layouts (Q4_K, Q5_K, Q6_K, Q8_0, Q4_0 with k % 256 == 0).  Why a create failed:
- * lgh_tp_last_error(NULL), per thread.  Quantized caches, MoE, the batched prompt pass, sampling and multi-sequence slots over
- * tensor parallelism are not built. ---- */
+ * lgh_tp_last_error(NULL), per thread.  Quantized caches, MoE, sampling and multi-sequence slots over tensor parallelism are not
+ * built. ---- */
 typedef struct lgh_tp lgh_tp;
 int lgh_tp_create(const lgh_model_desc* desc, const int* device_ids, int n_ranks, lgh_tp** out);   /* TPConfig + ShardingPlan::from_config */
 /* the WHOLE tensor, as lgh_pipeline_upload_tensor takes it; every rank gets its part through lgh_tp_shard (in place of
@@ -476,6 +476,20 @@ int lgh_tp_finalize(lgh_tp* tp);
 void lgh_tp_destroy(lgh_tp* tp);
 int lgh_tp_forward(lgh_tp* tp, uint32_t token_id, float* logits_out);          /* GpuInference::forward */
 int lgh_tp_prefill_token(lgh_tp* tp, uint32_t token_id);                       /* GpuInference::prefill_token */
+/* GpuOnlyInference::forward_batch minus the last token (gpu_only.rs:776-790) over the ranks.  When every rank context has the
+ * single context's batched path — head_dim 64 or 128, 1 / 2 / 4 / 8 query heads per kv head, LGH_FLAG_EXACT_PREFILL off;
+ * lgh_tp_create's width rules give the 256-multiples — the prompt runs in blocks of up to 128 tokens: every rank runs
+ * lgh_prefill_batch's GEMMs, QKV epilogue, block attention and SwiGLU over its own heads and FFN columns, and at the two
+ * synchronisation points of a layer each rank collapses its split-K partial sums into one [128][hidden] f32 block and every rank
+ * adds the ranks' blocks to its residual rows in rank order (all ranks hold the same bits).  One rank gives lgh_prefill_batch's
+ * bits.  The tolerance contract is lgh_prefill_batch's (the KV cache equals the token-by-token one within 1e-2 relative), because
+ * tensor parallelism only regroups the f32 sums of wo and down.  The pass runs eagerly, never inside a graph capture.  On distinct
+ * devices it uses decode's events and peer-mapped blocks (NOT executed so far, as above).  Any other handle runs n exact
+ * lgh_tp_prefill_tokens.  InvalidArgument, with the position unchanged and nothing enqueued: a token id >= vocab_size, position + n
+ * > max_seq_len, a handle that is not finalized. */
+int lgh_tp_prefill_batch(lgh_tp* tp, const uint32_t* tokens, size_t n);
+/* 1 when lgh_tp_prefill_batch will take the batched path for this (finalized) handle, else 0 (gpu_only.rs:776-790) */
+int lgh_tp_prefill_is_batched(lgh_tp* tp);
 int lgh_tp_decode_greedy(lgh_tp* tp, uint32_t first_token, size_t n_steps, uint32_t* tokens_out);   /* lgh_decode_greedy over the ranks */
 void lgh_tp_reset(lgh_tp* tp);                                                 /* GpuInference::reset */
 size_t lgh_tp_position(const lgh_tp* tp);                                      /* GpuInference::position */
@@ -483,6 +497,7 @@ int lgh_tp_kv_truncate(lgh_tp* tp, size_t new_len);                            /
 int lgh_tp_ranks(const lgh_tp* tp);                                            /* TensorParallel::world_size */
 uint64_t lgh_tp_graph_nodes(const lgh_tp* tp);   /* nodes of the captured token graph (0 before the first replay, and on distinct devices) */
 const char* lgh_tp_last_error(const lgh_tp* tp);
+int lgh_tp_get_stats(lgh_tp* tp, int rank, lgh_stats* out);   /* lgh_get_stats of one rank's context (its weights, KV rows and scratch) */
 /* Host only, no device needed: rank `rank`'s shard of a [ne1 rows][ne0 elements] tensor in GGUF order (shard_weight's job, for
  * quantized payloads too).  axis 0 = rows (out features): a contiguous row range — ne1 / n_ranks rows where n_ranks divides ne1
  * (whole heads, FFN columns), otherwise the same number of whole 16-row tiles for every rank and the remainder to the last one
@@ -497,6 +512,18 @@ int lgh_tp_shard(uint32_t ggml_type, const uint64_t ne[4], int axis, int rank, i
  * of out^2.  H % 16 == 0.  out, xq_image and ssq_parts are in / out: bytes the kernel does not write keep the caller's. */
 int lgh_op_tp_reduce(int device, const float* partials, uint32_t n, const float* resid, const float* norm_w, size_t H, float* out,
                      uint8_t* xq_image, float* ssq_parts);
+/* The two row-wise launches of a tensor-parallel prompt block on their own (host tensors in and out).  partials: n ranks' split-K
+ * partial sums [n][S][128][ncols], the block's columns at col0 .. col0 + H - 1; bias [H] or NULL (rank 0's); resid [m][H]; norm_w
+ * [H] or NULL.  path 0: every rank's partials collapsed into its compact block
+ *   a_r[t][i] = ((0 + part[0][t][col0 + i]) + part[1][t][col0 + i]) + ... (+ bias[i], rank 0),
+ * then hidden[t][i] = resid[t][i] + (((a_0 + a_1) + a_2) ...) in rank order, the XH image of f16(f32(hidden * norm_w)) (none without
+ * norm_w) and the per-2048-column sums of hidden^2.  path 1 (n == 1 only): lgh_prefill_batch's own row epilogue on rank 0's
+ * partials — what path 0 has to equal bit for bit.  hidden_io [128][H], xh_image (ceil(H / 256) * 65536 bytes) and ssq_io [128][8]
+ * are in / out: rows t >= m and bytes the kernels do not own keep the caller's.  InvalidArgument: n outside 1..8, m outside 1..128,
+ * H % 8, ncols % 4, col0 % 4, col0 + H > ncols, path 1 with n != 1. */
+int lgh_op_tp_pf_reduce(int device, int path, const float* partials, uint32_t n, uint32_t n_splits, size_t ncols, size_t col0,
+                        const float* bias, const float* resid, const float* norm_w, size_t H, size_t m, float* hidden_io,
+                        uint8_t* xh_image, float* ssq_io);
 
 /* ---- per-op surface: the `Backend` trait ops on the path (src/backend/mod.rs:29-265), host tensors
  * in / host tensors out, for parity tests of each kernel against the CPU backend. ---- */

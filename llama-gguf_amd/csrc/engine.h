@@ -263,6 +263,7 @@ int pf_ensure(lgh_ctx* c);
 int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_t m);
 // prefill_block's steps over the m tokens in the context's scratch (c->pf, after pf_ensure); next_nw: the norm weight of the step's
 // consumer, nullptr = leave no XH
+int pf_embed_tokens(lgh_ctx* c, uint32_t pos0, const uint32_t* tokens, uint32_t m);   // ids through the pinned ring, embedding rows into pf.hidden
 int pf_block_input(lgh_ctx* c, const float* nw, uint32_t m);
 int pf_qkv_step(lgh_ctx* c, lgh::LayerW& L, float* kcache, float* vcache, uint32_t pos0, uint32_t m);
 int pf_wo_step(lgh_ctx* c, lgh::LayerW& L, uint32_t m);

@@ -186,6 +186,31 @@ int pf_moe_step(lgh_ctx* c, LayerW& L, const float* next_nw, uint32_t m) {
   return pf_k(c, pf_moe_combine_launch(P.part, S, P.moe_tokmap, P.moe_w, topk, P.hidden, H, next_nw, next_xh, P.ssq, m, st), "MoE combine");
 }
 
+// the m token ids of a block at positions pos0 .. pos0+m-1 onto the device and their embedding rows into pf.hidden (after pf_ensure)
+int pf_embed_tokens(lgh_ctx* c, uint32_t pos0, const uint32_t* tokens, uint32_t m) {
+  PfScratch& P = c->pf;
+  const lgh_model_desc& d = c->d;
+  hipStream_t st = c->stream;
+  // The caller's `tokens` may be freed as soon as this returns (lgh_stage_prefill_batch does not synchronise), so the ids
+  // go through a context-owned PINNED buffer, one slot per position; a slot is only rewritten after the copy that last
+  // read it has completed (reset + a second prompt before the first one has run).
+  if (!P.tok_pinned) {
+    HIP_TRY(c, LGH_ALLOCATION_FAILED, hipHostMalloc((void**)&P.tok_pinned, (size_t)d.max_seq_len * 4, hipHostMallocDefault));
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipEventCreateWithFlags(&P.tok_copied, hipEventDisableTiming));
+  } else if (pos0 < P.tok_hi && pos0 + m > P.tok_lo) {
+    // only when a slot about to be rewritten may still be read: a reset / shift / truncate followed by a new prompt.  The blocks
+    // of ONE prompt use ascending slots and never wait here (lgh_stage_prefill_batch stays asynchronous).
+    HIP_TRY(c, LGH_OPERATION_FAILED, hipEventSynchronize(P.tok_copied));
+    P.tok_lo = P.tok_hi = 0;
+  }
+  if (P.tok_hi == P.tok_lo) { P.tok_lo = pos0; P.tok_hi = pos0 + m; }
+  else { P.tok_lo = std::min(P.tok_lo, pos0); P.tok_hi = std::max(P.tok_hi, pos0 + m); }
+  std::memcpy(P.tok_pinned + pos0, tokens, (size_t)m * 4);
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(P.tokens, P.tok_pinned + pos0, (size_t)m * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipEventRecord(P.tok_copied, st));
+  return pf_k(c, embed_batch_launch(c->embd_type, c->embd_raw, P.tokens, P.hidden, d.hidden_size, m, st), "embedding");
+}
+
 // m <= 128 prompt tokens at positions t.pos0 .. t.pos0+m-1 of the target sequence: fills every owned layer's K/V rows of that
 // sequence; the caller moves the sequence's position.  The first stage starts from the tokens' embedding rows, any other stage
 // from the block of hidden vectors its predecessor left in pf.hidden; a stage that is not the last leaves its output block there
@@ -195,29 +220,9 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
   if (rc) return rc;
   PfScratch& P = c->pf;
   const lgh_model_desc& d = c->d;
-  const uint32_t H = d.hidden_size;
   const uint32_t pos0 = (uint32_t)t.pos0;
   hipStream_t st = c->stream;
-  if (c->first) {
-    // The caller's `tokens` may be freed as soon as this returns (lgh_stage_prefill_batch does not synchronise), so the ids
-    // go through a context-owned PINNED buffer, one slot per position; a slot is only rewritten after the copy that last
-    // read it has completed (reset + a second prompt before the first one has run).
-    if (!P.tok_pinned) {
-      HIP_TRY(c, LGH_ALLOCATION_FAILED, hipHostMalloc((void**)&P.tok_pinned, (size_t)d.max_seq_len * 4, hipHostMallocDefault));
-      HIP_TRY(c, LGH_OPERATION_FAILED, hipEventCreateWithFlags(&P.tok_copied, hipEventDisableTiming));
-    } else if (pos0 < P.tok_hi && pos0 + m > P.tok_lo) {
-      // only when a slot about to be rewritten may still be read: a reset / shift / truncate followed by a new prompt.  The blocks
-      // of ONE prompt use ascending slots and never wait here (lgh_stage_prefill_batch stays asynchronous).
-      HIP_TRY(c, LGH_OPERATION_FAILED, hipEventSynchronize(P.tok_copied));
-      P.tok_lo = P.tok_hi = 0;
-    }
-    if (P.tok_hi == P.tok_lo) { P.tok_lo = pos0; P.tok_hi = pos0 + m; }
-    else { P.tok_lo = std::min(P.tok_lo, pos0); P.tok_hi = std::max(P.tok_hi, pos0 + m); }
-    std::memcpy(P.tok_pinned + pos0, tokens, (size_t)m * 4);
-    HIP_TRY(c, LGH_OPERATION_FAILED, hipMemcpyAsync(P.tokens, P.tok_pinned + pos0, (size_t)m * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, LGH_OPERATION_FAILED, hipEventRecord(P.tok_copied, st));
-    if ((rc = pf_k(c, embed_batch_launch(c->embd_type, c->embd_raw, P.tokens, P.hidden, H, m, st), "embedding"))) return rc;
-  }
+  if (c->first && (rc = pf_embed_tokens(c, pos0, tokens, m))) return rc;
   if ((rc = pf_block_input(c, c->layers[c->l0].attn_norm, m))) return rc;
   const float scale = 1.0f / std::sqrt((float)d.head_dim);  // layers.rs:374
   const bool tq = c->kvl.tq();

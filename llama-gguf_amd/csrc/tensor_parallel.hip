@@ -14,11 +14,15 @@
 // the per-chunk sums of h^2, exactly what the mat-vec epilogues leave for a matrix-core consumer.  The sum runs in rank order on
 // every rank, so all ranks hold the same bits.
 //
+// A prompt goes through lgh_tp_prefill_batch in blocks of up to 128 tokens (tp_prefill_block below): the single context's GEMMs, QKV
+// epilogue, block attention and SwiGLU on every rank, and at the two meeting places tp_prefill.hip's block forms of the reduce.
+//
 // Ranks that share a device share ONE stream and the whole token is ONE linear captured graph (no parallel branches, no event
 // nodes), like the same-device stages of pipeline.hip.  Ranks on distinct devices run the same launch order eagerly on their own
 // streams, with one event per synchronisation point and rank, waited for by the peers, and read the peers' partial vectors
 // through peer-mapped pointers.
 #include "engine.h"
+#include "tp_prefill.h"
 #include "xq.h"
 
 #include <algorithm>
@@ -97,6 +101,8 @@ struct lgh_tp {
   bool one_stream = true;                    // all ranks on one device: one stream, one graph per token
   bool finalized = false;
   std::vector<float*> part[2];               // [synchronisation point of a layer: 0 after wo, 1 after down][rank] f32[hidden]
+  std::vector<float*> pf_part[2];            // the batched prompt pass: the same two points, [rank] f32[128][hidden] (first lgh_tp_prefill_batch)
+  bool pf_ready = false;
   std::vector<hipEvent_t> ev[3];             // distinct devices: [synchronisation point; 2 = the logits slices][rank]
   hipEvent_t token_back = nullptr;           // ... and rank 0's arg-max has been copied into every rank's token word
   std::vector<uint32_t> out_row0, out_rows;  // rank r's rows of the output projection
@@ -470,6 +476,128 @@ int tp_ready(lgh_tp* t) {
   return LGH_OK;
 }
 
+// ---- the batched prompt pass (tp_prefill.hip; the single context's is engine_prefill.hip's prefill_block) ----
+bool tp_pf_eligible(const lgh_tp* t) {
+  for (const lgh_ctx* c : t->rank)
+    if (!pf_eligible(c, false)) return false;
+  return true;
+}
+
+// every rank's prompt scratch and its two compact partial blocks, peer-readable as part[] is (peer access was enabled at finalize)
+int tp_pf_ensure(lgh_tp* t) {
+  if (t->pf_ready) return LGH_OK;
+  const size_t n = t->rank.size();
+  int rc;
+  for (int w = 0; w < 2; w++) t->pf_part[w].assign(n, nullptr);
+  for (size_t r = 0; r < n; r++) {
+    lgh_ctx* c = t->rank[r];
+    TP_HIP(t, hipSetDevice(t->device[r]));
+    if ((rc = pf_ensure(c))) return rank_fail(t, r, rc);
+    const size_t bytes = (size_t)kPfTokens * t->d.hidden_size * 4;
+    const AllocSpec bufs[] = {{(void**)&t->pf_part[0][r], bytes}, {(void**)&t->pf_part[1][r], bytes}};
+    if ((rc = alloc_zeroed(c, bufs, 2, c->stats.scratch_bytes))) return rank_fail(t, r, rc);
+    TP_HIP(t, hipStreamSynchronize(c->stream));   // the zero-fills are done before a peer touches the blocks
+  }
+  t->pf_ready = true;
+  return LGH_OK;
+}
+
+int tp_pf_k(lgh_tp* t, size_t r, hipError_t e, const char* what) {
+  if (e == hipSuccess) return LGH_OK;
+  return tfail(t, LGH_OPERATION_FAILED, "rank " + std::to_string(r) + ": batched prefill, " + what + ": " + hipGetErrorString(e));
+}
+
+// the rank's split-K partial sums of a wo / down GEMM -> its compact block of synchronisation point `which`
+int tp_pf_partial_step(lgh_tp* t, size_t r, int which, uint32_t S, uint32_t ncols, const float* bias, uint32_t m) {
+  lgh_ctx* c = t->rank[r];
+  return tp_pf_k(t, r, tp_pf_partial_launch(c->pf.part, S, ncols, 0, bias, t->pf_part[which][r], c->d.hidden_size, m, c->stream), "partial block");
+}
+
+// the rank's block of residual rows after a synchronisation point, the XH of hidden * nw for the next GEMM (nw nullptr: none)
+int tp_pf_reduce_step(lgh_tp* t, size_t r, int which, const float* nw, uint32_t m) {
+  lgh_ctx* c = t->rank[r];
+  PfScratch& P = c->pf;
+  return tp_pf_k(t, r, tp_pf_reduce_launch(t->pf_part[which].data(), (uint32_t)t->rank.size(), P.hidden, c->d.hidden_size, nw, nw ? P.xh_h : nullptr, P.ssq, m,
+                                           c->stream),
+                 "reduce");
+}
+
+// One block of m <= 128 prompt tokens at positions t->pos .. t->pos + m - 1 on every rank, eagerly (never captured), in tp_enqueue's
+// pattern: a loop over the ranks per stretch between two synchronisation points.  The distinct-device branch (sync_point's events,
+// peer-mapped blocks) is the decode driver's and has NOT been executed: the development box has one GPU.
+int tp_prefill_block(lgh_tp* t, const uint32_t* tokens, uint32_t m) {
+  const size_t n = t->rank.size();
+  const lgh_model_desc& d = t->d;
+  const uint32_t pos0 = (uint32_t)t->pos;
+  int rc;
+  TP_HIP(t, hipSetDevice(t->device[0]));
+#define RANK_TRY(r, expr)                           \
+  do {                                              \
+    if ((rc = bind_rank(t, (r)))) return rc;        \
+    if ((rc = (expr))) return rank_fail(t, (r), rc); \
+  } while (0)
+  for (size_t r = 0; r < n; r++) {   // every rank dequantizes the block's rows itself: identical bits, nothing to broadcast
+    lgh_ctx* c = t->rank[r];
+    RANK_TRY(r, pf_embed_tokens(c, pos0, tokens, m));
+    RANK_TRY(r, pf_block_input(c, c->layers[0].attn_norm, m));
+  }
+  const float scale = 1.0f / std::sqrt((float)d.head_dim);   // layers.rs:374
+  for (uint32_t li = 0; li < d.num_layers; li++) {
+    const bool attend = li + 1 < d.num_layers;   // the model's last layer: its K / V rows are written, its output would be discarded
+    for (size_t r = 0; r < n; r++) {   // own heads into own cache rows, block attention over them, wo over the k-shard
+      lgh_ctx* c = t->rank[r];
+      LayerW& L = c->layers[li];
+      PfScratch& P = c->pf;
+      const lgh_model_desc& rd = c->d;
+      RANK_TRY(r, pf_qkv_step(c, L, L.kv.k_f32(), L.kv.v_f32(), pos0, m));
+      if (!attend) continue;
+      if ((rc = tp_pf_k(t, r, attn_prefill_launch(P.q, L.kv.k_f32(), L.kv.v_f32(), rd.num_heads, rd.num_kv_heads, rd.head_dim, rd.max_seq_len, scale, pos0, m,
+                                                  P.xh_attn, c->stream),
+                        "attention")))
+        return rc;
+      uint32_t S = 0, nc = 0;
+      const DevWeight* wo[1] = {&L.wo};
+      if ((rc = tp_pf_k(t, r, pf_gemm_launch(wo, 1, P.xh_attn, P.part, P.part_bytes, m, &S, &nc, c->stream), "wo GEMM"))) return rc;
+      if ((rc = tp_pf_partial_step(t, r, 0, S, nc, L.bo, m))) return rc;
+    }
+    if (!attend) break;
+    if ((rc = sync_point(t, 0))) return rc;
+    for (size_t r = 0; r < n; r++) {
+      if ((rc = bind_rank(t, r))) return rc;
+      if ((rc = tp_pf_reduce_step(t, r, 0, t->rank[r]->layers[li].ffn_norm, m))) return rc;
+    }
+    for (size_t r = 0; r < n; r++) {   // own columns of gate | up, SwiGLU, down over the k-shard
+      lgh_ctx* c = t->rank[r];
+      LayerW& L = c->layers[li];
+      PfScratch& P = c->pf;
+      const lgh_model_desc& rd = c->d;
+      if ((rc = bind_rank(t, r))) return rc;
+      uint32_t S = 0, nc = 0;
+      const DevWeight* gu[2] = {&L.gate, &L.up};
+      if ((rc = tp_pf_k(t, r, pf_gemm_launch(gu, 2, P.xh_h, P.part, P.part_bytes, m, &S, &nc, c->stream), "gate/up GEMM"))) return rc;
+      if ((rc = tp_pf_k(t, r, pf_swiglu_launch(P.part, S, rd.intermediate_size, P.xh_act, P.ssq, rd.hidden_size, rd.norm_eps, m, c->stream), "SwiGLU"))) return rc;
+      const DevWeight* dn[1] = {&L.down};
+      if ((rc = tp_pf_k(t, r, pf_gemm_launch(dn, 1, P.xh_act, P.part, P.part_bytes, m, &S, &nc, c->stream), "down GEMM"))) return rc;
+      if ((rc = tp_pf_partial_step(t, r, 1, S, nc, nullptr, m))) return rc;
+    }
+    if ((rc = sync_point(t, 1))) return rc;
+    for (size_t r = 0; r < n; r++) {   // (li + 1 exists: the last layer left above)
+      if ((rc = bind_rank(t, r))) return rc;
+      if ((rc = tp_pf_reduce_step(t, r, 1, t->rank[r]->layers[li + 1].attn_norm, m))) return rc;
+    }
+  }
+#undef RANK_TRY
+  t->pos += m;
+  for (size_t r = 0; r < n; r++) {
+    lgh_ctx* c = t->rank[r];
+    if ((rc = bind_rank(t, r))) return rc;
+    c->pos = t->pos;
+    c->stats.tokens_processed += m;
+    TP_HIP(t, hipMemsetD32Async((hipDeviceptr_t)(c->state + ST_NEXT), (int)c->pos, 1, c->stream));
+  }
+  return LGH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -607,6 +735,34 @@ int lgh_tp_prefill_token(lgh_tp* t, uint32_t token) {
     return tfail(t, LGH_INVALID_ARGUMENT, "position " + std::to_string(t->pos) + " >= max_seq_len " + std::to_string(t->d.max_seq_len));
   if ((rc = tp_set_token(t, token))) return rc;
   return tp_step(t, MODE_PREFILL);
+}
+
+int lgh_tp_prefill_is_batched(lgh_tp* t) { return t && t->finalized && tp_pf_eligible(t) ? 1 : 0; }
+
+// GpuOnlyInference::forward_batch minus the last token (gpu_only.rs:776-790) over the ranks: blocks of up to 128 tokens on the batched
+// path, or n exact lgh_tp_prefill_tokens.  Everything is checked before anything moves.
+int lgh_tp_prefill_batch(lgh_tp* t, const uint32_t* tokens, size_t n) {
+  int rc = tp_ready(t);
+  if (rc) return rc;
+  if (n && !tokens) return tfail(t, LGH_INVALID_ARGUMENT, "tokens is NULL");
+  if (t->pos + n > t->d.max_seq_len)
+    return tfail(t, LGH_INVALID_ARGUMENT, "prompt of " + std::to_string(n) + " tokens at position " + std::to_string(t->pos) + " exceeds max_seq_len");
+  for (size_t i = 0; i < n; i++)
+    if (tokens[i] >= t->d.vocab_size) return tfail(t, LGH_INVALID_ARGUMENT, "token id exceeds vocab size");
+  if (n >= 2 && tp_pf_eligible(t)) {
+    if ((rc = tp_pf_ensure(t))) return rc;
+    for (size_t i = 0; i < n; i += kPfTokens)
+      if ((rc = tp_prefill_block(t, tokens + i, (uint32_t)std::min<size_t>(kPfTokens, n - i)))) return rc;
+  } else {
+    for (size_t i = 0; i < n; i++)
+      if ((rc = lgh_tp_prefill_token(t, tokens[i]))) return rc;
+  }
+  return tp_sync_all(t);
+}
+
+int lgh_tp_get_stats(lgh_tp* t, int rank, lgh_stats* out) {
+  if (!t || !out || rank < 0 || (size_t)rank >= t->rank.size()) return LGH_INVALID_ARGUMENT;
+  return lgh_get_stats(t->rank[(size_t)rank], out);
 }
 
 int lgh_tp_decode_greedy(lgh_tp* t, uint32_t first_token, size_t n_steps, uint32_t* tokens_out) {

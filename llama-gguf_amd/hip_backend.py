@@ -37,6 +37,7 @@ ABI_SYMBOLS = (
     "lgh_pipeline_last_error",
     "lgh_tp_create", "lgh_tp_upload_tensor", "lgh_tp_finalize", "lgh_tp_destroy", "lgh_tp_forward", "lgh_tp_prefill_token", "lgh_tp_decode_greedy",
     "lgh_tp_reset", "lgh_tp_position", "lgh_tp_kv_truncate", "lgh_tp_ranks", "lgh_tp_graph_nodes", "lgh_tp_last_error", "lgh_tp_shard", "lgh_op_tp_reduce",
+    "lgh_tp_prefill_batch", "lgh_tp_prefill_is_batched", "lgh_tp_get_stats", "lgh_op_tp_pf_reduce",
     "lgh_set_kv_rotation_signs", "lgh_op_tq_compress", "lgh_set_kv_qjl_matrices", "lgh_op_tq_compress_qjl",
     "lgh_batch_create", "lgh_batch_reset", "lgh_batch_position", "lgh_batch_prefill", "lgh_forward_multi", "lgh_decode_greedy_multi",
     "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
@@ -232,6 +233,9 @@ def load_library() -> C.CDLL:
         "lgh_tp_graph_nodes": (C.c_uint64, [vp]), "lgh_tp_last_error": (C.c_char_p, [vp]),
         "lgh_tp_shard": (C.c_int, [u32, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, vp, sz, vp, sz, C.POINTER(sz)]),
         "lgh_op_tp_reduce": (C.c_int, [C.c_int, vp, u32, vp, vp, sz, vp, vp, vp]),
+        "lgh_tp_prefill_batch": (C.c_int, [vp, vp, sz]), "lgh_tp_prefill_is_batched": (C.c_int, [vp]),
+        "lgh_tp_get_stats": (C.c_int, [vp, C.c_int, C.POINTER(Stats)]),
+        "lgh_op_tp_pf_reduce": (C.c_int, [C.c_int, C.c_int, vp, u32, u32, sz, sz, vp, vp, vp, sz, sz, vp, vp, vp]),
         "lgh_set_kv_rotation_signs": (C.c_int, [vp, vp, sz]), "lgh_op_tq_compress": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp]),
         "lgh_set_kv_qjl_matrices": (C.c_int, [vp, vp, sz]), "lgh_op_tq_compress_qjl": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, vp]),
         "lgh_batch_create": (C.c_int, [vp, u32]), "lgh_batch_reset": (C.c_int, [vp, u32]), "lgh_batch_position": (sz, [vp, u32]),
@@ -723,6 +727,19 @@ class HipTensorParallel:
     def prefill_token(self, token_id: int) -> None:
         self._call(load_library().lgh_tp_prefill_token(self._h, token_id))
 
+    def forward_batch(self, tokens: Sequence[int]) -> None:  # gpu_only.rs:776-790 minus the final forward, over the ranks
+        toks = np.ascontiguousarray(tokens, dtype=np.uint32)
+        self._call(load_library().lgh_tp_prefill_batch(self._h, toks.ctypes.data, toks.size))
+
+    def prefill_is_batched(self) -> bool:
+        return bool(load_library().lgh_tp_prefill_is_batched(self._h))
+
+    def stats(self, rank: int = 0) -> dict:
+        """weight / KV / scratch bytes and tokens processed of one rank's context"""
+        s = Stats()
+        self._call(load_library().lgh_tp_get_stats(self._h, int(rank), C.byref(s)))
+        return {k: getattr(s, k) for k in ("weight_bytes", "kv_bytes", "scratch_bytes", "tokens_processed")}
+
     def decode_greedy(self, first_token: int, n_steps: int) -> np.ndarray:
         out = np.zeros(n_steps, dtype=np.uint32)
         self._call(load_library().lgh_tp_decode_greedy(self._h, first_token, n_steps, out.ctypes.data))
@@ -1029,6 +1046,25 @@ def op_tp_reduce(partials, resid=None, norm_w=None, *, image: bool = False, ssq:
     sq = np.full(max(H // 16, 1) * 4, fill, np.uint8).view(np.float32) if ssq else None
     _chk(load_library().lgh_op_tp_reduce(device, p.ctypes.data, n, _ptr(rs), _ptr(nw), H, out.ctypes.data, _ptr(img), _ptr(sq)), "tp_reduce")
     return {"out": out, "image": img, "ssq": sq}
+
+
+def op_tp_pf_reduce(partials, resid, *, col0: int = 0, bias=None, norm_w=None, path: int = 0, fill: int = 0, device: int = 0):
+    """The two row-wise launches of a tensor-parallel prompt block (path 0), or the single context's row epilogue on rank 0's partials
+    (path 1, one rank only).  partials [n, S, 128, ncols], resid [m, H].  -> dict(hidden [128, H], xh (uint8 image), ssq [128, 8]);
+    every output buffer starts filled with the byte `fill`, rows 0 .. m - 1 of hidden with resid."""
+    p, rs = _f32(partials), _f32(resid)
+    n, S, rows, ncols = p.shape
+    if rows != 128:
+        raise ValueError("partials are [n, S, 128, ncols]")
+    m, H = rs.shape
+    b, nw = (None if v is None else _f32(v) for v in (bias, norm_w))
+    hid = np.full((128, H), 0, np.float32)
+    hid.view(np.uint8)[...] = fill
+    xh = np.full((H + 255) // 256 * 65536, fill, np.uint8)
+    sq = np.full(128 * PF_SSQ_CHUNKS * 4, fill, np.uint8).view(np.float32).reshape(128, PF_SSQ_CHUNKS)
+    _chk(load_library().lgh_op_tp_pf_reduce(device, path, p.ctypes.data, n, S, ncols, col0, _ptr(b), rs.ctypes.data, _ptr(nw), H, m,
+                                            hid.ctypes.data, xh.ctypes.data, sq.ctypes.data), "tp_pf_reduce")
+    return {"hidden": hid, "xh": xh, "ssq": sq}
 
 
 def op_set_flags(flags: int) -> int:
