@@ -378,6 +378,51 @@ int lgh_batch_set_sampler_ex(lgh_ctx* ctx, uint32_t slot, const lgh_sampler_conf
  * far (synchronises).  10.0 when Mirostat is off, as Sampler::new leaves it (mod.rs:161). */
 int lgh_get_sampler_mu(lgh_ctx* ctx, int slot, float* mu);
 
+/* ---- device prompt cache: the KV rows of a prompt kept on the device, restored and shared by copying.  The device side of
+ * PromptCache / PrefixSharing (src/model/cache.rs:67-345, re-exported at src/lib.rs:75), whose CachedPrefix (cache.rs:28-65) clones
+ * every layer's K / V tensors on the host; the LRU table, the longest-match lookup and the reference counts stay with the host
+ * (llama-gguf_amd/hip_backend.py restates them).  A prefix holds rows [0, n_rows) of every cache tensor of every
+ * layer the context owns, packed [layer][K, V, K scales, V scales, K QJL words: those the format has][kv head][n_rows][bytes per
+ * position] (lgh_kv_cache_layout), in ONE device allocation of
+ *     layers * num_kv_heads * n_rows * (2 * (row_bytes + scale_bytes) + qjl_bytes)  bytes.
+ * slot: -1 = the context's own sequence, else a slot of lgh_batch_create.  A save or a restore is one kernel launch, enqueued on
+ * the context's stream: a decode call issued after a restore is ordered behind it.  A stage context of the layer pipeline saves
+ * and restores its own layers; the lgh_tp_* and lgh_pipeline_* handles have no prefix entry points (their rank / stage contexts
+ * are not reachable through this ABI).  lgh_stats is not changed by any of these calls: lgh_prefix_total_bytes reports the prefixes.
+ * TurboQuant rows mean something only under the rotation signs and QJL matrices they were written with (lgh_set_kv_rotation_signs,
+ * lgh_set_kv_qjl_matrices): a host that imports a prefix into another context must give that context the same ones; the library
+ * does not try to detect a change.
+ * InvalidArgument, with nothing changed: a NULL pointer; a slot >= max_batch, or any slot before lgh_batch_create; n_rows beyond
+ * the source's position (save) or the prefix's rows (restore); nothing to save (position 0); a handle that is not one of this
+ * context's live prefixes (freed, or made by another context: handles are looked up, never dereferenced first); an import whose
+ * header or size does not match the context.  AllocationFailed, with nothing changed, when the device allocation fails. ---- */
+typedef struct lgh_prefix lgh_prefix;   /* owned by the context that made it; lgh_destroy frees the live ones */
+typedef struct lgh_prefix_info {
+  uint32_t struct_size;              /* sizeof(lgh_prefix_info) */
+  uint32_t kv_cache_type;            /* LGH_KV_* */
+  uint32_t n_rows;                   /* CachedPrefix::seq_len (cache.rs:38) */
+  uint32_t layer_begin, layer_end;   /* the layers it holds: the context's */
+  uint64_t bytes;                    /* device bytes = CachedPrefix::memory_size (cache.rs:60-64) without the tokens */
+} lgh_prefix_info;
+/* PrefixSharing::save_prefix (cache.rs:313-326): rows [0, n_rows) of the sequence (n_rows 0: up to its position) into a new prefix.
+ * The source is not changed. */
+int lgh_prefix_save(lgh_ctx* ctx, int slot, size_t n_rows, lgh_prefix** out);
+/* PrefixSharing::try_restore's copy (cache.rs:287-306): the target reset, then a prompt of n_rows tokens, done by copying (n_rows 0:
+ * all of the prefix; fewer is valid, KV is causal).  Writes rows [0, n_rows) and sets the position as the prompt path does (the own
+ * sequence's position and its device word, or the slot's position); the sampler state stays as it is. */
+int lgh_prefix_restore(lgh_ctx* ctx, const lgh_prefix* prefix, int slot, size_t n_rows);
+/* PromptCache::remove_prefix (cache.rs:191-195): frees the device memory.  Synchronises the stream first. */
+int lgh_prefix_free(lgh_ctx* ctx, lgh_prefix* prefix);
+int lgh_prefix_get_info(lgh_ctx* ctx, const lgh_prefix* prefix, lgh_prefix_info* info);
+/* PromptCacheStats::memory_used (cache.rs:203-210) without the tokens: device bytes of the context's live prefixes */
+uint64_t lgh_prefix_total_bytes(lgh_ctx* ctx);
+/* A prefix as host bytes (a session file; CachedPrefix is Clone, cache.rs:29): a fixed header — magic, version, kv_cache_type,
+ * num_kv_heads, head_dim, layer_begin, layer_end, n_rows (uint32 each), payload bytes (uint64) — then the packed rows.  *needed
+ * receives the total; dst NULL only asks for it.  Synchronises the stream first. */
+int lgh_prefix_export(lgh_ctx* ctx, const lgh_prefix* prefix, void* dst, size_t dst_bytes, size_t* needed);
+/* ... and back: every header field is checked against the context, the size against the header. */
+int lgh_prefix_import(lgh_ctx* ctx, const void* src, size_t bytes, lgh_prefix** out);
+
 const char* lgh_last_error(const lgh_ctx* ctx);
 int lgh_get_stats(lgh_ctx* ctx, lgh_stats* out);
 /* on: run eagerly with hipEvent pairs around every launch and accumulate lgh_stats.k_* */
@@ -649,6 +694,13 @@ int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, 
 int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes,
                                 const float* signs, float* out, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_seq_len,
                                 float scale, size_t pos0, size_t m_tokens);
+/* kv_prefix_copy_kernel (the one launch of lgh_prefix_save / lgh_prefix_restore, src/model/cache.rs:287-326) over host arrays, with the
+ * engine's own table builder and launch: caches [n_layers][5] = per layer the K, V, K scale, V scale and K QJL tensors of n_slots
+ * slots as lgh_kv_cache_layout sizes them (NULL where the format has none).  restore 0: rows [0, n_rows) of `slot` come back in
+ * packed ([layer][kind][kv head][n_rows][bytes per position]); restore 1: packed goes into those rows, and every cache array comes
+ * back as the device holds it afterwards. */
+int lgh_op_kv_prefix_copy(int device, uint32_t kv_cache_type, uint32_t n_kv_heads, uint32_t max_seq_len, uint32_t head_dim, uint32_t n_layers,
+                          uint32_t n_slots, void* const* caches, uint32_t slot, uint32_t n_rows, void* packed, int restore);
 /* The engine's quantized mat-vec launches (launch_mv), one call site at a time, for kernel-level tests.  Test surface: these
  * exist to hold the kernels to a reference and are not part of the inference API.  Weights are native GGUF bytes, row-major
  * [out][in]; the library re-lays them out as lgh_upload_tensor does, so each weight runs on the kernel family the engine picks.

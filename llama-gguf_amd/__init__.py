@@ -9,4 +9,5 @@ package is registered as ``llama_gguf_amd`` by ``__graft_entry__.load_package()`
 """
 from . import hip_backend, synth  # noqa: F401
 from .hip_backend import BackendError, GpuModelWrapper, HipBackend, HipGpuInference, HipPipeline, HipTensorParallel, InferenceContext  # noqa: F401
+from .hip_backend import KvPrefix, PrefixSharing, PromptCache, PromptCacheConfig, PromptCacheStats  # noqa: F401
 from .synth import ModelConfig, SynthModel, make_config  # noqa: F401

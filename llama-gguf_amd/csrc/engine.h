@@ -127,6 +127,11 @@ struct lgh_ctx {
   lgh::SampBufs samp;                          // single-stage contexts: the sampler of lgh_set_sampler / lgh_decode_sample
   lgh_sampler_config_ex samp_cfg{};
   bool samp_set = false;
+  // device prompt cache (kv_prefix.hip): the live prefixes this context made, and the device tables of its cache tensors ([0] the own
+  // sequence's, [1] the slots'), built at first use
+  std::vector<lgh_prefix*> prefixes;
+  void* prefix_tab[2] = {nullptr, nullptr};
+  uint32_t prefix_tab_n[2] = {0, 0};
 };
 
 // ---- what crosses the engine's files: engine_launch.hip (uploads, mat-vec launch assembly, XQ registry), engine_layer.hip (the
@@ -270,6 +275,12 @@ int pf_wo_step(lgh_ctx* c, lgh::LayerW& L, uint32_t m);
 int pf_ffn_step(lgh_ctx* c, lgh::LayerW& L, const float* next_nw, uint32_t m);
 int pf_moe_step(lgh_ctx* c, lgh::LayerW& L, const float* next_nw, uint32_t m);
 int prefill_own(lgh_ctx* c, const uint32_t* tokens, size_t n);   // the context's own sequence: blocks of <= 128, position and ST_NEXT moved
+// device prompt cache (kv_prefix.hip).  Rows [0, n_rows) of every tensor of every owned layer of one sequence (slot < 0: the context's
+// own) to (restore: from) a packed buffer of n_stride rows, [layer][kind][kv head][n_stride][bytes per position]: one launch on the
+// context's stream
+int kv_prefix_copy(lgh_ctx* c, int slot, uint32_t n_rows, uint32_t n_stride, void* packed, bool restore);
+uint64_t kv_prefix_bytes(const lgh_ctx* c, uint64_t n_rows);   // bytes of n_rows packed rows of this context's layers
+void kv_prefix_release(lgh_ctx* c);                            // frees the live prefixes (lgh_destroy)
 // sampler plumbing (sample.hip)
 int samp_alloc(lgh_ctx* c, lgh::SampBufs& B, uint32_t n_slots, uint32_t n_rows);
 int samp_check(lgh_ctx* c, const lgh_sampler_config* cfg);

@@ -490,6 +490,7 @@ void lgh_destroy(lgh_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   drop_graphs(c);
   for (auto& r : c->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+  kv_prefix_release(c);
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->batch.h_ctl) (void)hipHostFree(c->batch.h_ctl);
   if (c->pf.tok_pinned) (void)hipHostFree(c->pf.tok_pinned);

@@ -799,6 +799,43 @@ int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, 
   return kv_download(t, l, 1, codes, kv);
 }
 
+int lgh_op_kv_prefix_copy(int device, uint32_t kv_cache_type, uint32_t n_kv, uint32_t max_seq, uint32_t head_dim, uint32_t n_layers, uint32_t n_slots,
+                          void* const* caches, uint32_t slot, uint32_t n_rows, void* packed, int restore) {
+  // the copy of PrefixSharing::save_prefix / try_restore (cache.rs:287-326) as lgh_prefix_save / lgh_prefix_restore launch it, over the
+  // slots' caches of a bare context
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (kv_cache_type > LGH_KV_TQ3_QJL) return LGH_INVALID_ARGUMENT;
+  if (head_dim != 64 && head_dim != 128) return LGH_UNSUPPORTED;
+  if (!caches || !packed || !n_kv || !max_seq || max_seq > 0x7FFFFFFFu || !n_layers || !n_slots || n_slots > (uint32_t)kMaxBatch) return LGH_INVALID_ARGUMENT;
+  if (slot >= n_slots || n_rows == 0 || n_rows > max_seq) return LGH_INVALID_ARGUMENT;
+  lgh_ctx* c = t.c;
+  c->d.num_kv_heads = n_kv;
+  c->d.head_dim = head_dim;
+  c->d.max_seq_len = max_seq;
+  c->d.kv_cache_type = kv_cache_type;
+  c->d.num_layers = n_layers;
+  c->kvl = KvLayout(c->d);
+  c->l0 = 0;
+  c->l1 = n_layers;
+  for (uint32_t li = 0; li < n_layers; li++)
+    for (int kind = 0; kind < KV_KINDS; kind++)
+      if (c->kvl.pos_bytes(kind) && !caches[li * KV_KINDS + kind]) return LGH_INVALID_ARGUMENT;
+  BatchScratch& Bs = c->batch;
+  Bs.max_batch = n_slots;
+  Bs.kv.assign(n_layers, KvCache{});
+  for (uint32_t li = 0; li < n_layers; li++)
+    if (int rc = kv_upload(t, c->kvl, n_slots, caches + li * KV_KINDS, Bs.kv[li])) return rc;
+  const size_t bytes = (size_t)kv_prefix_bytes(c, n_rows);
+  void* dp = up_bytes(t, restore ? packed : nullptr, bytes);
+  if (!dp) return LGH_ALLOCATION_FAILED;
+  if (int rc = kv_prefix_copy(c, (int)slot, n_rows, n_rows, dp, restore != 0)) return rc;
+  if (!restore) return down_bytes(t, packed, dp, bytes);
+  for (uint32_t li = 0; li < n_layers; li++)
+    if (int rc = kv_download(t, c->kvl, n_slots, caches + li * KV_KINDS, Bs.kv[li])) return rc;
+  return LGH_OK;
+}
+
 int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes, const float* signs,
                                 float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq, float scale, size_t pos0, size_t m_tokens) {
   // TurboQuantKVCache::attention_layer (kv_turboquant.rs:127-201) for a block of prompt tokens, as the batched prefill runs it

@@ -48,6 +48,8 @@ ABI_SYMBOLS = (
     "lgh_op_linear_multi", "lgh_op_linear_chain_multi", "lgh_op_qkv_rope_multi", "lgh_op_moe_multi", "lgh_debug_mvqb_structures",
     "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_attention_kv8_multi", "lgh_op_attention_tq_multi",
     "lgh_op_embed", "lgh_op_qkv_forward", "lgh_op_ffn_gateup", "lgh_op_argmax", "lgh_kv_cache_layout",
+    "lgh_prefix_save", "lgh_prefix_restore", "lgh_prefix_free", "lgh_prefix_get_info", "lgh_prefix_total_bytes", "lgh_prefix_export",
+    "lgh_prefix_import", "lgh_op_kv_prefix_copy",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -95,6 +97,11 @@ class KvLayout(C.Structure):
     """lgh_kv_layout: a KV cache format's bytes per (kv head, position) and per slot of one layer."""
     _fields_ = ([(n, C.c_uint32) for n in ("kv_cache_type", "row_bytes", "scale_bytes", "qjl_bytes")]
                 + [(n, C.c_uint64) for n in ("rows", "k_bytes", "v_bytes", "k_scale_bytes", "v_scale_bytes", "k_qjl_bytes", "slot_bytes")])
+
+
+class PrefixInfo(C.Structure):
+    """lgh_prefix_info: what a saved KV prefix holds."""
+    _fields_ = ([(n, C.c_uint32) for n in ("struct_size", "kv_cache_type", "n_rows", "layer_begin", "layer_end")] + [("bytes", C.c_uint64)])
 
 
 class GgufInfo(C.Structure):
@@ -285,6 +292,11 @@ def load_library() -> C.CDLL:
         "lgh_op_ffn_gateup": (C.c_int, [C.c_int, u32, vp, u32, vp, vp, vp, f32, sz, sz, vp]),
         "lgh_op_argmax": (C.c_int, [C.c_int, vp, sz, sz, vp]),
         "lgh_kv_cache_layout": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(KvLayout)]),
+        "lgh_prefix_save": (C.c_int, [vp, C.c_int, sz, C.POINTER(vp)]), "lgh_prefix_restore": (C.c_int, [vp, vp, C.c_int, sz]),
+        "lgh_prefix_free": (C.c_int, [vp, vp]), "lgh_prefix_get_info": (C.c_int, [vp, vp, C.POINTER(PrefixInfo)]),
+        "lgh_prefix_total_bytes": (C.c_uint64, [vp]), "lgh_prefix_export": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz)]),
+        "lgh_prefix_import": (C.c_int, [vp, vp, sz, C.POINTER(vp)]),
+        "lgh_op_kv_prefix_copy": (C.c_int, [C.c_int, u32, u32, u32, u32, u32, u32, C.POINTER(vp), u32, u32, vp, C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -508,6 +520,28 @@ class HipGpuInference:
                                                           u.ctypes.data if u is not None else None, out.ctypes.data))
         return out
 
+    # -- device prompt cache (PrefixSharing::save_prefix / try_restore, src/model/cache.rs:269-326; include/llama_gguf_hip.h lgh_prefix_*)
+    def prefix_save(self, n: Optional[int] = None, slot: int = -1) -> "KvPrefix":
+        """Rows [0, n) (None: up to the position) of the own sequence (slot -1) or of a batch slot, copied into a new device prefix."""
+        h = C.c_void_p()
+        self._call(load_library().lgh_prefix_save(self._h, slot, 0 if n is None else n, C.byref(h)))
+        return KvPrefix(self, h)
+
+    def prefix_restore(self, prefix: "KvPrefix", slot: int = -1, n: Optional[int] = None) -> None:
+        """The target reset, then a prompt of n tokens (None: the whole prefix) by copying; the position follows."""
+        self._call(load_library().lgh_prefix_restore(self._h, prefix._h, slot, 0 if n is None else n))
+
+    def prefix_from_bytes(self, blob) -> "KvPrefix":
+        """KvPrefix.to_bytes() back into a device prefix of this context (every header field is checked against it)."""
+        b = np.frombuffer(bytes(blob), dtype=np.uint8)
+        h = C.c_void_p()
+        self._call(load_library().lgh_prefix_import(self._h, b.ctypes.data if b.size else None, b.size, C.byref(h)))
+        return KvPrefix(self, h)
+
+    def prefix_total_bytes(self) -> int:
+        """Device bytes of this context's live prefixes (not part of stats())."""
+        return int(load_library().lgh_prefix_total_bytes(self._h))
+
     # -- pipeline stage
     def stage_hidden_ptr(self) -> int:
         p = C.c_void_p()
@@ -586,6 +620,204 @@ class HipGpuInference:
             self.close()
         except Exception:
             pass
+
+
+class KvPrefix:
+    """A saved KV prefix on the device (lgh_prefix; CachedPrefix's k_cache / v_cache, src/model/cache.rs:28-43).  Owned by the engine
+    that made it: `free()` releases the device memory, closing the engine releases what is left."""
+
+    def __init__(self, engine: HipGpuInference, handle: C.c_void_p):
+        self._engine, self._h = engine, handle
+        info = self.info()
+        self.n_rows, self.nbytes = int(info.n_rows), int(info.bytes)
+
+    def info(self) -> PrefixInfo:
+        out = PrefixInfo()
+        self._engine._call(load_library().lgh_prefix_get_info(self._engine._h, self._h, C.byref(out)))
+        return out
+
+    def free(self) -> None:
+        self._engine._call(load_library().lgh_prefix_free(self._engine._h, self._h))
+
+    def to_bytes(self) -> bytes:
+        """The exported blob (header + packed rows), for a session file or HipGpuInference.prefix_from_bytes."""
+        need = C.c_size_t(0)
+        L = load_library()
+        self._engine._call(L.lgh_prefix_export(self._engine._h, self._h, None, 0, C.byref(need)))
+        buf = np.empty(need.value, dtype=np.uint8)
+        self._engine._call(L.lgh_prefix_export(self._engine._h, self._h, buf.ctypes.data, buf.nbytes, C.byref(need)))
+        return buf.tobytes()
+
+
+# ---- PromptCache / PrefixSharing (src/model/cache.rs:67-345) over device prefixes.  The reference's entries clone the K / V tensors
+# of every layer; here an entry holds the handle `engine.prefix_save()` returned — anything with `.nbytes` and `.free()` — and the
+# copy is the engine's `prefix_restore`.  Restated as written, quirks included; nothing here touches a GPU by itself. ----
+class PromptCacheConfig:
+    """PromptCacheConfig and its Default (cache.rs:67-89)."""
+
+    def __init__(self, max_entries: int = 100, max_memory: int = 1024 * 1024 * 1024, min_prefix_len: int = 32,
+                 cache_system_prompts: bool = True):
+        self.max_entries, self.max_memory, self.min_prefix_len = max_entries, max_memory, min_prefix_len
+        self.cache_system_prompts = cache_system_prompts
+
+
+class PromptCacheStats:
+    """PromptCacheStats (cache.rs:238-247)."""
+
+    def __init__(self, num_entries: int, memory_used: int, total_tokens_cached: int):
+        self.num_entries, self.memory_used, self.total_tokens_cached = num_entries, memory_used, total_tokens_cached
+
+    def __repr__(self):
+        return f"PromptCacheStats(num_entries={self.num_entries}, memory_used={self.memory_used}, total_tokens_cached={self.total_tokens_cached})"
+
+
+def prefix_id(tokens: Sequence[int]) -> int:
+    """PrefixId::from_tokens (cache.rs:18-25): a 64-bit hash of the tokens.  Rust's DefaultHasher is unspecified, so its values are
+    not reproduced: FNV-1a over the length and the little-endian u32 tokens."""
+    h = 0xCBF29CE484222325
+    for b in len(tokens).to_bytes(8, "little") + b"".join(int(t).to_bytes(4, "little") for t in tokens):
+        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+class CachedPrefix:
+    """CachedPrefix (cache.rs:28-65): the tokens and the device handle of their KV rows."""
+
+    def __init__(self, tokens: Sequence[int], handle, stamp: int):
+        self.tokens = [int(t) for t in tokens]
+        self.handle = handle
+        self.seq_len = len(self.tokens)
+        self.ref_count = 0
+        self.last_access = stamp      # a counter, not a clock: later accesses have larger stamps
+
+    def memory_size(self) -> int:     # cache.rs:60-64: K bytes + V bytes + 4 per token
+        return int(self.handle.nbytes) + 4 * len(self.tokens)
+
+
+class PromptCache:
+    """PromptCache (cache.rs:91-236)."""
+
+    def __init__(self, config: Optional[PromptCacheConfig] = None):
+        self.config = config or PromptCacheConfig()
+        self.entries = {}
+        self.memory_used = 0
+        self._clock = 0
+
+    def _now(self) -> int:
+        self._clock += 1
+        return self._clock
+
+    def cache_prefix(self, tokens: Sequence[int], handle) -> int:
+        """cache.rs:112-150.  A known id bumps ref_count and refreshes the stamp; a prompt below min_prefix_len is not stored; in
+        both cases the caller's new handle is freed (the reference drops the tensors it was given).  Eviction stops when no
+        entry has ref_count 0, and the new entry is inserted anyway."""
+        pid = prefix_id(tokens)
+        entry = self.entries.get(pid)
+        if entry is not None:
+            entry.ref_count += 1
+            entry.last_access = self._now()
+            if handle is not None and handle is not entry.handle:
+                handle.free()
+            return pid
+        if len(tokens) < self.config.min_prefix_len:
+            if handle is not None:
+                handle.free()
+            return pid
+        prefix = CachedPrefix(tokens, handle, self._now())
+        size = prefix.memory_size()
+        while self.memory_used + size > self.config.max_memory or len(self.entries) >= self.config.max_entries:
+            if not self._evict_lru():
+                break
+        self.memory_used += size
+        self.entries[pid] = prefix
+        return pid
+
+    def get_prefix(self, pid: int) -> Optional[CachedPrefix]:          # cache.rs:153-161
+        entry = self.entries.get(pid)
+        if entry is not None:
+            entry.ref_count += 1
+            entry.last_access = self._now()
+        return entry
+
+    def find_matching_prefix(self, tokens: Sequence[int]):             # cache.rs:164-188 -> (id, length) or None
+        toks = [int(t) for t in tokens]
+        best = None
+        for pid, entry in self.entries.items():
+            n = len(entry.tokens)
+            if len(toks) >= n and toks[:n] == entry.tokens and (best is None or n > best[1]):
+                best = (pid, n)
+        if best is not None:
+            entry = self.entries[best[0]]
+            entry.last_access = self._now()
+            entry.ref_count += 1
+        return best
+
+    def remove_prefix(self, pid: int) -> None:                          # cache.rs:191-195; the device memory is freed
+        entry = self.entries.pop(pid, None)
+        if entry is not None:
+            self.memory_used = max(0, self.memory_used - entry.memory_size())
+            entry.handle.free()
+
+    def clear(self) -> None:                                            # cache.rs:198-201
+        for entry in self.entries.values():
+            entry.handle.free()
+        self.entries.clear()
+        self.memory_used = 0
+
+    def stats(self) -> PromptCacheStats:                                # cache.rs:204-210
+        return PromptCacheStats(len(self.entries), self.memory_used, sum(e.seq_len for e in self.entries.values()))
+
+    def _evict_lru(self) -> bool:                                       # cache.rs:213-228
+        idle = [(e.last_access, pid) for pid, e in self.entries.items() if e.ref_count == 0]
+        if not idle:
+            return False
+        self.remove_prefix(min(idle)[1])
+        return True
+
+    def release_prefix(self, pid: int) -> None:                         # cache.rs:231-235
+        entry = self.entries.get(pid)
+        if entry is not None:
+            entry.ref_count = max(0, entry.ref_count - 1)
+
+
+class PrefixSharing:
+    """PrefixSharing (cache.rs:250-345) over any engine object with `prefix_save(n, slot)` / `prefix_restore(prefix, slot, n)`."""
+
+    def __init__(self, config: Optional[PromptCacheConfig] = None):
+        self.cache = PromptCache(config)
+        self.active_prefix = None
+
+    def try_restore(self, tokens: Sequence[int], engine, slot: int = -1) -> int:
+        """cache.rs:269-310: the longest cached prefix of `tokens` copied into the engine's sequence; returns the tokens restored
+        (0: no match).  find_matching_prefix and get_prefix each bump ref_count, so a restore bumps it twice."""
+        m = self.cache.find_matching_prefix(tokens)
+        if m is None:
+            return 0
+        pid, match_len = m
+        prefix = self.cache.get_prefix(pid)
+        if prefix is None:
+            return 0
+        engine.prefix_restore(prefix.handle, slot, match_len)
+        self.active_prefix = pid
+        return match_len
+
+    def save_prefix(self, tokens: Sequence[int], engine, slot: int = -1) -> int:
+        """cache.rs:313-326: the first len(tokens) rows of the engine's sequence cached under the tokens' id."""
+        pid = self.cache.cache_prefix(tokens, engine.prefix_save(len(tokens), slot))
+        self.active_prefix = pid
+        return pid
+
+    def release_active(self) -> None:                                   # cache.rs:329-333: drops ref_count once
+        if self.active_prefix is not None:
+            self.cache.release_prefix(self.active_prefix)
+            self.active_prefix = None
+
+    def stats(self) -> PromptCacheStats:
+        return self.cache.stats()
+
+    def clear(self) -> None:                                            # cache.rs:341-344
+        self.active_prefix = None
+        self.cache.clear()
 
 
 class HipPipeline:
@@ -1412,6 +1644,25 @@ def op_pf_tq_store(kv_cache_type: int, k_rows, v_rows, pos0: int, signs, k_codes
     _chk(load_library().lgh_op_pf_tq_store(device, kv_cache_type, kr.ctypes.data, vr.ctypes.data, m, nkv, d, kc.shape[1], pos0,
                                            sg.ctypes.data, kc.ctypes.data, vc.ctypes.data), "pf_tq_store")
     return kc, vc
+
+
+def op_kv_prefix_copy(kv_cache_type: int, caches, slot: int, n_rows: int, head_dim: int, packed=None, device: int = 0):
+    """kv_prefix_copy_kernel over host arrays.  caches: per layer the five tensors (K, V, K scales, V scales, K QJL words) as uint8
+    arrays [n_slots, nkv, max_seq, bytes per position], None where the format has none.  packed None: save -> the packed rows
+    (uint8) of `slot`; else restore -> the caches after the launch (copies, same nesting)."""
+    lay = [[None if t is None else np.array(t, dtype=np.uint8, copy=True) for t in layer] for layer in caches]
+    first = next(t for t in lay[0] if t is not None)
+    n_slots, nkv, max_seq = first.shape[:3]
+    ptrs = (C.c_void_p * (5 * len(lay)))(*[None if t is None else t.ctypes.data for layer in lay for t in layer])
+    per_pos = sum(t.shape[3] for t in lay[0] if t is not None)
+    if packed is None:
+        buf = np.zeros(len(lay) * nkv * n_rows * per_pos, dtype=np.uint8)
+    else:
+        buf = np.ascontiguousarray(packed, dtype=np.uint8)
+        assert buf.size == len(lay) * nkv * n_rows * per_pos
+    _chk(load_library().lgh_op_kv_prefix_copy(device, kv_cache_type, nkv, max_seq, head_dim, len(lay), n_slots, ptrs, slot, n_rows,
+                                              buf.ctypes.data, 0 if packed is None else 1), "kv_prefix_copy")
+    return buf if packed is None else lay
 
 
 def op_attention_prefill_tq(kv_cache_type: int, q, k_codes, v_codes, signs, scale: float, pos0: int, device: int = 0) -> np.ndarray:

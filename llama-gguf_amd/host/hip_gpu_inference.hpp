@@ -119,6 +119,35 @@ class HipGpuInference {
     return out;
   }
 
+  // ---- the device prompt cache (PrefixSharing::save_prefix / try_restore, src/model/cache.rs:269-326): a sequence's KV rows kept in one
+  // packed device buffer and put back by copying.  slot -1 = the own sequence.  The handles belong to this engine; the destructor
+  // frees the live ones.
+  lgh_prefix* prefix_save(size_t n_rows = 0, int slot = -1) {                           // 0: up to the position
+    lgh_prefix* p = nullptr;
+    check(lgh_prefix_save(h_, slot, n_rows, &p));
+    return p;
+  }
+  void prefix_restore(const lgh_prefix* p, int slot = -1, size_t n_rows = 0) { check(lgh_prefix_restore(h_, p, slot, n_rows)); }   // 0: all
+  void prefix_free(lgh_prefix* p) { check(lgh_prefix_free(h_, p)); }                   // PromptCache::remove_prefix (cache.rs:191-195)
+  lgh_prefix_info prefix_info(const lgh_prefix* p) {
+    lgh_prefix_info info{};
+    check(lgh_prefix_get_info(h_, p, &info));
+    return info;
+  }
+  uint64_t prefix_total_bytes() { return lgh_prefix_total_bytes(h_); }                  // PromptCacheStats::memory_used, device bytes
+  std::vector<uint8_t> prefix_to_bytes(const lgh_prefix* p) {                           // header + packed rows (a session file)
+    size_t need = 0;
+    check(lgh_prefix_export(h_, p, nullptr, 0, &need));
+    std::vector<uint8_t> out(need);
+    check(lgh_prefix_export(h_, p, out.data(), out.size(), &need));
+    return out;
+  }
+  lgh_prefix* prefix_from_bytes(const std::vector<uint8_t>& blob) {
+    lgh_prefix* p = nullptr;
+    check(lgh_prefix_import(h_, blob.data(), blob.size(), &p));
+    return p;
+  }
+
  private:
   HipGpuInference(lgh_ctx* h, uint32_t vocab) : h_(h), vocab_(vocab) {}
   void check(int rc) { if (rc) throw BackendError(rc, lgh_last_error(h_)); }
