@@ -492,52 +492,30 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_q8_kernel(const float* _
 
 // n_seq 0: the single-sequence launch; else grid y = the sequences of a step over cache slots (engine_batch.hip).  NW = 4 whatever
 // max_seq is, for both: with another wave count the rows would be dealt differently and the sums would differ in their last bits.
-struct Q8Args {
-  int fmt; const float* q; int8_t *k8, *v8; float *ks, *vs; const float *k_new, *v_new; uint32_t n_kv, max_seq; float scale; const int* pos;
-  uint32_t n_splits; float *part_ml, *part_acc; hipStream_t st;
-  uint32_t n_seq; const int* slot; uint32_t x_stride;
-};
-
+// Caches [slot][n_kv][max_seq][D] bytes, scales (int8) [slot][n_kv][max_seq]; sequence s's staged (K row | V row) pair x_stride floats on.
 template <int D, int G, int FMT>
-static hipError_t attn_q8_go(const Q8Args& a) {
-  const dim3 grid(a.n_kv * a.n_splits, a.n_seq ? a.n_seq : 1);
+static hipError_t attn_q8_go(const KvLayout& l, const KvCache& kv, const AttnDecode& a) {
+  const float *k_new = a.kv_new, *v_new = a.kv_new + (size_t)l.n_kv * D;
+  const uint32_t x_stride = 2 * l.n_kv * D;
+  const dim3 grid(l.n_kv * a.n_splits, a.n_seq ? a.n_seq : 1);
   if (a.n_seq)
-    hipLaunchKernelGGL((attn_partial_q8_kernel<D, G, 4, FMT, true>), grid, dim3(256), 0, a.st, a.q, a.k8, a.v8, a.ks, a.vs, a.k_new, a.v_new, a.max_seq,
-                       a.scale, a.pos, a.n_splits, a.part_ml, a.part_acc, a.slot, a.x_stride);
+    hipLaunchKernelGGL((attn_partial_q8_kernel<D, G, 4, FMT, true>), grid, dim3(256), 0, a.st, a.q, kv.k_i8(), kv.v_i8(), kv.kscale(), kv.vscale(), k_new,
+                       v_new, l.max_seq, a.scale, a.pos, a.n_splits, a.part_ml, a.part_acc, a.slot, x_stride);
   else
-    hipLaunchKernelGGL((attn_partial_q8_kernel<D, G, 4, FMT>), grid, dim3(256), 0, a.st, a.q, a.k8, a.v8, a.ks, a.vs, a.k_new, a.v_new, a.max_seq,
-                       a.scale, a.pos, a.n_splits, a.part_ml, a.part_acc);
+    hipLaunchKernelGGL((attn_partial_q8_kernel<D, G, 4, FMT>), grid, dim3(256), 0, a.st, a.q, kv.k_i8(), kv.v_i8(), kv.kscale(), kv.vscale(), k_new,
+                       v_new, l.max_seq, a.scale, a.pos, a.n_splits, a.part_ml, a.part_acc);
   return hipGetLastError();
 }
 
-static hipError_t attn_q8_dispatch(uint32_t head_dim, uint32_t g, const Q8Args& a) {
-  return attn_dispatch(head_dim, g, [&](auto d, auto gg) {
+// FMT: the layout's type (1 = int8 + scales, 2 = FP8 E4M3, 3 = FP8 E5M2; the scale arrays are unused for 2 and 3)
+static hipError_t attn_q8_dispatch(const KvLayout& l, const KvCache& kv, const AttnDecode& a) {
+  return attn_dispatch(l.d, a.n_heads / l.n_kv, [&](auto d, auto gg) {
     constexpr int D = decltype(d)::value, G = decltype(gg)::value;
-    if (a.fmt == 1) return attn_q8_go<D, G, 1>(a);
-    if (a.fmt == 2) return attn_q8_go<D, G, 2>(a);
-    if (a.fmt == 3) return attn_q8_go<D, G, 3>(a);
+    if (l.type == LGH_KV_INT8) return attn_q8_go<D, G, 1>(l, kv, a);
+    if (l.type == LGH_KV_FP8_E4M3) return attn_q8_go<D, G, 2>(l, kv, a);
+    if (l.type == LGH_KV_FP8_E5M2) return attn_q8_go<D, G, 3>(l, kv, a);
     return hipErrorInvalidValue;
   });
-}
-
-// fmt: lgh_model_desc.kv_cache_type (1 = int8 + scales, 2 = FP8 E4M3, 3 = FP8 E5M2; the scale arrays are unused for 2 and 3)
-hipError_t attn_q8_launch(int fmt, const float* q, int8_t* k8, int8_t* v8, float* kscale, float* vscale, const float* k_new, const float* v_new,
-                          uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, uint32_t n_splits,
-                          float* part_ml, float* part_acc, hipStream_t st) {
-  if (n_kv == 0 || n_heads % n_kv || !pos) return hipErrorInvalidValue;
-  return attn_q8_dispatch(head_dim, n_heads / n_kv,
-                          Q8Args{fmt, q, k8, v8, kscale, vscale, k_new, v_new, n_kv, max_seq, scale, pos, n_splits, part_ml, part_acc, st, 0, nullptr, 0});
-}
-
-// caches [slot][n_kv][max_seq][D] bytes, scales (int8) [slot][n_kv][max_seq]; k_new / v_new of sequence s at + s * x_stride floats;
-// pos / slot: n_seq device words each
-hipError_t attn_q8_multi_launch(int fmt, const float* q, int8_t* k8, int8_t* v8, float* kscale, float* vscale, const float* k_new, const float* v_new,
-                                uint32_t x_stride, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos,
-                                const int* slot, uint32_t n_seq, uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
-  if (n_kv == 0 || n_heads % n_kv || !pos || !slot || n_seq == 0 || n_splits == 0 || n_splits > 32) return hipErrorInvalidValue;
-  if (fmt == 1 && (!kscale || !vscale)) return hipErrorInvalidValue;
-  return attn_q8_dispatch(head_dim, n_heads / n_kv,
-                          Q8Args{fmt, q, k8, v8, kscale, vscale, k_new, v_new, n_kv, max_seq, scale, pos, n_splits, part_ml, part_acc, st, n_seq, slot, x_stride});
 }
 
 // one row of n values through a byte KV format and back (the quantizers of attn_partial_q8_kernel, stand-alone): bytes and,
@@ -603,38 +581,39 @@ __global__ void __launch_bounds__(128) attn_combine_kernel(const float* __restri
 
 // n_seq 0: the single-sequence launch; else grid y = the sequences of a step over cache slots (engine_batch.hip).  The wave count
 // follows the cache capacity alone, so a sequence's rows are dealt the same way in both and its partials are the same bits.
-struct AttnArgs {
-  const float *q, *kc, *vc; uint32_t n_kv, max_seq; float scale; const int* pos; int kv_len_fixed; uint32_t n_splits; float *part_ml, *part_acc;
-  hipStream_t st;
-  uint32_t n_seq; const int* slot; uint64_t slot_stride;
-};
-
 template <int D, int G, int NW>
-static hipError_t attn_go(const AttnArgs& a) {
-  const dim3 grid(a.n_kv * a.n_splits, a.n_seq ? a.n_seq : 1);
+static hipError_t attn_go(const KvLayout& l, const KvCache& kv, const AttnDecode& a) {
+  const dim3 grid(l.n_kv * a.n_splits, a.n_seq ? a.n_seq : 1);
   if (a.n_seq)
-    hipLaunchKernelGGL((attn_partial_kernel<D, G, NW, false, false, true>), grid, dim3(NW * 64), 0, a.st, a.q, a.kc, a.vc, a.max_seq, a.scale, a.pos, 0,
-                       a.n_splits, a.part_ml, a.part_acc, a.slot, a.slot_stride);
+    hipLaunchKernelGGL((attn_partial_kernel<D, G, NW, false, false, true>), grid, dim3(NW * 64), 0, a.st, a.q, kv.k_f32(), kv.v_f32(), l.max_seq, a.scale,
+                       a.pos, 0, a.n_splits, a.part_ml, a.part_acc, a.slot, l.stride_floats());
   else
-    hipLaunchKernelGGL((attn_partial_kernel<D, G, NW>), grid, dim3(NW * 64), 0, a.st, a.q, a.kc, a.vc, a.max_seq, a.scale, a.pos, a.kv_len_fixed,
-                       a.n_splits, a.part_ml, a.part_acc);
+    hipLaunchKernelGGL((attn_partial_kernel<D, G, NW>), grid, dim3(NW * 64), 0, a.st, a.q, kv.k_f32(), kv.v_f32(), l.max_seq, a.scale, a.pos,
+                       a.kv_len_fixed, a.n_splits, a.part_ml, a.part_acc);
   return hipGetLastError();
 }
 
-static hipError_t attn_split_dispatch(uint32_t head_dim, uint32_t g, const AttnArgs& a) {
-  const bool long_ctx = (a.pos ? a.max_seq : (uint32_t)a.kv_len_fixed) >= 2048;
-  return attn_dispatch(head_dim, g, [&](auto d, auto gg) {
+static hipError_t attn_f32_dispatch(const KvLayout& l, const KvCache& kv, const AttnDecode& a) {
+  const bool long_ctx = (a.pos ? l.max_seq : (uint32_t)a.kv_len_fixed) >= 2048;
+  return attn_dispatch(l.d, a.n_heads / l.n_kv, [&](auto d, auto gg) {
     constexpr int D = decltype(d)::value, G = decltype(gg)::value;
-    return long_ctx ? attn_go<D, G, 8>(a) : attn_go<D, G, 4>(a);
+    return long_ctx ? attn_go<D, G, 8>(l, kv, a) : attn_go<D, G, 4>(l, kv, a);
   });
 }
 
-hipError_t attn_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv,
-                       uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, int kv_len_fixed,
-                       uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
-  if (n_kv == 0 || n_heads % n_kv) return hipErrorInvalidValue;
-  return attn_split_dispatch(head_dim, n_heads / n_kv,
-                             AttnArgs{q, kcache, vcache, n_kv, max_seq, scale, pos, kv_len_fixed, n_splits, part_ml, part_acc, st, 0, nullptr, 0});
+// What both launches of a split step ask of its description, whatever the format
+static bool attn_decode_ok(const KvLayout& l, const AttnDecode& a) {
+  return l.n_kv != 0 && a.n_heads % l.n_kv == 0 && a.n_splits >= 1 && a.n_splits <= 32 && (a.pos || (l.f32() && !a.n_seq && a.kv_len_fixed > 0)) &&
+         (a.n_seq == 0 || a.slot) && (!l.tq() || a.signs);
+}
+
+hipError_t attn_tq_split_launch(const KvLayout& l, const KvCache& kv, const AttnDecode& a);   // attention_tq.hip
+hipError_t attn_tq_merge_launch(const KvLayout& l, const AttnDecode& a);
+
+hipError_t attn_split_launch(const KvLayout& l, const KvCache& kv, const AttnDecode& a) {
+  if (!attn_decode_ok(l, a) || (l.staged() && !a.kv_new) || (l.has_scales() && (!kv.kscale() || !kv.vscale())) || (a.qjl_s != nullptr) != (kv.kx() != nullptr))
+    return hipErrorInvalidValue;
+  return l.tq() ? attn_tq_split_launch(l, kv, a) : l.staged() ? attn_q8_dispatch(l, kv, a) : attn_f32_dispatch(l, kv, a);
 }
 
 // single-launch decode attention for short contexts (engine.hip picks it by the host-side position)
@@ -954,28 +933,20 @@ hipError_t attn_decode_any_launch(const float* q, const float* kcache, const flo
   return hipGetLastError();
 }
 
-hipError_t attn_combine_launch(const float* part_ml, const float* part_acc, uint32_t n_heads, uint32_t n_kv,
-                               uint32_t head_dim, uint32_t n_splits, float* out, uint8_t* xq_out, hipStream_t st) {
-  if (n_kv == 0 || n_heads % n_kv || head_dim % 16 || head_dim > 128 || n_splits > 32) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(attn_combine_kernel<false>, dim3(n_heads), dim3(head_dim > 64 ? 128 : 64), 0, st, part_ml, part_acc,
-                     n_heads / n_kv, head_dim, n_splits, out, xq_out);
-  return hipGetLastError();
-}
-
-// ---- multi-sequence decode (engine_batch.hip): the split attention and its merge for n_seq sequences in one launch each
-hipError_t attn_multi_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
-                             uint32_t max_seq, float scale, const int* pos, const int* slot, uint64_t slot_stride, uint32_t n_seq,
-                             uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st) {
-  if (n_kv == 0 || n_heads % n_kv || !pos || !slot || n_seq == 0 || n_splits == 0 || n_splits > 32) return hipErrorInvalidValue;
-  return attn_split_dispatch(head_dim, n_heads / n_kv,
-                             AttnArgs{q, kcache, vcache, n_kv, max_seq, scale, pos, 0, n_splits, part_ml, part_acc, st, n_seq, slot, slot_stride});
-}
-
-hipError_t attn_combine_multi_launch(const float* part_ml, const float* part_acc, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
-                                     uint32_t n_splits, uint32_t n_seq, float* out, uint8_t* xq_out, hipStream_t st) {
-  if (n_kv == 0 || n_heads % n_kv || head_dim % 16 || head_dim > 128 || n_splits > 32 || n_seq == 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(attn_combine_kernel<true>, dim3(n_heads, n_seq), dim3(head_dim > 64 ? 128 : 64), 0, st, part_ml, part_acc,
-                     n_heads / n_kv, head_dim, n_splits, out, xq_out);
+// the merge of a split step's partials: the f32 and byte caches' here, the TurboQuant caches' with the inverse rotation (attention_tq.hip).
+// (Last in the file, the single-sequence instantiation first: kernels are emitted in the order of their first use, and the code
+// object keeps the kernel order it was measured with — the launch-description note under profiles/)
+hipError_t attn_merge_launch(const KvLayout& l, const AttnDecode& a) {
+  if (!attn_decode_ok(l, a)) return hipErrorInvalidValue;
+  if (l.tq()) return attn_tq_merge_launch(l, a);
+  if (l.d % 16 || l.d > 128) return hipErrorInvalidValue;
+  const dim3 block(l.d > 64 ? 128 : 64);
+  if (!a.n_seq)
+    hipLaunchKernelGGL(attn_combine_kernel<false>, dim3(a.n_heads), block, 0, a.st, a.part_ml, a.part_acc, a.n_heads / l.n_kv, l.d, a.n_splits, a.out,
+                       a.xq_out);
+  else
+    hipLaunchKernelGGL(attn_combine_kernel<true>, dim3(a.n_heads, a.n_seq), block, 0, a.st, a.part_ml, a.part_acc, a.n_heads / l.n_kv, l.d, a.n_splits, a.out,
+                       a.xq_out);
   return hipGetLastError();
 }
 

@@ -496,76 +496,50 @@ uint32_t tq_row_bytes_host(int bits, uint32_t d) { return bits == 2 ? d / 4 : d 
 // positions one split can hold scores for: max_seq spread over the splits
 uint32_t tq_split_cap(uint32_t max_seq, uint32_t n_splits) { return (max_seq + n_splits - 1) / n_splits; }
 
-struct TqArgs {
-  const float* q; uint8_t *kq, *vq; const float *k_new, *v_new, *signs; uint32_t n_kv, max_seq; float scale; const int* pos; uint32_t n_splits;
-  float *part_ml, *part_acc; const float* qjl_s; uint32_t* kx; hipStream_t st;
-  uint32_t n_seq; TqMulti ms;   // n_seq 0: the single-sequence launch
-};
-
+// The code caches' partial launch (attn_split_launch has checked the description).  a.n_seq 0: the single-sequence launch; else grid y =
+// sequences: positions pos[s], cache slots slot[s] (the layout's code bytes / QJL words between slots), queries n_heads * D floats
+// apart, the staged (K row | V row) pairs 2 * n_kv * D.  a.qjl_s (TurboQuantProd; NULL = TurboQuantMSE) goes with the cache's QJL
+// rows [n_kv][max_seq][D / 32 + 1]
 template <int D, int G, int BITS, bool QJL>
-static hipError_t attn_tq_go(const TqArgs& a) {
+static hipError_t attn_tq_go(const KvLayout& l, const KvCache& kv, const AttnDecode& a) {
   static bool attr_set[2][64] = {};
-  const uint32_t cap = tq_split_cap(a.max_seq, a.n_splits);
+  const uint32_t cap = tq_split_cap(l.max_seq, a.n_splits);
   const size_t lds = (size_t)(QJL ? 2 * G + 3 : G + 2) * D * 4 + 128 + 32 + (size_t)4 * G * 2 * 4 + (size_t)4 * G * D * 4 + 64;
   if (lds > 160 * 1024) return hipErrorInvalidValue;
+  const float *k_new = a.kv_new, *v_new = a.kv_new + (size_t)l.n_kv * D;
   if (a.n_seq) {
+    const TqMulti ms{a.slot, l.stride_bytes(), l.stride_words(), 2 * l.n_kv * D};
     if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&attn_tq_partial_kernel<D, G, BITS, QJL, true>), 160 * 1024, attr_set[1]); e != hipSuccess) return e;
-    hipLaunchKernelGGL((attn_tq_partial_kernel<D, G, BITS, QJL, true>), dim3(a.n_kv * a.n_splits, a.n_seq), dim3(256), lds, a.st, a.q, a.kq, a.vq, a.k_new,
-                       a.v_new, a.signs, tq_tables(D, BITS), a.max_seq, a.scale, a.pos, a.n_splits, cap, a.part_ml, a.part_acc, a.qjl_s, a.kx, a.ms);
+    hipLaunchKernelGGL((attn_tq_partial_kernel<D, G, BITS, QJL, true>), dim3(l.n_kv * a.n_splits, a.n_seq), dim3(256), lds, a.st, a.q, kv.k_bytes(), kv.v_bytes(),
+                       k_new, v_new, a.signs, tq_tables(D, BITS), l.max_seq, a.scale, a.pos, a.n_splits, cap, a.part_ml, a.part_acc, a.qjl_s, kv.kx(), ms);
   } else {
     if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&attn_tq_partial_kernel<D, G, BITS, QJL, false>), 160 * 1024, attr_set[0]); e != hipSuccess) return e;
-    hipLaunchKernelGGL((attn_tq_partial_kernel<D, G, BITS, QJL, false>), dim3(a.n_kv * a.n_splits), dim3(256), lds, a.st, a.q, a.kq, a.vq, a.k_new, a.v_new,
-                       a.signs, tq_tables(D, BITS), a.max_seq, a.scale, a.pos, a.n_splits, cap, a.part_ml, a.part_acc, a.qjl_s, a.kx, a.ms);
+    hipLaunchKernelGGL((attn_tq_partial_kernel<D, G, BITS, QJL, false>), dim3(l.n_kv * a.n_splits), dim3(256), lds, a.st, a.q, kv.k_bytes(), kv.v_bytes(), k_new,
+                       v_new, a.signs, tq_tables(D, BITS), l.max_seq, a.scale, a.pos, a.n_splits, cap, a.part_ml, a.part_acc, a.qjl_s, kv.kx(), TqMulti{});
   }
   return hipGetLastError();
 }
 
-static hipError_t attn_tq_dispatch(int bits, uint32_t head_dim, uint32_t g, const TqArgs& a) {
-  return attn_dispatch(head_dim, g, [&](auto d, auto gg) {
+hipError_t attn_tq_split_launch(const KvLayout& l, const KvCache& kv, const AttnDecode& a) {
+  const int bits = l.tq_bits();
+  return attn_dispatch(l.d, a.n_heads / l.n_kv, [&](auto d, auto gg) {
     constexpr int D = decltype(d)::value, G = decltype(gg)::value;
-    if (a.qjl_s) return bits == 2 ? attn_tq_go<D, G, 2, true>(a) : attn_tq_go<D, G, 3, true>(a);
-    return bits == 2 ? attn_tq_go<D, G, 2, false>(a) : attn_tq_go<D, G, 3, false>(a);
+    if (a.qjl_s) return bits == 2 ? attn_tq_go<D, G, 2, true>(l, kv, a) : attn_tq_go<D, G, 3, true>(l, kv, a);
+    return bits == 2 ? attn_tq_go<D, G, 2, false>(l, kv, a) : attn_tq_go<D, G, 3, false>(l, kv, a);
   });
 }
 
-// bits 2 / 3; signs: this layer's [n_kv][2][head_dim]; qjl_s (TurboQuantProd; NULL = TurboQuantMSE): this layer's [n_kv][head_dim][head_dim],
-// kx: its QJL rows [n_kv][max_seq][head_dim / 32 + 1]
-hipError_t attn_tq_launch(int bits, const float* q, uint8_t* kq, uint8_t* vq, const float* k_new, const float* v_new, const float* signs,
-                          uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, uint32_t n_splits,
-                          float* part_ml, float* part_acc, hipStream_t st, const float* qjl_s, uint32_t* kx) {
-  if (n_kv == 0 || n_heads % n_kv || !pos || (bits != 2 && bits != 3) || n_splits == 0 || n_splits > 32 || (qjl_s != nullptr) != (kx != nullptr))
-    return hipErrorInvalidValue;
-  const TqArgs a{q, kq, vq, k_new, v_new, signs, n_kv, max_seq, scale, pos, n_splits, part_ml, part_acc, qjl_s, kx, st, 0, TqMulti{}};
-  return attn_tq_dispatch(bits, head_dim, n_heads / n_kv, a);
-}
-
-// the same for n_seq sequences (grid y): positions pos[s], cache slots slot[s] (code_stride bytes / x_stride words between slots),
-// queries n_heads * head_dim floats apart, the staging (K row, V row) pairs kv_stride floats apart
-hipError_t attn_tq_multi_launch(int bits, const float* q, uint8_t* kq, uint8_t* vq, const float* k_new, const float* v_new, const float* signs,
-                                uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, const int* slot,
-                                uint64_t code_stride, uint64_t x_stride, uint32_t kv_stride, uint32_t n_seq, uint32_t n_splits, float* part_ml,
-                                float* part_acc, hipStream_t st, const float* qjl_s, uint32_t* kx) {
-  if (n_kv == 0 || n_heads % n_kv || !pos || !slot || n_seq == 0 || (bits != 2 && bits != 3) || n_splits == 0 || n_splits > 32 ||
-      (qjl_s != nullptr) != (kx != nullptr))
-    return hipErrorInvalidValue;
-  const TqArgs a{q, kq, vq, k_new, v_new, signs, n_kv, max_seq, scale, pos, n_splits, part_ml, part_acc, qjl_s, kx, st, n_seq,
-                 TqMulti{slot, code_stride, x_stride, kv_stride}};
-  return attn_tq_dispatch(bits, head_dim, n_heads / n_kv, a);
-}
-
-// n_seq 0: single sequence; otherwise grid y = sequences, XQ images xq_stride bytes apart
-hipError_t attn_tq_combine_launch(int bits, const float* part_ml, const float* part_acc, const float* signs, uint32_t n_heads, uint32_t n_kv,
-                                  uint32_t head_dim, uint32_t n_splits, float* out, uint8_t* xq_out, hipStream_t st, uint32_t n_seq,
-                                  uint32_t xq_stride) {
-  if (n_kv == 0 || n_heads % n_kv || n_splits > 32 || (head_dim != 64 && head_dim != 128)) return hipErrorInvalidValue;
-  const TqTables T = tq_tables(head_dim, bits);
-  const uint32_t gk = n_heads / n_kv;
-  if (n_seq) {
-    if (head_dim == 128) hipLaunchKernelGGL((attn_tq_combine_kernel<128, true>), dim3(n_heads, n_seq), dim3(128), 0, st, part_ml, part_acc, signs, T, gk, n_splits, out, xq_out, xq_stride);
-    else hipLaunchKernelGGL((attn_tq_combine_kernel<64, true>), dim3(n_heads, n_seq), dim3(64), 0, st, part_ml, part_acc, signs, T, gk, n_splits, out, xq_out, xq_stride);
+// ... and its merge (attn_merge_launch); sequences' XQ images a.xq_stride bytes apart
+hipError_t attn_tq_merge_launch(const KvLayout& l, const AttnDecode& a) {
+  if (l.d != 64 && l.d != 128) return hipErrorInvalidValue;
+  const TqTables T = tq_tables(l.d, l.tq_bits());
+  const uint32_t gk = a.n_heads / l.n_kv;
+  if (a.n_seq) {
+    if (l.d == 128) hipLaunchKernelGGL((attn_tq_combine_kernel<128, true>), dim3(a.n_heads, a.n_seq), dim3(128), 0, a.st, a.part_ml, a.part_acc, a.signs, T, gk, a.n_splits, a.out, a.xq_out, a.xq_stride);
+    else hipLaunchKernelGGL((attn_tq_combine_kernel<64, true>), dim3(a.n_heads, a.n_seq), dim3(64), 0, a.st, a.part_ml, a.part_acc, a.signs, T, gk, a.n_splits, a.out, a.xq_out, a.xq_stride);
   } else {
-    if (head_dim == 128) hipLaunchKernelGGL((attn_tq_combine_kernel<128, false>), dim3(n_heads), dim3(128), 0, st, part_ml, part_acc, signs, T, gk, n_splits, out, xq_out, 0u);
-    else hipLaunchKernelGGL((attn_tq_combine_kernel<64, false>), dim3(n_heads), dim3(64), 0, st, part_ml, part_acc, signs, T, gk, n_splits, out, xq_out, 0u);
+    if (l.d == 128) hipLaunchKernelGGL((attn_tq_combine_kernel<128, false>), dim3(a.n_heads), dim3(128), 0, a.st, a.part_ml, a.part_acc, a.signs, T, gk, a.n_splits, a.out, a.xq_out, 0u);
+    else hipLaunchKernelGGL((attn_tq_combine_kernel<64, false>), dim3(a.n_heads), dim3(64), 0, a.st, a.part_ml, a.part_acc, a.signs, T, gk, a.n_splits, a.out, a.xq_out, 0u);
   }
   return hipGetLastError();
 }

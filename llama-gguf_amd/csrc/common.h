@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/llama_gguf_hip.h"
+#include "kv_cache.h"
 
 namespace lgh {
 
@@ -234,11 +235,6 @@ hipError_t rope_launch(float* q, float* k, uint32_t n_heads, uint32_t n_kv, uint
 hipError_t embed_multi_launch(int src_type, const uint8_t* table, const int* tokens, float* dst, uint32_t hidden, uint32_t n_seq, uint8_t* xq,
                               const float* xq_nw, float* xq_ssq, uint32_t xq_stride, uint32_t ssq_stride, hipStream_t st);
 hipError_t argmax_multi_launch(const float* logits, uint32_t n, uint32_t n_seq, float* part_val, int* part_idx, int* next, hipStream_t st);
-hipError_t attn_multi_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
-                             uint32_t max_seq, float scale, const int* pos, const int* slot, uint64_t slot_stride, uint32_t n_seq,
-                             uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st);
-hipError_t attn_combine_multi_launch(const float* part_ml, const float* part_acc, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
-                                     uint32_t n_splits, uint32_t n_seq, float* out, uint8_t* xq_out, hipStream_t st);
 // the rest of the per-op Backend surface (misc.hip): op = 0 add, 1 mul, 2 scale, 3 silu, 4 gelu
 hipError_t ewise_launch(int op, const float* a, const float* b, float s, float* out, uint64_t n, hipStream_t st);
 hipError_t softmax_rows_launch(const float* x, float* out, uint32_t rows, uint32_t last_dim, hipStream_t st);
@@ -256,9 +252,29 @@ hipError_t moe_router_launch(const float* x, const float* norm_w, float eps, con
                              uint32_t n_experts, uint32_t top_k, int* sel, float* sel_w, hipStream_t st, uint32_t n_tokens = 1);
 
 // attention
-hipError_t attn_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv,
-                       uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, int kv_len_fixed,
-                       uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st);
+// A split decode-attention step over one layer's cache: everything but the cache.  The cache's format and shape (kv heads, head_dim,
+// max_seq, the distances between two slots' tensors) are the KvLayout's, its tensors the KvCache's.  Host-only, built on the stack.
+struct AttnDecode {
+  uint32_t n_heads;
+  float scale;
+  const float* q;            // [sequence][n_heads][head_dim]
+  const float* kv_new;       // staged formats: the current token's f32 rows [sequence][K row | V row], 2 * n_kv * head_dim floats per
+                             // sequence; the launch compresses and stores them (f32 cache: unused, its rows are in the cache already)
+  const int* pos;            // device: the position of every sequence; nullptr (f32 cache, n_seq 0): kv_len_fixed rows are attended to
+  int kv_len_fixed;
+  const int* slot;           // device: the cache slot of every sequence (n_seq > 0)
+  uint32_t n_seq;            // 0: the cache is one sequence's, no slots, grid y = 1; else grid y = the sequences of a step over cache slots
+  uint32_t n_splits;         // 1 .. 32 ranges of the context, and their partial results
+  float *part_ml, *part_acc;
+  const float *signs, *qjl_s;   // TurboQuant: this layer's [n_kv][k, v][head_dim] rotation signs; QJL formats: its [n_kv][head_dim][head_dim]
+  float* out;                // the merge's outputs: [sequence][n_heads][head_dim], and (optional) wo's input as XQ records, the
+  uint8_t* xq_out;           // sequences' images xq_stride bytes apart
+  uint32_t xq_stride;
+  hipStream_t st;
+};
+// the partial launch for the layout's format (n_splits ranges per kv head -> part_ml / part_acc), and the merge of its partials
+hipError_t attn_split_launch(const KvLayout& l, const KvCache& kv, const AttnDecode& a);
+hipError_t attn_merge_launch(const KvLayout& l, const AttnDecode& a);
 hipError_t attn_direct_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
                               uint32_t max_seq, float scale, const int* pos, float* out, uint8_t* xq_out, hipStream_t st);
 // one workgroup per query head (attention.hip: attn_head_kernel); max_rows: the longest context the caller will launch it at —
@@ -267,28 +283,8 @@ constexpr uint32_t kAttnHeadMaxRows = 16384;
 hipError_t attn_head_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
                             uint32_t max_seq, float scale, const int* pos, uint32_t max_rows, float* out, uint8_t* xq_out, hipStream_t st);
 bool attn_shape_has_fast_kernel(uint32_t head_dim, uint32_t group);
-// decode attention over the int8 KV cache (kv_quantized.rs); k_new / v_new: the current token's f32 rows [n_kv][D]
 // one row through a byte KV format (lgh_model_desc.kv_cache_type 1..3) and back
 hipError_t kv_roundtrip_launch(int fmt, const float* x, uint32_t n, uint8_t* bytes, float* scale_out, float* back, hipStream_t st);
-hipError_t attn_q8_launch(int fmt, const float* q, int8_t* k8, int8_t* v8, float* kscale, float* vscale, const float* k_new, const float* v_new,
-                          uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, uint32_t n_splits,
-                          float* part_ml, float* part_acc, hipStream_t st);
-// ... for the n_seq sequences of a multi-sequence step: caches [slot][n_kv][max_seq][D], scales [slot][n_kv][max_seq], sequence s's staged
-// rows at k_new / v_new + s * x_stride floats, its position pos[s] and slot slot[s] (device words)
-hipError_t attn_q8_multi_launch(int fmt, const float* q, int8_t* k8, int8_t* v8, float* kscale, float* vscale, const float* k_new, const float* v_new,
-                                uint32_t x_stride, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos,
-                                const int* slot, uint32_t n_seq, uint32_t n_splits, float* part_ml, float* part_acc, hipStream_t st);
-// decode attention over the TurboQuant code caches (attention_tq.hip); signs: the layer's [n_kv][2][head_dim]
-hipError_t attn_tq_launch(int bits, const float* q, uint8_t* kq, uint8_t* vq, const float* k_new, const float* v_new, const float* signs,
-                          uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, uint32_t n_splits,
-                          float* part_ml, float* part_acc, hipStream_t st, const float* qjl_s = nullptr, uint32_t* kx = nullptr);
-hipError_t attn_tq_combine_launch(int bits, const float* part_ml, const float* part_acc, const float* signs, uint32_t n_heads, uint32_t n_kv,
-                                  uint32_t head_dim, uint32_t n_splits, float* out, uint8_t* xq_out, hipStream_t st, uint32_t n_seq = 0,
-                                  uint32_t xq_stride = 0);
-hipError_t attn_tq_multi_launch(int bits, const float* q, uint8_t* kq, uint8_t* vq, const float* k_new, const float* v_new, const float* signs,
-                                uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, const int* slot,
-                                uint64_t code_stride, uint64_t x_stride, uint32_t kv_stride, uint32_t n_seq, uint32_t n_splits, float* part_ml,
-                                float* part_acc, hipStream_t st, const float* qjl_s = nullptr, uint32_t* kx = nullptr);
 hipError_t tq_compress_launch(int bits, const float* x, uint32_t dim, const float* signs, uint8_t* out, hipStream_t st, const float* qjl_s = nullptr,
                               uint32_t* qjl_out = nullptr);
 uint32_t tq_row_bytes_host(int bits, uint32_t d);
@@ -303,8 +299,6 @@ hipError_t attn_decode_any_launch(const float* q, const float* kcache, const flo
                                   uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, hipStream_t st);
 hipError_t attn_generic_launch(const float* q, const float* k, const float* v, float* out, uint32_t n_heads, uint32_t n_kv, uint32_t seq_len,
                                uint32_t kv_len, uint32_t kv_rows, uint32_t d, float scale, hipStream_t st);
-hipError_t attn_combine_launch(const float* part_ml, const float* part_acc, uint32_t n_heads, uint32_t n_kv,
-                               uint32_t head_dim, uint32_t n_splits, float* out, uint8_t* xq_out, hipStream_t st);
 
 // The opt-in to more than 64 KB of dynamic LDS is per kernel AND per device: `done` is that kernel's per-device record
 // (a process may drive several GPUs: two stage contexts, a test creating contexts on different devices).

@@ -186,8 +186,16 @@ int build_mv_group(lgh_ctx* c, const SegSpec* specs, int nseg, const float* norm
                    uint32_t& threads, uint64_t& alg, uint32_t tile_cap);
 int qkv_forward(lgh_ctx* c, lgh::LayerW& Lw, const AttnView& v);   // norm -> q, k, v -> RoPE -> cache write (or kv_tmp, staged formats)
 // attention over layer li's cache into v.attn_out, by the context's path (cache type, attn_generic, attn_direct, n_splits); xq_out: also
-// leave attn_out's XQ image, where the path's last launch can write one
+// leave attn_out's XQ image, where the path's last launch can write one.  One function behind this and attention_forward_multi
+// (engine_layer.hip: attention_step): the split paths build an AttnDecode for attn_split_launch / attn_merge_launch
 int attention_forward(lgh_ctx* c, lgh::LayerW& Lw, uint32_t li, const AttnView& v, float scale, bool xq_out);
+// layer li's TurboQuant inputs: its rotation signs [kv head][k, v][head_dim] and, for the QJL formats (else nullptr), its projection
+// matrices [kv head][head_dim][head_dim]
+struct TqLayer { const float *signs, *qjl_s; };
+inline TqLayer tq_layer(const lgh_ctx* c, uint32_t li) {
+  const size_t kd = (size_t)(li - c->l0) * c->d.num_kv_heads * c->d.head_dim;
+  return {c->tq_signs + kd * 2, c->kvl.qjl() ? c->tq_qjl + kd * c->d.head_dim : nullptr};
+}
 int ffn_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma);
 int ffn_gateup_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v);   // the dense FFN up to v.act (gate | up + SwiGLU), no down projection
 int embed_forward(lgh_ctx* c);   // the token's embedding row into c->hidden, the position advanced
@@ -223,7 +231,9 @@ inline lgh::KvCache kv_of(const lgh_ctx* c, uint32_t li, int slot) {
 int batch_scratch_alloc(lgh_ctx* c, uint32_t max_batch);
 // the step of a layer over the batch scratch (c->batch), one function each, shared by enqueue_multi and the per-launch entry points
 int qkv_forward_multi(lgh_ctx* c, lgh::LayerW& Lw, uint32_t li, uint32_t n_seq);
-int attention_forward_multi(lgh_ctx* c, uint32_t li, uint32_t n_seq, float scale, bool xq_out);   // Bs.q -> Bs.attn_out (+ its images)
+int attention_forward_multi(lgh_ctx* c, uint32_t li, uint32_t n_seq, float scale, bool xq_out);   // Bs.q -> Bs.attn_out (+ its images); engine_layer.hip
+// a launch left the images of n vectors of k floats from `base` on, multiplied with the norm weights `tag` (nullptr: none)
+void mark_fresh(lgh_ctx* c, const float* base, uint32_t k, uint32_t n, const float* tag);
 int linear_multi(lgh_ctx* c, int cls, const lgh::DevWeight& W, const lgh::DevWeight* W_up, const float* x, float* out, uint32_t out_stride,
                  uint32_t n_seq, const float* norm_w, const float* resid = nullptr, const float* bias = nullptr, int xq_next = 0,
                  const float* xq_next_nw = nullptr, const MvIndirect ind = MvIndirect{});

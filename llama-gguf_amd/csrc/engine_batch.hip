@@ -50,8 +50,7 @@ int register_views(lgh_ctx* c, float* f32, uint8_t* xq, float* ssq, uint32_t k, 
   return LGH_OK;
 }
 
-// a launch left the images of n vectors of k floats from `base` on, multiplied with the norm weights `tag` (nullptr: none)
-static void mark_fresh(lgh_ctx* c, const float* base, uint32_t k, uint32_t n, const float* tag) {
+void mark_fresh(lgh_ctx* c, const float* base, uint32_t k, uint32_t n, const float* tag) {
   for (uint32_t s = 0; s < n; s++)
     if (XqBuf* q = xq_find(c, base + (size_t)s * k)) { q->fresh = true; q->tag = tag; }
 }
@@ -197,61 +196,6 @@ int moe_grouped_forward(lgh_ctx* c, LayerW& Lw, uint32_t n_seq, const float* nex
        })))
     return rc;
   mark_fresh(c, Bs.hidden, H, n_seq, next_nw);
-  return LGH_OK;
-}
-
-// attention_cached per sequence (ops.rs:1479-1537) over layer li's cache slots, whatever their format: split + merge, the sequence as
-// the grid's second dimension, Bs.q -> Bs.attn_out.  The one place that knows which of the layout's strides goes to which launcher.
-// xq_out: the merge also leaves every sequence's XQ image of attn_out for wo (where its views are registered)
-int attention_forward_multi(lgh_ctx* c, uint32_t li, uint32_t n_seq, float scale, bool xq_out) {
-  BatchScratch& Bs = c->batch;
-  const lgh_model_desc& d = c->d;
-  const KvLayout& kvl = c->kvl;
-  const KvCache& kv = Bs.kv[li];
-  const uint32_t QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim;
-  int rc;
-  XqBuf* const qa = xq_out ? xq_find(c, Bs.attn_out) : nullptr;
-  uint8_t* const img = qa ? qa->xq : nullptr;
-  if (kvl.tq()) {
-    // TurboQuantKVCache (kv_turboquant.rs) per sequence: write_kv + attention over the slot's codes; the merge inverts the V rotation
-    const int bits = kvl.tq_bits();
-    const bool qjl = kvl.qjl();
-    const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
-    const float* qjl_s = qjl ? c->tq_qjl + (size_t)(li - c->l0) * d.num_kv_heads * d.head_dim * d.head_dim : nullptr;
-    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-           return attn_tq_multi_launch(bits, Bs.q, kv.k_bytes(), kv.v_bytes(), Bs.kv_tmp, Bs.kv_tmp + KD, signs, d.num_heads, d.num_kv_heads, d.head_dim,
-                                       d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, kvl.stride_bytes(), kvl.stride_words(), 2 * KD, n_seq, c->n_splits, Bs.part_ml,
-                                       Bs.part_acc, c->stream, qjl_s, qjl ? kv.kx() : nullptr);
-         })))
-      return rc;
-    rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
-      return attn_tq_combine_launch(bits, Bs.part_ml, Bs.part_acc, signs, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, Bs.attn_out, img,
-                                    c->stream, n_seq, (uint32_t)xq_stride_of(QD));
-    });
-  } else {
-    if (kvl.staged()) {
-      // QuantizedKVCache (kv_quantized.rs) per sequence: the launch quantizes and stores each sequence's staged rows into its slot; the
-      // partials merge as f32 ones do (as in the single-sequence engine)
-      rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-        return attn_q8_multi_launch((int)d.kv_cache_type, Bs.q, kv.k_i8(), kv.v_i8(), kv.kscale(), kv.vscale(), Bs.kv_tmp,
-                                    Bs.kv_tmp + KD, 2 * KD, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot, n_seq,
-                                    c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
-      });
-    } else {
-      rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, 0, [&] {
-        return attn_multi_launch(Bs.q, kv.k_f32(), kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, Bs.d_pos, Bs.d_slot,
-                                 kvl.stride_floats(), n_seq, c->n_splits, Bs.part_ml, Bs.part_acc, c->stream);
-      });
-    }
-    if (rc) return rc;
-    rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
-      return attn_combine_multi_launch(Bs.part_ml, Bs.part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, n_seq, Bs.attn_out, img, c->stream);
-    });
-  }
-  if (rc) return rc;
-  if (img) mark_fresh(c, Bs.attn_out, QD, n_seq, nullptr);
-  else
-    for (uint32_t s = 0; s < n_seq; s++) xq_stale(c, Bs.attn_out + (size_t)s * QD);
   return LGH_OK;
 }
 

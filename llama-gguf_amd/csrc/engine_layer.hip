@@ -1,6 +1,7 @@
 // engine_layer.hip — the per-token launch sequence of the single-sequence engine: one transformer layer as three steps on views of
 // one sequence's vectors (qkv_forward, attention_forward, ffn_forward; the per-op test entry points of ops_api.hip run these same
-// functions), and everything one token needs around the layers (enqueue_token).
+// functions), and everything one token needs around the layers (enqueue_token).  The attention step is the multi-sequence engine's
+// too (attention_forward_multi: the same function over the batch scratch).
 #include "engine.h"
 #include "xq.h"
 
@@ -153,80 +154,94 @@ int qkv_forward(lgh_ctx* c, LayerW& Lw, const AttnView& v) {
   });
 }
 
-// attention_cached (ops.rs:1479-1537) over the layer's cache, whatever its format: one branch per path, each ending in the launch
-// that writes attn_out — and, where that launch can and the caller asks, wo's input as XQ straight from it
-int attention_forward(lgh_ctx* c, LayerW& Lw, uint32_t li, const AttnView& v, float scale, bool xq_out) {
+// Where a decode-attention step's vectors live: the context's own sequence (n_seq 0: an AttnView, the context's partials and position
+// word, the layer's cache) or the n_seq sequences of a multi-sequence step side by side in the batch scratch, over the layer's slots
+struct AttnStep {
+  const float *q, *kv_new;
+  float *out, *part_ml, *part_acc;
+  const int *pos, *slot;
+  const KvCache& kv;
+  uint32_t n_seq;
+};
+static AttnStep attn_step_own(const lgh_ctx* c, const LayerW& Lw, const AttnView& v) {
+  return {v.q, v.kv_tmp, v.attn_out, c->part_ml, c->part_acc, c->state + ST_POS, nullptr, Lw.kv, 0};
+}
+static AttnStep attn_step_batch(const lgh_ctx* c, uint32_t li, uint32_t n_seq) {
+  const BatchScratch& Bs = c->batch;
+  return {Bs.q, Bs.kv_tmp, Bs.attn_out, Bs.part_ml, Bs.part_acc, Bs.d_pos, Bs.d_slot, Bs.kv[li], n_seq};
+}
+
+// wo's input as XQ records, where the caller asks for it: the image the step's last launch writes.  Own sequence: the output's image,
+// registered at first use; batch: sequence 0's registered view, the others' follow at xq_stride_of (nullptr: no views, no image)
+static XqBuf* attn_image(lgh_ctx* c, const AttnStep& s, bool xq_out) {
+  if (!xq_out) return nullptr;
+  return s.n_seq ? xq_find(c, s.out) : xq_get(c, s.out, c->d.num_heads * c->d.head_dim);
+}
+// ... and the registry after the step: the image(s) fresh with no norm weights in them, or the output's image(s) stale
+static void attn_image_done(lgh_ctx* c, const AttnStep& s, XqBuf* qa) {
+  const uint32_t QD = c->d.num_heads * c->d.head_dim;
+  if (s.n_seq && qa) return mark_fresh(c, s.out, QD, s.n_seq, nullptr);
+  if (qa) { qa->fresh = true; qa->tag = nullptr; }
+  else
+    for (uint32_t i = 0; i < std::max(s.n_seq, 1u); i++) xq_stale(c, s.out + (size_t)i * QD);
+}
+
+// attention_cached (ops.rs:1479-1537) over layer li's cache, whatever its format and for either engine: one branch per path, each ending
+// in the launch that writes the output — and, where that launch can and the caller asks, wo's input as XQ straight from it
+static int attention_step(lgh_ctx* c, uint32_t li, const AttnStep& s, float scale, bool xq_out) {
   const lgh_model_desc& d = c->d;
   int rc;
   const KvLayout& kvl = c->kvl;
-  const KvCache& kv = Lw.kv;
-  const float* const k_new = v.kv_tmp;                                                     // (staged formats only)
-  const float* const v_new = k_new ? k_new + (size_t)d.num_kv_heads * d.head_dim : nullptr;
-  const int* const pos = c->state + ST_POS;
-  const uint64_t kv_bytes = kvl.launch_bytes(c->pos + 1);
+  const uint64_t kv_bytes = s.n_seq ? 0 : kvl.launch_bytes(c->pos + 1);
+  const bool one_launch = !s.n_seq && kvl.f32();   // the context's own f32 cache: the paths of one launch, by the context's fields
   XqBuf* qa = nullptr;
-  auto image = [&]() -> uint8_t* {
-    qa = xq_out ? xq_get(c, v.attn_out, d.num_heads * d.head_dim) : nullptr;
-    return qa ? qa->xq : nullptr;
-  };
-  auto merge = [&](uint8_t* img) {
-    return run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
-      return attn_combine_launch(c->part_ml, c->part_acc, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, v.attn_out, img, c->stream);
-    });
-  };
-  if (kvl.tq()) {
-    // TurboQuantKVCache (kv_turboquant.rs): write_kv + attention_layer over the codes; the merge also inverts the V rotation
-    const int bits = kvl.tq_bits();
-    const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
-    const bool qjl = kvl.qjl();
-    const float* qjl_s = qjl ? c->tq_qjl + (size_t)(li - c->l0) * d.num_kv_heads * d.head_dim * d.head_dim : nullptr;
-    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-           return attn_tq_launch(bits, v.q, kv.k_bytes(), kv.v_bytes(), k_new, v_new, signs, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len,
-                                 scale, pos, c->n_splits, c->part_ml, c->part_acc, c->stream, qjl_s, qjl ? kv.kx() : nullptr);
-         })))
-      return rc;
-    uint8_t* const img = image();
-    rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] {
-      return attn_tq_combine_launch(bits, c->part_ml, c->part_acc, signs, d.num_heads, d.num_kv_heads, d.head_dim, c->n_splits, v.attn_out, img, c->stream);
-    });
-  } else if (kvl.staged()) {
-    // int8 rows + scales (kv_quantized.rs); the launch also quantizes and stores the current token's rows
-    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-           return attn_q8_launch((int)d.kv_cache_type, v.q, kv.k_i8(), kv.v_i8(), kv.kscale(), kv.vscale(), k_new, v_new, d.num_heads, d.num_kv_heads, d.head_dim,
-                                 d.max_seq_len, scale, pos, c->n_splits, c->part_ml, c->part_acc, c->stream);
-         })))
-      return rc;
-    rc = merge(image());
-  } else if (c->attn_generic) {   // any head size / group size: f32 out, no image
+  if (one_launch && c->attn_generic) {   // any head size / group size: f32 out, no image
     rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-      return attn_decode_any_launch(v.q, kv.k_f32(), kv.v_f32(), v.attn_out, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, c->stream);
+      return attn_decode_any_launch(s.q, s.kv.k_f32(), s.kv.v_f32(), s.out, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, s.pos, c->stream);
     });
-  } else if (c->attn_direct == ATTN_VAR_HEAD) {   // contexts up to direct_attn_max_kv rows: one launch, a workgroup per query head
+  } else if (one_launch && c->attn_direct == ATTN_VAR_HEAD) {   // contexts up to direct_attn_max_kv rows: one launch, a workgroup per query head
     if (c->pos + 1 > c->direct_attn_max_kv)   // (the kernel's LDS arrays end there: it would attend to a truncated context)
       return fail(c, LGH_INVALID_ARGUMENT, "single-launch attention at position " + std::to_string(c->pos) + " past its " +
                                                std::to_string(c->direct_attn_max_kv) + " rows");
-    uint8_t* const img = image();
+    qa = attn_image(c, s, xq_out);
     rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-      return attn_head_launch(v.q, kv.k_f32(), kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, c->direct_attn_max_kv,
-                              v.attn_out, img, c->stream);
+      return attn_head_launch(s.q, s.kv.k_f32(), s.kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, s.pos, c->direct_attn_max_kv,
+                              s.out, qa ? qa->xq : nullptr, c->stream);
     });
-  } else if (c->attn_direct == ATTN_VAR_DIRECT) {   // one launch, a workgroup per kv head
-    uint8_t* const img = image();
+  } else if (one_launch && c->attn_direct == ATTN_VAR_DIRECT) {   // one launch, a workgroup per kv head
+    qa = attn_image(c, s, xq_out);
     rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-      return attn_direct_launch(v.q, kv.k_f32(), kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, v.attn_out, img, c->stream);
+      return attn_direct_launch(s.q, s.kv.k_f32(), s.kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, s.pos, s.out,
+                                qa ? qa->xq : nullptr, c->stream);
     });
-  } else {                        // n_splits ranges of the context, then their merge
-    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-           return attn_launch(v.q, kv.k_f32(), kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos, 0, c->n_splits, c->part_ml,
-                              c->part_acc, c->stream);
-         })))
-      return rc;
-    rc = merge(image());
+  } else {
+    // n_splits ranges of the context, then their merge.  The launchers take the format from the layout: the staged formats' partial
+    // launch also compresses and stores the current token's rows (kv_quantized.rs, kv_turboquant.rs write_kv), the TurboQuant merge also
+    // inverts the V rotation
+    AttnDecode a{};
+    a.n_heads = d.num_heads; a.scale = scale;
+    a.q = s.q; a.kv_new = s.kv_new;
+    a.pos = s.pos; a.slot = s.slot; a.n_seq = s.n_seq;
+    a.n_splits = c->n_splits; a.part_ml = s.part_ml; a.part_acc = s.part_acc;
+    if (kvl.tq()) { const TqLayer t = tq_layer(c, li); a.signs = t.signs; a.qjl_s = t.qjl_s; }
+    a.out = s.out;
+    a.st = c->stream;
+    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] { return attn_split_launch(kvl, s.kv, a); }))) return rc;
+    qa = attn_image(c, s, xq_out);
+    a.xq_out = qa ? qa->xq : nullptr;
+    a.xq_stride = s.n_seq ? xq_stride_of(d.num_heads * d.head_dim) : 0;
+    rc = run_k(c, LGH_K_ATTN_COMBINE, LGH_SYM_ATTN_COMBINE, 0, [&] { return attn_merge_launch(kvl, a); });
   }
   if (rc) return rc;
-  if (qa) { qa->fresh = true; qa->tag = nullptr; }
-  else xq_stale(c, v.attn_out);
+  attn_image_done(c, s, qa);
   return LGH_OK;
+}
+
+int attention_forward(lgh_ctx* c, LayerW& Lw, uint32_t li, const AttnView& v, float scale, bool xq_out) {
+  return attention_step(c, li, attn_step_own(c, Lw, v), scale, xq_out);
+}
+int attention_forward_multi(lgh_ctx* c, uint32_t li, uint32_t n_seq, float scale, bool xq_out) {
+  return attention_step(c, li, attn_step_batch(c, li, n_seq), scale, xq_out);
 }
 
 // ------------------------------------------------------------------------------------------------

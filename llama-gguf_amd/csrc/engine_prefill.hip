@@ -114,9 +114,8 @@ int pf_qkv_step(lgh_ctx* c, LayerW& L, float* kcache, float* vcache, uint32_t po
 static int pf_tq_rows(lgh_ctx* c, LayerW& L, uint32_t li, uint32_t pos0, uint32_t m, bool attend) {
   PfScratch& P = c->pf;
   const lgh_model_desc& d = c->d;
-  const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
   float* const vscr = P.tq_kv + c->kvl.stride_floats();
-  return pf_k(c, tq_pf_rows_launch(c->kvl.tq_bits(), P.tq_kv, vscr, L.kv.k_bytes(), L.kv.v_bytes(), attend ? P.q : nullptr, signs, d.num_heads,
+  return pf_k(c, tq_pf_rows_launch(c->kvl.tq_bits(), P.tq_kv, vscr, L.kv.k_bytes(), L.kv.v_bytes(), attend ? P.q : nullptr, tq_layer(c, li).signs, d.num_heads,
                                    d.num_kv_heads, d.head_dim, d.max_seq_len, pos0, m, attend ? m : 0, attend ? pos0 : 0, c->stream),
               "TurboQuant rows");
 }
@@ -238,8 +237,8 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
     if (tq && (rc = pf_tq_rows(c, L, li, pos0, m, attend))) return rc;
     if (!attend) break;
     if (tq) {
-      const float* signs = c->tq_signs + (size_t)(li - c->l0) * d.num_kv_heads * 2 * d.head_dim;
-      rc = pf_k(c, attn_prefill_tq_launch(P.q, kcache, vcache, signs, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
+      rc = pf_k(c, attn_prefill_tq_launch(P.q, kcache, vcache, tq_layer(c, li).signs, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m,
+                                          P.xh_attn, st),
                 "attention");
     } else {
       rc = pf_k(c, attn_prefill_launch(P.q, kcache, vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),

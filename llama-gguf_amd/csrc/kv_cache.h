@@ -45,8 +45,9 @@ struct KvLayout {
   size_t slot_bytes(int kind) const { return rows() * pos_bytes(kind); }
   size_t slot_bytes() const { return rows() * (2 * (row_bytes() + scale_bytes()) + qjl_bytes()); }
 
-  // the distance between two slots' tensors, in the units the launchers take: floats (MvBatch::cache_stride, attn_multi_launch; the
-  // multi-sequence mat-vec carries it whatever the format), code bytes and QJL words (attn_tq_multi_launch; the words for every TQ format)
+  // the distance between two slots' tensors, in the units the kernels take: floats (MvBatch::cache_stride — the multi-sequence mat-vec
+  // carries it whatever the format — and the f32 attention), code bytes and QJL words (the TurboQuant attention; the words for every TQ
+  // format).  attn_split_launch (common.h) reads them here; no caller passes a stride
   uint64_t stride_floats() const { return (uint64_t)rows() * d; }
   uint64_t stride_bytes() const { return staged() ? (uint64_t)rows() * row_bytes() : 0; }
   uint64_t stride_words() const { return tq() ? (uint64_t)rows() * (d / 32 + 1) : 0; }

@@ -208,6 +208,25 @@ int lgh_op_rope(int device, float* q, float* k, size_t n_heads, size_t n_kv, siz
   return t.down(k, dk, n_kv * d);
 }
 
+// Split + merge over an f32 cache of max_seq rows per kv head with the first kv_len of them attended to, the length given by the host
+// (no position word): the statuses lgh_op_attention_cached and lgh_op_attention always answered — a refused partial launch Unsupported, a
+// refused merge (in particular more than 32 splits, which only the merge used to refuse) OperationFailed
+static int attn_fixed_len(hipStream_t st, const float* q, float* kc, float* vc, size_t n_heads, size_t n_kv, size_t d, size_t max_seq, float scale,
+                          size_t kv_len, int n_splits, float* pml, float* pacc, float* out) {
+  if (n_splits > 32) return LGH_OPERATION_FAILED;
+  const KvLayout l(LGH_KV_F32, n_kv, max_seq, d);
+  KvCache kv;
+  kv.t[KV_K] = kc; kv.t[KV_V] = vc;
+  AttnDecode a{};
+  a.n_heads = (uint32_t)n_heads; a.scale = scale;
+  a.q = q; a.kv_len_fixed = (int)kv_len;
+  a.n_splits = (uint32_t)n_splits; a.part_ml = pml; a.part_acc = pacc;
+  a.out = out;
+  a.st = st;
+  if (attn_split_launch(l, kv, a) != hipSuccess) return LGH_UNSUPPORTED;
+  return attn_merge_launch(l, a) == hipSuccess ? LGH_OK : LGH_OPERATION_FAILED;
+}
+
 int lgh_op_attention_cached(int device, const float* q, const float* kc, const float* vc, float* out, size_t n_heads,
                             size_t n_kv, size_t d, size_t max_seq, float scale, size_t kv_len, int n_splits) {
   Tmp t(device);
@@ -224,11 +243,7 @@ int lgh_op_attention_cached(int device, const float* q, const float* kc, const f
       return LGH_UNSUPPORTED;
     return t.down(out, dout, n_heads * d);
   }
-  if (attn_launch(dq, dk, dv, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, scale, nullptr, (int)kv_len,
-                  (uint32_t)n_splits, pml, pacc, t.c->stream) != hipSuccess)
-    return LGH_UNSUPPORTED;
-  if (attn_combine_launch(pml, pacc, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)n_splits, dout, nullptr, t.c->stream) != hipSuccess)
-    return LGH_OPERATION_FAILED;
+  if (int rc = attn_fixed_len(t.c->stream, dq, dk, dv, n_heads, n_kv, d, max_seq, scale, kv_len, n_splits, pml, pacc, dout)) return rc;
   return t.down(out, dout, n_heads * d);
 }
 
@@ -395,11 +410,7 @@ int lgh_op_attention(int device, const float* q, const float* k, const float* v,
     const size_t q_abs = (kv_len >= seq_len ? kv_len - seq_len : 0) + s;   // saturating_sub (ops.rs:1411)
     const size_t visible = q_abs + 1 < kv_len ? q_abs + 1 : kv_len;
     if (hipMemcpy2DAsync(qs, d * 4, dq + s * d, seq_len * d * 4, d * 4, n_heads, hipMemcpyDeviceToDevice, st) != hipSuccess) return LGH_OPERATION_FAILED;
-    if (attn_launch(qs, dk, dv, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)kv_len, scale, nullptr, (int)visible,
-                    (uint32_t)n_splits, pml, pacc, st) != hipSuccess)
-      return LGH_UNSUPPORTED;
-    if (attn_combine_launch(pml, pacc, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)n_splits, os, nullptr, st) != hipSuccess)
-      return LGH_OPERATION_FAILED;
+    if (int rc = attn_fixed_len(st, qs, dk, dv, n_heads, n_kv, d, kv_len, scale, visible, n_splits, pml, pacc, os)) return rc;
     if (hipMemcpy2DAsync(dout + s * d, seq_len * d * 4, os, d * 4, d * 4, n_heads, hipMemcpyDeviceToDevice, st) != hipSuccess) return LGH_OPERATION_FAILED;
   }
   return t.down(out, dout, n_heads * seq_len * d);
@@ -409,7 +420,7 @@ int lgh_op_attention(int device, const float* q, const float* k, const float* v,
 // holds each to a float64 restatement).  The bare context's fields select the path as a real context's do; the caches come from the
 // host, the position through the device word the engine's kernels read (state[ST_POS]); nothing falls back to another kernel: a
 // shape the path has no kernel for answers LGH_UNSUPPORTED.  The *_multi entry points do the same with the multi-sequence step's
-// attention (engine_batch.hip: attention_forward_multi) on the batch scratch of a bare context (attn_multi_setup). ----
+// attention (engine_layer.hip: attention_forward_multi) on the batch scratch of a bare context (attn_multi_setup). ----
 }  // extern "C"
 
 namespace {
@@ -612,7 +623,7 @@ int lgh_op_attention_decode(int device, int path, const float* q, const float* k
   if (!v.q || !v.attn_out) return LGH_ALLOCATION_FAILED;
   int rc;
   if ((rc = attn_setup(t, LGH_KV_F32, n_heads, n_kv, head_dim, max_seq, path == 0 ? n_splits : 0)) || (rc = set_pos(t, pos))) return rc;
-  // 0: split + merge (attn_launch picks 4 or 8 waves from max_seq); 1: one launch (engine: pos + 1 <= direct_attn_max_kv); 2: the
+  // 0: split + merge (attn_split_launch picks 4 or 8 waves from max_seq); 1: one launch (engine: pos + 1 <= direct_attn_max_kv); 2: the
   // kernel of the shapes the others do not cover (engine: every token of such a model), here on any head_dim / group size; 3: one launch,
   // a workgroup per query head (engine: pos + 1 <= direct_attn_max_kv)
   t.c->attn_direct = path == 1 ? ATTN_VAR_DIRECT : path == 3 ? ATTN_VAR_HEAD : ATTN_VAR_SPLIT;
@@ -625,7 +636,7 @@ int lgh_op_attention_decode(int device, int path, const float* q, const float* k
 int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads, size_t n_kv,
                                   size_t head_dim, size_t max_seq, size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale,
                                   int n_splits, uint8_t* image_out) {
-  // the multi-sequence decode step's attention (engine_batch.hip: attention_forward_multi) over f32 cache slots
+  // the multi-sequence decode step's attention (engine_layer.hip: attention_forward_multi) over f32 cache slots
   Tmp t(device);
   if (t.rc) return t.rc;
   if (!q || !k_cache || !v_cache || !out || !pos || !slot || n_kv == 0 || n_heads % n_kv || head_dim == 0 || max_seq == 0 || max_seq > 0x7FFFFFFFu ||
@@ -659,7 +670,7 @@ int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int
 int lgh_op_attention_kv8_multi(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
                                const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq,
                                size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale, int n_splits, uint8_t* image_out) {
-  // the multi-sequence decode step's attention (engine_batch.hip: attention_forward_multi) over byte-cache slots
+  // the multi-sequence decode step's attention (engine_layer.hip: attention_forward_multi) over byte-cache slots
   Tmp t(device);
   if (t.rc) return t.rc;
   if (kv_cache_type < LGH_KV_INT8 || kv_cache_type > LGH_KV_FP8_E5M2) return LGH_UNSUPPORTED;
@@ -704,7 +715,7 @@ int lgh_op_attention_tq_multi(int device, uint32_t kv_cache_type, const float* q
                               const float* k_new, const float* v_new, const float* signs, const float* qjl_matrices, float* out, size_t n_heads,
                               size_t n_kv, size_t head_dim, size_t max_seq, size_t n_slots, size_t n_seq, const int* pos, const int* slot, float scale,
                               int n_splits, uint8_t* image_out) {
-  // the multi-sequence decode step's attention (engine_batch.hip: attention_forward_multi) over TurboQuant cache slots
+  // the multi-sequence decode step's attention (engine_layer.hip: attention_forward_multi) over TurboQuant cache slots
   Tmp t(device);
   if (t.rc) return t.rc;
   const KvLayout l(kv_cache_type, n_kv, max_seq, head_dim);
