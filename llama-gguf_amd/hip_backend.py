@@ -831,7 +831,12 @@ class HipPipeline:
         self.vocab_size = 0
 
     @classmethod
-    def from_model(cls, model, max_seq_len: int, n_stages: int, devices: Optional[Sequence[int]] = None, flags: int = 0) -> "HipPipeline":
+    def from_model(cls, model, max_seq_len: int, n_stages: int, devices: Optional[Sequence[int]] = None, flags: int = 0,
+                   attn_direct: int = 0) -> "HipPipeline":
+        """`attn_direct` as in HipGpuInference.from_model (64-row units, 0 = tuned default, 255 = never), for every stage; the same
+        selector is bits 16..23 of `flags`: give one of the two."""
+        if attn_direct and flags & (0xFF << 16):
+            raise ValueError("attn_direct and bits 16..23 of flags are the same selector: give one")
         L = load_library()
         self = cls()
         cfg = model.config
@@ -843,7 +848,7 @@ class HipPipeline:
         d.max_seq_len = int(max_seq_len)
         d.use_neox_rope = int(cfg.use_neox_rope)
         d.norm_eps, d.rope_freq_base, d.rope_freq_scale = cfg.norm_eps, cfg.rope_freq_base, cfg.rope_freq_scale
-        d.device_id, d.flags = 0, flags
+        d.device_id, d.flags = 0, flags | ((attn_direct & 0xFF) << 16)
         devs = (C.c_int * n_stages)(*devices) if devices is not None else None
         _chk(L.lgh_pipeline_create(C.byref(d), devs, n_stages, C.byref(self._h)), "lgh_pipeline_create (is a HIP device visible?)")
         self.config, self.vocab_size, self.hidden_size = cfg, cfg.vocab_size, cfg.hidden_size
@@ -912,8 +917,12 @@ class HipTensorParallel:
 
     @classmethod
     def from_model(cls, model, max_seq_len: int, n_ranks: int, devices: Optional[Sequence[int]] = None, flags: int = 0,
-                   kv_cache_type: int = 0, layer_range: Optional[Sequence[int]] = None) -> "HipTensorParallel":
-        """`kv_cache_type` / `layer_range` exist to be refused: tensor parallelism runs whole models over the f32 cache."""
+                   kv_cache_type: int = 0, layer_range: Optional[Sequence[int]] = None, attn_direct: int = 0) -> "HipTensorParallel":
+        """`kv_cache_type` / `layer_range` exist to be refused: tensor parallelism runs whole models over the f32 cache.
+        `attn_direct` as in HipGpuInference.from_model (64-row units, 0 = tuned default, 255 = never), for every rank; the same selector
+        is bits 16..23 of `flags`: give one of the two."""
+        if attn_direct and flags & (0xFF << 16):
+            raise ValueError("attn_direct and bits 16..23 of flags are the same selector: give one")
         L = load_library()
         self = cls()
         cfg = model.config
@@ -925,7 +934,7 @@ class HipTensorParallel:
         d.max_seq_len = int(max_seq_len)
         d.use_neox_rope = int(cfg.use_neox_rope)
         d.norm_eps, d.rope_freq_base, d.rope_freq_scale = cfg.norm_eps, cfg.rope_freq_base, cfg.rope_freq_scale
-        d.device_id, d.flags, d.kv_cache_type = 0, flags, int(kv_cache_type)
+        d.device_id, d.flags, d.kv_cache_type = 0, flags | ((attn_direct & 0xFF) << 16), int(kv_cache_type)
         if layer_range is not None:
             d.layer_begin, d.layer_end = layer_range
         if devices is not None and len(devices) != n_ranks:

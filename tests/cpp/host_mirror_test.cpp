@@ -59,7 +59,7 @@ int main() {
     catch (const BackendError& e) { std::printf("error-variant %s\n", e.variant().c_str()); }
     // the device side of BatchedEngine through the mirror: two slots with different histories; slot 1 replays the single-sequence
     // run above token by token (slot 0 joins late, through the batched prompt path), so its logits equal the first line printed
-    // above (to rounding: below 64 rows the single-sequence engine uses its one-launch attention, another summation tree)
+    // above (to rounding: up to 256 rows the single-sequence engine uses its one-launch attention, another summation tree)
     HipGpuInference& g = model.gpu();
     g.batch_create(2);
     for (uint32_t t : {3u, 17u, 255u, 9u}) g.forward_multi({1}, {t});

@@ -222,3 +222,69 @@ def cold_tensor_parallel(pkg):
             tp.close()
     assert out["cold"].pop("graph_nodes") > 0 and out["eager"].pop("graph_nodes") == 0
     return out
+
+
+# ---- cold captures of BOTH decode-attention graphs (tests/switch_scenarios.py: the head form up to S rows, splits + merge beyond)
+def cold_switch_single(pkg):
+    """attn_direct=1 (the switch at 64 rows): 60 tokens through prefill_token, decode_greedy over 10 steps (positions 60 .. 69: the
+    head graph is captured cold, then the split graph, inside one call), then one forward (the MODE_FORWARD split graph)."""
+    import switch_scenarios as sw
+    hb = pkg.hip_backend
+    name, mix = sw.MAIN
+    cfg = pkg.make_config(name, max_seq_len=sw.MAX_SEQ)
+    model = pkg.SynthModel(cfg, mix=mix)
+    V = cfg.vocab_size
+    out = {}
+    for key, flags in (("cold", 0), ("eager", hb.FLAG_NO_GRAPH)):
+        eng = pkg.HipGpuInference.from_model(model, sw.MAX_SEQ, flags=flags | hb.FLAG_EXACT_PREFILL, attn_direct=sw.ATTN_DIRECT)
+        try:
+            (toks, logits), _ = sw.run(eng, sw.SCENARIOS["cold_switch"][1], V)
+            assert np.isfinite(logits).all() and eng.position() == 71
+            out[key] = {"tokens": toks, "logits": [_digest(logits)]}
+        finally:
+            eng.close()
+    return out
+
+
+def cold_split_first(pkg):
+    """A default engine (the switch at 256 rows): forward_batch of 257 tokens, then decode_greedy over 4 steps — the split graph is
+    captured cold and the head graph never."""
+    import switch_scenarios as sw
+    hb = pkg.hip_backend
+    name, mix = sw.MAIN
+    cfg = pkg.make_config(name, max_seq_len=sw.DEFAULT_MAX_SEQ)
+    model = pkg.SynthModel(cfg, mix=mix)
+    V = cfg.vocab_size
+    out = {}
+    for key, flags in (("cold", 0), ("eager", hb.FLAG_NO_GRAPH)):
+        eng = pkg.HipGpuInference.from_model(model, sw.DEFAULT_MAX_SEQ, flags=flags)
+        try:
+            (toks,), _ = sw.run(eng, sw.DEFAULT_SCENARIOS["cold_split_first"][1], V, max_seq=sw.DEFAULT_MAX_SEQ)
+            logits = eng.forward(toks[-1])                        # (what the loop left, read back through one more step)
+            assert np.isfinite(logits).all() and eng.position() == 262
+            out[key] = {"tokens": toks, "logits": [_digest(logits)]}
+        finally:
+            eng.close()
+    return out
+
+
+def cold_tensor_parallel_switch(pkg):
+    """HipTensorParallel over 2 ranks with the switch at 64 rows (flags = 1 << 16): 60 prompt tokens, decode_greedy(.., 10) across the
+    switch, then one token's logits."""
+    import switch_scenarios as sw
+    hb = pkg.hip_backend
+    name, mix = sw.MAIN
+    cfg = pkg.make_config(name, max_seq_len=sw.MAX_SEQ, intermediate_size=2048, num_kv_heads=4)   # test_gpu_tp.py's D128
+    model = pkg.SynthModel(cfg, mix=mix)
+    V = cfg.vocab_size
+    out = {}
+    for key, flags in (("cold", 0), ("eager", hb.FLAG_NO_GRAPH)):
+        tp = pkg.HipTensorParallel.from_model(model, sw.MAX_SEQ, 2, flags=flags | sw.TP_FLAGS)
+        try:
+            (toks, logits), _ = sw.run(tp, sw.SCENARIOS["cold_switch"][1], V)
+            assert np.isfinite(logits).all() and tp.position() == 71
+            out[key] = {"tokens": toks, "logits": [_digest(logits)], "graph_nodes": int(tp.graph_nodes())}
+        finally:
+            tp.close()
+    assert out["cold"].pop("graph_nodes") > 0 and out["eager"].pop("graph_nodes") == 0
+    return out

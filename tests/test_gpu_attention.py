@@ -19,8 +19,10 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(d, g) for d in (64, 128) for g in (1, 2, 4, 8)]
 ANY_SHAPES = [(96, 7), (80, 3), (96, 3), (80, 7)]
 N_KV = 2
-# (max_seq, pos): around the direct limit (kDirectAttnDefaultKv = 64 rows), a long context, and max_seq >= 2048 (8 waves)
-DECODE_POS = [(1024, p) for p in (0, 1, 63, 64, 65, 1000)] + [(4096, 1000), (4096, 4095)]
+# (max_seq, pos): around 64 rows (one row per lane; the smallest threshold the flags can set, attn_direct=1), the last context the
+# default engine gives the head kernel (kDirectAttnDefaultKv = 256 rows: pos 255) and the first it gives split + merge (pos 256), a long
+# context, and max_seq >= 2048 (8 waves).  (The case index seeds the case's data: new cases go at the end.)
+DECODE_POS = [(1024, p) for p in (0, 1, 63, 64, 65, 1000)] + [(4096, 1000), (4096, 4095)] + [(1024, 255), (1024, 256)]
 BYTE_POS = [(1024, p) for p in (0, 1, 63, 64, 65, 1000)] + [(4096, 4095)]
 SPLITS = (1, 7, 32)   # the engine's default is min(32, 256 / n_kv); 32 splits at pos 0 / 1 is more splits than rows
 PF_POS0 = (0, 5, 16, 2000)

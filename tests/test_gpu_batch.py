@@ -35,8 +35,8 @@ def _model(pkg, name, mix, max_seq=96, **kw):
 def _engines(pkg, name, mix, max_seq=96, n_single=1, **kw):
     cfg, model = _model(pkg, name, mix, max_seq, **kw)
     multi = pkg.HipGpuInference.from_model(model, max_seq)
-    # attn_direct=255: the single-sequence engine switches to a one-launch attention (another summation tree) for contexts of up
-    # to 64 rows; the multi-sequence step always runs the split attention + merge, the structure of every longer context.  The
+    # attn_direct=255: the single-sequence engine runs a one-launch attention (another summation tree) for contexts of up to 256
+    # rows by default; the multi-sequence step always runs the split attention + merge, the structure of every longer context.  The
     # bitwise comparison is against THAT structure; against the short-context variant the logits agree to rounding (last test).
     singles = [pkg.HipGpuInference.from_model(model, max_seq, attn_direct=255) for _ in range(n_single)]
     return cfg, model, multi, singles
@@ -208,8 +208,8 @@ def test_step_launch_sequence_by_class(pkg):
 
 
 def test_short_context_variant_of_the_single_engine_agrees_to_rounding(pkg):
-    """Below 64 rows the DEFAULT single-sequence engine runs its one-launch attention; the batched step (split attention + merge)
-    then differs from it by summation order only."""
+    """Up to 256 rows (here: the whole cache of 64) the DEFAULT single-sequence engine runs its one-launch attention; the batched step
+    (split attention + merge) then differs from it by summation order only."""
     cfg = pkg.make_config("test-dense-d128", max_seq_len=64)
     model = pkg.SynthModel(cfg, mix="Q4_K_M")
     multi = pkg.HipGpuInference.from_model(model, 64)

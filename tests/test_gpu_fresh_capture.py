@@ -43,3 +43,16 @@ def test_first_multi_sequence_step_is_a_greedy_loop_over_quantized_slots(gpu, pk
 
 def test_first_gpu_work_is_a_tensor_parallel_decode(gpu, pkg):
     _cold(pkg, "cold_tensor_parallel")
+
+
+# ---- both decode-attention graphs (tests/switch_scenarios.py): the head form up to the switch, splits + merge beyond
+def test_first_gpu_work_captures_the_head_graph_then_the_split_graph(gpu, pkg):
+    _cold(pkg, "cold_switch_single")
+
+
+def test_first_captured_step_is_the_split_graph_behind_a_batched_prompt(gpu, pkg):
+    _cold(pkg, "cold_split_first")
+
+
+def test_first_gpu_work_is_a_tensor_parallel_decode_across_the_switch(gpu, pkg):
+    _cold(pkg, "cold_tensor_parallel_switch")

@@ -327,8 +327,10 @@ def test_the_bench_workload_itself_matches_the_oracle(pkg, orc):
 
 def test_single_launch_and_split_attention_agree_across_the_switch(pkg, orc):
     """Decode attention runs as one launch per layer up to a context threshold and as split + combine beyond it (two
-    graph variants, picked by the host-side position).  One engine switches at 64 rows in mid-sequence, one never uses
-    the single launch, one always does; all three must follow the oracle."""
+    graph variants, picked by the host-side position; the default threshold is 256 rows).  One engine is told to switch at 64
+    rows (attn_direct=1) and does so in mid-sequence, one never uses the single launch (255), one has the default threshold spelled
+    out (4: 256 rows, above this cache) and always does; all three must follow the oracle.  tests/test_gpu_attn_switch.py takes
+    every state operation across the switch."""
     cfg = pkg.make_config("test-dense-d128", max_seq_len=160)
     model = pkg.SynthModel(cfg, mix="Q4_K_M")
     ref = orc.Model(cfg.as_dict())

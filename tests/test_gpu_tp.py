@@ -126,13 +126,34 @@ def test_tied_output_and_biases(gpu, pkg, orc, mix, over, with_bias, n):
 
 
 def test_long_context_takes_the_split_attention(gpu, pkg, orc):
-    """Past 64 rows the ranks run the attention splits + merge; before, the single-launch attention is all that runs."""
-    cfg, model, prompt, fed, logits = tp_ref.oracle_logits(pkg, orc, "test-dense", "Q4_K_M", {}, 150, 4, 192)
-    tp = pkg.HipTensorParallel.from_model(model, 192, 2)
+    """Past the ranks' default threshold of 256 rows (engine.hip: kDirectAttnDefaultKv) they run the attention splits + merge; up to
+    it, the single-launch attention is all that runs.  A prompt of 260 tokens in a cache of 288: the prompt's last four steps and the
+    four decode steps attend 257 .. 264 rows.  The witness that both forms ran: a twin whose ranks never take the single launch
+    (flags = 255 << 16), fed the same way, gives other bits at a step attending 200 rows — one form sums in another tree than the
+    other — while a twin with the default threshold spelled out (4 << 16) gives the same."""
+    cfg, model, prompt, fed, logits = tp_ref.oracle_logits(pkg, orc, "test-dense", "Q4_K_M", {}, 260, 4, 288)
+    tp = pkg.HipTensorParallel.from_model(model, 288, 2)
+    never = pkg.HipTensorParallel.from_model(model, 288, 2, flags=255 << 16)
+    same = pkg.HipTensorParallel.from_model(model, 288, 2, flags=4 << 16)
     try:
-        _check_against_oracle(pkg, orc, tp, cfg, prompt, fed, logits, "test-dense/Q4_K_M prompt 150 N=2")
+        _check_against_oracle(pkg, orc, tp, cfg, prompt, fed, logits, "test-dense/Q4_K_M prompt 260 N=2")
+        tp.reset()
+        got = [pkg.GpuModelWrapper(e).forward(prompt[:200], pkg.InferenceContext()) for e in (tp, never, same)]
+        assert tp.position() == never.position() == same.position() == 200
+        assert np.array_equal(_bits(got[0]), _bits(got[2]))
+        assert not np.array_equal(_bits(got[0]), _bits(got[1])), "the default ranks and ranks that never take the single launch agree at 200 rows"
+        assert float(np.abs(got[0] - got[1]).max()) <= 1e-4 * float(np.abs(got[0]).max())   # another summation tree, not another context
+        # ... and past 256 rows the default ranks still follow the never-switching ones within that: both run splits + merge there
+        for e in (tp, never):
+            for t in prompt[200:259]:
+                e.prefill_token(t)
+        a, b = tp.forward(prompt[259]), never.forward(prompt[259])
+        assert float(np.abs(a - b).max()) <= 1e-4 * float(np.abs(a).max())
+        assert float(np.abs(a - logits[0]).max()) <= _tol(logits[0]) and float(np.abs(b - logits[0]).max()) <= _tol(logits[0])
     finally:
         tp.close()
+        never.close()
+        same.close()
 
 
 def test_distinct_devices(gpu, pkg, orc):
