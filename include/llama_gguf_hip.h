@@ -240,11 +240,25 @@ int lgh_prefill_token(lgh_ctx* ctx, uint32_t token_id);
  * take the batched path: blocks of up to 128 tokens, one f16-MFMA GEMM per weight (MoE: per expert, over
  * the tokens routed to it), causal attention over the block; the KV cache it leaves equals the token-by-token one within
  * 1e-2 relative (f16 operands, f32 accumulation).  KV caches: f32, and TurboQuantMSE (LGH_KV_TQ2 / TQ3), whose rows are compressed as
- * write_kv does and attended through their codes, the block's own rows included.  Everything else (pipeline stages, other formats,
- * the QJL, int8 and FP8 caches), and any context created with LGH_FLAG_EXACT_PREFILL, runs n exact prefill_tokens. */
+ * write_kv does and attended through their codes, the block's own rows included.  The byte caches (LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2)
+ * take it on a context that asked for it with lgh_set_prefill_policy.  Everything else (the QJL caches, TurboQuant pipeline stages),
+ * and any context created with LGH_FLAG_EXACT_PREFILL, runs n exact prefill_tokens. */
 int lgh_prefill_batch(lgh_ctx* ctx, const uint32_t* tokens, size_t n);
 /* 1 when lgh_prefill_batch will take the batched GEMM path for this (finalized) context, else 0 */
 int lgh_prefill_is_batched(lgh_ctx* ctx);
+/* Which prompt path a context takes where it has a choice.  A call on a finalized context, at any time between calls; unknown bits answer
+ * InvalidArgument and change nothing.  The word is open for further bits.
+ *   LGH_PREFILL_BATCH_BYTE_KV  int8 / FP8 caches take the batched path: the context's own sequence (lgh_prefill_batch), the slots of the
+ *     multi-sequence engine (lgh_batch_prefill) and stage contexts (lgh_stage_prefill_batch).  A block's K / V rows are quantized by the
+ *     decode attention's own quantizers (same bytes and scales for the same f32 row) and every token attends to the stored bytes, the
+ *     block's own rows included.  Like every batched pass it differs from n prefill_tokens within the 1e-2 relative above, which is why
+ *     it is not the default: without the bit a byte cache's prompt is bit-identical to the token-by-token engine's.  All other
+ *     conditions of the batched path still apply, LGH_FLAG_EXACT_PREFILL still wins, and the bit does nothing on f32 and TurboQuant
+ *     contexts.  lgh_prefill_is_batched reports the result.
+ * TurboQuant slots and the QJL formats stay token by token whatever the word says; the lgh_tp_* and lgh_pipeline_* handles have no
+ * setter. */
+enum { LGH_PREFILL_DEFAULT = 0, LGH_PREFILL_BATCH_BYTE_KV = 1u << 0 };
+int lgh_set_prefill_policy(lgh_ctx* ctx, uint32_t policy);
 /* GpuInference::reset (gpu_only.rs:808-843) — O(1): only the position is rewound (model/mod.rs:110-117) */
 void lgh_reset(lgh_ctx* ctx);
 /* GpuInference::position (gpu_only.rs:845-847) */
@@ -294,8 +308,9 @@ int lgh_op_tq_compress_qjl(int device, int bits, const float* x, size_t dim, con
  * anything else answers LGH_UNSUPPORTED.  The slots' caches have the context's kv_cache_type: f32, int8 / FP8
  * (LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2: per slot a byte per element, + one f32 scale per int8 row: about a quarter of the f32 slots'
  * memory) or the TurboQuant formats (LGH_KV_TQ2 / TQ3 / TQ2_QJL / TQ3_QJL: per slot the packed code rows (+ QJL rows)); the
- * reference's BatchedEngine itself only ever creates f32 caches, engine_batched.rs:355-357.  Slots with a quantized cache take
- * their prompt token by token (lgh_batch_prefill).  The single-sequence entry points keep working on the context's own cache.  (A serving context is better created with 8 attention splits — flags bits 8..15 — than with
+ * reference's BatchedEngine itself only ever creates f32 caches, engine_batched.rs:355-357.  Slots with a TurboQuant cache take
+ * their prompt token by token (lgh_batch_prefill), and so do int8 / FP8 slots unless the context set LGH_PREFILL_BATCH_BYTE_KV
+ * (lgh_set_prefill_policy).  The single-sequence entry points keep working on the context's own cache.  (A serving context is better created with 8 attention splits — flags bits 8..15 — than with
  * the single-sequence default: the split count also sizes the multi-sequence attention launch, profiles/r03e_batched_decode.md.) */
 int lgh_batch_create(lgh_ctx* ctx, uint32_t max_batch);                 /* BatchedEngineConfig::max_batch_size (engine_batched.rs:23-41) */
 int lgh_batch_reset(lgh_ctx* ctx, uint32_t slot);                       /* create_active_sequence: model.create_context (332-353); O(1) */
@@ -694,6 +709,21 @@ int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, 
 int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes,
                                 const float* signs, float* out, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_seq_len,
                                 float scale, size_t pos0, size_t m_tokens);
+/* QuantizedKVCache's row write (kv_quantized.rs:143-300) for a block of m <= 128 prompt rows as the batched prefill over a byte cache
+ * runs it (kv8_pf_store_kernel): kv_cache_type LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2 (anything else: Unsupported); k_rows / v_rows
+ * [n_kv_heads][m][head_dim] are the block's f32 rows; k_bytes / v_bytes [n_kv_heads][max_seq_len][head_dim] and, int8, k_scales /
+ * v_scales [n_kv_heads][max_seq_len] (ignored for FP8, may be NULL) are in / out: rows pos0 .. pos0+m-1 come back as the launch
+ * quantized them (the bytes and scale of lgh_op_kv_roundtrip), every other row as it was.  head_dim 64 / 128 (else Unsupported);
+ * pos0 + m <= max_seq_len (else InvalidArgument). */
+int lgh_op_pf_kv8_store(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv_heads, size_t head_dim,
+                        size_t max_seq_len, size_t pos0, uint8_t* k_bytes, uint8_t* v_bytes, float* k_scales, float* v_scales);
+/* The block attention over a byte cache (attn_pf_kv8_kernel) for m_tokens prompt tokens at positions pos0.. as the batched prefill
+ * runs it: the caches already hold rows 0..pos0 + m_tokens - 1, and no row past them is read.  q [m_tokens][n_heads][head_dim];
+ * out [m_tokens][n_heads * head_dim] = the kernel's f16 results widened to f32.  Limits as lgh_op_attention_prefill; Unsupported for
+ * any other kv_cache_type, head_dim outside {64, 128} and n_heads / n_kv_heads outside {1, 2, 4, 8}; InvalidArgument past max_seq_len. */
+int lgh_op_attention_prefill_kv8(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_bytes, const uint8_t* v_bytes,
+                                 const float* k_scales, const float* v_scales, float* out, size_t n_heads, size_t n_kv_heads, size_t head_dim,
+                                 size_t max_seq_len, float scale, size_t pos0, size_t m_tokens);
 /* kv_prefix_copy_kernel (the one launch of lgh_prefix_save / lgh_prefix_restore, src/model/cache.rs:287-326) over host arrays, with the
  * engine's own table builder and launch: caches [n_layers][5] = per layer the K, V, K scale, V scale and K QJL tensors of n_slots
  * slots as lgh_kv_cache_layout sizes them (NULL where the format has none).  restore 0: rows [0, n_rows) of `slot` come back in

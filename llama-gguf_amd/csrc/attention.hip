@@ -553,6 +553,54 @@ hipError_t kv_roundtrip_launch(int fmt, const float* x, uint32_t n, uint8_t* byt
   return hipGetLastError();
 }
 
+// The batched prompt pass over a byte cache (engine_prefill.hip): the block's m K rows after RoPE and V rows, f32 [kv head][src_rows][D]
+// (row r of a head = position pos0 + r), into rows pos0 .. pos0+m-1 of the cache's byte tensors and, for int8, of its scale tensors.
+// LPR = D / 4 lanes hold a row, 4 elements each (one 16-byte load, one dword store), and quantize it with attn_partial_q8_kernel's own
+// functions: the bytes and scales are the ones the decode launch would have stored for the same f32 row.  grid = (row groups, kv
+// heads, K | V); no LDS.
+template <int D, int FMT>
+__global__ void __launch_bounds__(256) kv8_pf_store_kernel(const float* __restrict__ krows, const float* __restrict__ vrows, uint32_t src_rows,
+                                                           uint32_t m, uint32_t pos0, uint32_t max_seq, uint8_t* __restrict__ k8,
+                                                           uint8_t* __restrict__ v8, float* __restrict__ kscale, float* __restrict__ vscale) {
+  constexpr int LPR = D / 4, RPB = 256 / LPR;
+  const uint32_t kvh = blockIdx.y, isv = blockIdx.z;
+  const uint32_t sub = threadIdx.x / LPR, li = threadIdx.x % LPR;
+  const uint32_t r = blockIdx.x * RPB + sub, rr = r < m ? r : m - 1;   // (whole row groups stay active for the row maximum)
+  const f32x4 x = *reinterpret_cast<const f32x4*>((isv ? vrows : krows) + ((size_t)kvh * src_rows + rr) * D + li * 4);
+  float sc = 1.0f;
+  uint32_t w;
+  if (FMT == 1) w = quantize_row_i8<LPR>(x, sc);
+  else w = fp8_encode<FMT>(x.x) | fp8_encode<FMT>(x.y) << 8 | fp8_encode<FMT>(x.z) << 16 | fp8_encode<FMT>(x.w) << 24;
+  if (r >= m) return;
+  const size_t row = (size_t)kvh * max_seq + pos0 + r;
+  *reinterpret_cast<uint32_t*>((isv ? v8 : k8) + row * D + li * 4) = w;
+  if (FMT == 1 && li == 0) (isv ? vscale : kscale)[row] = sc;
+}
+
+template <int D, int FMT>
+static hipError_t kv8_pf_store_go(const float* krows, const float* vrows, uint32_t src_rows, const KvCache& kv, uint32_t n_kv, uint32_t max_seq,
+                                  uint32_t pos0, uint32_t m, hipStream_t st) {
+  constexpr uint32_t RPB = 256 / (D / 4);
+  hipLaunchKernelGGL((kv8_pf_store_kernel<D, FMT>), dim3((m + RPB - 1) / RPB, n_kv, 2), dim3(256), 0, st, krows, vrows, src_rows, m, pos0, max_seq,
+                     kv.k_bytes(), kv.v_bytes(), kv.kscale(), kv.vscale());
+  return hipGetLastError();
+}
+
+// type: LGH_KV_INT8 / LGH_KV_FP8_E4M3 / LGH_KV_FP8_E5M2 (= FMT 1 / 2 / 3); head_dim 64 or 128; rows pos0 .. pos0+m-1 must lie in the cache
+hipError_t kv8_pf_store_launch(uint32_t type, const float* krows, const float* vrows, uint32_t src_rows, const KvCache& kv, uint32_t n_kv,
+                               uint32_t head_dim, uint32_t max_seq, uint32_t pos0, uint32_t m, hipStream_t st) {
+  if (type < LGH_KV_INT8 || type > LGH_KV_FP8_E5M2 || (head_dim != 64 && head_dim != 128) || n_kv == 0 || m == 0 || m > src_rows ||
+      (uint64_t)pos0 + m > max_seq)
+    return hipErrorInvalidValue;
+  auto go = [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    return type == LGH_KV_INT8       ? kv8_pf_store_go<D, 1>(krows, vrows, src_rows, kv, n_kv, max_seq, pos0, m, st)
+           : type == LGH_KV_FP8_E4M3 ? kv8_pf_store_go<D, 2>(krows, vrows, src_rows, kv, n_kv, max_seq, pos0, m, st)
+                                     : kv8_pf_store_go<D, 3>(krows, vrows, src_rows, kv, n_kv, max_seq, pos0, m, st);
+  };
+  return head_dim == 128 ? go(std::integral_constant<int, 128>{}) : go(std::integral_constant<int, 64>{});
+}
+
 // out[h][dim] = the merge of head h's splits (attn_split.h: attn_combine_splits), and wo's input as XQ records
 template <bool MULTI>
 __global__ void __launch_bounds__(128) attn_combine_kernel(const float* __restrict__ part_ml, const float* __restrict__ part_acc,
@@ -847,6 +895,202 @@ hipError_t attn_prefill_tq_launch(const float* q, const float* kscr, const float
   const uint32_t g = n_heads / n_kv;
   return head_dim == 128 ? attn_pf_mfma_go<128, true>(q, kscr, vscr, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, tq)
                          : attn_pf_mfma_go<64, true>(q, kscr, vscr, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, tq);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The block attention over a byte cache (int8 + scales, FP8 E4M3 / E5M2; FMT 1 / 2 / 3): attn_pf_mfma_kernel's geometry, merge and f16
+// store, with the cache's own bytes as the A operands.  Every token attends to the STORED rows, the block's own included
+// (kv8_pf_store_kernel ran before), which is what the token-by-token engine and the reference attend to.  Lane (n, c) takes
+// D/4 contiguous bytes of K row kv0 + n and D/16 contiguous bytes of each V row kv0 + 4c + i; the next tile travels as raw dwords
+// (D = 128: 8 + 8, and 8 scales for int8) and is widened only once it is the current tile.  An int8 row's scale multiplies its score
+// (K) and its probability (V), 8 multiplies per tile and lane, not its 64 elements.  FP8 bytes are widened by the hardware's OCP
+// converters (v_cvt_pk_f32_fp8 / _bf8): they agree with fp8_decode on every code except that 0x80 reads as -0, which adds nothing
+// to a dot product either way (tests/test_gpu_kv8_prefill.py runs every code through both operands).
+// ------------------------------------------------------------------------------------------------
+template <int FMT>
+__device__ __forceinline__ f32x4 kv8_widen4(uint32_t w) {
+  f32x4 r;
+  if (FMT == 1) {
+    r.x = (float)(int)(int8_t)(w & 0xFFu); r.y = (float)(int)(int8_t)((w >> 8) & 0xFFu);
+    r.z = (float)(int)(int8_t)((w >> 16) & 0xFFu); r.w = (float)(int)(int8_t)(w >> 24);
+  } else if (FMT == 2) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+    r.x = lo[0]; r.y = lo[1]; r.z = hi[0]; r.w = hi[1];
+  } else {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true);
+    r.x = lo[0]; r.y = lo[1]; r.z = hi[0]; r.w = hi[1];
+  }
+  return r;
+}
+
+template <int D, int NW, int FMT>
+__global__ void __launch_bounds__(NW * 64) attn_pf_kv8_kernel(const float* __restrict__ q, const uint8_t* __restrict__ kc, const uint8_t* __restrict__ vc,
+                                                              const float* __restrict__ ksc, const float* __restrict__ vsc, uint32_t n_heads,
+                                                              uint32_t g_per_kv, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens,
+                                                              uint8_t* __restrict__ xh_out) {
+  constexpr int DJ = D / 4;    // contraction steps of S^T (bytes of a K row per lane)
+  constexpr int DQ = D / 16;   // output dims per M index (bytes of a V row per lane)
+  constexpr int DP = D + 4;    // padded row of the merge buffer
+  constexpr int KW = DJ / 4, VW = DQ / 4;   // dwords of the K fragment, of one V row's fragment
+  extern __shared__ __attribute__((aligned(16))) float pf_lds[];
+  float (*s_o)[16][DP] = reinterpret_cast<float (*)[16][DP]>(pf_lds);                 // [NW][16][DP]
+  float (*s_m)[16] = reinterpret_cast<float (*)[16]>(pf_lds + NW * 16 * DP);          // [NW][16]
+  float (*s_l)[16] = s_m + NW;
+  const uint32_t head = blockIdx.x, tt = blockIdx.y, kvh = head / g_per_kv;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
+  const uint32_t tok = tt * 16 + n, tokc = tok < m_tokens ? tok : m_tokens - 1;
+  const uint32_t kv_last = pos0 + m_tokens - 1;                               // last cached row
+  const uint32_t n_tiles = (pos0 + tt * 16 + 16 + 15) / 16;                   // tiles the last token of this tile can see
+  float qf[DJ];
+  {
+    const float* qp = q + ((size_t)tokc * n_heads + head) * D + c * DJ;
+#pragma unroll
+    for (int j = 0; j < DJ; j += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(qp + j);
+      qf[j] = v.x; qf[j + 1] = v.y; qf[j + 2] = v.z; qf[j + 3] = v.w;
+    }
+  }
+  const size_t hrow = (size_t)kvh * max_seq;   // first row of this kv head
+  float m_run = kNegBig, l_run = 0.0f;
+  f32x4 acc[DQ];
+#pragma unroll
+  for (int x = 0; x < DQ; x++) acc[x] = (f32x4)(0.0f);
+  // a tile's raw K fragment (row kv0 + n, bytes [c DJ, (c+1) DJ)), V fragments (rows kv0 + 4c + i, bytes [n DQ, (n+1) DQ)) and, int8,
+  // the K and V scales of rows kv0 + 4c + i (the rows of this lane's scores); rows past the block are clamped here and masked below
+  uint32_t kn[KW], vn[4][VW];
+  float ksn[4], vsn[4];
+  auto load_tile = [&](uint32_t tile) {
+    const uint32_t kv0 = tile * 16;
+    const uint32_t kr = kv0 + n < kv_last ? kv0 + n : kv_last;
+    const uint8_t* kp = kc + (hrow + kr) * D + c * DJ;
+#pragma unroll
+    for (int j = 0; j < KW; j += 4) {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(kp + 4 * j);
+      kn[j] = v.x; kn[j + 1] = v.y; kn[j + 2] = v.z; kn[j + 3] = v.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t r = kv0 + 4 * c + i, vr = r < kv_last ? r : kv_last;
+      const uint8_t* vp = vc + (hrow + vr) * D + n * DQ;
+      if (VW == 2) {
+        const u32x2 v = *reinterpret_cast<const u32x2*>(vp);
+        vn[i][0] = v.x; vn[i][VW - 1] = v.y;
+      } else {
+        vn[i][0] = *reinterpret_cast<const uint32_t*>(vp);
+      }
+      if (FMT == 1) { ksn[i] = ksc[hrow + vr]; vsn[i] = vsc[hrow + vr]; }
+    }
+  };
+  if (wave < n_tiles) load_tile(wave);
+  for (uint32_t tile = wave; tile < n_tiles; tile += NW) {
+    const uint32_t kv0 = tile * 16;
+    uint32_t kf[KW], vf[4][VW];
+    float ks[4], vs[4];
+#pragma unroll
+    for (int j = 0; j < KW; j++) kf[j] = kn[j];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+#pragma unroll
+      for (int x = 0; x < VW; x++) vf[i][x] = vn[i][x];
+      if (FMT == 1) { ks[i] = ksn[i]; vs[i] = vsn[i]; }
+    }
+    if (tile + NW < n_tiles) load_tile(tile + NW);   // the next tile's bytes are in flight while this one is computed
+    f32x4 st = (f32x4)(0.0f);
+#pragma unroll
+    for (int j = 0; j < KW; j++) {
+      const f32x4 k4 = kv8_widen4<FMT>(kf[j]);
+#pragma unroll
+      for (int e = 0; e < 4; e++) st = __builtin_amdgcn_mfma_f32_16x16x4f32(k4[e], qf[4 * j + e], st, 0, 0, 0);
+    }
+    // st[i] = <q(token n), k(row kv0 + 4c + i)> (int8: before the row's scale); token n sees rows <= pos0 + tok
+    float sv[4], mx = kNegBig;
+    bool ok[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      ok[i] = kv0 + 4 * c + i <= pos0 + tok;
+      const float s = FMT == 1 ? st[i] * ks[i] : st[i];
+      sv[i] = ok[i] ? s * scale : kNegBig;
+      mx = fmaxf(mx, sv[i]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mn = fmaxf(m_run, mx);
+    const float alpha = __expf(m_run - mn);
+    float pv[4], ps = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { pv[i] = ok[i] ? __expf(sv[i] - mn) : 0.0f; ps += pv[i]; }
+    ps += __shfl_xor(ps, 16, 64);
+    ps += __shfl_xor(ps, 32, 64);
+    l_run = __builtin_fmaf(l_run, alpha, ps);
+    m_run = mn;
+#pragma unroll
+    for (int x = 0; x < DQ; x++) acc[x] = acc[x] * alpha;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const float p = FMT == 1 ? pv[i] * vs[i] : pv[i];
+#pragma unroll
+      for (int x = 0; x < VW; x++) {
+        const f32x4 v4 = kv8_widen4<FMT>(vf[i][x]);
+#pragma unroll
+        for (int e = 0; e < 4; e++) acc[4 * x + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(v4[e], p, acc[4 * x + e], 0, 0, 0);
+      }
+    }
+  }
+  // acc[x][i] = O^T[dim DQ (4c + i) + x][token n] of this wave's tiles; the merge and the store are attn_pf_mfma_kernel's
+  if (c == 0) { s_m[wave][n] = m_run; s_l[wave][n] = l_run; }
+#pragma unroll
+  for (int x = 0; x < DQ; x++) {
+    s_o[wave][n][DQ * (4 * c + 0) + x] = acc[x].x;
+    s_o[wave][n][DQ * (4 * c + 1) + x] = acc[x].y;
+    s_o[wave][n][DQ * (4 * c + 2) + x] = acc[x].z;
+    s_o[wave][n][DQ * (4 * c + 3) + x] = acc[x].w;
+  }
+  __syncthreads();
+  for (uint32_t e = threadIdx.x; e < 16u * D; e += NW * 64) {
+    const uint32_t t = e / D, dim = e % D;
+    if (tt * 16 + t >= m_tokens) continue;
+    float mn = s_m[0][t];
+#pragma unroll
+    for (int w = 1; w < NW; w++) mn = fmaxf(mn, s_m[w][t]);
+    float lsum = 0.0f, a = 0.0f;
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+      const float f = expf(s_m[w][t] - mn);
+      lsum += s_l[w][t] * f;
+      a += s_o[w][t][dim] * f;
+    }
+    const _Float16 o = (_Float16)(a * (1.0f / lsum));   // simd.rs:718-720: multiply by 1/sum
+    *reinterpret_cast<_Float16*>(xh_out + xh_offset(tt * 16 + t, head * D + dim)) = o;
+  }
+}
+
+template <int D, int FMT>
+static hipError_t attn_pf_kv8_go(const float* q, const KvCache& kv, uint32_t n_heads, uint32_t g, uint32_t max_seq, float scale, uint32_t pos0,
+                                 uint32_t m_tokens, uint8_t* xh_out, hipStream_t st) {
+  constexpr int NW = 8;
+  constexpr size_t lds = (size_t)(NW * 16 * (D + 4) + 2 * NW * 16) * 4;
+  static bool attr_set[64] = {};
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&attn_pf_kv8_kernel<D, NW, FMT>), (int)lds, attr_set); e != hipSuccess) return e;
+  hipLaunchKernelGGL((attn_pf_kv8_kernel<D, NW, FMT>), dim3(n_heads, (m_tokens + 15) / 16), dim3(NW * 64), lds, st, q, kv.k_bytes(), kv.v_bytes(), kv.kscale(),
+                     kv.vscale(), n_heads, g, max_seq, scale, pos0, m_tokens, xh_out);
+  return hipGetLastError();
+}
+
+// type: LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2; kv: [n_kv][max_seq][head_dim] bytes (+ [n_kv][max_seq] scales, int8); head_dim 64 or 128,
+// 1 / 2 / 4 / 8 query heads per kv head — a property of the callers (pf_eligible), the kernel takes any divisor
+hipError_t attn_prefill_kv8_launch(uint32_t type, const float* q, const KvCache& kv, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq,
+                                   float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st) {
+  if (type < LGH_KV_INT8 || type > LGH_KV_FP8_E5M2 || (head_dim != 64 && head_dim != 128) || n_kv == 0 || n_heads % n_kv || m_tokens == 0 ||
+      (uint64_t)pos0 + m_tokens > max_seq)
+    return hipErrorInvalidValue;
+  const uint32_t g = n_heads / n_kv;
+  auto go = [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    return type == LGH_KV_INT8       ? attn_pf_kv8_go<D, 1>(q, kv, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st)
+           : type == LGH_KV_FP8_E4M3 ? attn_pf_kv8_go<D, 2>(q, kv, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st)
+                                     : attn_pf_kv8_go<D, 3>(q, kv, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st);
+  };
+  return head_dim == 128 ? go(std::integral_constant<int, 128>{}) : go(std::integral_constant<int, 64>{});
 }
 
 // Attention of one query row for any head_dim (256 threads): scores of the `visible` rows in LDS (sc), the arithmetic of

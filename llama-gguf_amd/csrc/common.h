@@ -295,6 +295,12 @@ hipError_t tq_pf_rows_launch(int bits, float* kscr, float* vscr, uint8_t* kq, ui
                              hipStream_t st);
 hipError_t attn_prefill_tq_launch(const float* q, const float* kscr, const float* vscr, const float* signs, uint32_t n_heads, uint32_t n_kv,
                                   uint32_t head_dim, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st);
+// the batched prompt pass over a byte cache (LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2; attention.hip): the block's f32 rows [n_kv][src_rows][head_dim]
+// into cache rows pos0 .. pos0+m-1, and the block attention over the stored bytes
+hipError_t kv8_pf_store_launch(uint32_t type, const float* krows, const float* vrows, uint32_t src_rows, const KvCache& kv, uint32_t n_kv,
+                               uint32_t head_dim, uint32_t max_seq, uint32_t pos0, uint32_t m, hipStream_t st);
+hipError_t attn_prefill_kv8_launch(uint32_t type, const float* q, const KvCache& kv, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq,
+                                   float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st);
 hipError_t attn_decode_any_launch(const float* q, const float* kcache, const float* vcache, float* out, uint32_t n_heads, uint32_t n_kv,
                                   uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, hipStream_t st);
 hipError_t attn_generic_launch(const float* q, const float* k, const float* v, float* out, uint32_t n_heads, uint32_t n_kv, uint32_t seq_len,

@@ -49,6 +49,9 @@ struct PfScratch {
   // TurboQuantMSE caches: one layer's rows as f32 in the rotated space (centroids of the codes), K then V, each [kv head][max_seq][head_dim];
   // rebuilt by every layer of every block (attention_tq.hip tq_pf_rows_kernel)
   float* tq_kv = nullptr;
+  // byte caches (int8 / FP8): the block's K rows after RoPE, then its V rows, f32 [kv head][128][head_dim] each — the block only; the
+  // store launch (attention.hip kv8_pf_store_kernel) turns them into the target's cache rows
+  float* kv8_rows = nullptr;
 };
 
 struct ProfRec { int cls; int sym; uint64_t bytes; hipEvent_t a, b; };
@@ -118,6 +121,7 @@ struct lgh_ctx {
   std::vector<void*> allocs;  // everything hipMalloc'ed by this context
   std::vector<lgh::XqBuf> xqs;
   lgh::PfScratch pf;
+  uint32_t pf_policy = 0;                      // LGH_PREFILL_* (lgh_set_prefill_policy)
   lgh::BatchScratch batch;
   float* tq_signs = nullptr;                   // TurboQuant KV cache: [owned layer][kv head][k, v][head_dim] rotation signs (device)
   std::vector<float> tq_signs_host;
@@ -272,7 +276,9 @@ int enqueue_token(lgh_ctx* c, int mode);   // everything one token needs, in str
 // batched prompt path (engine_prefill.hip).  The sequence a block of prompt tokens belongs to: the position of the block's first token,
 // and whose K / V rows it fills — the context's own (slot < 0) or a slot's of the multi-sequence engine (kv_of)
 struct PfTarget { size_t pos0; int slot; };
-// slot: the target is a slot of the multi-sequence engine (TurboQuant slots stay token by token: bit-identical to the single-sequence engine)
+// slot: the target is a slot of the multi-sequence engine (TurboQuant slots stay token by token: bit-identical to the single-sequence engine).
+// The byte caches (int8 / FP8) have the path for the own sequence, slots and stage contexts alike, on contexts that asked for it
+// (lgh_set_prefill_policy: lgh_ctx::pf_policy)
 bool pf_eligible(const lgh_ctx* c, bool slot = false);
 int pf_ensure(lgh_ctx* c);
 int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_t m);
@@ -280,7 +286,9 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
 // consumer, nullptr = leave no XH
 int pf_embed_tokens(lgh_ctx* c, uint32_t pos0, const uint32_t* tokens, uint32_t m);   // ids through the pinned ring, embedding rows into pf.hidden
 int pf_block_input(lgh_ctx* c, const float* nw, uint32_t m);
-int pf_qkv_step(lgh_ctx* c, lgh::LayerW& L, float* kcache, float* vcache, uint32_t pos0, uint32_t m);
+// cache_rows: rows per kv head of kcache / vcache whose row 0 is position 0 (0: max_seq_len, a whole cache).  The byte caches' block scratch
+// has 128 rows per head and row 0 = position pos0: the caller passes 128 and bases shifted back by pos0 rows
+int pf_qkv_step(lgh_ctx* c, lgh::LayerW& L, float* kcache, float* vcache, uint32_t pos0, uint32_t m, uint32_t cache_rows = 0);
 int pf_wo_step(lgh_ctx* c, lgh::LayerW& L, uint32_t m);
 int pf_ffn_step(lgh_ctx* c, lgh::LayerW& L, const float* next_nw, uint32_t m);
 int pf_moe_step(lgh_ctx* c, lgh::LayerW& L, const float* next_nw, uint32_t m);

@@ -521,6 +521,14 @@ int lgh_prefill_token(lgh_ctx* c, uint32_t token) {
 
 int lgh_prefill_is_batched(lgh_ctx* c) { return c && c->finalized && pf_eligible(c) ? 1 : 0; }
 
+int lgh_set_prefill_policy(lgh_ctx* c, uint32_t policy) {
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (policy & ~(uint32_t)LGH_PREFILL_BATCH_BYTE_KV) return fail(c, LGH_INVALID_ARGUMENT, "unknown prefill policy bits");
+  c->pf_policy = policy;   // read by pf_eligible at every prompt call; the scratch it needs is made by pf_ensure at the first one
+  return LGH_OK;
+}
+
 int lgh_stage_hidden_block_buffer(lgh_ctx* c, void** p) {
   int rc = check_ready(c);
   if (rc) return rc;

@@ -17,11 +17,15 @@ bool pf_eligible(const lgh_ctx* c, bool slot) {
   const lgh_model_desc& d = c->d;
   if (d.flags & LGH_FLAG_EXACT_PREFILL) return false;
   // The batched path writes f32 K/V rows.  The f32 cache takes them as they are; a TurboQuantMSE cache (tq2 / tq3) takes them through an
-  // f32 scratch (pf_tq_rows below), for the own sequence of a context that owns every layer.  The QJL formats, int8 and FP8, slots of
-  // the multi-sequence engine and stage contexts with a TurboQuant cache stay token by token.
-  if (c->kvl.staged()) {
+  // f32 scratch (pf_tq_rows below), for the own sequence of a context that owns every layer.  A byte cache (int8 / FP8) takes them
+  // through a scratch of the block's rows and a store launch (pf_kv8_store below), own sequence, slots and stage contexts alike, on
+  // a context that opted in (lgh_set_prefill_policy): the pass is not bit-identical to the token-by-token one.  The QJL formats, and
+  // slots of the multi-sequence engine and stage contexts with a TurboQuant cache, stay token by token.
+  if (c->kvl.tq()) {
     if (d.kv_cache_type != LGH_KV_TQ2 && d.kv_cache_type != LGH_KV_TQ3) return false;
     if (slot || !c->first || !c->last) return false;
+  } else if (c->kvl.staged() && !(c->pf_policy & LGH_PREFILL_BATCH_BYTE_KV)) {
+    return false;
   }
   const uint32_t QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, g = d.num_heads / d.num_kv_heads;
   if (d.hidden_size % 256 || d.hidden_size > 2048u * kPfSsqChunks || QD % 256 || KD % 16) return false;
@@ -44,6 +48,9 @@ bool pf_eligible(const lgh_ctx* c, bool slot) {
   }
   return true;
 }
+
+// a byte cache (the context reaches the batched path with one only through the policy: pf_eligible)
+static bool pf_kv8(const lgh_ctx* c) { return c->kvl.staged() && !c->kvl.tq(); }
 
 int pf_ensure(lgh_ctx* c) {
   PfScratch& P = c->pf;
@@ -72,6 +79,7 @@ int pf_ensure(lgh_ctx* c) {
       {(void**)&P.moe_tokmap, any_moe ? (size_t)kPfTokens * kPfMaxTopK * 4 : 0},
       {(void**)&P.xh_gather, any_moe ? xh_bytes(H) * d.num_experts : 0}, {(void**)&P.xh_act_e, any_moe ? xh_bytes(EI) * d.num_experts : 0},
       {(void**)&P.tq_kv, c->kvl.tq() ? (size_t)2 * c->kvl.stride_floats() * 4 : 0},   // (scratch, not KV bytes)
+      {(void**)&P.kv8_rows, pf_kv8(c) ? (size_t)2 * d.num_kv_heads * kPfTokens * d.head_dim * 4 : 0},   // (the block only; scratch too)
   };
   if (int rc = alloc_zeroed(c, bufs, sizeof(bufs) / sizeof(bufs[0]), c->stats.scratch_bytes)) return rc;
   // the zero-fills are done before anybody else (another stream, a peer's copy into the stage block) touches the buffers
@@ -94,7 +102,7 @@ int pf_block_input(lgh_ctx* c, const float* nw, uint32_t m) {
 // ---- the steps of one layer over a block of m tokens, on the context's scratch (c->pf); prefill_block strings them together, the
 // per-step test entry points (ops_api.hip) run them one at a time ----
 // XH(h * attn_norm) in pf.xh_h + the tokens' sums of squares in pf.ssq -> q in pf.q, K / V rows pos0 .. pos0+m-1 of the given caches
-int pf_qkv_step(lgh_ctx* c, LayerW& L, float* kcache, float* vcache, uint32_t pos0, uint32_t m) {
+int pf_qkv_step(lgh_ctx* c, LayerW& L, float* kcache, float* vcache, uint32_t pos0, uint32_t m, uint32_t cache_rows) {
   PfScratch& P = c->pf;
   const lgh_model_desc& d = c->d;
   const uint32_t H = d.hidden_size, QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim;
@@ -103,7 +111,7 @@ int pf_qkv_step(lgh_ctx* c, LayerW& L, float* kcache, float* vcache, uint32_t po
   uint32_t S = 0, nc = 0;
   const DevWeight* qkv[3] = {&L.wq, &L.wk, &L.wv};
   if ((rc = pf_k(c, pf_gemm_launch(qkv, 3, P.xh_h, P.part, P.part_bytes, m, &S, &nc, st), "qkv GEMM"))) return rc;
-  return pf_k(c, pf_qkv_epi_launch(P.part, S, nc, QD, KD, d.head_dim, L.bq, L.bk, L.bv, c->rope_cs, pos0, d.max_seq_len, P.q, kcache, vcache, P.ssq, H,
+  return pf_k(c, pf_qkv_epi_launch(P.part, S, nc, QD, KD, d.head_dim, L.bq, L.bk, L.bv, c->rope_cs, pos0, cache_rows ? cache_rows : d.max_seq_len, P.q, kcache, vcache, P.ssq, H,
                                    d.norm_eps, (int)d.use_neox_rope, m, st),
               "qkv epilogue");
 }
@@ -118,6 +126,16 @@ static int pf_tq_rows(lgh_ctx* c, LayerW& L, uint32_t li, uint32_t pos0, uint32_
   return pf_k(c, tq_pf_rows_launch(c->kvl.tq_bits(), P.tq_kv, vscr, L.kv.k_bytes(), L.kv.v_bytes(), attend ? P.q : nullptr, tq_layer(c, li).signs, d.num_heads,
                                    d.num_kv_heads, d.head_dim, d.max_seq_len, pos0, m, attend ? m : 0, attend ? pos0 : 0, c->stream),
               "TurboQuant rows");
+}
+
+// byte cache, after pf_qkv_step has left the block's f32 K / V rows in the scratch pf.kv8_rows: rows pos0 .. pos0+m-1 of the target's byte
+// tensors (and scales), quantized as the decode attention quantizes a token's rows
+static int pf_kv8_store(lgh_ctx* c, const KvCache& kv, uint32_t pos0, uint32_t m) {
+  const lgh_model_desc& d = c->d;
+  const float* const krows = c->pf.kv8_rows;
+  return pf_k(c, kv8_pf_store_launch(d.kv_cache_type, krows, krows + (size_t)d.num_kv_heads * kPfTokens * d.head_dim, kPfTokens, kv, d.num_kv_heads, d.head_dim,
+                                     d.max_seq_len, pos0, m, c->stream),
+              "byte cache rows");
 }
 
 // XH(attention output) in pf.xh_attn -> pf.hidden += wo . attn (+ bo), XH(h * ffn_norm) in pf.xh_h, sums of squares in pf.ssq
@@ -224,19 +242,25 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
   if (c->first && (rc = pf_embed_tokens(c, pos0, tokens, m))) return rc;
   if ((rc = pf_block_input(c, c->layers[c->l0].attn_norm, m))) return rc;
   const float scale = 1.0f / std::sqrt((float)d.head_dim);  // layers.rs:374
-  const bool tq = c->kvl.tq();
+  const bool tq = c->kvl.tq(), kv8 = pf_kv8(c);
   if (tq && t.slot >= 0) return fail(c, LGH_UNSUPPORTED, "TurboQuant slots have no batched prompt path");
   for (uint32_t li = c->l0; li < c->l1; li++) {
     LayerW& L = c->layers[li];
     // (a TurboQuant cache: the scratch stands in for the layer's f32 cache; pf_eligible admits the context's own sequence only)
     const KvCache kv = kv_of(c, li, t.slot);
-    float* const kcache = tq ? P.tq_kv : kv.k_f32();
-    float* const vcache = tq ? P.tq_kv + c->kvl.stride_floats() : kv.v_f32();
+    // (a byte cache: the scratch of the block's rows, its row 0 standing for position pos0; the attention reads the stored bytes only)
+    const size_t kv8_off = (size_t)pos0 * d.head_dim;
+    float* const kcache = tq ? P.tq_kv : kv8 ? P.kv8_rows - kv8_off : kv.k_f32();
+    float* const vcache = tq ? P.tq_kv + c->kvl.stride_floats() : kv8 ? P.kv8_rows + (size_t)d.num_kv_heads * kPfTokens * d.head_dim - kv8_off : kv.v_f32();
     const bool attend = !(li + 1 == c->l1 && c->last);   // the model's last layer: its K/V rows are written, its output would be discarded
-    if ((rc = pf_qkv_step(c, L, kcache, vcache, pos0, m))) return rc;
+    if ((rc = pf_qkv_step(c, L, kcache, vcache, pos0, m, kv8 ? (uint32_t)kPfTokens : 0))) return rc;
     if (tq && (rc = pf_tq_rows(c, L, li, pos0, m, attend))) return rc;
+    if (kv8 && (rc = pf_kv8_store(c, kv, pos0, m))) return rc;
     if (!attend) break;
-    if (tq) {
+    if (kv8) {
+      rc = pf_k(c, attn_prefill_kv8_launch(d.kv_cache_type, P.q, kv, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
+                "attention");
+    } else if (tq) {
       rc = pf_k(c, attn_prefill_tq_launch(P.q, kcache, vcache, tq_layer(c, li).signs, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m,
                                           P.xh_attn, st),
                 "attention");

@@ -879,6 +879,59 @@ int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float*
   return xh_down(t, xh, m_tokens, qd, out);
 }
 
+int lgh_op_pf_kv8_store(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv, size_t head_dim,
+                        size_t max_seq, size_t pos0, uint8_t* k_bytes, uint8_t* v_bytes, float* k_scales, float* v_scales) {
+  // QuantizedKVCache's row write for a block of prompt rows, as the batched prefill over a byte cache runs it
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (kv_cache_type != LGH_KV_INT8 && kv_cache_type != LGH_KV_FP8_E4M3 && kv_cache_type != LGH_KV_FP8_E5M2) return LGH_UNSUPPORTED;
+  if (head_dim != 64 && head_dim != 128) return LGH_UNSUPPORTED;
+  const KvLayout l(kv_cache_type, n_kv, max_seq, head_dim);
+  if (!k_rows || !v_rows || !k_bytes || !v_bytes || (l.has_scales() && (!k_scales || !v_scales)) || n_kv == 0 || max_seq > 0x7FFFFFFFu)
+    return LGH_INVALID_ARGUMENT;
+  if (m == 0 || m > (size_t)kPfTokens || pos0 > max_seq || pos0 + m > max_seq) return LGH_INVALID_ARGUMENT;
+  KvCache kv;
+  void* const host[KV_KINDS] = {k_bytes, v_bytes, k_scales, v_scales};
+  if (int rc = kv_upload(t, l, 1, host, kv)) return rc;
+  const size_t rows = n_kv * m * head_dim;
+  float *dk = t.up(k_rows, rows), *dv = t.up(v_rows, rows);
+  if (!dk || !dv) return LGH_ALLOCATION_FAILED;
+  if (kv8_pf_store_launch(kv_cache_type, dk, dv, (uint32_t)m, kv, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, (uint32_t)pos0, (uint32_t)m,
+                          t.c->stream) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  return kv_download(t, l, 1, host, kv);
+}
+
+int lgh_op_attention_prefill_kv8(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_bytes, const uint8_t* v_bytes, const float* k_scales,
+                                 const float* v_scales, float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq, float scale, size_t pos0,
+                                 size_t m_tokens) {
+  // QuantizedKVCache::attention for a block of prompt tokens, as the batched prefill over a byte cache runs it
+  Tmp t(device);
+  if (t.rc) return t.rc;
+  if (kv_cache_type != LGH_KV_INT8 && kv_cache_type != LGH_KV_FP8_E4M3 && kv_cache_type != LGH_KV_FP8_E5M2) return LGH_UNSUPPORTED;
+  if (head_dim != 64 && head_dim != 128) return LGH_UNSUPPORTED;
+  const KvLayout l(kv_cache_type, n_kv, max_seq, head_dim);
+  if (!q || !k_bytes || !v_bytes || (l.has_scales() && (!k_scales || !v_scales)) || !out || n_kv == 0 || n_heads % n_kv || max_seq > 0x7FFFFFFFu)
+    return LGH_INVALID_ARGUMENT;
+  const size_t g = n_heads / n_kv;
+  if (g != 1 && g != 2 && g != 4 && g != 8) return LGH_UNSUPPORTED;   // (pf_eligible's group sizes)
+  const size_t qd = n_heads * head_dim;
+  if (m_tokens == 0 || m_tokens > (size_t)kPfTokens || qd % 256 || pos0 > max_seq || pos0 + m_tokens > max_seq) return LGH_INVALID_ARGUMENT;
+  float* dq = t.up(q, m_tokens * qd);
+  KvCache kv;
+  const void* const host[KV_KINDS] = {k_bytes, v_bytes, k_scales, v_scales};
+  if (int rc = kv_upload(t, l, 1, host, kv)) return rc;
+  const size_t xb = xh_bytes((uint32_t)qd);
+  uint8_t* xh = (uint8_t*)up_bytes(t, nullptr, xb);
+  if (!dq || !xh) return LGH_ALLOCATION_FAILED;
+  hipStream_t st = t.c->stream;
+  if (hipMemsetAsync(xh, 0, xb, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  if (attn_prefill_kv8_launch(kv_cache_type, dq, kv, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, scale, (uint32_t)pos0,
+                              (uint32_t)m_tokens, xh, st) != hipSuccess)
+    return LGH_OPERATION_FAILED;
+  return xh_down(t, xh, m_tokens, qd, out);
+}
+
 // ---- device-resident weights by tensor name: CudaBackend::load_model_weights + the `b.name()` lookups of its vec_mat /
 // vec_mat_q (src/backend/cuda/mod.rs:121-146, 436-470, 511-575; store: cuda/dequant_weights.rs) ----
 }  // extern "C"

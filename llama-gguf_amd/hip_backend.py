@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libllama_gguf_hip%s.so" % ("_" + os.envir
 # every symbol include/llama_gguf_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "lgh_device_count", "lgh_create", "lgh_upload_tensor", "lgh_finalize", "lgh_destroy", "lgh_forward",
-    "lgh_prefill_token", "lgh_prefill_batch", "lgh_prefill_is_batched", "lgh_op_mat_mat",
+    "lgh_prefill_token", "lgh_prefill_batch", "lgh_prefill_is_batched", "lgh_set_prefill_policy", "lgh_op_mat_mat",
     "lgh_op_kv_roundtrip", "lgh_op_add", "lgh_op_mul", "lgh_op_scale", "lgh_op_silu", "lgh_op_gelu", "lgh_op_softmax", "lgh_op_matmul", "lgh_op_matvec",
     "lgh_op_matvec_q", "lgh_op_attention", "lgh_backend_create", "lgh_backend_destroy", "lgh_backend_load_weight",
     "lgh_backend_has_weight", "lgh_backend_vec_mat_q", "lgh_backend_last_error", "lgh_reset", "lgh_position", "lgh_kv_truncate", "lgh_kv_shift_left", "lgh_stage_prefill_batch", "lgh_stage_hidden_block_buffer", "lgh_forward_argmax", "lgh_decode_greedy",
@@ -46,7 +46,7 @@ ABI_SYMBOLS = (
     "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches",
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
     "lgh_op_linear_multi", "lgh_op_linear_chain_multi", "lgh_op_qkv_rope_multi", "lgh_op_moe_multi", "lgh_debug_mvqb_structures",
-    "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_attention_kv8_multi", "lgh_op_attention_tq_multi",
+    "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_pf_kv8_store", "lgh_op_attention_prefill_kv8", "lgh_op_attention_kv8_multi", "lgh_op_attention_tq_multi",
     "lgh_op_embed", "lgh_op_qkv_forward", "lgh_op_ffn_gateup", "lgh_op_argmax", "lgh_kv_cache_layout",
     "lgh_prefix_save", "lgh_prefix_restore", "lgh_prefix_free", "lgh_prefix_get_info", "lgh_prefix_total_bytes", "lgh_prefix_export",
     "lgh_prefix_import", "lgh_op_kv_prefix_copy",
@@ -62,6 +62,7 @@ SYM_NAMES = ("lgh::mv_kernel<1u, 1024>", "lgh::mv_kernel<8u, 1024>", "lgh::mv_ke
              "lgh::embed_kernel", "lgh::argmax_stage1+2", "lgh::moe_router_kernel", "other", "lgh::mvq_kernel<1u>", "lgh::mvq_kernel<2u>", "lgh::mvq_kernel<3u>", "lgh::mvq_kernel<4u>",
              "lgh::mvq_kernel<8u>", "unused")
 FLAG_NO_GRAPH = 1
+PREFILL_BATCH_BYTE_KV = 1   # lgh_set_prefill_policy: int8 / FP8 caches take the batched prompt pass (own sequence, slots, stage contexts)
 FLAG_EXACT_PREFILL = 4   # forward_batch feeds tokens one by one (f32 throughout) instead of the batched f16 GEMM path
 KV_F32, KV_INT8, KV_FP8_E4M3, KV_FP8_E5M2 = 0, 1, 2, 3   # lgh_model_desc.kv_cache_type: f32, or QuantizedKVCache's formats (kv_quantized.rs; no CLI flag reaches them)
 KV_TQ2, KV_TQ3 = 4, 5   # KVCacheType::TurboQuantMSE { bits: 2 | 3 }: what `--kv-cache-type tq2 | tq3` selects (src/config.rs:808-817)
@@ -189,6 +190,7 @@ def load_library() -> C.CDLL:
         "lgh_finalize": (C.c_int, [vp]), "lgh_destroy": (None, [vp]),
         "lgh_forward": (C.c_int, [vp, u32, vp]), "lgh_prefill_token": (C.c_int, [vp, u32]),
         "lgh_prefill_batch": (C.c_int, [vp, vp, sz]), "lgh_prefill_is_batched": (C.c_int, [vp]),
+        "lgh_set_prefill_policy": (C.c_int, [vp, C.c_uint32]),
         "lgh_op_mat_mat": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, sz]), "lgh_reset": (None, [vp]), "lgh_position": (sz, [vp]),
         "lgh_kv_truncate": (C.c_int, [vp, sz]), "lgh_kv_shift_left": (C.c_int, [vp, sz]),
         "lgh_stage_prefill_batch": (C.c_int, [vp, vp, sz]), "lgh_stage_hidden_block_buffer": (C.c_int, [vp, C.POINTER(vp)]),
@@ -266,6 +268,8 @@ def load_library() -> C.CDLL:
         "lgh_op_attention_prefill": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
         "lgh_op_pf_tq_store": (C.c_int, [C.c_int, u32, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp]),
         "lgh_op_attention_prefill_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
+        "lgh_op_pf_kv8_store": (C.c_int, [C.c_int, u32, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp]),
+        "lgh_op_attention_prefill_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
         "lgh_op_qkv_rope": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, sz, sz, f32, f32, vp, vp, vp]),
         "lgh_op_linear_image": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, f32, vp, C.c_int, vp, C.c_int, vp, vp, vp,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -330,7 +334,7 @@ class HipGpuInference:
     @classmethod
     def from_model(cls, model, max_seq_len: int, device: int = 0, layer_range: Optional[Sequence[int]] = None,
                    flags: int = 0, attn_splits: int = 0, attn_direct: int = 0, kv_cache_type: int = 0,
-                   kv_rotation_signs=None, kv_qjl_matrices=None) -> "HipGpuInference":
+                   kv_rotation_signs=None, kv_qjl_matrices=None, prefill_policy: int = 0) -> "HipGpuInference":
         """`model` hands over what LlamaModel::into_parts does (llama.rs:138-160): `.config` and
         `.tensors(layers)` yielding (gguf_name, ggml_type, ne, host bytes)."""
         L = load_library()
@@ -362,6 +366,8 @@ class HipGpuInference:
             for name, t, ne, data in model.tensors(range(lb, le)):
                 self.upload_tensor(name, t, ne, data)
             self._call(L.lgh_finalize(self._h))
+            if prefill_policy:
+                self.set_prefill_policy(prefill_policy)
         except Exception:
             self.close()
             raise
@@ -409,6 +415,10 @@ class HipGpuInference:
 
     def prefill_is_batched(self) -> bool:
         return bool(load_library().lgh_prefill_is_batched(self._h))
+
+    def set_prefill_policy(self, policy: int) -> None:
+        """lgh_set_prefill_policy: PREFILL_BATCH_BYTE_KV lets int8 / FP8 caches take the batched prompt pass; 0 restores the default."""
+        self._call(load_library().lgh_set_prefill_policy(self._h, policy))
 
     def reset(self) -> None:
         load_library().lgh_reset(self._h)
@@ -1653,6 +1663,37 @@ def op_pf_tq_store(kv_cache_type: int, k_rows, v_rows, pos0: int, signs, k_codes
     _chk(load_library().lgh_op_pf_tq_store(device, kv_cache_type, kr.ctypes.data, vr.ctypes.data, m, nkv, d, kc.shape[1], pos0,
                                            sg.ctypes.data, kc.ctypes.data, vc.ctypes.data), "pf_tq_store")
     return kc, vc
+
+
+def op_pf_kv8_store(kv_cache_type: int, k_rows, v_rows, pos0: int, k_bytes, v_bytes, k_scales=None, v_scales=None, device: int = 0):
+    """The batched prefill's byte-cache row store (KV_INT8 / KV_FP8_E4M3 / KV_FP8_E5M2): k_rows / v_rows [nkv, m, d] f32 are quantized
+    into rows pos0..pos0+m-1 of the byte caches [nkv, max_seq, d] and, int8, of the scales [nkv, max_seq] (ignored for FP8).
+    -> (k_bytes, v_bytes, k_scales, v_scales) after the call (copies; the scales None where none were given)."""
+    kr, vr = _f32(k_rows), _f32(v_rows)
+    kb, vb = np.array(k_bytes, dtype=np.uint8, copy=True), np.array(v_bytes, dtype=np.uint8, copy=True)
+    ks = None if k_scales is None else np.array(k_scales, dtype=np.float32, copy=True)
+    vs = None if v_scales is None else np.array(v_scales, dtype=np.float32, copy=True)
+    nkv, m, d = kr.shape
+    _chk(load_library().lgh_op_pf_kv8_store(device, kv_cache_type, kr.ctypes.data, vr.ctypes.data, m, nkv, d, kb.shape[1], pos0, kb.ctypes.data,
+                                            vb.ctypes.data, None if ks is None else ks.ctypes.data, None if vs is None else vs.ctypes.data),
+         "pf_kv8_store")
+    return kb, vb, ks, vs
+
+
+def op_attention_prefill_kv8(kv_cache_type: int, q, k_bytes, v_bytes, k_scales, v_scales, scale: float, pos0: int, device: int = 0) -> np.ndarray:
+    """Causal attention of a block of prompt tokens over a byte cache (KV_INT8 / KV_FP8_E4M3 / KV_FP8_E5M2) as the batched prefill runs
+    it: q [m, nh, d] at positions pos0..pos0+m-1; the byte caches [nkv, max_seq, d] hold rows 0..pos0+m-1, the scales [nkv, max_seq]
+    go with int8 (ignored, and may be None, for FP8).  -> [m, nh * d]: the kernel's f16 outputs widened to f32."""
+    q = _f32(q)
+    kb, vb = np.ascontiguousarray(k_bytes, dtype=np.uint8), np.ascontiguousarray(v_bytes, dtype=np.uint8)
+    ks = None if k_scales is None else _f32(k_scales)
+    vs = None if v_scales is None else _f32(v_scales)
+    m, nh, d = q.shape
+    out = np.empty((m, nh * d), dtype=np.float32)
+    _chk(load_library().lgh_op_attention_prefill_kv8(device, kv_cache_type, q.ctypes.data, kb.ctypes.data, vb.ctypes.data,
+                                                     None if ks is None else ks.ctypes.data, None if vs is None else vs.ctypes.data,
+                                                     out.ctypes.data, nh, kb.shape[0], d, kb.shape[1], scale, pos0, m), "attention_prefill_kv8")
+    return out
 
 
 def op_kv_prefix_copy(kv_cache_type: int, caches, slot: int, n_rows: int, head_dim: int, packed=None, device: int = 0):

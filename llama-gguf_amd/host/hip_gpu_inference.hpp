@@ -81,6 +81,8 @@ class HipGpuInference {
   // GpuOnlyInference::forward_batch minus the final forward (gpu_only.rs:776-790); batched f16-GEMM path when the model allows
   void forward_batch(const std::vector<uint32_t>& tokens) { check(lgh_prefill_batch(h_, tokens.data(), tokens.size())); }
   bool prefill_is_batched() { return lgh_prefill_is_batched(h_) != 0; }
+  // LGH_PREFILL_BATCH_BYTE_KV: int8 / FP8 caches (own sequence, slots, stage contexts) take the batched path; 0 restores the default
+  void set_prefill_policy(uint32_t policy) { check(lgh_set_prefill_policy(h_, policy)); }
   void kv_truncate(size_t new_len) { check(lgh_kv_truncate(h_, new_len)); }        // KVCache::truncate (model/mod.rs:130-134)
   void kv_shift_left(size_t amount) { check(lgh_kv_shift_left(h_, amount)); }      // KVCache::shift_left (model/mod.rs:142-172)
   void reset() { lgh_reset(h_); }                      // infallible, O(1)

@@ -8,6 +8,8 @@
   --mode recompute   the same prompts computed: forward_batch on the own sequence (the batched pass for f32 / tq2 / tq3, token by
                      token otherwise) and batch_prefill on a slot.  Uses entry points older than the prompt cache only, so
                      --root can point it at a checkout of the parent commit (built there) to time that library.
+                     --policy 1 (PREFILL_BATCH_BYTE_KV, lgh_set_prefill_policy) sends int8 / FP8 prompts, slots included, through
+                     the batched pass; 0, the default, calls nothing a parent checkout lacks.
 
 `python tools/prefix_bench.py --mode copy|recompute [--root DIR] [--kv f32,int8,tq3,tq3-qjl] [--lengths 128,512,2048]`;
 prints one JSON line per (format, length, target) and a markdown table."""
@@ -62,6 +64,7 @@ def main():
     ap.add_argument("--lengths", default="128,512,2048")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warm", type=int, default=2)
+    ap.add_argument("--policy", type=int, default=0, help="lgh_set_prefill_policy word, set on every engine when not 0")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
     import __graft_entry__ as graft
@@ -75,11 +78,13 @@ def main():
     for name in a.kv.split(","):
         kv = KV[name]
         eng = pkg.HipGpuInference.from_model(model, max_seq, kv_cache_type=kv)
+        if a.policy:
+            eng.set_prefill_policy(a.policy)
         eng.batch_create(1)
         for n in lengths:
             prompt = [(7 * i + 3) % cfg.vocab_size for i in range(n)]
             for target, slot in (("own", -1), ("slot", 0)):
-                rec = {"mode": a.mode, "model": a.model, "mix": a.mix, "kv": name, "n": n, "target": target}
+                rec = {"mode": a.mode, "model": a.model, "mix": a.mix, "kv": name, "policy": a.policy, "n": n, "target": target}
                 if a.mode == "copy":
                     src = eng.prefix_from_bytes(zero_blob(cfg, hb, kv, n, max_seq))
                     eng.prefix_restore(src, slot)
@@ -90,7 +95,7 @@ def main():
                         rec[k]["traffic_TBps"] = 2 * src.nbytes / (rec[k]["best_us"] * 1e-6) / 1e12
                     src.free()
                 else:
-                    batched = eng.prefill_is_batched() if slot < 0 else name == "f32"
+                    batched = eng.prefill_is_batched() if slot < 0 else name == "f32" or (eng.prefill_is_batched() and KV[name] in (1, 2, 3))
                     reps, warm = (a.reps, a.warm) if batched else (3, 1)
                     if slot < 0:
                         ts = timed(eng, lambda: eng.forward_batch(prompt), reps, warm, before=eng.reset)
