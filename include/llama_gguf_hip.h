@@ -762,6 +762,10 @@ int lgh_op_linear_image(int device, uint32_t type, const void* w, const void* w_
 uint32_t lgh_op_set_flags(uint32_t flags);
 /* How many matrix-core mat-vec launches of this process ran a static launch plan so far (tests: which kernel a launch took). */
 uint64_t lgh_debug_static_launches(void);
+/* The matrix-core mat-vec planner's answer for a [n_rows][k] weight inside a launch of launch_rows rows in all (host only, no device):
+ * out[0..6] = T k-slices, G row groups, blocks per k-slice, rows per workgroup, workgroups, threads, partial-sum floats (npass = 1).
+ * Returns LGH_OK, or LGH_UNSUPPORTED for a k the planner refuses. */
+int lgh_debug_mv_plan(uint32_t k, uint32_t n_rows, uint32_t launch_rows, uint32_t out[7]);
 /* ffn_forward's MoE half: out = x + sum_p sel_w[p] * down_e(silu(gate_e . x') * (up_e . x')), e = sel[p], x' = RMSNorm(x) * norm_w.
  * Expert stacks in GGUF order: w_gate / w_up [n_experts][ffn][hidden], w_down [n_experts][hidden][ffn].  With `router`
  * ([n_experts][hidden] f32) the device router selects (sel / sel_w are ignored); otherwise sel / sel_w (top_k entries) drive the

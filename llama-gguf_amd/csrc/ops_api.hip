@@ -1233,6 +1233,14 @@ int lgh_op_linear_chain(int device, uint32_t type_a, const void* w_a, const void
 // with and without the static launch plans).  Returns the previous value.
 uint64_t lgh_debug_static_launches(void) { return lgh::mvq_static_launches(); }
 
+int lgh_debug_mv_plan(uint32_t k, uint32_t n_rows, uint32_t launch_rows, uint32_t out[7]) {
+  if (!out) return LGH_INVALID_ARGUMENT;
+  lgh::MvPlan p;
+  if (lgh::mvq_plan(k, n_rows, 1, &p, launch_rows) != hipSuccess) return LGH_UNSUPPORTED;
+  out[0] = p.T; out[1] = p.G; out[2] = p.units; out[3] = p.rows_per_wg; out[4] = p.n_wg; out[5] = p.threads; out[6] = p.red_floats;
+  return LGH_OK;
+}
+
 uint32_t lgh_op_set_flags(uint32_t flags) {
   const uint32_t prev = g_op_flags;
   g_op_flags = flags;

@@ -43,7 +43,7 @@ ABI_SYMBOLS = (
     "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
     "lgh_set_sampler_ex", "lgh_batch_set_sampler_ex", "lgh_get_sampler_mu", "lgh_op_sample_ex",
     "lgh_op_attention_decode", "lgh_op_attention_decode_multi", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
-    "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches",
+    "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches", "lgh_debug_mv_plan",
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
     "lgh_op_linear_multi", "lgh_op_linear_chain_multi", "lgh_op_qkv_rope_multi", "lgh_op_moe_multi", "lgh_debug_mvqb_structures",
     "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_pf_kv8_store", "lgh_op_attention_prefill_kv8", "lgh_op_attention_kv8_multi", "lgh_op_attention_tq_multi",
@@ -275,6 +275,7 @@ def load_library() -> C.CDLL:
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "lgh_op_set_flags": (u32, [u32]),
         "lgh_debug_static_launches": (C.c_uint64, []),
+        "lgh_debug_mv_plan": (C.c_int, [u32, u32, u32, C.POINTER(C.c_uint32)]),
         "lgh_op_linear_chain": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, f32, vp, C.c_int, vp, u32, vp, sz, vp, vp, vp,
                                           C.POINTER(C.c_int)]),
         "lgh_op_moe_experts": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
@@ -1326,6 +1327,14 @@ def op_set_flags(flags: int) -> int:
 def static_launches() -> int:
     """Matrix-core mat-vec launches of this process that ran a static launch plan so far."""
     return int(load_library().lgh_debug_static_launches())
+
+
+def mv_plan(k: int, n_rows: int, launch_rows: int = 0) -> dict:
+    """lgh_debug_mv_plan (host only): the matrix-core mat-vec planner's geometry for a [n_rows, k] weight in a launch of launch_rows
+    rows in all.  -> dict(T, G, nbw, rows_per_wg, n_wg, threads, red_floats)."""
+    out = (C.c_uint32 * 7)()
+    _chk(load_library().lgh_debug_mv_plan(k, n_rows, launch_rows, out), "mv_plan")
+    return dict(zip(("T", "G", "nbw", "rows_per_wg", "n_wg", "threads", "red_floats"), (int(v) for v in out)))
 
 
 def op_linear_image(ggml_type: int, w, k: int, n: int, x, *, w_up=None, bias=None, norm_w=None, eps: float = 1e-5, resid=None,

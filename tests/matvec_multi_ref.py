@@ -181,13 +181,9 @@ def linear_blocks(tname: str, raw, k: int, n: int, x, keep_blocks, nw=None, rows
 
 
 def k_slices(k: int):
-    """(T, nbw): the k-slices of the single-sequence plan — the largest divisor of k / 256 up to 8, or 8 uneven slices of
-    ceil(nblk / 8) blocks when that divisor is below 4 and there are more than 8 blocks."""
-    nblk = k // 256
-    T = max(t for t in range(1, min(8, nblk) + 1) if nblk % t == 0)
-    if T < 4 and nblk > 8:
-        T = 8
-    return T, (nblk + T - 1) // T
+    """(T, nbw): the k-slices of the single-sequence plan (matvec_ref.mvq_geometry)."""
+    g = mr.mvq_geometry(k, 16)
+    return g["T"], g["nbw"]
 
 
 def rope_rows(orc, Y, E, pos, head_dim: int, base: float, scale: float):

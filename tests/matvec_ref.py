@@ -384,3 +384,44 @@ def router(x, nw, eps: float, wr, top_k: int):
     p = np.exp(top - top.max())
     lerr = c_f32(x64.size) * U * (np.abs(w64) @ np.abs(xn)) + 8 * TINY
     return sel, p / p.sum(), logits, lerr
+
+
+# ---- the matrix-core planner (csrc/matvec_mfma.hip: mvq_plan), restated
+MVQ_WAVES = 8        # waves of a full workgroup
+MVQ_CUS = 256        # the planner aims at one workgroup per CU
+
+
+def mvq_geometry(k: int, n: int, launch_rows=None) -> dict:
+    """The workgroup shape of a [n, k] weight (k a multiple of 256) in a launch of launch_rows rows in all (default: n).
+    T k-slices: the largest divisor of k / 256 up to 8, or 8 uneven slices when that divisor is below 4 and there are more than 8
+    blocks; G = 8 // T row groups; nbw = ceil(nblk / T) blocks per slice, `slices` the blocks each slice really has (the last busy one
+    may be short, the ones behind it idle); 64 T G threads.  A workgroup takes R = Rg G tiles of 16 rows: one workgroup per CU, rounded
+    up to whole row groups and capped at rmax (the epilogue gives every row a thread); n_wg workgroups, the last with `last` tiles."""
+    if k <= 0 or k % 256 or n <= 0:
+        raise ValueError("k must be a positive multiple of 256, n positive")
+    nblk = k // 256
+    T = max(t for t in range(1, min(MVQ_WAVES, nblk) + 1) if nblk % t == 0)
+    if T < MVQ_WAVES // 2 and nblk > MVQ_WAVES:
+        T = MVQ_WAVES
+    G = MVQ_WAVES // T
+    nbw = -(-nblk // T)
+    slices = tuple(max(0, min(nbw, nblk - s * nbw)) for s in range(T))
+    threads = 64 * T * G
+    tiles = -(-n // 16)
+    R = -(-(-(-max(launch_rows or n, n) // 16)) // MVQ_CUS)
+    R = -(-R // G) * G
+    rmax = threads // 16 // G * G
+    R = min(R, rmax)
+    n_wg = -(-tiles // R)
+    return dict(T=T, G=G, nbw=nbw, slices=slices, idle=sum(1 for b in slices if b == 0), threads=threads, Rg=R // G, R=R, rmax=rmax,
+                n_wg=n_wg, last=tiles - (n_wg - 1) * R)
+
+
+def mvq_class(k: int) -> str:
+    """The geometry class of k: '(T,G)', and for T = 8 how its slices divide the blocks."""
+    g = mvq_geometry(k, 16)
+    if g["T"] < 8:
+        return "(%d,%d)" % (g["T"], g["G"])
+    if len(set(g["slices"])) == 1:
+        return "(8,1) even"
+    return "(8,1) uneven busy" if g["idle"] == 0 else "(8,1) uneven idle%d" % g["idle"]

@@ -155,6 +155,11 @@ CHAIN_CASES = [
 
 @pytest.mark.parametrize("ta,k,na,tb,nb", CHAIN_CASES)
 def test_epilogues_and_xq_chain(gpu, pkg, orc, ta, k, na, tb, nb):
+    chain_case(gpu, ta, k, na, tb, nb)
+
+
+def chain_case(gpu, ta, k, na, tb, nb, tag=""):
+    """The seven (epilogue, xq_next) pairs of launch A [na, k] feeding launch B [nb, na]; `tag` leads every WORST line."""
     W = Worst()
     fam_a, fam_b = mr.kernel_family(ta, k), mr.kernel_family(tb, na)
     rng = np.random.default_rng(k + na)
@@ -178,7 +183,7 @@ def test_epilogues_and_xq_chain(gpu, pkg, orc, ta, k, na, tb, nb):
             kw["resid"] = res
         oa, ob1, ob2, used = gpu.op_linear_chain(mr.TYPE[ta], wa, k, na, x, mr.TYPE[tb], wb, nb, **kw)
         oa2, ob1b, _, _ = gpu.op_linear_chain(mr.TYPE[ta], wa, k, na, x, mr.TYPE[tb], wb, nb, **kw)
-        path = "%s %s %s" % (fam_a, ta, epi)
+        path = "%s%s %s %s" % (tag, fam_a, ta, epi)
         W.expect(np.array_equal(oa.view(np.uint32), oa2.view(np.uint32)) and np.array_equal(ob1.view(np.uint32), ob1b.view(np.uint32)),
                  "%s: not deterministic" % path)
         y, e = _ref(ta, wa, k, na, x, fam_a, nw=nw, bias=kw.get("bias_a"))
@@ -190,8 +195,8 @@ def test_epilogues_and_xq_chain(gpu, pkg, orc, ta, k, na, tb, nb):
         W.check(path, oa, y, e, "xq_next=%d" % xq_next)
         # B reads A's f32 output exactly as the kernel left it
         yb, eb = mr.matvec(ab, ob, oa, nw=nnw if xq_next == 2 else None, eps=EPS, family=fam_b)
-        W.check("%s %s fed by %s %s" % (fam_b, tb, fam_a, epi), ob1, yb, eb, "xq_next=%d" % xq_next)
-        W.check("%s %s fed by xq_quantize" % (fam_b, tb), ob2, yb, eb, "xq_next=%d" % xq_next)
+        W.check("%s%s %s fed by %s %s" % (tag, fam_b, tb, fam_a, epi), ob1, yb, eb, "xq_next=%d" % xq_next)
+        W.check("%s%s %s fed by xq_quantize" % (tag, fam_b, tb), ob2, yb, eb, "xq_next=%d" % xq_next)
         if xq_next and fam_b == "mfma" and na % 16 == 0:
             W.expect(used, "%s xq_next=%d: A left no XQ image" % (path, xq_next))
         W.expect(np.array_equal(ob1.view(np.uint32), ob2.view(np.uint32)),
@@ -215,6 +220,11 @@ QKV_CASES = [
 
 @pytest.mark.parametrize("types,hidden,hd,nh,nkv", QKV_CASES)
 def test_fused_qkv_rope(gpu, pkg, orc, types, hidden, hd, nh, nkv):
+    qkv_case(gpu, orc, types, hidden, hd, nh, nkv)
+
+
+def qkv_case(gpu, orc, types, hidden, hd, nh, nkv, tag=""):
+    """The fused QKV launch with and without biases at pos 0, 1 and last; `tag` leads every WORST line."""
     W = Worst()
     max_seq, base, scale = 40, 500000.0, 1.0
     fam = mr.kernel_family(types[0], hidden)
@@ -230,20 +240,20 @@ def test_fused_qkv_rope(gpu, pkg, orc, types, hidden, hd, nh, nkv):
             vc = kc.copy()
             q, k2, v2 = gpu.op_qkv_rope([mr.TYPE[t] for t in types], ws, biases, x, nw, EPS, hd, nh, nkv, kc, vc, pos, base, scale)
             q_b, k2b, v2b = gpu.op_qkv_rope([mr.TYPE[t] for t in types], ws, biases, x, nw, EPS, hd, nh, nkv, kc, vc, pos, base, scale)
-            tag = "%s/%s/%s %d%s" % (types + (hidden, " bias" if with_bias else ""))
+            what = "%s/%s/%s %d%s" % (types + (hidden, " bias" if with_bias else ""))
             W.expect(all(np.array_equal(p.view(np.uint32), r.view(np.uint32)) for p, r in ((q, q_b), (k2, k2b), (v2, v2b))),
-                     "%s pos %d: not deterministic" % (tag, pos))
+                     "%s pos %d: not deterministic" % (what, pos))
             c, s = mr.rope_cs(orc, pos, hd, base, scale)
             refs = [_ref(types[i], ws[i], hidden, rows[i], x, fam, nw=nw, bias=biases[i]) for i in range(3)]
             yq, eq = mr.rope(*refs[0], c, s, hd)
             yk, ek = mr.rope(*refs[1], c, s, hd)
-            W.check("%s qkv ROPE_Q %s" % (fam, tag), q, yq, eq, "pos %d" % pos)
-            W.check("%s qkv ROPE_K %s" % (fam, tag), k2[:, pos, :].reshape(-1), yk, ek, "pos %d" % pos)
-            W.check("%s qkv V_CACHE %s" % (fam, tag), v2[:, pos, :].reshape(-1), refs[2][0], refs[2][1], "pos %d" % pos)
+            W.check("%s%s qkv ROPE_Q %s" % (tag, fam, what), q, yq, eq, "pos %d" % pos)
+            W.check("%s%s qkv ROPE_K %s" % (tag, fam, what), k2[:, pos, :].reshape(-1), yk, ek, "pos %d" % pos)
+            W.check("%s%s qkv V_CACHE %s" % (tag, fam, what), v2[:, pos, :].reshape(-1), refs[2][0], refs[2][1], "pos %d" % pos)
             others = np.ones(max_seq, bool)
             others[pos] = False
             W.expect(np.all(k2[:, others].view(np.uint32) == NAN_BITS) and np.all(v2[:, others].view(np.uint32) == NAN_BITS),
-                     "%s pos %d: a cache row other than pos changed" % (tag, pos))
+                     "%s pos %d: a cache row other than pos changed" % (what, pos))
     W.done()
 
 

@@ -507,6 +507,32 @@ def test_generic_attention_shapes_and_top_k_follow_the_oracle(pkg, orc):
         ref.close()
 
 
+def test_decode_matvec_geometries_follow_the_oracle(pkg, orc):
+    """Widths whose decode mat-vecs run in 5- and 7-slice workgroups (320 / 448 threads) or in 8 uneven slices with idle waves
+    (tests/matvec_ref.py: mvq_geometry): hidden 1792 / ffn 2304, hidden 1280 / ffn 3328, hidden 2560 / ffn 3584; 2 layers, 24 tokens."""
+    cases = [("Q4_K_M", True, dict(num_heads=14, num_kv_heads=2, head_dim=128, hidden_size=1792, intermediate_size=2304, use_neox_rope=True)),
+             ("Q5_K_M", False, dict(num_heads=10, num_kv_heads=10, head_dim=128, hidden_size=1280, intermediate_size=3328)),
+             ("Q8_0", False, dict(num_heads=20, num_kv_heads=4, head_dim=128, hidden_size=2560, intermediate_size=3584))]
+    for mix, with_bias, kw in cases:
+        cfg = pkg.make_config("test-dense", max_seq_len=32, **kw)
+        assert cfg.num_layers == 2
+        model = pkg.SynthModel(cfg, mix=mix, with_bias=with_bias)
+        ref = orc.Model(cfg.as_dict())
+        for nm, t, ne, data in model.tensors(keep=True):
+            ref.add_tensor(nm, t, ne, data)
+        ref.finalize()
+        eng = pkg.HipGpuInference.from_model(model, 32)
+        worst = 0.0
+        for i in range(24):
+            t = (31 * i + 2) % cfg.vocab_size
+            got, want = eng.forward(t), ref.forward([t])
+            worst = max(worst, float(np.abs(got - want).max()))
+            assert np.all(np.isfinite(got)) and np.abs(got - want).max() <= _tol(want), (mix, kw, i)
+        print(f"test-dense/{mix} {kw}: max|dlogit|={worst:.3e}")
+        eng.close()
+        ref.close()
+
+
 def test_generic_attention_refuses_contexts_that_do_not_fit_lds(pkg):
     """The generic attention kernel keeps max_seq_len scores in LDS: a longer context is refused by lgh_create with
     Unsupported and a message naming the shape (not by a launch error in finalize)."""

@@ -99,7 +99,10 @@ def _check_against_oracle(pkg, orc, tp, cfg, prompt, fed, logits, what):
 
 D128 = dict(intermediate_size=2048, num_kv_heads=4)
 ENGINE_CASES = [("test-dense", "Q4_K_M", {}, 2), ("test-dense", "Q8_0", dict(num_heads=16, num_kv_heads=4), 4),
-                ("test-dense-d128", "Q4_K_M", D128, 2), ("test-dense-d128", "Q4_K_M", D128, 4), ("test-dense", "Q4_K_M", {}, 1)]
+                ("test-dense-d128", "Q4_K_M", D128, 2), ("test-dense-d128", "Q4_K_M", D128, 4), ("test-dense", "Q4_K_M", {}, 1),
+                # ffn_down shards of k = 1792 (7 k-slices, 448-thread workgroups) and k = 1280 (5 k-slices, 320 threads)
+                ("test-dense-d128", "Q4_K_M", dict(num_kv_heads=4, intermediate_size=3584, num_layers=2), 2),
+                ("test-dense-d128", "Q4_K_M", dict(num_kv_heads=4, intermediate_size=5120, num_layers=2), 4)]
 
 
 @pytest.mark.parametrize("name,mix,over,n", ENGINE_CASES)
