@@ -19,7 +19,7 @@
 // kernel this one does not (each skipped term is < 1e-8 of the output scale).
 #include <cstdlib>
 
-#include "attn_split.h"
+#include "attn_block.h"
 #include "tq_fwht.h"
 #include "xq.h"
 #include "prefill.h"
@@ -718,57 +718,43 @@ hipError_t attn_head_launch(const float* q, const float* kcache, const float* vc
 // ------------------------------------------------------------------------------------------------
 struct PfTqEpi { const float* signs; float inv_scale, inv_d; };   // (unused without TQ)
 
+// the f16 element (token t of the block, column col) of the XH matrix the wo GEMM reads
+__device__ __forceinline__ void pf_xh_store(uint8_t* xh_out, uint32_t t, uint32_t col, float v) {
+  *reinterpret_cast<_Float16*>(xh_out + xh_offset(t, col)) = (_Float16)v;
+}
+
 template <int D, int NW, bool TQ>
 __global__ void __launch_bounds__(NW * 64) attn_pf_mfma_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc,
                                                                uint32_t n_heads, uint32_t g_per_kv, uint32_t max_seq, float scale, uint32_t pos0,
                                                                uint32_t m_tokens, uint8_t* __restrict__ xh_out, const PfTqEpi tq) {
-  constexpr int DJ = D / 4;    // contraction steps of S^T (dims per lane group)
-  constexpr int DQ = D / 16;   // output dims per M index
-  constexpr int DP = D + 4;    // padded row of the merge buffer
-  extern __shared__ __attribute__((aligned(16))) float pf_lds[];
-  float (*s_o)[16][DP] = reinterpret_cast<float (*)[16][DP]>(pf_lds);                 // [NW][16][DP]
-  float (*s_m)[16] = reinterpret_cast<float (*)[16]>(pf_lds + NW * 16 * DP);          // [NW][16]
-  float (*s_l)[16] = s_m + NW;
-  const uint32_t head = blockIdx.x, tt = blockIdx.y, kvh = head / g_per_kv;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
-  const uint32_t tok = tt * 16 + n, tokc = tok < m_tokens ? tok : m_tokens - 1;
-  const uint32_t kv_last = pos0 + m_tokens - 1;                               // last cached row
-  const uint32_t n_tiles = (pos0 + tt * 16 + 16 + 15) / 16;                   // tiles the last token of this tile can see
+  using Core = AttnBlockCore<D, NW>;
+  constexpr int DJ = Core::DJ, DQ = Core::DQ;
+  Core b(g_per_kv, pos0, m_tokens);
+  const uint32_t n = b.n, c = b.c;
   float qf[DJ];
-  {
-    const float* qp = q + ((size_t)tokc * n_heads + head) * D + c * DJ;
-#pragma unroll
-    for (int j = 0; j < DJ; j += 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(qp + j);
-      qf[j] = v.x; qf[j + 1] = v.y; qf[j + 2] = v.z; qf[j + 3] = v.w;
-    }
-  }
-  const float* kbase = kc + (size_t)kvh * max_seq * D;
-  const float* vbase = vc + (size_t)kvh * max_seq * D;
+  b.load_q(qf, q, n_heads, m_tokens);
+  const float* kbase = kc + (size_t)b.kvh * max_seq * D;
+  const float* vbase = vc + (size_t)b.kvh * max_seq * D;
   float m_run = kNegBig, l_run = 0.0f;
-  f32x4 acc[DQ];
+  f32x4 acc[DQ];   // acc[x][i] = O^T[dim DQ (4c + i) + x][token n] of this wave's tiles
 #pragma unroll
   for (int x = 0; x < DQ; x++) acc[x] = (f32x4)(0.0f);
-  // a tile's K fragment (row kv0 + n, dims [c DJ, (c+1) DJ)) and V fragments (rows kv0 + 4c + i, dims [n DQ, (n+1) DQ)); rows
-  // past the block are clamped here and masked below
+  // a tile's K fragment (row kv0 + n, dims [c DJ, (c+1) DJ)) and V fragments (rows kv0 + 4c + i, dims [n DQ, (n+1) DQ))
   f32x4 kn[DJ / 4], vn[4][DQ / 4];
   auto load_tile = [&](uint32_t tile) {
     const uint32_t kv0 = tile * 16;
-    const uint32_t kr = kv0 + n < kv_last ? kv0 + n : kv_last;
-    const float* kp = kbase + (size_t)kr * D + c * DJ;
+    const float* kp = kbase + (size_t)b.row(kv0 + n) * D + c * DJ;
 #pragma unroll
     for (int j = 0; j < DJ / 4; j++) kn[j] = *reinterpret_cast<const f32x4*>(kp + 4 * j);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      const uint32_t r = kv0 + 4 * c + i, vr = r < kv_last ? r : kv_last;
-      const float* vp = vbase + (size_t)vr * D + n * DQ;
+      const float* vp = vbase + (size_t)b.row(kv0 + 4 * c + i) * D + n * DQ;
 #pragma unroll
       for (int x = 0; x < DQ / 4; x++) vn[i][x] = *reinterpret_cast<const f32x4*>(vp + 4 * x);
     }
   };
-  if (wave < n_tiles) load_tile(wave);
-  for (uint32_t tile = wave; tile < n_tiles; tile += NW) {
-    const uint32_t kv0 = tile * 16;
+  if (b.wave < b.n_tiles) load_tile(b.wave);
+  for (uint32_t tile = b.wave; tile < b.n_tiles; tile += NW) {
     f32x4 kf[DJ / 4], vf[4][DQ / 4];
 #pragma unroll
     for (int j = 0; j < DJ / 4; j++) kf[j] = kn[j];
@@ -776,129 +762,40 @@ __global__ void __launch_bounds__(NW * 64) attn_pf_mfma_kernel(const float* __re
     for (int i = 0; i < 4; i++)
 #pragma unroll
       for (int x = 0; x < DQ / 4; x++) vf[i][x] = vn[i][x];
-    if (tile + NW < n_tiles) load_tile(tile + NW);   // the next tile's fragments are in flight while this one is computed
+    if (tile + NW < b.n_tiles) load_tile(tile + NW);   // the next tile's fragments are in flight while this one is computed
     f32x4 st = (f32x4)(0.0f);
 #pragma unroll
     for (int j = 0; j < DJ; j++) st = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[j / 4][j % 4], qf[j], st, 0, 0, 0);
-    // st[i] = <q(token n), k(row kv0 + 4c + i)>; token n sees rows <= pos0 + tok
-    float sv[4], mx = kNegBig;
-    bool ok[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      ok[i] = kv0 + 4 * c + i <= pos0 + tok;
-      sv[i] = ok[i] ? st[i] * scale : kNegBig;
-      mx = fmaxf(mx, sv[i]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mn = fmaxf(m_run, mx);
-    const float alpha = __expf(m_run - mn);
-    float pv[4], ps = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { pv[i] = ok[i] ? __expf(sv[i] - mn) : 0.0f; ps += pv[i]; }
-    ps += __shfl_xor(ps, 16, 64);
-    ps += __shfl_xor(ps, 32, 64);
-    l_run = __builtin_fmaf(l_run, alpha, ps);
-    m_run = mn;
-#pragma unroll
-    for (int x = 0; x < DQ; x++) acc[x] = acc[x] * alpha;
+    float pv[4];
+    b.update(st, tile * 16, pos0, scale, m_run, l_run, acc, pv);
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
       for (int x = 0; x < DQ; x++) acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[i][x / 4][x % 4], pv[i], acc[x], 0, 0, 0);
   }
-  // acc[x][i] = O^T[dim DQ (4c + i) + x][token n] of this wave's tiles
-  if (c == 0) { s_m[wave][n] = m_run; s_l[wave][n] = l_run; }
-#pragma unroll
-  for (int x = 0; x < DQ; x++) {
-    s_o[wave][n][DQ * (4 * c + 0) + x] = acc[x].x;
-    s_o[wave][n][DQ * (4 * c + 1) + x] = acc[x].y;
-    s_o[wave][n][DQ * (4 * c + 2) + x] = acc[x].z;
-    s_o[wave][n][DQ * (4 * c + 3) + x] = acc[x].w;
-  }
-  __syncthreads();
-  for (uint32_t e = threadIdx.x; e < 16u * D; e += NW * 64) {
-    const uint32_t t = e / D, dim = e % D;
-    if (tt * 16 + t >= m_tokens) continue;
-    float mn = s_m[0][t];
-#pragma unroll
-    for (int w = 1; w < NW; w++) mn = fmaxf(mn, s_m[w][t]);
-    float lsum = 0.0f, a = 0.0f;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-      const float f = expf(s_m[w][t] - mn);
-      lsum += s_l[w][t] * f;
-      a += s_o[w][t][dim] * f;
-    }
-    if (TQ) {   // (this thread alone reads s_o[.][t][dim]: the merged value may take wave 0's place)
-      s_o[0][t][dim] = (a * (1.0f / lsum)) * tq.inv_scale;                // x * sqrt(d), as attn_tq_combine_kernel
-      continue;
-    }
-    const _Float16 o = (_Float16)(a * (1.0f / lsum));   // simd.rs:718-720: multiply by 1/sum
-    *reinterpret_cast<_Float16*>(xh_out + xh_offset(tt * 16 + t, head * D + dim)) = o;
-  }
-  if (TQ) {
-    // the inverse rotation (rotation.rs:80-96): out = signs * (1 / d) * H (sqrt(d) * o), a wave per token, butterflies in registers
+  b.stash(m_run, l_run, acc);
+  if (!TQ) {
+    b.merge(m_tokens, [&](uint32_t t, uint32_t dim, float o) { pf_xh_store(xh_out, b.tt * 16 + t, b.head * D + dim, o); });
+  } else {
+    // the merged value takes wave 0's place, x sqrt(d) as attn_tq_combine_kernel; then the inverse rotation (rotation.rs:80-96):
+    // out = signs * (1 / d) * H (sqrt(d) * o), a wave per token, butterflies in registers
+    b.merge(m_tokens, [&](uint32_t t, uint32_t dim, float o) { b.s_o[0][t][dim] = o * tq.inv_scale; });
     __syncthreads();
-    const float* sv = tq.signs + (size_t)(kvh * 2 + 1) * D;
-    for (uint32_t t = wave; t < 16u; t += NW) {
-      if (tt * 16 + t >= m_tokens) continue;   // wave-uniform
-      float x0 = s_o[0][t][lane], x1 = 0.0f;
-      if (D == 128) x1 = s_o[0][t][lane + 64];
+    const float* sv = tq.signs + (size_t)(b.kvh * 2 + 1) * D;
+    const uint32_t lane = b.lane;
+    for (uint32_t t = b.wave; t < 16u; t += NW) {
+      if (b.tt * 16 + t >= m_tokens) continue;   // wave-uniform
+      float x0 = b.s_o[0][t][lane], x1 = 0.0f;
+      if (D == 128) x1 = b.s_o[0][t][lane + 64];
       tq_fwht_wave<D>(x0, x1, lane);
-      *reinterpret_cast<_Float16*>(xh_out + xh_offset(tt * 16 + t, head * D + lane)) = (_Float16)(x0 * tq.inv_d * sv[lane]);
-      if (D == 128) *reinterpret_cast<_Float16*>(xh_out + xh_offset(tt * 16 + t, head * D + lane + 64)) = (_Float16)(x1 * tq.inv_d * sv[lane + 64]);
+      pf_xh_store(xh_out, b.tt * 16 + t, b.head * D + lane, x0 * tq.inv_d * sv[lane]);
+      if (D == 128) pf_xh_store(xh_out, b.tt * 16 + t, b.head * D + lane + 64, x1 * tq.inv_d * sv[lane + 64]);
     }
   }
-}
-
-template <int D, bool TQ>
-static hipError_t attn_pf_mfma_go(const float* q, const float* kc, const float* vc, uint32_t n_heads, uint32_t g, uint32_t max_seq, float scale,
-                                  uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st, const PfTqEpi& tq) {
-  constexpr int NW = 8;   // (4 waves: 11.7 us per layer of a 128-token Llama-3-8B prompt, the last token tile's waves take two kv tiles each)
-  constexpr size_t lds = (size_t)(NW * 16 * (D + 4) + 2 * NW * 16) * 4;
-  static bool attr_set[64] = {};
-  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&attn_pf_mfma_kernel<D, NW, TQ>), (int)lds, attr_set); e != hipSuccess) return e;
-  hipLaunchKernelGGL((attn_pf_mfma_kernel<D, NW, TQ>), dim3(n_heads, (m_tokens + 15) / 16), dim3(NW * 64), lds, st, q, kc, vc, n_heads, g, max_seq, scale,
-                     pos0, m_tokens, xh_out, tq);
-  return hipGetLastError();
-}
-
-hipError_t attn_prefill_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv,
-                               uint32_t head_dim, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out,
-                               hipStream_t st) {
-  if (n_kv == 0 || n_heads % n_kv || m_tokens == 0) return hipErrorInvalidValue;
-  const uint32_t g = n_heads / n_kv;
-  // (read once per process: tests/test_gpu_fresh_env.py::test_valu_prompt_attention holds the VALU kernel to test_prefill's bound)
-  static const bool valu = [] { const char* e = std::getenv("LGH_PF_ATTN_VALU"); return e && std::atoi(e) != 0; }();   // (A/B switch: the VALU kernel)
-  if (!valu && (head_dim == 128 || head_dim == 64)) {
-    return head_dim == 128 ? attn_pf_mfma_go<128, false>(q, kcache, vcache, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, PfTqEpi{})
-                           : attn_pf_mfma_go<64, false>(q, kcache, vcache, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, PfTqEpi{});
-  }
-  // 4 waves per (kv head, token) workgroup: 8 and 16 waves measured slower on the 128-token Llama-3-8B prompt (4.79 / 5.07 vs
-  // 4.74 ms per prompt pass) — the grid is already 1024 workgroups wide.
-  return attn_dispatch(head_dim, g, [&](auto d, auto gg) {
-    hipLaunchKernelGGL((attn_partial_kernel<decltype(d)::value, decltype(gg)::value, 4, true>), dim3(n_kv, m_tokens), dim3(256), 0, st, q, kcache, vcache,
-                       max_seq, scale, (const int*)nullptr, (int)(pos0 + 1), 1u, (float*)nullptr, reinterpret_cast<float*>(xh_out));
-    return hipGetLastError();
-  });
-}
-
-// the block attention over the TurboQuantMSE prompt pass's scratch (tq_pf_rows_launch filled it and rotated q): head_dim 64 / 128 only,
-// no VALU variant.  signs: this layer's [n_kv][k, v][head_dim]
-void tq_inverse_factors(uint32_t head_dim, float* inv_scale, float* inv_d);   // attention_tq.hip
-hipError_t attn_prefill_tq_launch(const float* q, const float* kscr, const float* vscr, const float* signs, uint32_t n_heads, uint32_t n_kv,
-                                  uint32_t head_dim, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st) {
-  if (n_kv == 0 || n_heads % n_kv || m_tokens == 0 || !signs || (head_dim != 64 && head_dim != 128)) return hipErrorInvalidValue;
-  PfTqEpi tq{signs, 0.0f, 0.0f};
-  tq_inverse_factors(head_dim, &tq.inv_scale, &tq.inv_d);
-  const uint32_t g = n_heads / n_kv;
-  return head_dim == 128 ? attn_pf_mfma_go<128, true>(q, kscr, vscr, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, tq)
-                         : attn_pf_mfma_go<64, true>(q, kscr, vscr, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st, tq);
 }
 
 // ------------------------------------------------------------------------------------------------
-// The block attention over a byte cache (int8 + scales, FP8 E4M3 / E5M2; FMT 1 / 2 / 3): attn_pf_mfma_kernel's geometry, merge and f16
+// The block attention over a byte cache (int8 + scales, FP8 E4M3 / E5M2; FMT 1 / 2 / 3): the same core (attn_block.h) and f16
 // store, with the cache's own bytes as the A operands.  Every token attends to the STORED rows, the block's own included
 // (kv8_pf_store_kernel ran before), which is what the token-by-token engine and the reference attend to.  Lane (n, c) takes
 // D/4 contiguous bytes of K row kv0 + n and D/16 contiguous bytes of each V row kv0 + 4c + i; the next tile travels as raw dwords
@@ -928,41 +825,25 @@ __global__ void __launch_bounds__(NW * 64) attn_pf_kv8_kernel(const float* __res
                                                               const float* __restrict__ ksc, const float* __restrict__ vsc, uint32_t n_heads,
                                                               uint32_t g_per_kv, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens,
                                                               uint8_t* __restrict__ xh_out) {
-  constexpr int DJ = D / 4;    // contraction steps of S^T (bytes of a K row per lane)
-  constexpr int DQ = D / 16;   // output dims per M index (bytes of a V row per lane)
-  constexpr int DP = D + 4;    // padded row of the merge buffer
-  constexpr int KW = DJ / 4, VW = DQ / 4;   // dwords of the K fragment, of one V row's fragment
-  extern __shared__ __attribute__((aligned(16))) float pf_lds[];
-  float (*s_o)[16][DP] = reinterpret_cast<float (*)[16][DP]>(pf_lds);                 // [NW][16][DP]
-  float (*s_m)[16] = reinterpret_cast<float (*)[16]>(pf_lds + NW * 16 * DP);          // [NW][16]
-  float (*s_l)[16] = s_m + NW;
-  const uint32_t head = blockIdx.x, tt = blockIdx.y, kvh = head / g_per_kv;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
-  const uint32_t tok = tt * 16 + n, tokc = tok < m_tokens ? tok : m_tokens - 1;
-  const uint32_t kv_last = pos0 + m_tokens - 1;                               // last cached row
-  const uint32_t n_tiles = (pos0 + tt * 16 + 16 + 15) / 16;                   // tiles the last token of this tile can see
+  using Core = AttnBlockCore<D, NW>;
+  constexpr int DJ = Core::DJ, DQ = Core::DQ;   // bytes of a K row, of a V row per lane
+  constexpr int KW = DJ / 4, VW = DQ / 4;       // dwords of the K fragment, of one V row's fragment
+  Core b(g_per_kv, pos0, m_tokens);
+  const uint32_t n = b.n, c = b.c;
   float qf[DJ];
-  {
-    const float* qp = q + ((size_t)tokc * n_heads + head) * D + c * DJ;
-#pragma unroll
-    for (int j = 0; j < DJ; j += 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(qp + j);
-      qf[j] = v.x; qf[j + 1] = v.y; qf[j + 2] = v.z; qf[j + 3] = v.w;
-    }
-  }
-  const size_t hrow = (size_t)kvh * max_seq;   // first row of this kv head
+  b.load_q(qf, q, n_heads, m_tokens);
+  const size_t hrow = (size_t)b.kvh * max_seq;   // first row of this kv head
   float m_run = kNegBig, l_run = 0.0f;
-  f32x4 acc[DQ];
+  f32x4 acc[DQ];   // acc[x][i] = O^T[dim DQ (4c + i) + x][token n] of this wave's tiles
 #pragma unroll
   for (int x = 0; x < DQ; x++) acc[x] = (f32x4)(0.0f);
   // a tile's raw K fragment (row kv0 + n, bytes [c DJ, (c+1) DJ)), V fragments (rows kv0 + 4c + i, bytes [n DQ, (n+1) DQ)) and, int8,
-  // the K and V scales of rows kv0 + 4c + i (the rows of this lane's scores); rows past the block are clamped here and masked below
+  // the K and V scales of rows kv0 + 4c + i (the rows of this lane's scores)
   uint32_t kn[KW], vn[4][VW];
   float ksn[4], vsn[4];
   auto load_tile = [&](uint32_t tile) {
     const uint32_t kv0 = tile * 16;
-    const uint32_t kr = kv0 + n < kv_last ? kv0 + n : kv_last;
-    const uint8_t* kp = kc + (hrow + kr) * D + c * DJ;
+    const uint8_t* kp = kc + (hrow + b.row(kv0 + n)) * D + c * DJ;
 #pragma unroll
     for (int j = 0; j < KW; j += 4) {
       const u32x4 v = *reinterpret_cast<const u32x4*>(kp + 4 * j);
@@ -970,7 +851,7 @@ __global__ void __launch_bounds__(NW * 64) attn_pf_kv8_kernel(const float* __res
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      const uint32_t r = kv0 + 4 * c + i, vr = r < kv_last ? r : kv_last;
+      const uint32_t vr = b.row(kv0 + 4 * c + i);
       const uint8_t* vp = vc + (hrow + vr) * D + n * DQ;
       if (VW == 2) {
         const u32x2 v = *reinterpret_cast<const u32x2*>(vp);
@@ -981,9 +862,8 @@ __global__ void __launch_bounds__(NW * 64) attn_pf_kv8_kernel(const float* __res
       if (FMT == 1) { ksn[i] = ksc[hrow + vr]; vsn[i] = vsc[hrow + vr]; }
     }
   };
-  if (wave < n_tiles) load_tile(wave);
-  for (uint32_t tile = wave; tile < n_tiles; tile += NW) {
-    const uint32_t kv0 = tile * 16;
+  if (b.wave < b.n_tiles) load_tile(b.wave);
+  for (uint32_t tile = b.wave; tile < b.n_tiles; tile += NW) {
     uint32_t kf[KW], vf[4][VW];
     float ks[4], vs[4];
 #pragma unroll
@@ -994,7 +874,7 @@ __global__ void __launch_bounds__(NW * 64) attn_pf_kv8_kernel(const float* __res
       for (int x = 0; x < VW; x++) vf[i][x] = vn[i][x];
       if (FMT == 1) { ks[i] = ksn[i]; vs[i] = vsn[i]; }
     }
-    if (tile + NW < n_tiles) load_tile(tile + NW);   // the next tile's bytes are in flight while this one is computed
+    if (tile + NW < b.n_tiles) load_tile(tile + NW);   // the next tile's bytes are in flight while this one is computed
     f32x4 st = (f32x4)(0.0f);
 #pragma unroll
     for (int j = 0; j < KW; j++) {
@@ -1002,29 +882,12 @@ __global__ void __launch_bounds__(NW * 64) attn_pf_kv8_kernel(const float* __res
 #pragma unroll
       for (int e = 0; e < 4; e++) st = __builtin_amdgcn_mfma_f32_16x16x4f32(k4[e], qf[4 * j + e], st, 0, 0, 0);
     }
-    // st[i] = <q(token n), k(row kv0 + 4c + i)> (int8: before the row's scale); token n sees rows <= pos0 + tok
-    float sv[4], mx = kNegBig;
-    bool ok[4];
+    if (FMT == 1) {   // an int8 row's scale on its score
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-      ok[i] = kv0 + 4 * c + i <= pos0 + tok;
-      const float s = FMT == 1 ? st[i] * ks[i] : st[i];
-      sv[i] = ok[i] ? s * scale : kNegBig;
-      mx = fmaxf(mx, sv[i]);
+      for (int i = 0; i < 4; i++) st[i] = st[i] * ks[i];
     }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mn = fmaxf(m_run, mx);
-    const float alpha = __expf(m_run - mn);
-    float pv[4], ps = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { pv[i] = ok[i] ? __expf(sv[i] - mn) : 0.0f; ps += pv[i]; }
-    ps += __shfl_xor(ps, 16, 64);
-    ps += __shfl_xor(ps, 32, 64);
-    l_run = __builtin_fmaf(l_run, alpha, ps);
-    m_run = mn;
-#pragma unroll
-    for (int x = 0; x < DQ; x++) acc[x] = acc[x] * alpha;
+    float pv[4];
+    b.update(st, tile * 16, pos0, scale, m_run, l_run, acc, pv);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const float p = FMT == 1 ? pv[i] * vs[i] : pv[i];
@@ -1036,61 +899,69 @@ __global__ void __launch_bounds__(NW * 64) attn_pf_kv8_kernel(const float* __res
       }
     }
   }
-  // acc[x][i] = O^T[dim DQ (4c + i) + x][token n] of this wave's tiles; the merge and the store are attn_pf_mfma_kernel's
-  if (c == 0) { s_m[wave][n] = m_run; s_l[wave][n] = l_run; }
-#pragma unroll
-  for (int x = 0; x < DQ; x++) {
-    s_o[wave][n][DQ * (4 * c + 0) + x] = acc[x].x;
-    s_o[wave][n][DQ * (4 * c + 1) + x] = acc[x].y;
-    s_o[wave][n][DQ * (4 * c + 2) + x] = acc[x].z;
-    s_o[wave][n][DQ * (4 * c + 3) + x] = acc[x].w;
-  }
-  __syncthreads();
-  for (uint32_t e = threadIdx.x; e < 16u * D; e += NW * 64) {
-    const uint32_t t = e / D, dim = e % D;
-    if (tt * 16 + t >= m_tokens) continue;
-    float mn = s_m[0][t];
-#pragma unroll
-    for (int w = 1; w < NW; w++) mn = fmaxf(mn, s_m[w][t]);
-    float lsum = 0.0f, a = 0.0f;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-      const float f = expf(s_m[w][t] - mn);
-      lsum += s_l[w][t] * f;
-      a += s_o[w][t][dim] * f;
-    }
-    const _Float16 o = (_Float16)(a * (1.0f / lsum));   // simd.rs:718-720: multiply by 1/sum
-    *reinterpret_cast<_Float16*>(xh_out + xh_offset(tt * 16 + t, head * D + dim)) = o;
-  }
+  b.stash(m_run, l_run, acc);
+  b.merge(m_tokens, [&](uint32_t t, uint32_t dim, float o) { pf_xh_store(xh_out, b.tt * 16 + t, b.head * D + dim, o); });
 }
 
-template <int D, int FMT>
-static hipError_t attn_pf_kv8_go(const float* q, const KvCache& kv, uint32_t n_heads, uint32_t g, uint32_t max_seq, float scale, uint32_t pos0,
-                                 uint32_t m_tokens, uint8_t* xh_out, hipStream_t st) {
-  constexpr int NW = 8;
-  constexpr size_t lds = (size_t)(NW * 16 * (D + 4) + 2 * NW * 16) * 4;
+// ---- host: the block attention's one launch (common.h: AttnBlock) ----
+void tq_inverse_factors(uint32_t head_dim, float* inv_scale, float* inv_d);   // attention_tq.hip
+
+// the LDS opt-in and the grid of whichever kernel was picked: n_heads x token tiles of NW waves
+template <auto Kernel, int D, int NW, typename... Args>
+static hipError_t attn_block_go(const AttnBlock& a, Args... args) {
+  constexpr size_t lds = AttnBlockCore<D, NW>::kLdsBytes;
   static bool attr_set[64] = {};
-  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&attn_pf_kv8_kernel<D, NW, FMT>), (int)lds, attr_set); e != hipSuccess) return e;
-  hipLaunchKernelGGL((attn_pf_kv8_kernel<D, NW, FMT>), dim3(n_heads, (m_tokens + 15) / 16), dim3(NW * 64), lds, st, q, kv.k_bytes(), kv.v_bytes(), kv.kscale(),
-                     kv.vscale(), n_heads, g, max_seq, scale, pos0, m_tokens, xh_out);
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(Kernel), (int)lds, attr_set); e != hipSuccess) return e;
+  hipLaunchKernelGGL(Kernel, dim3(a.n_heads, (a.m_tokens + 15) / 16), dim3(NW * 64), lds, a.st, args...);
   return hipGetLastError();
 }
 
-// type: LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2; kv: [n_kv][max_seq][head_dim] bytes (+ [n_kv][max_seq] scales, int8); head_dim 64 or 128,
-// 1 / 2 / 4 / 8 query heads per kv head — a property of the callers (pf_eligible), the kernel takes any divisor
-hipError_t attn_prefill_kv8_launch(uint32_t type, const float* q, const KvCache& kv, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq,
-                                   float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st) {
-  if (type < LGH_KV_INT8 || type > LGH_KV_FP8_E5M2 || (head_dim != 64 && head_dim != 128) || n_kv == 0 || n_heads % n_kv || m_tokens == 0 ||
-      (uint64_t)pos0 + m_tokens > max_seq)
+// (The formats in this order, f32's VALU fallback between f32 and TurboQuant, head_dim 128 before 64: kernels are emitted in the order
+// of their first use, and the code object keeps the kernel order it was measured with — the launch-description note under profiles/)
+hipError_t attn_block_launch(const KvLayout& l, const KvCache& kv, const AttnBlock& a) {
+  if (l.type > LGH_KV_TQ3_QJL || l.n_kv == 0 || a.n_heads % l.n_kv || a.m_tokens == 0 || (uint64_t)a.pos0 + a.m_tokens > l.max_seq || l.qjl() ||
+      (l.tq() && (!a.signs || !a.tq_kv)))
     return hipErrorInvalidValue;
-  const uint32_t g = n_heads / n_kv;
-  auto go = [&](auto d) {
+  constexpr int NW = 8;   // (4 waves: 11.7 us per layer of a 128-token Llama-3-8B prompt, the last token tile's waves take two kv tiles each)
+  const uint32_t g = a.n_heads / l.n_kv;
+  const bool mfma_shape = l.d == 128 || l.d == 64;   // the matrix-core kernels' head sizes
+  auto by_head_dim = [&](auto go) { return l.d == 128 ? go(std::integral_constant<int, 128>{}) : go(std::integral_constant<int, 64>{}); };
+  if (l.f32()) {
+    // (read once per process: tests/test_gpu_fresh_env.py::test_valu_prompt_attention holds the VALU kernel to test_prefill's bound)
+    static const bool valu = [] { const char* e = std::getenv("LGH_PF_ATTN_VALU"); return e && std::atoi(e) != 0; }();   // (A/B switch: the VALU kernel)
+    if (!valu && mfma_shape)
+      return by_head_dim([&](auto d) {
+        constexpr int D = decltype(d)::value;
+        return attn_block_go<&attn_pf_mfma_kernel<D, NW, false>, D, NW>(a, a.q, kv.k_f32(), kv.v_f32(), a.n_heads, g, l.max_seq, a.scale, a.pos0, a.m_tokens,
+                                                                        a.xh_out, PfTqEpi{});
+      });
+    // 4 waves per (kv head, token) workgroup: 8 and 16 waves measured slower on the 128-token Llama-3-8B prompt (4.79 / 5.07 vs
+    // 4.74 ms per prompt pass) — the grid is already 1024 workgroups wide.
+    return attn_dispatch(l.d, g, [&](auto d, auto gg) {
+      hipLaunchKernelGGL((attn_partial_kernel<decltype(d)::value, decltype(gg)::value, 4, true>), dim3(l.n_kv, a.m_tokens), dim3(256), 0, a.st, a.q, kv.k_f32(),
+                         kv.v_f32(), l.max_seq, a.scale, (const int*)nullptr, (int)(a.pos0 + 1), 1u, (float*)nullptr, reinterpret_cast<float*>(a.xh_out));
+      return hipGetLastError();
+    });
+  }
+  if (!mfma_shape) return hipErrorInvalidValue;
+  if (l.tq())   // over the prompt pass's scratch (tq_pf_rows_launch filled it and rotated q)
+    return by_head_dim([&](auto d) {
+      constexpr int D = decltype(d)::value;
+      PfTqEpi tq{a.signs, 0.0f, 0.0f};
+      tq_inverse_factors(D, &tq.inv_scale, &tq.inv_d);
+      return attn_block_go<&attn_pf_mfma_kernel<D, NW, true>, D, NW>(a, a.q, a.tq_kv, a.tq_kv + l.stride_floats(), a.n_heads, g, l.max_seq, a.scale, a.pos0,
+                                                                     a.m_tokens, a.xh_out, tq);
+    });
+  return by_head_dim([&](auto d) {
     constexpr int D = decltype(d)::value;
-    return type == LGH_KV_INT8       ? attn_pf_kv8_go<D, 1>(q, kv, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st)
-           : type == LGH_KV_FP8_E4M3 ? attn_pf_kv8_go<D, 2>(q, kv, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st)
-                                     : attn_pf_kv8_go<D, 3>(q, kv, n_heads, g, max_seq, scale, pos0, m_tokens, xh_out, st);
-  };
-  return head_dim == 128 ? go(std::integral_constant<int, 128>{}) : go(std::integral_constant<int, 64>{});
+    auto go = [&](auto fmt) {
+      return attn_block_go<&attn_pf_kv8_kernel<D, NW, decltype(fmt)::value>, D, NW>(a, a.q, kv.k_bytes(), kv.v_bytes(), kv.kscale(), kv.vscale(), a.n_heads, g,
+                                                                                    l.max_seq, a.scale, a.pos0, a.m_tokens, a.xh_out);
+    };
+    return l.type == LGH_KV_INT8       ? go(std::integral_constant<int, 1>{})
+           : l.type == LGH_KV_FP8_E4M3 ? go(std::integral_constant<int, 2>{})
+                                       : go(std::integral_constant<int, 3>{});
+  });
 }
 
 // Attention of one query row for any head_dim (256 threads): scores of the `visible` rows in LDS (sc), the arithmetic of

@@ -275,6 +275,22 @@ struct AttnDecode {
 // the partial launch for the layout's format (n_splits ranges per kv head -> part_ml / part_acc), and the merge of its partials
 hipError_t attn_split_launch(const KvLayout& l, const KvCache& kv, const AttnDecode& a);
 hipError_t attn_merge_launch(const KvLayout& l, const AttnDecode& a);
+// The causal attention of a block of m_tokens prompt tokens at positions pos0 .. pos0 + m_tokens - 1 over one layer's cache, their K / V
+// rows already stored: everything but the cache, as AttnDecode.  Host-only, built on the stack.
+struct AttnBlock {
+  uint32_t n_heads;
+  float scale;
+  const float* q;            // [token][n_heads][head_dim]; TurboQuant: rotated (tq_pf_rows_launch)
+  uint32_t pos0, m_tokens;
+  const float* tq_kv;        // TurboQuant: the f32 scratch the attention reads instead of the codes (tq_pf_rows_launch filled it), K, then V
+                             // at KvLayout::stride_floats()
+  const float* signs;        // TurboQuant: this layer's [n_kv][k, v][head_dim] rotation signs
+  uint8_t* xh_out;           // the wo GEMM's input: the f16 XH matrix [token][n_heads * head_dim] (prefill.h)
+  hipStream_t st;
+};
+// the launch for the layout's format: f32 (any head_dim and group size the decode kernels take; 64 / 128 on the matrix cores), TQ2 / TQ3
+// and int8 / FP8 (head_dim 64 / 128).  QJL formats and cache slots of a TurboQuant cache have no block attention
+hipError_t attn_block_launch(const KvLayout& l, const KvCache& kv, const AttnBlock& a);
 hipError_t attn_direct_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
                               uint32_t max_seq, float scale, const int* pos, float* out, uint8_t* xq_out, hipStream_t st);
 // one workgroup per query head (attention.hip: attn_head_kernel); max_rows: the longest context the caller will launch it at —
@@ -288,19 +304,14 @@ hipError_t kv_roundtrip_launch(int fmt, const float* x, uint32_t n, uint8_t* byt
 hipError_t tq_compress_launch(int bits, const float* x, uint32_t dim, const float* signs, uint8_t* out, hipStream_t st, const float* qjl_s = nullptr,
                               uint32_t* qjl_out = nullptr);
 uint32_t tq_row_bytes_host(int bits, uint32_t d);
-// the prompt pass over a TurboQuantMSE cache: the block's row work on the f32 scratch (attention_tq.hip) and the block attention over it
-// (attention.hip)
+// the prompt pass over a TurboQuantMSE cache: the block's row work on the f32 scratch (attention_tq.hip; attn_block_launch attends over it)
 hipError_t tq_pf_rows_launch(int bits, float* kscr, float* vscr, uint8_t* kq, uint8_t* vq, float* q, const float* signs, uint32_t n_heads,
                              uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, uint32_t pos0, uint32_t m_store, uint32_t m_q, uint32_t n_expand,
                              hipStream_t st);
-hipError_t attn_prefill_tq_launch(const float* q, const float* kscr, const float* vscr, const float* signs, uint32_t n_heads, uint32_t n_kv,
-                                  uint32_t head_dim, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st);
 // the batched prompt pass over a byte cache (LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2; attention.hip): the block's f32 rows [n_kv][src_rows][head_dim]
-// into cache rows pos0 .. pos0+m-1, and the block attention over the stored bytes
+// into cache rows pos0 .. pos0+m-1 (attn_block_launch attends over the stored bytes)
 hipError_t kv8_pf_store_launch(uint32_t type, const float* krows, const float* vrows, uint32_t src_rows, const KvCache& kv, uint32_t n_kv,
                                uint32_t head_dim, uint32_t max_seq, uint32_t pos0, uint32_t m, hipStream_t st);
-hipError_t attn_prefill_kv8_launch(uint32_t type, const float* q, const KvCache& kv, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim, uint32_t max_seq,
-                                   float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out, hipStream_t st);
 hipError_t attn_decode_any_launch(const float* q, const float* kcache, const float* vcache, float* out, uint32_t n_heads, uint32_t n_kv,
                                   uint32_t head_dim, uint32_t max_seq, float scale, const int* pos, hipStream_t st);
 hipError_t attn_generic_launch(const float* q, const float* k, const float* v, float* out, uint32_t n_heads, uint32_t n_kv, uint32_t seq_len,

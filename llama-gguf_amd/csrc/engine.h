@@ -289,6 +289,7 @@ int pf_block_input(lgh_ctx* c, const float* nw, uint32_t m);
 // cache_rows: rows per kv head of kcache / vcache whose row 0 is position 0 (0: max_seq_len, a whole cache).  The byte caches' block scratch
 // has 128 rows per head and row 0 = position pos0: the caller passes 128 and bases shifted back by pos0 rows
 int pf_qkv_step(lgh_ctx* c, lgh::LayerW& L, float* kcache, float* vcache, uint32_t pos0, uint32_t m, uint32_t cache_rows = 0);
+int pf_attn_step(lgh_ctx* c, uint32_t li, const lgh::KvCache& kv, uint32_t pos0, uint32_t m);
 int pf_wo_step(lgh_ctx* c, lgh::LayerW& L, uint32_t m);
 int pf_ffn_step(lgh_ctx* c, lgh::LayerW& L, const float* next_nw, uint32_t m);
 int pf_moe_step(lgh_ctx* c, lgh::LayerW& L, const float* next_nw, uint32_t m);

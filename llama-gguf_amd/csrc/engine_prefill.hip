@@ -138,6 +138,23 @@ static int pf_kv8_store(lgh_ctx* c, const KvCache& kv, uint32_t pos0, uint32_t m
               "byte cache rows");
 }
 
+// q in pf.q + the stored rows 0 .. pos0+m-1 of layer li's cache kv (a TurboQuant cache: of the scratch pf.tq_kv) -> XH(attention output)
+// in pf.xh_attn
+int pf_attn_step(lgh_ctx* c, uint32_t li, const KvCache& kv, uint32_t pos0, uint32_t m) {
+  PfScratch& P = c->pf;
+  AttnBlock a{};
+  a.n_heads = c->d.num_heads;
+  a.scale = 1.0f / std::sqrt((float)c->d.head_dim);   // layers.rs:374
+  a.q = P.q;
+  a.pos0 = pos0;
+  a.m_tokens = m;
+  a.tq_kv = P.tq_kv;
+  a.signs = c->kvl.tq() ? tq_layer(c, li).signs : nullptr;
+  a.xh_out = P.xh_attn;
+  a.st = c->stream;
+  return pf_k(c, attn_block_launch(c->kvl, kv, a), "attention");
+}
+
 // XH(attention output) in pf.xh_attn -> pf.hidden += wo . attn (+ bo), XH(h * ffn_norm) in pf.xh_h, sums of squares in pf.ssq
 int pf_wo_step(lgh_ctx* c, LayerW& L, uint32_t m) {
   PfScratch& P = c->pf;
@@ -238,10 +255,8 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
   PfScratch& P = c->pf;
   const lgh_model_desc& d = c->d;
   const uint32_t pos0 = (uint32_t)t.pos0;
-  hipStream_t st = c->stream;
   if (c->first && (rc = pf_embed_tokens(c, pos0, tokens, m))) return rc;
   if ((rc = pf_block_input(c, c->layers[c->l0].attn_norm, m))) return rc;
-  const float scale = 1.0f / std::sqrt((float)d.head_dim);  // layers.rs:374
   const bool tq = c->kvl.tq(), kv8 = pf_kv8(c);
   if (tq && t.slot >= 0) return fail(c, LGH_UNSUPPORTED, "TurboQuant slots have no batched prompt path");
   for (uint32_t li = c->l0; li < c->l1; li++) {
@@ -257,18 +272,7 @@ int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_
     if (tq && (rc = pf_tq_rows(c, L, li, pos0, m, attend))) return rc;
     if (kv8 && (rc = pf_kv8_store(c, kv, pos0, m))) return rc;
     if (!attend) break;
-    if (kv8) {
-      rc = pf_k(c, attn_prefill_kv8_launch(d.kv_cache_type, P.q, kv, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
-                "attention");
-    } else if (tq) {
-      rc = pf_k(c, attn_prefill_tq_launch(P.q, kcache, vcache, tq_layer(c, li).signs, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m,
-                                          P.xh_attn, st),
-                "attention");
-    } else {
-      rc = pf_k(c, attn_prefill_launch(P.q, kcache, vcache, d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, pos0, m, P.xh_attn, st),
-                "attention");
-    }
-    if (rc) return rc;
+    if ((rc = pf_attn_step(c, li, kv, pos0, m))) return rc;
     if ((rc = pf_wo_step(c, L, m))) return rc;
     const float* next_nw = li + 1 < c->l1 ? c->layers[li + 1].attn_norm : nullptr;   // nullptr: the block goes to the next stage as f32
     if ((rc = L.moe() ? pf_moe_step(c, L, next_nw, m) : pf_ffn_step(c, L, next_nw, m))) return rc;

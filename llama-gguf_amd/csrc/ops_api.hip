@@ -752,6 +752,21 @@ static int xh_down(Tmp& t, const uint8_t* xh, size_t m, size_t k, float* out) {
   return LGH_OK;
 }
 
+// what the three block-attention entry points share once their cache is on the device: the block's queries dq (uploaded by the
+// caller; a TurboQuant cache: rotated by now, scr its filled scratch, signs the layer's), a zeroed XH, the launch, the XH's rows as f32.
+// refused: the status of a launch that did not start
+static int attn_block_run(Tmp& t, const KvLayout& l, const KvCache& kv, const float* dq, const float* scr, const float* signs, size_t n_heads, float scale,
+                          size_t pos0, size_t m_tokens, int refused, float* out) {
+  const size_t qd = n_heads * l.d, xb = xh_bytes((uint32_t)qd);
+  uint8_t* xh = (uint8_t*)up_bytes(t, nullptr, xb);
+  if (!dq || !xh) return LGH_ALLOCATION_FAILED;
+  hipStream_t st = t.c->stream;
+  if (hipMemsetAsync(xh, 0, xb, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  const AttnBlock a{(uint32_t)n_heads, scale, dq, (uint32_t)pos0, (uint32_t)m_tokens, scr, signs, xh, st};
+  if (attn_block_launch(l, kv, a) != hipSuccess) return refused;
+  return xh_down(t, xh, m_tokens, qd, out);
+}
+
 int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, const float* v_cache, float* out, size_t n_heads, size_t n_kv,
                              size_t head_dim, size_t max_seq, float scale, size_t pos0, size_t m_tokens) {
   // causal Backend::attention (ops.rs:1353-1472) of a block of prompt tokens as the batched prefill runs it: the f16 XH matrix that
@@ -759,18 +774,13 @@ int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, c
   Tmp t(device);
   if (t.rc) return t.rc;
   if (!q || !k_cache || !v_cache || !out || n_kv == 0 || n_heads % n_kv || max_seq > 0x7FFFFFFFu) return LGH_INVALID_ARGUMENT;
-  const size_t qd = n_heads * head_dim, cache = n_kv * max_seq * head_dim;
+  const size_t qd = n_heads * head_dim;
   if (m_tokens == 0 || m_tokens > (size_t)kPfTokens || qd % 256 || pos0 + m_tokens > max_seq) return LGH_INVALID_ARGUMENT;
-  float *dq = t.up(q, m_tokens * qd), *dk = t.up(k_cache, cache), *dv = t.up(v_cache, cache);
-  const size_t xb = xh_bytes((uint32_t)qd);
-  uint8_t* xh = (uint8_t*)up_bytes(t, nullptr, xb);
-  if (!dq || !dk || !dv || !xh) return LGH_ALLOCATION_FAILED;
-  hipStream_t st = t.c->stream;
-  if (hipMemsetAsync(xh, 0, xb, st) != hipSuccess) return LGH_OPERATION_FAILED;
-  if (attn_prefill_launch(dq, dk, dv, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, scale, (uint32_t)pos0,
-                          (uint32_t)m_tokens, xh, st) != hipSuccess)
-    return LGH_UNSUPPORTED;
-  return xh_down(t, xh, m_tokens, qd, out);
+  const KvLayout l(LGH_KV_F32, n_kv, max_seq, head_dim);
+  KvCache kv;
+  const void* const host[KV_KINDS] = {k_cache, v_cache};
+  if (int rc = kv_upload(t, l, 1, host, kv)) return rc;
+  return attn_block_run(t, l, kv, t.up(q, m_tokens * qd), nullptr, nullptr, n_heads, scale, pos0, m_tokens, LGH_UNSUPPORTED, out);
 }
 
 // the f32 scratch of the TurboQuant prompt pass, NaN-filled: K then V, each [n_kv][max_seq][head_dim]
@@ -865,18 +875,11 @@ int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float*
   KvCache kv;
   const void* const codes[KV_KINDS] = {k_codes, v_codes};
   if (int rc = kv_upload(t, l, 1, codes, kv)) return rc;
-  const size_t xb = xh_bytes((uint32_t)qd);
-  uint8_t* xh = (uint8_t*)up_bytes(t, nullptr, xb);
-  if (!dq || !ds || !scr || !xh) return LGH_ALLOCATION_FAILED;
-  hipStream_t st = t.c->stream;
-  if (hipMemsetAsync(xh, 0, xb, st) != hipSuccess) return LGH_OPERATION_FAILED;
+  if (!dq || !ds || !scr) return LGH_ALLOCATION_FAILED;
   if (tq_pf_rows_launch(l.tq_bits(), scr, scr + cache, kv.k_bytes(), kv.v_bytes(), dq, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, (uint32_t)pos0, 0,
-                        (uint32_t)m_tokens, (uint32_t)(pos0 + m_tokens), st) != hipSuccess)
+                        (uint32_t)m_tokens, (uint32_t)(pos0 + m_tokens), t.c->stream) != hipSuccess)
     return LGH_OPERATION_FAILED;
-  if (attn_prefill_tq_launch(dq, scr, scr + cache, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, scale, (uint32_t)pos0,
-                             (uint32_t)m_tokens, xh, st) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  return xh_down(t, xh, m_tokens, qd, out);
+  return attn_block_run(t, l, kv, dq, scr, ds, n_heads, scale, pos0, m_tokens, LGH_OPERATION_FAILED, out);
 }
 
 int lgh_op_pf_kv8_store(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv, size_t head_dim,
@@ -917,19 +920,10 @@ int lgh_op_attention_prefill_kv8(int device, uint32_t kv_cache_type, const float
   if (g != 1 && g != 2 && g != 4 && g != 8) return LGH_UNSUPPORTED;   // (pf_eligible's group sizes)
   const size_t qd = n_heads * head_dim;
   if (m_tokens == 0 || m_tokens > (size_t)kPfTokens || qd % 256 || pos0 > max_seq || pos0 + m_tokens > max_seq) return LGH_INVALID_ARGUMENT;
-  float* dq = t.up(q, m_tokens * qd);
   KvCache kv;
   const void* const host[KV_KINDS] = {k_bytes, v_bytes, k_scales, v_scales};
   if (int rc = kv_upload(t, l, 1, host, kv)) return rc;
-  const size_t xb = xh_bytes((uint32_t)qd);
-  uint8_t* xh = (uint8_t*)up_bytes(t, nullptr, xb);
-  if (!dq || !xh) return LGH_ALLOCATION_FAILED;
-  hipStream_t st = t.c->stream;
-  if (hipMemsetAsync(xh, 0, xb, st) != hipSuccess) return LGH_OPERATION_FAILED;
-  if (attn_prefill_kv8_launch(kv_cache_type, dq, kv, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)head_dim, (uint32_t)max_seq, scale, (uint32_t)pos0,
-                              (uint32_t)m_tokens, xh, st) != hipSuccess)
-    return LGH_OPERATION_FAILED;
-  return xh_down(t, xh, m_tokens, qd, out);
+  return attn_block_run(t, l, kv, t.up(q, m_tokens * qd), nullptr, nullptr, n_heads, scale, pos0, m_tokens, LGH_OPERATION_FAILED, out);
 }
 
 // ---- device-resident weights by tensor name: CudaBackend::load_model_weights + the `b.name()` lookups of its vec_mat /

@@ -69,10 +69,6 @@ hipError_t pf_to_xh_launch(const float* x, uint32_t K, uint8_t* xh, uint32_t m_t
 // dequant.hip: rows tokens[0..m) of the embedding table -> dst[m][hidden]
 hipError_t embed_batch_launch(int src_type, const uint8_t* table, const int* tokens, float* dst, uint32_t hidden, uint32_t m_tokens,
                               hipStream_t st);
-// attention.hip: causal attention of a block of m tokens at positions pos0 .. pos0+m-1 (their K/V rows already cached)
-hipError_t attn_prefill_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv,
-                               uint32_t head_dim, uint32_t max_seq, float scale, uint32_t pos0, uint32_t m_tokens, uint8_t* xh_out,
-                               hipStream_t st);
 // byte offset of element k of token t in an XH matrix
 __host__ __device__ inline size_t xh_offset(uint32_t t, uint32_t k) {
   const uint32_t ch = k >> 3, j = k & 7, pj = (j == 1 || j == 5) ? j + 1 : (j == 2 || j == 6) ? j - 1 : j;

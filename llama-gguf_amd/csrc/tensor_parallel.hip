@@ -541,20 +541,15 @@ int tp_prefill_block(lgh_tp* t, const uint32_t* tokens, uint32_t m) {
     RANK_TRY(r, pf_embed_tokens(c, pos0, tokens, m));
     RANK_TRY(r, pf_block_input(c, c->layers[0].attn_norm, m));
   }
-  const float scale = 1.0f / std::sqrt((float)d.head_dim);   // layers.rs:374
   for (uint32_t li = 0; li < d.num_layers; li++) {
     const bool attend = li + 1 < d.num_layers;   // the model's last layer: its K / V rows are written, its output would be discarded
     for (size_t r = 0; r < n; r++) {   // own heads into own cache rows, block attention over them, wo over the k-shard
       lgh_ctx* c = t->rank[r];
       LayerW& L = c->layers[li];
       PfScratch& P = c->pf;
-      const lgh_model_desc& rd = c->d;
       RANK_TRY(r, pf_qkv_step(c, L, L.kv.k_f32(), L.kv.v_f32(), pos0, m));
       if (!attend) continue;
-      if ((rc = tp_pf_k(t, r, attn_prefill_launch(P.q, L.kv.k_f32(), L.kv.v_f32(), rd.num_heads, rd.num_kv_heads, rd.head_dim, rd.max_seq_len, scale, pos0, m,
-                                                  P.xh_attn, c->stream),
-                        "attention")))
-        return rc;
+      RANK_TRY(r, pf_attn_step(c, li, L.kv, pos0, m));
       uint32_t S = 0, nc = 0;
       const DevWeight* wo[1] = {&L.wo};
       if ((rc = tp_pf_k(t, r, pf_gemm_launch(wo, 1, P.xh_attn, P.part, P.part_bytes, m, &S, &nc, c->stream), "wo GEMM"))) return rc;

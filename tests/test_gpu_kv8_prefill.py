@@ -218,6 +218,28 @@ def test_every_fp8_code_as_a_k_element(gpu, orc, kvt):
             assert ratio <= 1.0, f"d={d} dims {g * c}..{g * c + g - 1}: err / bound = {ratio:.3g}"
 
 
+@pytest.mark.parametrize("d", [64, 128])
+@pytest.mark.parametrize("kvt", [kr.KV_FP8_E4M3, kr.KV_FP8_E5M2], ids=["e4m3", "e5m2"])
+def test_fp8_block_equals_f32_block_over_decoded_bytes(gpu, orc, kvt, d):
+    """attn_pf_kv8_kernel and attn_pf_mfma_kernel share their softmax core (csrc/attn_block.h) and feed identical f32 operands to the
+    same matrix instructions in the same order: over the oracle's decoding of the bytes the f32 op gives the byte op's output bit for
+    bit (a -0 for the oracle's +0 changes no sum that starts at +0).  A part-filled token tile; a kv tile that straddles pos0 and ten
+    kv tiles over eight waves.  int8 is not held to this: its scale multiplies the score, not the elements."""
+    n_kv, g, max_seq = 2, 2, 160
+    table = ar.fp8_table(orc, kvt)
+    rng = np.random.default_rng([kvt, d, 4])
+    kb = rng.integers(0, 256, (n_kv, max_seq, d), dtype=np.uint8) & np.uint8(0xBF)   # magnitude below 2: no NaN or infinity codes
+    vb = rng.integers(0, 256, (n_kv, max_seq, d), dtype=np.uint8) & np.uint8(0xBF)
+    kc, vc = table[kb].astype(np.float32), table[vb].astype(np.float32)
+    assert np.isfinite(kc).all() and np.isfinite(vc).all()
+    for pos0, m in ((0, 17), (125, 21)):
+        q = rng.standard_normal((m, n_kv * g, d)).astype(np.float32)
+        got = gpu.op_attention_prefill_kv8(kvt, q, kb, vb, None, None, d ** -0.5, pos0)
+        want = gpu.op_attention_prefill(q, kc, vc, d ** -0.5, pos0)
+        assert np.isfinite(got).all()
+        assert np.array_equal(_bits(got), _bits(want)), f"pos0={pos0} m={m}: {np.count_nonzero(_bits(got) != _bits(want))} elements differ"
+
+
 def test_entry_points_refuse(gpu, pkg):
     q = np.zeros((4, 2, 128), np.float32)
     b = np.zeros((2, 64, 128), np.uint8)

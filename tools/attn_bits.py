@@ -5,14 +5,14 @@
 
 Every per-path entry point of the attention kernels is run on seeded inputs: op_attention_decode (split, direct, any),
 op_attention_cached, op_attention_decode_multi, op_attention_kv8 / _kv8_multi (cache types 1-3), op_attention_tq (cache types 4-7),
-op_attention_prefill and op_attention_prefill_tq — for head_dim 64 / 128 with 1, 2, 4, 8 query heads per kv head, (max_seq, pos) in
-{(1024, 0), (1024, 65), (1024, 1000), (4096, 4095)} and 1, 7, 32 splits where the path has splits; the multi-sequence forms with 3
-sequences in distinct slots at distinct positions.  A case's hash covers the output and, where the entry point returns the cache,
+op_attention_prefill, op_attention_prefill_tq (cache types 4, 5) and op_attention_prefill_kv8 (cache types 1-3) — for head_dim
+64 / 128 with 1, 2, 4, 8 query heads per kv head, (max_seq, pos) in {(1024, 0), (1024, 65), (1024, 1000), (4096, 4095)} and 1, 7,
+32 splits where the path has splits; the multi-sequence forms with 3 sequences in distinct slots at distinct positions.  A case's hash covers the output and, where the entry point returns the cache,
 the row the launch wrote.  The prefill op is run once more in a fresh process with LGH_PF_ATTN_VALU=1 (the only route to
 attn_partial_kernel<..., PF = true>).
 
 --out gets one SHA-256 per (entry point, head_dim, group size): the digest of that group's case names and case hashes, in order
-(1440 cases in 152 groups; small enough to keep beside the code).  --full FILE writes the hash of every case as well, for finding
+(1536 cases in 176 groups; small enough to keep beside the code).  --full FILE writes the hash of every case as well, for finding
 the case once a group differs.  Two builds compute the same bits exactly when their files are equal.
 """
 import argparse
@@ -70,6 +70,13 @@ def prefill_cases(hb, res, tag, tq):
                 kcodes = rng.integers(0, 256, (PF_N_KV, max_seq, rb), dtype=np.uint8)
                 vcodes = rng.integers(0, 256, (PF_N_KV, max_seq, rb), dtype=np.uint8)
                 res[f"prefill_tq_t{t}/{key}"] = sha(hb.op_attention_prefill_tq(t, q, kcodes, vcodes, signs, d ** -0.5, pos0))
+            for t in (hb.KV_INT8, hb.KV_FP8_E4M3, hb.KV_FP8_E5M2):
+                i8 = t == hb.KV_INT8
+                kb = rng.integers(0, 256, (PF_N_KV, max_seq, d), dtype=np.uint8) if i8 else small_fp8(rng, (PF_N_KV, max_seq, d))
+                vb = rng.integers(0, 256, (PF_N_KV, max_seq, d), dtype=np.uint8) if i8 else small_fp8(rng, (PF_N_KV, max_seq, d))
+                ks = rng.uniform(0.002, 0.03, (PF_N_KV, max_seq)).astype(np.float32) if i8 else None
+                vs = rng.uniform(0.002, 0.03, (PF_N_KV, max_seq)).astype(np.float32) if i8 else None
+                res[f"prefill_kv8_t{t}/{key}"] = sha(hb.op_attention_prefill_kv8(t, q, kb, vb, ks, vs, d ** -0.5, pos0))
 
 
 def run(valu_only):
