@@ -311,7 +311,22 @@ int lgh_op_tq_compress_qjl(int device, int bits, const float* x, size_t dim, con
  * reference's BatchedEngine itself only ever creates f32 caches, engine_batched.rs:355-357.  Slots with a TurboQuant cache take
  * their prompt token by token (lgh_batch_prefill), and so do int8 / FP8 slots unless the context set LGH_PREFILL_BATCH_BYTE_KV
  * (lgh_set_prefill_policy).  The single-sequence entry points keep working on the context's own cache.  (A serving context is better created with 8 attention splits — flags bits 8..15 — than with
- * the single-sequence default: the split count also sizes the multi-sequence attention launch, profiles/r03e_batched_decode.md.) */
+ * the single-sequence default: the split count also sizes the multi-sequence attention launch, profiles/r03e_batched_decode.md.)
+ *
+ * lgh_set_batch_policy (after lgh_batch_create, between steps; unknown bits or no lgh_batch_create: InvalidArgument):
+ *   LGH_BATCH_DEFAULT      every step as described above.
+ *   LGH_BATCH_F32_MATRIX   steps of at least `minimum` sequences (bits 8..15 of the word; 0 = the library default, 11) run their
+ *                          quantized mat-vecs on the f32 matrix cores: every weight tile is dequantized once to f32 and multiplied
+ *                          with all sequences' f32 activations (matvec_batch_f32.hip).  The arithmetic is f32 x f32 -> f32, within the
+ *                          project's bound of the reference (2e-3 * max|logit| + 2e-3) but NOT bit-identical to lgh_forward; steps of
+ *                          fewer sequences, MoE expert launches and everything that is not a quantized mat-vec stay as they are.
+ * Every multi-sequence entry point honours the policy (lgh_forward_multi, lgh_decode_greedy_multi, lgh_decode_sample_multi, and
+ * lgh_batch_prefill's token-by-token route, whose steps have one sequence).  Setting it drops the captured multi-sequence graphs
+ * and runs one step per sequence bucket the policy reaches, eagerly, on slots that are not full (the row a step writes is the one the
+ * slot's next token overwrites; positions stay); with fewer such slots than a step needs — up to max(9, minimum), capped by max_batch —
+ * the call answers InvalidArgument and the context keeps the policy it had.  Policy 0 restores the default path, bit for bit.  measured: profiles/batch_f32.md */
+enum { LGH_BATCH_DEFAULT = 0, LGH_BATCH_F32_MATRIX = 1u << 0 };
+int lgh_set_batch_policy(lgh_ctx* ctx, uint32_t policy);
 int lgh_batch_create(lgh_ctx* ctx, uint32_t max_batch);                 /* BatchedEngineConfig::max_batch_size (engine_batched.rs:23-41) */
 int lgh_batch_reset(lgh_ctx* ctx, uint32_t slot);                       /* create_active_sequence: model.create_context (332-353); O(1) */
 size_t lgh_batch_position(lgh_ctx* ctx, uint32_t slot);                 /* ActiveSequence.ctx.position */
@@ -790,6 +805,11 @@ int lgh_op_moe_experts(int device, uint32_t type_gate_up, const void* w_gate, co
 int lgh_op_linear_multi(int device, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, size_t n_seq,
                         size_t max_batch, const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
                         float* out, uint8_t* image_out, float* ssq_out, int* image_used, int* structures);
+/* ... on a context with lgh_set_batch_policy's word `batch_policy`; structures: int[4], [3] = launches that ran as mvqf (the f32
+ * matrix-core kernel).  lgh_op_linear_multi is this with batch_policy 0. */
+int lgh_op_linear_multi_ex(int device, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, size_t n_seq,
+                           size_t max_batch, const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
+                           uint32_t batch_policy, float* out, uint8_t* image_out, float* ssq_out, int* image_used, int* structures);
 /* lgh_op_linear_chain for n_seq sequences: launch A (the SwiGLU pair or a residual launch, xq_next 1 or 2) leaves every sequence's
  * image; B (a store, [n_b][n_a]) runs on A's outputs from those images, then again after they were marked stale and converted afresh.
  * out_a [n_seq][n_a]; out_b, out_b_requant [n_seq][n_b]. */
@@ -804,6 +824,11 @@ int lgh_op_qkv_rope_multi(int device, const uint32_t* types, const void* const* 
                           float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t n_seq,
                           size_t max_batch, const int* pos, const int* slot, float rope_base, float rope_scale, int staged, float* q_out,
                           float* k_cache, float* v_cache, float* staged_out, int* structures);
+/* ... with a batch policy word and int[4] structures, as lgh_op_linear_multi_ex */
+int lgh_op_qkv_rope_multi_ex(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                             float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t n_seq,
+                             size_t max_batch, const int* pos, const int* slot, float rope_base, float rope_scale, int staged, uint32_t batch_policy,
+                             float* q_out, float* k_cache, float* v_cache, float* staged_out, int* structures);
 /* The grouped MoE half of a step on x [n_seq][hidden] (also the residual), n_seq >= 2: router (or the given sel / sel_w
  * [n_seq][top_k], a sequence's experts distinct), grouping, every expert's gate | up and down over its pairs, combine.  Expert stacks
  * as lgh_op_moe_experts.  out [max_batch][hidden]; image_out / ssq_out: the rows' XQ images (times next_nw) and sums of squares as
@@ -844,6 +869,8 @@ int lgh_op_argmax(int device, const float* logits, size_t n, size_t n_seq, int* 
 /* Multi-sequence mat-vec launches of this process per structure so far: out[0] mvqb, out[1] mvqb2 with the k-slices in the grid,
  * out[2] mvqb2 SEQ (tests: a launch whose partial-sum buffer is too small falls back to mvqb without a word). */
 void lgh_debug_mvqb_structures(uint64_t* out);
+/* ... and those that took the f32 matrix-core kernel (mvqf, lgh_set_batch_policy) */
+void lgh_debug_mvqf_launches(uint64_t* out);
 /* The batched prompt path's layer steps (prefill_block's own launch sequences), one at a time on a block of m_tokens <= 128 tokens,
  * for kernel-level tests.  Test support: not part of the inference API.  Weights are native GGUF bytes, row-major [out][in], of the
  * types the batched path takes (Q4_K, Q5_K, Q6_K, Q8_0, Q4_0); hidden_size % 256 == 0.  Before the first launch the scratch the kernels

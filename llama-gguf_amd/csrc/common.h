@@ -160,6 +160,8 @@ struct MvBatch {
   const int* slot;            // device [n_seq]
   uint64_t cache_stride;      // floats between the caches of two slots
   uint32_t xq_stride;         // bytes between the input XQ images of consecutive sequences
+  uint32_t x_stride;          // floats between their f32 input vectors (MvPass::x names sequence 0's; mvqf reads these, not the images)
+  uint32_t f32_min;           // 0: mvqb / mvqb2 only; else launches of at least this many sequences take mvqf (lgh_set_batch_policy)
   uint32_t ssq_stride;        // floats between their sum-of-squares partials
   uint32_t out_stride[3];     // per segment
   uint32_t resid_stride[3];
@@ -178,6 +180,15 @@ struct MvBatch {
   uint32_t ind_stride;
   uint32_t ind_nz;            // experts in the launch (grid z); 0 / 1: a single entry list
   uint64_t part_z_floats;     // (set by the launcher)
+};
+
+// the unit decomposition of a multi-sequence launch (matvec_batch.hip: mvqb2; matvec_batch_f32.hip: mvqf): a unit = one row tile of one pass
+struct Mvqb2Geom {
+  uint32_t T, nbw, nblk;      // the single-sequence kernel's k-slices
+  uint32_t n_units;           // sum over segments of npass * row tiles
+  uint32_t ub1, ub2;          // first unit of segment 1 / 2 (n_units when absent)
+  uint32_t cb;                // blocks staged per chunk (mvqb2)
+  uint32_t nslots;            // partial sums per (sequence, row) in the buffer: 1 (SEQ) or T
 };
 
 // launch-uniform geometry of one int8-MFMA launch as the kernel takes it (mvq_pack)
@@ -213,6 +224,14 @@ size_t mvqb_lds_bytes(uint32_t n_seq, uint32_t red_floats);
 uint64_t mvqb_part_floats(uint32_t k, uint32_t n_units, uint32_t n_seq, uint32_t nz);
 // launches of this process per structure: [0] mvqb, [1] mvqb2 with the k-slices as the grid's second dimension, [2] mvqb2 SEQ
 void mvqb_structure_launches(uint64_t out[3]);
+// matvec_batch_f32.hip: the f32 matrix-core first launch of a multi-sequence op (B.part in mvqb2's layout; mvqb_launch puts mvqb2's
+// epilogue launch behind it), its dynamic LDS, and this process's launches that took it
+hipError_t mvqf_launch(uint32_t mask, const Mvqb2Geom& Gm, const MvLaunch& L, const MvBatch& B, bool seq, uint32_t groups, hipStream_t st);
+size_t mvqf_lds_bytes();
+uint64_t mvqf_launches();
+// lgh_set_batch_policy: the minimum sequence count when the policy names none — the lowest measured count at which the f32 kernel's
+// step beats the default's (Llama-3-8B Q4_K_M: slower up to 10 sequences, faster from 11 on: profiles/batch_f32.md)
+constexpr uint32_t kBatchF32MinDefault = 11;
 hipError_t xq_quantize_launch(const float* x, const float* nw, uint8_t* xq, float* ssq_part, uint32_t k, hipStream_t st);
 hipError_t repack_t16_launch(int dev_type, const uint8_t* raw, uint8_t* dst, uint32_t n_rows, uint32_t nblk, hipStream_t st);
 hipError_t repack_q6k_t16_launch(const uint8_t* raw, uint8_t* dst, uint32_t n_rows, uint32_t nblk, hipStream_t st);  // LGH_SYM_MV_* of the instantiation mv_launch will pick

@@ -112,10 +112,15 @@ int launch_mvb(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float*
   B.ind_div = ind.div;
   B.ind_nz = ind.nz;
   B.ind_stride = ind.stride;
+  if (c->batch_policy & LGH_BATCH_F32_MATRIX) {   // (mvqb_launch: from that many sequences on, the f32 matrix-core kernel)
+    const uint32_t m = (c->batch_policy >> 8) & 0xFFu;
+    B.f32_min = m ? m : kBatchF32MinDefault;
+  }
   {   // the input vector's images lie at the strides its views were registered with
     const XqBuf* q0 = xq_find(c, specs[0].x[0]);
     const uint32_t kreg = q0 ? q0->k : k;
     B.xq_stride = xq_stride_of(kreg);
+    B.x_stride = kreg;
     B.ssq_stride = ssq_stride_of(kreg);
   }
   for (int s = 0; s < nseg; s++) {
@@ -513,6 +518,43 @@ int lgh_batch_create(lgh_ctx* c, uint32_t max_batch) {
     if ((rc = samp_warm(c, Bs.samp, Bs.logits, n))) return rc;
   Bs.ready = true;   // (only now: a context whose warm-up failed takes no step)
   return LGH_OK;
+}
+
+int lgh_set_batch_policy(lgh_ctx* c, uint32_t policy) {
+  int rc = check_ready(c);
+  if (rc) return rc;
+  BatchScratch& Bs = c->batch;
+  if (policy & ~((uint32_t)LGH_BATCH_F32_MATRIX | 0xFF00u)) return fail(c, LGH_INVALID_ARGUMENT, "unknown batch policy bits");
+  if (!Bs.ready) return fail(c, LGH_INVALID_ARGUMENT, "lgh_batch_create has not been called");
+  HIP_TRY(c, LGH_OPERATION_FAILED, hipStreamSynchronize(c->stream));
+  // the captured steps hold the launches of the policy they were captured under
+  for (auto& per_n : Bs.graph)
+    for (hipGraphExec_t& ge : per_n)
+      if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
+  const uint32_t before = c->batch_policy;
+  c->batch_policy = 0;
+  if (!(policy & LGH_BATCH_F32_MATRIX)) return LGH_OK;   // (everything the default path launches is warm since lgh_batch_create)
+  // mvqf_kernel<MASK, SEQ> and the steps around it, launched eagerly before any capture (the trap lgh_batch_create's warm-up describes):
+  // one step per sequence bucket the policy reaches, at the bucket's first count that takes the kernel.  A step writes row pos[slot] of
+  // its slots' caches — the row the slot's next token overwrites; only slots with such a row take part, and positions stay.
+  // (mvqf's instantiation follows the formats and the grid, not the sequence count, so the first of these steps already launches
+  // every one of them; the further buckets' steps are kept for symmetry with lgh_batch_create's warm-up and cost one step each.)
+  const uint32_t m0 = (policy >> 8) & 0xFFu, fmin = std::max(m0 ? m0 : kBatchF32MinDefault, 2u);
+  uint32_t slots[kMaxBatch], toks[kMaxBatch], n_free = 0;
+  for (uint32_t i = 0; i < Bs.max_batch; i++)
+    if (Bs.pos[i] < c->d.max_seq_len) { slots[n_free] = i; toks[n_free++] = 0; }
+  c->batch_policy = policy;
+  const uint32_t lo[3] = {2, 5, 9}, hi[3] = {4, 8, (uint32_t)kMaxBatch};
+  for (int b = 0; b < 3 && !rc; b++) {
+    const uint32_t n = std::max(lo[b], fmin);
+    if (n > std::min(hi[b], Bs.max_batch)) continue;
+    if (n > n_free) rc = fail(c, LGH_INVALID_ARGUMENT, "lgh_set_batch_policy: the warm-up steps need " + std::to_string(n) + " slots below max_seq_len");
+    if (!rc) rc = stage_words(c, slots, toks, n);
+    if (!rc) rc = enqueue_multi(c, n, 1);
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, LGH_OPERATION_FAILED, "lgh_set_batch_policy: warm-up step failed");
+  }
+  if (rc) c->batch_policy = before;   // (the context reports a policy only after its steps succeeded)
+  return rc;
 }
 
 int lgh_batch_reset(lgh_ctx* c, uint32_t slot) {   // create_active_sequence: a fresh context for the slot (O(1): position rewind)

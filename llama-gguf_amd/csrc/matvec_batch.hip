@@ -19,6 +19,8 @@
 // entry list (MvBatch::ind_*: the (sequence, top-k slot) pairs that chose the expert, their number read from device memory), so
 // that an expert's matrices are read once per step; below 3 sequences (engine_batch.hip: moe_group_min) the FFN runs sequence by
 // sequence instead.
+// A third first launch, mvqf (matvec_batch_f32.hip: the f32 matrix cores, not bit-identical), is taken by mvqb_launch only on contexts
+// whose policy asks for it (MvBatch::f32_min): never for one sequence, an expert launch, unshared inputs or a short partial buffer.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -229,14 +231,7 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb_kernel(uint32_t wbpack, uin
 // Either way a second, small launch (mvqb2_epilogue_kernel) loads the partial sums into LDS in the layout the single-sequence
 // epilogue reads and runs exactly that epilogue per sequence — every sequence's result is bit-identical to matvec_mfma.hip's.
 // ================================================================================================
-struct Mvqb2Geom {
-  uint32_t T, nbw, nblk;      // the single-sequence kernel's k-slices
-  uint32_t n_units;           // sum over segments of npass * row tiles
-  uint32_t ub1, ub2;          // first unit of segment 1 / 2 (n_units when absent)
-  uint32_t cb;                // blocks staged per chunk
-  uint32_t nslots;            // partial sums per (sequence, row) in the buffer: 1 (SEQ) or T
-};
-
+// (Mvqb2Geom: common.h)
 #ifndef LGH_XSTAGE_KB
 #define LGH_XSTAGE_KB 40   /* (experiment builds vary it: the cost of a chunk boundary, profiles/r03e_batched_decode.md) */
 #endif
@@ -472,10 +467,11 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb2_epilogue_kernel(uint32_t w
 size_t mvqb_lds_bytes(uint32_t n_seq, uint32_t red_floats) { return ((size_t)n_seq * red_floats + (size_t)n_seq * 8) * 4 + 64; }
 
 // which structure a launch took (a launch whose partial buffer is too small falls back to the first one without a word: tests read this)
-static std::atomic<uint64_t> g_structure_launches[3];
+static std::atomic<uint64_t> g_structure_launches[4];   // [3]: mvqf (matvec_batch_f32.hip), counted apart
 void mvqb_structure_launches(uint64_t out[3]) {
   for (int i = 0; i < 3; i++) out[i] = g_structure_launches[i].load(std::memory_order_relaxed);
 }
+uint64_t mvqf_launches() { return g_structure_launches[3].load(std::memory_order_relaxed); }
 
 template <uint32_t MASK, int NB>
 static hipError_t mvqb_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g, uint32_t threads, size_t lds, hipStream_t st) {
@@ -486,10 +482,20 @@ static hipError_t mvqb_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g, 
   return hipGetLastError();
 }
 
+// the second launch of an op: behind mvqb2_kernel, or behind mvqf_kernel (matvec_batch_f32.hip), which leaves B.part in the same layout
+static hipError_t mvqb2_epilogue_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g, const Mvqb2Geom& Gm, uint32_t nz, size_t lds_e,
+                                    uint32_t threads, hipStream_t st) {
+  static bool attr_set[64] = {};
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvqb2_epilogue_kernel), 160 * 1024, attr_set); e != hipSuccess) return e;
+  hipLaunchKernelGGL(mvqb2_epilogue_kernel, dim3(g.n_wg, 1, nz), dim3(threads), lds_e, st, g.wbpack, g.geom, g.geom2, L.red_floats, Gm, L, B,
+                     (const float*)B.part);
+  return hipGetLastError();
+}
+
 template <uint32_t MASK, int NB>
 static hipError_t mvqb2_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g, const Mvqb2Geom& Gm, bool seq, uint32_t groups, size_t lds_x,
                            size_t lds_e, uint32_t threads, hipStream_t st) {
-  static bool attr_set[3][64] = {};
+  static bool attr_set[2][64] = {};
   const uint32_t nz = B.ind_cnt && B.ind_nz > 1 ? B.ind_nz : 1;   // a layer's experts as the grid's third dimension
   g_structure_launches[seq ? 2 : 1].fetch_add(1, std::memory_order_relaxed);
   if (seq) {
@@ -500,10 +506,7 @@ static hipError_t mvqb2_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g,
     hipLaunchKernelGGL((mvqb2_kernel<MASK, NB, false>), dim3(groups, Gm.T, nz), dim3(kBWaves * 64), lds_x, st, Gm, L, B, B.part);
   }
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvqb2_epilogue_kernel), 160 * 1024, attr_set[2]); e != hipSuccess) return e;
-  hipLaunchKernelGGL(mvqb2_epilogue_kernel, dim3(g.n_wg, 1, nz), dim3(threads), lds_e, st, g.wbpack, g.geom, g.geom2, L.red_floats, Gm, L, B,
-                     (const float*)B.part);
-  return hipGetLastError();
+  return mvqb2_epilogue_go(L, B, g, Gm, nz, lds_e, threads, st);
 }
 
 // A threshold on n_seq: launches of at least LGH_MVQB2_MIN sequences take the records-through-LDS structure (mvqb2), fewer take mvqb.
@@ -579,8 +582,15 @@ hipError_t mvqb_launch(const MvLaunch& L, const MvBatch& Bin, uint32_t n_wg, uin
     Gm.cb = std::max(1u, std::min(Gm.nbw, mvqb2_stage_bytes((mask & (mask - 1)) == 0, nb_inst) / (B.n_seq * (uint32_t)kXqRecord)));
     const size_t lds_x = (size_t)2 * Gm.cb * B.n_seq * kXqRecord + kXZeroBytes + kXSelBytes;
     B.part_z_floats = P.z_floats;
+    // a context that asked for the f32 matrix-core kernel (MvBatch::f32_min, lgh_set_batch_policy) gets it as the first launch from that
+    // many sequences on — never for one sequence or an expert launch, and not where the partial buffer is short (mvqb below, as ever)
+    if (P.floats <= B.part_floats && B.f32_min && B.n_seq >= std::max(B.f32_min, 2u) && !B.ind_cnt) {
+      if (hipError_t e = mvqf_launch(mask, Gm, L, B, seq, groups, st); e != hipSuccess) return e;
+      g_structure_launches[3].fetch_add(1, std::memory_order_relaxed);
+      return mvqb2_epilogue_go(L, B, g, Gm, 1, lds, threads, st);
+    }
     if (P.floats <= B.part_floats) {
-#define LGH_MVQB2_CASE(M)                                                                         \
+#define LGH_MVQB2_CASE(M)                                                                        \
   case M:                                                                                         \
     if (B.n_seq <= 4) return mvqb2_go<M, 4>(L, B, g, Gm, seq, groups, lds_x, lds, threads, st);  \
     if (B.n_seq <= 8) return mvqb2_go<M, 8>(L, B, g, Gm, seq, groups, lds_x, lds, threads, st);  \

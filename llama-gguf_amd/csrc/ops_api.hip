@@ -1596,7 +1596,11 @@ static void mb_structures(int* out, const uint64_t before[3]) {
   for (int i = 0; out && i < 3; i++) out[i] = (int)(now[i] - before[i]);
 }
 
+// the `_ex` entries' policy word: what lgh_set_batch_policy accepts
+static bool mb_policy_ok(uint32_t p) { return (p & ~((uint32_t)LGH_BATCH_F32_MATRIX | 0xFF00u)) == 0; }
+
 void lgh_debug_mvqb_structures(uint64_t* out) { lgh::mvqb_structure_launches(out); }
+void lgh_debug_mvqf_launches(uint64_t* out) { if (out) *out = lgh::mvqf_launches(); }
 
 // What a launch of the step multiplies: A = the SwiGLU gate | up pair (w_up: hidden -> act), a residual launch (resid: attn_out -> hidden,
 // wo and down) or a plain store (hidden -> logits, the output projection).  The model fields follow from the launch's k and n.
@@ -1650,18 +1654,31 @@ static int mb_linear_launch(Tmp& t, MbLinear& M, size_t n_seq, int xq_next) {
 int lgh_op_linear_multi(int device, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, size_t n_seq,
                         size_t max_batch, const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
                         float* out, uint8_t* image_out, float* ssq_out, int* image_used, int* structures) {
+  int st4[4] = {structures ? structures[0] : 0, structures ? structures[1] : 0, structures ? structures[2] : 0, 0};   // (written at the launch, as ever)
+  const int rc = lgh_op_linear_multi_ex(device, type, w, w_up, bias, k, n, n_seq, max_batch, x, norm_w, eps, resid, xq_next, next_nw, 0, out, image_out,
+                                        ssq_out, image_used, st4);
+  for (int i = 0; structures && i < 3; i++) structures[i] = st4[i];
+  return rc;
+}
+
+int lgh_op_linear_multi_ex(int device, uint32_t type, const void* w, const void* w_up, const float* bias, size_t k, size_t n, size_t n_seq,
+                           size_t max_batch, const float* x, const float* norm_w, float eps, const float* resid, int xq_next, const float* next_nw,
+                           uint32_t batch_policy, float* out, uint8_t* image_out, float* ssq_out, int* image_used, int* structures) {
   Tmp t(device);
   if (t.rc) return t.rc;
   if (!w || !x || !out || n_seq == 0 || n_seq > max_batch || max_batch > (size_t)kMaxBatch || xq_next < 0 || xq_next > 2 || (xq_next == 2 && !next_nw) ||
-      (w_up && (resid || bias)) || (!w_up && !resid && xq_next))
+      (w_up && (resid || bias)) || (!w_up && !resid && xq_next) || !mb_policy_ok(batch_policy))
     return LGH_INVALID_ARGUMENT;
   MbLinear M;
   int rc;
   if ((rc = mb_linear_setup(t, M, type, w, w_up, bias, k, n, n_seq, max_batch, x, norm_w, eps, resid, next_nw, 16))) return rc;
+  t.c->batch_policy = batch_policy;
   uint64_t before[3];
   lgh::mvqb_structure_launches(before);
+  const uint64_t f_before = lgh::mvqf_launches();
   if ((rc = mb_linear_launch(t, M, n_seq, xq_next))) return rc;
   mb_structures(structures, before);
+  if (structures) structures[3] = (int)(lgh::mvqf_launches() - f_before);
   const XqBuf* qo = M.role ? xq_find(t.c, M.out) : nullptr;
   const bool used = qo && qo->fresh;
   if (image_used) *image_used = used ? 1 : 0;
@@ -1708,8 +1725,20 @@ int lgh_op_qkv_rope_multi(int device, const uint32_t* types, const void* const* 
                           float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t n_seq,
                           size_t max_batch, const int* pos, const int* slot, float rope_base, float rope_scale, int staged, float* q_out,
                           float* k_cache, float* v_cache, float* staged_out, int* structures) {
+  int st4[4] = {structures ? structures[0] : 0, structures ? structures[1] : 0, structures ? structures[2] : 0, 0};   // (written at the launch, as ever)
+  const int rc = lgh_op_qkv_rope_multi_ex(device, types, w, bias, x, norm_w, eps, hidden, head_dim, n_heads, n_kv_heads, max_seq_len, n_seq, max_batch, pos,
+                                          slot, rope_base, rope_scale, staged, 0, q_out, k_cache, v_cache, staged_out, st4);
+  for (int i = 0; structures && i < 3; i++) structures[i] = st4[i];
+  return rc;
+}
+
+int lgh_op_qkv_rope_multi_ex(int device, const uint32_t* types, const void* const* w, const float* const* bias, const float* x, const float* norm_w,
+                             float eps, size_t hidden, size_t head_dim, size_t n_heads, size_t n_kv_heads, size_t max_seq_len, size_t n_seq,
+                             size_t max_batch, const int* pos, const int* slot, float rope_base, float rope_scale, int staged, uint32_t batch_policy,
+                             float* q_out, float* k_cache, float* v_cache, float* staged_out, int* structures) {
   Tmp t(device);
   if (t.rc) return t.rc;
+  if (!mb_policy_ok(batch_policy)) return LGH_INVALID_ARGUMENT;
   if (!types || !w || !x || !norm_w || !pos || !slot || !q_out || (staged ? !staged_out : (!k_cache || !v_cache)) || hidden == 0 || head_dim == 0 ||
       head_dim % 2 || n_kv_heads == 0 || n_heads % n_kv_heads || max_seq_len == 0 || max_seq_len > 0x7FFFFFFFu || rope_scale == 0.0f ||
       max_batch > (size_t)kMaxBatch || !seqs_ok(n_seq, max_batch, slot, max_batch, true, pos, max_seq_len))
@@ -1741,10 +1770,13 @@ int lgh_op_qkv_rope_multi(int device, const uint32_t* types, const void* const* 
   const BatchScratch& Bs = t.c->batch;
   if (hipMemcpyAsync(Bs.hidden, x, n_seq * hidden * 4, hipMemcpyHostToDevice, t.c->stream) != hipSuccess) return LGH_OPERATION_FAILED;
   if ((rc = mb_produce_images(t.c, Bs.hidden, (uint32_t)hidden, n_seq, Lw.attn_norm))) return rc;
+  t.c->batch_policy = batch_policy;
   uint64_t before[3];
   lgh::mvqb_structure_launches(before);
+  const uint64_t f_before = lgh::mvqf_launches();
   if ((rc = qkv_forward_multi(t.c, t.c->layers[0], 0, (uint32_t)n_seq))) return rc;
   mb_structures(structures, before);
+  if (structures) structures[3] = (int)(lgh::mvqf_launches() - f_before);
   if ((rc = t.down(q_out, Bs.q, max_batch * QD))) return rc;
   if (staged) return t.down(staged_out, Bs.kv_tmp, max_batch * 2 * KD);
   void* const caches[KV_KINDS] = {k_cache, v_cache};

@@ -39,13 +39,14 @@ ABI_SYMBOLS = (
     "lgh_tp_reset", "lgh_tp_position", "lgh_tp_kv_truncate", "lgh_tp_ranks", "lgh_tp_graph_nodes", "lgh_tp_last_error", "lgh_tp_shard", "lgh_op_tp_reduce",
     "lgh_tp_prefill_batch", "lgh_tp_prefill_is_batched", "lgh_tp_get_stats", "lgh_op_tp_pf_reduce",
     "lgh_set_kv_rotation_signs", "lgh_op_tq_compress", "lgh_set_kv_qjl_matrices", "lgh_op_tq_compress_qjl",
-    "lgh_batch_create", "lgh_batch_reset", "lgh_batch_position", "lgh_batch_prefill", "lgh_forward_multi", "lgh_decode_greedy_multi",
+    "lgh_batch_create", "lgh_set_batch_policy", "lgh_batch_reset", "lgh_batch_position", "lgh_batch_prefill", "lgh_forward_multi", "lgh_decode_greedy_multi",
     "lgh_set_sampler", "lgh_decode_sample", "lgh_batch_set_sampler", "lgh_decode_sample_multi", "lgh_op_sample",
     "lgh_set_sampler_ex", "lgh_batch_set_sampler_ex", "lgh_get_sampler_mu", "lgh_op_sample_ex",
     "lgh_op_attention_decode", "lgh_op_attention_decode_multi", "lgh_op_attention_kv8", "lgh_op_attention_tq", "lgh_op_attention_prefill",
     "lgh_op_qkv_rope", "lgh_op_linear_chain", "lgh_op_moe_experts", "lgh_op_linear_image", "lgh_op_set_flags", "lgh_debug_static_launches", "lgh_debug_mv_plan",
     "lgh_op_pf_qkv", "lgh_op_pf_linear", "lgh_op_pf_ffn", "lgh_op_pf_moe",
     "lgh_op_linear_multi", "lgh_op_linear_chain_multi", "lgh_op_qkv_rope_multi", "lgh_op_moe_multi", "lgh_debug_mvqb_structures",
+    "lgh_op_linear_multi_ex", "lgh_op_qkv_rope_multi_ex", "lgh_debug_mvqf_launches",
     "lgh_op_pf_tq_store", "lgh_op_attention_prefill_tq", "lgh_op_pf_kv8_store", "lgh_op_attention_prefill_kv8", "lgh_op_attention_kv8_multi", "lgh_op_attention_tq_multi",
     "lgh_op_embed", "lgh_op_qkv_forward", "lgh_op_ffn_gateup", "lgh_op_argmax", "lgh_kv_cache_layout",
     "lgh_prefix_save", "lgh_prefix_restore", "lgh_prefix_free", "lgh_prefix_get_info", "lgh_prefix_total_bytes", "lgh_prefix_export",
@@ -62,6 +63,7 @@ SYM_NAMES = ("lgh::mv_kernel<1u, 1024>", "lgh::mv_kernel<8u, 1024>", "lgh::mv_ke
              "lgh::embed_kernel", "lgh::argmax_stage1+2", "lgh::moe_router_kernel", "other", "lgh::mvq_kernel<1u>", "lgh::mvq_kernel<2u>", "lgh::mvq_kernel<3u>", "lgh::mvq_kernel<4u>",
              "lgh::mvq_kernel<8u>", "unused")
 FLAG_NO_GRAPH = 1
+BATCH_F32_MATRIX = 1        # lgh_set_batch_policy: steps of >= (policy >> 8 & 0xFF, 0 = the library default) sequences on the f32 matrix cores
 PREFILL_BATCH_BYTE_KV = 1   # lgh_set_prefill_policy: int8 / FP8 caches take the batched prompt pass (own sequence, slots, stage contexts)
 FLAG_EXACT_PREFILL = 4   # forward_batch feeds tokens one by one (f32 throughout) instead of the batched f16 GEMM path
 KV_F32, KV_INT8, KV_FP8_E4M3, KV_FP8_E5M2 = 0, 1, 2, 3   # lgh_model_desc.kv_cache_type: f32, or QuantizedKVCache's formats (kv_quantized.rs; no CLI flag reaches them)
@@ -247,6 +249,7 @@ def load_library() -> C.CDLL:
         "lgh_op_tp_pf_reduce": (C.c_int, [C.c_int, C.c_int, vp, u32, u32, sz, sz, vp, vp, vp, sz, sz, vp, vp, vp]),
         "lgh_set_kv_rotation_signs": (C.c_int, [vp, vp, sz]), "lgh_op_tq_compress": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp]),
         "lgh_set_kv_qjl_matrices": (C.c_int, [vp, vp, sz]), "lgh_op_tq_compress_qjl": (C.c_int, [C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, vp]),
+        "lgh_set_batch_policy": (C.c_int, [vp, u32]),
         "lgh_batch_create": (C.c_int, [vp, u32]), "lgh_batch_reset": (C.c_int, [vp, u32]), "lgh_batch_position": (sz, [vp, u32]),
         "lgh_batch_prefill": (C.c_int, [vp, u32, vp, sz]), "lgh_forward_multi": (C.c_int, [vp, vp, vp, u32, vp, vp]),
         "lgh_decode_greedy_multi": (C.c_int, [vp, vp, vp, u32, sz, vp]),
@@ -286,6 +289,9 @@ def load_library() -> C.CDLL:
         "lgh_op_moe_multi": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, sz, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp,
                                        vp, vp, vp]),
         "lgh_debug_mvqb_structures": (None, [vp]),
+        "lgh_debug_mvqf_launches": (None, [vp]),
+        "lgh_op_linear_multi_ex": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, sz, sz, vp, vp, f32, vp, C.c_int, vp, u32, vp, vp, vp, C.POINTER(C.c_int), vp]),
+        "lgh_op_qkv_rope_multi_ex": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, sz, sz, sz, vp, vp, f32, f32, C.c_int, u32, vp, vp, vp, vp, vp]),
         "lgh_op_pf_qkv": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, C.c_int, sz, sz, sz, f32, f32, vp, vp, vp]),
         "lgh_op_pf_linear": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, vp, vp, sz, vp, vp, vp]),
         "lgh_op_pf_ffn": (C.c_int, [C.c_int, u32, vp, vp, u32, vp, vp, vp, vp, f32, sz, sz, sz, vp, vp, vp, vp]),
@@ -448,6 +454,11 @@ class HipGpuInference:
     def batch_create(self, max_batch: int) -> None:
         """`max_batch` slots (BatchedEngineConfig::max_batch_size), each one sequence's KV caches + position."""
         self._call(load_library().lgh_batch_create(self._h, max_batch))
+
+    def set_batch_policy(self, policy: int) -> None:
+        """lgh_set_batch_policy: BATCH_F32_MATRIX (| minimum sequence count << 8) runs the steps' quantized mat-vecs on the f32 matrix
+        cores from that many sequences on; 0 restores the default, bit-identical path.  After batch_create, between steps."""
+        self._call(load_library().lgh_set_batch_policy(self._h, policy))
 
     def batch_reset(self, slot: int) -> None:          # create_active_sequence: a fresh context for the slot
         self._call(load_library().lgh_batch_reset(self._h, slot))
@@ -1375,11 +1386,12 @@ def op_moe_experts(type_gate_up: int, w_gate, w_up, type_down: int, w_down, n_ex
 # ---- the multi-sequence step's launches, one at a time (lgh_op_*_multi)
 MAX_BATCH = 16                                       # kMaxBatch
 MV_STRUCTURES = ("mvqb", "mvqb2 split", "mvqb2 seq")  # lgh_debug_mvqb_structures' order
+MVQF = "mvqf"                                        # the `_ex` entries' fourth count: the f32 matrix-core kernel (lgh_set_batch_policy)
 
 
 def _structure(counts) -> str:
     """The one structure the launches of a call ran as ('mixed: ...' when they differ)."""
-    ran = [MV_STRUCTURES[i] for i in range(3) if counts[i]]
+    ran = [(MV_STRUCTURES + (MVQF,))[i] for i in range(len(counts)) if counts[i]]
     return ran[0] if len(ran) == 1 else "mixed: %s" % list(counts)
 
 
@@ -1394,11 +1406,35 @@ def mvqb_structures():
     return [int(v) for v in out]
 
 
+def mvqf_launches() -> int:
+    """Multi-sequence mat-vec launches of this process so far that took the f32 matrix-core kernel."""
+    out = C.c_uint64(0)
+    load_library().lgh_debug_mvqf_launches(C.byref(out))
+    return int(out.value)
+
+
+def op_linear_multi_ex(ggml_type: int, w, k: int, n: int, x, batch_policy: int, **kw):
+    """op_linear_multi on a context with lgh_set_batch_policy's word `batch_policy`; counts has a fourth entry, the mvqf launches."""
+    return _linear_multi(batch_policy, ggml_type, w, k, n, x, **kw)
+
+
+def op_qkv_rope_multi_ex(*args, batch_policy: int, **kw):
+    """op_qkv_rope_multi under a batch policy word; counts has a fourth entry, the mvqf launches."""
+    return _qkv_rope_multi(batch_policy, *args, **kw)
+
+
 def op_linear_multi(ggml_type: int, w, k: int, n: int, x, *, max_batch: int = MAX_BATCH, w_up=None, bias=None, norm_w=None, eps: float = 1e-5,
                     resid=None, xq_next: int = 0, next_nw=None, device: int = 0):
     """One multi-sequence launch on x [n_seq, k] as the step assembles it: the SwiGLU pair (w_up), a residual launch (resid [n_seq, n], + bias)
     or a store.  -> dict(out [max_batch, n], pad (a store: the floats between row n and the next sequence's row 0), image [max_batch, bytes] / ssq [max_batch, n / 16] (None without image slots), used,
     structure, counts); rows of sequences >= n_seq come back as the scratch held them (the NaN pattern 0x7FC0BEEF)."""
+    return _linear_multi(None, ggml_type, w, k, n, x, max_batch=max_batch, w_up=w_up, bias=bias, norm_w=norm_w, eps=eps, resid=resid, xq_next=xq_next,
+                         next_nw=next_nw, device=device)
+
+
+def _linear_multi(_policy, ggml_type, w, k, n, x, *, max_batch=MAX_BATCH, w_up=None, bias=None, norm_w=None, eps=1e-5, resid=None, xq_next=0,
+                  next_nw=None, device=0):
+    """op_linear_multi (_policy None) / op_linear_multi_ex"""
     x = _f32(x)
     n_seq = x.shape[0]
     wa = np.ascontiguousarray(w, dtype=np.uint8)
@@ -1408,10 +1444,13 @@ def op_linear_multi(ggml_type: int, w, k: int, n: int, x, *, max_batch: int = MA
     out = np.empty((max_batch, n if slots else (n + 15) // 16 * 16), np.float32)   # (a store's rows lie a whole number of tiles apart)
     img = np.zeros((max_batch, _xq_bytes(n)), np.uint8) if slots else None
     ssq = np.zeros((max_batch, n // 16 + 64), np.float32) if slots else None
-    used, counts = C.c_int(0), np.zeros(3, np.int32)
-    _chk(load_library().lgh_op_linear_multi(device, ggml_type, wa.ctypes.data, _ptr(wu), _ptr(ba), k, n, n_seq, max_batch, x.ctypes.data, _ptr(nw),
-                                            eps, _ptr(rs), xq_next, _ptr(nn), out.ctypes.data, _ptr(img), _ptr(ssq), C.byref(used),
-                                            counts.ctypes.data), "linear_multi")
+    used, counts = C.c_int(0), np.zeros(3 if _policy is None else 4, np.int32)
+    head = (device, ggml_type, wa.ctypes.data, _ptr(wu), _ptr(ba), k, n, n_seq, max_batch, x.ctypes.data, _ptr(nw), eps, _ptr(rs), xq_next, _ptr(nn))
+    tail = (out.ctypes.data, _ptr(img), _ptr(ssq), C.byref(used), counts.ctypes.data)
+    if _policy is None:
+        _chk(load_library().lgh_op_linear_multi(*head, *tail), "linear_multi")
+    else:
+        _chk(load_library().lgh_op_linear_multi_ex(*head, _policy, *tail), "linear_multi_ex")
     return {"out": out[:, :n], "pad": out[:, n:], "image": img, "ssq": None if ssq is None else ssq[:, :n // 16], "used": bool(used.value),
             "structure": _structure(counts), "counts": [int(v) for v in counts]}
 
@@ -1438,6 +1477,13 @@ def op_qkv_rope_multi(types, ws, biases, x, norm_w, eps: float, head_dim: int, n
     """The step's QKV launch(es) on x [n_seq, hidden]: sequence s rotated at pos[s], its K / V rows into row pos[s] of cache slot slot[s].
     -> dict(q [max_batch, n_heads * head_dim], k / v [max_batch, n_kv, max_seq, head_dim] (f32 caches) or staged [max_batch, 2, n_kv *
     head_dim] (the quantized caches' variant), structure, counts)."""
+    return _qkv_rope_multi(None, types, ws, biases, x, norm_w, eps, head_dim, n_heads, n_kv, max_seq, pos, slot, rope_base, rope_scale,
+                           max_batch=max_batch, staged=staged, device=device)
+
+
+def _qkv_rope_multi(_policy, types, ws, biases, x, norm_w, eps, head_dim, n_heads, n_kv, max_seq, pos, slot, rope_base, rope_scale, *,
+                    max_batch=MAX_BATCH, staged=False, device=0):
+    """op_qkv_rope_multi (_policy None) / op_qkv_rope_multi_ex"""
     x, nw = _f32(x), _f32(norm_w)
     n_seq, hidden = x.shape
     ws = [np.ascontiguousarray(w, dtype=np.uint8) for w in ws]
@@ -1452,11 +1498,14 @@ def op_qkv_rope_multi(types, ws, biases, x, norm_w, eps: float, head_dim: int, n
         st = np.empty((max_batch, 2, n_kv * head_dim), np.float32)
     else:
         kc, vc = np.empty((max_batch, n_kv, max_seq, head_dim), np.float32), np.empty((max_batch, n_kv, max_seq, head_dim), np.float32)
-    counts = np.zeros(3, np.int32)
-    _chk(load_library().lgh_op_qkv_rope_multi(device, tarr.ctypes.data, C.cast(warr, C.c_void_p), C.cast(barr, C.c_void_p), x.ctypes.data,
-                                              nw.ctypes.data, eps, hidden, head_dim, n_heads, n_kv, max_seq, n_seq, max_batch, p.ctypes.data,
-                                              s.ctypes.data, rope_base, rope_scale, int(staged), q.ctypes.data, _ptr(kc), _ptr(vc), _ptr(st),
-                                              counts.ctypes.data), "qkv_rope_multi")
+    counts = np.zeros(3 if _policy is None else 4, np.int32)
+    head = (device, tarr.ctypes.data, C.cast(warr, C.c_void_p), C.cast(barr, C.c_void_p), x.ctypes.data, nw.ctypes.data, eps, hidden, head_dim, n_heads,
+            n_kv, max_seq, n_seq, max_batch, p.ctypes.data, s.ctypes.data, rope_base, rope_scale, int(staged))
+    tail = (q.ctypes.data, _ptr(kc), _ptr(vc), _ptr(st), counts.ctypes.data)
+    if _policy is None:
+        _chk(load_library().lgh_op_qkv_rope_multi(*head, *tail), "qkv_rope_multi")
+    else:
+        _chk(load_library().lgh_op_qkv_rope_multi_ex(*head, _policy, *tail), "qkv_rope_multi_ex")
     return {"q": q, "k": kc, "v": vc, "staged": st, "structure": _structure(counts), "counts": [int(v) for v in counts]}
 
 
