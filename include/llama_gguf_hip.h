@@ -143,7 +143,7 @@ enum {
  * LGH_SYM_MV_* are the instantiations of lgh::mv_kernel<MASK, MAXT> (the VALU dequant mat-vec, csrc/matvec.hip; MASK bits:
  * Q4_K 1, Q5_K 2, Q6_K 4, Q8_0 8, Q4_0 16; MAXT = the instantiation's thread cap).  LGH_SYM_MVQ_* are the instantiations of
  * lgh::mvq_kernel<MASK> (the int8 matrix-core mat-vec, csrc/matvec_mfma.hip; ITS mask bits: Q4_K 1, Q6_K 2, Q5_K 4, Q8_0 8,
- * Q4_0 16). */
+ * Q4_0 16, Q3_K 32, Q2_K 64). */
 enum {
   LGH_SYM_MV_Q4K = 0,      /* lgh::mv_kernel<1u, 1024>  : every matrix of the launch Q4_K */
   LGH_SYM_MV_Q80 = 1,      /* lgh::mv_kernel<8u, 1024>  : Q8_0 */
@@ -166,6 +166,7 @@ enum {
   LGH_SYM_MVQ_Q5K = 18,    /* lgh::mvq_kernel<4u> / <6u> : Q5_K (and Q5_K + Q6_K) */
   LGH_SYM_MVQ_Q80_Q40 = 19, /* lgh::mvq_kernel<8u> / <16u> : Q8_0 / Q4_0 */
   LGH_SYM_PTOK = 20,       /* (unused since round 3) */
+  LGH_SYM_MVQ_Q3K_Q2K = 21, /* lgh::mvq_kernel<32u> / <64u> : Q3_K / Q2_K (contexts with LGH_WEIGHTS_LOWBIT_TILES) */
   LGH_SYM_COUNT = 24
 };
 
@@ -259,6 +260,22 @@ int lgh_prefill_is_batched(lgh_ctx* ctx);
  * setter. */
 enum { LGH_PREFILL_DEFAULT = 0, LGH_PREFILL_BATCH_BYTE_KV = 1u << 0 };
 int lgh_set_prefill_policy(lgh_ctx* ctx, uint32_t policy);
+/* Which device layout lgh_upload_tensor gives a 2-D weight where it has a choice.  A call between lgh_create and the first
+ * lgh_upload_tensor: every matrix of a context is laid out under one policy.  After the first upload, or with unknown bits, it answers
+ * InvalidArgument and changes nothing.  The word is open for further bits.
+ *   LGH_WEIGHTS_LOWBIT_TILES  Q3_K and Q2_K matrices (k % 256 == 0) stay quantized in HBM, in 16-row tile layouts of 1824 / 1344 B per
+ *     256 elements (csrc/matvec_mfma.hip), and are multiplied on the matrix cores by the kernels of the other five tile formats: the decode
+ *     mat-vec, the multi-sequence mat-vecs (lgh_forward_multi: bit-identical per sequence to lgh_forward, as ever; LGH_BATCH_F32_MATRIX
+ *     applies), and the batched prompt pass (lgh_prefill_batch).  This departs from the reference's rule, which this library follows by
+ *     default: a type without a quantized kernel is expanded to f32 at upload (src/backend/cuda/dequant_weights.rs:211-231), 1024 B per
+ *     256 elements, and multiplied by the f32 mat-vec — bit for bit the reference's dequantized weights times x in its order.  With the
+ *     bit the numbers are the same dequantized weights times x (the reference's sequential Q2_K / Q3_K layout, dequant.rs:129-200)
+ *     within the tile kernels' bound, |delta| <= 1e-4 * sum|x_i * w_i| + 1e-6, not the f32 mat-vec's bits; lgh_stats.weight_bytes
+ *     counts the native GGUF bytes.  Which is why it is not the default.
+ * Out of scope: the handles that create their contexts themselves — lgh_tp_*, lgh_pipeline_*, lgh_load_gguf — keep the default, and
+ * so do the other expanded types (Q4_1, Q5_0, Q5_1, Q8_1, Q8_K, F16) whatever the word says.  measured: profiles/lowbit_weights.md */
+enum { LGH_WEIGHTS_DEFAULT = 0, LGH_WEIGHTS_LOWBIT_TILES = 1u << 0 };
+int lgh_set_weight_policy(lgh_ctx* ctx, uint32_t policy);
 /* GpuInference::reset (gpu_only.rs:808-843) — O(1): only the position is rewound (model/mod.rs:110-117) */
 void lgh_reset(lgh_ctx* ctx);
 /* GpuInference::position (gpu_only.rs:845-847) */
@@ -608,6 +625,14 @@ int lgh_op_vec_mat(int device, uint32_t ggml_type, const void* w, const float* x
 /* out[m][n] = x[m][k] . W^T through the batched-prefill GEMM (f16 matrix cores, f32 accumulation; m <= 128, n % 16 == 0,
  * k % 256 == 0, type in {Q4_K, Q5_K, Q6_K, Q8_0, Q4_0}); no reference counterpart */
 int lgh_op_mat_mat(int device, uint32_t type, const void* w, const float* x, float* out, size_t k, size_t n, size_t m);
+/* lgh_op_vec_mat (norm_w == NULL) / lgh_op_norm_vec_mat and lgh_op_mat_mat on a context with lgh_set_weight_policy's word `weight_policy`:
+ * with LGH_WEIGHTS_LOWBIT_TILES a Q3_K / Q2_K matrix runs from its tile layout (and lgh_op_mat_mat_ex takes those two types as well).
+ * Policy 0 is the plain entry point, bit for bit.  *device_bytes (optional): the bytes the matrix occupies on the device — rows padded
+ * to 16 times the tile layout's bytes per row, or 4 * n * k where it was expanded to f32 — which tells the layout it ran from. */
+int lgh_op_vec_mat_ex(int device, uint32_t ggml_type, const void* w, const float* x, const float* norm_w, float eps, float* out, size_t k,
+                      size_t n, uint32_t weight_policy, uint64_t* device_bytes);
+int lgh_op_mat_mat_ex(int device, uint32_t type, const void* w, const float* x, float* out, size_t k, size_t n, size_t m,
+                      uint32_t weight_policy);
 int lgh_op_rms_norm(int device, const float* x, const float* w, float eps, float* out, size_t n);
 /* Backend::rope with seq_len 1: q [n_heads, d], k [n_kv_heads, d] rotated in place */
 int lgh_op_rope(int device, float* q, float* k, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t pos,

@@ -46,7 +46,10 @@ __host__ __device__ inline uint32_t blk_bytes(int t) {
 constexpr int kDevQ4K_T16 = 1012;  // device-only type tag: Q4_K in the 16-row tile layout of matvec_mfma.hip
 constexpr int kDevQ6K_T16 = 1014;  // Q6_K in its 16-row tile layout (3392 B per tile), same kernel
 constexpr int kDevQ5K_T16 = 1013, kDevQ80_T16 = 1008, kDevQ40_T16 = 1002;   // Q5_K (2816 B), Q8_0 (4352 B), Q4_0 (2304 B) tiles
-inline bool mfma_type(int t) { return t == kDevQ4K_T16 || t == kDevQ6K_T16 || t == kDevQ5K_T16 || t == kDevQ80_T16 || t == kDevQ40_T16; }
+constexpr int kDevQ3K_T16 = 1011, kDevQ2K_T16 = 1010;   // Q3_K (1824 B), Q2_K (1344 B) tiles: contexts with LGH_WEIGHTS_LOWBIT_TILES only
+inline bool mfma_type(int t) {
+  return t == kDevQ4K_T16 || t == kDevQ6K_T16 || t == kDevQ5K_T16 || t == kDevQ80_T16 || t == kDevQ40_T16 || t == kDevQ3K_T16 || t == kDevQ2K_T16;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Device weight layouts (what lgh_upload_tensor leaves in HBM).  Byte counts equal the GGUF payload;
@@ -60,6 +63,7 @@ inline bool mfma_type(int t) { return t == kDevQ4K_T16 || t == kDevQ6K_T16 || t 
 //   Q8_0  plane0 qs[32]/blk,  plane1 d(f16)/blk
 //   Q4_0  plane0 qs[16]/blk,  plane1 d(f16)/blk
 //   F32   plane0 row-major [n][k]
+//   Q3_K / Q2_K  tiles of 1824 / 1344 B for the same kernel, on contexts that asked for them (lgh_set_weight_policy)   plane0
 // Every other GGUF type is dequantized to F32 at upload (the reference does the same for types
 // without a quantized kernel, src/backend/cuda/dequant_weights.rs:211-231).
 // ---------------------------------------------------------------------------------------------

@@ -19,6 +19,15 @@ __device__ __forceinline__ uint16_t ldg_nt16(const void* p) {
   return __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p));
 }
 
+// Kernels added for the low-bit weight formats are compiled without packed f32 operations (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32), as
+// matvec_batch_f32.hip is as a whole (Makefile): on a kernel, everything inlined into it included.  An attribute, not a compiler flag, because
+// they are instantiations of templates whose other instantiations keep the code they have.
+#ifdef __HIP_DEVICE_COMPILE__
+#define LGH_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define LGH_NO_PK_F32
+#endif
+
 __device__ __forceinline__ float h2f(uint32_t bits16) {
   _Float16 h;
   uint16_t b = (uint16_t)bits16;

@@ -122,6 +122,8 @@ struct lgh_ctx {
   std::vector<lgh::XqBuf> xqs;
   lgh::PfScratch pf;
   uint32_t pf_policy = 0;                      // LGH_PREFILL_* (lgh_set_prefill_policy)
+  uint32_t weight_policy = 0;                  // LGH_WEIGHTS_* (lgh_set_weight_policy): read by upload_matrix; fixed once a tensor arrived
+  bool uploads_begun = false;
   uint32_t batch_policy = 0;                   // LGH_BATCH_* | minimum sequence count << 8 (lgh_set_batch_policy)
   lgh::BatchScratch batch;
   float* tq_signs = nullptr;                   // TurboQuant KV cache: [owned layer][kv head][k, v][head_dim] rotation signs (device)

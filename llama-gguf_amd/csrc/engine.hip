@@ -281,6 +281,7 @@ int lgh_upload_tensor(lgh_ctx* c, const char* name, uint32_t type, const uint64_
   if (!c || !name || !ne || !host) return LGH_INVALID_ARGUMENT;
   if (bind(c)) return fail(c, LGH_NOT_AVAILABLE, "hipSetDevice failed");
   if (c->finalized) return fail(c, LGH_INVALID_ARGUMENT, "upload after finalize");
+  c->uploads_begun = true;   // (lgh_set_weight_policy: every matrix of a context is laid out under one policy)
   const lgh_model_desc& d = c->d;
   const std::string nm(name);
   const uint64_t n0 = ne[0], n1 = ne[1] ? ne[1] : 1, n2 = ne[2] ? ne[2] : 1;
@@ -526,6 +527,14 @@ int lgh_set_prefill_policy(lgh_ctx* c, uint32_t policy) {
   if (rc) return rc;
   if (policy & ~(uint32_t)LGH_PREFILL_BATCH_BYTE_KV) return fail(c, LGH_INVALID_ARGUMENT, "unknown prefill policy bits");
   c->pf_policy = policy;   // read by pf_eligible at every prompt call; the scratch it needs is made by pf_ensure at the first one
+  return LGH_OK;
+}
+
+int lgh_set_weight_policy(lgh_ctx* c, uint32_t policy) {
+  if (!c) return LGH_INVALID_ARGUMENT;
+  if (policy & ~(uint32_t)LGH_WEIGHTS_LOWBIT_TILES) return fail(c, LGH_INVALID_ARGUMENT, "unknown weight policy bits");
+  if (c->uploads_begun || c->finalized) return fail(c, LGH_INVALID_ARGUMENT, "lgh_set_weight_policy: a tensor has been uploaded already");
+  c->weight_policy = policy;   // read by upload_matrix
   return LGH_OK;
 }
 

@@ -79,9 +79,11 @@ int upload_matrix(lgh_ctx* c, DevWeight& W, int src_type, uint32_t k, uint32_t n
   const uint32_t n_in_payload = slot < 0 ? n_stack : 1;
   if (nbytes != per_expert_src * n_in_payload) return fail(c, LGH_SHAPE_MISMATCH, "tensor byte size does not match its shape");
   uint64_t blocks_per_expert = (uint64_t)n * (k / li.belems);
-  // int8-MFMA tile layouts (16 rows x 256 elements, rows padded to 16) for the five fused formats when k allows it
+  // int8-MFMA tile layouts (16 rows x 256 elements, rows padded to 16) for the five fused formats when k allows it — and for Q3_K /
+  // Q2_K on a context that asked for them (lgh_set_weight_policy); without the bit those two are expanded to f32 below, as ever
+  const bool lowbit = (c->weight_policy & LGH_WEIGHTS_LOWBIT_TILES) && (src_type == LGH_TYPE_Q3_K || src_type == LGH_TYPE_Q2_K);
   const bool t16 = k % 256 == 0 && (src_type == LGH_TYPE_Q4_K || src_type == LGH_TYPE_Q6_K || src_type == LGH_TYPE_Q5_K ||
-                                    src_type == LGH_TYPE_Q8_0 || src_type == LGH_TYPE_Q4_0);
+                                    src_type == LGH_TYPE_Q8_0 || src_type == LGH_TYPE_Q4_0 || lowbit);
   if (t16) {
     li.nplanes = 1;
     li.belems = 256;
@@ -91,6 +93,8 @@ int upload_matrix(lgh_ctx* c, DevWeight& W, int src_type, uint32_t k, uint32_t n
       case LGH_TYPE_Q6_K: li.dev_type = kDevQ6K_T16; li.bpb[0] = 212; break;
       case LGH_TYPE_Q5_K: li.dev_type = kDevQ5K_T16; li.bpb[0] = 176; break;
       case LGH_TYPE_Q8_0: li.dev_type = kDevQ80_T16; li.bpb[0] = 272; break;
+      case LGH_TYPE_Q3_K: li.dev_type = kDevQ3K_T16; li.bpb[0] = 114; break;
+      case LGH_TYPE_Q2_K: li.dev_type = kDevQ2K_T16; li.bpb[0] = 84; break;
       default: li.dev_type = kDevQ40_T16; li.bpb[0] = 144; break;
     }
     blocks_per_expert = (uint64_t)((n + 15) / 16) * 16 * (k / 256);
@@ -354,9 +358,9 @@ static int mvq_symbol(const MvLaunch& L) {
   bool has[8] = {false, false, false, false, false, false, false, false};
   for (int s = 0; s < L.nseg; s++) {
     const int t = L.seg[s].type;
-    has[t == kDevQ4K_T16 ? 0 : t == kDevQ6K_T16 ? 1 : t == kDevQ5K_T16 ? 2 : t == kDevQ80_T16 ? 3 : 4] = true;
+    has[t == kDevQ4K_T16 ? 0 : t == kDevQ6K_T16 ? 1 : t == kDevQ5K_T16 ? 2 : t == kDevQ80_T16 ? 3 : t == kDevQ40_T16 ? 4 : 5] = true;
   }
-  return has[2] ? LGH_SYM_MVQ_Q5K : (has[3] || has[4]) ? LGH_SYM_MVQ_Q80_Q40 : (has[0] && has[1]) ? LGH_SYM_MVQ_MIXED
+  return has[5] ? LGH_SYM_MVQ_Q3K_Q2K : has[2] ? LGH_SYM_MVQ_Q5K : (has[3] || has[4]) ? LGH_SYM_MVQ_Q80_Q40 : (has[0] && has[1]) ? LGH_SYM_MVQ_MIXED
          : has[1] ? LGH_SYM_MVQ_Q6K : LGH_SYM_MVQ_Q4K;
 }
 
@@ -379,12 +383,13 @@ static int launch_mv_group(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, 
   return run_k(c, cls, mv_symbol(L), alg, [&] { return mv_launch(L, wg, threads, c->stream); });
 }
 
-// The formats that have a common instantiation: Q4_K + Q6_K, Q5_K + Q6_K (the "_M" mixes).
+// The formats that have a common instantiation: Q4_K + Q6_K, Q5_K + Q6_K (the "_M" mixes).  Q8_0, Q4_0, Q3_K and Q2_K have none:
+// a launch that mixes one of them with anything else goes out as one launch per segment.
 bool mv_formats_split(const SegSpec* specs, int nseg) {
   bool q4 = false, q5 = false, other = false, uniform = true;
   for (int s = 0; s < nseg; s++) {
     const int t = specs[s].W[0]->type;
-    q4 |= t == kDevQ4K_T16; q5 |= t == kDevQ5K_T16; other |= t == kDevQ80_T16 || t == kDevQ40_T16;
+    q4 |= t == kDevQ4K_T16; q5 |= t == kDevQ5K_T16; other |= t == kDevQ80_T16 || t == kDevQ40_T16 || t == kDevQ3K_T16 || t == kDevQ2K_T16;
     uniform &= t == specs[0].W[0]->type;
   }
   return !uniform && ((q4 && q5) || other);

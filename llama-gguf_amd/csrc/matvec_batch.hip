@@ -76,17 +76,14 @@ __device__ __forceinline__ void mvqb_tail(const MvLaunch& L, const MvSeg& S, con
 }
 
 template <uint32_t MASK, int NB>
-__global__ void __launch_bounds__(kBWaves * 64) mvqb_kernel(uint32_t wbpack, uint32_t geom, uint32_t geom2, uint32_t red_floats, const MvLaunch L,
-                                                            const MvBatch B) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+__device__ __forceinline__ void mvqb_body(uint32_t wbpack, uint32_t geom, uint32_t geom2, uint32_t red_floats, const MvLaunch& L, const MvBatch& B,
+                                          uint8_t* smem8) {
   const uint32_t bid = blockIdx.x;
   const int sg = (int)(bid >= (wbpack & 0xFFFFu)) + (int)(bid >= (wbpack >> 16));
   const MvSeg& S = L.seg[sg];
   constexpr bool kSingle = (MASK & (MASK - 1)) == 0;
   const int fmt = kSingle ? __builtin_ctz(MASK) : fmt_of_dev_type(S.type);
-  auto is = [&](int f) { return ((MASK >> f) & 1u) != 0 && (kSingle || fmt == f); };
-  const uint32_t tb = is(F_Q4K) ? fmt_tile_bytes(F_Q4K) : is(F_Q6K) ? fmt_tile_bytes(F_Q6K) : is(F_Q5K) ? fmt_tile_bytes(F_Q5K)
-                      : is(F_Q80) ? fmt_tile_bytes(F_Q80) : fmt_tile_bytes(F_Q40);
+  const uint32_t tb = mvq_tile_stride<MASK>(fmt);
   const uint32_t S_T = geom & 0xFFu, S_G = (geom >> 8) & 0xFFu, nbw = (geom >> 16) & 0x3FFFu;
   const bool nrm = (geom >> 31) != 0;
   const uint32_t S_nblk = geom2 & 0xFFFFu;
@@ -210,6 +207,25 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb_kernel(uint32_t wbpack, uin
   mvqb_tail(L, S, B, sg, wg, nrm, n_seq, red_floats, red, ssq, S_T);
 }
 
+template <uint32_t MASK, int NB>
+__global__ void __launch_bounds__(kBWaves * 64) mvqb_kernel(uint32_t wbpack, uint32_t geom, uint32_t geom2, uint32_t red_floats, const MvLaunch L,
+                                                            const MvBatch B) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  mvqb_body<MASK, NB>(wbpack, geom, geom2, red_floats, L, B, smem8);
+}
+// Q3_K, Q2_K: the same kernel compiled without packed f32 operations (LGH_NO_PK_F32)
+template <uint32_t MASK, int NB>
+__global__ void __launch_bounds__(kBWaves * 64) LGH_NO_PK_F32 mvqb_lowbit_kernel(uint32_t wbpack, uint32_t geom, uint32_t geom2, uint32_t red_floats,
+                                                                                 const MvLaunch L, const MvBatch B) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  mvqb_body<MASK, NB>(wbpack, geom, geom2, red_floats, L, B, smem8);
+}
+template <uint32_t MASK, int NB>
+static auto mvqb_kernel_of() {
+  if constexpr ((MASK & kLowbitMask) != 0) return &mvqb_lowbit_kernel<MASK, NB>;
+  else return &mvqb_kernel<MASK, NB>;
+}
+
 // ================================================================================================
 // Second structure (mvqb2): the sequences' XQ records through LDS, shared by the eight waves of a workgroup.
 //
@@ -242,8 +258,7 @@ constexpr uint32_t kXZeroBytes = 2 * 1280 + 256;   // the zero block; also what 
 constexpr uint32_t kXSelBytes = 64;                // behind it: whose input vector entry s reads (s itself, or an indirect entry's sequence)
 
 template <uint32_t MASK, int NB, bool SEQ>
-__global__ void __launch_bounds__(kBWaves * 64) mvqb2_kernel(const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B, float* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+__device__ __forceinline__ void mvqb2_body(const Mvqb2Geom& Gm, const MvLaunch& L, const MvBatch& B, float* __restrict__ part, uint8_t* smem8) {
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint32_t n_seq = B.n_seq;
@@ -262,9 +277,7 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb2_kernel(const Mvqb2Geom Gm,
   const MvSeg& S = L.seg[active ? sg : 0];
   constexpr bool kSingle = (MASK & (MASK - 1)) == 0;
   const int fmt = kSingle ? __builtin_ctz(MASK) : fmt_of_dev_type(S.type);
-  auto is = [&](int f) { return ((MASK >> f) & 1u) != 0 && (kSingle || fmt == f); };
-  const uint32_t tb = is(F_Q4K) ? fmt_tile_bytes(F_Q4K) : is(F_Q6K) ? fmt_tile_bytes(F_Q6K) : is(F_Q5K) ? fmt_tile_bytes(F_Q5K)
-                      : is(F_Q80) ? fmt_tile_bytes(F_Q80) : fmt_tile_bytes(F_Q40);
+  const uint32_t tb = mvq_tile_stride<MASK>(fmt);
   const uint32_t ntiles = (S.n_rows + 15) >> 4;
   const uint32_t ul = u - (sg == 0 ? 0u : sg == 1 ? Gm.ub1 : Gm.ub2);
   const uint32_t pass = active ? ul / ntiles : 0, tl = active ? ul - pass * ntiles : 0;
@@ -419,6 +432,24 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb2_kernel(const Mvqb2Geom Gm,
   }
 }
 
+template <uint32_t MASK, int NB, bool SEQ>
+__global__ void __launch_bounds__(kBWaves * 64) mvqb2_kernel(const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B, float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  mvqb2_body<MASK, NB, SEQ>(Gm, L, B, part, smem8);
+}
+// Q3_K, Q2_K: the same kernel compiled without packed f32 operations (LGH_NO_PK_F32)
+template <uint32_t MASK, int NB, bool SEQ>
+__global__ void __launch_bounds__(kBWaves * 64) LGH_NO_PK_F32 mvqb2_lowbit_kernel(const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B,
+                                                                                  float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  mvqb2_body<MASK, NB, SEQ>(Gm, L, B, part, smem8);
+}
+template <uint32_t MASK, int NB, bool SEQ>
+static auto mvqb2_kernel_of() {
+  if constexpr ((MASK & kLowbitMask) != 0) return &mvqb2_lowbit_kernel<MASK, NB, SEQ>;
+  else return &mvqb2_kernel<MASK, NB, SEQ>;
+}
+
 // grid / block = the single-sequence geometry of `L` (segments' wg_begin, rows_per_wg).  dynamic LDS: mvqb_lds_bytes(n_seq, L.red_floats)
 __global__ void __launch_bounds__(kBWaves * 64) mvqb2_epilogue_kernel(uint32_t wbpack, uint32_t geom, uint32_t geom2, uint32_t red_floats,
                                                                       const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B,
@@ -476,9 +507,10 @@ uint64_t mvqf_launches() { return g_structure_launches[3].load(std::memory_order
 template <uint32_t MASK, int NB>
 static hipError_t mvqb_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g, uint32_t threads, size_t lds, hipStream_t st) {
   static bool attr_set[64] = {};
-  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvqb_kernel<MASK, NB>), 160 * 1024, attr_set); e != hipSuccess) return e;
+  const auto kern = mvqb_kernel_of<MASK, NB>();
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set); e != hipSuccess) return e;
   g_structure_launches[0].fetch_add(1, std::memory_order_relaxed);
-  hipLaunchKernelGGL((mvqb_kernel<MASK, NB>), dim3(g.n_wg), dim3(threads), lds, st, g.wbpack, g.geom, g.geom2, L.red_floats, L, B);
+  hipLaunchKernelGGL(kern, dim3(g.n_wg), dim3(threads), lds, st, g.wbpack, g.geom, g.geom2, L.red_floats, L, B);
   return hipGetLastError();
 }
 
@@ -499,11 +531,13 @@ static hipError_t mvqb2_go(const MvLaunch& L, const MvBatch& B, const MvGeom& g,
   const uint32_t nz = B.ind_cnt && B.ind_nz > 1 ? B.ind_nz : 1;   // a layer's experts as the grid's third dimension
   g_structure_launches[seq ? 2 : 1].fetch_add(1, std::memory_order_relaxed);
   if (seq) {
-    if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvqb2_kernel<MASK, NB, true>), 160 * 1024, attr_set[0]); e != hipSuccess) return e;
-    hipLaunchKernelGGL((mvqb2_kernel<MASK, NB, true>), dim3(groups, 1, nz), dim3(kBWaves * 64), lds_x, st, Gm, L, B, B.part);
+    const auto kern = mvqb2_kernel_of<MASK, NB, true>();
+    if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set[0]); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(groups, 1, nz), dim3(kBWaves * 64), lds_x, st, Gm, L, B, B.part);
   } else {
-    if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvqb2_kernel<MASK, NB, false>), 160 * 1024, attr_set[1]); e != hipSuccess) return e;
-    hipLaunchKernelGGL((mvqb2_kernel<MASK, NB, false>), dim3(groups, Gm.T, nz), dim3(kBWaves * 64), lds_x, st, Gm, L, B, B.part);
+    const auto kern = mvqb2_kernel_of<MASK, NB, false>();
+    if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set[1]); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(groups, Gm.T, nz), dim3(kBWaves * 64), lds_x, st, Gm, L, B, B.part);
   }
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   return mvqb2_epilogue_go(L, B, g, Gm, nz, lds_e, threads, st);
@@ -597,6 +631,7 @@ hipError_t mvqb_launch(const MvLaunch& L, const MvBatch& Bin, uint32_t n_wg, uin
     return mvqb2_go<M, 16>(L, B, g, Gm, seq, groups, lds_x, lds, threads, st)
       switch (mask) {
         LGH_MVQB2_CASE(1u << F_Q4K); LGH_MVQB2_CASE(1u << F_Q6K); LGH_MVQB2_CASE(1u << F_Q5K); LGH_MVQB2_CASE(1u << F_Q80); LGH_MVQB2_CASE(1u << F_Q40);
+        LGH_MVQB2_CASE(1u << F_Q3K); LGH_MVQB2_CASE(1u << F_Q2K);
         LGH_MVQB2_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQB2_CASE((1u << F_Q5K) | (1u << F_Q6K));
         default: break;
       }
@@ -612,6 +647,7 @@ hipError_t mvqb_launch(const MvLaunch& L, const MvBatch& Bin, uint32_t n_wg, uin
     else LGH_MVQB_NB(M, 16)
   switch (mask) {
     LGH_MVQB_CASE(1u << F_Q4K); LGH_MVQB_CASE(1u << F_Q6K); LGH_MVQB_CASE(1u << F_Q5K); LGH_MVQB_CASE(1u << F_Q80); LGH_MVQB_CASE(1u << F_Q40);
+    LGH_MVQB_CASE(1u << F_Q3K); LGH_MVQB_CASE(1u << F_Q2K);
     LGH_MVQB_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQB_CASE((1u << F_Q5K) | (1u << F_Q6K));
     default: return hipErrorInvalidValue;
   }

@@ -22,6 +22,7 @@
 // used).  Per (row, sub-block) factors once per tile, then per weight one v_cvt_f32_ubyte and one fma:
 //   Q4_K, Q5_K  w = fma(q, d * sc, -(dmin * mn))      Q6_K  w = fma(q', d * sc, -32 * d * sc) = round(d * sc * (q' - 32))
 //   Q4_0        w = fma(q, d, -8 * d)                 Q8_0  w = fma(q ^ 0x80, d, -128 * d)    = round(d * q)
+//   Q2_K        as Q4_K, one (sc, mn) per chunk       Q3_K  w = fma(q, d * sc, -4 * d * sc)   = round(d * sc * (q - 4))
 //
 // Activations.  Plain f32: x[s][.] * norm_w[.] (the product the XQ producers round; x alone without a norm) staged per chunk of
 // kXfCb blocks for all sequences in LDS, double-buffered with one barrier per chunk; rows of sequences >= n_seq are zero.  A
@@ -55,8 +56,7 @@ mvqf_kernel(const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B, float* __rest
   constexpr bool kSingle = (MASK & (MASK - 1)) == 0;
   const int fmt = kSingle ? __builtin_ctz(MASK) : fmt_of_dev_type(S.type);
   auto is = [&](int f) { return mvq_is<MASK>(fmt, f); };
-  const uint32_t tb = is(F_Q4K) ? fmt_tile_bytes(F_Q4K) : is(F_Q6K) ? fmt_tile_bytes(F_Q6K) : is(F_Q5K) ? fmt_tile_bytes(F_Q5K)
-                      : is(F_Q80) ? fmt_tile_bytes(F_Q80) : fmt_tile_bytes(F_Q40);
+  const uint32_t tb = mvq_tile_stride<MASK>(fmt);
   const uint32_t ntiles = (S.n_rows + 15) >> 4;
   const uint32_t ul = u - (sg == 0 ? 0u : sg == 1 ? Gm.ub1 : Gm.ub2);
   const uint32_t pass = active ? ul / ntiles : 0, tl = active ? ul - pass * ntiles : 0;
@@ -123,6 +123,7 @@ mvqf_kernel(const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B, float* __rest
           if (is(F_Q6K)) { sa[pp] = t.dd * t.f[pp]; sb[pp] = -32.0f * sa[pp]; }
           else if (is(F_Q80)) { sa[pp] = t.f[pp]; sb[pp] = -128.0f * sa[pp]; }
           else if (is(F_Q40)) { sa[pp] = t.f[pp]; sb[pp] = -8.0f * sa[pp]; }
+          else if (is(F_Q3K)) { sa[pp] = t.dd * t.f[pp]; sb[pp] = -4.0f * sa[pp]; }
           else { sa[pp] = t.dd * t.f[pp]; sb[pp] = -(t.dmin * t.g[pp]); }
         }
         const float* xrow = xsm + buf * kXfBuf + sq * kXfRow + bi * 256 + c * 16;
@@ -175,6 +176,7 @@ hipError_t mvqf_launch(uint32_t mask, const Mvqb2Geom& Gm, const MvLaunch& L, co
 #define LGH_MVQF_CASE(M) case M: return mvqf_go<M>(Gm, L, B, seq, groups, st)
   switch (mask) {
     LGH_MVQF_CASE(1u << F_Q4K); LGH_MVQF_CASE(1u << F_Q6K); LGH_MVQF_CASE(1u << F_Q5K); LGH_MVQF_CASE(1u << F_Q80); LGH_MVQF_CASE(1u << F_Q40);
+    LGH_MVQF_CASE(1u << F_Q3K); LGH_MVQF_CASE(1u << F_Q2K);
     LGH_MVQF_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQF_CASE((1u << F_Q5K) | (1u << F_Q6K));
     default: return hipErrorInvalidValue;
   }

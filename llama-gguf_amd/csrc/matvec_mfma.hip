@@ -1,4 +1,5 @@
-// matvec_mfma.hip — quantized mat-vec on the int8 matrix cores (v_mfma_i32_16x16x64_i8): Q4_K, Q5_K, Q6_K, Q8_0, Q4_0.
+// matvec_mfma.hip — quantized mat-vec on the int8 matrix cores (v_mfma_i32_16x16x64_i8): Q4_K, Q5_K, Q6_K, Q8_0, Q4_0, and Q3_K / Q2_K on
+// contexts that keep them quantized (lgh_set_weight_policy).
 //
 // Why MFMA for a mat-VEC.  The VALU formulation (matvec.hip) needs ~3.6 vector instructions per weight
 // (byte->f32 convert, FMA, nibble masks); measured on MI355X a wave64 v_cvt_f32_ubyte costs ~2.0 ns and a
@@ -13,7 +14,7 @@
 // MFMA is block-diagonal over its four k-chunks (rows 4c..4c+3 = the four digits of chunk c), 16 weight rows x 64
 // quants are the B operand, and D holds sum_k q_k * digit_i,k as exact int32 — lane group c gets chunk c.  The four
 // digit sums are recombined once in f32 (V = D0*2^24 + D1*2^16 + D2*2^8 + D3) and scaled by d*sc*s*2^-30; min terms
-// (Q4_K, Q5_K) and offsets (Q6_K -32, Q4_0 -8) go through the f32 sums of x per chunk, the reference's x_acc.
+// (Q4_K, Q5_K, Q2_K) and offsets (Q6_K -32, Q4_0 -8, Q3_K -4) go through the f32 sums of x per chunk, the reference's x_acc.
 // Error vs the reference's sequential f32 sum is at f32 rounding level and independent of summation order.
 //
 // Device layout "tile16" (same bytes as GGUF, rows padded to 16): a tile = 16 rows x one 256-element block = 2304 B.
@@ -273,6 +274,72 @@ __global__ void __launch_bounds__(256) repack_t16_kernel(const uint8_t* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Q3_K, Q2_K -> tile16 (contexts with LGH_WEIGHTS_LOWBIT_TILES; without it both are expanded to f32 at upload).  The reference's
+// SEQUENTIAL layout (dequant.rs:129-200, not upstream ggml's interleave): sub-block g = elements 16g .. 16g+15, so a sub-block is
+// exactly the k-chunk c = g & 3 of MFMA step pp = g >> 2 and its scale belongs to one lane.  Same lane mapping as above.
+//   Q2_K (1344 B = 16 x 84)   y = d * (sc & 15) * q - dmin * (sc >> 4), q in 0..3
+//     [0, 1024)     lane-major 16 B: dword pp = the 16 quants of step pp, byte t = q[t] | q[t+4] << 2 | q[t+8] << 4 | q[t+12] << 6,
+//                   so B-operand dword j (elements 4j .. 4j+3) = (w >> 2j) & 0x03030303
+//     [1024, 1280)  lane-major 4 B: the native sc | mn << 4 bytes of the lane's chunks c, 4 + c, 8 + c, 12 + c
+//     [1280, 1344)  per row d | dmin << 16 (f16)
+//   Q3_K (1824 B = 16 x 114)  y = d * (s6 - 32) * (q - 4), q = lo2 | hi1 << 2 in 0..7
+//     [0, 1024)     the low two bits, as Q2_K's quants
+//     [1024, 1536)  lane-major 8 B: the third bits, a dword per step PAIR (low nibbles = even step, high nibbles = odd step), byte t =
+//                   f[t] | f[t+4] << 1 | f[t+8] << 2 | f[t+12] << 3, so ((H >> j) & 0x01010101) << 2 completes B-operand dword j
+//     [1536, 1792)  lane-major 4 B: s6 - 32 of the lane's four chunks as int8 (the 6-bit unpacking: dequant.rs:170-186)
+//     [1792, 1824)  the rows' f16 d
+// One thread per (row, 256-element block, step); every destination byte is written, padded rows as zeros.
+// ------------------------------------------------------------------------------------------------
+template <int F>
+__global__ void __launch_bounds__(256) repack_lowbit_t16_kernel(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dst, uint32_t n_rows,
+                                                               uint32_t nblk, uint64_t total) {
+  constexpr uint32_t TB = fmt_tile_bytes(F);
+  constexpr uint32_t SRC = F == F_Q3K ? 110u : 84u, QS = F == F_Q3K ? 32u : 16u;   // native bytes of a block, offset of its two-bit quants
+  for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (uint64_t)gridDim.x * 256) {
+    const uint32_t pp = (uint32_t)(idx & 3);
+    const uint64_t rb = idx >> 2;
+    const uint32_t row = (uint32_t)(rb / nblk), b = (uint32_t)(rb % nblk);
+    const uint32_t rt = row >> 4, n = row & 15;
+    uint8_t* tile = dst + ((size_t)rt * nblk + b) * TB;
+    const bool live = row < n_rows;
+    const uint8_t* src = raw + ((size_t)row * nblk + b) * SRC;
+    auto lo2 = [&](uint32_t e) -> uint32_t { return live ? (src[QS + (e >> 2)] >> ((e & 3) * 2)) & 3u : 0u; };
+    auto hi1 = [&](uint32_t e) -> uint32_t { return live ? (src[e >> 3] >> (e & 7)) & 1u : 0u; };   // Q3_K's hmask
+    auto hword = [&](uint32_t e0) {   // the third bits of the 16 elements from e0 on, in the low nibbles
+      uint32_t H = 0;
+#pragma unroll
+      for (uint32_t t = 0; t < 4; t++)
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) H |= hi1(e0 + 4 * j + t) << (8 * t + j);
+      return H;
+    };
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++) {
+      const uint32_t lane = 16 * c + n, g = 4 * pp + c, e0 = 16 * g;
+      uint32_t w = 0;
+#pragma unroll
+      for (uint32_t t = 0; t < 4; t++)
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) w |= lo2(e0 + 4 * j + t) << (8 * t + 2 * j);
+      *reinterpret_cast<uint32_t*>(tile + lane * 16 + pp * 4) = w;
+      if (F == F_Q2K) {
+        tile[1024 + lane * 4 + pp] = live ? src[g] : (uint8_t)0;
+      } else {
+        if ((pp & 1) == 0) *reinterpret_cast<uint32_t*>(tile + 1024 + lane * 8 + (pp >> 1) * 4) = hword(e0) | hword(e0 + 64) << 4;
+        const uint8_t* sc = src + 96 + (g >> 2) * 3;
+        const uint32_t b0 = live ? sc[0] : 0u, b1 = live ? sc[1] : 0u, b2 = live ? sc[2] : 0u;
+        const uint32_t s6 = (g & 3) == 0 ? b0 & 0x3Fu : (g & 3) == 1 ? (b0 >> 6) | ((b1 & 0x0Fu) << 2) : (g & 3) == 2 ? (b1 >> 4) | ((b2 & 0x03u) << 4) : b2 >> 2;
+        tile[1536 + lane * 4 + pp] = live ? (uint8_t)(int8_t)((int)s6 - 32) : (uint8_t)0;
+      }
+    }
+    if (pp == 0) {   // d (| dmin) once per (row, block)
+      if (F == F_Q2K) *reinterpret_cast<uint32_t*>(tile + 1280 + n * 4) = live ? (uint32_t)(src[80] | src[81] << 8) | (uint32_t)(src[82] | src[83] << 8) << 16 : 0u;
+      else *reinterpret_cast<uint16_t*>(tile + 1792 + n * 2) = live ? (uint16_t)(src[108] | src[109] << 8) : (uint16_t)0;
+    }
+  }
+}
+
 hipError_t repack_t16_launch(int dev_type, const uint8_t* raw, uint8_t* dst, uint32_t n_rows, uint32_t nblk, hipStream_t st) {
   const uint64_t total = (uint64_t)((n_rows + 15) / 16) * 16 * nblk * 4;
   uint64_t blocks = (total + 255) / 256;
@@ -289,6 +356,8 @@ hipError_t repack_t16_launch(int dev_type, const uint8_t* raw, uint8_t* dst, uin
     }
     case F_Q80: hipLaunchKernelGGL((repack_t16_kernel<F_Q80>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
     case F_Q40: hipLaunchKernelGGL((repack_t16_kernel<F_Q40>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
+    case F_Q3K: hipLaunchKernelGGL((repack_lowbit_t16_kernel<F_Q3K>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
+    case F_Q2K: hipLaunchKernelGGL((repack_lowbit_t16_kernel<F_Q2K>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -348,8 +417,7 @@ __device__ __forceinline__ void mvq_body(const uint32_t bid, uint32_t wbpack, ui
   constexpr int kDp = kDepth;   // weight tiles in flight per wave
   const int fmt = kSingle ? __builtin_ctz(MASK) : fmt_of_dev_type(S.type);
   auto is = [&](int f) { return ((MASK >> f) & 1u) != 0 && (kSingle || fmt == f); };   // compile-time false for absent formats
-  const uint32_t tb = is(F_Q4K) ? fmt_tile_bytes(F_Q4K) : is(F_Q6K) ? fmt_tile_bytes(F_Q6K) : is(F_Q5K) ? fmt_tile_bytes(F_Q5K)
-                      : is(F_Q80) ? fmt_tile_bytes(F_Q80) : fmt_tile_bytes(F_Q40);
+  const uint32_t tb = mvq_tile_stride<MASK>(fmt);
   const uint32_t S_T = geom & 0xFFu, S_G = (geom >> 8) & 0xFFu, nbw = (geom >> 16) & 0x3FFFu;
   const bool nrm = (geom >> 31) != 0;
   const uint32_t S_nblk = geom2 & 0xFFFFu;
@@ -496,7 +564,7 @@ __device__ __forceinline__ void mvq_body(const uint32_t bid, uint32_t wbpack, ui
     else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");                                         \
   } while (0)
       if (is(F_Q6K) || is(F_Q80)) LGH_WAIT_BEHIND(5);
-      else if (is(F_Q5K)) LGH_WAIT_BEHIND(4);
+      else if (is(F_Q5K) || is(F_Q3K)) LGH_WAIT_BEHIND(4);
       else LGH_WAIT_BEHIND(3);
 #undef LGH_WAIT_BEHIND
       LGH_WSTAMP(4);
@@ -580,6 +648,20 @@ __global__ void __launch_bounds__(kWaves * 64) mvq_kernel(uint32_t wbpack, uint3
   LGH_TL_BEGIN(mvq, lgh::TL_MVQ, geom2);
   mvq_body<MASK>(blockIdx.x, wbpack, geom, geom2, L_red_floats, lds_red_off, L, smem8);
   LGH_TL_END();
+}
+// Q3_K, Q2_K: the same kernel compiled without packed f32 operations (LGH_NO_PK_F32)
+template <uint32_t MASK>
+__global__ void __launch_bounds__(kWaves * 64) LGH_NO_PK_F32 mvq_lowbit_kernel(uint32_t wbpack, uint32_t geom, uint32_t geom2, uint32_t L_red_floats,
+                                                                               uint32_t lds_red_off, const MvLaunch L) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  LGH_TL_BEGIN(mvq, lgh::TL_MVQ, geom2);
+  mvq_body<MASK>(blockIdx.x, wbpack, geom, geom2, L_red_floats, lds_red_off, L, smem8);
+  LGH_TL_END();
+}
+template <uint32_t MASK>
+static auto mvq_kernel_of() {
+  if constexpr ((MASK & kLowbitMask) != 0) return &mvq_lowbit_kernel<MASK>;
+  else return &mvq_kernel<MASK>;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -854,8 +936,9 @@ template <uint32_t MASK>
 static hipError_t mvq_go(const MvLaunch& L, uint32_t n_wg, uint32_t threads, size_t lds, hipStream_t st, uint32_t wbpack, uint32_t geom,
                          uint32_t geom2, uint32_t red_off) {
   static bool attr_set[64] = {};
-  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&mvq_kernel<MASK>), 160 * 1024, attr_set); e != hipSuccess) return e;
-  hipLaunchKernelGGL((mvq_kernel<MASK>), dim3(n_wg), dim3(threads), lds, st, wbpack, geom, geom2, L.red_floats, red_off, L);
+  const auto kern = mvq_kernel_of<MASK>();
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(n_wg), dim3(threads), lds, st, wbpack, geom, geom2, L.red_floats, red_off, L);
   return hipGetLastError();
 }
 
@@ -983,6 +1066,7 @@ hipError_t mvq_launch(const MvLaunch& L0, uint32_t n_wg, uint32_t threads, hipSt
 #define LGH_MVQ_CASE(M) case M: return mvq_go<M>(L, n_wg, threads, lds, st, wbpack, geom, geom2, red_off)
   switch (mask) {   // single formats and the two mixes of the "_M" quantisations (fused QKV: V in Q6_K)
     LGH_MVQ_CASE(1u << F_Q4K); LGH_MVQ_CASE(1u << F_Q6K); LGH_MVQ_CASE(1u << F_Q5K); LGH_MVQ_CASE(1u << F_Q80); LGH_MVQ_CASE(1u << F_Q40);
+    LGH_MVQ_CASE(1u << F_Q3K); LGH_MVQ_CASE(1u << F_Q2K);
     LGH_MVQ_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQ_CASE((1u << F_Q5K) | (1u << F_Q6K));
     default: return hipErrorInvalidValue;   // other mixes: the caller launches one format at a time
   }

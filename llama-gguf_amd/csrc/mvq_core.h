@@ -14,13 +14,17 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTileBytes = 2304;      // Q4_K tile16
 constexpr int kTileBytesQ6 = 3392;    // Q6_K tile16
 // formats of the matrix-core mat-vec; a kernel instantiation handles the formats in its MASK (bit = 1 << format)
-enum : int { F_Q4K = 0, F_Q6K = 1, F_Q5K = 2, F_Q80 = 3, F_Q40 = 4, F_COUNT = 5 };
-__host__ __device__ constexpr uint32_t fmt_tile_bytes(int f) {   // = 16 rows x the GGUF bytes of 256 elements (Q6_K: +32 pad)
-  return f == F_Q4K ? 2304u : f == F_Q6K ? 3392u : f == F_Q5K ? 2816u : f == F_Q80 ? 4352u : 2304u;
+enum : int { F_Q4K = 0, F_Q6K = 1, F_Q5K = 2, F_Q80 = 3, F_Q40 = 4, F_Q3K = 5, F_Q2K = 6, F_COUNT = 7 };
+constexpr uint32_t kLowbitMask = (1u << F_Q3K) | (1u << F_Q2K);   // instantiations that hold one of these are the *_lowbit_kernel twins
+__host__ __device__ constexpr uint32_t fmt_tile_bytes(int f) {   // = 16 rows x the GGUF bytes of 256 elements (Q6_K: +32 pad; Q3_K: 114 per row)
+  return f == F_Q4K ? 2304u : f == F_Q6K ? 3392u : f == F_Q5K ? 2816u : f == F_Q80 ? 4352u : f == F_Q3K ? 1824u : f == F_Q2K ? 1344u : 2304u;
 }
-__host__ __device__ constexpr int fmt_loads_per_tile(int f) { return f == F_Q4K ? 3 : f == F_Q6K ? 5 : f == F_Q5K ? 4 : f == F_Q80 ? 5 : 3; }
+__host__ __device__ constexpr int fmt_loads_per_tile(int f) {
+  return f == F_Q4K ? 3 : f == F_Q6K ? 5 : f == F_Q5K ? 4 : f == F_Q80 ? 5 : f == F_Q3K ? 4 : 3;
+}
 __host__ __device__ constexpr int fmt_of_dev_type(int t) {
-  return t == kDevQ4K_T16 ? F_Q4K : t == kDevQ6K_T16 ? F_Q6K : t == kDevQ5K_T16 ? F_Q5K : t == kDevQ80_T16 ? F_Q80 : t == kDevQ40_T16 ? F_Q40 : -1;
+  return t == kDevQ4K_T16 ? F_Q4K : t == kDevQ6K_T16 ? F_Q6K : t == kDevQ5K_T16 ? F_Q5K : t == kDevQ80_T16 ? F_Q80 : t == kDevQ40_T16 ? F_Q40
+         : t == kDevQ3K_T16 ? F_Q3K : t == kDevQ2K_T16 ? F_Q2K : -1;
 }
 
 
@@ -31,6 +35,36 @@ template <uint32_t MASK>
 __device__ __forceinline__ bool mvq_is(int fmt, int f) {
   constexpr bool kSingle = (MASK & (MASK - 1)) == 0;
   return ((MASK >> f) & 1u) != 0 && (kSingle || fmt == f);
+}
+
+// bytes of one tile of the segment's format (a constant in a single-format instantiation)
+template <uint32_t MASK>
+__device__ __forceinline__ uint32_t mvq_tile_stride(int fmt) {
+  auto is = [&](int f) { return mvq_is<MASK>(fmt, f); };
+  return is(F_Q4K) ? fmt_tile_bytes(F_Q4K) : is(F_Q6K) ? fmt_tile_bytes(F_Q6K) : is(F_Q5K) ? fmt_tile_bytes(F_Q5K) : is(F_Q80) ? fmt_tile_bytes(F_Q80)
+         : is(F_Q3K) ? fmt_tile_bytes(F_Q3K) : is(F_Q2K) ? fmt_tile_bytes(F_Q2K) : fmt_tile_bytes(F_Q40);
+}
+
+// The two low-bit K-quants (tile layouts: matvec_mfma.hip).  r.q[0] dword pp: the lane's 16 two-bit quants of step pp, byte t = q[t] |
+// q[t+4] << 2 | q[t+8] << 4 | q[t+12] << 6, so B-operand dword j (elements 4j .. 4j+3) is one shift and one mask; Q3_K's third bits
+// (r.q[1].x / .y: a dword per step pair, low nibbles = even step, high nibbles = odd step, byte t = f[t] | f[t+4] << 1 | f[t+8] << 2 |
+// f[t+12] << 3) complete it to q = lo2 | hi1 << 2 (0..7; the reference's "- 4" goes through the chunk's sum of x).
+template <bool Q3>
+__device__ __forceinline__ i32x4 mvq_lowbit_operand(const RawT16& r, int pp) {
+  const uint32_t w = pp == 0 ? r.q[0].x : pp == 1 ? r.q[0].y : pp == 2 ? r.q[0].z : r.q[0].w;
+  i32x4 bw;
+  bw.x = (int)(w & 0x03030303u);
+  bw.y = (int)((w >> 2) & 0x03030303u);
+  bw.z = (int)((w >> 4) & 0x03030303u);
+  bw.w = (int)((w >> 6) & 0x03030303u);
+  if (Q3) {
+    const uint32_t H = ((pp >> 1) ? r.q[1].y : r.q[1].x) >> (4 * (pp & 1));
+    bw.x |= (int)((H & 0x01010101u) << 2);
+    bw.y |= (int)(((H >> 1) & 0x01010101u) << 2);
+    bw.z |= (int)(((H >> 2) & 0x01010101u) << 2);
+    bw.w |= (int)(((H >> 3) & 0x01010101u) << 2);
+  }
+  return bw;
 }
 
 // fmt_loads_per_tile(format) non-temporal loads of this lane's share of the tile at `tile` (lane roles: row n = lane & 15)
@@ -47,6 +81,17 @@ __device__ __forceinline__ void mvq_issue_tile(int fmt, const uint8_t* tile, uin
       r.hd = ldg_nt128(tile + 4096 + n * 16);
 #pragma unroll
       for (int i = 0; i < 4; i++) r.q[i] = ldg_nt128(tile + i * 1024 + lane * 16);
+    } else if (is(F_Q3K)) {   // two-bit words, third bits, the lane's four int8 scales, the row pair's d
+      r.q[0] = ldg_nt128(tile + lane * 16);
+      const u32x2 h = ldg_nt64(tile + 1024 + lane * 8);
+      r.q[1].x = h.x;
+      r.q[1].y = h.y;
+      r.hd.x = ldg_nt32(tile + 1536 + lane * 4);
+      r.hd.y = ldg_nt32(tile + 1792 + (n >> 1) * 4);
+    } else if (is(F_Q2K)) {   // two-bit words, the lane's four scale | min << 4 bytes, the row's d | dmin
+      r.q[0] = ldg_nt128(tile + lane * 16);
+      r.hd.x = ldg_nt32(tile + 1024 + lane * 4);
+      r.hd.y = ldg_nt32(tile + 1280 + n * 4);
     } else {   // Q4_K, Q5_K, Q4_0: header + two nibble loads (+ the fifth bits)
       r.hd = ldg_nt128(tile + 2048 + n * 16);
       r.q[0] = ldg_nt128(tile + lane * 16);
@@ -125,6 +170,36 @@ __device__ __forceinline__ void mvq_consume_tile(int fmt, const RawT16& r, const
         s1 = __builtin_fmaf(dd, is(F_Q40) ? __builtin_fmaf(sx[pp], V, -8.0f * xs[pp]) : sx[pp] * V, s1);
       }
       acc += s1;
+    } else if (is(F_Q3K)) {
+      // y = d * (s6 - 32) * (q - 4), one scale per 16 elements = per chunk (dequant.rs:161-200): the Q6_K shape
+      float s1 = 0.0f;
+#pragma unroll
+      for (int pp = 0; pp < 4; pp++) {
+        const i32x4 zero = {0, 0, 0, 0};
+        const i32x4 d = __builtin_amdgcn_mfma_i32_16x16x64_i8(areg[pp], mvq_lowbit_operand<true>(r, pp), zero, 0, 0, 0);
+        // both halves exact in f32: every limb sum is at most 16 * 7 * 128
+        const float hi = (float)((d.x << 8) + d.y), lo = (float)((d.z << 8) + d.w);
+        const float V = __builtin_fmaf(hi, 65536.0f, lo);
+        const float scf = (float)(int)__builtin_amdgcn_sbfe((int)r.hd.x, 8 * pp, 8);
+        s1 = __builtin_fmaf(scf, __builtin_fmaf(sx[pp], V, -4.0f * xs[pp]), s1);
+      }
+      const uint32_t dh = (n & 1) ? r.hd.y >> 16 : r.hd.y & 0xFFFFu;
+      acc = __builtin_fmaf(h2f(dh), s1, acc);
+    } else if (is(F_Q2K)) {
+      // y = d * sc * q - dmin * mn, a 4-bit (sc, mn) per chunk (dequant.rs:129-156): the Q4_K shape
+      float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+      for (int pp = 0; pp < 4; pp++) {
+        const i32x4 zero = {0, 0, 0, 0};
+        const i32x4 d = __builtin_amdgcn_mfma_i32_16x16x64_i8(areg[pp], mvq_lowbit_operand<false>(r, pp), zero, 0, 0, 0);
+        const float hi = (float)((d.x << 8) + d.y), lo = (float)((d.z << 8) + d.w);
+        const float V = __builtin_fmaf(hi, 65536.0f, lo);
+        const uint32_t sm = (r.hd.x >> (8 * pp)) & 0xFFu;
+        s1 = __builtin_fmaf((float)(sm & 15u) * sx[pp], V, s1);
+        s2 = __builtin_fmaf((float)(sm >> 4), xs[pp], s2);
+      }
+      const float dd = h2f(r.hd.y & 0xFFFFu), dmin = h2f(r.hd.y >> 16);
+      acc += dd * s1 - dmin * s2;
     } else {
       // Q4_K / Q5_K: 6-bit scales / mins of sub-blocks h, h+2, h+4, h+6 of row n, h = c >> 1 (packing: dequant.rs:210-223);
       // chunk 4pp + c lies in sub-block 2pp + h
@@ -191,9 +266,9 @@ __device__ __forceinline__ void xq_load_ops(const uint8_t* rec, uint32_t lane, X
 
 struct TileOps {
   i32x4 bw[4];      // B operand of step pp
-  float f[4];       // per step: Q4_K/Q5_K sub-block scale, Q6_K int8 scale, Q8_0/Q4_0 block d
-  float g[4];       // Q4_K/Q5_K: sub-block min
-  float dd, dmin;   // Q4_K/Q5_K: d, dmin; Q6_K: d
+  float f[4];       // per step: Q4_K/Q5_K sub-block scale, Q6_K / Q3_K int8 scale, Q8_0/Q4_0 block d, Q2_K chunk scale
+  float g[4];       // Q4_K/Q5_K: sub-block min; Q2_K: chunk min
+  float dd, dmin;   // Q4_K/Q5_K/Q2_K: d, dmin; Q6_K/Q3_K: d
 };
 
 template <uint32_t MASK>
@@ -234,6 +309,25 @@ __device__ __forceinline__ void mvq_unpack_tile(int fmt, const RawT16& r, uint32
       t.g[pp] = 0.0f;
     }
     t.dd = t.dmin = 0.0f;
+  } else if (is(F_Q3K)) {
+#pragma unroll
+    for (int pp = 0; pp < 4; pp++) {
+      t.bw[pp] = mvq_lowbit_operand<true>(r, pp);
+      t.f[pp] = (float)(int)__builtin_amdgcn_sbfe((int)r.hd.x, 8 * pp, 8);
+      t.g[pp] = 0.0f;
+    }
+    t.dd = h2f((n & 1) ? r.hd.y >> 16 : r.hd.y & 0xFFFFu);
+    t.dmin = 0.0f;
+  } else if (is(F_Q2K)) {
+#pragma unroll
+    for (int pp = 0; pp < 4; pp++) {
+      t.bw[pp] = mvq_lowbit_operand<false>(r, pp);
+      const uint32_t sm = (r.hd.x >> (8 * pp)) & 0xFFu;
+      t.f[pp] = (float)(sm & 15u);
+      t.g[pp] = (float)(sm >> 4);
+    }
+    t.dd = h2f(r.hd.y & 0xFFFFu);
+    t.dmin = h2f(r.hd.y >> 16);
   } else {
     const uint32_t s8 = (c >> 1) * 8;
     const uint32_t a = (r.hd.y >> s8) & 0x00FF00FFu, bq = (r.hd.z >> s8) & 0x00FF00FFu, cq = (r.hd.w >> s8) & 0x00FF00FFu;
@@ -298,13 +392,18 @@ __device__ __forceinline__ void mvq_mac_finish(int fmt, const TileOps& t, const 
 #pragma unroll
     for (int pp = 0; pp < 4; pp++) s1 = __builtin_fmaf(t.f[pp], __builtin_fmaf(o.sx[pp], V[pp], -32.0f * o.xs[pp]), s1);
     acc = __builtin_fmaf(t.dd, s1, acc);
+  } else if (is(F_Q3K)) {
+    float s1 = 0.0f;
+#pragma unroll
+    for (int pp = 0; pp < 4; pp++) s1 = __builtin_fmaf(t.f[pp], __builtin_fmaf(o.sx[pp], V[pp], -4.0f * o.xs[pp]), s1);
+    acc = __builtin_fmaf(t.dd, s1, acc);
   } else if (is(F_Q80) || is(F_Q40)) {
     float s1 = 0.0f;
 #pragma unroll
     for (int pp = 0; pp < 4; pp++)
       s1 = __builtin_fmaf(t.f[pp], is(F_Q40) ? __builtin_fmaf(o.sx[pp], V[pp], -8.0f * o.xs[pp]) : o.sx[pp] * V[pp], s1);
     acc += s1;
-  } else {
+  } else {   // Q4_K, Q5_K, Q2_K
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
     for (int pp = 0; pp < 4; pp++) {

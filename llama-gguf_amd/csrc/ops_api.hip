@@ -98,9 +98,11 @@ int lgh_op_dequantize(int device, uint32_t type, const void* src, size_t n, floa
 }
 
 static int vec_mat_impl(int device, uint32_t type, const void* w, const void* w2, const float* x, const float* norm_w,
-                        float eps, const float* resid, float* out, size_t k, size_t n) {
+                        float eps, const float* resid, float* out, size_t k, size_t n, uint32_t weight_policy = 0, uint64_t* device_bytes = nullptr) {
   Tmp t(device);
   if (t.rc) return t.rc;
+  if (weight_policy & ~(uint32_t)LGH_WEIGHTS_LOWBIT_TILES) return LGH_INVALID_ARGUMENT;
+  t.c->weight_policy = weight_policy;
   t.c->d.norm_eps = eps;
   const uint32_t be = blk_elems((int)type);
   if (!be || k % be) return LGH_SHAPE_MISMATCH;
@@ -109,6 +111,10 @@ static int vec_mat_impl(int device, uint32_t type, const void* w, const void* w2
   int rc;
   if ((rc = upload_matrix(t.c, W, (int)type, (uint32_t)k, (uint32_t)n, 1, -1, w, nbytes))) return rc;
   if (w2 && (rc = upload_matrix(t.c, W2, (int)type, (uint32_t)k, (uint32_t)n, 1, -1, w2, nbytes))) return rc;
+  if (device_bytes) {
+    *device_bytes = 0;
+    for (int p = 0; p < 4; p++) *device_bytes += W.stack_stride[p];
+  }
   float* dx = t.up(x, k);
   float* dnw = norm_w ? t.up(norm_w, k) : nullptr;
   float* dres = resid ? t.up(resid, n) : nullptr;
@@ -143,10 +149,21 @@ int lgh_op_swiglu_vec_mat(int device, uint32_t type, const void* w_gate, const v
   return vec_mat_impl(device, type, w_gate, w_up, x, norm_w, eps, nullptr, out, k, n);
 }
 
-// out[m][n] = x[m][k] . W^T on the batched-prefill GEMM path (prefill.hip): f16 operands, f32 accumulation
+int lgh_op_vec_mat_ex(int device, uint32_t type, const void* w, const float* x, const float* norm_w, float eps, float* out, size_t k, size_t n,
+                      uint32_t weight_policy, uint64_t* device_bytes) {
+  return vec_mat_impl(device, type, w, nullptr, x, norm_w, eps, nullptr, out, k, n, weight_policy, device_bytes);
+}
+
 int lgh_op_mat_mat(int device, uint32_t type, const void* w, const float* x, float* out, size_t k, size_t n, size_t m) {
+  return lgh_op_mat_mat_ex(device, type, w, x, out, k, n, m, LGH_WEIGHTS_DEFAULT);
+}
+
+// out[m][n] = x[m][k] . W^T on the batched-prefill GEMM path (prefill.hip): f16 operands, f32 accumulation
+int lgh_op_mat_mat_ex(int device, uint32_t type, const void* w, const float* x, float* out, size_t k, size_t n, size_t m, uint32_t weight_policy) {
   Tmp t(device);
   if (t.rc) return t.rc;
+  if (weight_policy & ~(uint32_t)LGH_WEIGHTS_LOWBIT_TILES) return LGH_INVALID_ARGUMENT;
+  t.c->weight_policy = weight_policy;
   const uint32_t be = blk_elems((int)type);
   if (!be || k % be || m == 0 || m > (size_t)kPfTokens) return LGH_SHAPE_MISMATCH;
   const size_t nbytes = n * (k / be) * blk_bytes((int)type);

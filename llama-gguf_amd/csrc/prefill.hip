@@ -43,13 +43,14 @@ namespace lgh {
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 
 // formats as in matvec_mfma.hip (same tile16 layouts)
-enum : int { PF_Q4K = 0, PF_Q6K = 1, PF_Q5K = 2, PF_Q80 = 3, PF_Q40 = 4 };
+enum : int { PF_Q4K = 0, PF_Q6K = 1, PF_Q5K = 2, PF_Q80 = 3, PF_Q40 = 4, PF_Q3K = 5, PF_Q2K = 6 };
 __host__ __device__ constexpr uint32_t pf_tile_bytes(int f) {
-  return f == PF_Q4K ? 2304u : f == PF_Q6K ? 3392u : f == PF_Q5K ? 2816u : f == PF_Q80 ? 4352u : 2304u;
+  return f == PF_Q4K ? 2304u : f == PF_Q6K ? 3392u : f == PF_Q5K ? 2816u : f == PF_Q80 ? 4352u : f == PF_Q3K ? 1824u : f == PF_Q2K ? 1344u : 2304u;
 }
 static int pf_fmt_of(int dev_type) {
   return dev_type == kDevQ4K_T16 ? PF_Q4K : dev_type == kDevQ6K_T16 ? PF_Q6K : dev_type == kDevQ5K_T16 ? PF_Q5K
-         : dev_type == kDevQ80_T16 ? PF_Q80 : dev_type == kDevQ40_T16 ? PF_Q40 : -1;
+         : dev_type == kDevQ80_T16 ? PF_Q80 : dev_type == kDevQ40_T16 ? PF_Q40 : dev_type == kDevQ3K_T16 ? PF_Q3K
+         : dev_type == kDevQ2K_T16 ? PF_Q2K : -1;
 }
 
 // waves per workgroup: 4 (one per SIMD, 4 row tiles each).  8 waves of 2 tiles (-DPF_WAVES=8: two per SIMD, twice the LDS
@@ -101,6 +102,17 @@ __device__ __forceinline__ void pf_load(PfRaw& r, const uint8_t* tile, uint32_t 
     r.hd = ldg_nt128(tile + 4096 + n * 16);
 #pragma unroll
     for (int i = 0; i < 4; i++) r.q[i] = ldg_nt128(tile + i * 1024 + lane * 16);
+  } else if (F == PF_Q3K) {   // two-bit words, third bits, the lane's four int8 scales, the row pair's d
+    r.q[0] = ldg_nt128(tile + lane * 16);
+    const u32x2 h = ldg_nt64(tile + 1024 + lane * 8);
+    r.q[1].x = h.x;
+    r.q[1].y = h.y;
+    r.hd.x = ldg_nt32(tile + 1536 + lane * 4);
+    r.hd.y = ldg_nt32(tile + 1792 + (n >> 1) * 4);
+  } else if (F == PF_Q2K) {   // two-bit words, the lane's four scale | min << 4 bytes, the row's d | dmin
+    r.q[0] = ldg_nt128(tile + lane * 16);
+    r.hd.x = ldg_nt32(tile + 1024 + lane * 4);
+    r.hd.y = ldg_nt32(tile + 1280 + n * 4);
   } else {
     r.hd = ldg_nt128(tile + 2048 + n * 16);
     r.q[0] = ldg_nt128(tile + lane * 16);
@@ -134,6 +146,15 @@ __device__ __forceinline__ void pf_scale(const PfRaw& r, int pp, uint32_t n, uin
     const float dd = h2f((c >> 1) ? hdw >> 16 : hdw & 0xFFFFu);
     S = pf_bcast(dd * kPfScale);
     O = S * pf_bcast(F == PF_Q80 ? -128.0f : -8.0f);
+  } else if (F == PF_Q3K) {   // y = d * (s6 - 32) * (q - 4), the lane's int8 scale of step pp (dequant.rs:161-200)
+    const float scf = (float)(int)__builtin_amdgcn_sbfe((int)r.hd.x, 8 * pp, 8);
+    const uint32_t dh = (n & 1) ? r.hd.y >> 16 : r.hd.y & 0xFFFFu;
+    S = pf_bcast(h2f(dh) * scf * kPfScale);
+    O = S * pf_bcast(-4.0f);
+  } else if (F == PF_Q2K) {   // y = d * sc * q - dmin * mn, 4-bit (sc, mn) per 16 elements (dequant.rs:129-156)
+    const uint32_t sm = (r.hd.x >> (8 * pp)) & 0xFFu;
+    S = pf_bcast(h2f(r.hd.y & 0xFFFFu) * (float)(sm & 15u) * kPfScale);
+    O = pf_bcast(-(h2f(r.hd.y >> 16) * (float)(sm >> 4)) * kPfScale);
   } else {   // Q4_K / Q5_K: y = d * sc * q - dmin * m, 6-bit (sc, m) per 32 elements (dequant.rs:210-255)
     const uint32_t s8 = (c >> 1) * 8;
     const uint32_t a = (r.hd.y >> s8) & 0x00FF00FFu, bq = (r.hd.z >> s8) & 0x00FF00FFu, cq = (r.hd.w >> s8) & 0x00FF00FFu;
@@ -178,9 +199,32 @@ __device__ __forceinline__ h16x8 pf_frag_bytes(uint32_t B0, uint32_t B1, h16x2 S
                  __builtin_amdgcn_perm(e, B1, 0x04020400u), __builtin_amdgcn_perm(e, B1, 0x04030401u), S, O);
 }
 
+// eight quants of two (Q2_K) or three (Q3_K) bits -> f16 in the same order.  W: the step's two-bit word (byte t = q[t] | q[t+4] << 2 |
+// q[t+8] << 4 | q[t+12] << 6), of which half h is nibble h of every byte; H: the step's third bits in the low nibbles (byte t = f[t] |
+// f[t+4] << 1 | f[t+8] << 2 | f[t+12] << 3), of which half h is bit pair h
+template <bool Q3>
+__device__ __forceinline__ h16x8 pf_frag_lowbit(uint32_t W, uint32_t H, int h, h16x2 S, h16x2 O) {
+  const uint32_t m = opaque(0x00030003u), e = 0x64006400u;
+  const uint32_t N = W >> (4 * h);
+  uint32_t b0 = (N & m) | e, b1 = ((N >> 8) & m) | e, b2 = ((N >> 2) & m) | e, b3 = ((N >> 10) & m) | e;
+  if (Q3) {
+    const uint32_t k = 0x00010001u, T = H >> (2 * h);
+    b0 |= (T & k) << 2;
+    b1 |= ((T >> 8) & k) << 2;
+    b2 |= ((T >> 1) & k) << 2;
+    b3 |= ((T >> 9) & k) << 2;
+  }
+  return pf_fin4(b0, b1, b2, b3, S, O);
+}
+
 // the A operand of MFMA (pp, h): elements 64pp + 16c + 8h .. +7 of row n, dequantized
 template <int F>
 __device__ __forceinline__ h16x8 pf_frag(const PfRaw& r, int pp, int h, h16x2 S, h16x2 O) {
+  if (F == PF_Q3K || F == PF_Q2K) {
+    const uint32_t W = pp == 0 ? r.q[0].x : pp == 1 ? r.q[0].y : pp == 2 ? r.q[0].z : r.q[0].w;
+    const uint32_t H = F == PF_Q3K ? ((pp >> 1) ? r.q[1].y : r.q[1].x) >> (4 * (pp & 1)) : 0u;
+    return pf_frag_lowbit<F == PF_Q3K>(W, H, h, S, O);
+  }
   if (F == PF_Q80) {
     const u32x4 b = r.q[pp];
     const uint32_t B0 = (h ? b.z : b.x) ^ 0x80808080u, B1 = (h ? b.w : b.y) ^ 0x80808080u;
@@ -478,8 +522,7 @@ __device__ __forceinline__ void pf_body32(const PfGemm& G, const PfSeg& sg, uint
 }
 
 template <uint32_t MASK>
-__global__ void __launch_bounds__(kPfWaves * 64) pf_gemm_kernel(const PfGemm G) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
+__device__ __forceinline__ void pf_gemm_body(const PfGemm& G, uint8_t* pf_smem) {
   const uint32_t rgid = blockIdx.x;
   int si = 0;
   if (G.nseg > 1 && rgid >= G.seg[1].rg_begin) si = 1;
@@ -513,15 +556,36 @@ __global__ void __launch_bounds__(kPfWaves * 64) pf_gemm_kernel(const PfGemm G) 
   else if (is(PF_Q5K)) LGH_PF_RUN(PF_Q5K);
   else if (is(PF_Q80)) LGH_PF_RUN(PF_Q80);
   else if (is(PF_Q40)) LGH_PF_RUN(PF_Q40);
+  else if (is(PF_Q3K)) LGH_PF_RUN(PF_Q3K);
+  else if (is(PF_Q2K)) LGH_PF_RUN(PF_Q2K);
 #undef LGH_PF_RUN
+}
+
+template <uint32_t MASK>
+__global__ void __launch_bounds__(kPfWaves * 64) pf_gemm_kernel(const PfGemm G) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
+  pf_gemm_body<MASK>(G, pf_smem);
+}
+// the instantiations that hold Q3_K / Q2_K: the same kernel compiled without packed f32 operations (LGH_NO_PK_F32)
+constexpr uint32_t kPfLowbitMask = (1u << PF_Q3K) | (1u << PF_Q2K);
+template <uint32_t MASK>
+__global__ void __launch_bounds__(kPfWaves * 64) LGH_NO_PK_F32 pf_gemm_lowbit_kernel(const PfGemm G) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
+  pf_gemm_body<MASK>(G, pf_smem);
+}
+template <uint32_t MASK>
+static auto pf_gemm_kernel_of() {
+  if constexpr ((MASK & kPfLowbitMask) != 0) return &pf_gemm_lowbit_kernel<MASK>;
+  else return &pf_gemm_kernel<MASK>;
 }
 
 template <uint32_t MASK>
 static hipError_t pf_gemm_go(const PfGemm& G, uint32_t n_rg, hipStream_t st) {
   static bool attr_set[64] = {};
   constexpr size_t lds = 2 * kPfSlabBytes;
-  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(&pf_gemm_kernel<MASK>), (int)lds, attr_set); e != hipSuccess) return e;
-  hipLaunchKernelGGL((pf_gemm_kernel<MASK>), dim3(n_rg, G.S), dim3(kPfWaves * 64), lds, st, G);
+  const auto kern = pf_gemm_kernel_of<MASK>();
+  if (hipError_t e = lds_opt_in(reinterpret_cast<const void*>(kern), (int)lds, attr_set); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(n_rg, G.S), dim3(kPfWaves * 64), lds, st, G);
   return hipGetLastError();
 }
 
@@ -592,7 +656,10 @@ hipError_t pf_gemm_launch(const DevWeight* const* W, int nw, const uint8_t* xh, 
     case (1u << PF_Q5K) | (1u << PF_Q6K): return pf_gemm_go<(1u << PF_Q5K) | (1u << PF_Q6K)>(G, rg, st);
     case 1u << PF_Q80: return pf_gemm_go<1u << PF_Q80>(G, rg, st);
     case 1u << PF_Q40: return pf_gemm_go<1u << PF_Q40>(G, rg, st);
-    default: return pf_gemm_go<31u>(G, rg, st);   // any other mix of the five formats
+    case 1u << PF_Q3K: return pf_gemm_go<1u << PF_Q3K>(G, rg, st);
+    case 1u << PF_Q2K: return pf_gemm_go<1u << PF_Q2K>(G, rg, st);
+    case (1u << PF_Q3K) | (1u << PF_Q6K): return pf_gemm_go<(1u << PF_Q3K) | (1u << PF_Q6K)>(G, rg, st);   // fused QKV of Q3_K_M
+    default: return mask & ~31u ? pf_gemm_go<127u>(G, rg, st) : pf_gemm_go<31u>(G, rg, st);   // any other mix: of the first five formats, of all
   }
 }
 

@@ -24,6 +24,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libllama_gguf_hip%s.so" % ("_" + os.envir
 ABI_SYMBOLS = (
     "lgh_device_count", "lgh_create", "lgh_upload_tensor", "lgh_finalize", "lgh_destroy", "lgh_forward",
     "lgh_prefill_token", "lgh_prefill_batch", "lgh_prefill_is_batched", "lgh_set_prefill_policy", "lgh_op_mat_mat",
+    "lgh_set_weight_policy", "lgh_op_vec_mat_ex", "lgh_op_mat_mat_ex",
     "lgh_op_kv_roundtrip", "lgh_op_add", "lgh_op_mul", "lgh_op_scale", "lgh_op_silu", "lgh_op_gelu", "lgh_op_softmax", "lgh_op_matmul", "lgh_op_matvec",
     "lgh_op_matvec_q", "lgh_op_attention", "lgh_backend_create", "lgh_backend_destroy", "lgh_backend_load_weight",
     "lgh_backend_has_weight", "lgh_backend_vec_mat_q", "lgh_backend_last_error", "lgh_reset", "lgh_position", "lgh_kv_truncate", "lgh_kv_shift_left", "lgh_stage_prefill_batch", "lgh_stage_hidden_block_buffer", "lgh_forward_argmax", "lgh_decode_greedy",
@@ -61,9 +62,10 @@ SYM_NAMES = ("lgh::mv_kernel<1u, 1024>", "lgh::mv_kernel<8u, 1024>", "lgh::mv_ke
              "lgh::mv_kernel<2u, 768>", "lgh::mv_kernel<4u, 512>", "lgh::mv_kernel<5u, 512>", "lgh::mv_kernel<6u, 512>",
              "lgh::mv_kernel<31u, 512>", "lgh::f32_matvec_kernel", "lgh::attn_partial_kernel", "lgh::attn_combine_kernel",
              "lgh::embed_kernel", "lgh::argmax_stage1+2", "lgh::moe_router_kernel", "other", "lgh::mvq_kernel<1u>", "lgh::mvq_kernel<2u>", "lgh::mvq_kernel<3u>", "lgh::mvq_kernel<4u>",
-             "lgh::mvq_kernel<8u>", "unused")
+             "lgh::mvq_kernel<8u>", "unused", "lgh::mvq_kernel<32u>")
 FLAG_NO_GRAPH = 1
 BATCH_F32_MATRIX = 1        # lgh_set_batch_policy: steps of >= (policy >> 8 & 0xFF, 0 = the library default) sequences on the f32 matrix cores
+WEIGHTS_LOWBIT_TILES = 1    # lgh_set_weight_policy: Q3_K / Q2_K matrices stay quantized in HBM (matrix-core tile layouts) instead of f32
 PREFILL_BATCH_BYTE_KV = 1   # lgh_set_prefill_policy: int8 / FP8 caches take the batched prompt pass (own sequence, slots, stage contexts)
 FLAG_EXACT_PREFILL = 4   # forward_batch feeds tokens one by one (f32 throughout) instead of the batched f16 GEMM path
 KV_F32, KV_INT8, KV_FP8_E4M3, KV_FP8_E5M2 = 0, 1, 2, 3   # lgh_model_desc.kv_cache_type: f32, or QuantizedKVCache's formats (kv_quantized.rs; no CLI flag reaches them)
@@ -193,6 +195,9 @@ def load_library() -> C.CDLL:
         "lgh_forward": (C.c_int, [vp, u32, vp]), "lgh_prefill_token": (C.c_int, [vp, u32]),
         "lgh_prefill_batch": (C.c_int, [vp, vp, sz]), "lgh_prefill_is_batched": (C.c_int, [vp]),
         "lgh_set_prefill_policy": (C.c_int, [vp, C.c_uint32]),
+        "lgh_set_weight_policy": (C.c_int, [vp, C.c_uint32]),
+        "lgh_op_vec_mat_ex": (C.c_int, [C.c_int, u32, vp, vp, vp, f32, vp, sz, sz, u32, vp]),
+        "lgh_op_mat_mat_ex": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, sz, u32]),
         "lgh_op_mat_mat": (C.c_int, [C.c_int, u32, vp, vp, vp, sz, sz, sz]), "lgh_reset": (None, [vp]), "lgh_position": (sz, [vp]),
         "lgh_kv_truncate": (C.c_int, [vp, sz]), "lgh_kv_shift_left": (C.c_int, [vp, sz]),
         "lgh_stage_prefill_batch": (C.c_int, [vp, vp, sz]), "lgh_stage_hidden_block_buffer": (C.c_int, [vp, C.POINTER(vp)]),
@@ -341,7 +346,7 @@ class HipGpuInference:
     @classmethod
     def from_model(cls, model, max_seq_len: int, device: int = 0, layer_range: Optional[Sequence[int]] = None,
                    flags: int = 0, attn_splits: int = 0, attn_direct: int = 0, kv_cache_type: int = 0,
-                   kv_rotation_signs=None, kv_qjl_matrices=None, prefill_policy: int = 0) -> "HipGpuInference":
+                   kv_rotation_signs=None, kv_qjl_matrices=None, prefill_policy: int = 0, weight_policy: int = 0) -> "HipGpuInference":
         """`model` hands over what LlamaModel::into_parts does (llama.rs:138-160): `.config` and
         `.tensors(layers)` yielding (gguf_name, ggml_type, ne, host bytes)."""
         L = load_library()
@@ -370,6 +375,8 @@ class HipGpuInference:
             if kv_qjl_matrices is not None:        # TurboQuantProd: the K engines' QjlProjector matrices [layer][kv head][d][d]
                 qm = np.ascontiguousarray(kv_qjl_matrices, dtype=np.float32)
                 self._call(L.lgh_set_kv_qjl_matrices(self._h, qm.ctypes.data, qm.size))
+            if weight_policy:
+                self.set_weight_policy(weight_policy)
             for name, t, ne, data in model.tensors(range(lb, le)):
                 self.upload_tensor(name, t, ne, data)
             self._call(L.lgh_finalize(self._h))
@@ -426,6 +433,10 @@ class HipGpuInference:
     def set_prefill_policy(self, policy: int) -> None:
         """lgh_set_prefill_policy: PREFILL_BATCH_BYTE_KV lets int8 / FP8 caches take the batched prompt pass; 0 restores the default."""
         self._call(load_library().lgh_set_prefill_policy(self._h, policy))
+
+    def set_weight_policy(self, policy: int) -> None:
+        """lgh_set_weight_policy: WEIGHTS_LOWBIT_TILES keeps Q3_K / Q2_K matrices quantized in HBM; before the first upload_tensor only."""
+        self._call(load_library().lgh_set_weight_policy(self._h, policy))
 
     def reset(self) -> None:
         load_library().lgh_reset(self._h)
@@ -1088,6 +1099,25 @@ def op_mat_mat(ggml_type: int, w: np.ndarray, x, n: int, device: int = 0) -> np.
     m, k = x.shape
     out = np.empty((m, n), dtype=np.float32)
     _chk(load_library().lgh_op_mat_mat(device, ggml_type, w.ctypes.data, x.ctypes.data, out.ctypes.data, k, n, m), "mat_mat")
+    return out
+
+
+def op_vec_mat_ex(ggml_type: int, w: np.ndarray, x, n: int, weight_policy: int, norm_w=None, eps: float = 1e-5, device: int = 0):
+    """lgh_op_vec_mat / lgh_op_norm_vec_mat (with norm_w) under lgh_set_weight_policy's word -> (out, bytes the matrix occupies on the device)."""
+    w, x = np.ascontiguousarray(w), _f32(x)
+    nw = _f32(norm_w) if norm_w is not None else None
+    out, dev_bytes = np.empty(n, dtype=np.float32), C.c_uint64(0)
+    _chk(load_library().lgh_op_vec_mat_ex(device, ggml_type, w.ctypes.data, x.ctypes.data, nw.ctypes.data if nw is not None else None, eps,
+                                          out.ctypes.data, x.size, n, weight_policy, C.byref(dev_bytes)), "vec_mat_ex")
+    return out, dev_bytes.value
+
+
+def op_mat_mat_ex(ggml_type: int, w: np.ndarray, x, n: int, weight_policy: int, device: int = 0) -> np.ndarray:
+    """op_mat_mat under lgh_set_weight_policy's word (WEIGHTS_LOWBIT_TILES: Q3_K / Q2_K as well)."""
+    w, x = np.ascontiguousarray(w), _f32(x)
+    m, k = x.shape
+    out = np.empty((m, n), dtype=np.float32)
+    _chk(load_library().lgh_op_mat_mat_ex(device, ggml_type, w.ctypes.data, x.ctypes.data, out.ctypes.data, k, n, m, weight_policy), "mat_mat_ex")
     return out
 
 

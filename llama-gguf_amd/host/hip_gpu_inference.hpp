@@ -50,7 +50,8 @@ class HipGpuInference {
   // tq2-qjl | tq3-qjl`) draws from its seeded RNG in the reference — HadamardRotation::signs() of every (layer, kv head, K / V) engine
   // and the K engines' QjlProjector matrices (src/model/kv_turboquant.rs:44-71) — as data; empty = the library's stand-ins
   static HipGpuInference from_model(lgh_model_desc desc, const std::vector<HostTensor>& tensors, size_t max_seq_len,
-                                    const std::vector<float>& kv_rotation_signs = {}, const std::vector<float>& kv_qjl_matrices = {}) {
+                                    const std::vector<float>& kv_rotation_signs = {}, const std::vector<float>& kv_qjl_matrices = {},
+                                    uint32_t weight_policy = LGH_WEIGHTS_DEFAULT) {
     desc.struct_size = sizeof(lgh_model_desc);
     desc.max_seq_len = (uint32_t)max_seq_len;
     lgh_ctx* h = nullptr;
@@ -59,6 +60,8 @@ class HipGpuInference {
     HipGpuInference g(h, desc.vocab_size);
     if (!kv_rotation_signs.empty()) g.check(lgh_set_kv_rotation_signs(h, kv_rotation_signs.data(), kv_rotation_signs.size()));
     if (!kv_qjl_matrices.empty()) g.check(lgh_set_kv_qjl_matrices(h, kv_qjl_matrices.data(), kv_qjl_matrices.size()));
+    // LGH_WEIGHTS_LOWBIT_TILES: Q3_K / Q2_K matrices stay quantized in HBM (before the first upload: one policy per context)
+    if (weight_policy) g.check(lgh_set_weight_policy(h, weight_policy));
     for (const HostTensor& t : tensors) g.check(lgh_upload_tensor(h, t.name.c_str(), t.ggml_type, t.ne, t.data, t.nbytes));
     g.check(lgh_finalize(h));
     return g;
