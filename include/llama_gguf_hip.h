@@ -167,7 +167,9 @@ enum {
   LGH_SYM_MVQ_Q80_Q40 = 19, /* lgh::mvq_kernel<8u> / <16u> : Q8_0 / Q4_0 */
   LGH_SYM_PTOK = 20,       /* (unused since round 3) */
   LGH_SYM_MVQ_Q3K_Q2K = 21, /* lgh::mvq_kernel<32u> / <64u> : Q3_K / Q2_K (contexts with LGH_WEIGHTS_LOWBIT_TILES) */
-  LGH_SYM_COUNT = 24
+  LGH_SYM_MVH_F16 = 22,    /* lgh::mvh_kernel<false> : F16 kept 16-bit (csrc/matvec_h16.hip; contexts with LGH_WEIGHTS_HALF_TILES) */
+  LGH_SYM_MVH_BF16 = 23,   /* lgh::mvh_kernel<true>  : BF16 kept 16-bit */
+  LGH_SYM_COUNT = 24       /* = the last entry + 1: a new symbol is appended and bumps this, and SYM_NAMES of hip_backend.py follows by hand */
 };
 
 typedef struct lgh_stats {
@@ -272,9 +274,21 @@ int lgh_set_prefill_policy(lgh_ctx* ctx, uint32_t policy);
  *     bit the numbers are the same dequantized weights times x (the reference's sequential Q2_K / Q3_K layout, dequant.rs:129-200)
  *     within the tile kernels' bound, |delta| <= 1e-4 * sum|x_i * w_i| + 1e-6, not the f32 mat-vec's bits; lgh_stats.weight_bytes
  *     counts the native GGUF bytes.  Which is why it is not the default.
+ *   LGH_WEIGHTS_HALF_TILES  (bit 2; bit 1 is not assigned and stays refused)  F16 and BF16 matrices and expert stacks (k % 256 == 0) stay
+ *     16-bit in HBM, in tiles of 16 rows x 256 elements = 8192 B (csrc/matvec_h16.hip), 2 B per element instead of the expansion's 4.
+ *     lgh_forward and its kin multiply them with a mat-vec of their own (plain f32 multiply-adds over exactly converted weights, x in
+ *     f32) that has every fused prologue and epilogue of the quantized formats: RMSNorm, QKV + RoPE + cache write, gate|up + SwiGLU,
+ *     residual, bias, the MoE epilogues, the greedy step's arg-max parts.  Same weights times x as the expansion within
+ *     |delta| <= 1e-4 * sum|x_i * w_i| + 1e-6, not the f32 mat-vec's bits; lgh_stats.weight_bytes counts 2 B per element.  The bits
+ *     combine (0, 1, 4, 5), and a file may mix 16-bit and int8-tile matrices: every matrix takes the kernel of its own layout.
+ *     The batched prompt pass (lgh_prefill_batch, lgh_op_mat_mat_ex) reads the same tiles on the f16 matrix cores: the operand is
+ *     f16(256 w), exact for F16 and one round-to-nearest-even for BF16, under the pass's standing |w| < 256; lgh_prefill_is_batched is 1
+ *     for such a model.  A matrix with k > 32768, or an expert stack with k > 16384, keeps the f32 expansion (the mat-vec stages its
+ *     input vectors in LDS).  Not with the bit: lgh_forward_multi (refused as for the f32 expansion) and tensor-parallel sharding.
  * Out of scope: the handles that create their contexts themselves — lgh_tp_*, lgh_pipeline_*, lgh_load_gguf — keep the default, and
- * so do the other expanded types (Q4_1, Q5_0, Q5_1, Q8_1, Q8_K, F16) whatever the word says.  measured: profiles/lowbit_weights.md */
-enum { LGH_WEIGHTS_DEFAULT = 0, LGH_WEIGHTS_LOWBIT_TILES = 1u << 0 };
+ * so do the other expanded types (Q4_1, Q5_0, Q5_1, Q8_1, Q8_K) whatever the word says.  measured: profiles/lowbit_weights.md,
+ * profiles/half_weights.md */
+enum { LGH_WEIGHTS_DEFAULT = 0, LGH_WEIGHTS_LOWBIT_TILES = 1u << 0, LGH_WEIGHTS_HALF_TILES = 1u << 2 };
 int lgh_set_weight_policy(lgh_ctx* ctx, uint32_t policy);
 /* GpuInference::reset (gpu_only.rs:808-843) — O(1): only the position is rewound (model/mod.rs:110-117) */
 void lgh_reset(lgh_ctx* ctx);
@@ -626,7 +640,9 @@ int lgh_op_vec_mat(int device, uint32_t ggml_type, const void* w, const float* x
  * k % 256 == 0, type in {Q4_K, Q5_K, Q6_K, Q8_0, Q4_0}); no reference counterpart */
 int lgh_op_mat_mat(int device, uint32_t type, const void* w, const float* x, float* out, size_t k, size_t n, size_t m);
 /* lgh_op_vec_mat (norm_w == NULL) / lgh_op_norm_vec_mat and lgh_op_mat_mat on a context with lgh_set_weight_policy's word `weight_policy`:
- * with LGH_WEIGHTS_LOWBIT_TILES a Q3_K / Q2_K matrix runs from its tile layout (and lgh_op_mat_mat_ex takes those two types as well).
+ * with LGH_WEIGHTS_LOWBIT_TILES a Q3_K / Q2_K matrix runs from its tile layout (and lgh_op_mat_mat_ex takes those two types as well);
+ * with LGH_WEIGHTS_HALF_TILES an F16 / BF16 matrix runs from its 16-bit tiles in both (without the bit lgh_op_mat_mat_ex answers Unsupported
+ * for the two types, as ever).
  * Policy 0 is the plain entry point, bit for bit.  *device_bytes (optional): the bytes the matrix occupies on the device — rows padded
  * to 16 times the tile layout's bytes per row, or 4 * n * k where it was expanded to f32 — which tells the layout it ran from. */
 int lgh_op_vec_mat_ex(int device, uint32_t ggml_type, const void* w, const float* x, const float* norm_w, float eps, float* out, size_t k,

@@ -47,6 +47,14 @@ constexpr int kDevQ4K_T16 = 1012;  // device-only type tag: Q4_K in the 16-row t
 constexpr int kDevQ6K_T16 = 1014;  // Q6_K in its 16-row tile layout (3392 B per tile), same kernel
 constexpr int kDevQ5K_T16 = 1013, kDevQ80_T16 = 1008, kDevQ40_T16 = 1002;   // Q5_K (2816 B), Q8_0 (4352 B), Q4_0 (2304 B) tiles
 constexpr int kDevQ3K_T16 = 1011, kDevQ2K_T16 = 1010;   // Q3_K (1824 B), Q2_K (1344 B) tiles: contexts with LGH_WEIGHTS_LOWBIT_TILES only
+// F16 / BF16 kept 16-bit, in 8192-B tiles (matvec_h16.hip): contexts with LGH_WEIGHTS_HALF_TILES only.  Not mfma_type: their decode
+// mat-vec reads f32 x, not XQ records
+constexpr int kDevF16_T16 = 1001, kDevBF16_T16 = 1030;
+inline bool half_type(int t) { return t == kDevF16_T16 || t == kDevBF16_T16; }
+// Their mat-vec stages its input vectors in LDS as f32: 128 KiB of the 160 KiB, the rest is the k-slices' partial sums.  A matrix is
+// one vector of k floats, an expert stack two (the pair of experts a MoE down launch carries); a longer k keeps the f32 expansion.
+constexpr uint32_t kMvhMaxStagedFloats = 32768;
+inline bool half_tiles_fit(uint32_t k, uint32_t n_stack) { return (uint64_t)k * (n_stack > 1 ? 2 : 1) <= kMvhMaxStagedFloats; }
 inline bool mfma_type(int t) {
   return t == kDevQ4K_T16 || t == kDevQ6K_T16 || t == kDevQ5K_T16 || t == kDevQ80_T16 || t == kDevQ40_T16 || t == kDevQ3K_T16 || t == kDevQ2K_T16;
 }
@@ -64,6 +72,7 @@ inline bool mfma_type(int t) {
 //   Q4_0  plane0 qs[16]/blk,  plane1 d(f16)/blk
 //   F32   plane0 row-major [n][k]
 //   Q3_K / Q2_K  tiles of 1824 / 1344 B for the same kernel, on contexts that asked for them (lgh_set_weight_policy)   plane0
+//   F16 / BF16   tiles of 8192 B (2 B per element) for mvh_kernel (matvec_h16.hip), on contexts that asked for them             plane0
 // Every other GGUF type is dequantized to F32 at upload (the reference does the same for types
 // without a quantized kernel, src/backend/cuda/dequant_weights.rs:211-231).
 // ---------------------------------------------------------------------------------------------
@@ -241,6 +250,10 @@ hipError_t repack_t16_launch(int dev_type, const uint8_t* raw, uint8_t* dst, uin
 hipError_t repack_q6k_t16_launch(const uint8_t* raw, uint8_t* dst, uint32_t n_rows, uint32_t nblk, hipStream_t st);  // LGH_SYM_MV_* of the instantiation mv_launch will pick
 hipError_t f32_matvec_launch(const float* w, const float* x, float* out, uint32_t k, uint32_t n, const float* norm_w,
                              float eps, const float* resid, hipStream_t st);
+// F16 / BF16 tiles (matvec_h16.hip): geometry, launch (x as f32; *amax_done as mvq_launch's) and the upload-time repack
+hipError_t mvh_plan(uint32_t k, uint32_t n_rows, int npass, MvPlan* plan, uint32_t launch_rows);
+hipError_t mvh_launch(const MvLaunch& L, uint32_t n_wg, uint32_t threads, hipStream_t st, bool* amax_done = nullptr);
+hipError_t repack_half_t16_launch(const uint8_t* raw, uint8_t* dst, uint32_t n_rows, uint32_t nblk, hipStream_t st);
 
 // upload-time re-layout and dequantization (dst device buffers)
 hipError_t repack_launch(int src_type, const uint8_t* raw, uint8_t* dst, const uint64_t plane_off[4], uint64_t n_blocks,

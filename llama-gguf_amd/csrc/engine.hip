@@ -532,7 +532,7 @@ int lgh_set_prefill_policy(lgh_ctx* c, uint32_t policy) {
 
 int lgh_set_weight_policy(lgh_ctx* c, uint32_t policy) {
   if (!c) return LGH_INVALID_ARGUMENT;
-  if (policy & ~(uint32_t)LGH_WEIGHTS_LOWBIT_TILES) return fail(c, LGH_INVALID_ARGUMENT, "unknown weight policy bits");
+  if (policy & ~kWeightPolicyBits) return fail(c, LGH_INVALID_ARGUMENT, "unknown weight policy bits");
   if (c->uploads_begun || c->finalized) return fail(c, LGH_INVALID_ARGUMENT, "lgh_set_weight_policy: a tensor has been uploaded already");
   c->weight_policy = policy;   // read by upload_matrix
   return LGH_OK;

@@ -64,7 +64,7 @@ LayoutInfo layout_for(int src_type) {
 }
 
 bool fused_type(int t) {
-  return mfma_type(t) || t == LGH_TYPE_Q4_K || t == LGH_TYPE_Q5_K || t == LGH_TYPE_Q6_K || t == LGH_TYPE_Q8_0 || t == LGH_TYPE_Q4_0;
+  return mfma_type(t) || half_type(t) || t == LGH_TYPE_Q4_K || t == LGH_TYPE_Q5_K || t == LGH_TYPE_Q6_K || t == LGH_TYPE_Q8_0 || t == LGH_TYPE_Q4_0;
 }
 
 // Upload one matrix (or expert `slot` of a stack, or the whole stack when slot < 0) given in native
@@ -82,7 +82,10 @@ int upload_matrix(lgh_ctx* c, DevWeight& W, int src_type, uint32_t k, uint32_t n
   // int8-MFMA tile layouts (16 rows x 256 elements, rows padded to 16) for the five fused formats when k allows it — and for Q3_K /
   // Q2_K on a context that asked for them (lgh_set_weight_policy); without the bit those two are expanded to f32 below, as ever
   const bool lowbit = (c->weight_policy & LGH_WEIGHTS_LOWBIT_TILES) && (src_type == LGH_TYPE_Q3_K || src_type == LGH_TYPE_Q2_K);
-  const bool t16 = k % 256 == 0 && (src_type == LGH_TYPE_Q4_K || src_type == LGH_TYPE_Q6_K || src_type == LGH_TYPE_Q5_K ||
+  // ... and F16 / BF16 stay 16-bit, in the tiles of matvec_h16.hip, on a context with LGH_WEIGHTS_HALF_TILES
+  // (where their mat-vec can stage k: half_tiles_fit; a longer k is expanded as without the bit)
+  const bool half = (c->weight_policy & LGH_WEIGHTS_HALF_TILES) && (src_type == LGH_TYPE_F16 || src_type == LGH_TYPE_BF16) && half_tiles_fit(k, n_stack);
+  const bool t16 = k % 256 == 0 && (half || src_type == LGH_TYPE_Q4_K || src_type == LGH_TYPE_Q6_K || src_type == LGH_TYPE_Q5_K ||
                                     src_type == LGH_TYPE_Q8_0 || src_type == LGH_TYPE_Q4_0 || lowbit);
   if (t16) {
     li.nplanes = 1;
@@ -95,6 +98,8 @@ int upload_matrix(lgh_ctx* c, DevWeight& W, int src_type, uint32_t k, uint32_t n
       case LGH_TYPE_Q8_0: li.dev_type = kDevQ80_T16; li.bpb[0] = 272; break;
       case LGH_TYPE_Q3_K: li.dev_type = kDevQ3K_T16; li.bpb[0] = 114; break;
       case LGH_TYPE_Q2_K: li.dev_type = kDevQ2K_T16; li.bpb[0] = 84; break;
+      case LGH_TYPE_F16: li.dev_type = kDevF16_T16; li.bpb[0] = 512; break;
+      case LGH_TYPE_BF16: li.dev_type = kDevBF16_T16; li.bpb[0] = 512; break;
       default: li.dev_type = kDevQ40_T16; li.bpb[0] = 144; break;
     }
     blocks_per_expert = (uint64_t)((n + 15) / 16) * 16 * (k / 256);
@@ -136,6 +141,8 @@ int upload_matrix(lgh_ctx* c, DevWeight& W, int src_type, uint32_t k, uint32_t n
     const uint8_t* src = (const uint8_t*)raw + (uint64_t)i * per_expert_src;
     if (li.dev_type == LGH_TYPE_F32) {
       e = dequant_launch(src_type, src, (float*)(W.plane[0] + (uint64_t)(e0 + i) * W.stack_stride[0]), (uint64_t)n * k, c->stream);
+    } else if (t16 && half) {
+      e = repack_half_t16_launch(src, W.base + (uint64_t)(e0 + i) * W.stack_stride[0], n, k / 256, c->stream);
     } else if (t16) {
       e = repack_t16_launch(li.dev_type, src, W.base + (uint64_t)(e0 + i) * W.stack_stride[0], n, k / 256, c->stream);
     } else {
@@ -289,6 +296,7 @@ int build_mv_group(lgh_ctx* c, const SegSpec* specs, int nseg, const float* norm
     const DevWeight& W0 = *sp.W[0];
     MvPlan plan;
     hipError_t pe = mfma ? mvq_plan(W0.k, W0.n, sp.npass, &plan, launch_rows, force_tiles[s])
+                    : half_type(W0.type) ? mvh_plan(W0.k, W0.n, sp.npass, &plan, launch_rows)
                          : mv_plan(W0.type, W0.k, W0.n, sp.npass, &plan, launch_rows, wave_cap);
     if (pe != hipSuccess)
       return fail(c, LGH_UNSUPPORTED, "no fused mat-vec plan for type " + std::to_string(W0.type) + " k=" + std::to_string(W0.k));
@@ -296,7 +304,7 @@ int build_mv_group(lgh_ctx* c, const SegSpec* specs, int nseg, const float* norm
     S.type = W0.type;
     S.epi = sp.epi;
     S.n_rows = W0.n;
-    S.nblk = mfma ? W0.k / 256 : W0.k / layout_for(W0.src_type).belems;
+    S.nblk = mfma || half_type(W0.type) ? W0.k / 256 : W0.k / layout_for(W0.src_type).belems;
     S.units = plan.units; S.T = plan.T; S.G = plan.G;
     S.rows_per_wg = plan.rows_per_wg;
     S.wg_begin = wg;
@@ -380,6 +388,14 @@ static int launch_mv_group(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, 
     if (!rc && amax_done && specs[0].amax_parts) *specs[0].amax_parts = wg;
     return rc;
   }
+  if (half_type(L.seg[0].type)) {   // (asked to, the output projection of a greedy step also leaves its workgroups' arg-max parts)
+    if (nseg == 1) { L.amax_v = specs[0].amax_v; L.amax_i = specs[0].amax_i; }
+    bool amax_done = false;
+    rc = run_k(c, cls, L.seg[0].type == kDevBF16_T16 ? LGH_SYM_MVH_BF16 : LGH_SYM_MVH_F16, alg,
+               [&] { return mvh_launch(L, wg, threads, c->stream, &amax_done); });
+    if (!rc && amax_done && specs[0].amax_parts) *specs[0].amax_parts = wg;
+    return rc;
+  }
   return run_k(c, cls, mv_symbol(L), alg, [&] { return mv_launch(L, wg, threads, c->stream); });
 }
 
@@ -396,12 +412,13 @@ bool mv_formats_split(const SegSpec* specs, int nseg) {
 }
 
 // Segments are independent (disjoint outputs), so a launch whose matrices live in different kernel families
-// (Q4_K on the matrix cores, the rest on the VALU kernel) is issued as one launch per family.
+// (the tile formats on the matrix cores, F16 / BF16 tiles on mvh_kernel, the rest on the VALU kernel) is issued as one launch per family.
 int launch_mv(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float* norm_w, uint32_t k) {
-  SegSpec a[3], b[3];
-  int na = 0, nb = 0;
+  SegSpec a[3], b[3], h[3];
+  int na = 0, nb = 0, nh = 0;
   for (int s = 0; s < nseg; s++) {
     if (mfma_type(specs[s].W[0]->type)) a[na++] = specs[s];
+    else if (half_type(specs[s].W[0]->type)) h[nh++] = specs[s];
     else b[nb++] = specs[s];
   }
   int rc = LGH_OK;
@@ -412,6 +429,12 @@ int launch_mv(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, const float* 
   }
   if (na && (rc = launch_mv_group(c, cls, a, na, norm_w, k, true))) return rc;
   if (nb && (rc = launch_mv_group(c, cls, b, nb, norm_w, k, false))) return rc;
+  for (int s = 0; s < nh;) {   // F16 and BF16 are two instantiations: consecutive segments of one type share a launch
+    int e = s + 1;
+    while (e < nh && h[e].W[0]->type == h[s].W[0]->type) e++;
+    if ((rc = launch_mv_group(c, cls, h + s, e - s, norm_w, k, false))) return rc;
+    s = e;
+  }
   return rc;
 }
 

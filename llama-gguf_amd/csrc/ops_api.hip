@@ -101,7 +101,7 @@ static int vec_mat_impl(int device, uint32_t type, const void* w, const void* w2
                         float eps, const float* resid, float* out, size_t k, size_t n, uint32_t weight_policy = 0, uint64_t* device_bytes = nullptr) {
   Tmp t(device);
   if (t.rc) return t.rc;
-  if (weight_policy & ~(uint32_t)LGH_WEIGHTS_LOWBIT_TILES) return LGH_INVALID_ARGUMENT;
+  if (weight_policy & ~kWeightPolicyBits) return LGH_INVALID_ARGUMENT;
   t.c->weight_policy = weight_policy;
   t.c->d.norm_eps = eps;
   const uint32_t be = blk_elems((int)type);
@@ -162,7 +162,7 @@ int lgh_op_mat_mat(int device, uint32_t type, const void* w, const float* x, flo
 int lgh_op_mat_mat_ex(int device, uint32_t type, const void* w, const float* x, float* out, size_t k, size_t n, size_t m, uint32_t weight_policy) {
   Tmp t(device);
   if (t.rc) return t.rc;
-  if (weight_policy & ~(uint32_t)LGH_WEIGHTS_LOWBIT_TILES) return LGH_INVALID_ARGUMENT;
+  if (weight_policy & ~kWeightPolicyBits) return LGH_INVALID_ARGUMENT;
   t.c->weight_policy = weight_policy;
   const uint32_t be = blk_elems((int)type);
   if (!be || k % be || m == 0 || m > (size_t)kPfTokens) return LGH_SHAPE_MISMATCH;

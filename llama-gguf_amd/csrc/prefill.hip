@@ -43,14 +43,15 @@ namespace lgh {
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 
 // formats as in matvec_mfma.hip (same tile16 layouts)
-enum : int { PF_Q4K = 0, PF_Q6K = 1, PF_Q5K = 2, PF_Q80 = 3, PF_Q40 = 4, PF_Q3K = 5, PF_Q2K = 6 };
+// ... and the two 16-bit layouts of matvec_h16.hip (contexts with LGH_WEIGHTS_HALF_TILES): pf_body_half
+enum : int { PF_Q4K = 0, PF_Q6K = 1, PF_Q5K = 2, PF_Q80 = 3, PF_Q40 = 4, PF_Q3K = 5, PF_Q2K = 6, PF_F16 = 7, PF_BF16 = 8 };
 __host__ __device__ constexpr uint32_t pf_tile_bytes(int f) {
-  return f == PF_Q4K ? 2304u : f == PF_Q6K ? 3392u : f == PF_Q5K ? 2816u : f == PF_Q80 ? 4352u : f == PF_Q3K ? 1824u : f == PF_Q2K ? 1344u : 2304u;
+  return f >= PF_F16 ? 8192u : f == PF_Q4K ? 2304u : f == PF_Q6K ? 3392u : f == PF_Q5K ? 2816u : f == PF_Q80 ? 4352u : f == PF_Q3K ? 1824u : f == PF_Q2K ? 1344u : 2304u;
 }
 static int pf_fmt_of(int dev_type) {
   return dev_type == kDevQ4K_T16 ? PF_Q4K : dev_type == kDevQ6K_T16 ? PF_Q6K : dev_type == kDevQ5K_T16 ? PF_Q5K
          : dev_type == kDevQ80_T16 ? PF_Q80 : dev_type == kDevQ40_T16 ? PF_Q40 : dev_type == kDevQ3K_T16 ? PF_Q3K
-         : dev_type == kDevQ2K_T16 ? PF_Q2K : -1;
+         : dev_type == kDevQ2K_T16 ? PF_Q2K : dev_type == kDevF16_T16 ? PF_F16 : dev_type == kDevBF16_T16 ? PF_BF16 : -1;
 }
 
 // waves per workgroup: 4 (one per SIMD, 4 row tiles each).  8 waves of 2 tiles (-DPF_WAVES=8: two per SIMD, twice the LDS
@@ -388,6 +389,150 @@ __device__ __forceinline__ void pf_body(const PfGemm& G, const PfSeg& sg, uint32
   LGH_PF_STAMP(14);
 }
 
+// ------------------------------------------------------------------------------------------------
+// F16 / BF16 weights kept 16-bit (kDevF16_T16 / kDevBF16_T16, matvec_h16.hip)
+// ------------------------------------------------------------------------------------------------
+// The A operand of MFMA (pp, h) from piece 2pp + h as it was loaded: f16(w * kPfScale).  The piece's inner order is the XH chunk's, so
+// nothing moves between lanes or inside the piece.  F16: a packed multiply, exact for |w| < 256 (subnormals included).  BF16: widened
+// exactly by a shift or a mask, multiplied in f32 (exact: a power of two) and rounded to nearest even into f16 — the one rounding.
+template <bool BF16>
+__device__ __forceinline__ h16x8 pf_half_frag(u32x4 q) {
+  h16x2 w[4];
+  const uint32_t d[4] = {q.x, q.y, q.z, q.w};
+  if (BF16) {
+    float lo[4], hi[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {   // stage by stage over the four words, as pf_fin4
+      lo[i] = __builtin_bit_cast(float, d[i] << 16) * kPfScale;
+      hi[i] = __builtin_bit_cast(float, d[i] & 0xFFFF0000u) * kPfScale;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = h16x2{(_Float16)lo[i], (_Float16)hi[i]};
+  } else {
+    const h16x2 s = {(_Float16)kPfScale, (_Float16)kPfScale};
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = __builtin_bit_cast(h16x2, d[i]) * s;
+  }
+  h16x8 r = {w[0].x, w[0].y, w[1].x, w[1].y, w[2].x, w[2].y, w[3].x, w[3].y};
+  return r;
+}
+
+// pf_body over 16-bit tiles.  The work split, the activation slabs, the 128 accumulators and the partial sums are pf_body's; what
+// differs is the weight stream.  A tile is 32 VGPRs per lane and row tile, so two whole blocks in registers (pf_body's scheme) would
+// be 256 VGPRs: the stream is pipelined by MFMA step instead.  A step is 64 elements of k = pieces 2pp, 2pp + 1 of each of the wave's
+// row tiles (2 * kPfRT loads of 1 KiB per wave); steps live in a ring of four buffers indexed by pp — a block has four steps, so the
+// indices are static across blocks — and the step kPfHalfAhead ahead is requested at the head of each step: three buffers (96 VGPRs)
+// are live at a time.  Dequantization is one packed multiply per word (or shift, multiply, convert for BF16): the unit loop is the
+// MFMAs' and the LDS reads'.
+constexpr int kPfHalfAhead = 2;
+template <bool BF16, int MT>
+__device__ __forceinline__ void pf_body_half(const PfGemm& G, const PfSeg& sg, uint32_t rg, uint32_t ks, uint32_t m_tiles, uint8_t* smem) {
+  static_assert(kPfHalfAhead >= 1 && kPfHalfAhead <= 3, "the ring holds four steps");
+  constexpr uint32_t kDma = (uint32_t)MT * 16 * 512 / kPfWaves;
+  constexpr uint32_t tb = 8192;
+  const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t n = lane & 15, c = lane >> 4;
+  const uint32_t per = (G.nblk + G.S - 1) / G.S;
+  const uint32_t b0 = ks * per, b1 = b0 + per < G.nblk ? b0 + per : G.nblk;
+  const uint32_t tile0 = (rg * kPfWaves + wave) * kPfRT;
+  const uint8_t* wt[kPfRT];
+#pragma unroll
+  for (int r = 0; r < kPfRT; r++) {
+    const uint32_t tl = tile0 + r < sg.ntiles ? tile0 + r : sg.ntiles - 1;   // clamped: loads are unconditional
+    wt[r] = sg.w + (size_t)tl * G.nblk * tb + lane * 16;
+  }
+  const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem;
+
+  f32x4 acc[kPfRT][MT];
+#pragma unroll
+  for (int r = 0; r < kPfRT; r++)
+#pragma unroll
+    for (int t = 0; t < MT; t++) acc[r][t] = (f32x4)(0.0f);
+
+  auto x_dma = [&](uint32_t b, uint32_t buf) {
+    const uint8_t* src = G.xh + (size_t)b * kPfSlabBytes + wave * kDma + lane * 16;
+    const uint32_t dst = lds_base + buf * kPfSlabBytes + wave * kDma;
+#pragma unroll
+    for (int i = 0; i < (int)(kDma / 1024); i++) {
+      uint32_t keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(src + i * 1024), "s"(dst + i * 1024) : "memory");
+    }
+  };
+  u32x4 ring[4][kPfRT][2];
+  auto w_load = [&](int pp, uint32_t b) {   // step pp of block b -> ring[pp]
+#pragma unroll
+    for (int r = 0; r < kPfRT; r++)
+#pragma unroll
+      for (int h = 0; h < 2; h++) ring[pp][r][h] = ldg_nt128(wt[r] + (size_t)b * tb + (2 * pp + h) * 1024);
+  };
+
+  if (b0 < b1) {
+    x_dma(b0, 0);
+#pragma unroll
+    for (int pp = 0; pp < kPfHalfAhead; pp++) w_load(pp, b0);
+  }
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) (the builtin: see pf_body)
+  __syncthreads();
+  for (uint32_t b = b0; b < b1; b++) {
+    const uint32_t cur = (b - b0) & 1;
+    const uint32_t bn = b + 1 < b1 ? b + 1 : b;   // the last block re-requests its own steps (unconditional loads)
+    // the next slab first: every weight load of this block is younger than it, so the partial wait at the block's end covers it
+    if (b + 1 < b1) x_dma(b + 1, cur ^ 1);
+    const uint8_t* xb = smem + cur * kPfSlabBytes + n * 512;
+    h16x8 bf[2][MT];
+    auto read_bf = [&](int ph, h16x8* dst) {
+      const uint32_t q = (uint32_t)((ph >> 1) * 8 + (ph & 1)) + c * 2;
+#pragma unroll
+      for (int t = 0; t < MT; t++) dst[t] = *reinterpret_cast<const h16x8*>(xb + t * 8192 + ((q ^ n) << 4));
+    };
+    read_bf(0, bf[0]);
+    h16x8 af[2];
+    af[0] = pf_half_frag<BF16>(ring[0][0][0]);
+    __builtin_amdgcn_sched_barrier(0);
+    // the block's 32 units (piece ph = 2pp + h, row tile r), one scheduling region each, as in pf_body: the unit's MFMAs, the NEXT
+    // unit's A fragment, the next phase's activation fragments in the first unit of a phase — and, at the head of a step, the
+    // requests of the step kPfHalfAhead ahead
+#pragma unroll
+    for (int u = 0; u < 8 * kPfRT; u++) {
+      const int ph = u / kPfRT, r = u % kPfRT;
+      if (u % (2 * kPfRT) == 0) {
+        const int pa = (ph >> 1) + kPfHalfAhead;
+        w_load(pa & 3, pa < 4 ? b : bn);
+      }
+      if (u + 1 < 8 * kPfRT) {
+        const int ph2 = (u + 1) / kPfRT, r2 = (u + 1) % kPfRT;
+        af[(u + 1) & 1] = pf_half_frag<BF16>(ring[ph2 >> 1][r2][ph2 & 1]);
+      }
+#pragma unroll
+      for (int t = 0; t < MT; t++) acc[r][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[u & 1], bf[ph & 1][t], acc[r][t], 0, 0, 0);
+      if (r == 0 && ph + 1 < 8) read_bf(ph + 1, bf[(ph + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // the next slab has landed (this wave's share; the barrier makes it everybody's); the kPfHalfAhead steps requested last stay in
+    // flight.  vmcnt's six bits: [3:0] and [15:14] of the operand.
+    constexpr int kLeft = kPfHalfAhead * 2 * kPfRT;
+    static_assert(kLeft < 64, "vmcnt has six bits");
+    __builtin_amdgcn_s_waitcnt(0x0F70 | (kLeft & 15) | ((kLeft >> 4) << 14));
+    __syncthreads();
+  }
+  // partial sums: as pf_body
+  uint32_t row0 = 0;
+  if (G.row_base) row0 = sload_u32(G.row_base);
+  float* part = G.part + ((size_t)ks * G.part_rows + row0) * G.ncols;
+#pragma unroll
+  for (int r = 0; r < kPfRT; r++) {
+    if (tile0 + r >= sg.ntiles) continue;
+    const uint32_t col = sg.col0 + (tile0 + r) * 16 + c * 4;
+#pragma unroll
+    for (int t = 0; t < MT; t++) {
+      if ((uint32_t)t >= m_tiles) continue;
+      const f32x4 v = acc[r][t] * (1.0f / kPfScale);
+      *reinterpret_cast<f32x4*>(part + (size_t)(t * 16 + n) * G.ncols + col) = v;
+    }
+  }
+}
+
 // EXPERIMENT (not in the product build; `make variant NAME=pf32 VSRC=prefill DEFS=-DPF_SHAPE32=1`), measured and not faster: Llama-3-8B
 // Q4_K_M 4.90 ms per 128-token pass against 4.82 on the same box, Mixtral 15.19 against 15.24; test_gpu_prefill.py passes on it; 290
 // registers per wave instead of 424.
@@ -559,6 +704,15 @@ __device__ __forceinline__ void pf_gemm_body(const PfGemm& G, uint8_t* pf_smem) 
   else if (is(PF_Q3K)) LGH_PF_RUN(PF_Q3K);
   else if (is(PF_Q2K)) LGH_PF_RUN(PF_Q2K);
 #undef LGH_PF_RUN
+#define LGH_PF_RUN_HALF(B)                                                               \
+  do {                                                                                   \
+    if (m_tiles <= 2) pf_body_half<B, 2>(G, sg, rg, blockIdx.y, m_tiles, pf_smem);       \
+    else if (m_tiles <= 4) pf_body_half<B, 4>(G, sg, rg, blockIdx.y, m_tiles, pf_smem);  \
+    else pf_body_half<B, kPfMT>(G, sg, rg, blockIdx.y, m_tiles, pf_smem);                \
+  } while (0)
+  else if (is(PF_F16)) LGH_PF_RUN_HALF(false);
+  else if (is(PF_BF16)) LGH_PF_RUN_HALF(true);
+#undef LGH_PF_RUN_HALF
 }
 
 template <uint32_t MASK>
@@ -573,9 +727,18 @@ __global__ void __launch_bounds__(kPfWaves * 64) LGH_NO_PK_F32 pf_gemm_lowbit_ke
   extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
   pf_gemm_body<MASK>(G, pf_smem);
 }
+// the instantiations over 16-bit tiles (pf_body_half): F16, BF16, and both (a launch whose matrices differ in type)
+constexpr uint32_t kPfHalfMask = (1u << PF_F16) | (1u << PF_BF16);
+template <uint32_t MASK>
+__global__ void __launch_bounds__(kPfWaves * 64) pf_gemm_half_kernel(const PfGemm G) {
+  static_assert((MASK & ~kPfHalfMask) == 0, "16-bit formats only: other families go in a launch of their own");
+  extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
+  pf_gemm_body<MASK>(G, pf_smem);
+}
 template <uint32_t MASK>
 static auto pf_gemm_kernel_of() {
-  if constexpr ((MASK & kPfLowbitMask) != 0) return &pf_gemm_lowbit_kernel<MASK>;
+  if constexpr ((MASK & kPfHalfMask) != 0) return &pf_gemm_half_kernel<MASK>;
+  else if constexpr ((MASK & kPfLowbitMask) != 0) return &pf_gemm_lowbit_kernel<MASK>;
   else return &pf_gemm_kernel<MASK>;
 }
 
@@ -609,6 +772,26 @@ size_t pf_part_bytes(const uint32_t* n_rows, int nw, uint32_t k, uint32_t part_r
   pf_plan(n_rows, nw, k, &rg, &S);
   for (int i = 0; i < nw; i++) cols += n_rows[i];
   return (size_t)S * part_rows * cols * 4;
+}
+
+// the instantiation for a launch's set of formats
+static hipError_t pf_gemm_dispatch(const PfGemm& G, uint32_t rg, uint32_t mask, hipStream_t st) {
+  switch (mask) {
+    case 1u << PF_Q4K: return pf_gemm_go<1u << PF_Q4K>(G, rg, st);
+    case 1u << PF_Q6K: return pf_gemm_go<1u << PF_Q6K>(G, rg, st);
+    case (1u << PF_Q4K) | (1u << PF_Q6K): return pf_gemm_go<(1u << PF_Q4K) | (1u << PF_Q6K)>(G, rg, st);
+    case 1u << PF_Q5K: return pf_gemm_go<1u << PF_Q5K>(G, rg, st);
+    case (1u << PF_Q5K) | (1u << PF_Q6K): return pf_gemm_go<(1u << PF_Q5K) | (1u << PF_Q6K)>(G, rg, st);
+    case 1u << PF_Q80: return pf_gemm_go<1u << PF_Q80>(G, rg, st);
+    case 1u << PF_Q40: return pf_gemm_go<1u << PF_Q40>(G, rg, st);
+    case 1u << PF_Q3K: return pf_gemm_go<1u << PF_Q3K>(G, rg, st);
+    case 1u << PF_Q2K: return pf_gemm_go<1u << PF_Q2K>(G, rg, st);
+    case (1u << PF_Q3K) | (1u << PF_Q6K): return pf_gemm_go<(1u << PF_Q3K) | (1u << PF_Q6K)>(G, rg, st);   // fused QKV of Q3_K_M
+    case 1u << PF_F16: return pf_gemm_go<1u << PF_F16>(G, rg, st);
+    case 1u << PF_BF16: return pf_gemm_go<1u << PF_BF16>(G, rg, st);
+    case kPfHalfMask: return pf_gemm_go<kPfHalfMask>(G, rg, st);
+    default: return mask & ~31u ? pf_gemm_go<127u>(G, rg, st) : pf_gemm_go<31u>(G, rg, st);   // any other mix: of the first five formats, of all
+  }
 }
 
 // Plans and launches one GEMM: up to 3 weight matrices that share the input XH (k elements per token), outputs side by
@@ -648,19 +831,24 @@ hipError_t pf_gemm_launch(const DevWeight* const* W, int nw, const uint8_t* xh, 
   if (part_rows < (uint32_t)kPfTokens || (size_t)G.S * part_rows * col * 4 > part_bytes) return hipErrorInvalidValue;
   *S_out = G.S;
   *ncols_out = col;
-  switch (mask) {
-    case 1u << PF_Q4K: return pf_gemm_go<1u << PF_Q4K>(G, rg, st);
-    case 1u << PF_Q6K: return pf_gemm_go<1u << PF_Q6K>(G, rg, st);
-    case (1u << PF_Q4K) | (1u << PF_Q6K): return pf_gemm_go<(1u << PF_Q4K) | (1u << PF_Q6K)>(G, rg, st);
-    case 1u << PF_Q5K: return pf_gemm_go<1u << PF_Q5K>(G, rg, st);
-    case (1u << PF_Q5K) | (1u << PF_Q6K): return pf_gemm_go<(1u << PF_Q5K) | (1u << PF_Q6K)>(G, rg, st);
-    case 1u << PF_Q80: return pf_gemm_go<1u << PF_Q80>(G, rg, st);
-    case 1u << PF_Q40: return pf_gemm_go<1u << PF_Q40>(G, rg, st);
-    case 1u << PF_Q3K: return pf_gemm_go<1u << PF_Q3K>(G, rg, st);
-    case 1u << PF_Q2K: return pf_gemm_go<1u << PF_Q2K>(G, rg, st);
-    case (1u << PF_Q3K) | (1u << PF_Q6K): return pf_gemm_go<(1u << PF_Q3K) | (1u << PF_Q6K)>(G, rg, st);   // fused QKV of Q3_K_M
-    default: return mask & ~31u ? pf_gemm_go<127u>(G, rg, st) : pf_gemm_go<31u>(G, rg, st);   // any other mix: of the first five formats, of all
+  if (!(mask & kPfHalfMask) || !(mask & ~kPfHalfMask)) return pf_gemm_dispatch(G, rg, mask, st);
+  // 16-bit and int8-tile matrices side by side (a file that keeps some projections unquantized): one launch per family over its own
+  // matrices, as mv_formats_split does for decode.  Columns, splits and the partial-sum buffer stay the whole GEMM's.
+  for (int half = 0; half < 2; half++) {
+    PfGemm Gf = G;
+    uint32_t rgf = 0, maskf = 0;
+    Gf.nseg = 0;
+    for (int i = 0; i < nw; i++) {
+      if ((int)((kPfHalfMask >> G.seg[i].fmt) & 1u) != half) continue;
+      PfSeg& sgf = Gf.seg[Gf.nseg++];
+      sgf = G.seg[i];
+      sgf.rg_begin = rgf;
+      rgf += (sgf.ntiles + kPfWaves * kPfRT - 1) / (kPfWaves * kPfRT);
+      maskf |= 1u << sgf.fmt;
+    }
+    if (hipError_t e = pf_gemm_dispatch(Gf, rgf, maskf, st); e != hipSuccess) return e;
   }
+  return hipSuccess;
 }
 
 // ------------------------------------------------------------------------------------------------

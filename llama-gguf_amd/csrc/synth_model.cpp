@@ -16,7 +16,7 @@ namespace {
 
 enum : uint32_t {
   T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q4_1 = 3, T_Q5_0 = 6, T_Q5_1 = 7, T_Q8_0 = 8,
-  T_Q2_K = 10, T_Q3_K = 11, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14
+  T_Q2_K = 10, T_Q3_K = 11, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_BF16 = 30
 };
 
 struct Rng {
@@ -85,7 +85,7 @@ void st16(uint8_t* p, uint16_t v) { std::memcpy(p, &v, 2); }
 
 size_t blk_size(uint32_t t) {
   switch (t) {
-    case T_F32: case T_F16: return 1;
+    case T_F32: case T_F16: case T_BF16: return 1;
     case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q8_0: return 32;
     case T_Q2_K: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: return 256;
     default: return 0;
@@ -94,7 +94,7 @@ size_t blk_size(uint32_t t) {
 
 size_t blk_bytes(uint32_t t) {
   switch (t) {
-    case T_F32: return 4; case T_F16: return 2;
+    case T_F32: return 4; case T_F16: case T_BF16: return 2;
     case T_Q4_0: return 18; case T_Q4_1: return 20; case T_Q5_0: return 22; case T_Q5_1: return 24;
     case T_Q8_0: return 34; case T_Q2_K: return 84; case T_Q3_K: return 110; case T_Q4_K: return 144;
     case T_Q5_K: return 176; case T_Q6_K: return 210;
@@ -243,7 +243,13 @@ int lgs_fill_tensor(const char* name, uint32_t type, uint64_t n_elems, uint64_t 
         else if (kind == 2) v = 0.01f * r.sym();
         else v = 1.7320508f * base * r.sym();
         if (type == T_F32) std::memcpy(dst + e * 4, &v, 4);
-        else st16(dst + e * 2, f2h(v));
+        else if (type == T_F16) st16(dst + e * 2, f2h(v));
+        else {   // BF16: the F16 fill's value, kept as the high half of its f32
+          const float hv = h2f(f2h(v));
+          uint32_t bits;
+          std::memcpy(&bits, &hv, 4);
+          st16(dst + e * 2, (uint16_t)(bits >> 16));
+        }
       }
     }
   };

@@ -62,10 +62,11 @@ SYM_NAMES = ("lgh::mv_kernel<1u, 1024>", "lgh::mv_kernel<8u, 1024>", "lgh::mv_ke
              "lgh::mv_kernel<2u, 768>", "lgh::mv_kernel<4u, 512>", "lgh::mv_kernel<5u, 512>", "lgh::mv_kernel<6u, 512>",
              "lgh::mv_kernel<31u, 512>", "lgh::f32_matvec_kernel", "lgh::attn_partial_kernel", "lgh::attn_combine_kernel",
              "lgh::embed_kernel", "lgh::argmax_stage1+2", "lgh::moe_router_kernel", "other", "lgh::mvq_kernel<1u>", "lgh::mvq_kernel<2u>", "lgh::mvq_kernel<3u>", "lgh::mvq_kernel<4u>",
-             "lgh::mvq_kernel<8u>", "unused", "lgh::mvq_kernel<32u>")
+             "lgh::mvq_kernel<8u>", "unused", "lgh::mvq_kernel<32u>", "lgh::mvh_kernel<false>", "lgh::mvh_kernel<true>")
 FLAG_NO_GRAPH = 1
 BATCH_F32_MATRIX = 1        # lgh_set_batch_policy: steps of >= (policy >> 8 & 0xFF, 0 = the library default) sequences on the f32 matrix cores
 WEIGHTS_LOWBIT_TILES = 1    # lgh_set_weight_policy: Q3_K / Q2_K matrices stay quantized in HBM (matrix-core tile layouts) instead of f32
+WEIGHTS_HALF_TILES = 4      # ... F16 / BF16 matrices stay 16-bit in HBM (8192-B tiles, their own decode mat-vec); bit 1 is not assigned
 PREFILL_BATCH_BYTE_KV = 1   # lgh_set_prefill_policy: int8 / FP8 caches take the batched prompt pass (own sequence, slots, stage contexts)
 FLAG_EXACT_PREFILL = 4   # forward_batch feeds tokens one by one (f32 throughout) instead of the batched f16 GEMM path
 KV_F32, KV_INT8, KV_FP8_E4M3, KV_FP8_E5M2 = 0, 1, 2, 3   # lgh_model_desc.kv_cache_type: f32, or QuantizedKVCache's formats (kv_quantized.rs; no CLI flag reaches them)
@@ -435,7 +436,8 @@ class HipGpuInference:
         self._call(load_library().lgh_set_prefill_policy(self._h, policy))
 
     def set_weight_policy(self, policy: int) -> None:
-        """lgh_set_weight_policy: WEIGHTS_LOWBIT_TILES keeps Q3_K / Q2_K matrices quantized in HBM; before the first upload_tensor only."""
+        """lgh_set_weight_policy: WEIGHTS_LOWBIT_TILES keeps Q3_K / Q2_K matrices quantized in HBM, WEIGHTS_HALF_TILES F16 / BF16 ones 16-bit;
+        before the first upload_tensor only."""
         self._call(load_library().lgh_set_weight_policy(self._h, policy))
 
     def reset(self) -> None:
