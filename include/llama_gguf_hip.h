@@ -143,7 +143,7 @@ enum {
  * LGH_SYM_MV_* are the instantiations of lgh::mv_kernel<MASK, MAXT> (the VALU dequant mat-vec, csrc/matvec.hip; MASK bits:
  * Q4_K 1, Q5_K 2, Q6_K 4, Q8_0 8, Q4_0 16; MAXT = the instantiation's thread cap).  LGH_SYM_MVQ_* are the instantiations of
  * lgh::mvq_kernel<MASK> (the int8 matrix-core mat-vec, csrc/matvec_mfma.hip; ITS mask bits: Q4_K 1, Q6_K 2, Q5_K 4, Q8_0 8,
- * Q4_0 16, Q3_K 32, Q2_K 64). */
+ * Q4_0 16, Q3_K 32, Q2_K 64, Q4_1 128, Q5_0 256, Q5_1 512). */
 enum {
   LGH_SYM_MV_Q4K = 0,      /* lgh::mv_kernel<1u, 1024>  : every matrix of the launch Q4_K */
   LGH_SYM_MV_Q80 = 1,      /* lgh::mv_kernel<8u, 1024>  : Q8_0 */
@@ -169,7 +169,8 @@ enum {
   LGH_SYM_MVQ_Q3K_Q2K = 21, /* lgh::mvq_kernel<32u> / <64u> : Q3_K / Q2_K (contexts with LGH_WEIGHTS_LOWBIT_TILES) */
   LGH_SYM_MVH_F16 = 22,    /* lgh::mvh_kernel<false> : F16 kept 16-bit (csrc/matvec_h16.hip; contexts with LGH_WEIGHTS_HALF_TILES) */
   LGH_SYM_MVH_BF16 = 23,   /* lgh::mvh_kernel<true>  : BF16 kept 16-bit */
-  LGH_SYM_COUNT = 24       /* = the last entry + 1: a new symbol is appended and bumps this, and SYM_NAMES of hip_backend.py follows by hand */
+  LGH_SYM_MVQ_LEGACY = 24, /* lgh::mvq_legacy_kernel<128u> / <256u> / <512u> : Q4_1 / Q5_0 / Q5_1 (contexts with LGH_WEIGHTS_LEGACY_TILES) */
+  LGH_SYM_COUNT = 25       /* = the last entry + 1: a new symbol is appended and bumps this, and SYM_NAMES of hip_backend.py follows by hand */
 };
 
 typedef struct lgh_stats {
@@ -285,10 +286,18 @@ int lgh_set_prefill_policy(lgh_ctx* ctx, uint32_t policy);
  *     f16(256 w), exact for F16 and one round-to-nearest-even for BF16, under the pass's standing |w| < 256; lgh_prefill_is_batched is 1
  *     for such a model.  A matrix with k > 32768, or an expert stack with k > 16384, keeps the f32 expansion (the mat-vec stages its
  *     input vectors in LDS).  Not with the bit: lgh_forward_multi (refused as for the f32 expansion) and tensor-parallel sharding.
+ *   LGH_WEIGHTS_LEGACY_TILES  (bit 3, value 8; combines freely with bits 0 and 2)  Q4_1, Q5_0 and Q5_1 matrices and expert stacks
+ *     (k % 256 == 0) stay quantized in HBM, in 16-row tile layouts of 2560 / 2816 / 3072 B per 256 elements — the native bytes of 16 rows
+ *     (csrc/matvec_mfma.hip) — and take the kernels of the other tile formats: the decode mat-vec, the multi-sequence mat-vecs
+ *     (lgh_forward_multi, bit-identical per sequence to lgh_forward; LGH_BATCH_F32_MATRIX applies) and the batched prompt pass, for which
+ *     lgh_prefill_is_batched then answers 1.  Same dequantized weights times x (dequant.rs:36-101) as the f32 expansion within the tile
+ *     kernels' bound, |delta| <= 1e-4 * sum|x_i * w_i| + 1e-6, not the f32 mat-vec's bits; the prompt pass under its standing |w| < 256
+ *     and, for the additive minimum of Q4_1 / Q5_1, 256 * |m| <= 65504.  lgh_stats.weight_bytes counts the native GGUF bytes.  A launch
+ *     that mixes one of the three with another format (a Q6_K output projection, say) goes out as one launch per matrix.
  * Out of scope: the handles that create their contexts themselves — lgh_tp_*, lgh_pipeline_*, lgh_load_gguf — keep the default, and
- * so do the other expanded types (Q4_1, Q5_0, Q5_1, Q8_1, Q8_K) whatever the word says.  measured: profiles/lowbit_weights.md,
- * profiles/half_weights.md */
-enum { LGH_WEIGHTS_DEFAULT = 0, LGH_WEIGHTS_LOWBIT_TILES = 1u << 0, LGH_WEIGHTS_HALF_TILES = 1u << 2 };
+ * so do the other expanded types (Q8_1, Q8_K) and any matrix with k % 256 != 0, whatever the word says.  measured:
+ * profiles/lowbit_weights.md, profiles/half_weights.md, profiles/legacy_weights.md */
+enum { LGH_WEIGHTS_DEFAULT = 0, LGH_WEIGHTS_LOWBIT_TILES = 1u << 0, LGH_WEIGHTS_HALF_TILES = 1u << 2, LGH_WEIGHTS_LEGACY_TILES = 1u << 3 };
 int lgh_set_weight_policy(lgh_ctx* ctx, uint32_t policy);
 /* GpuInference::reset (gpu_only.rs:808-843) — O(1): only the position is rewound (model/mod.rs:110-117) */
 void lgh_reset(lgh_ctx* ctx);
@@ -642,7 +651,8 @@ int lgh_op_mat_mat(int device, uint32_t type, const void* w, const float* x, flo
 /* lgh_op_vec_mat (norm_w == NULL) / lgh_op_norm_vec_mat and lgh_op_mat_mat on a context with lgh_set_weight_policy's word `weight_policy`:
  * with LGH_WEIGHTS_LOWBIT_TILES a Q3_K / Q2_K matrix runs from its tile layout (and lgh_op_mat_mat_ex takes those two types as well);
  * with LGH_WEIGHTS_HALF_TILES an F16 / BF16 matrix runs from its 16-bit tiles in both (without the bit lgh_op_mat_mat_ex answers Unsupported
- * for the two types, as ever).
+ * for the two types, as ever); with LGH_WEIGHTS_LEGACY_TILES a Q4_1 / Q5_0 / Q5_1 matrix runs from its tile layout in both (without the
+ * bit lgh_op_mat_mat_ex answers Unsupported for the three).
  * Policy 0 is the plain entry point, bit for bit.  *device_bytes (optional): the bytes the matrix occupies on the device — rows padded
  * to 16 times the tile layout's bytes per row, or 4 * n * k where it was expanded to f32 — which tells the layout it ran from. */
 int lgh_op_vec_mat_ex(int device, uint32_t ggml_type, const void* w, const float* x, const float* norm_w, float eps, float* out, size_t k,

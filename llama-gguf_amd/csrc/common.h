@@ -47,6 +47,8 @@ constexpr int kDevQ4K_T16 = 1012;  // device-only type tag: Q4_K in the 16-row t
 constexpr int kDevQ6K_T16 = 1014;  // Q6_K in its 16-row tile layout (3392 B per tile), same kernel
 constexpr int kDevQ5K_T16 = 1013, kDevQ80_T16 = 1008, kDevQ40_T16 = 1002;   // Q5_K (2816 B), Q8_0 (4352 B), Q4_0 (2304 B) tiles
 constexpr int kDevQ3K_T16 = 1011, kDevQ2K_T16 = 1010;   // Q3_K (1824 B), Q2_K (1344 B) tiles: contexts with LGH_WEIGHTS_LOWBIT_TILES only
+// Q4_1 (2560 B), Q5_0 (2816 B), Q5_1 (3072 B) tiles: contexts with LGH_WEIGHTS_LEGACY_TILES only
+constexpr int kDevQ41_T16 = 1003, kDevQ50_T16 = 1006, kDevQ51_T16 = 1007;
 // F16 / BF16 kept 16-bit, in 8192-B tiles (matvec_h16.hip): contexts with LGH_WEIGHTS_HALF_TILES only.  Not mfma_type: their decode
 // mat-vec reads f32 x, not XQ records
 constexpr int kDevF16_T16 = 1001, kDevBF16_T16 = 1030;
@@ -56,7 +58,8 @@ inline bool half_type(int t) { return t == kDevF16_T16 || t == kDevBF16_T16; }
 constexpr uint32_t kMvhMaxStagedFloats = 32768;
 inline bool half_tiles_fit(uint32_t k, uint32_t n_stack) { return (uint64_t)k * (n_stack > 1 ? 2 : 1) <= kMvhMaxStagedFloats; }
 inline bool mfma_type(int t) {
-  return t == kDevQ4K_T16 || t == kDevQ6K_T16 || t == kDevQ5K_T16 || t == kDevQ80_T16 || t == kDevQ40_T16 || t == kDevQ3K_T16 || t == kDevQ2K_T16;
+  return t == kDevQ4K_T16 || t == kDevQ6K_T16 || t == kDevQ5K_T16 || t == kDevQ80_T16 || t == kDevQ40_T16 || t == kDevQ3K_T16 || t == kDevQ2K_T16 ||
+         t == kDevQ41_T16 || t == kDevQ50_T16 || t == kDevQ51_T16;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -72,6 +75,7 @@ inline bool mfma_type(int t) {
 //   Q4_0  plane0 qs[16]/blk,  plane1 d(f16)/blk
 //   F32   plane0 row-major [n][k]
 //   Q3_K / Q2_K  tiles of 1824 / 1344 B for the same kernel, on contexts that asked for them (lgh_set_weight_policy)   plane0
+//   Q4_1 / Q5_0 / Q5_1  tiles of 2560 / 2816 / 3072 B for the same kernel, on contexts that asked for them (LGH_WEIGHTS_LEGACY_TILES)   plane0
 //   F16 / BF16   tiles of 8192 B (2 B per element) for mvh_kernel (matvec_h16.hip), on contexts that asked for them             plane0
 // Every other GGUF type is dequantized to F32 at upload (the reference does the same for types
 // without a quantized kernel, src/backend/cuda/dequant_weights.rs:211-231).

@@ -27,6 +27,8 @@ __device__ __forceinline__ uint16_t ldg_nt16(const void* p) {
 #else
 #define LGH_NO_PK_F32
 #endif
+// (The kernels of Q4_1 / Q5_0 / Q5_1, *_legacy_kernel, keep packed f32 operations like the five default formats: within their register
+// limits either way, 0 to 4 VGPRs apart.)
 
 __device__ __forceinline__ float h2f(uint32_t bits16) {
   _Float16 h;

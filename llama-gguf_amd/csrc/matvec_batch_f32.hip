@@ -23,6 +23,7 @@
 //   Q4_K, Q5_K  w = fma(q, d * sc, -(dmin * mn))      Q6_K  w = fma(q', d * sc, -32 * d * sc) = round(d * sc * (q' - 32))
 //   Q4_0        w = fma(q, d, -8 * d)                 Q8_0  w = fma(q ^ 0x80, d, -128 * d)    = round(d * q)
 //   Q2_K        as Q4_K, one (sc, mn) per chunk       Q3_K  w = fma(q, d * sc, -4 * d * sc)   = round(d * sc * (q - 4))
+//   Q4_1, Q5_1  w = fma(q, d, m)                      Q5_0  w = fma(q, d, -16 * d)            = round(d * (q - 16))
 //
 // Activations.  Plain f32: x[s][.] * norm_w[.] (the product the XQ producers round; x alone without a norm) staged per chunk of
 // kXfCb blocks for all sequences in LDS, double-buffered with one barrier per chunk; rows of sequences >= n_seq are zero.  A
@@ -124,6 +125,8 @@ mvqf_kernel(const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B, float* __rest
           else if (is(F_Q80)) { sa[pp] = t.f[pp]; sb[pp] = -128.0f * sa[pp]; }
           else if (is(F_Q40)) { sa[pp] = t.f[pp]; sb[pp] = -8.0f * sa[pp]; }
           else if (is(F_Q3K)) { sa[pp] = t.dd * t.f[pp]; sb[pp] = -4.0f * sa[pp]; }
+          else if (is(F_Q50)) { sa[pp] = t.f[pp]; sb[pp] = -16.0f * sa[pp]; }
+          else if (is(F_Q41) || is(F_Q51)) { sa[pp] = t.f[pp]; sb[pp] = t.g[pp]; }
           else { sa[pp] = t.dd * t.f[pp]; sb[pp] = -(t.dmin * t.g[pp]); }
         }
         const float* xrow = xsm + buf * kXfBuf + sq * kXfRow + bi * 256 + c * 16;
@@ -177,6 +180,7 @@ hipError_t mvqf_launch(uint32_t mask, const Mvqb2Geom& Gm, const MvLaunch& L, co
   switch (mask) {
     LGH_MVQF_CASE(1u << F_Q4K); LGH_MVQF_CASE(1u << F_Q6K); LGH_MVQF_CASE(1u << F_Q5K); LGH_MVQF_CASE(1u << F_Q80); LGH_MVQF_CASE(1u << F_Q40);
     LGH_MVQF_CASE(1u << F_Q3K); LGH_MVQF_CASE(1u << F_Q2K);
+    LGH_MVQF_CASE(1u << F_Q41); LGH_MVQF_CASE(1u << F_Q50); LGH_MVQF_CASE(1u << F_Q51);
     LGH_MVQF_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQF_CASE((1u << F_Q5K) | (1u << F_Q6K));
     default: return hipErrorInvalidValue;
   }

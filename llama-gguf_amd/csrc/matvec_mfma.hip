@@ -1,5 +1,5 @@
-// matvec_mfma.hip — quantized mat-vec on the int8 matrix cores (v_mfma_i32_16x16x64_i8): Q4_K, Q5_K, Q6_K, Q8_0, Q4_0, and Q3_K / Q2_K on
-// contexts that keep them quantized (lgh_set_weight_policy).
+// matvec_mfma.hip — quantized mat-vec on the int8 matrix cores (v_mfma_i32_16x16x64_i8): Q4_K, Q5_K, Q6_K, Q8_0, Q4_0, and Q3_K / Q2_K and
+// Q4_1 / Q5_0 / Q5_1 on contexts that keep them quantized (lgh_set_weight_policy).
 //
 // Why MFMA for a mat-VEC.  The VALU formulation (matvec.hip) needs ~3.6 vector instructions per weight
 // (byte->f32 convert, FMA, nibble masks); measured on MI355X a wave64 v_cvt_f32_ubyte costs ~2.0 ns and a
@@ -14,7 +14,7 @@
 // MFMA is block-diagonal over its four k-chunks (rows 4c..4c+3 = the four digits of chunk c), 16 weight rows x 64
 // quants are the B operand, and D holds sum_k q_k * digit_i,k as exact int32 — lane group c gets chunk c.  The four
 // digit sums are recombined once in f32 (V = D0*2^24 + D1*2^16 + D2*2^8 + D3) and scaled by d*sc*s*2^-30; min terms
-// (Q4_K, Q5_K, Q2_K) and offsets (Q6_K -32, Q4_0 -8, Q3_K -4) go through the f32 sums of x per chunk, the reference's x_acc.
+// (Q4_K, Q5_K, Q2_K, Q4_1, Q5_1) and offsets (Q6_K -32, Q4_0 -8, Q3_K -4, Q5_0 -16) go through the f32 sums of x per chunk, the reference's x_acc.
 // Error vs the reference's sequential f32 sum is at f32 rounding level and independent of summation order.
 //
 // Device layout "tile16" (same bytes as GGUF, rows padded to 16): a tile = 16 rows x one 256-element block = 2304 B.
@@ -340,6 +340,72 @@ __global__ void __launch_bounds__(256) repack_lowbit_t16_kernel(const uint8_t* _
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Q4_1, Q5_0, Q5_1 -> tile16 (contexts with LGH_WEIGHTS_LEGACY_TILES; without it all three are expanded to f32 at upload).  Eight
+// native blocks of 32 elements {d, [m], [qh[4]], qs[16]} make a row's 256 elements; elements 0..15 of a block are the low nibbles of
+// qs[0..15], 16..31 the high nibbles, bit j of qh the fifth bit of element j (dequant.rs:36-101).  Same lane mapping as above: chunk
+// 4pp + c lies in block 2pp + (c >> 1).  Tile bytes = the native bytes of 16 rows:
+//   Q4_1 (2560 B = 16 x 160)  y = d * q + m, q in 0..15
+//     [0, 2048)     the nibble words, exactly as Q4_0's      [2048, 2304)  per row the 8 f16 d      [2304, 2560)  per row the 8 f16 m
+//   Q5_0 (2816 B = 16 x 176)  y = d * (q - 16), q = nibble | fifth << 4 in 0..31
+//     [0, 2304)     the Q4_0 tile (nibble words, d)
+//     [2304, 2816)  lane-major 8 B: the fifth bits as Q5_K stores them, a dword per step PAIR (low nibbles = even step, high nibbles =
+//                   odd step), byte t = f[t] | f[t+4] << 1 | f[t+8] << 2 | f[t+12] << 3
+//   Q5_1 (3072 B = 16 x 192)  y = d * q + m, q in 0..31
+//     [0, 2560)     the Q4_1 tile (nibble words, d, m)       [2560, 3072)  the fifth bits likewise
+// One thread per (row, 256-element block, step); the even step of a pair writes the pair's fifth-bit dword, so no atomics and no
+// clearing pass; every destination byte is written, padded rows as zeros.
+// ------------------------------------------------------------------------------------------------
+template <int F>
+__global__ void __launch_bounds__(256) repack_legacy_t16_kernel(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dst, uint32_t n_rows,
+                                                               uint32_t nblk, uint64_t total) {
+  constexpr uint32_t TB = fmt_tile_bytes(F);
+  constexpr bool kMin = F != F_Q50, kFifth = F != F_Q41;
+  constexpr uint32_t QH = kMin ? 4u : 2u, QS = QH + (kFifth ? 4u : 0u), BS = QS + 16u;   // offsets of qh and qs, bytes of a native block
+  constexpr uint32_t HOFF = kMin ? 2560u : 2304u;                                         // the fifth bits' place in the tile
+  for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (uint64_t)gridDim.x * 256) {
+    const uint32_t pp = (uint32_t)(idx & 3);
+    const uint64_t rb = idx >> 2;
+    const uint32_t row = (uint32_t)(rb / nblk), b = (uint32_t)(rb % nblk);
+    const uint32_t rt = row >> 4, n = row & 15;
+    uint8_t* tile = dst + ((size_t)rt * nblk + b) * TB;
+    const bool live = row < n_rows;
+    const uint8_t* src = raw + ((size_t)row * nblk + b) * (8 * BS);
+    auto nib = [&](uint32_t e) -> uint32_t {   // element e of the 256
+      if (!live) return 0u;
+      const uint32_t byte = src[(e >> 5) * BS + QS + (e & 15)];
+      return (e & 16) ? byte >> 4 : byte & 15u;
+    };
+    auto fifth = [&](uint32_t e) -> uint32_t { return live ? (src[(e >> 5) * BS + QH + ((e & 31) >> 3)] >> (e & 7)) & 1u : 0u; };
+    auto hword = [&](uint32_t e0) {   // the fifth bits of the 16 elements from e0 on, in the low nibbles
+      uint32_t H = 0;
+#pragma unroll
+      for (uint32_t t = 0; t < 4; t++)
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) H |= fifth(e0 + 4 * j + t) << (8 * t + j);
+      return H;
+    };
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++) {
+      const uint32_t lane = 16 * c + n, e0 = 64 * pp + 16 * c;
+      uint32_t N0 = 0, N1 = 0;
+#pragma unroll
+      for (uint32_t t = 0; t < 4; t++) {
+        N0 |= (nib(e0 + t) | nib(e0 + t + 4) << 4) << (8 * t);
+        N1 |= (nib(e0 + t + 8) | nib(e0 + t + 12) << 4) << (8 * t);
+      }
+      uint32_t* w = reinterpret_cast<uint32_t*>(tile + (pp >> 1) * 1024 + lane * 16 + (pp & 1) * 8);
+      w[0] = N0;
+      w[1] = N1;
+      if (kFifth && (pp & 1) == 0) *reinterpret_cast<uint32_t*>(tile + HOFF + lane * 8 + (pp >> 1) * 4) = hword(e0) | hword(e0 + 64) << 4;
+    }
+    // two f16 d (and m) per step thread: blocks 2pp, 2pp + 1
+    const uint8_t *s0 = src + (2 * pp) * BS, *s1 = s0 + BS;
+    *reinterpret_cast<uint32_t*>(tile + 2048 + n * 16 + pp * 4) = live ? (uint32_t)(s0[0] | s0[1] << 8) | (uint32_t)(s1[0] | s1[1] << 8) << 16 : 0u;
+    if (kMin) *reinterpret_cast<uint32_t*>(tile + 2304 + n * 16 + pp * 4) = live ? (uint32_t)(s0[2] | s0[3] << 8) | (uint32_t)(s1[2] | s1[3] << 8) << 16 : 0u;
+  }
+}
+
 hipError_t repack_t16_launch(int dev_type, const uint8_t* raw, uint8_t* dst, uint32_t n_rows, uint32_t nblk, hipStream_t st) {
   const uint64_t total = (uint64_t)((n_rows + 15) / 16) * 16 * nblk * 4;
   uint64_t blocks = (total + 255) / 256;
@@ -358,6 +424,9 @@ hipError_t repack_t16_launch(int dev_type, const uint8_t* raw, uint8_t* dst, uin
     case F_Q40: hipLaunchKernelGGL((repack_t16_kernel<F_Q40>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
     case F_Q3K: hipLaunchKernelGGL((repack_lowbit_t16_kernel<F_Q3K>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
     case F_Q2K: hipLaunchKernelGGL((repack_lowbit_t16_kernel<F_Q2K>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
+    case F_Q41: hipLaunchKernelGGL((repack_legacy_t16_kernel<F_Q41>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
+    case F_Q50: hipLaunchKernelGGL((repack_legacy_t16_kernel<F_Q50>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
+    case F_Q51: hipLaunchKernelGGL((repack_legacy_t16_kernel<F_Q51>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -563,8 +632,8 @@ __device__ __forceinline__ void mvq_body(const uint32_t bid, uint32_t wbpack, ui
     else if constexpr (NT * (LPT) == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");          \
     else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");                                         \
   } while (0)
-      if (is(F_Q6K) || is(F_Q80)) LGH_WAIT_BEHIND(5);
-      else if (is(F_Q5K) || is(F_Q3K)) LGH_WAIT_BEHIND(4);
+      if (is(F_Q6K) || is(F_Q80) || is(F_Q51)) LGH_WAIT_BEHIND(5);
+      else if (is(F_Q5K) || is(F_Q3K) || is(F_Q41) || is(F_Q50)) LGH_WAIT_BEHIND(4);
       else LGH_WAIT_BEHIND(3);
 #undef LGH_WAIT_BEHIND
       LGH_WSTAMP(4);
@@ -658,9 +727,19 @@ __global__ void __launch_bounds__(kWaves * 64) LGH_NO_PK_F32 mvq_lowbit_kernel(u
   mvq_body<MASK>(blockIdx.x, wbpack, geom, geom2, L_red_floats, lds_red_off, L, smem8);
   LGH_TL_END();
 }
+// Q4_1, Q5_0, Q5_1 (contexts with LGH_WEIGHTS_LEGACY_TILES): the same body under a name of its own
+template <uint32_t MASK>
+__global__ void __launch_bounds__(kWaves * 64) mvq_legacy_kernel(uint32_t wbpack, uint32_t geom, uint32_t geom2, uint32_t L_red_floats,
+                                                                               uint32_t lds_red_off, const MvLaunch L) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  LGH_TL_BEGIN(mvq, lgh::TL_MVQ, geom2);
+  mvq_body<MASK>(blockIdx.x, wbpack, geom, geom2, L_red_floats, lds_red_off, L, smem8);
+  LGH_TL_END();
+}
 template <uint32_t MASK>
 static auto mvq_kernel_of() {
-  if constexpr ((MASK & kLowbitMask) != 0) return &mvq_lowbit_kernel<MASK>;
+  if constexpr ((MASK & kLegacyMask) != 0) return &mvq_legacy_kernel<MASK>;
+  else if constexpr ((MASK & kLowbitMask) != 0) return &mvq_lowbit_kernel<MASK>;
   else return &mvq_kernel<MASK>;
 }
 
@@ -1067,6 +1146,7 @@ hipError_t mvq_launch(const MvLaunch& L0, uint32_t n_wg, uint32_t threads, hipSt
   switch (mask) {   // single formats and the two mixes of the "_M" quantisations (fused QKV: V in Q6_K)
     LGH_MVQ_CASE(1u << F_Q4K); LGH_MVQ_CASE(1u << F_Q6K); LGH_MVQ_CASE(1u << F_Q5K); LGH_MVQ_CASE(1u << F_Q80); LGH_MVQ_CASE(1u << F_Q40);
     LGH_MVQ_CASE(1u << F_Q3K); LGH_MVQ_CASE(1u << F_Q2K);
+    LGH_MVQ_CASE(1u << F_Q41); LGH_MVQ_CASE(1u << F_Q50); LGH_MVQ_CASE(1u << F_Q51);
     LGH_MVQ_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQ_CASE((1u << F_Q5K) | (1u << F_Q6K));
     default: return hipErrorInvalidValue;   // other mixes: the caller launches one format at a time
   }

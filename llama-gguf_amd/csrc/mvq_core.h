@@ -14,17 +14,19 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTileBytes = 2304;      // Q4_K tile16
 constexpr int kTileBytesQ6 = 3392;    // Q6_K tile16
 // formats of the matrix-core mat-vec; a kernel instantiation handles the formats in its MASK (bit = 1 << format)
-enum : int { F_Q4K = 0, F_Q6K = 1, F_Q5K = 2, F_Q80 = 3, F_Q40 = 4, F_Q3K = 5, F_Q2K = 6, F_COUNT = 7 };
+enum : int { F_Q4K = 0, F_Q6K = 1, F_Q5K = 2, F_Q80 = 3, F_Q40 = 4, F_Q3K = 5, F_Q2K = 6, F_Q41 = 7, F_Q50 = 8, F_Q51 = 9, F_COUNT = 10 };
 constexpr uint32_t kLowbitMask = (1u << F_Q3K) | (1u << F_Q2K);   // instantiations that hold one of these are the *_lowbit_kernel twins
+constexpr uint32_t kLegacyMask = (1u << F_Q41) | (1u << F_Q50) | (1u << F_Q51);   // ... and of these the *_legacy_kernel ones
 __host__ __device__ constexpr uint32_t fmt_tile_bytes(int f) {   // = 16 rows x the GGUF bytes of 256 elements (Q6_K: +32 pad; Q3_K: 114 per row)
-  return f == F_Q4K ? 2304u : f == F_Q6K ? 3392u : f == F_Q5K ? 2816u : f == F_Q80 ? 4352u : f == F_Q3K ? 1824u : f == F_Q2K ? 1344u : 2304u;
+  return f == F_Q4K ? 2304u : f == F_Q6K ? 3392u : f == F_Q5K ? 2816u : f == F_Q80 ? 4352u : f == F_Q3K ? 1824u : f == F_Q2K ? 1344u
+         : f == F_Q41 ? 2560u : f == F_Q50 ? 2816u : f == F_Q51 ? 3072u : 2304u;
 }
 __host__ __device__ constexpr int fmt_loads_per_tile(int f) {
-  return f == F_Q4K ? 3 : f == F_Q6K ? 5 : f == F_Q5K ? 4 : f == F_Q80 ? 5 : f == F_Q3K ? 4 : 3;
+  return f == F_Q4K ? 3 : f == F_Q6K ? 5 : f == F_Q5K ? 4 : f == F_Q80 ? 5 : f == F_Q3K ? 4 : f == F_Q41 ? 4 : f == F_Q50 ? 4 : f == F_Q51 ? 5 : 3;
 }
 __host__ __device__ constexpr int fmt_of_dev_type(int t) {
   return t == kDevQ4K_T16 ? F_Q4K : t == kDevQ6K_T16 ? F_Q6K : t == kDevQ5K_T16 ? F_Q5K : t == kDevQ80_T16 ? F_Q80 : t == kDevQ40_T16 ? F_Q40
-         : t == kDevQ3K_T16 ? F_Q3K : t == kDevQ2K_T16 ? F_Q2K : -1;
+         : t == kDevQ3K_T16 ? F_Q3K : t == kDevQ2K_T16 ? F_Q2K : t == kDevQ41_T16 ? F_Q41 : t == kDevQ50_T16 ? F_Q50 : t == kDevQ51_T16 ? F_Q51 : -1;
 }
 
 
@@ -42,7 +44,8 @@ template <uint32_t MASK>
 __device__ __forceinline__ uint32_t mvq_tile_stride(int fmt) {
   auto is = [&](int f) { return mvq_is<MASK>(fmt, f); };
   return is(F_Q4K) ? fmt_tile_bytes(F_Q4K) : is(F_Q6K) ? fmt_tile_bytes(F_Q6K) : is(F_Q5K) ? fmt_tile_bytes(F_Q5K) : is(F_Q80) ? fmt_tile_bytes(F_Q80)
-         : is(F_Q3K) ? fmt_tile_bytes(F_Q3K) : is(F_Q2K) ? fmt_tile_bytes(F_Q2K) : fmt_tile_bytes(F_Q40);
+         : is(F_Q3K) ? fmt_tile_bytes(F_Q3K) : is(F_Q2K) ? fmt_tile_bytes(F_Q2K) : is(F_Q41) ? fmt_tile_bytes(F_Q41)
+         : is(F_Q50) ? fmt_tile_bytes(F_Q50) : is(F_Q51) ? fmt_tile_bytes(F_Q51) : fmt_tile_bytes(F_Q40);
 }
 
 // The two low-bit K-quants (tile layouts: matvec_mfma.hip).  r.q[0] dword pp: the lane's 16 two-bit quants of step pp, byte t = q[t] |
@@ -65,6 +68,33 @@ __device__ __forceinline__ i32x4 mvq_lowbit_operand(const RawT16& r, int pp) {
     bw.w |= (int)(((H >> 3) & 0x01010101u) << 2);
   }
   return bw;
+}
+
+// The three 32-element-block formats with an additive minimum and / or a fifth bit: Q4_1, Q5_0, Q5_1 (tile layouts: matvec_mfma.hip).
+// Nibble words r.q[0] / r.q[1] as Q4_0's; with FIFTH the fifth bits (r.q[2].x / .y, stored as Q5_K's: a dword per step pair, low nibbles =
+// even step, high nibbles = odd step, byte t = f[t] | f[t+4] << 1 | f[t+8] << 2 | f[t+12] << 3) complete B-operand dword j to q = nibble |
+// fifth << 4 (0..31).  Q5_0's "- 16" and the minima of Q4_1 / Q5_1 go through the chunk's sum of x.
+template <bool FIFTH>
+__device__ __forceinline__ i32x4 mvq_legacy_operand(const RawT16& r, int pp) {
+  const uint32_t N0 = (pp & 1) ? r.q[pp >> 1].z : r.q[pp >> 1].x, N1 = (pp & 1) ? r.q[pp >> 1].w : r.q[pp >> 1].y;
+  i32x4 bw;
+  bw.x = (int)(N0 & 0x0F0F0F0Fu);
+  bw.y = (int)((N0 >> 4) & 0x0F0F0F0Fu);
+  bw.z = (int)(N1 & 0x0F0F0F0Fu);
+  bw.w = (int)((N1 >> 4) & 0x0F0F0F0Fu);
+  if (FIFTH) {
+    const uint32_t H = ((pp >> 1) ? r.q[2].y : r.q[2].x) >> (4 * (pp & 1));
+    bw.x |= (int)((H & 0x01010101u) << 4);
+    bw.y |= (int)(((H >> 1) & 0x01010101u) << 4);
+    bw.z |= (int)(((H >> 2) & 0x01010101u) << 4);
+    bw.w |= (int)(((H >> 3) & 0x01010101u) << 4);
+  }
+  return bw;
+}
+// the f16 of block 2pp + (c >> 1) out of a row's eight (one dword per step: blocks 2pp, 2pp + 1)
+__device__ __forceinline__ float mvq_block_f16(const u32x4& h, int pp, uint32_t c) {
+  const uint32_t w = pp == 0 ? h.x : pp == 1 ? h.y : pp == 2 ? h.z : h.w;
+  return h2f((c >> 1) ? w >> 16 : w & 0xFFFFu);
 }
 
 // fmt_loads_per_tile(format) non-temporal loads of this lane's share of the tile at `tile` (lane roles: row n = lane & 15)
@@ -92,6 +122,16 @@ __device__ __forceinline__ void mvq_issue_tile(int fmt, const uint8_t* tile, uin
       r.q[0] = ldg_nt128(tile + lane * 16);
       r.hd.x = ldg_nt32(tile + 1024 + lane * 4);
       r.hd.y = ldg_nt32(tile + 1280 + n * 4);
+    } else if (is(F_Q41) || is(F_Q50) || is(F_Q51)) {   // the row's eight d, two nibble loads, then the row's eight m and / or the fifth bits
+      r.hd = ldg_nt128(tile + 2048 + n * 16);
+      r.q[0] = ldg_nt128(tile + lane * 16);
+      r.q[1] = ldg_nt128(tile + 1024 + lane * 16);
+      if (!is(F_Q50)) r.q[3] = ldg_nt128(tile + 2304 + n * 16);
+      if (!is(F_Q41)) {
+        const u32x2 h = ldg_nt64(tile + (is(F_Q50) ? 2304 : 2560) + lane * 8);
+        r.q[2].x = h.x;
+        r.q[2].y = h.y;
+      }
     } else {   // Q4_K, Q5_K, Q4_0: header + two nibble loads (+ the fifth bits)
       r.hd = ldg_nt128(tile + 2048 + n * 16);
       r.q[0] = ldg_nt128(tile + lane * 16);
@@ -200,6 +240,28 @@ __device__ __forceinline__ void mvq_consume_tile(int fmt, const RawT16& r, const
       }
       const float dd = h2f(r.hd.y & 0xFFFFu), dmin = h2f(r.hd.y >> 16);
       acc += dd * s1 - dmin * s2;
+    } else if (is(F_Q41) || is(F_Q50) || is(F_Q51)) {
+      // 32-element blocks: chunk 4pp + c lies in block 2pp + (c >> 1) of the row's eight, whose f16 d (and m) it takes.
+      // Q5_0: y = d * (q - 16) (dequant.rs:54-76), the Q4_0 shape; Q4_1 / Q5_1: y = d * q + m (dequant.rs:36-48, 81-101), the Q4_K shape
+      // with a plus sign.  q <= 31: |D0| <= 64*31*16, |D1..3| <= 128*31*16 as for Q5_K, so both halves of V are exact in f32.
+      float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+      for (int pp = 0; pp < 4; pp++) {
+        const i32x4 bw = is(F_Q41) ? mvq_legacy_operand<false>(r, pp) : mvq_legacy_operand<true>(r, pp);
+        const i32x4 zero = {0, 0, 0, 0};
+        const i32x4 d = __builtin_amdgcn_mfma_i32_16x16x64_i8(areg[pp], bw, zero, 0, 0, 0);
+        const float hi = (float)((d.x << 8) + d.y), lo = (float)((d.z << 8) + d.w);
+        const float V = __builtin_fmaf(hi, 65536.0f, lo);
+        const float dd = mvq_block_f16(r.hd, pp, c);
+        if (is(F_Q50)) {
+          s1 = __builtin_fmaf(dd, __builtin_fmaf(sx[pp], V, -16.0f * xs[pp]), s1);
+        } else {
+          s1 = __builtin_fmaf(dd * sx[pp], V, s1);
+          s2 = __builtin_fmaf(mvq_block_f16(r.q[3], pp, c), xs[pp], s2);
+        }
+      }
+      if (is(F_Q50)) acc += s1;
+      else acc += s1 + s2;
     } else {
       // Q4_K / Q5_K: 6-bit scales / mins of sub-blocks h, h+2, h+4, h+6 of row n, h = c >> 1 (packing: dequant.rs:210-223);
       // chunk 4pp + c lies in sub-block 2pp + h
@@ -266,8 +328,8 @@ __device__ __forceinline__ void xq_load_ops(const uint8_t* rec, uint32_t lane, X
 
 struct TileOps {
   i32x4 bw[4];      // B operand of step pp
-  float f[4];       // per step: Q4_K/Q5_K sub-block scale, Q6_K / Q3_K int8 scale, Q8_0/Q4_0 block d, Q2_K chunk scale
-  float g[4];       // Q4_K/Q5_K: sub-block min; Q2_K: chunk min
+  float f[4];       // per step: Q4_K/Q5_K sub-block scale, Q6_K / Q3_K int8 scale, Q8_0/Q4_0/Q4_1/Q5_0/Q5_1 block d, Q2_K chunk scale
+  float g[4];       // Q4_K/Q5_K: sub-block min; Q2_K: chunk min; Q4_1/Q5_1: block m
   float dd, dmin;   // Q4_K/Q5_K/Q2_K: d, dmin; Q6_K/Q3_K: d
 };
 
@@ -328,6 +390,14 @@ __device__ __forceinline__ void mvq_unpack_tile(int fmt, const RawT16& r, uint32
     }
     t.dd = h2f(r.hd.y & 0xFFFFu);
     t.dmin = h2f(r.hd.y >> 16);
+  } else if (is(F_Q41) || is(F_Q50) || is(F_Q51)) {
+#pragma unroll
+    for (int pp = 0; pp < 4; pp++) {
+      t.bw[pp] = is(F_Q41) ? mvq_legacy_operand<false>(r, pp) : mvq_legacy_operand<true>(r, pp);
+      t.f[pp] = mvq_block_f16(r.hd, pp, c);
+      t.g[pp] = is(F_Q50) ? 0.0f : mvq_block_f16(r.q[3], pp, c);
+    }
+    t.dd = t.dmin = 0.0f;
   } else {
     const uint32_t s8 = (c >> 1) * 8;
     const uint32_t a = (r.hd.y >> s8) & 0x00FF00FFu, bq = (r.hd.z >> s8) & 0x00FF00FFu, cq = (r.hd.w >> s8) & 0x00FF00FFu;
@@ -403,6 +473,19 @@ __device__ __forceinline__ void mvq_mac_finish(int fmt, const TileOps& t, const 
     for (int pp = 0; pp < 4; pp++)
       s1 = __builtin_fmaf(t.f[pp], is(F_Q40) ? __builtin_fmaf(o.sx[pp], V[pp], -8.0f * o.xs[pp]) : o.sx[pp] * V[pp], s1);
     acc += s1;
+  } else if (is(F_Q50)) {
+    float s1 = 0.0f;
+#pragma unroll
+    for (int pp = 0; pp < 4; pp++) s1 = __builtin_fmaf(t.f[pp], __builtin_fmaf(o.sx[pp], V[pp], -16.0f * o.xs[pp]), s1);
+    acc += s1;
+  } else if (is(F_Q41) || is(F_Q51)) {
+    float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+    for (int pp = 0; pp < 4; pp++) {
+      s1 = __builtin_fmaf(t.f[pp] * o.sx[pp], V[pp], s1);
+      s2 = __builtin_fmaf(t.g[pp], o.xs[pp], s2);
+    }
+    acc += s1 + s2;
   } else {   // Q4_K, Q5_K, Q2_K
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll

@@ -44,14 +44,16 @@ typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 
 // formats as in matvec_mfma.hip (same tile16 layouts)
 // ... and the two 16-bit layouts of matvec_h16.hip (contexts with LGH_WEIGHTS_HALF_TILES): pf_body_half
-enum : int { PF_Q4K = 0, PF_Q6K = 1, PF_Q5K = 2, PF_Q80 = 3, PF_Q40 = 4, PF_Q3K = 5, PF_Q2K = 6, PF_F16 = 7, PF_BF16 = 8 };
+// ... and Q4_1 / Q5_0 / Q5_1 (contexts with LGH_WEIGHTS_LEGACY_TILES)
+enum : int { PF_Q4K = 0, PF_Q6K = 1, PF_Q5K = 2, PF_Q80 = 3, PF_Q40 = 4, PF_Q3K = 5, PF_Q2K = 6, PF_F16 = 7, PF_BF16 = 8, PF_Q41 = 9, PF_Q50 = 10, PF_Q51 = 11 };
 __host__ __device__ constexpr uint32_t pf_tile_bytes(int f) {
-  return f >= PF_F16 ? 8192u : f == PF_Q4K ? 2304u : f == PF_Q6K ? 3392u : f == PF_Q5K ? 2816u : f == PF_Q80 ? 4352u : f == PF_Q3K ? 1824u : f == PF_Q2K ? 1344u : 2304u;
+  return f == PF_Q41 ? 2560u : f == PF_Q50 ? 2816u : f == PF_Q51 ? 3072u : f >= PF_F16 ? 8192u : f == PF_Q4K ? 2304u : f == PF_Q6K ? 3392u : f == PF_Q5K ? 2816u : f == PF_Q80 ? 4352u : f == PF_Q3K ? 1824u : f == PF_Q2K ? 1344u : 2304u;
 }
 static int pf_fmt_of(int dev_type) {
   return dev_type == kDevQ4K_T16 ? PF_Q4K : dev_type == kDevQ6K_T16 ? PF_Q6K : dev_type == kDevQ5K_T16 ? PF_Q5K
          : dev_type == kDevQ80_T16 ? PF_Q80 : dev_type == kDevQ40_T16 ? PF_Q40 : dev_type == kDevQ3K_T16 ? PF_Q3K
-         : dev_type == kDevQ2K_T16 ? PF_Q2K : dev_type == kDevF16_T16 ? PF_F16 : dev_type == kDevBF16_T16 ? PF_BF16 : -1;
+         : dev_type == kDevQ2K_T16 ? PF_Q2K : dev_type == kDevF16_T16 ? PF_F16 : dev_type == kDevBF16_T16 ? PF_BF16
+         : dev_type == kDevQ41_T16 ? PF_Q41 : dev_type == kDevQ50_T16 ? PF_Q50 : dev_type == kDevQ51_T16 ? PF_Q51 : -1;
 }
 
 // waves per workgroup: 4 (one per SIMD, 4 row tiles each).  8 waves of 2 tiles (-DPF_WAVES=8: two per SIMD, twice the LDS
@@ -114,6 +116,16 @@ __device__ __forceinline__ void pf_load(PfRaw& r, const uint8_t* tile, uint32_t 
     r.q[0] = ldg_nt128(tile + lane * 16);
     r.hd.x = ldg_nt32(tile + 1024 + lane * 4);
     r.hd.y = ldg_nt32(tile + 1280 + n * 4);
+  } else if (F == PF_Q41 || F == PF_Q50 || F == PF_Q51) {   // the row's eight d, two nibble loads, the row's eight m and / or the fifth bits
+    r.hd = ldg_nt128(tile + 2048 + n * 16);
+    r.q[0] = ldg_nt128(tile + lane * 16);
+    r.q[1] = ldg_nt128(tile + 1024 + lane * 16);
+    if (F != PF_Q50) r.q[3] = ldg_nt128(tile + 2304 + n * 16);
+    if (F != PF_Q41) {
+      const u32x2 h = ldg_nt64(tile + (F == PF_Q50 ? 2304 : 2560) + lane * 8);
+      r.q[2].x = h.x;
+      r.q[2].y = h.y;
+    }
   } else {
     r.hd = ldg_nt128(tile + 2048 + n * 16);
     r.q[0] = ldg_nt128(tile + lane * 16);
@@ -147,6 +159,15 @@ __device__ __forceinline__ void pf_scale(const PfRaw& r, int pp, uint32_t n, uin
     const float dd = h2f((c >> 1) ? hdw >> 16 : hdw & 0xFFFFu);
     S = pf_bcast(dd * kPfScale);
     O = S * pf_bcast(F == PF_Q80 ? -128.0f : -8.0f);
+  } else if (F == PF_Q41 || F == PF_Q50 || F == PF_Q51) {   // y = d * (q - 16) (Q5_0) / d * q + m (Q4_1, Q5_1), d and m of block 2pp + (c >> 1)
+    const uint32_t hdw = pp == 0 ? r.hd.x : pp == 1 ? r.hd.y : pp == 2 ? r.hd.z : r.hd.w;
+    S = pf_bcast(h2f((c >> 1) ? hdw >> 16 : hdw & 0xFFFFu) * kPfScale);
+    if (F == PF_Q50) {
+      O = S * pf_bcast(-16.0f);
+    } else {
+      const uint32_t mw = pp == 0 ? r.q[3].x : pp == 1 ? r.q[3].y : pp == 2 ? r.q[3].z : r.q[3].w;
+      O = pf_bcast(h2f((c >> 1) ? mw >> 16 : mw & 0xFFFFu) * kPfScale);
+    }
   } else if (F == PF_Q3K) {   // y = d * (s6 - 32) * (q - 4), the lane's int8 scale of step pp (dequant.rs:161-200)
     const float scf = (float)(int)__builtin_amdgcn_sbfe((int)r.hd.x, 8 * pp, 8);
     const uint32_t dh = (n & 1) ? r.hd.y >> 16 : r.hd.y & 0xFFFFu;
@@ -233,13 +254,13 @@ __device__ __forceinline__ h16x8 pf_frag(const PfRaw& r, int pp, int h, h16x2 S,
   }
   const uint32_t N0 = (pp & 1) ? r.q[pp >> 1].z : r.q[pp >> 1].x, N1 = (pp & 1) ? r.q[pp >> 1].w : r.q[pp >> 1].y;
   const uint32_t N = h ? N1 : N0;
-  if (F == PF_Q4K || F == PF_Q40) return pf_frag_nib(N, S, O);
+  if (F == PF_Q4K || F == PF_Q40 || F == PF_Q41) return pf_frag_nib(N, S, O);
   uint32_t B0 = N & 0x0F0F0F0Fu, B1 = (N >> 4) & 0x0F0F0F0Fu;
   if (F == PF_Q6K) {   // H byte t = f[t] | f[t+4] << 2 | f[t+8] << 4 | f[t+12] << 6 (the two high bits of the chunk's 16 weights)
     const uint32_t H = pp == 0 ? r.q[2].x : pp == 1 ? r.q[2].y : pp == 2 ? r.q[2].z : r.q[2].w;
     B0 |= ((H >> (4 * h)) & 0x03030303u) << 4;
     B1 |= ((H >> (4 * h + 2)) & 0x03030303u) << 4;
-  } else {             // Q5_K: fifth bits, dword of the step pair, low nibbles = even step, high nibbles = odd step
+  } else {             // Q5_K, Q5_0, Q5_1: fifth bits, dword of the step pair, low nibbles = even step, high nibbles = odd step
     const uint32_t H = ((pp >> 1) ? r.q[2].y : r.q[2].x) >> (4 * (pp & 1));
     B0 |= ((H >> (2 * h)) & 0x01010101u) << 4;
     B1 |= ((H >> (2 * h + 1)) & 0x01010101u) << 4;
@@ -703,6 +724,9 @@ __device__ __forceinline__ void pf_gemm_body(const PfGemm& G, uint8_t* pf_smem) 
   else if (is(PF_Q40)) LGH_PF_RUN(PF_Q40);
   else if (is(PF_Q3K)) LGH_PF_RUN(PF_Q3K);
   else if (is(PF_Q2K)) LGH_PF_RUN(PF_Q2K);
+  else if (is(PF_Q41)) LGH_PF_RUN(PF_Q41);
+  else if (is(PF_Q50)) LGH_PF_RUN(PF_Q50);
+  else if (is(PF_Q51)) LGH_PF_RUN(PF_Q51);
 #undef LGH_PF_RUN
 #define LGH_PF_RUN_HALF(B)                                                               \
   do {                                                                                   \
@@ -727,6 +751,14 @@ __global__ void __launch_bounds__(kPfWaves * 64) LGH_NO_PK_F32 pf_gemm_lowbit_ke
   extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
   pf_gemm_body<MASK>(G, pf_smem);
 }
+// Q4_1, Q5_0, Q5_1 (contexts with LGH_WEIGHTS_LEGACY_TILES): single-format instantiations under a name of their own
+constexpr uint32_t kPfLegacyMask = (1u << PF_Q41) | (1u << PF_Q50) | (1u << PF_Q51);
+template <uint32_t MASK>
+__global__ void __launch_bounds__(kPfWaves * 64) pf_gemm_legacy_kernel(const PfGemm G) {
+  static_assert((MASK & ~kPfLegacyMask) == 0 && (MASK & (MASK - 1)) == 0, "one of the three formats: a mix goes out as one launch per matrix");
+  extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
+  pf_gemm_body<MASK>(G, pf_smem);
+}
 // the instantiations over 16-bit tiles (pf_body_half): F16, BF16, and both (a launch whose matrices differ in type)
 constexpr uint32_t kPfHalfMask = (1u << PF_F16) | (1u << PF_BF16);
 template <uint32_t MASK>
@@ -738,6 +770,7 @@ __global__ void __launch_bounds__(kPfWaves * 64) pf_gemm_half_kernel(const PfGem
 template <uint32_t MASK>
 static auto pf_gemm_kernel_of() {
   if constexpr ((MASK & kPfHalfMask) != 0) return &pf_gemm_half_kernel<MASK>;
+  else if constexpr ((MASK & kPfLegacyMask) != 0) return &pf_gemm_legacy_kernel<MASK>;
   else if constexpr ((MASK & kPfLowbitMask) != 0) return &pf_gemm_lowbit_kernel<MASK>;
   else return &pf_gemm_kernel<MASK>;
 }
@@ -790,7 +823,10 @@ static hipError_t pf_gemm_dispatch(const PfGemm& G, uint32_t rg, uint32_t mask, 
     case 1u << PF_F16: return pf_gemm_go<1u << PF_F16>(G, rg, st);
     case 1u << PF_BF16: return pf_gemm_go<1u << PF_BF16>(G, rg, st);
     case kPfHalfMask: return pf_gemm_go<kPfHalfMask>(G, rg, st);
-    default: return mask & ~31u ? pf_gemm_go<127u>(G, rg, st) : pf_gemm_go<31u>(G, rg, st);   // any other mix: of the first five formats, of all
+    case 1u << PF_Q41: return pf_gemm_go<1u << PF_Q41>(G, rg, st);
+    case 1u << PF_Q50: return pf_gemm_go<1u << PF_Q50>(G, rg, st);
+    case 1u << PF_Q51: return pf_gemm_go<1u << PF_Q51>(G, rg, st);
+    default: return mask & ~127u ? hipErrorInvalidValue : mask & ~31u ? pf_gemm_go<127u>(G, rg, st) : pf_gemm_go<31u>(G, rg, st);   // any other mix: of the first five formats, of all
   }
 }
 
@@ -831,21 +867,26 @@ hipError_t pf_gemm_launch(const DevWeight* const* W, int nw, const uint8_t* xh, 
   if (part_rows < (uint32_t)kPfTokens || (size_t)G.S * part_rows * col * 4 > part_bytes) return hipErrorInvalidValue;
   *S_out = G.S;
   *ncols_out = col;
-  if (!(mask & kPfHalfMask) || !(mask & ~kPfHalfMask)) return pf_gemm_dispatch(G, rg, mask, st);
-  // 16-bit and int8-tile matrices side by side (a file that keeps some projections unquantized): one launch per family over its own
-  // matrices, as mv_formats_split does for decode.  Columns, splits and the partial-sum buffer stay the whole GEMM's.
-  for (int half = 0; half < 2; half++) {
+  // family of a format: the int8 tiles that have mixed instantiations 0, the 16-bit tiles 1, Q4_1 / Q5_0 / Q5_1 one each
+  auto family = [](int f) { return (kPfHalfMask >> f) & 1u ? 1 : (kPfLegacyMask >> f) & 1u ? 2 + f - PF_Q41 : 0; };
+  bool one_family = true;
+  for (int i = 1; i < nw; i++) one_family &= family(G.seg[i].fmt) == family(G.seg[0].fmt);
+  if (one_family) return pf_gemm_dispatch(G, rg, mask, st);
+  // matrices of several families side by side (a file that keeps some projections unquantized, or in a type of its own): one launch
+  // per family over its own matrices, as mv_formats_split does for decode.  Columns, splits and the partial-sum buffer stay the whole GEMM's.
+  for (int fam = 0; fam < 5; fam++) {
     PfGemm Gf = G;
     uint32_t rgf = 0, maskf = 0;
     Gf.nseg = 0;
     for (int i = 0; i < nw; i++) {
-      if ((int)((kPfHalfMask >> G.seg[i].fmt) & 1u) != half) continue;
+      if (family(G.seg[i].fmt) != fam) continue;
       PfSeg& sgf = Gf.seg[Gf.nseg++];
       sgf = G.seg[i];
       sgf.rg_begin = rgf;
       rgf += (sgf.ntiles + kPfWaves * kPfRT - 1) / (kPfWaves * kPfRT);
       maskf |= 1u << sgf.fmt;
     }
+    if (Gf.nseg == 0) continue;
     if (hipError_t e = pf_gemm_dispatch(Gf, rgf, maskf, st); e != hipSuccess) return e;
   }
   return hipSuccess;
