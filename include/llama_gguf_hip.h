@@ -245,8 +245,9 @@ int lgh_prefill_token(lgh_ctx* ctx, uint32_t token_id);
  * the tokens routed to it), causal attention over the block; the KV cache it leaves equals the token-by-token one within
  * 1e-2 relative (f16 operands, f32 accumulation).  KV caches: f32, and TurboQuantMSE (LGH_KV_TQ2 / TQ3), whose rows are compressed as
  * write_kv does and attended through their codes, the block's own rows included.  The byte caches (LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2)
- * take it on a context that asked for it with lgh_set_prefill_policy.  Everything else (the QJL caches, TurboQuant pipeline stages),
- * and any context created with LGH_FLAG_EXACT_PREFILL, runs n exact prefill_tokens. */
+ * and TurboQuantProd (LGH_KV_TQ2_QJL / TQ3_QJL), whose K rows also get their QJL words as compress writes them and whose scores carry the
+ * QJL correction, take it on a context that asked for it with lgh_set_prefill_policy.  Everything else (TurboQuant pipeline stages), and
+ * any context created with LGH_FLAG_EXACT_PREFILL, runs n exact prefill_tokens. */
 int lgh_prefill_batch(lgh_ctx* ctx, const uint32_t* tokens, size_t n);
 /* 1 when lgh_prefill_batch will take the batched GEMM path for this (finalized) context, else 0 */
 int lgh_prefill_is_batched(lgh_ctx* ctx);
@@ -259,9 +260,14 @@ int lgh_prefill_is_batched(lgh_ctx* ctx);
  *     it is not the default: without the bit a byte cache's prompt is bit-identical to the token-by-token engine's.  All other
  *     conditions of the batched path still apply, LGH_FLAG_EXACT_PREFILL still wins, and the bit does nothing on f32 and TurboQuant
  *     contexts.  lgh_prefill_is_batched reports the result.
- * TurboQuant slots and the QJL formats stay token by token whatever the word says; the lgh_tp_* and lgh_pipeline_* handles have no
- * setter. */
-enum { LGH_PREFILL_DEFAULT = 0, LGH_PREFILL_BATCH_BYTE_KV = 1u << 0 };
+ *   LGH_PREFILL_BATCH_TQ_QJL  TurboQuantProd caches (LGH_KV_TQ2_QJL / TQ3_QJL) take the batched path under the conditions of LGH_KV_TQ2 /
+ *     TQ3: the own sequence of a context that owns every layer, head_dim 64 / 128, 1 / 2 / 4 / 8 heads per kv head.  Codes and QJL words
+ *     of a block's rows are the bits compress gives the same f32 row, and every token attends to the stored rows with the QJL score
+ *     correction, the block's own rows included.  Off by default for the reason above: without the bit a QJL cache's prompt is
+ *     bit-identical to the token-by-token engine's.  LGH_FLAG_EXACT_PREFILL still wins, and the bit does nothing on any other cache type.
+ * Bit 1 is not assigned.  TurboQuant slots and stage contexts stay token by token whatever the word says; the lgh_tp_* and lgh_pipeline_*
+ * handles have no setter. */
+enum { LGH_PREFILL_DEFAULT = 0, LGH_PREFILL_BATCH_BYTE_KV = 1u << 0, LGH_PREFILL_BATCH_TQ_QJL = 1u << 2 };
 int lgh_set_prefill_policy(lgh_ctx* ctx, uint32_t policy);
 /* Which device layout lgh_upload_tensor gives a 2-D weight where it has a choice.  A call between lgh_create and the first
  * lgh_upload_tensor: every matrix of a context is laid out under one policy.  After the first upload, or with unknown bits, it answers
@@ -775,6 +781,19 @@ int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, 
 int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes,
                                 const float* signs, float* out, size_t n_heads, size_t n_kv_heads, size_t head_dim, size_t max_seq_len,
                                 float scale, size_t pos0, size_t m_tokens);
+/* lgh_op_pf_tq_store for a TurboQuantProd cache (kv_cache_type LGH_KV_TQ2_QJL / TQ3_QJL; anything else: Unsupported): + qjl_matrices
+ * [n_kv_heads][head_dim][head_dim], and k_qjl [n_kv_heads][max_seq_len][head_dim / 32 + 1] words in / out: rows pos0 .. pos0+m-1 come back
+ * as the sign bits of the projected residual and its norm (the bits of lgh_op_tq_compress_qjl), every other row as it was.  V rows get
+ * codes only. */
+int lgh_op_pf_tq_store_qjl(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv_heads,
+                           size_t head_dim, size_t max_seq_len, size_t pos0, const float* signs, const float* qjl_matrices, uint8_t* k_codes,
+                           uint8_t* v_codes, uint32_t* k_qjl);
+/* lgh_op_attention_prefill_tq for a TurboQuantProd cache (LGH_KV_TQ2_QJL / TQ3_QJL; anything else: Unsupported): the scores carry the
+ * QJL correction of the K rows' words k_qjl [n_kv_heads][max_seq_len][head_dim / 32 + 1] under qjl_matrices
+ * [n_kv_heads][head_dim][head_dim] (attn_pf_tq_qjl_kernel).  Everything else as there. */
+int lgh_op_attention_prefill_tq_qjl(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes,
+                                    const uint32_t* k_qjl, const float* signs, const float* qjl_matrices, float* out, size_t n_heads,
+                                    size_t n_kv_heads, size_t head_dim, size_t max_seq_len, float scale, size_t pos0, size_t m_tokens);
 /* QuantizedKVCache's row write (kv_quantized.rs:143-300) for a block of m <= 128 prompt rows as the batched prefill over a byte cache
  * runs it (kv8_pf_store_kernel): kv_cache_type LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2 (anything else: Unsupported); k_rows / v_rows
  * [n_kv_heads][m][head_dim] are the block's f32 rows; k_bytes / v_bytes [n_kv_heads][max_seq_len][head_dim] and, int8, k_scales /

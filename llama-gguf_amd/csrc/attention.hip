@@ -903,8 +903,126 @@ __global__ void __launch_bounds__(NW * 64) attn_pf_kv8_kernel(const float* __res
   b.merge(m_tokens, [&](uint32_t t, uint32_t dim, float o) { pf_xh_store(xh_out, b.tt * 16 + t, b.head * D + dim, o); });
 }
 
+// ------------------------------------------------------------------------------------------------
+// The block attention over a TurboQuantProd cache (tq2-qjl / tq3-qjl; attention_tq.hip says what a QJL row is): attn_pf_mfma_kernel<D, NW,
+// true> — rotated queries, the K / V centroids of the f32 scratch, the TurboQuant epilogue — with a score of 2 D contraction dims:
+//   score(t, p) = scale * ( sum_i rq_i c[p, i]  +  coeff |r_p| sum_i sigma[p, i] (S rq)_i )
+// Prologue: pq = S_kvh rq for the workgroup's 16 tokens on the matrix cores.  Output tile o (16 rows of S, D / 16 tiles over the
+// waves) is DJ steps whose B operand is the query fragment qf itself and whose A operand, lane (n, c), is S[16 o + n][c DJ + j]: plain
+// 16-byte loads of S, which every workgroup of the kv head reads from L2 (64 KB at D = 128).  The tiles meet in LDS (wave 0's slab of the
+// merge buffer, free until the stash) and lane (n, c) takes pqf[j] = pq[token n][c DJ + j] back, next to qf.
+// Per kv tile: a second accumulator takes DJ more steps, A = +1 / -1 from bit j of the lane's sign word of K row kv0 + n (D = 128: word c;
+// D = 64: word c >> 1, bits (c & 1) 16 ..), B = pqf[j]; then the rows' coeff |r| join the two, one multiply-add per cached row as the
+// int8 row scale above.  The sign word and the four norms travel with the next tile's fragments.  V is untouched: the reference never
+// reads V's QJL bits.
+// ------------------------------------------------------------------------------------------------
+struct PfQjl { const float* s; const uint32_t* kx; float coeff; };   // [kv head][D][D]; [kv head][max_seq][D / 32 + 1]; sqrt(pi / 2) / D
+
+template <int D, int NW>
+__global__ void __launch_bounds__(NW * 64) attn_pf_tq_qjl_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc,
+                                                                 uint32_t n_heads, uint32_t g_per_kv, uint32_t max_seq, float scale, uint32_t pos0,
+                                                                 uint32_t m_tokens, uint8_t* __restrict__ xh_out, const PfTqEpi tq, const PfQjl qj) {
+  using Core = AttnBlockCore<D, NW>;
+  constexpr int DJ = Core::DJ, DQ = Core::DQ;
+  constexpr uint32_t XW = D / 32 + 1;
+  Core b(g_per_kv, pos0, m_tokens);
+  const uint32_t n = b.n, c = b.c;
+  float qf[DJ], pqf[DJ];
+  b.load_q(qf, q, n_heads, m_tokens);
+  // ---- pq = S rq: this wave's output tiles into s_o[0][token][.], then the lane's fragment back
+  for (uint32_t o = b.wave; o < (uint32_t)D / 16; o += NW) {
+    const float* sp = qj.s + ((size_t)b.kvh * D + o * 16 + n) * D + c * DJ;
+    f32x4 sa[DJ / 4];
+#pragma unroll
+    for (int j = 0; j < DJ / 4; j++) sa[j] = *reinterpret_cast<const f32x4*>(sp + 4 * j);
+    f32x4 pt = (f32x4)(0.0f);   // pt[i] = pq[token n][16 o + 4c + i]
+#pragma unroll
+    for (int j = 0; j < DJ; j++) pt = __builtin_amdgcn_mfma_f32_16x16x4f32(sa[j / 4][j % 4], qf[j], pt, 0, 0, 0);
+    *reinterpret_cast<f32x4*>(&b.s_o[0][n][o * 16 + 4 * c]) = pt;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < DJ; j += 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(&b.s_o[0][n][c * DJ + j]);
+    pqf[j] = v.x; pqf[j + 1] = v.y; pqf[j + 2] = v.z; pqf[j + 3] = v.w;
+  }
+  __syncthreads();   // (wave 0 stashes into the same slab)
+  const float* kbase = kc + (size_t)b.kvh * max_seq * D;
+  const float* vbase = vc + (size_t)b.kvh * max_seq * D;
+  const uint32_t* xbase = qj.kx + (size_t)b.kvh * max_seq * XW;
+  float m_run = kNegBig, l_run = 0.0f;
+  f32x4 acc[DQ];   // acc[x][i] = O^T[dim DQ (4c + i) + x][token n] of this wave's tiles
+#pragma unroll
+  for (int x = 0; x < DQ; x++) acc[x] = (f32x4)(0.0f);
+  // A tile's K / V fragments as attn_pf_mfma_kernel's, the sign word of K row kv0 + n that covers dims [c DJ, (c+1) DJ), and |r| of rows
+  // kv0 + 4c + i (the rows of this lane's scores).  Two query fragments leave no room for that kernel's second copy of a tile (218 VGPRs
+  // there, 256 and spills here), and the score phase is twice as long: a half's next tile is requested into the SAME registers as soon
+  // as the half has been consumed — K, signs and norms behind the scores, in flight during the softmax update and the V products; V
+  // behind those, in flight during the next tile's 2 DJ score steps.
+  f32x4 kn[DJ / 4], vn[4][DQ / 4];
+  uint32_t xn;
+  float rn[4];
+  auto load_k = [&](uint32_t tile) {
+    const uint32_t kv0 = tile * 16;
+    const uint32_t kr = b.row(kv0 + n);
+    const float* kp = kbase + (size_t)kr * D + c * DJ;
+#pragma unroll
+    for (int j = 0; j < DJ / 4; j++) kn[j] = *reinterpret_cast<const f32x4*>(kp + 4 * j);
+    xn = xbase[(size_t)kr * XW + (D == 128 ? c : c >> 1)];
+#pragma unroll
+    for (int i = 0; i < 4; i++) rn[i] = __uint_as_float(xbase[(size_t)b.row(kv0 + 4 * c + i) * XW + D / 32]);
+  };
+  auto load_v = [&](uint32_t tile) {
+    const uint32_t kv0 = tile * 16;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const float* vp = vbase + (size_t)b.row(kv0 + 4 * c + i) * D + n * DQ;
+#pragma unroll
+      for (int x = 0; x < DQ / 4; x++) vn[i][x] = *reinterpret_cast<const f32x4*>(vp + 4 * x);
+    }
+  };
+  if (b.wave < b.n_tiles) { load_k(b.wave); load_v(b.wave); }
+  for (uint32_t tile = b.wave; tile < b.n_tiles; tile += NW) {
+    const bool more = tile + NW < b.n_tiles;
+    const uint32_t xf = D == 128 ? xn : xn >> ((c & 1u) * 16);   // bit j: the sign of dim c DJ + j
+    f32x4 st = (f32x4)(0.0f), st2 = (f32x4)(0.0f);
+#pragma unroll
+    for (int j = 0; j < DJ; j++) st = __builtin_amdgcn_mfma_f32_16x16x4f32(kn[j / 4][j % 4], qf[j], st, 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < DJ; j++) {
+      const float sgn = __uint_as_float(0xBF800000u ^ (((xf >> j) & 1u) << 31));   // bit ? 1.0f : -1.0f
+      st2 = __builtin_amdgcn_mfma_f32_16x16x4f32(sgn, pqf[j], st2, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) st[i] = __builtin_fmaf(qj.coeff * rn[i], st2[i], st[i]);   // coeff * key_norm (qjl.rs:120-131)
+    if (more) load_k(tile + NW);
+    float pv[4];
+    b.update(st, tile * 16, pos0, scale, m_run, l_run, acc, pv);
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int x = 0; x < DQ; x++) acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(vn[i][x / 4][x % 4], pv[i], acc[x], 0, 0, 0);
+    if (more) load_v(tile + NW);
+  }
+  b.stash(m_run, l_run, acc);
+  // the TurboQuant epilogue of attn_pf_mfma_kernel: the merged value x sqrt(d) in wave 0's place, the inverse rotation per token
+  b.merge(m_tokens, [&](uint32_t t, uint32_t dim, float o) { b.s_o[0][t][dim] = o * tq.inv_scale; });
+  __syncthreads();
+  const float* sv = tq.signs + (size_t)(b.kvh * 2 + 1) * D;
+  const uint32_t lane = b.lane;
+  for (uint32_t t = b.wave; t < 16u; t += NW) {
+    if (b.tt * 16 + t >= m_tokens) continue;   // wave-uniform
+    float x0 = b.s_o[0][t][lane], x1 = 0.0f;
+    if (D == 128) x1 = b.s_o[0][t][lane + 64];
+    tq_fwht_wave<D>(x0, x1, lane);
+    pf_xh_store(xh_out, b.tt * 16 + t, b.head * D + lane, x0 * tq.inv_d * sv[lane]);
+    if (D == 128) pf_xh_store(xh_out, b.tt * 16 + t, b.head * D + lane + 64, x1 * tq.inv_d * sv[lane + 64]);
+  }
+}
+
 // ---- host: the block attention's one launch (common.h: AttnBlock) ----
 void tq_inverse_factors(uint32_t head_dim, float* inv_scale, float* inv_d);   // attention_tq.hip
+float tq_qjl_coeff(uint32_t head_dim);
 
 // the LDS opt-in and the grid of whichever kernel was picked: n_heads x token tiles of NW waves
 template <auto Kernel, int D, int NW, typename... Args>
@@ -916,11 +1034,11 @@ static hipError_t attn_block_go(const AttnBlock& a, Args... args) {
   return hipGetLastError();
 }
 
-// (The formats in this order, f32's VALU fallback between f32 and TurboQuant, head_dim 128 before 64: kernels are emitted in the order
+// (The formats in this order, f32's VALU fallback between f32 and TurboQuant, the QJL formats last, head_dim 128 before 64: kernels are emitted in the order
 // of their first use, and the code object keeps the kernel order it was measured with — the launch-description note under profiles/)
 hipError_t attn_block_launch(const KvLayout& l, const KvCache& kv, const AttnBlock& a) {
-  if (l.type > LGH_KV_TQ3_QJL || l.n_kv == 0 || a.n_heads % l.n_kv || a.m_tokens == 0 || (uint64_t)a.pos0 + a.m_tokens > l.max_seq || l.qjl() ||
-      (l.tq() && (!a.signs || !a.tq_kv)))
+  if (l.type > LGH_KV_TQ3_QJL || l.n_kv == 0 || a.n_heads % l.n_kv || a.m_tokens == 0 || (uint64_t)a.pos0 + a.m_tokens > l.max_seq ||
+      (l.tq() && (!a.signs || !a.tq_kv)) || (l.qjl() && (!a.qjl_s || !kv.kx())))
     return hipErrorInvalidValue;
   constexpr int NW = 8;   // (4 waves: 11.7 us per layer of a 128-token Llama-3-8B prompt, the last token tile's waves take two kv tiles each)
   const uint32_t g = a.n_heads / l.n_kv;
@@ -944,7 +1062,7 @@ hipError_t attn_block_launch(const KvLayout& l, const KvCache& kv, const AttnBlo
     });
   }
   if (!mfma_shape) return hipErrorInvalidValue;
-  if (l.tq())   // over the prompt pass's scratch (tq_pf_rows_launch filled it and rotated q)
+  if (l.tq() && !l.qjl())   // over the prompt pass's scratch (tq_pf_rows_launch filled it and rotated q)
     return by_head_dim([&](auto d) {
       constexpr int D = decltype(d)::value;
       PfTqEpi tq{a.signs, 0.0f, 0.0f};
@@ -952,15 +1070,24 @@ hipError_t attn_block_launch(const KvLayout& l, const KvCache& kv, const AttnBlo
       return attn_block_go<&attn_pf_mfma_kernel<D, NW, true>, D, NW>(a, a.q, a.tq_kv, a.tq_kv + l.stride_floats(), a.n_heads, g, l.max_seq, a.scale, a.pos0,
                                                                      a.m_tokens, a.xh_out, tq);
     });
+  if (!l.tq())
+    return by_head_dim([&](auto d) {
+      constexpr int D = decltype(d)::value;
+      auto go = [&](auto fmt) {
+        return attn_block_go<&attn_pf_kv8_kernel<D, NW, decltype(fmt)::value>, D, NW>(a, a.q, kv.k_bytes(), kv.v_bytes(), kv.kscale(), kv.vscale(), a.n_heads, g,
+                                                                                      l.max_seq, a.scale, a.pos0, a.m_tokens, a.xh_out);
+      };
+      return l.type == LGH_KV_INT8       ? go(std::integral_constant<int, 1>{})
+             : l.type == LGH_KV_FP8_E4M3 ? go(std::integral_constant<int, 2>{})
+                                         : go(std::integral_constant<int, 3>{});
+    });
+  // TurboQuantProd: the same scratch and rotated q, with the cache's QJL rows and the layer's projection
   return by_head_dim([&](auto d) {
     constexpr int D = decltype(d)::value;
-    auto go = [&](auto fmt) {
-      return attn_block_go<&attn_pf_kv8_kernel<D, NW, decltype(fmt)::value>, D, NW>(a, a.q, kv.k_bytes(), kv.v_bytes(), kv.kscale(), kv.vscale(), a.n_heads, g,
-                                                                                    l.max_seq, a.scale, a.pos0, a.m_tokens, a.xh_out);
-    };
-    return l.type == LGH_KV_INT8       ? go(std::integral_constant<int, 1>{})
-           : l.type == LGH_KV_FP8_E4M3 ? go(std::integral_constant<int, 2>{})
-                                       : go(std::integral_constant<int, 3>{});
+    PfTqEpi tq{a.signs, 0.0f, 0.0f};
+    tq_inverse_factors(D, &tq.inv_scale, &tq.inv_d);
+    return attn_block_go<&attn_pf_tq_qjl_kernel<D, NW>, D, NW>(a, a.q, a.tq_kv, a.tq_kv + l.stride_floats(), a.n_heads, g, l.max_seq, a.scale, a.pos0,
+                                                               a.m_tokens, a.xh_out, tq, PfQjl{a.qjl_s, kv.kx(), tq_qjl_coeff(D)});
   });
 }
 

@@ -473,6 +473,106 @@ __global__ void __launch_bounds__(256) tq_pf_rows_kernel(float* __restrict__ ksc
 }
 
 // ------------------------------------------------------------------------------------------------
+// The same launch for a TurboQuantProd cache (tq2-qjl / tq3-qjl): tq_pf_rows_kernel's three kinds of row work, unchanged, and for
+// every stored K row its QJL words at kx row pos0 + t: the sign bits of S res and |res|, res = the rotated row - its centroids
+// (QjlProjector::compress, qjl.rs:36-62).  V rows get codes only.  The words are tq_compress_kernel's bit for bit: output bit i of
+// a row is one thread's `dot += s_ij * res[j]` in index order, unfused, and the norm one thread's sequential sum of squares
+// (qjl.rs:180-182) — the work is spread over (row, output bit), never inside a sum.  A workgroup's 4 waves leave the residuals of
+// their rows in LDS; then its 256 threads take the 4 x D (row, bit) pairs, a wave 64 consecutive bits of one row, whose ballot is
+// two of the row's words.  S is read from L2 once per row: 64 KB at D = 128, 0.5 MB per layer of an 8-kv-head model.
+// ------------------------------------------------------------------------------------------------
+template <int D, int BITS>
+__global__ void __launch_bounds__(256) tq_pf_rows_qjl_kernel(float* __restrict__ kscr, float* __restrict__ vscr, uint8_t* __restrict__ kq,
+                                                             uint8_t* __restrict__ vq, float* __restrict__ q, const float* __restrict__ signs,
+                                                             const TqTables T, uint32_t n_kv, uint32_t g_per_kv, uint32_t max_seq, uint32_t pos0,
+                                                             uint32_t m_store, uint32_t m_q, uint32_t n_expand, const float* __restrict__ qjl_s,
+                                                             uint32_t* __restrict__ kx) {
+  constexpr uint32_t RB = tq_row_bytes<BITS>(D);
+  constexpr uint32_t XW = D / 32 + 1;   // words of a QJL row
+  constexpr uint32_t kNone = 0xFFFFFFFFu;
+  __shared__ float s_y[4][D];
+  __shared__ float s_res[4][D];
+  __shared__ __attribute__((aligned(4))) uint8_t s_code[4][64];
+  __shared__ uint32_t s_xrow[4], s_xkvh[4];   // a wave's stored K row: its row index in kx ([kv head][max_seq]) and its kv head; kNone: none
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t n_store = n_kv * 2 * m_store, n_query = m_q * n_kv * g_per_kv, n_exp = n_kv * 2 * n_expand;
+  const uint32_t job = blockIdx.x * 4 + wave;
+  const int kind = job < n_store ? 0 : job < n_store + n_query ? 1 : job < n_store + n_query + n_exp ? 2 : 3;   // wave-uniform
+  float* row = nullptr;        // the f32 row this wave works on
+  uint8_t* crow = nullptr;     // its code row
+  const float* sg = nullptr;
+  uint32_t xrow = kNone, xkvh = 0;
+  if (kind == 0 || kind == 2) {
+    const uint32_t j = kind == 0 ? job : job - n_store - n_query, per = kind == 0 ? m_store : n_expand;
+    const uint32_t kvh = j / (2 * per), kv = (j / per) & 1u, r = (kind == 0 ? pos0 : 0u) + j % per;
+    const size_t ri = (size_t)kvh * max_seq + r;
+    row = (kv ? vscr : kscr) + ri * D;
+    crow = (kv ? vq : kq) + ri * RB;
+    sg = signs + (size_t)(kvh * 2 + kv) * D;
+    if (kind == 0 && kv == 0) { xrow = (uint32_t)ri; xkvh = kvh; }   // (n_kv * max_seq rows: the launch checks that they fit 32 bits)
+  } else if (kind == 1) {
+    const uint32_t j = job - n_store;                       // (token, head)
+    row = q + (size_t)j * D;
+    sg = signs + (size_t)((j % (n_kv * g_per_kv)) / g_per_kv * 2) * D;
+  }
+  if (lane == 0) { s_xrow[wave] = xrow; s_xkvh[wave] = xkvh; }
+  if (kind <= 1) {
+    float x0 = row[lane] * sg[lane], x1 = 0.0f;
+    if (D == 128) x1 = row[lane + 64] * sg[lane + 64];
+    tq_fwht_wave<D>(x0, x1, lane);
+    x0 *= T.norm;
+    x1 *= T.norm;
+    if (kind == 1) {
+      row[lane] = x0;
+      if (D == 128) row[lane + 64] = x1;
+    } else {
+      const float c0 = tq_centroid<BITS>(T, tq_quantize<BITS>(T, x0)), c1 = tq_centroid<BITS>(T, tq_quantize<BITS>(T, x1));
+      s_y[wave][lane] = x0;
+      s_res[wave][lane] = x0 - c0;   // quant.rs:85-89: the row minus its dequantized codes
+      row[lane] = c0;
+      if (D == 128) { s_y[wave][lane + 64] = x1; s_res[wave][lane + 64] = x1 - c1; row[lane + 64] = c1; }
+    }
+  }
+  __syncthreads();
+  if (kind == 0) tq_pack_row<D, BITS>(T, s_y[wave], s_code[wave], lane);
+  __syncthreads();
+  if (kind == 0 && lane < RB / 4) reinterpret_cast<uint32_t*>(crow)[lane] = reinterpret_cast<const uint32_t*>(s_code[wave])[lane];
+  if (kind == 2) {
+    row[lane] = tq_centroid<BITS>(T, tq_index<BITS>(crow, lane));
+    if (D == 128) row[lane + 64] = tq_centroid<BITS>(T, tq_index<BITS>(crow, lane + 64));
+  }
+  // ---- QJL words of the workgroup's stored K rows: pair e = (row r of the 4, output bit i); a wave's 64 pairs share r
+  for (uint32_t e = threadIdx.x; e < 4u * D; e += 256) {
+    const uint32_t r = e / D, i = e % D;
+    if (s_xrow[r] == kNone) continue;   // wave-uniform
+    const float4* srow = reinterpret_cast<const float4*>(qjl_s + ((size_t)s_xkvh[r] * D + i) * D);
+    const float* res = s_res[r];
+    float dot = 0.0f;
+#pragma unroll 8
+    for (uint32_t j4 = 0; j4 < (uint32_t)D / 4; j4++) {   // tq_qjl_rows' loop: the reference's order, unfused
+      const float4 s4 = srow[j4];
+      dot += s4.x * res[4 * j4];
+      dot += s4.y * res[4 * j4 + 1];
+      dot += s4.z * res[4 * j4 + 2];
+      dot += s4.w * res[4 * j4 + 3];
+    }
+    const unsigned long long bl = __ballot(dot >= 0.0f);   // bit (i % 64) of word i / 64 (qjl.rs:58-60)
+    if (lane == 0) {
+      uint32_t* xr = kx + (size_t)s_xrow[r] * XW + (i >> 6) * 2;
+      xr[0] = (uint32_t)bl;
+      xr[1] = (uint32_t)(bl >> 32);
+    }
+  }
+  if (lane == 63 && s_xrow[wave] != kNone) {   // l2_norm (qjl.rs:180-182): sequential sum of squares, one thread per row
+    const float* res = s_res[wave];
+    float ss = 0.0f;
+#pragma unroll 16
+    for (uint32_t i = 0; i < (uint32_t)D; i++) ss += res[i] * res[i];
+    kx[(size_t)s_xrow[wave] * XW + D / 32] = __float_as_uint(sqrtf(ss));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
 static TqTables tq_tables(uint32_t d, int bits) {
@@ -558,12 +658,14 @@ hipError_t tq_compress_launch(int bits, const float* x, uint32_t dim, const floa
 
 // the TurboQuantMSE prompt pass's row work (tq_pf_rows_kernel): store m_store block rows at pos0 (kscr / vscr rows -> kq / vq codes, rows
 // -> centroids), rotate the m_q x n_heads query rows of q in place (q may be NULL with m_q 0), expand code rows 0 .. n_expand-1 into
-// the scratch.  signs: this layer's [n_kv][k, v][head_dim]
+// the scratch.  signs: this layer's [n_kv][k, v][head_dim].  TurboQuantProd: qjl_s, this layer's [n_kv][head_dim][head_dim] projection, and kx,
+// the cache's QJL rows [n_kv][max_seq][head_dim / 32 + 1], both or neither: the stored K rows' words as well (tq_pf_rows_qjl_kernel)
 hipError_t tq_pf_rows_launch(int bits, float* kscr, float* vscr, uint8_t* kq, uint8_t* vq, float* q, const float* signs, uint32_t n_heads,
                              uint32_t n_kv, uint32_t head_dim, uint32_t max_seq, uint32_t pos0, uint32_t m_store, uint32_t m_q, uint32_t n_expand,
-                             hipStream_t st) {
+                             hipStream_t st, const float* qjl_s, uint32_t* kx) {
   if ((bits != 2 && bits != 3) || (head_dim != 64 && head_dim != 128) || n_kv == 0 || n_heads % n_kv || (m_q && !q) ||
-      (uint64_t)pos0 + m_store > max_seq || n_expand > max_seq)
+      (uint64_t)pos0 + m_store > max_seq || n_expand > max_seq || (qjl_s != nullptr) != (kx != nullptr) ||
+      (kx && (uint64_t)n_kv * max_seq >= 0xFFFFFFFFull))
     return hipErrorInvalidValue;
   const uint64_t jobs = (uint64_t)n_kv * 2 * m_store + (uint64_t)m_q * n_heads + (uint64_t)n_kv * 2 * n_expand;
   if (jobs == 0) return hipSuccess;
@@ -573,10 +675,19 @@ hipError_t tq_pf_rows_launch(int bits, float* kscr, float* vscr, uint8_t* kq, ui
   const uint32_t g = n_heads / n_kv;
 #define LGH_TQ_PF(DD, BB) \
   hipLaunchKernelGGL((tq_pf_rows_kernel<DD, BB>), grid, dim3(256), 0, st, kscr, vscr, kq, vq, q, signs, T, n_kv, g, max_seq, pos0, m_store, m_q, n_expand)
-  if (head_dim == 128 && bits == 2) LGH_TQ_PF(128, 2);
-  else if (head_dim == 128) LGH_TQ_PF(128, 3);
-  else if (bits == 2) LGH_TQ_PF(64, 2);
-  else LGH_TQ_PF(64, 3);
+#define LGH_TQ_PF_QJL(DD, BB)                                                                                                                  \
+  hipLaunchKernelGGL((tq_pf_rows_qjl_kernel<DD, BB>), grid, dim3(256), 0, st, kscr, vscr, kq, vq, q, signs, T, n_kv, g, max_seq, pos0, m_store, m_q, \
+                     n_expand, qjl_s, kx)
+  if (!kx) {
+    if (head_dim == 128 && bits == 2) LGH_TQ_PF(128, 2);
+    else if (head_dim == 128) LGH_TQ_PF(128, 3);
+    else if (bits == 2) LGH_TQ_PF(64, 2);
+    else LGH_TQ_PF(64, 3);
+  } else if (head_dim == 128 && bits == 2) LGH_TQ_PF_QJL(128, 2);
+  else if (head_dim == 128) LGH_TQ_PF_QJL(128, 3);
+  else if (bits == 2) LGH_TQ_PF_QJL(64, 2);
+  else LGH_TQ_PF_QJL(64, 3);
+#undef LGH_TQ_PF_QJL
 #undef LGH_TQ_PF
   return hipGetLastError();
 }
@@ -587,5 +698,7 @@ void tq_inverse_factors(uint32_t head_dim, float* inv_scale, float* inv_d) {
   *inv_scale = T.inv_scale;
   *inv_d = T.inv_d;
 }
+// ... and the QJL correction's sqrt(pi / 2) / d for its TurboQuantProd variant
+float tq_qjl_coeff(uint32_t head_dim) { return tq_tables(head_dim, 2).qjl_coeff; }
 
 }  // namespace lgh

@@ -282,7 +282,7 @@ int enqueue_token(lgh_ctx* c, int mode);   // everything one token needs, in str
 struct PfTarget { size_t pos0; int slot; };
 // slot: the target is a slot of the multi-sequence engine (TurboQuant slots stay token by token: bit-identical to the single-sequence engine).
 // The byte caches (int8 / FP8) have the path for the own sequence, slots and stage contexts alike, on contexts that asked for it
-// (lgh_set_prefill_policy: lgh_ctx::pf_policy)
+// (lgh_set_prefill_policy: lgh_ctx::pf_policy), and so have the QJL caches for the own sequence (their own bit)
 bool pf_eligible(const lgh_ctx* c, bool slot = false);
 int pf_ensure(lgh_ctx* c);
 int prefill_block(lgh_ctx* c, const PfTarget& t, const uint32_t* tokens, uint32_t m);

@@ -19,10 +19,11 @@ bool pf_eligible(const lgh_ctx* c, bool slot) {
   // The batched path writes f32 K/V rows.  The f32 cache takes them as they are; a TurboQuantMSE cache (tq2 / tq3) takes them through an
   // f32 scratch (pf_tq_rows below), for the own sequence of a context that owns every layer.  A byte cache (int8 / FP8) takes them
   // through a scratch of the block's rows and a store launch (pf_kv8_store below), own sequence, slots and stage contexts alike, on
-  // a context that opted in (lgh_set_prefill_policy): the pass is not bit-identical to the token-by-token one.  The QJL formats, and
-  // slots of the multi-sequence engine and stage contexts with a TurboQuant cache, stay token by token.
+  // a context that opted in (lgh_set_prefill_policy): the pass is not bit-identical to the token-by-token one.  A TurboQuantProd cache
+  // (tq2-qjl / tq3-qjl) goes the TurboQuantMSE way, its K rows' QJL words stored by the same row launch, on a context that opted in with
+  // its own bit, for the same reason.  Slots of the multi-sequence engine and stage contexts with a TurboQuant cache stay token by token.
   if (c->kvl.tq()) {
-    if (d.kv_cache_type != LGH_KV_TQ2 && d.kv_cache_type != LGH_KV_TQ3) return false;
+    if (c->kvl.qjl() && !(c->pf_policy & LGH_PREFILL_BATCH_TQ_QJL)) return false;
     if (slot || !c->first || !c->last) return false;
   } else if (c->kvl.staged() && !(c->pf_policy & LGH_PREFILL_BATCH_BYTE_KV)) {
     return false;
@@ -118,13 +119,15 @@ int pf_qkv_step(lgh_ctx* c, LayerW& L, float* kcache, float* vcache, uint32_t po
 
 // TurboQuantMSE cache, after pf_qkv_step has left the block's f32 K / V rows in the scratch pf.tq_kv: their codes into layer li's code
 // cache and their centroids back into the scratch (TurboQuantKVCache::write_kv); with `attend`, also the block's queries rotated in
-// place and rows 0 .. pos0-1 of the scratch filled from the cached codes, which is what the block attention reads
+// place and rows 0 .. pos0-1 of the scratch filled from the cached codes, which is what the block attention reads.  TurboQuantProd: the
+// same launch also stores the K rows' QJL words (tq_layer's qjl_s is NULL for TurboQuantMSE, and so is the cache's kx())
 static int pf_tq_rows(lgh_ctx* c, LayerW& L, uint32_t li, uint32_t pos0, uint32_t m, bool attend) {
   PfScratch& P = c->pf;
   const lgh_model_desc& d = c->d;
   float* const vscr = P.tq_kv + c->kvl.stride_floats();
-  return pf_k(c, tq_pf_rows_launch(c->kvl.tq_bits(), P.tq_kv, vscr, L.kv.k_bytes(), L.kv.v_bytes(), attend ? P.q : nullptr, tq_layer(c, li).signs, d.num_heads,
-                                   d.num_kv_heads, d.head_dim, d.max_seq_len, pos0, m, attend ? m : 0, attend ? pos0 : 0, c->stream),
+  const TqLayer t = tq_layer(c, li);
+  return pf_k(c, tq_pf_rows_launch(c->kvl.tq_bits(), P.tq_kv, vscr, L.kv.k_bytes(), L.kv.v_bytes(), attend ? P.q : nullptr, t.signs, d.num_heads,
+                                   d.num_kv_heads, d.head_dim, d.max_seq_len, pos0, m, attend ? m : 0, attend ? pos0 : 0, c->stream, t.qjl_s, L.kv.kx()),
               "TurboQuant rows");
 }
 
@@ -149,7 +152,7 @@ int pf_attn_step(lgh_ctx* c, uint32_t li, const KvCache& kv, uint32_t pos0, uint
   a.pos0 = pos0;
   a.m_tokens = m;
   a.tq_kv = P.tq_kv;
-  a.signs = c->kvl.tq() ? tq_layer(c, li).signs : nullptr;
+  if (c->kvl.tq()) { const TqLayer t = tq_layer(c, li); a.signs = t.signs; a.qjl_s = t.qjl_s; }
   a.xh_out = P.xh_attn;
   a.st = c->stream;
   return pf_k(c, attn_block_launch(c->kvl, kv, a), "attention");

@@ -770,16 +770,16 @@ static int xh_down(Tmp& t, const uint8_t* xh, size_t m, size_t k, float* out) {
 }
 
 // what the three block-attention entry points share once their cache is on the device: the block's queries dq (uploaded by the
-// caller; a TurboQuant cache: rotated by now, scr its filled scratch, signs the layer's), a zeroed XH, the launch, the XH's rows as f32.
+// caller; a TurboQuant cache: rotated by now, scr its filled scratch, signs the layer's, qjl_s its QJL projection), a zeroed XH, the launch, the XH's rows as f32.
 // refused: the status of a launch that did not start
-static int attn_block_run(Tmp& t, const KvLayout& l, const KvCache& kv, const float* dq, const float* scr, const float* signs, size_t n_heads, float scale,
-                          size_t pos0, size_t m_tokens, int refused, float* out) {
+static int attn_block_run(Tmp& t, const KvLayout& l, const KvCache& kv, const float* dq, const float* scr, const float* signs, const float* qjl_s, size_t n_heads,
+                          float scale, size_t pos0, size_t m_tokens, int refused, float* out) {
   const size_t qd = n_heads * l.d, xb = xh_bytes((uint32_t)qd);
   uint8_t* xh = (uint8_t*)up_bytes(t, nullptr, xb);
   if (!dq || !xh) return LGH_ALLOCATION_FAILED;
   hipStream_t st = t.c->stream;
   if (hipMemsetAsync(xh, 0, xb, st) != hipSuccess) return LGH_OPERATION_FAILED;
-  const AttnBlock a{(uint32_t)n_heads, scale, dq, (uint32_t)pos0, (uint32_t)m_tokens, scr, signs, xh, st};
+  const AttnBlock a{(uint32_t)n_heads, scale, dq, (uint32_t)pos0, (uint32_t)m_tokens, scr, signs, qjl_s, xh, st};
   if (attn_block_launch(l, kv, a) != hipSuccess) return refused;
   return xh_down(t, xh, m_tokens, qd, out);
 }
@@ -797,7 +797,7 @@ int lgh_op_attention_prefill(int device, const float* q, const float* k_cache, c
   KvCache kv;
   const void* const host[KV_KINDS] = {k_cache, v_cache};
   if (int rc = kv_upload(t, l, 1, host, kv)) return rc;
-  return attn_block_run(t, l, kv, t.up(q, m_tokens * qd), nullptr, nullptr, n_heads, scale, pos0, m_tokens, LGH_UNSUPPORTED, out);
+  return attn_block_run(t, l, kv, t.up(q, m_tokens * qd), nullptr, nullptr, nullptr, n_heads, scale, pos0, m_tokens, LGH_UNSUPPORTED, out);
 }
 
 // the f32 scratch of the TurboQuant prompt pass, NaN-filled: K then V, each [n_kv][max_seq][head_dim]
@@ -807,23 +807,26 @@ static float* pf_tq_scratch(Tmp& t, size_t cache) {
   return s;
 }
 
-int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv, size_t head_dim,
-                       size_t max_seq, size_t pos0, const float* signs, uint8_t* k_codes, uint8_t* v_codes) {
-  // TurboQuantKVCache::write_kv (kv_turboquant.rs:88-122) for a block of prompt rows, as the batched prefill runs it
+// TurboQuantKVCache::write_kv (kv_turboquant.rs:88-122) for a block of prompt rows, as the batched prefill runs it; a QJL layout: with the K
+// rows' QJL words under qjl_matrices.  The two entry points below have checked kv_cache_type
+static int pf_tq_store_op(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv, size_t head_dim,
+                          size_t max_seq, size_t pos0, const float* signs, const float* qjl_matrices, uint8_t* k_codes, uint8_t* v_codes,
+                          uint32_t* k_qjl) {
   Tmp t(device);
   if (t.rc) return t.rc;
-  if (kv_cache_type != LGH_KV_TQ2 && kv_cache_type != LGH_KV_TQ3) return LGH_UNSUPPORTED;
   if (head_dim != 64 && head_dim != 128) return LGH_UNSUPPORTED;
   if (!k_rows || !v_rows || !signs || !k_codes || !v_codes || n_kv == 0 || max_seq > 0x7FFFFFFFu) return LGH_INVALID_ARGUMENT;
   if (m == 0 || m > (size_t)kPfTokens || pos0 + m > max_seq || !signs_ok(signs, n_kv * 2 * head_dim)) return LGH_INVALID_ARGUMENT;
   const KvLayout l(kv_cache_type, n_kv, max_seq, head_dim);
   const size_t d = head_dim, cache = l.stride_floats();
   float* scr = pf_tq_scratch(t, cache);
+  if (l.qjl() && (!qjl_matrices || !k_qjl)) return LGH_INVALID_ARGUMENT;
   KvCache kv;
-  void* const codes[KV_KINDS] = {k_codes, v_codes};
+  void* const codes[KV_KINDS] = {k_codes, v_codes, nullptr, nullptr, k_qjl};
   if (int rc = kv_upload(t, l, 1, codes, kv)) return rc;
   float* ds = t.up(signs, n_kv * 2 * d);
-  if (!scr || !ds) return LGH_ALLOCATION_FAILED;
+  const float* dS = l.qjl() ? t.up(qjl_matrices, n_kv * d * d) : nullptr;
+  if (!scr || !ds || (l.qjl() && !dS)) return LGH_ALLOCATION_FAILED;
   hipStream_t st = t.c->stream;
   // the block's rows where the QKV epilogue leaves them: rows pos0 .. pos0+m-1 of every kv head
   for (size_t h = 0; h < n_kv; h++) {
@@ -832,9 +835,22 @@ int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, 
       return LGH_OPERATION_FAILED;
   }
   if (tq_pf_rows_launch(l.tq_bits(), scr, scr + cache, kv.k_bytes(), kv.v_bytes(), nullptr, ds, (uint32_t)n_kv, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, (uint32_t)pos0,
-                        (uint32_t)m, 0, 0, st) != hipSuccess)
+                        (uint32_t)m, 0, 0, st, dS, kv.kx()) != hipSuccess)
     return LGH_OPERATION_FAILED;
   return kv_download(t, l, 1, codes, kv);
+}
+
+int lgh_op_pf_tq_store(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv, size_t head_dim,
+                       size_t max_seq, size_t pos0, const float* signs, uint8_t* k_codes, uint8_t* v_codes) {
+  if (kv_cache_type != LGH_KV_TQ2 && kv_cache_type != LGH_KV_TQ3) return LGH_UNSUPPORTED;
+  return pf_tq_store_op(device, kv_cache_type, k_rows, v_rows, m, n_kv, head_dim, max_seq, pos0, signs, nullptr, k_codes, v_codes, nullptr);
+}
+
+int lgh_op_pf_tq_store_qjl(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv, size_t head_dim,
+                           size_t max_seq, size_t pos0, const float* signs, const float* qjl_matrices, uint8_t* k_codes, uint8_t* v_codes,
+                           uint32_t* k_qjl) {
+  if (kv_cache_type != LGH_KV_TQ2_QJL && kv_cache_type != LGH_KV_TQ3_QJL) return LGH_UNSUPPORTED;
+  return pf_tq_store_op(device, kv_cache_type, k_rows, v_rows, m, n_kv, head_dim, max_seq, pos0, signs, qjl_matrices, k_codes, v_codes, k_qjl);
 }
 
 int lgh_op_kv_prefix_copy(int device, uint32_t kv_cache_type, uint32_t n_kv, uint32_t max_seq, uint32_t head_dim, uint32_t n_layers, uint32_t n_slots,
@@ -874,12 +890,13 @@ int lgh_op_kv_prefix_copy(int device, uint32_t kv_cache_type, uint32_t n_kv, uin
   return LGH_OK;
 }
 
-int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes, const float* signs,
-                                float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq, float scale, size_t pos0, size_t m_tokens) {
-  // TurboQuantKVCache::attention_layer (kv_turboquant.rs:127-201) for a block of prompt tokens, as the batched prefill runs it
+// TurboQuantKVCache::attention_layer (kv_turboquant.rs:127-201) for a block of prompt tokens, as the batched prefill runs it; a QJL layout:
+// with the K rows' QJL words and qjl_matrices.  The two entry points below have checked kv_cache_type
+static int attention_prefill_tq_op(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes, const uint32_t* k_qjl,
+                                   const float* signs, const float* qjl_matrices, float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq,
+                                   float scale, size_t pos0, size_t m_tokens) {
   Tmp t(device);
   if (t.rc) return t.rc;
-  if (kv_cache_type != LGH_KV_TQ2 && kv_cache_type != LGH_KV_TQ3) return LGH_UNSUPPORTED;
   if (head_dim != 64 && head_dim != 128) return LGH_UNSUPPORTED;
   if (!q || !k_codes || !v_codes || !signs || !out || n_kv == 0 || n_heads % n_kv || max_seq > 0x7FFFFFFFu) return LGH_INVALID_ARGUMENT;
   const size_t g = n_heads / n_kv;
@@ -888,15 +905,32 @@ int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float*
   const size_t d = head_dim, qd = n_heads * d, cache = l.stride_floats();
   if (m_tokens == 0 || m_tokens > (size_t)kPfTokens || qd % 256 || pos0 + m_tokens > max_seq || !signs_ok(signs, n_kv * 2 * d))
     return LGH_INVALID_ARGUMENT;
+  if (l.qjl() && (!qjl_matrices || !k_qjl)) return LGH_INVALID_ARGUMENT;
   float *dq = t.up(q, m_tokens * qd), *ds = t.up(signs, n_kv * 2 * d), *scr = pf_tq_scratch(t, cache);
+  const float* dS = l.qjl() ? t.up(qjl_matrices, n_kv * d * d) : nullptr;
   KvCache kv;
-  const void* const codes[KV_KINDS] = {k_codes, v_codes};
+  const void* const codes[KV_KINDS] = {k_codes, v_codes, nullptr, nullptr, k_qjl};
   if (int rc = kv_upload(t, l, 1, codes, kv)) return rc;
-  if (!dq || !ds || !scr) return LGH_ALLOCATION_FAILED;
+  if (!dq || !ds || !scr || (l.qjl() && !dS)) return LGH_ALLOCATION_FAILED;
   if (tq_pf_rows_launch(l.tq_bits(), scr, scr + cache, kv.k_bytes(), kv.v_bytes(), dq, ds, (uint32_t)n_heads, (uint32_t)n_kv, (uint32_t)d, (uint32_t)max_seq, (uint32_t)pos0, 0,
                         (uint32_t)m_tokens, (uint32_t)(pos0 + m_tokens), t.c->stream) != hipSuccess)
     return LGH_OPERATION_FAILED;
-  return attn_block_run(t, l, kv, dq, scr, ds, n_heads, scale, pos0, m_tokens, LGH_OPERATION_FAILED, out);
+  return attn_block_run(t, l, kv, dq, scr, ds, dS, n_heads, scale, pos0, m_tokens, LGH_OPERATION_FAILED, out);
+}
+
+int lgh_op_attention_prefill_tq(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes, const float* signs,
+                                float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq, float scale, size_t pos0, size_t m_tokens) {
+  if (kv_cache_type != LGH_KV_TQ2 && kv_cache_type != LGH_KV_TQ3) return LGH_UNSUPPORTED;
+  return attention_prefill_tq_op(device, kv_cache_type, q, k_codes, v_codes, nullptr, signs, nullptr, out, n_heads, n_kv, head_dim, max_seq, scale, pos0,
+                                 m_tokens);
+}
+
+int lgh_op_attention_prefill_tq_qjl(int device, uint32_t kv_cache_type, const float* q, const uint8_t* k_codes, const uint8_t* v_codes, const uint32_t* k_qjl,
+                                    const float* signs, const float* qjl_matrices, float* out, size_t n_heads, size_t n_kv, size_t head_dim, size_t max_seq,
+                                    float scale, size_t pos0, size_t m_tokens) {
+  if (kv_cache_type != LGH_KV_TQ2_QJL && kv_cache_type != LGH_KV_TQ3_QJL) return LGH_UNSUPPORTED;
+  return attention_prefill_tq_op(device, kv_cache_type, q, k_codes, v_codes, k_qjl, signs, qjl_matrices, out, n_heads, n_kv, head_dim, max_seq, scale, pos0,
+                                 m_tokens);
 }
 
 int lgh_op_pf_kv8_store(int device, uint32_t kv_cache_type, const float* k_rows, const float* v_rows, size_t m, size_t n_kv, size_t head_dim,
@@ -940,7 +974,7 @@ int lgh_op_attention_prefill_kv8(int device, uint32_t kv_cache_type, const float
   KvCache kv;
   const void* const host[KV_KINDS] = {k_bytes, v_bytes, k_scales, v_scales};
   if (int rc = kv_upload(t, l, 1, host, kv)) return rc;
-  return attn_block_run(t, l, kv, t.up(q, m_tokens * qd), nullptr, nullptr, n_heads, scale, pos0, m_tokens, LGH_OPERATION_FAILED, out);
+  return attn_block_run(t, l, kv, t.up(q, m_tokens * qd), nullptr, nullptr, nullptr, n_heads, scale, pos0, m_tokens, LGH_OPERATION_FAILED, out);
 }
 
 // ---- device-resident weights by tensor name: CudaBackend::load_model_weights + the `b.name()` lookups of its vec_mat /

@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "lgh_op_embed", "lgh_op_qkv_forward", "lgh_op_ffn_gateup", "lgh_op_argmax", "lgh_kv_cache_layout",
     "lgh_prefix_save", "lgh_prefix_restore", "lgh_prefix_free", "lgh_prefix_get_info", "lgh_prefix_total_bytes", "lgh_prefix_export",
     "lgh_prefix_import", "lgh_op_kv_prefix_copy",
+    "lgh_op_pf_tq_store_qjl", "lgh_op_attention_prefill_tq_qjl",
 )
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
@@ -70,6 +71,7 @@ WEIGHTS_LOWBIT_TILES = 1    # lgh_set_weight_policy: Q3_K / Q2_K matrices stay q
 WEIGHTS_LEGACY_TILES = 8    # ... Q4_1 / Q5_0 / Q5_1 matrices stay quantized in HBM (tile layouts of 160 / 176 / 192 B per row and 256 elements)
 WEIGHTS_HALF_TILES = 4      # ... F16 / BF16 matrices stay 16-bit in HBM (8192-B tiles, their own decode mat-vec); bit 1 is not assigned
 PREFILL_BATCH_BYTE_KV = 1   # lgh_set_prefill_policy: int8 / FP8 caches take the batched prompt pass (own sequence, slots, stage contexts)
+PREFILL_BATCH_TQ_QJL = 4    # ... tq2-qjl / tq3-qjl caches take it (own sequence, as tq2 / tq3); bit 1 is not assigned
 FLAG_EXACT_PREFILL = 4   # forward_batch feeds tokens one by one (f32 throughout) instead of the batched f16 GEMM path
 KV_F32, KV_INT8, KV_FP8_E4M3, KV_FP8_E5M2 = 0, 1, 2, 3   # lgh_model_desc.kv_cache_type: f32, or QuantizedKVCache's formats (kv_quantized.rs; no CLI flag reaches them)
 KV_TQ2, KV_TQ3 = 4, 5   # KVCacheType::TurboQuantMSE { bits: 2 | 3 }: what `--kv-cache-type tq2 | tq3` selects (src/config.rs:808-817)
@@ -279,6 +281,8 @@ def load_library() -> C.CDLL:
         "lgh_op_attention_prefill": (C.c_int, [C.c_int, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
         "lgh_op_pf_tq_store": (C.c_int, [C.c_int, u32, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp]),
         "lgh_op_attention_prefill_tq": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
+        "lgh_op_pf_tq_store_qjl": (C.c_int, [C.c_int, u32, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp]),
+        "lgh_op_attention_prefill_tq_qjl": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
         "lgh_op_pf_kv8_store": (C.c_int, [C.c_int, u32, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp]),
         "lgh_op_attention_prefill_kv8": (C.c_int, [C.c_int, u32, vp, vp, vp, vp, vp, vp, sz, sz, sz, sz, f32, sz, sz]),
         "lgh_op_qkv_rope": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, f32, sz, sz, sz, sz, sz, sz, f32, f32, vp, vp, vp]),
@@ -434,7 +438,8 @@ class HipGpuInference:
         return bool(load_library().lgh_prefill_is_batched(self._h))
 
     def set_prefill_policy(self, policy: int) -> None:
-        """lgh_set_prefill_policy: PREFILL_BATCH_BYTE_KV lets int8 / FP8 caches take the batched prompt pass; 0 restores the default."""
+        """lgh_set_prefill_policy: PREFILL_BATCH_BYTE_KV lets int8 / FP8 caches take the batched prompt pass, PREFILL_BATCH_TQ_QJL the
+        tq2-qjl / tq3-qjl caches; 0 restores the default."""
         self._call(load_library().lgh_set_prefill_policy(self._h, policy))
 
     def set_weight_policy(self, policy: int) -> None:
@@ -1817,6 +1822,33 @@ def op_attention_prefill_tq(kv_cache_type: int, q, k_codes, v_codes, signs, scal
     out = np.empty((m, nh * d), dtype=np.float32)
     _chk(load_library().lgh_op_attention_prefill_tq(device, kv_cache_type, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, sg.ctypes.data,
                                                     out.ctypes.data, nh, kc.shape[0], d, kc.shape[1], scale, pos0, m), "attention_prefill_tq")
+    return out
+
+
+def op_pf_tq_store_qjl(kv_cache_type: int, k_rows, v_rows, pos0: int, signs, qjl_matrices, k_codes, v_codes, k_qjl, device: int = 0):
+    """op_pf_tq_store for KV_TQ2_QJL / KV_TQ3_QJL: + qjl_matrices [nkv, d, d] and the K rows' QJL words k_qjl [nkv, max_seq, d / 32 + 1]
+    uint32.  -> (k_codes, v_codes, k_qjl) after the call (copies)."""
+    kr, vr, sg, S = _f32(k_rows), _f32(v_rows), _f32(signs), _f32(qjl_matrices)
+    kc, vc = np.array(k_codes, dtype=np.uint8, copy=True), np.array(v_codes, dtype=np.uint8, copy=True)
+    kx = np.array(k_qjl, dtype=np.uint32, copy=True)
+    nkv, m, d = kr.shape
+    _chk(load_library().lgh_op_pf_tq_store_qjl(device, kv_cache_type, kr.ctypes.data, vr.ctypes.data, m, nkv, d, kc.shape[1], pos0,
+                                               sg.ctypes.data, S.ctypes.data, kc.ctypes.data, vc.ctypes.data, kx.ctypes.data), "pf_tq_store_qjl")
+    return kc, vc, kx
+
+
+def op_attention_prefill_tq_qjl(kv_cache_type: int, q, k_codes, v_codes, k_qjl, signs, qjl_matrices, scale: float, pos0: int,
+                                device: int = 0) -> np.ndarray:
+    """op_attention_prefill_tq for KV_TQ2_QJL / KV_TQ3_QJL: the scores carry the QJL correction of k_qjl [nkv, max_seq, d / 32 + 1]
+    uint32 under qjl_matrices [nkv, d, d].  -> [m, nh * d]: the kernel's f16 outputs widened to f32."""
+    q, sg, S = _f32(q), _f32(signs), _f32(qjl_matrices)
+    kc, vc = np.ascontiguousarray(k_codes, dtype=np.uint8), np.ascontiguousarray(v_codes, dtype=np.uint8)
+    kx = np.ascontiguousarray(k_qjl, dtype=np.uint32)
+    m, nh, d = q.shape
+    out = np.empty((m, nh * d), dtype=np.float32)
+    _chk(load_library().lgh_op_attention_prefill_tq_qjl(device, kv_cache_type, q.ctypes.data, kc.ctypes.data, vc.ctypes.data, kx.ctypes.data,
+                                                        sg.ctypes.data, S.ctypes.data, out.ctypes.data, nh, kc.shape[0], d, kc.shape[1], scale,
+                                                        pos0, m), "attention_prefill_tq_qjl")
     return out
 
 

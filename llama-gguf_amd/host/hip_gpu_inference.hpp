@@ -85,7 +85,8 @@ class HipGpuInference {
   // GpuOnlyInference::forward_batch minus the final forward (gpu_only.rs:776-790); batched f16-GEMM path when the model allows
   void forward_batch(const std::vector<uint32_t>& tokens) { check(lgh_prefill_batch(h_, tokens.data(), tokens.size())); }
   bool prefill_is_batched() { return lgh_prefill_is_batched(h_) != 0; }
-  // LGH_PREFILL_BATCH_BYTE_KV: int8 / FP8 caches (own sequence, slots, stage contexts) take the batched path; 0 restores the default
+  // LGH_PREFILL_BATCH_BYTE_KV: int8 / FP8 caches (own sequence, slots, stage contexts) take the batched path; LGH_PREFILL_BATCH_TQ_QJL: the
+  // tq2-qjl / tq3-qjl caches do (own sequence, as tq2 / tq3); 0 restores the default
   void set_prefill_policy(uint32_t policy) { check(lgh_set_prefill_policy(h_, policy)); }
   // LGH_BATCH_F32_MATRIX (| minimum sequence count << 8): multi-sequence steps of that many sequences run their quantized mat-vecs on
   // the f32 matrix cores; 0 restores the default, bit-identical path.  After batch_create, between steps

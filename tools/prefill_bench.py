@@ -2,7 +2,8 @@
 """Times lgh_prefill_batch alone (the batched f16-GEMM prompt path): `python tools/prefill_bench.py [--model M --mix X
 --prompt N --iters I --kv f32|tq2|tq3|... --policy P]`; run it under `rocprofv3 --kernel-trace --stats` for the per-kernel split.
 --kv selects the KV cache type (f32 and the TurboQuantMSE types tq2 / tq3 have the batched path; int8 / fp8-* have it with
---policy 1 = PREFILL_BATCH_BYTE_KV (lgh_set_prefill_policy); the others run token by token)."""
+--policy 1 = PREFILL_BATCH_BYTE_KV, tq2-qjl / tq3-qjl with --policy 4 = PREFILL_BATCH_TQ_QJL (lgh_set_prefill_policy); without their
+bit they run token by token)."""
 import argparse
 import os
 import sys
@@ -19,7 +20,7 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--kv", default="f32", choices=["f32", "int8", "fp8-e4m3", "fp8-e5m2", "tq2", "tq3", "tq2-qjl", "tq3-qjl"])
-    ap.add_argument("--policy", type=int, default=0, help="lgh_set_prefill_policy word (1: int8 / FP8 caches take the batched pass)")
+    ap.add_argument("--policy", type=int, default=0, help="lgh_set_prefill_policy word (1: int8 / FP8 caches take the batched pass; 4: tq2-qjl / tq3-qjl caches do)")
     a = ap.parse_args()
     pkg = graft.load_package()
     hb = pkg.hip_backend

@@ -10,7 +10,8 @@ so the f16 GEMM path's error shows larger in the logits over a TurboQuant cache 
   (b)  CPU:  python tools/tq_prefill_calibrate.py --a test-dense=A1,test-dense-d128=A2,test-moe=A3
        the oracle alone: attn_norm / ffn_norm weights times (1 + eps u), u uniform in [-1, 1]; eps scaled until the f32-cache oracle's
        perturbed-versus-unperturbed ratio reproduces (a) (the response is linear); at that eps the TurboQuant oracle's ratio, bits 2
-       and 3, 5 perturbation seeds
+       and 3, 5 perturbation seeds; with --qjl the TurboQuantProd oracle's (tq2-qjl / tq3-qjl: codes and QJL sign bits both flip),
+       which gives K_QJL of tests/test_gpu_tq_qjl_prefill.py
   (c)  K = 2 x the largest ratio of (b)
 
 Prompts of 70 and 300 tokens, then 4 tokens, as the test runs them."""
@@ -62,8 +63,14 @@ def perturbed(eps, seed):
     return f
 
 
-def oracle_ratio(pkg, orc, name, mix, n, eps, seed, bits):
-    """max|dlogit| / tol of the oracle with perturbed norm weights against the unperturbed oracle; bits 0: the f32 cache."""
+def model_qjl(cfg, seed: int) -> np.ndarray:
+    """The K engines' projection matrices [layer][kv head][d][d], as tests/test_gpu_tq_qjl_prefill.py draws them."""
+    return np.random.default_rng(seed).standard_normal(cfg.num_layers * cfg.num_kv_heads * cfg.head_dim * cfg.head_dim).astype(np.float32)
+
+
+def oracle_ratio(pkg, orc, name, mix, n, eps, seed, bits, qjl=False):
+    """max|dlogit| / tol of the oracle with perturbed norm weights against the unperturbed oracle; bits 0: the f32 cache; qjl: the
+    TurboQuantProd cache of those bits."""
     cfg = pkg.make_config(name, max_seq_len=n + 8)
     model = pkg.SynthModel(cfg, mix=mix)
     ref, per = tr.oracle_model(orc, cfg, model), tr.oracle_model(orc, cfg, model, perturbed(eps, seed))
@@ -71,6 +78,10 @@ def oracle_ratio(pkg, orc, name, mix, n, eps, seed, bits):
         signs = tr.model_signs(cfg, 7 + bits)
         ref.set_kv_turboquant(bits, signs)
         per.set_kv_turboquant(bits, signs)
+        if qjl:
+            mats = model_qjl(cfg, 17 + bits)
+            ref.set_kv_turboquant_qjl(mats)
+            per.set_kv_turboquant_qjl(mats)
     prompt = tr.prompt_tokens(cfg, n)
     per.forward(prompt)
     r = worst(tr.follow(orc, lambda tok: per.forward([tok]), ref, prompt))
@@ -79,7 +90,7 @@ def oracle_ratio(pkg, orc, name, mix, n, eps, seed, bits):
     return r
 
 
-def calibrate(pkg, orc, a):
+def calibrate(pkg, orc, a, qjl):
     biggest = 0.0
     for name, mix in MODELS:
         base = max(oracle_ratio(pkg, orc, name, mix, n, EPS0, 0, 0) for n in PROMPTS)
@@ -88,9 +99,9 @@ def calibrate(pkg, orc, a):
         print(f"(b) {name}/{mix}: f32-cache oracle moves {base:.4f} tol at eps 2^-11; (a) = {a[name]:.4f} -> eps = {eps:.3e} = 2^{np.log2(eps):.2f} "
               f"(f32-cache oracle at that eps: {check:.4f})", flush=True)
         for bits in (2, 3):
-            rs = [max(oracle_ratio(pkg, orc, name, mix, n, eps, seed, bits) for n in PROMPTS) for seed in range(5)]
+            rs = [max(oracle_ratio(pkg, orc, name, mix, n, eps, seed, bits, qjl) for n in PROMPTS) for seed in range(5)]
             biggest = max(biggest, max(rs))
-            print(f"(b) {name}/{mix} tq{bits}: perturbed / unperturbed over 5 seeds = {['%.3f' % r for r in rs]}", flush=True)
+            print(f"(b) {name}/{mix} tq{bits}{'-qjl' if qjl else ''}: perturbed / unperturbed over 5 seeds = {['%.3f' % r for r in rs]}", flush=True)
     print(f"(c) largest ratio {biggest:.3f} -> K = {2 * biggest:.2f}")
 
 
@@ -98,13 +109,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--measure-a", action="store_true")
     ap.add_argument("--a", default="")
+    ap.add_argument("--qjl", action="store_true", help="step (b) over the TurboQuantProd caches (tq2-qjl / tq3-qjl)")
     args = ap.parse_args()
     pkg, orc = graft.load_package(), graft.load_oracle()
     orc.set_threads(min(16, os.cpu_count() or 1))
     if args.measure_a:
         measure_a(pkg, orc)
     if args.a:
-        calibrate(pkg, orc, {k: float(v) for k, v in (kv.split("=") for kv in args.a.split(","))})
+        calibrate(pkg, orc, {k: float(v) for k, v in (kv.split("=") for kv in args.a.split(","))}, args.qjl)
 
 
 if __name__ == "__main__":
