@@ -88,7 +88,25 @@ typedef struct lgh_model_desc {
                                         11-20), which the reference exports (model/mod.rs:31, lib.rs:77) but which NO forward path and no
                                         CLI flag of it reaches; they are offered for hosts that use that cache type directly.
                                         0 = f32, or int8 when LGH_FLAG_KV_INT8 is set (the field was added after the flag) */
+  uint32_t attn_policy;              /* LGH_ATTN_*: which decode-attention kernels the context may take (below).  A descriptor from before
+                                        the field (struct_size up to kv_cache_type, or up to flags) reads as 0; a bit that is not assigned
+                                        answers LGH_INVALID_ARGUMENT, before any device is looked for */
 } lgh_model_desc;
+
+/* lgh_model_desc.attn_policy.  The engine has split decode-attention kernels, a batched prompt pass and byte caches for head_dim 64 / 128
+ * with 1, 2, 4 or 8 query heads per kv head.  By default every other group size (3: Llama-3.2-3B; 5: Qwen2.5-14B / 32B; 6: InternLM2-20B;
+ * 7: Yi-34B, Qwen2.5-7B) decodes on lgh::attn_decode_any_kernel (one workgroup per query head, scores in LDS: max_seq_len <= 38400) and
+ * takes its prompts token by token.
+ *   LGH_ATTN_GROUP_MATRIX  an f32-cache context with head_dim 64 / 128 and such a group size up to 16 decodes on
+ *       lgh::attn_group_kernel<D, NW> (csrc/attention_group.hip: the query heads of a kv group as the N index of the f32 matrix
+ *       instruction, every cached row read once per kv head) + lgh::attn_combine_kernel at every position, has no max_seq_len limit of
+ *       its own, and takes the batched prompt pass under that pass's other conditions (lgh_prefill_is_batched reports it;
+ *       LGH_FLAG_EXACT_PREFILL still wins).  Accepted and without effect on a shape that has split kernels and on a shape the kernel does
+ *       not cover (another head_dim, more than 16 heads per kv head), which keeps lgh::attn_decode_any_kernel and its row limit.
+ * Not covered, as before: byte and TurboQuant caches for these group sizes (lgh_create: Unsupported), the multi-sequence engine
+ * (lgh_batch_create refuses the shape), and lgh_load_gguf, which leaves the field 0.  lgh_pipeline_* / lgh_tp_* pass the field to their
+ * contexts as they pass every other. */
+enum { LGH_ATTN_DEFAULT = 0, LGH_ATTN_GROUP_MATRIX = 1u << 0 };
 
 enum {
   LGH_KV_F32 = 0,
@@ -170,7 +188,8 @@ enum {
   LGH_SYM_MVH_F16 = 22,    /* lgh::mvh_kernel<false> : F16 kept 16-bit (csrc/matvec_h16.hip; contexts with LGH_WEIGHTS_HALF_TILES) */
   LGH_SYM_MVH_BF16 = 23,   /* lgh::mvh_kernel<true>  : BF16 kept 16-bit */
   LGH_SYM_MVQ_LEGACY = 24, /* lgh::mvq_legacy_kernel<128u> / <256u> / <512u> : Q4_1 / Q5_0 / Q5_1 (contexts with LGH_WEIGHTS_LEGACY_TILES) */
-  LGH_SYM_COUNT = 25       /* = the last entry + 1: a new symbol is appended and bumps this, and SYM_NAMES of hip_backend.py follows by hand */
+  LGH_SYM_ATTN_GROUP = 25, /* lgh::attn_group_kernel<D, NW> : decode attention of any group size up to 16 (contexts with LGH_ATTN_GROUP_MATRIX) */
+  LGH_SYM_COUNT = 26       /* = the last entry + 1: a new symbol is appended and bumps this, and SYM_NAMES of hip_backend.py follows by hand */
 };
 
 typedef struct lgh_stats {
@@ -712,7 +731,9 @@ int lgh_op_attention(int device, const float* q, const float* k, const float* v,
  * Backend::attention_cached (ops.rs:1479-1537) over the f32 cache [n_kv_heads][max_seq_len][head_dim], rows 0..pos already
  * stored (as after the engine's kv_store).  path 0: split + merge (4 or 8 waves per workgroup, chosen from max_seq_len as in
  * the engine; n_splits 1..32); path 1: the single-launch kernel with one workgroup per kv head; path 2: the kernel of any head_dim / group
- * size (max_seq_len <= 38400); path 3: the engine's single-launch kernel, one workgroup per query head (max_seq_len <= 16384).
+ * size (max_seq_len <= 38400); path 3: the engine's single-launch kernel, one workgroup per query head (max_seq_len <= 16384);
+ * path 4: lgh::attn_group_kernel + merge, as a context with LGH_ATTN_GROUP_MATRIX runs it (head_dim 64 / 128, any 1 .. 16 query heads per
+ * kv head, anything else Unsupported; 4 or 8 waves from max_seq_len; n_splits 1..32).  A path above 4: InvalidArgument.
  *
  * image_out (every entry point of this group; may be NULL): wo's input as the launch that writes `out` leaves it for the mat-vec, the XQ
  * image of `out` (1280 bytes per 256 elements, rounded up).  One sequence: (n_heads * head_dim + 255) / 256 * 1280 bytes; path 2

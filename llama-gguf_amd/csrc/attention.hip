@@ -1047,7 +1047,8 @@ hipError_t attn_block_launch(const KvLayout& l, const KvCache& kv, const AttnBlo
   if (l.f32()) {
     // (read once per process: tests/test_gpu_fresh_env.py::test_valu_prompt_attention holds the VALU kernel to test_prefill's bound)
     static const bool valu = [] { const char* e = std::getenv("LGH_PF_ATTN_VALU"); return e && std::atoi(e) != 0; }();   // (A/B switch: the VALU kernel)
-    if (!valu && mfma_shape)
+    // (a group size without split kernels, LGH_ATTN_GROUP_MATRIX contexts: the VALU kernel has no instantiation, the switch does not apply)
+    if ((!valu || !attn_shape_has_fast_kernel(l.d, g)) && mfma_shape)
       return by_head_dim([&](auto d) {
         constexpr int D = decltype(d)::value;
         return attn_block_go<&attn_pf_mfma_kernel<D, NW, false>, D, NW>(a, a.q, kv.k_f32(), kv.v_f32(), a.n_heads, g, l.max_seq, a.scale, a.pos0, a.m_tokens,

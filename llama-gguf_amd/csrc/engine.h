@@ -111,6 +111,7 @@ struct lgh_ctx {
   std::string err;
   hipGraphExec_t graph[lgh::MODE_COUNT][2] = {};   // [mode][attention variant: 0 split + combine, 1 single launch (contexts up to direct_attn_max_kv rows)]
   lgh::AttnVariant attn_direct = lgh::ATTN_VAR_SPLIT;   // variant of the token being enqueued (chosen by the host-side position)
+  bool attn_group = false;                         // LGH_ATTN_GROUP_MATRIX in effect: every token runs attn_group_kernel + the merge
   bool attn_generic = false;                       // the shape has no split kernel: every token runs attn_decode_any_kernel (a field, not
                                                    // re-derived from the shape, so that lgh_op_attention_decode can run that kernel on any shape)
   uint32_t direct_attn_max_kv = 0;                 // contexts up to this many rows take the single-launch attention
@@ -209,6 +210,7 @@ int embed_forward(lgh_ctx* c);   // the token's embedding row into c->hidden, th
 int moe_experts_forward(lgh_ctx* c, lgh::LayerW& Lw, const FfnView& v, const float* next_nw, bool next_mfma);   // given v.moe_sel / v.moe_w
 void rope_table_host(const lgh_model_desc& d, std::vector<float>& cs);
 int engine_shape_check(const lgh_model_desc& d, std::string& why);   // LGH_OK, or the status lgh_create returns and why
+bool attn_group_in_effect(const lgh_model_desc& d);                  // lgh_model_desc.attn_policy: the group kernel serves this context
 int dev_alloc(lgh_ctx* c, void** p, size_t bytes);
 // every buffer of the table with a size, in order: allocated, zeroed on the context's stream, added to `counter`
 int alloc_zeroed(lgh_ctx* c, const AllocSpec* bufs, size_t count, uint64_t& counter);

@@ -132,15 +132,25 @@ static uint32_t desc_kv_type(const lgh_model_desc& d) {
   return d.kv_cache_type == LGH_KV_F32 && (d.flags & LGH_FLAG_KV_INT8) ? (uint32_t)LGH_KV_INT8 : d.kv_cache_type;
 }
 
-// A caller's descriptor as lgh_create reads it (one from before kv_cache_type was appended is still taken), the cache type resolved
+// A caller's descriptor as lgh_create reads it (one from before attn_policy or before kv_cache_type was appended is still taken, the
+// missing fields 0), the cache type resolved
 static int desc_normalize(const lgh_model_desc* desc, lgh_model_desc& d) {
-  if (!desc || (desc->struct_size != sizeof(lgh_model_desc) && desc->struct_size != offsetof(lgh_model_desc, kv_cache_type))) return LGH_INVALID_ARGUMENT;
+  if (!desc || (desc->struct_size != sizeof(lgh_model_desc) && desc->struct_size != offsetof(lgh_model_desc, attn_policy) &&
+                desc->struct_size != offsetof(lgh_model_desc, kv_cache_type)))
+    return LGH_INVALID_ARGUMENT;
   d = lgh_model_desc{};
   std::memcpy(&d, desc, desc->struct_size);
   d.struct_size = sizeof(lgh_model_desc);
-  if (d.kv_cache_type > LGH_KV_TQ3_QJL) return LGH_INVALID_ARGUMENT;
+  if (d.kv_cache_type > LGH_KV_TQ3_QJL || (d.attn_policy & ~(uint32_t)LGH_ATTN_GROUP_MATRIX)) return LGH_INVALID_ARGUMENT;
   d.kv_cache_type = desc_kv_type(d);
   return LGH_OK;
+}
+
+// LGH_ATTN_GROUP_MATRIX takes effect: an f32 cache, a group size without split kernels that attn_group_kernel covers
+bool attn_group_in_effect(const lgh_model_desc& d) {
+  if (!(d.attn_policy & LGH_ATTN_GROUP_MATRIX) || desc_kv_type(d) != LGH_KV_F32 || !d.num_kv_heads || d.num_heads % d.num_kv_heads) return false;
+  const uint32_t g = d.num_heads / d.num_kv_heads;
+  return !attn_shape_has_fast_kernel(d.head_dim, g) && attn_group_covers(d.head_dim, g);
 }
 
 int engine_shape_check(const lgh_model_desc& d, std::string& why) {
@@ -155,8 +165,9 @@ int engine_shape_check(const lgh_model_desc& d, std::string& why) {
   }
   const uint32_t g = d.num_heads / d.num_kv_heads;
   // head_dim 64 / 128 with 1, 2, 4, 8 query heads per kv head take the split attention kernels; every other shape takes the
-  // one-workgroup-per-head kernel (attention.hip: attn_decode_any_kernel), whose scores live in LDS
-  if (!attn_shape_has_fast_kernel(d.head_dim, g) && (size_t)d.max_seq_len * 4 > 150 * 1024) {
+  // one-workgroup-per-head kernel (attention.hip: attn_decode_any_kernel), whose scores live in LDS — unless the context asked for the
+  // group kernel and it covers the shape (attention_group.hip: split partials, no row limit)
+  if (!attn_shape_has_fast_kernel(d.head_dim, g) && !attn_group_in_effect(d) && (size_t)d.max_seq_len * 4 > 150 * 1024) {
     why = "head_dim " + std::to_string(d.head_dim) + " with " + std::to_string(g) + " query heads per kv head runs the generic attention "
           "kernel, which holds max_seq_len scores in LDS: max_seq_len must be <= 38400 for it (got " + std::to_string(d.max_seq_len) + ")";
     return LGH_UNSUPPORTED;
@@ -221,7 +232,9 @@ int lgh_create(const lgh_model_desc* desc, lgh_ctx** out) {
   c->n_splits = splits;
   const uint32_t dsel = (d.flags >> LGH_FLAG_ATTN_DIRECT_SHIFT) & 0xFFu;
   c->direct_attn_max_kv = dsel == 255 ? 0 : dsel ? dsel * 64 : kDirectAttnDefaultKv;
-  c->attn_generic = !attn_shape_has_fast_kernel(d.head_dim, d.num_heads / d.num_kv_heads);
+  c->attn_group = attn_group_in_effect(d);
+  c->attn_generic = !c->attn_group && !attn_shape_has_fast_kernel(d.head_dim, d.num_heads / d.num_kv_heads);
+  if (c->attn_group) c->direct_attn_max_kv = 0;   // these shapes have no single-launch variant: the group launch + merge at every position
   if (c->kvl.staged()) c->direct_attn_max_kv = 0;   // the staged formats have one attention structure: splits + combine
   *out = c;
   return LGH_OK;

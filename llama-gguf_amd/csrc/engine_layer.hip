@@ -226,7 +226,11 @@ static int attention_step(lgh_ctx* c, uint32_t li, const AttnStep& s, float scal
     if (kvl.tq()) { const TqLayer t = tq_layer(c, li); a.signs = t.signs; a.qjl_s = t.qjl_s; }
     a.out = s.out;
     a.st = c->stream;
-    if ((rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] { return attn_split_launch(kvl, s.kv, a); }))) return rc;
+    if (c->attn_group)   // LGH_ATTN_GROUP_MATRIX in effect (own sequence, f32 cache): the group kernel's partials, the same merge
+      rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN_GROUP, kv_bytes, [&] { return attn_group_launch(kvl, s.kv, a); });
+    else
+      rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] { return attn_split_launch(kvl, s.kv, a); });
+    if (rc) return rc;
     qa = attn_image(c, s, xq_out);
     a.xq_out = qa ? qa->xq : nullptr;
     a.xq_stride = s.n_seq ? xq_stride_of(d.num_heads * d.head_dim) : 0;

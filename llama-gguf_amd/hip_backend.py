@@ -57,14 +57,14 @@ ABI_SYMBOLS = (
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
 K_COUNT = 16
-SYM_COUNT = 25
+SYM_COUNT = 26
 # kernel symbols as rocprofv3 prints them (LGH_SYM_* order)
 SYM_NAMES = ("lgh::mv_kernel<1u, 1024>", "lgh::mv_kernel<8u, 1024>", "lgh::mv_kernel<16u, 1024>",
              "lgh::mv_kernel<2u, 768>", "lgh::mv_kernel<4u, 512>", "lgh::mv_kernel<5u, 512>", "lgh::mv_kernel<6u, 512>",
              "lgh::mv_kernel<31u, 512>", "lgh::f32_matvec_kernel", "lgh::attn_partial_kernel", "lgh::attn_combine_kernel",
              "lgh::embed_kernel", "lgh::argmax_stage1+2", "lgh::moe_router_kernel", "other", "lgh::mvq_kernel<1u>", "lgh::mvq_kernel<2u>", "lgh::mvq_kernel<3u>", "lgh::mvq_kernel<4u>",
              "lgh::mvq_kernel<8u>", "unused", "lgh::mvq_kernel<32u>", "lgh::mvh_kernel<false>", "lgh::mvh_kernel<true>",
-             "lgh::mvq_legacy_kernel<128u>")
+             "lgh::mvq_legacy_kernel<128u>", "lgh::attn_group_kernel")
 FLAG_NO_GRAPH = 1
 BATCH_F32_MATRIX = 1        # lgh_set_batch_policy: steps of >= (policy >> 8 & 0xFF, 0 = the library default) sequences on the f32 matrix cores
 WEIGHTS_LOWBIT_TILES = 1    # lgh_set_weight_policy: Q3_K / Q2_K matrices stay quantized in HBM (matrix-core tile layouts) instead of f32
@@ -72,6 +72,8 @@ WEIGHTS_LEGACY_TILES = 8    # ... Q4_1 / Q5_0 / Q5_1 matrices stay quantized in 
 WEIGHTS_HALF_TILES = 4      # ... F16 / BF16 matrices stay 16-bit in HBM (8192-B tiles, their own decode mat-vec); bit 1 is not assigned
 PREFILL_BATCH_BYTE_KV = 1   # lgh_set_prefill_policy: int8 / FP8 caches take the batched prompt pass (own sequence, slots, stage contexts)
 PREFILL_BATCH_TQ_QJL = 4    # ... tq2-qjl / tq3-qjl caches take it (own sequence, as tq2 / tq3); bit 1 is not assigned
+ATTN_GROUP_MATRIX = 1       # lgh_model_desc.attn_policy: f32-cache contexts whose group size has no split kernel (3, 5, 6, 7 .. 16 heads per kv head)
+                            # decode on attn_group_kernel + merge and take the batched prompt pass
 FLAG_EXACT_PREFILL = 4   # forward_batch feeds tokens one by one (f32 throughout) instead of the batched f16 GEMM path
 KV_F32, KV_INT8, KV_FP8_E4M3, KV_FP8_E5M2 = 0, 1, 2, 3   # lgh_model_desc.kv_cache_type: f32, or QuantizedKVCache's formats (kv_quantized.rs; no CLI flag reaches them)
 KV_TQ2, KV_TQ3 = 4, 5   # KVCacheType::TurboQuantMSE { bits: 2 | 3 }: what `--kv-cache-type tq2 | tq3` selects (src/config.rs:808-817)
@@ -100,7 +102,7 @@ class ModelDesc(C.Structure):
         "use_neox_rope")]
                 + [(n, C.c_float) for n in ("norm_eps", "rope_freq_base", "rope_freq_scale")]
                 + [("device_id", C.c_int32), ("layer_begin", C.c_uint32), ("layer_end", C.c_uint32),
-                   ("flags", C.c_uint32), ("kv_cache_type", C.c_uint32)])
+                   ("flags", C.c_uint32), ("kv_cache_type", C.c_uint32), ("attn_policy", C.c_uint32)])
 
 
 class KvLayout(C.Structure):
@@ -353,9 +355,10 @@ class HipGpuInference:
     @classmethod
     def from_model(cls, model, max_seq_len: int, device: int = 0, layer_range: Optional[Sequence[int]] = None,
                    flags: int = 0, attn_splits: int = 0, attn_direct: int = 0, kv_cache_type: int = 0,
-                   kv_rotation_signs=None, kv_qjl_matrices=None, prefill_policy: int = 0, weight_policy: int = 0) -> "HipGpuInference":
+                   kv_rotation_signs=None, kv_qjl_matrices=None, prefill_policy: int = 0, weight_policy: int = 0,
+                   attn_policy: int = 0) -> "HipGpuInference":
         """`model` hands over what LlamaModel::into_parts does (llama.rs:138-160): `.config` and
-        `.tensors(layers)` yielding (gguf_name, ggml_type, ne, host bytes)."""
+        `.tensors(layers)` yielding (gguf_name, ggml_type, ne, host bytes).  attn_policy: lgh_model_desc.attn_policy (ATTN_GROUP_MATRIX)."""
         L = load_library()
         self = cls()
         cfg = model.config
@@ -372,7 +375,7 @@ class HipGpuInference:
         d.layer_begin, d.layer_end = lb, le
         # attn_direct: 64-row units, 0 = tuned default, 255 = never
         d.flags = flags | ((attn_splits & 0xFF) << 8) | ((attn_direct & 0xFF) << 16)
-        d.kv_cache_type = int(kv_cache_type)
+        d.kv_cache_type, d.attn_policy = int(kv_cache_type), int(attn_policy)
         _chk(L.lgh_create(C.byref(d), C.byref(self._h)), "lgh_create (is a HIP device visible?)")
         self.config, self.vocab_size, self.hidden_size = cfg, cfg.vocab_size, cfg.hidden_size
         try:
@@ -1172,7 +1175,7 @@ def op_attention_cached(q, k_cache, v_cache, scale: float, kv_len: int, n_splits
     return out
 
 
-ATTN_SPLIT, ATTN_DIRECT, ATTN_ANY, ATTN_HEAD = 0, 1, 2, 3   # lgh_op_attention_decode paths
+ATTN_SPLIT, ATTN_DIRECT, ATTN_ANY, ATTN_HEAD, ATTN_GROUP = 0, 1, 2, 3, 4   # lgh_op_attention_decode paths
 
 
 def _attn_image(q, n_images: int = 1):
@@ -1184,7 +1187,8 @@ def _attn_image(q, n_images: int = 1):
 def op_attention_decode(path: int, q, k_cache, v_cache, scale: float, pos: int, n_splits: int = 8, device: int = 0, *, image: bool = False):
     """One decode step's attention over the f32 cache (rows 0..pos stored) on the engine path `path`: ATTN_SPLIT (split + merge),
     ATTN_DIRECT (one launch, a workgroup per kv head), ATTN_HEAD (one launch, a workgroup per query head: the engine's single launch;
-    max_seq <= 16384, its scores live in LDS) or ATTN_ANY (any head_dim / group size).  q [nh, d]; caches [nkv, max_seq, d]; pos via the
+    max_seq <= 16384, its scores live in LDS), ATTN_ANY (any head_dim / group size) or ATTN_GROUP (attn_group_kernel + merge: head_dim 64 / 128,
+    any 1 .. 16 heads per kv head).  q [nh, d]; caches [nkv, max_seq, d]; pos via the
     device word.
     image: -> (out, wo's input as the launch leaves it: the XQ image of out, uint8 [bytes]); ATTN_ANY writes none (InvalidArgument)."""
     q, kc, vc = _f32(q), _f32(k_cache), _f32(v_cache)

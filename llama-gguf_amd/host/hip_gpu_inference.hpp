@@ -49,10 +49,13 @@ class HipGpuInference {
   // kv_rotation_signs / kv_qjl_matrices: what a TurboQuant KV cache (desc.kv_cache_type LGH_KV_TQ*; `--kv-cache-type tq2 | tq3 |
   // tq2-qjl | tq3-qjl`) draws from its seeded RNG in the reference — HadamardRotation::signs() of every (layer, kv head, K / V) engine
   // and the K engines' QjlProjector matrices (src/model/kv_turboquant.rs:44-71) — as data; empty = the library's stand-ins
+  // attn_policy: desc.attn_policy (LGH_ATTN_GROUP_MATRIX: an f32-cache model with 3, 5, 6, 7 .. 16 query heads per kv head decodes on
+  // the matrix-core group kernel, has no 38400-row limit and takes the batched prompt pass); not 0 replaces the descriptor's value
   static HipGpuInference from_model(lgh_model_desc desc, const std::vector<HostTensor>& tensors, size_t max_seq_len,
                                     const std::vector<float>& kv_rotation_signs = {}, const std::vector<float>& kv_qjl_matrices = {},
-                                    uint32_t weight_policy = LGH_WEIGHTS_DEFAULT) {
+                                    uint32_t weight_policy = LGH_WEIGHTS_DEFAULT, uint32_t attn_policy = LGH_ATTN_DEFAULT) {
     desc.struct_size = sizeof(lgh_model_desc);
+    if (attn_policy) desc.attn_policy = attn_policy;
     desc.max_seq_len = (uint32_t)max_seq_len;
     lgh_ctx* h = nullptr;
     int rc = lgh_create(&desc, &h);

@@ -92,6 +92,8 @@ CONFIGS = {
                            head_dim=64, vocab_size=32000, rope_freq_base=10000.0),
     "llama-3-8b": dict(hidden_size=4096, intermediate_size=14336, num_layers=32, num_heads=32, num_kv_heads=8,
                        head_dim=128, vocab_size=128256, rope_freq_base=500000.0),
+    "llama-3.2-3b": dict(hidden_size=3072, intermediate_size=8192, num_layers=28, num_heads=24, num_kv_heads=8,
+                         head_dim=128, vocab_size=128256, rope_freq_base=500000.0),
     "mixtral-8x7b": dict(hidden_size=4096, intermediate_size=14336, num_layers=32, num_heads=32, num_kv_heads=8,
                          head_dim=128, vocab_size=32000, rope_freq_base=1000000.0, num_experts=8,
                          num_experts_per_token=2, expert_intermediate_size=14336),
