@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <atomic>
 #include <type_traits>
+#include <utility>
 
 #include "device_utils.h"
 #include "mv_epilogue.h"
@@ -768,6 +769,9 @@ struct MvsPlan {
 
 template <int N>
 __device__ __forceinline__ void wait_vm_behind() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order: a loop whose index is a constant in every iteration
+template <typename Fn, int... I>
+__device__ __forceinline__ void for_each_int(Fn&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 
 template <typename P, int SEG>
 __device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, const uint32_t ntile_w, const uint8_t* xq, const uint8_t* plane0,
@@ -799,14 +803,22 @@ __device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, 
   const uint32_t xrec_lds = lds_base + wave * (nbw * kXqRecord);
   const uint8_t* xg = xq + wave * (nbw * kXqRecord);
   LGH_WSTAMP(2);
-#pragma unroll
-  for (uint32_t b = 0; b < nbw; b++) {
+  auto x_request = [&](uint32_t b) {   // record b of the wave's k-slice: two vector-memory requests
     const uint8_t* src = xg + b * kXqRecord;
     const uint32_t dst = xrec_lds + b * kXqRecord;
     uint32_t keep;   // (moves only: nothing here may touch SCC, which the compiler can hold live across the asm)
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %4\n\t"
                  "s_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(src + lane * 16), "v"(src + 1024 + lane * 4), "s"(dst), "s"(dst + 1024u) : "memory");
+  };
+  // Plans whose waves own at least kDepth blocks (the 56-block plans: nbw = 7, 72 KB of records per workgroup) request record b
+  // right in front of the tile that first uses it instead of all records first: a CU serves its waves' requests in order, and
+  // with every record in front the second wave of each SIMD got its x 1.2 - 1.9 us after the first (profiles/down_stream.md).
+  constexpr bool kXStream = nbw >= (uint32_t)kDepth;
+  constexpr int kRecLoads = 2;   // vector-memory requests of one x_request
+  if constexpr (!kXStream) {
+#pragma unroll
+    for (uint32_t b = 0; b < nbw; b++) x_request(b);
   }
   // ---- geometry: G = 1, so the workgroup's ntile_w tiles (Rg, fewer in the segment's last workgroup; never none: mvqs_match)
   // are this wave's, blocks [wave * nbw, (wave + 1) * nbw) of each.  The input vector, the planes and the tile count are
@@ -841,10 +853,38 @@ __device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, 
   const uint32_t nitems = (uint32_t)NP * ntile_w * nbw;
   RawT16 buf[kDp];
   Pos pos[kDp];
+  // `rem` items not yet consumed, kDp of them in flight, the oldest in slot `slot0`; ends with nothing in flight
+  auto stream = [&](uint32_t rem, auto slot0) {
+    constexpr int s0 = decltype(slot0)::value;
+    while (rem >= 2 * kDp) {
+#pragma unroll
+      for (int j = 0; j < kDp; j++) {
+        const int s = (j + s0) % kDp;
+        consume(pos[s], buf[s]);
+        pos[s] = nx; issue(nx, buf[s]); advance();
+      }
+      rem -= kDp;
+    }
+    const uint32_t unissued = rem - kDp;   // 0 .. kDp-1
+#pragma unroll
+    for (int j = 0; j < kDp; j++) {
+      const int s = (j + s0) % kDp;
+      consume(pos[s], buf[s]);
+      if ((uint32_t)j < unissued) { pos[s] = nx; issue(nx, buf[s]); advance(); }
+    }
+#pragma unroll
+    for (int j = 0; j < kDp - 1; j++) {
+      const int s = (j + s0) % kDp;
+      if ((uint32_t)j < unissued) consume(pos[s], buf[s]);
+    }
+  };
   auto run = [&](auto n_first) {
     constexpr int NF = decltype(n_first)::value;
 #pragma unroll
-    for (int j = 0; j < NF; j++) { pos[j] = nx; issue(nx, buf[j]); advance(); }
+    for (int j = 0; j < NF; j++) {
+      if constexpr (kXStream) x_request((uint32_t)j);   // item j of the opening is block j of the first tile (NF = kDp <= nbw)
+      pos[j] = nx; issue(nx, buf[j]); advance();
+    }
     // Behind the first tiles: what the epilogue needs that does not depend on the mat-vec — the residual pair, RoPE's (cos, sin)
     // pair at the position, and in wave 0 the producer's 256 partial sums of x^2 (RMSNorm; first used after the last tile).
     mv_epilogue_prefetch_resid_static<EPI>(S_resid, A, wg, epi_pre);
@@ -853,40 +893,64 @@ __device__ __forceinline__ void mvqs_body(const uint32_t wg, const uint32_t Rg, 
 #pragma unroll
       for (int j = 0; j < 4; j++) ssp[j] = L_ssq_part[lane + 64 * j];
     }
-    // The wait for x counts the NF * LPT tile loads ONLY (one instruction per ldg_nt*, the generic body's bookkeeping) and not the
-    // plain loads just issued, however many instructions the compiler made of them: vmcnt retires in order, so with K of those in
-    // flight too the wave passes once x AND the K oldest tile loads have arrived.  K <= 6 loads of tiles 0 and 1, which the very
-    // next instructions wait for in full anyway.  A count that is too SMALL can only wait longer, never let x be read early.
-    wait_vm_behind<NF * LPT>();
-    LGH_WSTAMP(4);
-    LGH_WSTAMP(5);
-    if constexpr (NF < kDp) {
-#pragma unroll
-      for (int j = 0; j < NF; j++) consume(pos[j], buf[j]);
-    } else {
-      uint32_t rem = nitems;
-      while (rem >= 2 * kDp) {
-#pragma unroll
-        for (int j = 0; j < kDp; j++) {
-          consume(pos[j], buf[j]);
-          pos[j] = nx; issue(nx, buf[j]); advance();
+    if constexpr (kXStream) {
+      // The first tile's pass, unrolled: item i = block i, in slot i % kDp, with record i requested right in front of its tile;
+      // behind the consume of item i goes item i + kDp, with its record while that is still a block of the first tile.  Later
+      // tiles and passes read the records from LDS: every record is requested exactly once, whatever Rg.
+      // The wait in front of consume i counts what was issued BEHIND (record i, tile i), tile loads one per ldg_nt* as above: the
+      // items i+1 .. i+kDp-1 — with a record (kRecLoads more) up to block nbw-1, and behind that block only if the wave has a
+      // second tile or pass (`more`: then it has all of them, nitems >= 2 nbw >= nbw + kDp).  The plain loads above are not
+      // counted: they can only make the wait longer.
+      static_assert(NF == kDp && nbw >= (uint32_t)kDp, "the opening is kDp blocks of the first tile");
+      auto first_pass = [&](auto has_more) {
+       constexpr bool more = decltype(has_more)::value;
+       for_each_int([&](auto ic) {
+        constexpr int i = decltype(ic)::value, s = i % kDp;
+        constexpr int last_rec = (int)nbw - 1;   // last item that carries a record
+        constexpr int with_rec = i + kDp - 1 <= last_rec ? kDp - 1 : last_rec - i, without = kDp - 1 - with_rec;
+        if (without > 0 && more) wait_vm_behind<with_rec * (kRecLoads + LPT) + without * LPT>();
+        else wait_vm_behind<with_rec * (kRecLoads + LPT)>();
+        if (i == 0) { LGH_WSTAMP(4); LGH_WSTAMP(5); }
+        consume(pos[s], buf[s]);
+        // (the item's sum is wanted HERE: in this straight-line code the compiler otherwise leaves every item's recombination and
+        // scaling for the end of the pass and keeps the MFMA results of all of them live — 256 VGPRs and scratch)
+        asm volatile("" : "+v"(acc));
+        if (i + kDp <= last_rec) {
+          x_request((uint32_t)(i + kDp));
+          pos[s] = nx; issue(nx, buf[s]); advance();
+        } else if (more) {
+          pos[s] = nx; issue(nx, buf[s]); advance();
         }
-        rem -= kDp;
+       }, std::make_integer_sequence<int, (int)nbw>{});
+      };
+      if (nitems > nbw) {
+        first_pass(std::true_type{});
+        // every record is in LDS now; the remaining items stream as in the other plans, from slot nbw % kDp on
+        stream(nitems - nbw, std::integral_constant<int, (int)(nbw % (uint32_t)kDp)>{});
+      } else {
+        first_pass(std::false_type{});
       }
-      const uint32_t unissued = rem - kDp;   // 0 .. kDp-1
+    } else {
+      // The wait for x counts the NF * LPT tile loads ONLY (one instruction per ldg_nt*, the generic body's bookkeeping) and not the
+      // plain loads just issued, however many instructions the compiler made of them: vmcnt retires in order, so with K of those in
+      // flight too the wave passes once x AND the K oldest tile loads have arrived.  K <= 6 loads of tiles 0 and 1, which the very
+      // next instructions wait for in full anyway.  A count that is too SMALL can only wait longer, never let x be read early.
+      wait_vm_behind<NF * LPT>();
+      LGH_WSTAMP(4);
+      LGH_WSTAMP(5);
+      if constexpr (NF < kDp) {
 #pragma unroll
-      for (int j = 0; j < kDp; j++) {
-        consume(pos[j], buf[j]);
-        if ((uint32_t)j < unissued) { pos[j] = nx; issue(nx, buf[j]); advance(); }
+        for (int j = 0; j < NF; j++) consume(pos[j], buf[j]);
+      } else {
+        stream(nitems, std::integral_constant<int, 0>{});
       }
-#pragma unroll
-      for (int j = 0; j < kDp - 1; j++)
-        if ((uint32_t)j < unissued) consume(pos[j], buf[j]);
     }
   };
   // a wave has NP * nbw items per tile: at least kDp of them unless the plan is one pass over two blocks and the workgroup one tile
   // (every workgroup has a tile: mvq_plan makes none without and mvqs_match refuses launches that have one)
-  if (NP * nbw >= (uint32_t)kDp || ntile_w > 1) {
+  if constexpr (NP * nbw >= (uint32_t)kDp) {
+    run(std::integral_constant<int, kDp>{});
+  } else if (ntile_w > 1) {
     run(std::integral_constant<int, kDp>{});
   } else {
     run(std::integral_constant<int, (NP * nbw < (uint32_t)kDp ? NP * nbw : 1)>{});
