@@ -103,8 +103,14 @@ typedef struct lgh_model_desc {
  *       its own, and takes the batched prompt pass under that pass's other conditions (lgh_prefill_is_batched reports it;
  *       LGH_FLAG_EXACT_PREFILL still wins).  Accepted and without effect on a shape that has split kernels and on a shape the kernel does
  *       not cover (another head_dim, more than 16 heads per kv head), which keeps lgh::attn_decode_any_kernel and its row limit.
- * Not covered, as before: byte and TurboQuant caches for these group sizes (lgh_create: Unsupported), the multi-sequence engine
- * (lgh_batch_create refuses the shape), and lgh_load_gguf, which leaves the field 0.  lgh_pipeline_* / lgh_tp_* pass the field to their
+ *       With kv_cache_type LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2 (or LGH_FLAG_KV_INT8) the same shapes decode on
+ *       lgh::attn_group_kv8_kernel<D, NW, FMT> (csrc/attention_group_kv8.hip: the same kernel reading bytes; its launch also quantizes
+ *       and stores the current token's rows, bit for bit as the split kernels' launch does) + lgh::attn_combine_kernel; without the bit
+ *       such a context stays Unsupported at lgh_create.  Its prompts go token by token whatever lgh_set_prefill_policy says
+ *       (lgh_prefill_is_batched: 0).
+ * Not covered, as before: TurboQuant caches for these group sizes (lgh_create: Unsupported, with or without the bit), the batched prompt
+ * pass over byte caches for them, head sizes other than 64 / 128 and more than 16 heads per kv head with a byte cache (Unsupported), the
+ * multi-sequence engine (lgh_batch_create refuses the shape), and lgh_load_gguf, which leaves the field 0.  lgh_pipeline_* / lgh_tp_* pass the field to their
  * contexts as they pass every other. */
 enum { LGH_ATTN_DEFAULT = 0, LGH_ATTN_GROUP_MATRIX = 1u << 0 };
 
@@ -188,7 +194,8 @@ enum {
   LGH_SYM_MVH_F16 = 22,    /* lgh::mvh_kernel<false> : F16 kept 16-bit (csrc/matvec_h16.hip; contexts with LGH_WEIGHTS_HALF_TILES) */
   LGH_SYM_MVH_BF16 = 23,   /* lgh::mvh_kernel<true>  : BF16 kept 16-bit */
   LGH_SYM_MVQ_LEGACY = 24, /* lgh::mvq_legacy_kernel<128u> / <256u> / <512u> : Q4_1 / Q5_0 / Q5_1 (contexts with LGH_WEIGHTS_LEGACY_TILES) */
-  LGH_SYM_ATTN_GROUP = 25, /* lgh::attn_group_kernel<D, NW> : decode attention of any group size up to 16 (contexts with LGH_ATTN_GROUP_MATRIX) */
+  LGH_SYM_ATTN_GROUP = 25, /* lgh::attn_group_kernel<D, NW>, over a byte cache lgh::attn_group_kv8_kernel<D, NW, FMT> : decode attention of any
+                              group size up to 16 (contexts with LGH_ATTN_GROUP_MATRIX) */
   LGH_SYM_COUNT = 26       /* = the last entry + 1: a new symbol is appended and bumps this, and SYM_NAMES of hip_backend.py follows by hand */
 };
 
@@ -750,7 +757,10 @@ int lgh_op_attention_decode_multi(int device, const float* q, const float* k_cac
                                   const int* slot, float scale, int n_splits, uint8_t* image_out);
 /* QuantizedKVCache (kv_quantized.rs:143-300, 385-565): kv_cache_type LGH_KV_INT8 / FP8_E4M3 / FP8_E5M2.  k_bytes / v_bytes
  * [n_kv_heads][max_seq_len][head_dim] and (int8 only; may be NULL otherwise) k_scale / v_scale [n_kv_heads][max_seq_len] are in / out:
- * rows 0..pos-1 are read, row `pos` comes back as the launch quantized and stored k_new / v_new [n_kv_heads][head_dim]. */
+ * rows 0..pos-1 are read, row `pos` comes back as the launch quantized and stored k_new / v_new [n_kv_heads][head_dim].
+ * There is no path argument, the shape picks the kernel: one with split kernels (head_dim 64 / 128; 1, 2, 4 or 8 query heads per kv head)
+ * runs lgh::attn_partial_q8_kernel + merge; any other group size up to 16 at head_dim 64 / 128 runs lgh::attn_group_kv8_kernel + merge, as
+ * a context with LGH_ATTN_GROUP_MATRIX does (4 or 8 waves from max_seq_len); anything else answers LGH_UNSUPPORTED. */
 int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int8_t* k_bytes, int8_t* v_bytes, float* k_scale, float* v_scale,
                          const float* k_new, const float* v_new, float* out, size_t n_heads, size_t n_kv_heads, size_t head_dim,
                          size_t max_seq_len, float scale, size_t pos, int n_splits, uint8_t* image_out);

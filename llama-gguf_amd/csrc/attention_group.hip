@@ -17,16 +17,11 @@
 // for the load and its score masked to kNegBig in the update, so nothing stored past the context is ever read.  The next tile's K and V
 // fragments are requested before the current tile's matrix work begins.  The waves merge through LDS (expf, as AttnBlockCore::merge) and
 // the workgroup leaves one unnormalised (m, l, acc) partial per real head in the layout attn_store_partial / attn_combine_splits read;
-// attn_combine_kernel (attention.hip) merges the splits unchanged and leaves wo's XQ image.
-#include "attn_split.h"
+// attn_combine_kernel (attention.hip) merges the splits unchanged and leaves wo's XQ image.  The softmax update and the tail are
+// attn_group.h's, shared with the byte caches' kernel (attention_group_kv8.hip).
+#include "attn_group.h"
 
 namespace lgh {
-
-template <int D, int NW>
-struct AttnGroupLds {
-  static constexpr int DP = D + 4;   // padded row of the merge buffer
-  static constexpr size_t kBytes = (size_t)(NW * 16 * DP + 2 * NW * 16) * 4;   // s_o [NW][16][DP], s_m, s_l [NW][16]
-};
 
 template <int D, int NW>
 __global__ void __launch_bounds__(NW * 64) attn_group_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc,
@@ -34,11 +29,7 @@ __global__ void __launch_bounds__(NW * 64) attn_group_kernel(const float* __rest
                                                              uint32_t n_splits, float* __restrict__ part_ml, float* __restrict__ part_acc) {
   constexpr int DJ = D / 4;    // contraction steps of S^T (dims per lane group)
   constexpr int DQ = D / 16;   // output dims per M index
-  constexpr int DP = AttnGroupLds<D, NW>::DP;
   extern __shared__ __attribute__((aligned(16))) float grp_lds[];
-  float (*s_o)[16][DP] = reinterpret_cast<float (*)[16][DP]>(grp_lds);
-  float (*s_m)[16] = reinterpret_cast<float (*)[16]>(grp_lds + NW * 16 * DP);
-  float (*s_l)[16] = s_m + NW;
 
   const uint32_t kvh = blockIdx.x / n_splits, sp = blockIdx.x % n_splits;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
@@ -94,62 +85,15 @@ __global__ void __launch_bounds__(NW * 64) attn_group_kernel(const float* __rest
     f32x4 st = (f32x4)(0.0f);
 #pragma unroll
     for (int j = 0; j < DJ; j++) st = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[j / 4][j % 4], qf[j], st, 0, 0, 0);
-    // the tile enters the online softmax of head column n: st[i] = <q(head n), k(row kv0 + 4c + i)>, unscaled (AttnBlockCore::update
-    // without the causal term: every head sees rows < kv_len)
-    const uint32_t kv0 = tile * 16;
-    float sv[4], pv[4], mx = kNegBig;
-    bool ok[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      ok[i] = kv0 + 4 * c + i < kv_len;
-      sv[i] = ok[i] ? st[i] * scale : kNegBig;
-      mx = fmaxf(mx, sv[i]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mn = fmaxf(m_run, mx);
-    const float alpha = __expf(m_run - mn);
-    float ps = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { pv[i] = ok[i] ? __expf(sv[i] - mn) : 0.0f; ps += pv[i]; }
-    ps += __shfl_xor(ps, 16, 64);
-    ps += __shfl_xor(ps, 32, 64);
-    l_run = __builtin_fmaf(l_run, alpha, ps);
-    m_run = mn;
-#pragma unroll
-    for (int x = 0; x < DQ; x++) acc[x] = acc[x] * alpha;
+    float pv[4];
+    attn_group_update<DQ>(st, tile * 16, c, kv_len, scale, m_run, l_run, acc, pv);
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
       for (int x = 0; x < DQ; x++) acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[i][x / 4][x % 4], pv[i], acc[x], 0, 0, 0);
   }
 
-  // the wave's (m, l, acc) -> LDS (a wave without a tile leaves kNegBig, 0, 0: weight 0 in every merge that has a real row)
-  if (c == 0) { s_m[wave][n] = m_run; s_l[wave][n] = l_run; }
-#pragma unroll
-  for (int x = 0; x < DQ; x++) {
-    s_o[wave][n][DQ * (4 * c + 0) + x] = acc[x].x;
-    s_o[wave][n][DQ * (4 * c + 1) + x] = acc[x].y;
-    s_o[wave][n][DQ * (4 * c + 2) + x] = acc[x].z;
-    s_o[wave][n][DQ * (4 * c + 3) + x] = acc[x].w;
-  }
-  __syncthreads();
-  // the NW states merged, wave 0 first; thread t takes output elements t, t + 64 NW, ... of the real heads
-  const size_t pbase = ((size_t)kvh * n_splits + sp) * g_per_kv;
-  for (uint32_t e = threadIdx.x; e < g_per_kv * D; e += NW * 64) {
-    const uint32_t g = e / D, dim = e % D;
-    float mn = s_m[0][g];
-#pragma unroll
-    for (int w = 1; w < NW; w++) mn = fmaxf(mn, s_m[w][g]);
-    float lsum = 0.0f, a = 0.0f;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-      const float f = expf(s_m[w][g] - mn);
-      lsum += s_l[w][g] * f;
-      a += s_o[w][g][dim] * f;
-    }
-    attn_store_partial<D>(part_ml, part_acc, pbase + g, dim, mn, lsum, a);
-  }
+  attn_group_merge_store<D, NW>(grp_lds, wave, n, c, m_run, l_run, acc, g_per_kv, ((size_t)kvh * n_splits + sp) * g_per_kv, part_ml, part_acc);
 }
 
 template <int D, int NW>
@@ -164,12 +108,14 @@ static hipError_t attn_group_go(const KvLayout& l, const KvCache& kv, const Attn
 
 bool attn_group_covers(uint32_t head_dim, uint32_t group) { return (head_dim == 64 || head_dim == 128) && group >= 1 && group <= 16; }
 
-// The partial launch of a split step on the group kernel: the context's own f32 cache, the position from the device word.  The wave
-// count follows the cache capacity as the split kernels' does (attn_f32_dispatch): 4 waves below 2048 rows, 8 from there
+// The partial launch of a split step on the group kernels: the context's own cache, f32 here or int8 / FP8 (attention_group_kv8.hip:
+// the launch also quantizes and stores the current token's rows, a.kv_new), the position from the device word.  The wave count follows
+// the cache capacity as the split kernels' does (attn_f32_dispatch): 4 waves below 2048 rows, 8 from there
 hipError_t attn_group_launch(const KvLayout& l, const KvCache& kv, const AttnDecode& a) {
-  if (!l.f32() || l.n_kv == 0 || a.n_heads % l.n_kv || !attn_group_covers(l.d, a.n_heads / l.n_kv) || !a.pos || a.n_seq || a.n_splits < 1 ||
+  if (l.tq() || l.n_kv == 0 || a.n_heads % l.n_kv || !attn_group_covers(l.d, a.n_heads / l.n_kv) || !a.pos || a.n_seq || a.n_splits < 1 ||
       a.n_splits > 32 || !a.part_ml || !a.part_acc)
     return hipErrorInvalidValue;
+  if (l.staged()) return attn_group_kv8_launch(l, kv, a);
   const bool long_ctx = l.max_seq >= 2048;
   if (l.d == 128) return long_ctx ? attn_group_go<128, 8>(l, kv, a) : attn_group_go<128, 4>(l, kv, a);
   return long_ctx ? attn_group_go<64, 8>(l, kv, a) : attn_group_go<64, 4>(l, kv, a);

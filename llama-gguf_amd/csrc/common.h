@@ -340,8 +340,9 @@ constexpr uint32_t kAttnHeadMaxRows = 16384;
 hipError_t attn_head_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
                             uint32_t max_seq, float scale, const int* pos, uint32_t max_rows, float* out, uint8_t* xq_out, hipStream_t st);
 bool attn_shape_has_fast_kernel(uint32_t head_dim, uint32_t group);
-// attention_group.hip: the partial launch of a split step for any group size 1 .. 16 at head_dim 64 / 128 (f32 cache, the context's own
-// sequence; attn_merge_launch merges its partials), and the shapes it covers
+// attention_group.hip, attention_group_kv8.hip: the partial launch of a split step for any group size 1 .. 16 at head_dim 64 / 128 (an
+// f32, int8 or FP8 cache, the context's own sequence; the byte launch also quantizes and stores the rows of a.kv_new;
+// attn_merge_launch merges its partials), and the shapes it covers
 bool attn_group_covers(uint32_t head_dim, uint32_t group);
 hipError_t attn_group_launch(const KvLayout& l, const KvCache& kv, const AttnDecode& a);
 // one row through a byte KV format (lgh_model_desc.kv_cache_type 1..3) and back

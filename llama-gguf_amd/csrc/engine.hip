@@ -146,9 +146,10 @@ static int desc_normalize(const lgh_model_desc* desc, lgh_model_desc& d) {
   return LGH_OK;
 }
 
-// LGH_ATTN_GROUP_MATRIX takes effect: an f32 cache, a group size without split kernels that attn_group_kernel covers
+// LGH_ATTN_GROUP_MATRIX takes effect: an f32, int8 or FP8 cache (no TurboQuant one), a group size without split kernels that the group
+// kernels cover (attn_group_kernel, attn_group_kv8_kernel)
 bool attn_group_in_effect(const lgh_model_desc& d) {
-  if (!(d.attn_policy & LGH_ATTN_GROUP_MATRIX) || desc_kv_type(d) != LGH_KV_F32 || !d.num_kv_heads || d.num_heads % d.num_kv_heads) return false;
+  if (!(d.attn_policy & LGH_ATTN_GROUP_MATRIX) || desc_kv_type(d) > LGH_KV_FP8_E5M2 || !d.num_kv_heads || d.num_heads % d.num_kv_heads) return false;
   const uint32_t g = d.num_heads / d.num_kv_heads;
   return !attn_shape_has_fast_kernel(d.head_dim, g) && attn_group_covers(d.head_dim, g);
 }
@@ -172,8 +173,9 @@ int engine_shape_check(const lgh_model_desc& d, std::string& why) {
           "kernel, which holds max_seq_len scores in LDS: max_seq_len must be <= 38400 for it (got " + std::to_string(d.max_seq_len) + ")";
     return LGH_UNSUPPORTED;
   }
-  if (kvl.staged() && !attn_shape_has_fast_kernel(d.head_dim, g)) {
-    why = "the int8 KV cache runs on the split attention kernels (head_dim 64 / 128; 1, 2, 4 or 8 query heads per kv head) of the default decode path";
+  if (kvl.staged() && !attn_shape_has_fast_kernel(d.head_dim, g) && !attn_group_in_effect(d)) {
+    why = "a quantized KV cache runs on the split attention kernels (head_dim 64 / 128; 1, 2, 4 or 8 query heads per kv head); an int8 / FP8 "
+          "cache also on the group kernel, for up to 16 query heads per kv head at head_dim 64 / 128, when attn_policy has LGH_ATTN_GROUP_MATRIX";
     return LGH_UNSUPPORTED;
   }
   if (kvl.tq() && (d.head_dim != 64 && d.head_dim != 128)) {

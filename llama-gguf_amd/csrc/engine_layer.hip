@@ -226,7 +226,7 @@ static int attention_step(lgh_ctx* c, uint32_t li, const AttnStep& s, float scal
     if (kvl.tq()) { const TqLayer t = tq_layer(c, li); a.signs = t.signs; a.qjl_s = t.qjl_s; }
     a.out = s.out;
     a.st = c->stream;
-    if (c->attn_group)   // LGH_ATTN_GROUP_MATRIX in effect (own sequence, f32 cache): the group kernel's partials, the same merge
+    if (c->attn_group)   // LGH_ATTN_GROUP_MATRIX in effect (own sequence; f32, int8 or FP8 cache): the group kernels' partials, the same merge
       rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN_GROUP, kv_bytes, [&] { return attn_group_launch(kvl, s.kv, a); });
     else
       rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] { return attn_split_launch(kvl, s.kv, a); });

@@ -31,8 +31,9 @@ bool pf_eligible(const lgh_ctx* c, bool slot) {
   const uint32_t QD = d.num_heads * d.head_dim, KD = d.num_kv_heads * d.head_dim, g = d.num_heads / d.num_kv_heads;
   if (d.hidden_size % 256 || d.hidden_size > 2048u * kPfSsqChunks || QD % 256 || KD % 16) return false;
   // (c->attn_group: the block attention's matrix-core kernel takes the group size at run time, and such a context decodes on split
-  // partials like the four group sizes of the split kernels)
-  if ((d.head_dim != 64 && d.head_dim != 128) || (g != 1 && g != 2 && g != 4 && g != 8 && !c->attn_group)) return false;
+  // partials like the four group sizes of the split kernels.  Over the f32 cache only: the byte caches' block attention and its tests
+  // stop at the four group sizes, so a byte-cache context of any other takes its prompts token by token whatever the policy says)
+  if ((d.head_dim != 64 && d.head_dim != 128) || (g != 1 && g != 2 && g != 4 && g != 8 && !(c->attn_group && c->kvl.f32()))) return false;
   for (uint32_t i = c->l0; i < c->l1; i++) {
     const LayerW& L = c->layers[i];
     for (const DevWeight* W : {&L.wq, &L.wk, &L.wv, &L.wo})

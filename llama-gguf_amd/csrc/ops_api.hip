@@ -678,11 +678,15 @@ int lgh_op_attention_kv8(int device, uint32_t kv_cache_type, const float* q, int
   const bool i8 = kv_cache_type == LGH_KV_INT8;
   if (!q || !k_bytes || !v_bytes || !k_new || !v_new || !out || (i8 && (!k_scale || !v_scale))) return LGH_INVALID_ARGUMENT;
   if (n_kv == 0 || n_heads % n_kv || pos >= max_seq || max_seq > 0x7FFFFFFFu || n_splits < 1 || n_splits > 32) return LGH_INVALID_ARGUMENT;
-  if (!attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)(n_heads / n_kv))) return LGH_UNSUPPORTED;
+  // a shape with a split kernel runs it; any other the group kernel covers runs that, as a context with LGH_ATTN_GROUP_MATRIX does
+  const size_t g = n_heads / n_kv;
+  const bool fast = attn_shape_has_fast_kernel((uint32_t)head_dim, (uint32_t)g);
+  if (!fast && (g > 16 || !attn_group_covers((uint32_t)head_dim, (uint32_t)g))) return LGH_UNSUPPORTED;
   const AttnView v{nullptr, t.up(q, n_heads * head_dim), up_kv_new(t, k_new, v_new, n_kv * head_dim), t.up(nullptr, n_heads * head_dim)};
   if (!v.q || !v.kv_tmp || !v.attn_out) return LGH_ALLOCATION_FAILED;
   int rc;
   if ((rc = attn_setup(t, kv_cache_type, n_heads, n_kv, head_dim, max_seq, n_splits)) || (rc = set_pos(t, pos))) return rc;
+  t.c->attn_group = !fast;
   void* const caches[KV_KINDS] = {k_bytes, v_bytes, k_scale, v_scale};
   return attn_run(t, v, caches, caches, scale, out, image_out);
 }

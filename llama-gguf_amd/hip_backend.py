@@ -72,8 +72,9 @@ WEIGHTS_LEGACY_TILES = 8    # ... Q4_1 / Q5_0 / Q5_1 matrices stay quantized in 
 WEIGHTS_HALF_TILES = 4      # ... F16 / BF16 matrices stay 16-bit in HBM (8192-B tiles, their own decode mat-vec); bit 1 is not assigned
 PREFILL_BATCH_BYTE_KV = 1   # lgh_set_prefill_policy: int8 / FP8 caches take the batched prompt pass (own sequence, slots, stage contexts)
 PREFILL_BATCH_TQ_QJL = 4    # ... tq2-qjl / tq3-qjl caches take it (own sequence, as tq2 / tq3); bit 1 is not assigned
-ATTN_GROUP_MATRIX = 1       # lgh_model_desc.attn_policy: f32-cache contexts whose group size has no split kernel (3, 5, 6, 7 .. 16 heads per kv head)
-                            # decode on attn_group_kernel + merge and take the batched prompt pass
+ATTN_GROUP_MATRIX = 1       # lgh_model_desc.attn_policy: contexts whose group size has no split kernel (3, 5, 6, 7 .. 16 heads per kv head) decode on
+                            # attn_group_kernel + merge; f32 caches also take the batched prompt pass, int8 / FP8 caches (attn_group_kv8_kernel)
+                            # exist for these shapes only with the bit and take their prompts token by token
 FLAG_EXACT_PREFILL = 4   # forward_batch feeds tokens one by one (f32 throughout) instead of the batched f16 GEMM path
 KV_F32, KV_INT8, KV_FP8_E4M3, KV_FP8_E5M2 = 0, 1, 2, 3   # lgh_model_desc.kv_cache_type: f32, or QuantizedKVCache's formats (kv_quantized.rs; no CLI flag reaches them)
 KV_TQ2, KV_TQ3 = 4, 5   # KVCacheType::TurboQuantMSE { bits: 2 | 3 }: what `--kv-cache-type tq2 | tq3` selects (src/config.rs:808-817)
@@ -1658,7 +1659,8 @@ def op_pf_moe(type_gate_up: int, w_gate, w_up, type_down: int, w_down, router, n
 def op_attention_kv8(kv_cache_type: int, q, k_bytes, v_bytes, k_scale, v_scale, k_new, v_new, scale: float, pos: int, n_splits: int = 8,
                      device: int = 0, *, image: bool = False):
     """One decode step's attention over an int8 / FP8 cache (KV_INT8 / KV_FP8_E4M3 / KV_FP8_E5M2): bytes [nkv, max_seq, d] (uint8 or
-    int8), scales [nkv, max_seq] (int8 only, else None); the launch stores k_new / v_new [nkv, d] at row `pos`.
+    int8), scales [nkv, max_seq] (int8 only, else None); the launch stores k_new / v_new [nkv, d] at row `pos`.  The shape picks the
+    kernel: 1, 2, 4 or 8 heads per kv head the split kernel, any other group size up to 16 attn_group_kv8_kernel (d 64 / 128).
     -> (out [nh, d], k_bytes, v_bytes, k_scale, v_scale) after the call (copies; the inputs are untouched); image: and the XQ image of
     out (op_attention_decode) as a last element."""
     q, kn, vn = _f32(q), _f32(k_new), _f32(v_new)
