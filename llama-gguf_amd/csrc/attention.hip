@@ -152,6 +152,10 @@ __global__ void __launch_bounds__(NW * 64) attn_partial_kernel(const float* __re
 // counted waits in front of their uses exact); a row past the end has no score stored and p = 0, so nothing of it reaches the result.
 // cap_rows (a multiple of 128): the rows the LDS arrays hold.  A position past it would be attended to as cap_rows rows (the clamp
 // below keeps every LDS index inside the arrays); no caller lets it happen: attention_forward refuses such a position on the host.
+// Who runs it: a context whose single-launch threshold is above 256 rows (flag bits 16..23 above 4) and lgh_op_attention_decode path 3
+// over a cache of more than 256 rows.  Where no context of the launch passes 256 rows — the default engine — attention_step launches
+// attn_slice_kernel (attention_slice.hip) instead: this kernel's passes 1 and 2 repeated by S workgroups per query head, each with a
+// slice of the output's columns and of V, and this kernel's summation tree per column, so the same bits.
 // ------------------------------------------------------------------------------------------------
 template <int D, int G>
 __global__ void __launch_bounds__(1024) attn_head_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ vc,

@@ -339,6 +339,11 @@ hipError_t attn_direct_launch(const float* q, const float* kcache, const float* 
 constexpr uint32_t kAttnHeadMaxRows = 16384;
 hipError_t attn_head_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
                             uint32_t max_seq, float scale, const int* pos, uint32_t max_rows, float* out, uint8_t* xq_out, hipStream_t st);
+// the same bits from S workgroups per query head, each over a slice of the output's columns (attention_slice.hip: attn_slice_kernel), for
+// contexts of at most kAttnSliceMaxRows rows: min(max_rows, max_seq) must not exceed it
+constexpr uint32_t kAttnSliceMaxRows = 256;
+hipError_t attn_slice_launch(const float* q, const float* kcache, const float* vcache, uint32_t n_heads, uint32_t n_kv, uint32_t head_dim,
+                             uint32_t max_seq, float scale, const int* pos, uint32_t max_rows, float* out, uint8_t* xq_out, hipStream_t st);
 bool attn_shape_has_fast_kernel(uint32_t head_dim, uint32_t group);
 // attention_group.hip, attention_group_kv8.hip: the partial launch of a split step for any group size 1 .. 16 at head_dim 64 / 128 (an
 // f32, int8 or FP8 cache, the context's own sequence; the byte launch also quantizes and stores the rows of a.kv_new;

@@ -26,9 +26,13 @@
 
 using namespace lgh;
 
-// Contexts up to this many rows run the single-launch decode attention (attention.hip: attn_head_kernel, one workgroup per
-// query head) unless the flags say otherwise: the largest multiple of 64 rows at which it beats split + combine by more than
-// the run-to-run spread.  Measured on Llama-3-8B Q4_K_M (profiles/r06_attn_head.md): 743 vs 694 tokens/s at kv 65..128,
+// Contexts up to this many rows run the single-launch decode attention unless the flags say otherwise: the largest multiple of 64
+// rows at which attn_head_kernel (attention.hip, one workgroup per query head) beats split + combine by more than the run-to-run
+// spread.  Which kernel is the single launch follows the threshold in effect (engine_layer.hip: attention_step): up to
+// kAttnSliceMaxRows = 256 rows — this default, and flag values 1..4 — attn_slice_kernel (attention_slice.hip: four workgroups per query
+// head over slices of the output's columns, the same bits, 1.0 us per layer shorter at 200 rows: profiles/attn_slice.md); a larger
+// threshold (flag values above 4) attn_head_kernel at every position.  The switch itself was measured with attn_head_kernel on
+// Llama-3-8B Q4_K_M (profiles/r06_attn_head.md): 743 vs 694 tokens/s at kv 65..128,
 // 730 vs 693 at 129..192, 718 vs 692 at 193..256, 685 vs 685 at 257..320, 668 vs 683 at 321..384.  (The kernel it replaced
 // here, one workgroup per KV head with an online softmax per row, lost from 128 rows on: it was bound by vector issue, about
 // 16 vector instructions per row and head and merges full of exponentials, not by one CU's memory path as this comment said.)

@@ -204,9 +204,12 @@ static int attention_step(lgh_ctx* c, uint32_t li, const AttnStep& s, float scal
       return fail(c, LGH_INVALID_ARGUMENT, "single-launch attention at position " + std::to_string(c->pos) + " past its " +
                                                std::to_string(c->direct_attn_max_kv) + " rows");
     qa = attn_image(c, s, xq_out);
+    // ... or, where no context of this launch passes kAttnSliceMaxRows rows, several per query head over slices of the output's columns: the
+    // same bits.  By the threshold, not the position: a captured graph is replayed at every position up to the threshold
+    const auto launch = c->direct_attn_max_kv <= kAttnSliceMaxRows ? attn_slice_launch : attn_head_launch;
     rc = run_k(c, LGH_K_ATTN, LGH_SYM_ATTN, kv_bytes, [&] {
-      return attn_head_launch(s.q, s.kv.k_f32(), s.kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, s.pos, c->direct_attn_max_kv,
-                              s.out, qa ? qa->xq : nullptr, c->stream);
+      return launch(s.q, s.kv.k_f32(), s.kv.v_f32(), d.num_heads, d.num_kv_heads, d.head_dim, d.max_seq_len, scale, s.pos, c->direct_attn_max_kv, s.out,
+                    qa ? qa->xq : nullptr, c->stream);
     });
   } else if (one_launch && c->attn_direct == ATTN_VAR_DIRECT) {   // one launch, a workgroup per kv head
     qa = attn_image(c, s, xq_out);
