@@ -53,7 +53,8 @@ typedef enum lgh_status {
 typedef enum lgh_ggml_type {
   LGH_TYPE_F32 = 0, LGH_TYPE_F16 = 1, LGH_TYPE_Q4_0 = 2, LGH_TYPE_Q4_1 = 3, LGH_TYPE_Q5_0 = 6,
   LGH_TYPE_Q5_1 = 7, LGH_TYPE_Q8_0 = 8, LGH_TYPE_Q8_1 = 9, LGH_TYPE_Q2_K = 10, LGH_TYPE_Q3_K = 11,
-  LGH_TYPE_Q4_K = 12, LGH_TYPE_Q5_K = 13, LGH_TYPE_Q6_K = 14, LGH_TYPE_Q8_K = 15, LGH_TYPE_BF16 = 30
+  LGH_TYPE_Q4_K = 12, LGH_TYPE_Q5_K = 13, LGH_TYPE_Q6_K = 14, LGH_TYPE_Q8_K = 15, LGH_TYPE_IQ4_NL = 20,
+  LGH_TYPE_IQ4_XS = 23, LGH_TYPE_BF16 = 30
 } lgh_ggml_type;
 
 /* What GpuOnlyInference::from_model reads out of ModelConfig and the per-layer Attention scalars
@@ -167,7 +168,7 @@ enum {
  * LGH_SYM_MV_* are the instantiations of lgh::mv_kernel<MASK, MAXT> (the VALU dequant mat-vec, csrc/matvec.hip; MASK bits:
  * Q4_K 1, Q5_K 2, Q6_K 4, Q8_0 8, Q4_0 16; MAXT = the instantiation's thread cap).  LGH_SYM_MVQ_* are the instantiations of
  * lgh::mvq_kernel<MASK> (the int8 matrix-core mat-vec, csrc/matvec_mfma.hip; ITS mask bits: Q4_K 1, Q6_K 2, Q5_K 4, Q8_0 8,
- * Q4_0 16, Q3_K 32, Q2_K 64, Q4_1 128, Q5_0 256, Q5_1 512). */
+ * Q4_0 16, Q3_K 32, Q2_K 64, Q4_1 128, Q5_0 256, Q5_1 512, IQ4_NL 1024, IQ4_XS 2048). */
 enum {
   LGH_SYM_MV_Q4K = 0,      /* lgh::mv_kernel<1u, 1024>  : every matrix of the launch Q4_K */
   LGH_SYM_MV_Q80 = 1,      /* lgh::mv_kernel<8u, 1024>  : Q8_0 */
@@ -196,7 +197,8 @@ enum {
   LGH_SYM_MVQ_LEGACY = 24, /* lgh::mvq_legacy_kernel<128u> / <256u> / <512u> : Q4_1 / Q5_0 / Q5_1 (contexts with LGH_WEIGHTS_LEGACY_TILES) */
   LGH_SYM_ATTN_GROUP = 25, /* lgh::attn_group_kernel<D, NW>, over a byte cache lgh::attn_group_kv8_kernel<D, NW, FMT> : decode attention of any
                               group size up to 16 (contexts with LGH_ATTN_GROUP_MATRIX) */
-  LGH_SYM_COUNT = 26       /* = the last entry + 1: a new symbol is appended and bumps this, and SYM_NAMES of hip_backend.py follows by hand */
+  LGH_SYM_MVQ_IQ4 = 26,    /* lgh::mvq_iq4_kernel<1024u> / <2048u> : IQ4_NL / IQ4_XS (contexts with LGH_WEIGHTS_IQ4_TILES) */
+  LGH_SYM_COUNT = 27       /* = the last entry + 1: a new symbol is appended and bumps this, and SYM_NAMES of hip_backend.py follows by hand */
 };
 
 typedef struct lgh_stats {
@@ -326,10 +328,25 @@ int lgh_set_prefill_policy(lgh_ctx* ctx, uint32_t policy);
  *     kernels' bound, |delta| <= 1e-4 * sum|x_i * w_i| + 1e-6, not the f32 mat-vec's bits; the prompt pass under its standing |w| < 256
  *     and, for the additive minimum of Q4_1 / Q5_1, 256 * |m| <= 65504.  lgh_stats.weight_bytes counts the native GGUF bytes.  A launch
  *     that mixes one of the three with another format (a Q6_K output projection, say) goes out as one launch per matrix.
+ *   LGH_WEIGHTS_IQ4_TILES  (bit 4, value 16; combines freely with bits 0, 2 and 3)  IQ4_NL and IQ4_XS matrices and expert stacks
+ *     (k % 256 == 0) stay quantized in HBM, in 16-row tile layouts of 2304 / 2176 B per 256 elements — the native bytes of 16 rows
+ *     (csrc/matvec_mfma.hip; IQ4_NL's tile is Q4_0's) — and take the kernels of the other tile formats: the decode mat-vec, the
+ *     multi-sequence mat-vecs (lgh_forward_multi, bit-identical per sequence to lgh_forward; LGH_BATCH_F32_MATRIX applies) and the
+ *     batched prompt pass, for which lgh_prefill_is_batched then answers 1.  The 16 codebook values are signed int8, so a nibble is
+ *     decoded in registers (two byte permutes and a bit select per four weights) straight into the matrix cores' int8 operand.  Same
+ *     dequantized weights times x (d * kv[q], d * (ls - 32) * kv[q]: iq_quants.rs:14-99) as the f32 expansion within the tile kernels'
+ *     bound, |delta| <= 1e-4 * sum|x_i * w_i| + 1e-6, not the f32 mat-vec's bits; the prompt pass under its standing |w| < 256.
+ *     lgh_stats.weight_bytes counts the native GGUF bytes.  A launch that mixes one of the two with another format goes out as one
+ *     launch per matrix.  Without the bit both types follow the default rule: expanded to f32 at upload (exactly: both products fit
+ *     f32) and multiplied by the f32 mat-vec.  No forward path of the reference reaches either type: it defines the block formats and
+ *     their dequantization only (blocks.rs:265-290, iq_quants.rs:14-99).  Measured on Llama-3-8B shapes: decode 1.60 / 1.65 ms per
+ *     token against 6.65 expanded, the 128-token prompt 4.97 / 5.03 ms against 801; IQ4_NL is 14 % behind Q4_0 at the same bytes — the
+ *     lookup costs vector issue that HBM streaming does not hide; per-kernel times were not taken.
  * Out of scope: the handles that create their contexts themselves — lgh_tp_*, lgh_pipeline_*, lgh_load_gguf — keep the default, and
- * so do the other expanded types (Q8_1, Q8_K) and any matrix with k % 256 != 0, whatever the word says.  measured:
- * profiles/lowbit_weights.md, profiles/half_weights.md, profiles/legacy_weights.md */
-enum { LGH_WEIGHTS_DEFAULT = 0, LGH_WEIGHTS_LOWBIT_TILES = 1u << 0, LGH_WEIGHTS_HALF_TILES = 1u << 2, LGH_WEIGHTS_LEGACY_TILES = 1u << 3 };
+ * so do the other expanded types (Q8_1, Q8_K), the other IQ types (not loadable) and any matrix with k % 256 != 0, whatever the word
+ * says.  measured: profiles/lowbit_weights.md, profiles/half_weights.md, profiles/legacy_weights.md, profiles/iq4_weights.md */
+enum { LGH_WEIGHTS_DEFAULT = 0, LGH_WEIGHTS_LOWBIT_TILES = 1u << 0, LGH_WEIGHTS_HALF_TILES = 1u << 2, LGH_WEIGHTS_LEGACY_TILES = 1u << 3,
+       LGH_WEIGHTS_IQ4_TILES = 1u << 4 };
 int lgh_set_weight_policy(lgh_ctx* ctx, uint32_t policy);
 /* GpuInference::reset (gpu_only.rs:808-843) — O(1): only the position is rewound (model/mod.rs:110-117) */
 void lgh_reset(lgh_ctx* ctx);
@@ -684,7 +701,8 @@ int lgh_op_mat_mat(int device, uint32_t type, const void* w, const float* x, flo
  * with LGH_WEIGHTS_LOWBIT_TILES a Q3_K / Q2_K matrix runs from its tile layout (and lgh_op_mat_mat_ex takes those two types as well);
  * with LGH_WEIGHTS_HALF_TILES an F16 / BF16 matrix runs from its 16-bit tiles in both (without the bit lgh_op_mat_mat_ex answers Unsupported
  * for the two types, as ever); with LGH_WEIGHTS_LEGACY_TILES a Q4_1 / Q5_0 / Q5_1 matrix runs from its tile layout in both (without the
- * bit lgh_op_mat_mat_ex answers Unsupported for the three).
+ * bit lgh_op_mat_mat_ex answers Unsupported for the three); with LGH_WEIGHTS_IQ4_TILES an IQ4_NL / IQ4_XS matrix likewise (without the bit
+ * Unsupported for the two).
  * Policy 0 is the plain entry point, bit for bit.  *device_bytes (optional): the bytes the matrix occupies on the device — rows padded
  * to 16 times the tile layout's bytes per row, or 4 * n * k where it was expanded to f32 — which tells the layout it ran from. */
 int lgh_op_vec_mat_ex(int device, uint32_t ggml_type, const void* w, const float* x, const float* norm_w, float eps, float* out, size_t k,

@@ -32,7 +32,7 @@ size_t lgs_tensor_nbytes(uint32_t ggml_type, uint64_t n_elems);
  *   kind        : 0 = linear weight, 1 = norm weight (1 + 0.01*u, F32 only), 2 = bias (0.01*u, F32 only)
  *   seed        : global seed, mixed with fnv1a(name)
  *   threads     : worker threads (<=0: all cores)
- * Supported types: F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K.
+ * Supported types: F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS.
  * Returns 0 on success, 1 on bad arguments. */
 int lgs_fill_tensor(const char* name, uint32_t ggml_type, uint64_t n_elems, uint64_t in_features, int kind,
                     uint64_t seed, void* out, size_t nbytes, int threads);

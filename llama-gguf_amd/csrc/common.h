@@ -25,9 +25,9 @@ __host__ __device__ inline uint32_t blk_elems(int t) {
   switch (t) {
     case LGH_TYPE_F32: case LGH_TYPE_F16: case LGH_TYPE_BF16: return 1;
     case LGH_TYPE_Q4_0: case LGH_TYPE_Q4_1: case LGH_TYPE_Q5_0: case LGH_TYPE_Q5_1: case LGH_TYPE_Q8_0:
-    case LGH_TYPE_Q8_1: return 32;
+    case LGH_TYPE_Q8_1: case LGH_TYPE_IQ4_NL: return 32;
     case LGH_TYPE_Q2_K: case LGH_TYPE_Q3_K: case LGH_TYPE_Q4_K: case LGH_TYPE_Q5_K: case LGH_TYPE_Q6_K:
-    case LGH_TYPE_Q8_K: return 256;
+    case LGH_TYPE_Q8_K: case LGH_TYPE_IQ4_XS: return 256;
     default: return 0;
   }
 }
@@ -39,6 +39,7 @@ __host__ __device__ inline uint32_t blk_bytes(int t) {
     case LGH_TYPE_Q5_1: return 24; case LGH_TYPE_Q8_0: return 34; case LGH_TYPE_Q8_1: return 36;
     case LGH_TYPE_Q2_K: return 84; case LGH_TYPE_Q3_K: return 110; case LGH_TYPE_Q4_K: return 144;
     case LGH_TYPE_Q5_K: return 176; case LGH_TYPE_Q6_K: return 210; case LGH_TYPE_Q8_K: return 292;
+    case LGH_TYPE_IQ4_NL: return 18; case LGH_TYPE_IQ4_XS: return 136;
     default: return 0;
   }
 }
@@ -49,6 +50,8 @@ constexpr int kDevQ5K_T16 = 1013, kDevQ80_T16 = 1008, kDevQ40_T16 = 1002;   // Q
 constexpr int kDevQ3K_T16 = 1011, kDevQ2K_T16 = 1010;   // Q3_K (1824 B), Q2_K (1344 B) tiles: contexts with LGH_WEIGHTS_LOWBIT_TILES only
 // Q4_1 (2560 B), Q5_0 (2816 B), Q5_1 (3072 B) tiles: contexts with LGH_WEIGHTS_LEGACY_TILES only
 constexpr int kDevQ41_T16 = 1003, kDevQ50_T16 = 1006, kDevQ51_T16 = 1007;
+// IQ4_NL (2304 B, Q4_0's tile), IQ4_XS (2176 B) tiles: contexts with LGH_WEIGHTS_IQ4_TILES only
+constexpr int kDevIQ4NL_T16 = 1020, kDevIQ4XS_T16 = 1023;
 // F16 / BF16 kept 16-bit, in 8192-B tiles (matvec_h16.hip): contexts with LGH_WEIGHTS_HALF_TILES only.  Not mfma_type: their decode
 // mat-vec reads f32 x, not XQ records
 constexpr int kDevF16_T16 = 1001, kDevBF16_T16 = 1030;
@@ -59,7 +62,7 @@ constexpr uint32_t kMvhMaxStagedFloats = 32768;
 inline bool half_tiles_fit(uint32_t k, uint32_t n_stack) { return (uint64_t)k * (n_stack > 1 ? 2 : 1) <= kMvhMaxStagedFloats; }
 inline bool mfma_type(int t) {
   return t == kDevQ4K_T16 || t == kDevQ6K_T16 || t == kDevQ5K_T16 || t == kDevQ80_T16 || t == kDevQ40_T16 || t == kDevQ3K_T16 || t == kDevQ2K_T16 ||
-         t == kDevQ41_T16 || t == kDevQ50_T16 || t == kDevQ51_T16;
+         t == kDevQ41_T16 || t == kDevQ50_T16 || t == kDevQ51_T16 || t == kDevIQ4NL_T16 || t == kDevIQ4XS_T16;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -76,6 +79,7 @@ inline bool mfma_type(int t) {
 //   F32   plane0 row-major [n][k]
 //   Q3_K / Q2_K  tiles of 1824 / 1344 B for the same kernel, on contexts that asked for them (lgh_set_weight_policy)   plane0
 //   Q4_1 / Q5_0 / Q5_1  tiles of 2560 / 2816 / 3072 B for the same kernel, on contexts that asked for them (LGH_WEIGHTS_LEGACY_TILES)   plane0
+//   IQ4_NL / IQ4_XS  tiles of 2304 / 2176 B for the same kernel, on contexts that asked for them (LGH_WEIGHTS_IQ4_TILES)   plane0
 //   F16 / BF16   tiles of 8192 B (2 B per element) for mvh_kernel (matvec_h16.hip), on contexts that asked for them             plane0
 // Every other GGUF type is dequantized to F32 at upload (the reference does the same for types
 // without a quantized kernel, src/backend/cuda/dequant_weights.rs:211-231).

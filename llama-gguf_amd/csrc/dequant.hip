@@ -34,6 +34,12 @@ __device__ __forceinline__ void k4_scale_min(const uint8_t* s, int j, uint32_t& 
   }
 }
 
+// entry q of the IQ4_NL / IQ4_XS codebook (device_utils.h)
+__device__ __forceinline__ int iq4_value(uint32_t q) {
+  const uint32_t t = q < 4 ? kIq4T0 : q < 8 ? kIq4T1 : q < 12 ? kIq4T2 : kIq4T3;
+  return (int)(int8_t)(t >> (8 * (q & 3)));
+}
+
 // element `i` of the block at `b`
 __device__ float deq_elem(int type, const uint8_t* b, uint32_t i) {
   switch (type) {
@@ -122,6 +128,17 @@ __device__ float deq_elem(int type, const uint8_t* b, uint32_t i) {
       return ldh(b + 208) * sc * (float)q;
     }
     case LGH_TYPE_Q8_K: return (float)(int)(int8_t)b[4 + i] * ldf(b);       // dequant.rs:361-367
+    case LGH_TYPE_IQ4_NL: {  // {d, qs[16]}, iq_quants.rs:66-75
+      uint32_t byte = b[2 + (i & 15)];
+      return ldh(b) * (float)iq4_value(i < 16 ? (byte & 0x0F) : (byte >> 4));
+    }
+    case LGH_TYPE_IQ4_XS: {  // {d, scales_h u16, scales_l[4], qs[128]}, iq_quants.rs:82-99
+      uint32_t ib = i >> 5, w = i & 31;
+      int ls = (int)(((b[4 + (ib >> 1)] >> (4 * (ib & 1))) & 0x0F) | (((ld16u(b + 2) >> (2 * ib)) & 3) << 4));
+      float dl = ldh(b) * (float)(ls - 32);
+      uint32_t byte = b[8 + ib * 16 + (w & 15)];
+      return dl * (float)iq4_value(w < 16 ? (byte & 0x0F) : (byte >> 4));
+    }
     default: return 0.0f;
   }
 }

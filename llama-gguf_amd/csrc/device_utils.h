@@ -42,6 +42,20 @@ __device__ __forceinline__ float ub1(uint32_t v) { return (float)((v >> 8) & 0xF
 __device__ __forceinline__ float ub2(uint32_t v) { return (float)((v >> 16) & 0xFFu); }
 __device__ __forceinline__ float ub3(uint32_t v) { return (float)(v >> 24); }
 
+// The 16-entry codebook of IQ4_NL / IQ4_XS, kv = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}
+// (iq_quants.rs:16-18): signed int8, entries 4i .. 4i+3 in the bytes of T_i.  iq4_decode4 turns four indices 0..15, one per byte of
+// `w`, into their four codebook bytes in registers: two v_perm_b32 pick the byte out of the lower (T0, T1) and the upper (T2, T3) half
+// of the table by the low three index bits, and the fourth bit, spread over its byte, selects between the two (v_bfi_b32).  The
+// constants live in scalar registers; no table in LDS or memory, no loop over bytes.  `bias` is XOR-ed into every table byte at
+// compile time (0x80808080: the entries plus 128 as unsigned bytes).
+constexpr uint32_t kIq4T0 = 0xBFAD9881u, kIq4T1 = 0xF6EADDCFu, kIq4T2 = 0x26190D01u, kIq4T3 = 0x71594535u;
+__device__ __forceinline__ uint32_t iq4_decode4(uint32_t w, uint32_t bias = 0u) {
+  const uint32_t sel = w & 0x07070707u;
+  const uint32_t lo = __builtin_amdgcn_perm(kIq4T1 ^ bias, kIq4T0 ^ bias, sel), hi = __builtin_amdgcn_perm(kIq4T3 ^ bias, kIq4T2 ^ bias, sel);
+  const uint32_t m = ((w >> 3) & 0x01010101u) * 0xFFu;
+  return (lo & ~m) | (hi & m);
+}
+
 // 4 FMAs of the 4 bytes of `v` against x[0..3]
 __device__ __forceinline__ float fma4(uint32_t v, const float* x, float acc) {
   acc = __builtin_fmaf(ub0(v), x[0], acc);

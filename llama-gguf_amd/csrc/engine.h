@@ -216,7 +216,7 @@ int dev_alloc(lgh_ctx* c, void** p, size_t bytes);
 int alloc_zeroed(lgh_ctx* c, const AllocSpec* bufs, size_t count, uint64_t& counter);
 LayoutInfo layout_for(int src_type);
 bool fused_type(int t);
-constexpr uint32_t kWeightPolicyBits = LGH_WEIGHTS_LOWBIT_TILES | LGH_WEIGHTS_HALF_TILES | LGH_WEIGHTS_LEGACY_TILES;   // the bits lgh_set_weight_policy knows (bit 1 is refused)
+constexpr uint32_t kWeightPolicyBits = LGH_WEIGHTS_LOWBIT_TILES | LGH_WEIGHTS_HALF_TILES | LGH_WEIGHTS_LEGACY_TILES | LGH_WEIGHTS_IQ4_TILES;   // the bits lgh_set_weight_policy knows (bit 1 is refused)
 int upload_matrix(lgh_ctx* c, lgh::DevWeight& W, int src_type, uint32_t k, uint32_t n, uint32_t n_stack, int slot,
                   const void* host, size_t nbytes);
 int upload_f32(lgh_ctx* c, float** dst, int src_type, uint64_t n, const void* host, size_t nbytes);

@@ -87,7 +87,9 @@ int upload_matrix(lgh_ctx* c, DevWeight& W, int src_type, uint32_t k, uint32_t n
   const bool half = (c->weight_policy & LGH_WEIGHTS_HALF_TILES) && (src_type == LGH_TYPE_F16 || src_type == LGH_TYPE_BF16) && half_tiles_fit(k, n_stack);
   // ... and Q4_1 / Q5_0 / Q5_1 stay quantized, in tile layouts of their own, on a context with LGH_WEIGHTS_LEGACY_TILES
   const bool legacy = (c->weight_policy & LGH_WEIGHTS_LEGACY_TILES) && (src_type == LGH_TYPE_Q4_1 || src_type == LGH_TYPE_Q5_0 || src_type == LGH_TYPE_Q5_1);
-  const bool t16 = k % 256 == 0 && (half || legacy || src_type == LGH_TYPE_Q4_K || src_type == LGH_TYPE_Q6_K || src_type == LGH_TYPE_Q5_K ||
+  // ... and IQ4_NL / IQ4_XS on a context with LGH_WEIGHTS_IQ4_TILES
+  const bool iq4 = (c->weight_policy & LGH_WEIGHTS_IQ4_TILES) && (src_type == LGH_TYPE_IQ4_NL || src_type == LGH_TYPE_IQ4_XS);
+  const bool t16 = k % 256 == 0 && (half || legacy || iq4 || src_type == LGH_TYPE_Q4_K || src_type == LGH_TYPE_Q6_K || src_type == LGH_TYPE_Q5_K ||
                                     src_type == LGH_TYPE_Q8_0 || src_type == LGH_TYPE_Q4_0 || lowbit);
   if (t16) {
     li.nplanes = 1;
@@ -103,6 +105,8 @@ int upload_matrix(lgh_ctx* c, DevWeight& W, int src_type, uint32_t k, uint32_t n
       case LGH_TYPE_Q4_1: li.dev_type = kDevQ41_T16; li.bpb[0] = 160; break;
       case LGH_TYPE_Q5_0: li.dev_type = kDevQ50_T16; li.bpb[0] = 176; break;
       case LGH_TYPE_Q5_1: li.dev_type = kDevQ51_T16; li.bpb[0] = 192; break;
+      case LGH_TYPE_IQ4_NL: li.dev_type = kDevIQ4NL_T16; li.bpb[0] = 144; break;
+      case LGH_TYPE_IQ4_XS: li.dev_type = kDevIQ4XS_T16; li.bpb[0] = 136; break;
       case LGH_TYPE_F16: li.dev_type = kDevF16_T16; li.bpb[0] = 512; break;
       case LGH_TYPE_BF16: li.dev_type = kDevBF16_T16; li.bpb[0] = 512; break;
       default: li.dev_type = kDevQ40_T16; li.bpb[0] = 144; break;
@@ -368,13 +372,13 @@ int build_mv_group(lgh_ctx* c, const SegSpec* specs, int nseg, const float* norm
 }
 
 static int mvq_symbol(const MvLaunch& L) {
-  bool has[8] = {false, false, false, false, false, false, false, false};
+  bool has[8] = {false, false, false, false, false, false, false, false};   // [7]: IQ4_NL / IQ4_XS
   for (int s = 0; s < L.nseg; s++) {
     const int t = L.seg[s].type;
     has[t == kDevQ4K_T16 ? 0 : t == kDevQ6K_T16 ? 1 : t == kDevQ5K_T16 ? 2 : t == kDevQ80_T16 ? 3 : t == kDevQ40_T16 ? 4
-        : t == kDevQ3K_T16 || t == kDevQ2K_T16 ? 5 : 6] = true;
+        : t == kDevQ3K_T16 || t == kDevQ2K_T16 ? 5 : t == kDevIQ4NL_T16 || t == kDevIQ4XS_T16 ? 7 : 6] = true;
   }
-  return has[6] ? LGH_SYM_MVQ_LEGACY : has[5] ? LGH_SYM_MVQ_Q3K_Q2K : has[2] ? LGH_SYM_MVQ_Q5K : (has[3] || has[4]) ? LGH_SYM_MVQ_Q80_Q40 : (has[0] && has[1]) ? LGH_SYM_MVQ_MIXED
+  return has[7] ? LGH_SYM_MVQ_IQ4 : has[6] ? LGH_SYM_MVQ_LEGACY : has[5] ? LGH_SYM_MVQ_Q3K_Q2K : has[2] ? LGH_SYM_MVQ_Q5K : (has[3] || has[4]) ? LGH_SYM_MVQ_Q80_Q40 : (has[0] && has[1]) ? LGH_SYM_MVQ_MIXED
          : has[1] ? LGH_SYM_MVQ_Q6K : LGH_SYM_MVQ_Q4K;
 }
 
@@ -406,13 +410,14 @@ static int launch_mv_group(lgh_ctx* c, int cls, const SegSpec* specs, int nseg, 
 }
 
 // The formats that have a common instantiation: Q4_K + Q6_K, Q5_K + Q6_K (the "_M" mixes).  Q8_0, Q4_0, Q3_K, Q2_K, Q4_1,
-// Q5_0 and Q5_1 have none: a launch that mixes one of them with anything else goes out as one launch per segment.
+// Q5_0, Q5_1, IQ4_NL and IQ4_XS have none: a launch that mixes one of them with anything else goes out as one launch per segment.
 bool mv_formats_split(const SegSpec* specs, int nseg) {
   bool q4 = false, q5 = false, other = false, uniform = true;
   for (int s = 0; s < nseg; s++) {
     const int t = specs[s].W[0]->type;
     q4 |= t == kDevQ4K_T16; q5 |= t == kDevQ5K_T16; other |= t == kDevQ80_T16 || t == kDevQ40_T16 || t == kDevQ3K_T16 || t == kDevQ2K_T16 ||
-                                                             t == kDevQ41_T16 || t == kDevQ50_T16 || t == kDevQ51_T16;
+                                                             t == kDevQ41_T16 || t == kDevQ50_T16 || t == kDevQ51_T16 ||
+                                                             t == kDevIQ4NL_T16 || t == kDevIQ4XS_T16;
     uniform &= t == specs[0].W[0]->type;
   }
   return !uniform && ((q4 && q5) || other);

@@ -169,14 +169,15 @@ int parse(const Mapping& m, Parsed& g, std::string& why) {
 
 uint32_t blk_elems_of(uint32_t t) {
   switch (t) { case LGH_TYPE_F32: case LGH_TYPE_F16: case LGH_TYPE_BF16: return 1; case LGH_TYPE_Q4_0: case LGH_TYPE_Q4_1: case LGH_TYPE_Q5_0:
-               case LGH_TYPE_Q5_1: case LGH_TYPE_Q8_0: case LGH_TYPE_Q8_1: return 32; case LGH_TYPE_Q2_K: case LGH_TYPE_Q3_K: case LGH_TYPE_Q4_K:
-               case LGH_TYPE_Q5_K: case LGH_TYPE_Q6_K: case LGH_TYPE_Q8_K: return 256; default: return 0; }
+               case LGH_TYPE_Q5_1: case LGH_TYPE_Q8_0: case LGH_TYPE_Q8_1: case LGH_TYPE_IQ4_NL: return 32; case LGH_TYPE_Q2_K: case LGH_TYPE_Q3_K:
+               case LGH_TYPE_Q4_K: case LGH_TYPE_Q5_K: case LGH_TYPE_Q6_K: case LGH_TYPE_Q8_K: case LGH_TYPE_IQ4_XS: return 256; default: return 0; }
 }
 uint32_t blk_bytes_of(uint32_t t) {   // src/tensor/quant/blocks.rs:293-305
   switch (t) { case LGH_TYPE_F32: return 4; case LGH_TYPE_F16: case LGH_TYPE_BF16: return 2; case LGH_TYPE_Q4_0: return 18; case LGH_TYPE_Q4_1: return 20;
                case LGH_TYPE_Q5_0: return 22; case LGH_TYPE_Q5_1: return 24; case LGH_TYPE_Q8_0: return 34; case LGH_TYPE_Q8_1: return 36;
                case LGH_TYPE_Q2_K: return 84; case LGH_TYPE_Q3_K: return 110; case LGH_TYPE_Q4_K: return 144; case LGH_TYPE_Q5_K: return 176;
-               case LGH_TYPE_Q6_K: return 210; case LGH_TYPE_Q8_K: return 292; default: return 0; }
+               case LGH_TYPE_Q6_K: return 210; case LGH_TYPE_Q8_K: return 292; case LGH_TYPE_IQ4_NL: return 18; case LGH_TYPE_IQ4_XS: return 136;
+               default: return 0; }
 }
 
 bool get_u(const Parsed& g, const std::string& k, uint64_t& out) {

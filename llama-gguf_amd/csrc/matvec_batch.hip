@@ -227,9 +227,17 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb_legacy_kernel(uint32_t wbpa
   extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
   mvqb_body<MASK, NB>(wbpack, geom, geom2, red_floats, L, B, smem8);
 }
+// IQ4_NL, IQ4_XS (contexts with LGH_WEIGHTS_IQ4_TILES): likewise
+template <uint32_t MASK, int NB>
+__global__ void __launch_bounds__(kBWaves * 64) mvqb_iq4_kernel(uint32_t wbpack, uint32_t geom, uint32_t geom2, uint32_t red_floats,
+                                                                const MvLaunch L, const MvBatch B) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  mvqb_body<MASK, NB>(wbpack, geom, geom2, red_floats, L, B, smem8);
+}
 template <uint32_t MASK, int NB>
 static auto mvqb_kernel_of() {
-  if constexpr ((MASK & kLegacyMask) != 0) return &mvqb_legacy_kernel<MASK, NB>;
+  if constexpr ((MASK & kIq4Mask) != 0) return &mvqb_iq4_kernel<MASK, NB>;
+  else if constexpr ((MASK & kLegacyMask) != 0) return &mvqb_legacy_kernel<MASK, NB>;
   else if constexpr ((MASK & kLowbitMask) != 0) return &mvqb_lowbit_kernel<MASK, NB>;
   else return &mvqb_kernel<MASK, NB>;
 }
@@ -459,9 +467,17 @@ __global__ void __launch_bounds__(kBWaves * 64) mvqb2_legacy_kernel(const Mvqb2G
   extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
   mvqb2_body<MASK, NB, SEQ>(Gm, L, B, part, smem8);
 }
+// IQ4_NL, IQ4_XS (contexts with LGH_WEIGHTS_IQ4_TILES): likewise
+template <uint32_t MASK, int NB, bool SEQ>
+__global__ void __launch_bounds__(kBWaves * 64) mvqb2_iq4_kernel(const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B,
+                                                                 float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  mvqb2_body<MASK, NB, SEQ>(Gm, L, B, part, smem8);
+}
 template <uint32_t MASK, int NB, bool SEQ>
 static auto mvqb2_kernel_of() {
-  if constexpr ((MASK & kLegacyMask) != 0) return &mvqb2_legacy_kernel<MASK, NB, SEQ>;
+  if constexpr ((MASK & kIq4Mask) != 0) return &mvqb2_iq4_kernel<MASK, NB, SEQ>;
+  else if constexpr ((MASK & kLegacyMask) != 0) return &mvqb2_legacy_kernel<MASK, NB, SEQ>;
   else if constexpr ((MASK & kLowbitMask) != 0) return &mvqb2_lowbit_kernel<MASK, NB, SEQ>;
   else return &mvqb2_kernel<MASK, NB, SEQ>;
 }
@@ -649,6 +665,7 @@ hipError_t mvqb_launch(const MvLaunch& L, const MvBatch& Bin, uint32_t n_wg, uin
         LGH_MVQB2_CASE(1u << F_Q4K); LGH_MVQB2_CASE(1u << F_Q6K); LGH_MVQB2_CASE(1u << F_Q5K); LGH_MVQB2_CASE(1u << F_Q80); LGH_MVQB2_CASE(1u << F_Q40);
         LGH_MVQB2_CASE(1u << F_Q3K); LGH_MVQB2_CASE(1u << F_Q2K);
         LGH_MVQB2_CASE(1u << F_Q41); LGH_MVQB2_CASE(1u << F_Q50); LGH_MVQB2_CASE(1u << F_Q51);
+        LGH_MVQB2_CASE(1u << F_IQ4NL); LGH_MVQB2_CASE(1u << F_IQ4XS);
         LGH_MVQB2_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQB2_CASE((1u << F_Q5K) | (1u << F_Q6K));
         default: break;
       }
@@ -666,6 +683,7 @@ hipError_t mvqb_launch(const MvLaunch& L, const MvBatch& Bin, uint32_t n_wg, uin
     LGH_MVQB_CASE(1u << F_Q4K); LGH_MVQB_CASE(1u << F_Q6K); LGH_MVQB_CASE(1u << F_Q5K); LGH_MVQB_CASE(1u << F_Q80); LGH_MVQB_CASE(1u << F_Q40);
     LGH_MVQB_CASE(1u << F_Q3K); LGH_MVQB_CASE(1u << F_Q2K);
     LGH_MVQB_CASE(1u << F_Q41); LGH_MVQB_CASE(1u << F_Q50); LGH_MVQB_CASE(1u << F_Q51);
+    LGH_MVQB_CASE(1u << F_IQ4NL); LGH_MVQB_CASE(1u << F_IQ4XS);
     LGH_MVQB_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQB_CASE((1u << F_Q5K) | (1u << F_Q6K));
     default: return hipErrorInvalidValue;
   }

@@ -24,6 +24,7 @@
 //   Q4_0        w = fma(q, d, -8 * d)                 Q8_0  w = fma(q ^ 0x80, d, -128 * d)    = round(d * q)
 //   Q2_K        as Q4_K, one (sc, mn) per chunk       Q3_K  w = fma(q, d * sc, -4 * d * sc)   = round(d * sc * (q - 4))
 //   Q4_1, Q5_1  w = fma(q, d, m)                      Q5_0  w = fma(q, d, -16 * d)            = round(d * (q - 16))
+//   IQ4_NL, IQ4_XS  as Q8_0 over the decoded codebook bytes, d resp. d * (ls - 32) for d: w = round(d * kv[q])
 //
 // Activations.  Plain f32: x[s][.] * norm_w[.] (the product the XQ producers round; x alone without a norm) staged per chunk of
 // kXfCb blocks for all sequences in LDS, double-buffered with one barrier per chunk; rows of sequences >= n_seq are zero.  A
@@ -122,7 +123,8 @@ mvqf_kernel(const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B, float* __rest
 #pragma unroll
         for (int pp = 0; pp < 4; pp++) {
           if (is(F_Q6K)) { sa[pp] = t.dd * t.f[pp]; sb[pp] = -32.0f * sa[pp]; }
-          else if (is(F_Q80)) { sa[pp] = t.f[pp]; sb[pp] = -128.0f * sa[pp]; }
+          else if (is(F_Q80) || is(F_IQ4NL)) { sa[pp] = t.f[pp]; sb[pp] = -128.0f * sa[pp]; }
+          else if (is(F_IQ4XS)) { sa[pp] = t.dd * t.f[pp]; sb[pp] = -128.0f * sa[pp]; }
           else if (is(F_Q40)) { sa[pp] = t.f[pp]; sb[pp] = -8.0f * sa[pp]; }
           else if (is(F_Q3K)) { sa[pp] = t.dd * t.f[pp]; sb[pp] = -4.0f * sa[pp]; }
           else if (is(F_Q50)) { sa[pp] = t.f[pp]; sb[pp] = -16.0f * sa[pp]; }
@@ -138,7 +140,7 @@ mvqf_kernel(const Mvqb2Geom Gm, const MvLaunch L, const MvBatch B, float* __rest
 #pragma unroll
           for (int j = 0; j < 4; j++) {
             uint32_t qw = (uint32_t)t.bw[pp][j];
-            if (is(F_Q80)) qw ^= 0x80808080u;                     // int8 quants as bytes biased by 128
+            if (is(F_Q80) || is(F_IQ4NL) || is(F_IQ4XS)) qw ^= 0x80808080u;   // int8 quants as bytes biased by 128
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_fmaf(ub0(qw), sa[pp], sb[pp]), xv[j].x, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_fmaf(ub1(qw), sa[pp], sb[pp]), xv[j].y, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_fmaf(ub2(qw), sa[pp], sb[pp]), xv[j].z, acc, 0, 0, 0);
@@ -181,6 +183,7 @@ hipError_t mvqf_launch(uint32_t mask, const Mvqb2Geom& Gm, const MvLaunch& L, co
     LGH_MVQF_CASE(1u << F_Q4K); LGH_MVQF_CASE(1u << F_Q6K); LGH_MVQF_CASE(1u << F_Q5K); LGH_MVQF_CASE(1u << F_Q80); LGH_MVQF_CASE(1u << F_Q40);
     LGH_MVQF_CASE(1u << F_Q3K); LGH_MVQF_CASE(1u << F_Q2K);
     LGH_MVQF_CASE(1u << F_Q41); LGH_MVQF_CASE(1u << F_Q50); LGH_MVQF_CASE(1u << F_Q51);
+    LGH_MVQF_CASE(1u << F_IQ4NL); LGH_MVQF_CASE(1u << F_IQ4XS);
     LGH_MVQF_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQF_CASE((1u << F_Q5K) | (1u << F_Q6K));
     default: return hipErrorInvalidValue;
   }

@@ -1,5 +1,5 @@
 // matvec_mfma.hip — quantized mat-vec on the int8 matrix cores (v_mfma_i32_16x16x64_i8): Q4_K, Q5_K, Q6_K, Q8_0, Q4_0, and Q3_K / Q2_K and
-// Q4_1 / Q5_0 / Q5_1 on contexts that keep them quantized (lgh_set_weight_policy).
+// Q4_1 / Q5_0 / Q5_1 and IQ4_NL / IQ4_XS on contexts that keep them quantized (lgh_set_weight_policy).
 //
 // Why MFMA for a mat-VEC.  The VALU formulation (matvec.hip) needs ~3.6 vector instructions per weight
 // (byte->f32 convert, FMA, nibble masks); measured on MI355X a wave64 v_cvt_f32_ubyte costs ~2.0 ns and a
@@ -205,13 +205,18 @@ hipError_t repack_q6k_t16_launch(const uint8_t* raw, uint8_t* dst, uint32_t n_ro
 //   Q8_0 (4352 B): [pp][lane] 16 quants as they are (int8) [0,4096), then per row the 8 f16 d of its 32-element blocks
 //   Q4_0 (2304 B): nibble words [0,2048) as Q4_K (unsigned 0..15; the reference's "- 8" goes through the sums of x), then
 //         per row the 8 f16 d
+//   IQ4_NL (2304 B, contexts with LGH_WEIGHTS_IQ4_TILES): native blocks {d, qs[16]} in Q4_0's nibble order, so the Q4_0 tile as it is;
+//         a nibble is an index into the 16-entry int8 codebook (mvq_iq4_operand), y = d * kv[q]
+//   IQ4_XS (2176 B = 16 x 136, the same contexts): native blocks {d, scales_h, scales_l[4], qs[128]}, sub-block ib = qs[16 ib ..] laid
+//         out as a Q4_0 block: nibble words [0,2048) as Q4_0's, then per row the native 8-byte header [2048,2176), one 64-bit load
+//         per lane at 2048 + 8 n; y = d * (ls - 32) * kv[q] with the 6-bit ls of sub-block 2pp + (c >> 1) (mvq_iq4xs_scale)
 // One thread per (row, 256-element block, step).
 // ------------------------------------------------------------------------------------------------
 template <int F>
 __global__ void __launch_bounds__(256) repack_t16_kernel(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dst,
                                                         uint32_t n_rows, uint32_t nblk, uint64_t total) {
   constexpr uint32_t TB = fmt_tile_bytes(F);
-  constexpr uint32_t SRC = F == F_Q5K ? 176u : F == F_Q80 ? 8u * 34u : 8u * 18u;   // native bytes of 256 elements
+  constexpr uint32_t SRC = F == F_Q5K ? 176u : F == F_Q80 ? 8u * 34u : F == F_IQ4XS ? 136u : 8u * 18u;   // native bytes of 256 elements
   for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (uint64_t)gridDim.x * 256) {
     const uint32_t pp = (uint32_t)(idx & 3);
     const uint64_t rb = idx >> 2;
@@ -229,7 +234,8 @@ __global__ void __launch_bounds__(256) repack_t16_kernel(const uint8_t* __restri
       }
       const uint32_t sb = e >> 5, i = e & 31;   // 32-element block and offset
       if (F == F_Q80) return src[sb * 34 + 2 + i];                       // dequant.rs:106-112
-      const uint32_t byte = src[sb * 18 + 2 + (i & 15)];               // Q4_0, dequant.rs:16-30
+      const uint32_t byte = F == F_IQ4XS ? src[8 + sb * 16 + (i & 15)]   // iq_quants.rs:91-96
+                                         : src[sb * 18 + 2 + (i & 15)];  // Q4_0, dequant.rs:16-30 (IQ4_NL: iq_quants.rs:68-73)
       return i < 16 ? (byte & 15u) : (byte >> 4);
     };
     uint32_t hpair[4] = {0, 0, 0, 0};
@@ -265,6 +271,8 @@ __global__ void __launch_bounds__(256) repack_t16_kernel(const uint8_t* __restri
       for (uint32_t c = 0; c < 4; c++)
         atomicOr(reinterpret_cast<uint32_t*>(tile + 2304 + (16 * c + n) * 8 + (pp >> 1) * 4), hpair[c] << (4 * (pp & 1)));
       *reinterpret_cast<uint32_t*>(tile + 2048 + n * 16 + pp * 4) = live ? *reinterpret_cast<const uint32_t*>(src + pp * 4) : 0u;
+    } else if (F == F_IQ4XS) {   // the native 8-byte header, a dword from each of the first two step threads
+      if (pp < 2) *reinterpret_cast<uint32_t*>(tile + 2048 + n * 8 + pp * 4) = live ? *reinterpret_cast<const uint32_t*>(src + pp * 4) : 0u;
     } else {
       // two f16 d per step thread: blocks 2pp, 2pp+1
       const uint32_t bs = F == F_Q80 ? 34u : 18u, hoff = F == F_Q80 ? 4096u : 2048u;
@@ -428,6 +436,8 @@ hipError_t repack_t16_launch(int dev_type, const uint8_t* raw, uint8_t* dst, uin
     case F_Q41: hipLaunchKernelGGL((repack_legacy_t16_kernel<F_Q41>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
     case F_Q50: hipLaunchKernelGGL((repack_legacy_t16_kernel<F_Q50>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
     case F_Q51: hipLaunchKernelGGL((repack_legacy_t16_kernel<F_Q51>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
+    case F_IQ4NL: hipLaunchKernelGGL((repack_t16_kernel<F_Q40>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;   // Q4_0's bytes, Q4_0's tile
+    case F_IQ4XS: hipLaunchKernelGGL((repack_t16_kernel<F_IQ4XS>), g, t, 0, st, raw, dst, n_rows, nblk, total); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -737,9 +747,19 @@ __global__ void __launch_bounds__(kWaves * 64) mvq_legacy_kernel(uint32_t wbpack
   mvq_body<MASK>(blockIdx.x, wbpack, geom, geom2, L_red_floats, lds_red_off, L, smem8);
   LGH_TL_END();
 }
+// IQ4_NL, IQ4_XS (contexts with LGH_WEIGHTS_IQ4_TILES): the same body under a name of its own
+template <uint32_t MASK>
+__global__ void __launch_bounds__(kWaves * 64) mvq_iq4_kernel(uint32_t wbpack, uint32_t geom, uint32_t geom2, uint32_t L_red_floats,
+                                                              uint32_t lds_red_off, const MvLaunch L) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
+  LGH_TL_BEGIN(mvq, lgh::TL_MVQ, geom2);
+  mvq_body<MASK>(blockIdx.x, wbpack, geom, geom2, L_red_floats, lds_red_off, L, smem8);
+  LGH_TL_END();
+}
 template <uint32_t MASK>
 static auto mvq_kernel_of() {
-  if constexpr ((MASK & kLegacyMask) != 0) return &mvq_legacy_kernel<MASK>;
+  if constexpr ((MASK & kIq4Mask) != 0) return &mvq_iq4_kernel<MASK>;
+  else if constexpr ((MASK & kLegacyMask) != 0) return &mvq_legacy_kernel<MASK>;
   else if constexpr ((MASK & kLowbitMask) != 0) return &mvq_lowbit_kernel<MASK>;
   else return &mvq_kernel<MASK>;
 }
@@ -1211,6 +1231,7 @@ hipError_t mvq_launch(const MvLaunch& L0, uint32_t n_wg, uint32_t threads, hipSt
     LGH_MVQ_CASE(1u << F_Q4K); LGH_MVQ_CASE(1u << F_Q6K); LGH_MVQ_CASE(1u << F_Q5K); LGH_MVQ_CASE(1u << F_Q80); LGH_MVQ_CASE(1u << F_Q40);
     LGH_MVQ_CASE(1u << F_Q3K); LGH_MVQ_CASE(1u << F_Q2K);
     LGH_MVQ_CASE(1u << F_Q41); LGH_MVQ_CASE(1u << F_Q50); LGH_MVQ_CASE(1u << F_Q51);
+    LGH_MVQ_CASE(1u << F_IQ4NL); LGH_MVQ_CASE(1u << F_IQ4XS);
     LGH_MVQ_CASE((1u << F_Q4K) | (1u << F_Q6K)); LGH_MVQ_CASE((1u << F_Q5K) | (1u << F_Q6K));
     default: return hipErrorInvalidValue;   // other mixes: the caller launches one format at a time
   }

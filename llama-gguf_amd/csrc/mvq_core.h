@@ -14,19 +14,22 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTileBytes = 2304;      // Q4_K tile16
 constexpr int kTileBytesQ6 = 3392;    // Q6_K tile16
 // formats of the matrix-core mat-vec; a kernel instantiation handles the formats in its MASK (bit = 1 << format)
-enum : int { F_Q4K = 0, F_Q6K = 1, F_Q5K = 2, F_Q80 = 3, F_Q40 = 4, F_Q3K = 5, F_Q2K = 6, F_Q41 = 7, F_Q50 = 8, F_Q51 = 9, F_COUNT = 10 };
+enum : int { F_Q4K = 0, F_Q6K = 1, F_Q5K = 2, F_Q80 = 3, F_Q40 = 4, F_Q3K = 5, F_Q2K = 6, F_Q41 = 7, F_Q50 = 8, F_Q51 = 9, F_IQ4NL = 10,
+              F_IQ4XS = 11, F_COUNT = 12 };
 constexpr uint32_t kLowbitMask = (1u << F_Q3K) | (1u << F_Q2K);   // instantiations that hold one of these are the *_lowbit_kernel twins
 constexpr uint32_t kLegacyMask = (1u << F_Q41) | (1u << F_Q50) | (1u << F_Q51);   // ... and of these the *_legacy_kernel ones
+constexpr uint32_t kIq4Mask = (1u << F_IQ4NL) | (1u << F_IQ4XS);                 // ... and of these the *_iq4_kernel ones
 __host__ __device__ constexpr uint32_t fmt_tile_bytes(int f) {   // = 16 rows x the GGUF bytes of 256 elements (Q6_K: +32 pad; Q3_K: 114 per row)
   return f == F_Q4K ? 2304u : f == F_Q6K ? 3392u : f == F_Q5K ? 2816u : f == F_Q80 ? 4352u : f == F_Q3K ? 1824u : f == F_Q2K ? 1344u
-         : f == F_Q41 ? 2560u : f == F_Q50 ? 2816u : f == F_Q51 ? 3072u : 2304u;
+         : f == F_Q41 ? 2560u : f == F_Q50 ? 2816u : f == F_Q51 ? 3072u : f == F_IQ4XS ? 2176u : 2304u;   // (Q4_0, IQ4_NL: 2304)
 }
 __host__ __device__ constexpr int fmt_loads_per_tile(int f) {
-  return f == F_Q4K ? 3 : f == F_Q6K ? 5 : f == F_Q5K ? 4 : f == F_Q80 ? 5 : f == F_Q3K ? 4 : f == F_Q41 ? 4 : f == F_Q50 ? 4 : f == F_Q51 ? 5 : 3;
+  return f == F_Q4K ? 3 : f == F_Q6K ? 5 : f == F_Q5K ? 4 : f == F_Q80 ? 5 : f == F_Q3K ? 4 : f == F_Q41 ? 4 : f == F_Q50 ? 4 : f == F_Q51 ? 5 : 3;   // (IQ4_NL, IQ4_XS: 3)
 }
 __host__ __device__ constexpr int fmt_of_dev_type(int t) {
   return t == kDevQ4K_T16 ? F_Q4K : t == kDevQ6K_T16 ? F_Q6K : t == kDevQ5K_T16 ? F_Q5K : t == kDevQ80_T16 ? F_Q80 : t == kDevQ40_T16 ? F_Q40
-         : t == kDevQ3K_T16 ? F_Q3K : t == kDevQ2K_T16 ? F_Q2K : t == kDevQ41_T16 ? F_Q41 : t == kDevQ50_T16 ? F_Q50 : t == kDevQ51_T16 ? F_Q51 : -1;
+         : t == kDevQ3K_T16 ? F_Q3K : t == kDevQ2K_T16 ? F_Q2K : t == kDevQ41_T16 ? F_Q41 : t == kDevQ50_T16 ? F_Q50 : t == kDevQ51_T16 ? F_Q51
+         : t == kDevIQ4NL_T16 ? F_IQ4NL : t == kDevIQ4XS_T16 ? F_IQ4XS : -1;
 }
 
 
@@ -45,7 +48,7 @@ __device__ __forceinline__ uint32_t mvq_tile_stride(int fmt) {
   auto is = [&](int f) { return mvq_is<MASK>(fmt, f); };
   return is(F_Q4K) ? fmt_tile_bytes(F_Q4K) : is(F_Q6K) ? fmt_tile_bytes(F_Q6K) : is(F_Q5K) ? fmt_tile_bytes(F_Q5K) : is(F_Q80) ? fmt_tile_bytes(F_Q80)
          : is(F_Q3K) ? fmt_tile_bytes(F_Q3K) : is(F_Q2K) ? fmt_tile_bytes(F_Q2K) : is(F_Q41) ? fmt_tile_bytes(F_Q41)
-         : is(F_Q50) ? fmt_tile_bytes(F_Q50) : is(F_Q51) ? fmt_tile_bytes(F_Q51) : fmt_tile_bytes(F_Q40);
+         : is(F_Q50) ? fmt_tile_bytes(F_Q50) : is(F_Q51) ? fmt_tile_bytes(F_Q51) : is(F_IQ4XS) ? fmt_tile_bytes(F_IQ4XS) : fmt_tile_bytes(F_Q40);
 }
 
 // The two low-bit K-quants (tile layouts: matvec_mfma.hip).  r.q[0] dword pp: the lane's 16 two-bit quants of step pp, byte t = q[t] |
@@ -97,6 +100,27 @@ __device__ __forceinline__ float mvq_block_f16(const u32x4& h, int pp, uint32_t 
   return h2f((c >> 1) ? w >> 16 : w & 0xFFFFu);
 }
 
+// The two non-linear 4-bit formats, IQ4_NL and IQ4_XS (tile layouts: matvec_mfma.hip).  Nibble words r.q[0] / r.q[1] as Q4_0's; a nibble
+// is an index into the 16-entry codebook kv = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}, whose entries
+// are signed int8: the decoded byte IS the B-operand byte, as Q8_0's quants are — no offset, no minimum.  The lookup is done in registers
+// (iq4_decode4, device_utils.h): about 6 vector operations per operand dword against Q4_0's 2.
+__device__ __forceinline__ i32x4 mvq_iq4_operand(const RawT16& r, int pp) {
+  const uint32_t N0 = (pp & 1) ? r.q[pp >> 1].z : r.q[pp >> 1].x, N1 = (pp & 1) ? r.q[pp >> 1].w : r.q[pp >> 1].y;
+  i32x4 bw;
+  bw.x = (int)iq4_decode4(N0 & 0x0F0F0F0Fu);
+  bw.y = (int)iq4_decode4((N0 >> 4) & 0x0F0F0F0Fu);
+  bw.z = (int)iq4_decode4(N1 & 0x0F0F0F0Fu);
+  bw.w = (int)iq4_decode4((N1 >> 4) & 0x0F0F0F0Fu);
+  return bw;
+}
+// IQ4_XS: ls - 32 of sub-block ib = 2pp + (c >> 1), the sub-block of chunk 4pp + c; hd.x = d | scales_h << 16, hd.y = scales_l[0..3]
+// (ls = (scales_l[ib / 2] >> 4 (ib % 2) & 15) | (scales_h >> 2 ib & 3) << 4, iq_quants.rs:86-89)
+__device__ __forceinline__ float mvq_iq4xs_scale(const u32x4& hd, int pp, uint32_t c) {
+  const uint32_t h = c >> 1;
+  const uint32_t ls = ((hd.y >> (8 * pp + 4 * h)) & 15u) | (((hd.x >> (16 + 4 * pp + 2 * h)) & 3u) << 4);
+  return (float)((int)ls - 32);
+}
+
 // fmt_loads_per_tile(format) non-temporal loads of this lane's share of the tile at `tile` (lane roles: row n = lane & 15)
 template <uint32_t MASK>
 __device__ __forceinline__ void mvq_issue_tile(int fmt, const uint8_t* tile, uint32_t lane, RawT16& r) {
@@ -132,7 +156,13 @@ __device__ __forceinline__ void mvq_issue_tile(int fmt, const uint8_t* tile, uin
         r.q[2].x = h.x;
         r.q[2].y = h.y;
       }
-    } else {   // Q4_K, Q5_K, Q4_0: header + two nibble loads (+ the fifth bits)
+    } else if (is(F_IQ4XS)) {   // the row's native 8-byte header {d, scales_h, scales_l[4]}, two nibble loads
+      const u32x2 h = ldg_nt64(tile + 2048 + n * 8);
+      r.hd.x = h.x;
+      r.hd.y = h.y;
+      r.q[0] = ldg_nt128(tile + lane * 16);
+      r.q[1] = ldg_nt128(tile + 1024 + lane * 16);
+    } else {   // Q4_K, Q5_K, Q4_0, IQ4_NL: header + two nibble loads (+ the fifth bits)
       r.hd = ldg_nt128(tile + 2048 + n * 16);
       r.q[0] = ldg_nt128(tile + lane * 16);
       r.q[1] = ldg_nt128(tile + 1024 + lane * 16);
@@ -262,6 +292,20 @@ __device__ __forceinline__ void mvq_consume_tile(int fmt, const RawT16& r, const
       }
       if (is(F_Q50)) acc += s1;
       else acc += s1 + s2;
+    } else if (is(F_IQ4NL) || is(F_IQ4XS)) {
+      // y = d * kv[q] (IQ4_NL, 32-element blocks: the Q8_0 shape) / d * (ls - 32) * kv[q] (IQ4_XS, a 6-bit scale per 32 elements: the
+      // Q6_K shape without an offset), iq_quants.rs:66-99.  |kv| <= 127: the limb sums stay within Q8_0's.
+      float s1 = 0.0f;
+#pragma unroll
+      for (int pp = 0; pp < 4; pp++) {
+        const i32x4 zero = {0, 0, 0, 0};
+        const i32x4 d = __builtin_amdgcn_mfma_i32_16x16x64_i8(areg[pp], mvq_iq4_operand(r, pp), zero, 0, 0, 0);
+        const float hi = (float)((d.x << 8) + d.y), lo = (float)((d.z << 8) + d.w);
+        const float V = __builtin_fmaf(hi, 65536.0f, lo);
+        s1 = __builtin_fmaf(is(F_IQ4NL) ? mvq_block_f16(r.hd, pp, c) : mvq_iq4xs_scale(r.hd, pp, c), sx[pp] * V, s1);
+      }
+      if (is(F_IQ4NL)) acc += s1;
+      else acc = __builtin_fmaf(h2f(r.hd.x & 0xFFFFu), s1, acc);
     } else {
       // Q4_K / Q5_K: 6-bit scales / mins of sub-blocks h, h+2, h+4, h+6 of row n, h = c >> 1 (packing: dequant.rs:210-223);
       // chunk 4pp + c lies in sub-block 2pp + h
@@ -328,9 +372,10 @@ __device__ __forceinline__ void xq_load_ops(const uint8_t* rec, uint32_t lane, X
 
 struct TileOps {
   i32x4 bw[4];      // B operand of step pp
-  float f[4];       // per step: Q4_K/Q5_K sub-block scale, Q6_K / Q3_K int8 scale, Q8_0/Q4_0/Q4_1/Q5_0/Q5_1 block d, Q2_K chunk scale
+  float f[4];       // per step: Q4_K/Q5_K sub-block scale, Q6_K / Q3_K int8 scale, Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/IQ4_NL block d, Q2_K chunk scale,
+                    // IQ4_XS sub-block ls - 32
   float g[4];       // Q4_K/Q5_K: sub-block min; Q2_K: chunk min; Q4_1/Q5_1: block m
-  float dd, dmin;   // Q4_K/Q5_K/Q2_K: d, dmin; Q6_K/Q3_K: d
+  float dd, dmin;   // Q4_K/Q5_K/Q2_K: d, dmin; Q6_K/Q3_K/IQ4_XS: d
 };
 
 template <uint32_t MASK>
@@ -398,6 +443,15 @@ __device__ __forceinline__ void mvq_unpack_tile(int fmt, const RawT16& r, uint32
       t.g[pp] = is(F_Q50) ? 0.0f : mvq_block_f16(r.q[3], pp, c);
     }
     t.dd = t.dmin = 0.0f;
+  } else if (is(F_IQ4NL) || is(F_IQ4XS)) {
+#pragma unroll
+    for (int pp = 0; pp < 4; pp++) {
+      t.bw[pp] = mvq_iq4_operand(r, pp);
+      t.f[pp] = is(F_IQ4NL) ? mvq_block_f16(r.hd, pp, c) : mvq_iq4xs_scale(r.hd, pp, c);
+      t.g[pp] = 0.0f;
+    }
+    t.dd = is(F_IQ4NL) ? 0.0f : h2f(r.hd.x & 0xFFFFu);
+    t.dmin = 0.0f;
   } else {
     const uint32_t s8 = (c >> 1) * 8;
     const uint32_t a = (r.hd.y >> s8) & 0x00FF00FFu, bq = (r.hd.z >> s8) & 0x00FF00FFu, cq = (r.hd.w >> s8) & 0x00FF00FFu;
@@ -486,6 +540,12 @@ __device__ __forceinline__ void mvq_mac_finish(int fmt, const TileOps& t, const 
       s2 = __builtin_fmaf(t.g[pp], o.xs[pp], s2);
     }
     acc += s1 + s2;
+  } else if (is(F_IQ4NL) || is(F_IQ4XS)) {
+    float s1 = 0.0f;
+#pragma unroll
+    for (int pp = 0; pp < 4; pp++) s1 = __builtin_fmaf(t.f[pp], o.sx[pp] * V[pp], s1);
+    if (is(F_IQ4NL)) acc += s1;
+    else acc = __builtin_fmaf(t.dd, s1, acc);
   } else {   // Q4_K, Q5_K, Q2_K
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll

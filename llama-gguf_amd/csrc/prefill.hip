@@ -44,16 +44,18 @@ typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 
 // formats as in matvec_mfma.hip (same tile16 layouts)
 // ... and the two 16-bit layouts of matvec_h16.hip (contexts with LGH_WEIGHTS_HALF_TILES): pf_body_half
-// ... and Q4_1 / Q5_0 / Q5_1 (contexts with LGH_WEIGHTS_LEGACY_TILES)
-enum : int { PF_Q4K = 0, PF_Q6K = 1, PF_Q5K = 2, PF_Q80 = 3, PF_Q40 = 4, PF_Q3K = 5, PF_Q2K = 6, PF_F16 = 7, PF_BF16 = 8, PF_Q41 = 9, PF_Q50 = 10, PF_Q51 = 11 };
+// ... and Q4_1 / Q5_0 / Q5_1 (contexts with LGH_WEIGHTS_LEGACY_TILES), IQ4_NL / IQ4_XS (contexts with LGH_WEIGHTS_IQ4_TILES)
+enum : int { PF_Q4K = 0, PF_Q6K = 1, PF_Q5K = 2, PF_Q80 = 3, PF_Q40 = 4, PF_Q3K = 5, PF_Q2K = 6, PF_F16 = 7, PF_BF16 = 8, PF_Q41 = 9, PF_Q50 = 10, PF_Q51 = 11,
+              PF_IQ4NL = 12, PF_IQ4XS = 13 };
 __host__ __device__ constexpr uint32_t pf_tile_bytes(int f) {
-  return f == PF_Q41 ? 2560u : f == PF_Q50 ? 2816u : f == PF_Q51 ? 3072u : f >= PF_F16 ? 8192u : f == PF_Q4K ? 2304u : f == PF_Q6K ? 3392u : f == PF_Q5K ? 2816u : f == PF_Q80 ? 4352u : f == PF_Q3K ? 1824u : f == PF_Q2K ? 1344u : 2304u;
+  return f == PF_IQ4NL ? 2304u : f == PF_IQ4XS ? 2176u : f == PF_Q41 ? 2560u : f == PF_Q50 ? 2816u : f == PF_Q51 ? 3072u : f >= PF_F16 ? 8192u : f == PF_Q4K ? 2304u : f == PF_Q6K ? 3392u : f == PF_Q5K ? 2816u : f == PF_Q80 ? 4352u : f == PF_Q3K ? 1824u : f == PF_Q2K ? 1344u : 2304u;
 }
 static int pf_fmt_of(int dev_type) {
   return dev_type == kDevQ4K_T16 ? PF_Q4K : dev_type == kDevQ6K_T16 ? PF_Q6K : dev_type == kDevQ5K_T16 ? PF_Q5K
          : dev_type == kDevQ80_T16 ? PF_Q80 : dev_type == kDevQ40_T16 ? PF_Q40 : dev_type == kDevQ3K_T16 ? PF_Q3K
          : dev_type == kDevQ2K_T16 ? PF_Q2K : dev_type == kDevF16_T16 ? PF_F16 : dev_type == kDevBF16_T16 ? PF_BF16
-         : dev_type == kDevQ41_T16 ? PF_Q41 : dev_type == kDevQ50_T16 ? PF_Q50 : dev_type == kDevQ51_T16 ? PF_Q51 : -1;
+         : dev_type == kDevQ41_T16 ? PF_Q41 : dev_type == kDevQ50_T16 ? PF_Q50 : dev_type == kDevQ51_T16 ? PF_Q51
+         : dev_type == kDevIQ4NL_T16 ? PF_IQ4NL : dev_type == kDevIQ4XS_T16 ? PF_IQ4XS : -1;
 }
 
 // waves per workgroup: 4 (one per SIMD, 4 row tiles each).  8 waves of 2 tiles (-DPF_WAVES=8: two per SIMD, twice the LDS
@@ -126,7 +128,13 @@ __device__ __forceinline__ void pf_load(PfRaw& r, const uint8_t* tile, uint32_t 
       r.q[2].x = h.x;
       r.q[2].y = h.y;
     }
-  } else {
+  } else if (F == PF_IQ4XS) {   // the row's native 8-byte header {d, scales_h, scales_l[4]}, two nibble loads
+    const u32x2 h = ldg_nt64(tile + 2048 + n * 8);
+    r.hd.x = h.x;
+    r.hd.y = h.y;
+    r.q[0] = ldg_nt128(tile + lane * 16);
+    r.q[1] = ldg_nt128(tile + 1024 + lane * 16);
+  } else {   // (IQ4_NL: Q4_0's tile)
     r.hd = ldg_nt128(tile + 2048 + n * 16);
     r.q[0] = ldg_nt128(tile + lane * 16);
     r.q[1] = ldg_nt128(tile + 1024 + lane * 16);
@@ -168,6 +176,18 @@ __device__ __forceinline__ void pf_scale(const PfRaw& r, int pp, uint32_t n, uin
       const uint32_t mw = pp == 0 ? r.q[3].x : pp == 1 ? r.q[3].y : pp == 2 ? r.q[3].z : r.q[3].w;
       O = pf_bcast(h2f((c >> 1) ? mw >> 16 : mw & 0xFFFFu) * kPfScale);
     }
+  } else if (F == PF_IQ4NL || F == PF_IQ4XS) {   // y = d * kv[q] / d * (ls - 32) * kv[q], block or sub-block 2pp + (c >> 1); no offset
+    float sc;
+    if (F == PF_IQ4NL) {
+      const uint32_t hdw = pp == 0 ? r.hd.x : pp == 1 ? r.hd.y : pp == 2 ? r.hd.z : r.hd.w;
+      sc = h2f((c >> 1) ? hdw >> 16 : hdw & 0xFFFFu);
+    } else {   // hd.x = d | scales_h << 16, hd.y = scales_l[0..3] (iq_quants.rs:86-89)
+      const uint32_t hb = c >> 1;
+      const uint32_t ls = ((r.hd.y >> (8 * pp + 4 * hb)) & 15u) | (((r.hd.x >> (16 + 4 * pp + 2 * hb)) & 3u) << 4);
+      sc = h2f(r.hd.x & 0xFFFFu) * (float)((int)ls - 32);
+    }
+    S = pf_bcast(sc * kPfScale);
+    O = pf_bcast(0.0f);
   } else if (F == PF_Q3K) {   // y = d * (s6 - 32) * (q - 4), the lane's int8 scale of step pp (dequant.rs:161-200)
     const float scf = (float)(int)__builtin_amdgcn_sbfe((int)r.hd.x, 8 * pp, 8);
     const uint32_t dh = (n & 1) ? r.hd.y >> 16 : r.hd.y & 0xFFFFu;
@@ -221,6 +241,21 @@ __device__ __forceinline__ h16x8 pf_frag_bytes(uint32_t B0, uint32_t B1, h16x2 S
                  __builtin_amdgcn_perm(e, B1, 0x04020400u), __builtin_amdgcn_perm(e, B1, 0x04030401u), S, O);
 }
 
+// eight codebook indices of IQ4_NL / IQ4_XS (word byte t = q[t] | q[t+4] << 4) -> f16(kv[q] * S) in the same order: the table lookup
+// of iq4_decode4 over entries biased by 128 (unsigned bytes b = kv + 128), 0x6400 | b == 1152 + kv exactly, one multiply
+__device__ __forceinline__ h16x8 pf_frag_iq4(uint32_t N, h16x2 S) {
+  const uint32_t e = 0x64646464u;
+  const uint32_t B0 = iq4_decode4(N & 0x0F0F0F0Fu, 0x80808080u), B1 = iq4_decode4((N >> 4) & 0x0F0F0F0Fu, 0x80808080u);
+  const h16x2 k = {(_Float16)1152.0f, (_Float16)1152.0f};
+  const h16x2 u0 = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(e, B0, 0x04020400u)) - k;
+  const h16x2 u1 = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(e, B0, 0x04030401u)) - k;
+  const h16x2 u2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(e, B1, 0x04020400u)) - k;
+  const h16x2 u3 = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(e, B1, 0x04030401u)) - k;
+  const h16x2 w0 = u0 * S, w1 = u1 * S, w2 = u2 * S, w3 = u3 * S;
+  h16x8 r = {w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, w3.x, w3.y};
+  return r;
+}
+
 // eight quants of two (Q2_K) or three (Q3_K) bits -> f16 in the same order.  W: the step's two-bit word (byte t = q[t] | q[t+4] << 2 |
 // q[t+8] << 4 | q[t+12] << 6), of which half h is nibble h of every byte; H: the step's third bits in the low nibbles (byte t = f[t] |
 // f[t+4] << 1 | f[t+8] << 2 | f[t+12] << 3), of which half h is bit pair h
@@ -255,6 +290,7 @@ __device__ __forceinline__ h16x8 pf_frag(const PfRaw& r, int pp, int h, h16x2 S,
   const uint32_t N0 = (pp & 1) ? r.q[pp >> 1].z : r.q[pp >> 1].x, N1 = (pp & 1) ? r.q[pp >> 1].w : r.q[pp >> 1].y;
   const uint32_t N = h ? N1 : N0;
   if (F == PF_Q4K || F == PF_Q40 || F == PF_Q41) return pf_frag_nib(N, S, O);
+  if (F == PF_IQ4NL || F == PF_IQ4XS) return pf_frag_iq4(N, S);
   uint32_t B0 = N & 0x0F0F0F0Fu, B1 = (N >> 4) & 0x0F0F0F0Fu;
   if (F == PF_Q6K) {   // H byte t = f[t] | f[t+4] << 2 | f[t+8] << 4 | f[t+12] << 6 (the two high bits of the chunk's 16 weights)
     const uint32_t H = pp == 0 ? r.q[2].x : pp == 1 ? r.q[2].y : pp == 2 ? r.q[2].z : r.q[2].w;
@@ -727,6 +763,8 @@ __device__ __forceinline__ void pf_gemm_body(const PfGemm& G, uint8_t* pf_smem) 
   else if (is(PF_Q41)) LGH_PF_RUN(PF_Q41);
   else if (is(PF_Q50)) LGH_PF_RUN(PF_Q50);
   else if (is(PF_Q51)) LGH_PF_RUN(PF_Q51);
+  else if (is(PF_IQ4NL)) LGH_PF_RUN(PF_IQ4NL);
+  else if (is(PF_IQ4XS)) LGH_PF_RUN(PF_IQ4XS);
 #undef LGH_PF_RUN
 #define LGH_PF_RUN_HALF(B)                                                               \
   do {                                                                                   \
@@ -759,6 +797,14 @@ __global__ void __launch_bounds__(kPfWaves * 64) pf_gemm_legacy_kernel(const PfG
   extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
   pf_gemm_body<MASK>(G, pf_smem);
 }
+// IQ4_NL, IQ4_XS (contexts with LGH_WEIGHTS_IQ4_TILES): likewise
+constexpr uint32_t kPfIq4Mask = (1u << PF_IQ4NL) | (1u << PF_IQ4XS);
+template <uint32_t MASK>
+__global__ void __launch_bounds__(kPfWaves * 64) pf_gemm_iq4_kernel(const PfGemm G) {
+  static_assert((MASK & ~kPfIq4Mask) == 0 && (MASK & (MASK - 1)) == 0, "one of the two formats: a mix goes out as one launch per matrix");
+  extern __shared__ __attribute__((aligned(16))) uint8_t pf_smem[];
+  pf_gemm_body<MASK>(G, pf_smem);
+}
 // the instantiations over 16-bit tiles (pf_body_half): F16, BF16, and both (a launch whose matrices differ in type)
 constexpr uint32_t kPfHalfMask = (1u << PF_F16) | (1u << PF_BF16);
 template <uint32_t MASK>
@@ -771,6 +817,7 @@ template <uint32_t MASK>
 static auto pf_gemm_kernel_of() {
   if constexpr ((MASK & kPfHalfMask) != 0) return &pf_gemm_half_kernel<MASK>;
   else if constexpr ((MASK & kPfLegacyMask) != 0) return &pf_gemm_legacy_kernel<MASK>;
+  else if constexpr ((MASK & kPfIq4Mask) != 0) return &pf_gemm_iq4_kernel<MASK>;
   else if constexpr ((MASK & kPfLowbitMask) != 0) return &pf_gemm_lowbit_kernel<MASK>;
   else return &pf_gemm_kernel<MASK>;
 }
@@ -826,6 +873,8 @@ static hipError_t pf_gemm_dispatch(const PfGemm& G, uint32_t rg, uint32_t mask, 
     case 1u << PF_Q41: return pf_gemm_go<1u << PF_Q41>(G, rg, st);
     case 1u << PF_Q50: return pf_gemm_go<1u << PF_Q50>(G, rg, st);
     case 1u << PF_Q51: return pf_gemm_go<1u << PF_Q51>(G, rg, st);
+    case 1u << PF_IQ4NL: return pf_gemm_go<1u << PF_IQ4NL>(G, rg, st);
+    case 1u << PF_IQ4XS: return pf_gemm_go<1u << PF_IQ4XS>(G, rg, st);
     default: return mask & ~127u ? hipErrorInvalidValue : mask & ~31u ? pf_gemm_go<127u>(G, rg, st) : pf_gemm_go<31u>(G, rg, st);   // any other mix: of the first five formats, of all
   }
 }
@@ -867,14 +916,14 @@ hipError_t pf_gemm_launch(const DevWeight* const* W, int nw, const uint8_t* xh, 
   if (part_rows < (uint32_t)kPfTokens || (size_t)G.S * part_rows * col * 4 > part_bytes) return hipErrorInvalidValue;
   *S_out = G.S;
   *ncols_out = col;
-  // family of a format: the int8 tiles that have mixed instantiations 0, the 16-bit tiles 1, Q4_1 / Q5_0 / Q5_1 one each
-  auto family = [](int f) { return (kPfHalfMask >> f) & 1u ? 1 : (kPfLegacyMask >> f) & 1u ? 2 + f - PF_Q41 : 0; };
+  // family of a format: the int8 tiles that have mixed instantiations 0, the 16-bit tiles 1, Q4_1 / Q5_0 / Q5_1 / IQ4_NL / IQ4_XS one each
+  auto family = [](int f) { return (kPfHalfMask >> f) & 1u ? 1 : ((kPfLegacyMask | kPfIq4Mask) >> f) & 1u ? 2 + f - PF_Q41 : 0; };
   bool one_family = true;
   for (int i = 1; i < nw; i++) one_family &= family(G.seg[i].fmt) == family(G.seg[0].fmt);
   if (one_family) return pf_gemm_dispatch(G, rg, mask, st);
   // matrices of several families side by side (a file that keeps some projections unquantized, or in a type of its own): one launch
   // per family over its own matrices, as mv_formats_split does for decode.  Columns, splits and the partial-sum buffer stay the whole GEMM's.
-  for (int fam = 0; fam < 5; fam++) {
+  for (int fam = 0; fam < 7; fam++) {
     PfGemm Gf = G;
     uint32_t rgf = 0, maskf = 0;
     Gf.nseg = 0;

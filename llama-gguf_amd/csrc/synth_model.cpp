@@ -16,7 +16,7 @@ namespace {
 
 enum : uint32_t {
   T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q4_1 = 3, T_Q5_0 = 6, T_Q5_1 = 7, T_Q8_0 = 8,
-  T_Q2_K = 10, T_Q3_K = 11, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_BF16 = 30
+  T_Q2_K = 10, T_Q3_K = 11, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_IQ4_NL = 20, T_IQ4_XS = 23, T_BF16 = 30
 };
 
 struct Rng {
@@ -86,8 +86,8 @@ void st16(uint8_t* p, uint16_t v) { std::memcpy(p, &v, 2); }
 size_t blk_size(uint32_t t) {
   switch (t) {
     case T_F32: case T_F16: case T_BF16: return 1;
-    case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q8_0: return 32;
-    case T_Q2_K: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: return 256;
+    case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q8_0: case T_IQ4_NL: return 32;
+    case T_Q2_K: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_IQ4_XS: return 256;
     default: return 0;
   }
 }
@@ -97,7 +97,7 @@ size_t blk_bytes(uint32_t t) {
     case T_F32: return 4; case T_F16: case T_BF16: return 2;
     case T_Q4_0: return 18; case T_Q4_1: return 20; case T_Q5_0: return 22; case T_Q5_1: return 24;
     case T_Q8_0: return 34; case T_Q2_K: return 84; case T_Q3_K: return 110; case T_Q4_K: return 144;
-    case T_Q5_K: return 176; case T_Q6_K: return 210;
+    case T_Q5_K: return 176; case T_Q6_K: return 210; case T_IQ4_NL: return 18; case T_IQ4_XS: return 136;
     default: return 0;
   }
 }
@@ -200,6 +200,16 @@ void fill_block(uint32_t type, Rng& r, float base, uint8_t* b) {
         b[192 + i] = (uint8_t)(int8_t)v;
       }
       st16(b + 208, f2h(base * jitter / 338.0f));
+      break;
+    }
+    case T_IQ4_NL: {  // {d, qs[16]}: d * kv[q]; the codebook's RMS over uniform nibbles is 67.4
+      st16(b, f2h(base * jitter / 67.4f));
+      r.bytes(b + 2, 16);
+      break;
+    }
+    case T_IQ4_XS: {  // {d, scales_h, scales_l[4], qs[128]}: d * (ls - 32) * kv[q]; any 6 bytes decode to valid 6-bit scales, RMS of ls - 32: 18.5
+      st16(b, f2h(base * jitter / (67.4f * 18.5f)));
+      r.bytes(b + 2, 134);
       break;
     }
     default: break;

@@ -57,18 +57,19 @@ ABI_SYMBOLS = (
 
 K_NAMES = ("embed", "qkv", "attn", "attn_combine", "wo", "gate_up", "down", "router", "output", "argmax", "misc", "token")
 K_COUNT = 16
-SYM_COUNT = 26
+SYM_COUNT = 27
 # kernel symbols as rocprofv3 prints them (LGH_SYM_* order)
 SYM_NAMES = ("lgh::mv_kernel<1u, 1024>", "lgh::mv_kernel<8u, 1024>", "lgh::mv_kernel<16u, 1024>",
              "lgh::mv_kernel<2u, 768>", "lgh::mv_kernel<4u, 512>", "lgh::mv_kernel<5u, 512>", "lgh::mv_kernel<6u, 512>",
              "lgh::mv_kernel<31u, 512>", "lgh::f32_matvec_kernel", "lgh::attn_partial_kernel", "lgh::attn_combine_kernel",
              "lgh::embed_kernel", "lgh::argmax_stage1+2", "lgh::moe_router_kernel", "other", "lgh::mvq_kernel<1u>", "lgh::mvq_kernel<2u>", "lgh::mvq_kernel<3u>", "lgh::mvq_kernel<4u>",
              "lgh::mvq_kernel<8u>", "unused", "lgh::mvq_kernel<32u>", "lgh::mvh_kernel<false>", "lgh::mvh_kernel<true>",
-             "lgh::mvq_legacy_kernel<128u>", "lgh::attn_group_kernel")
+             "lgh::mvq_legacy_kernel<128u>", "lgh::attn_group_kernel", "lgh::mvq_iq4_kernel<1024u>")
 FLAG_NO_GRAPH = 1
 BATCH_F32_MATRIX = 1        # lgh_set_batch_policy: steps of >= (policy >> 8 & 0xFF, 0 = the library default) sequences on the f32 matrix cores
 WEIGHTS_LOWBIT_TILES = 1    # lgh_set_weight_policy: Q3_K / Q2_K matrices stay quantized in HBM (matrix-core tile layouts) instead of f32
 WEIGHTS_LEGACY_TILES = 8    # ... Q4_1 / Q5_0 / Q5_1 matrices stay quantized in HBM (tile layouts of 160 / 176 / 192 B per row and 256 elements)
+WEIGHTS_IQ4_TILES = 16      # ... IQ4_NL / IQ4_XS matrices stay quantized in HBM (tile layouts of 144 / 136 B per row and 256 elements)
 WEIGHTS_HALF_TILES = 4      # ... F16 / BF16 matrices stay 16-bit in HBM (8192-B tiles, their own decode mat-vec); bit 1 is not assigned
 PREFILL_BATCH_BYTE_KV = 1   # lgh_set_prefill_policy: int8 / FP8 caches take the batched prompt pass (own sequence, slots, stage contexts)
 PREFILL_BATCH_TQ_QJL = 4    # ... tq2-qjl / tq3-qjl caches take it (own sequence, as tq2 / tq3); bit 1 is not assigned
@@ -448,7 +449,7 @@ class HipGpuInference:
 
     def set_weight_policy(self, policy: int) -> None:
         """lgh_set_weight_policy: WEIGHTS_LOWBIT_TILES keeps Q3_K / Q2_K matrices quantized in HBM, WEIGHTS_HALF_TILES F16 / BF16 ones 16-bit,
-        WEIGHTS_LEGACY_TILES Q4_1 / Q5_0 / Q5_1 ones quantized; before the first upload_tensor only."""
+        WEIGHTS_LEGACY_TILES Q4_1 / Q5_0 / Q5_1 ones quantized, WEIGHTS_IQ4_TILES IQ4_NL / IQ4_XS ones; before the first upload_tensor only."""
         self._call(load_library().lgh_set_weight_policy(self._h, policy))
 
     def reset(self) -> None:
@@ -1126,7 +1127,8 @@ def op_vec_mat_ex(ggml_type: int, w: np.ndarray, x, n: int, weight_policy: int, 
 
 
 def op_mat_mat_ex(ggml_type: int, w: np.ndarray, x, n: int, weight_policy: int, device: int = 0) -> np.ndarray:
-    """op_mat_mat under lgh_set_weight_policy's word (WEIGHTS_LOWBIT_TILES: Q3_K / Q2_K as well; WEIGHTS_LEGACY_TILES: Q4_1 / Q5_0 / Q5_1)."""
+    """op_mat_mat under lgh_set_weight_policy's word (WEIGHTS_LOWBIT_TILES: Q3_K / Q2_K as well; WEIGHTS_LEGACY_TILES: Q4_1 / Q5_0 / Q5_1;
+    WEIGHTS_IQ4_TILES: IQ4_NL / IQ4_XS)."""
     w, x = np.ascontiguousarray(w), _f32(x)
     m, k = x.shape
     out = np.empty((m, n), dtype=np.float32)

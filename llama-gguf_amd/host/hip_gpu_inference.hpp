@@ -64,7 +64,8 @@ class HipGpuInference {
     if (!kv_rotation_signs.empty()) g.check(lgh_set_kv_rotation_signs(h, kv_rotation_signs.data(), kv_rotation_signs.size()));
     if (!kv_qjl_matrices.empty()) g.check(lgh_set_kv_qjl_matrices(h, kv_qjl_matrices.data(), kv_qjl_matrices.size()));
     // LGH_WEIGHTS_LOWBIT_TILES: Q3_K / Q2_K matrices stay quantized in HBM; LGH_WEIGHTS_HALF_TILES: F16 / BF16 ones stay 16-bit;
-    // LGH_WEIGHTS_LEGACY_TILES (8): Q4_1 / Q5_0 / Q5_1 ones stay quantized (before the first upload: one policy per context)
+    // LGH_WEIGHTS_LEGACY_TILES (8): Q4_1 / Q5_0 / Q5_1 ones stay quantized; LGH_WEIGHTS_IQ4_TILES (16): IQ4_NL / IQ4_XS ones (before the
+    // first upload: one policy per context)
     if (weight_policy) g.check(lgh_set_weight_policy(h, weight_policy));
     for (const HostTensor& t : tensors) g.check(lgh_upload_tensor(h, t.name.c_str(), t.ggml_type, t.ne, t.data, t.nbytes));
     g.check(lgh_finalize(h));

@@ -22,9 +22,10 @@ _SYNTH_LIB = os.path.join(_HERE, "lib", "libllama_gguf_synth.so")
 
 F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 = 0, 1, 2, 3, 6, 7, 8
 Q2_K, Q3_K, Q4_K, Q5_K, Q6_K = 10, 11, 12, 13, 14
+IQ4_NL, IQ4_XS = 20, 23
 BF16 = 30
 TYPE_IDS = {"F32": F32, "F16": F16, "Q4_0": Q4_0, "Q4_1": Q4_1, "Q5_0": Q5_0, "Q5_1": Q5_1, "Q8_0": Q8_0,
-            "Q2_K": Q2_K, "Q3_K": Q3_K, "Q4_K": Q4_K, "Q5_K": Q5_K, "Q6_K": Q6_K, "BF16": BF16}
+            "Q2_K": Q2_K, "Q3_K": Q3_K, "Q4_K": Q4_K, "Q5_K": Q5_K, "Q6_K": Q6_K, "IQ4_NL": IQ4_NL, "IQ4_XS": IQ4_XS, "BF16": BF16}
 
 _lib = None
 
